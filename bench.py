@@ -6,12 +6,18 @@ One "step" = one pass of the hot path over one resident synthetic batch:
 Workload (BASELINE.json configs[1]): ResNet-34 student, 5-channel 128x128 crops (RGB+flow),
 emb_dim 128, batch 256 per GPU, bf16 operands / fp32 accumulation, weak scaling over GPUs.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 One rank per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a rank; started
 from a bare shell with --gpus N > 1 it spawns the N ranks itself (before anything touches the GPU) and relays rank 0's
-line.  W warm-up steps, then `--repeats` timed regions of EXACTLY K steps each, every one bracketed by barrier +
+line.  W warm-up steps, then `--repeats` timed regions (default 1) of EXACTLY K steps each, every one bracketed by barrier +
 synchronize with the MAX over ranks; the reported value is the MEDIAN region, all of them are listed.
 Rank 0 prints ONE JSON line.
+
+A plain run does only that.  --dump-outputs DIR writes what the last timed step left to its caller (loss, updated
+parameters, BatchNorm running statistics) as DIR/<name>.npy.  --full adds everything else the benchmark measures or
+checks: embedding parity against the reference fixture (before the timed steps), five timed regions unless --repeats
+says otherwise, the per-kernel roofline from instrumented steps, the multi-GPU self-validation, the inference twin and
+the CPU baseline.
 """
 import argparse
 import json
@@ -346,29 +352,104 @@ def apply_block(enc, device, batches=30, warmup=4):
             "finite": bool(torch.isfinite(out).all())}
 
 
+DUMP_PARAM_SAMPLE = 1 << 23          # parameters written by --dump-outputs: all of them up to 8 M (32 MB), else this many
+
+
+def dump_outputs(out_dir, eng):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy files -- `loss` (the step's
+    sum-MSE, what loss.item() returns), `params` (the flat fp32 parameters AdamW left, state_dict order; a fixed seeded
+    sample of DUMP_PARAM_SAMPLE of them, in index order, when there are more) and `bn_running` (BatchNorm running means and
+    variances after the step's train-mode forward)."""
+    os.makedirs(out_dir, exist_ok=True)
+    params = eng.params
+    if params.numel() > DUMP_PARAM_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(params.numel(), DUMP_PARAM_SAMPLE, replace=False))
+        params = params[torch.from_numpy(idx).to(params.device)]
+    for name, t in (("loss", eng.loss_step), ("params", params), ("bn_running", eng.bn_running[:eng.bn_numel])):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
+def roofline_block(cls, profile_steps, value, world, flop, local_rank):
+    """--full: the dominant matrix-kernel class of the instrumented steps against the bf16 MFMA peak, with the committed
+    HBM traffic figure of that class."""
+    kernels = {}
+    for k, v in cls.items():
+        if v["launches"] > 0:
+            kernels[k] = {"launches_per_step": v["launches"] / profile_steps,
+                          "ms_per_step": v["ms"] / profile_steps,
+                          "avg_launch_us": 1e3 * v["ms"] / v["launches"],
+                          "tflops": v["flops"] / (v["ms"] * 1e-3) / 1e12}
+    if not kernels:      # --profile-steps 0 (used under rocprofv3): no event timing, no roofline object
+        kernels = {"(not timed)": {"ms_per_step": 0.0, "tflops": 0.0}}
+    dom = max(kernels, key=lambda k: kernels[k]["ms_per_step"])
+    mat_ms = sum(v["ms"] for v in cls.values()) / max(profile_steps, 1)
+    mat_flops = sum(v["flops"] for v in cls.values()) / max(profile_steps, 1)
+    traffic, traffic_note, traffic_source = None, None, None
+    try:      # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE x2 per the gfx950 note)
+        pmc = json.load(open(os.path.join(REPO, "profiles", "pmc_traffic.json")))
+        # rows of the dominant class only: its kernel name AND one of its tile shapes ("<256,64,416>" -> "<256, 64, 416,")
+        import re
+        base = dom.split("<")[0].split(" ")[0]
+        tiles = [", ".join(t.split(",")) for t in re.findall(r"<([0-9,]+)>", dom)]
+        rows = [v for k, v in pmc["kernels"].items()
+                if base in k and (not tiles or any(("<" + t + ",") in k or ("<" + t + ">") in k for t in tiles))]
+        n = sum(r["launches"] for r in rows)
+        traffic = sum(r["launches"] * (2 * r["fetch_KB_per_launch"] + r["write_KB_per_launch"]) for r in rows) / n * 1024
+        traffic_note = pmc["note"]
+        from vpd_amd.boxid import gpu_unique_id
+        traffic_source = dict(pmc.get("source") or {}, file="profiles/pmc_traffic.json")
+        # hosts may share one hostname: the GPU is named by its unique_id (KFD topology)
+        here = gpu_unique_id(local_rank)
+        traffic_source["this_run_gpu_unique_id"] = here
+        traffic_source["same_gpu_as_this_run"] = here != "unknown" and traffic_source.get("gpu_unique_id") == here
+    except Exception:
+        pass
+    return {"bound": "mfma", "kernel": dom, "achieved": kernels[dom]["tflops"],
+            "peak": MFMA_BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": kernels[dom]["tflops"] / MFMA_BF16_DENSE_PEAK_TFLOPS, "traffic": traffic,
+            "traffic_note": traffic_note, "traffic_source": traffic_source,
+            "whole_step_frac": value / world * flop / (MFMA_BF16_DENSE_PEAK_TFLOPS * 1e12),
+            # FLOP-weighted over ALL matrix-kernel classes (= their FLOPs / their summed time); `frac` above
+            # is the single class that takes the most time
+            "matrix_kernels_frac": (mat_flops / (mat_ms * 1e-3) / 1e12 / MFMA_BF16_DENSE_PEAK_TFLOPS) if mat_ms > 0 else None,
+            "matrix_kernels_ms_per_step": mat_ms,
+            "kernels": kernels,
+            "note": "per-class HIP-event timing from %d instrumented steps run right after the timed region: the "
+                    "start/stop events ride in each kernel's own dispatch packet (hipExtLaunchKernelGGL), so the "
+                    "figure is the kernel's duration as rocprofv3 --kernel-trace reports it; a grouped weight-gradient "
+                    "launch (all 3x3 stride-1 convs of one ResNet stage) is timed without its slab reduce" % profile_steps}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps; the median is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also parity, roofline, multi-GPU self-validation, inference twin and CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, parameters and BatchNorm running statistics to DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=None, help="crops per GPU per step (default: the config's)")
     ap.add_argument("--config", default="c2", choices=sorted(BENCH_CONFIGS),
                     help="BASELINE.json workload: c2 = configs[1] (default, the metric's config), c3 = configs[2] (6-channel input, "
                          "motion head, 256 crops per GPU), c4 = configs[3] (fs normalisation, motion head, 512 crops per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-apply", action="store_true", help="skip the inference-twin block")
-    ap.add_argument("--no-parity", action="store_true", help="skip the embedding-parity block (emb L2 vs the reference fixture)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-apply", action="store_true", help="--full without the inference-twin block")
+    ap.add_argument("--no-parity", action="store_true", help="--full without the embedding-parity block (emb L2 vs the reference fixture)")
     ap.add_argument("--arch", default=ARCH, help="student architecture (default: the BASELINE config, resnet34)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"],
                     help="element type of the HIP path: bf16 (BASELINE configs[1], default) or fp16 + static loss scale (the reference's own "
                          "GPU precision: fp16 autocast + GradScaler)")
-    ap.add_argument("--profile-steps", type=int, default=3, help="event-instrumented steps after the timed region")
+    ap.add_argument("--profile-steps", type=int, default=3, help="event-instrumented steps after the timed region (--full)")
     args = ap.parse_args()
 
     cfg = BENCH_CONFIGS[args.config]
     if args.batch is None:
         args.batch = cfg["batch"]
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     c_in, motion = cfg["c_in"], cfg["motion"]
     if args.gpus > 1 and "RANK" not in os.environ:
         return spawn_ranks(args.gpus, sys.argv[1:])
@@ -398,7 +479,7 @@ def main():
     from vpd_amd.data import RGB_MEAN_STD
     # "emb L2 vs ref": before anything is timed, on a model of its own (rank 0; every rank computes the same thing)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         parity = parity_block(device)
         if not parity["ok"]:
             raise SystemExit("bench.py: embeddings differ from the reference fixture: %s" % json.dumps(parity))
@@ -452,24 +533,27 @@ def main():
         region_s.append(dt)
     dt = sorted(region_s)[len(region_s) // 2]            # median timed region of exactly --steps steps
     loss_now = float(eng.loss_step.item())
+    if rank == 0 and args.dump_outputs:                  # before any further step changes the weights
+        dump_outputs(args.dump_outputs, eng)
 
     # ---- instrumented steps for the roofline: EVERY rank runs them (they contain the gradient all-reduce; a rank that
     # ran them alone would wait for its peers forever), rank 0 arms the per-kernel dispatch events and reads them ----
-    pl = eng.plan(HW, HW, args.batch, True, motion)
-    if rank == 0:
-        eng.set_timing(pl, True)
-    for _ in range(args.profile_steps):
-        one_step()
-    sync()
     cls = {}
-    if rank == 0:
-        cls = eng.read_timing(pl) if args.profile_steps > 0 else {}
-        eng.set_timing(pl, False)
+    if args.full:
+        pl = eng.plan(HW, HW, args.batch, True, motion)
+        if rank == 0:
+            eng.set_timing(pl, True)
+        for _ in range(args.profile_steps):
+            one_step()
+        sync()
+        if rank == 0:
+            cls = eng.read_timing(pl) if args.profile_steps > 0 else {}
+            eng.set_timing(pl, False)
 
     # multi-GPU self-validation (every rank takes part): the same K steps with the all-reduces NOT overlapped with backward
     # (VPD_DDP_OVERLAP=0: reduced in line after it), and the communicator's own numbers
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         os.environ["VPD_DDP_OVERLAP"] = "0"
         for _ in range(3):
             one_step()
@@ -507,52 +591,7 @@ def main():
         assert (args.arch, c_in) not in TRAIN_FLOP_PER_CROP or flop == TRAIN_FLOP_PER_CROP[(args.arch, c_in)]
         if motion:      # FCNet(D, [128, 128], 2D) (models/module.py:133-156): forward + both gradients of three linear layers
             flop += 2 * 3 * (EMB_DIM * 128 + 128 * 128 + 128 * 2 * EMB_DIM)
-        kernels = {}
-        for k, v in cls.items():
-            if v["launches"] > 0:
-                kernels[k] = {"launches_per_step": v["launches"] / args.profile_steps,
-                              "ms_per_step": v["ms"] / args.profile_steps,
-                              "avg_launch_us": 1e3 * v["ms"] / v["launches"],
-                              "tflops": v["flops"] / (v["ms"] * 1e-3) / 1e12}
-        if not kernels:      # --profile-steps 0 (used under rocprofv3): no event timing, no roofline object
-            kernels = {"(not timed)": {"ms_per_step": 0.0, "tflops": 0.0}}
-        dom = max(kernels, key=lambda k: kernels[k]["ms_per_step"])
-        mat_ms = sum(v["ms"] for v in cls.values()) / max(args.profile_steps, 1)
-        mat_flops = sum(v["flops"] for v in cls.values()) / max(args.profile_steps, 1)
-        traffic, traffic_note, traffic_source = None, None, None
-        try:      # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE x2 per the gfx950 note)
-            pmc = json.load(open(os.path.join(REPO, "profiles", "pmc_traffic.json")))
-            # rows of the dominant class only: its kernel name AND one of its tile shapes ("<256,64,416>" -> "<256, 64, 416,")
-            import re
-            base = dom.split("<")[0].split(" ")[0]
-            tiles = [", ".join(t.split(",")) for t in re.findall(r"<([0-9,]+)>", dom)]
-            rows = [v for k, v in pmc["kernels"].items()
-                    if base in k and (not tiles or any(("<" + t + ",") in k or ("<" + t + ">") in k for t in tiles))]
-            n = sum(r["launches"] for r in rows)
-            traffic = sum(r["launches"] * (2 * r["fetch_KB_per_launch"] + r["write_KB_per_launch"]) for r in rows) / n * 1024
-            traffic_note = pmc["note"]
-            from vpd_amd.boxid import gpu_unique_id
-            traffic_source = dict(pmc.get("source") or {}, file="profiles/pmc_traffic.json")
-            # the pool's containers share one hostname: the box is named by the GPU's unique_id (KFD topology)
-            here = gpu_unique_id(local_rank)
-            traffic_source["this_run_gpu_unique_id"] = here
-            traffic_source["same_gpu_as_this_run"] = here != "unknown" and traffic_source.get("gpu_unique_id") == here
-        except Exception:
-            pass
-        roofline = {"bound": "mfma", "kernel": dom, "achieved": kernels[dom]["tflops"],
-                    "peak": MFMA_BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": kernels[dom]["tflops"] / MFMA_BF16_DENSE_PEAK_TFLOPS, "traffic": traffic,
-                    "traffic_note": traffic_note, "traffic_source": traffic_source,
-                    "whole_step_frac": value / world * flop / (MFMA_BF16_DENSE_PEAK_TFLOPS * 1e12),
-                    # FLOP-weighted over ALL matrix-kernel classes (= their FLOPs / their summed time); `frac` above
-                    # is the single class that takes the most time
-                    "matrix_kernels_frac": (mat_flops / (mat_ms * 1e-3) / 1e12 / MFMA_BF16_DENSE_PEAK_TFLOPS) if mat_ms > 0 else None,
-                    "matrix_kernels_ms_per_step": mat_ms,
-                    "kernels": kernels,
-                    "note": "per-class HIP-event timing from %d instrumented steps run right after the timed region: the "
-                            "start/stop events ride in each kernel's own dispatch packet (hipExtLaunchKernelGGL), so the "
-                            "figure is the kernel's duration as rocprofv3 --kernel-trace reports it; a grouped weight-gradient "
-                            "launch (all 3x3 stride-1 convs of one ResNet stage) is timed without its slab reduce" % args.profile_steps}
+        roofline = roofline_block(cls, args.profile_steps, value, world, flop, local_rank) if args.full else None
         out = {"metric": "frame-crops/sec (VPD student train)", "value": value, "unit": "crops/s", "n_gpus": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
                "repeats": {"n": len(region_s), "pick": "median", "crops_per_s": [args.batch * world * args.steps / t for t in region_s]},
@@ -560,15 +599,16 @@ def main():
                "gpu_unique_id": __import__("vpd_amd.boxid", fromlist=["gpu_unique_id"]).gpu_unique_id(local_rank),
                "config": {"workload": cfg["what"] % ("ResNet-34" if args.arch == ARCH else args.arch) + ", batch=%d per GPU" % args.batch,
                           "global_batch": args.batch * world, "parallelism": "dp%d" % world,
-                          "flop_per_crop": flop, "loss_last_step": loss_now},
-               "roofline": roofline}
+                          "flop_per_crop": flop, "loss_last_step": loss_now}}
+        if roofline is not None:
+            out["roofline"] = roofline
         if parity is not None:
             out["parity"] = parity
         if multi is not None:
             out["multi_gpu"] = multi
-        if world == 1 and not args.no_apply and args.arch == ARCH and args.config == "c2":
+        if args.full and world == 1 and not args.no_apply and args.arch == ARCH and args.config == "c2":
             out["apply"] = apply_block(enc, device)
-        if world == 1 and not args.no_cpu_baseline and args.arch == ARCH and args.config == "c2":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.arch == ARCH and args.config == "c2":
             out["cpu_baseline"], apply_cpu = cpu_baseline()
             if "apply" in out:
                 out["apply"]["cpu_baseline"] = apply_cpu

@@ -309,7 +309,7 @@ def test_bench_self_launches_two_ranks_from_a_bare_shell():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["VPD_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
                         "--repeats", "2", "--batch", "16", "--profile-steps", "1", "--no-cpu-baseline", "--no-apply"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -415,7 +415,7 @@ _C4_EPOCH = {}
 
 
 def test_bench_c4_four_ranks_reports_its_multi_gpu_block():
-    """`bench.py --config c4 --gpus 4` (gloo, shared GPU, 32 crops per rank): one JSON line whose multi_gpu block is well formed --
+    """`bench.py --config c4 --gpus 4 --full` (gloo, shared GPU, 32 crops per rank): one JSON line whose multi_gpu block is well formed --
     backend, world size, per-bucket all-reduce timings, overlap on / off, the early-bucket-0 flag and `replicas_identical`."""
     import json
     import subprocess
@@ -425,7 +425,7 @@ def test_bench_c4_four_ranks_reports_its_multi_gpu_block():
     env["VPD_DIST_BACKEND"] = "gloo"
     env["VPD_DDP_EARLY_BUCKET0"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--config", "c4", "--steps", "2", "--warmup", "1",
-                        "--repeats", "1", "--batch", "32", "--profile-steps", "0", "--no-cpu-baseline", "--no-apply"],
+                        "--full", "--repeats", "1", "--batch", "32", "--profile-steps", "0", "--no-cpu-baseline", "--no-apply"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -18,8 +18,8 @@ python3 $R/tools/pmc_traffic.py $OUT/${TAG}_pmc_fetch $OUT/${TAG}_pmc_write $OUT
 cp $OUT/${TAG}_pmc_traffic.json $R/profiles/pmc_traffic.json
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES -d $OUT/${TAG}_pmc_mfma -o pmc --output-format csv -- python3 $R/bench.py $PARGS > /dev/null 2>&1
 python3 $R/tools/pmc_mfma_util.py $OUT/${TAG}_pmc_mfma $OUT/${TAG}_mfma_util.json > $OUT/${TAG}_mfma_util.txt
-# 2. the default bench line (with cpu_baseline and the apply block) and the kernel trace of the same command
-python3 $R/bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+# 2. the full bench line (roofline, parity, cpu_baseline and the apply block) and the kernel trace of the same workload
+python3 $R/bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o p -- python3 $R/bench.py $ARGS > $OUT/${TAG}_bench_under_rocprof.json 2> /dev/null
 cp $OUT/${TAG}_prof/p_kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
 python3 $R/tools/launch_gaps.py $OUT/${TAG}_prof/p_kernel_trace.csv > $OUT/${TAG}_launch_gaps.txt 2>&1
