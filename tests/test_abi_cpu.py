@@ -123,3 +123,15 @@ def test_product_does_not_import_oracle():
                           "print(any(m.startswith('oracle') for m in sys.modules))"],
                          cwd=REPO, capture_output=True, text=True)
     assert out.stdout.strip() == "False", out.stdout + out.stderr
+
+
+def test_library_shares_torchs_hip_runtime():
+    """Loading the library before anything imports torch must still leave ONE HIP runtime in the process: a second copy (the
+    system ROCm's next to torch's) sees no device, and the library's first GPU call fails."""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, "-c",
+                          "from vpd_amd import _lib; _lib.lib(); import torch;"
+                          "print(len({l.split()[-1] for l in open('/proc/self/maps') if 'libamdhip64' in l}))"],
+                         cwd=REPO, capture_output=True, text=True)
+    assert out.stdout.strip() == "1", out.stdout + out.stderr

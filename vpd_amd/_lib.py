@@ -94,6 +94,10 @@ def lib(dtype="bf16"):
         raise VpdHipError(
             "%s not found at %s: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C vpd_amd/csrc`.  vpd_amd has no PyTorch/CPU fallback." % (name, path))
+    # torch first: its libamdhip64 becomes the process's HIP runtime and the library binds to it by soname.  Loaded before torch,
+    # the library would pull in the system ROCm's runtime and torch would still map its own (its libraries ask for the unversioned
+    # name): two runtimes in one process, and the library's sees no device
+    import torch  # noqa: F401
     h = C.CDLL(path)
     # VPD_LIB_PATH (same-box A/B against an OLDER build of the library, tools/build_head_lib.sh): the operator-level test entry
     # points that build does not have yet are skipped; the in-tree library must export every declared symbol

@@ -281,9 +281,8 @@ __global__ __launch_bounds__(256) void stem_pool_pair_kernel(const StemPoolParam
     }
 }
 hipError_t vpd_launch_stem_pool(const StemPoolParams& p, hipStream_t s) {
-    static const bool pair = !(getenv("VPD_STEM_PAIR") && !atoi(getenv("VPD_STEM_PAIR")));
     const int cv = p.C / 8;
-    if (pair && !(p.Wo & 1) && 256 % cv == 0) {
+    if (vpd_switches().stem_pair && !(p.Wo & 1) && 256 % cv == 0) {
         // the grid-stride loop must keep a thread's channel slice fixed: total stride a multiple of cv (256 is)
         hipLaunchKernelGGL(stem_pool_pair_kernel, dim3(ew_grid((long)p.N * p.Ho * (p.Wo / 2) * cv)), dim3(256), 0, s, p);
         return hipGetLastError();
@@ -703,8 +702,7 @@ hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p0, float count, co
     if (p.C % 8 || 256 % (p.C / 8)) return hipErrorInvalidValue;
     const int T = vpd_bn_bwd_blocks(p.M, p.C, &p.ppb);
     p.pass = 1; p.coef = coef; p.dz = dz;
-    static const bool pooled_sums = !(getenv("VPD_STEM_POOLSUMS") && !atoi(getenv("VPD_STEM_POOLSUMS")));
-    if (pooled_sums && p.pooled) {
+    if (vpd_switches().stem_poolsums && p.pooled) {
         StemPoolBwdParams q = p;
         const int Mo = p.M / (p.Hz * p.Wz) * p.Ho * p.Wo;
         const int To = vpd_bn_bwd_blocks(Mo, p.C, &q.ppb);
@@ -716,8 +714,7 @@ hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p0, float count, co
                        VPD_STAT_ROWS, p.C, count,
                        gamma, p.rstd, dgamma, dbeta, coef);
     p.pass = 2;
-    static const bool quad = !(getenv("VPD_STEM_QUAD") && !atoi(getenv("VPD_STEM_QUAD")));
-    if (quad && !(p.Hz & 1) && !(p.Wz & 1) && p.Ho == p.Hz / 2 && p.Wo == p.Wz / 2) {
+    if (vpd_switches().stem_quad && !(p.Hz & 1) && !(p.Wz & 1) && p.Ho == p.Hz / 2 && p.Wo == p.Wz / 2) {
         const int per = 256 / (p.C / 8);
         const long items = (long)(p.M / (p.Hz * p.Wz)) * (p.Hz / 2) * (p.Wz / 2);
         long blocks = (items + per - 1) / per;
@@ -747,8 +744,7 @@ hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p0, float count, co
 #include "sync.h"
 
 static int vpd_bn_xcd_on() {      // VPD_BN_XCD=0: plain grid-stride order (same-box A/B; bit-identical either way)
-    static const int on = getenv("VPD_BN_XCD") ? atoi(getenv("VPD_BN_XCD")) : 1;
-    return on;
+    return vpd_switches().bn_xcd;
 }
 
 // XCD-affine block order of the fused BatchNorm launches (round 5).  conv3x3_pws_kernel runs pixel tile t (BM pixels) on XCD t % 8
@@ -938,7 +934,7 @@ hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f0,
     const int xcd_on = vpd_bn_xcd_on();
     f.xcd_r = xcd_on ? vpd_bn_xcd_r(p.xcd_tile_px, p.C, (int)g) : 0;
 #ifdef VPD_ENABLE_ABLATE      // tools/bench_bn_chain.py: the operator-level entry point knows no neighbouring convolution
-    if (const char* e = getenv("VPD_BN_XCD_FORCE")) f.xcd_r = vpd_bn_xcd_r(atoi(e), p.C, (int)g);
+    if (vpd_switches().bn_xcd_force >= 0) f.xcd_r = vpd_bn_xcd_r(vpd_switches().bn_xcd_force, p.C, (int)g);
 #endif
     hipLaunchKernelGGL(bn_fwd_fused_kernel, dim3((unsigned)g), dim3(1024), (size_t)4 * p.C * sizeof(float), s, p, f);
     return hipGetLastError();
@@ -1381,9 +1377,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_fused2_kernel(const BnBwdParams p
 }
 
 bool vpd_bn_bwd_fused2_ok(int M, int C) {
-    static const int off = getenv("VPD_FUSED_BN") ? !atoi(getenv("VPD_FUSED_BN")) : 0;
-    static const int off2 = getenv("VPD_BN_PAIR") ? !atoi(getenv("VPD_BN_PAIR")) : 0;
-    return !(off || off2 || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) && M >= 1;
+    return !(!vpd_switches().fused_bn || !vpd_switches().bn_pair || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) && M >= 1;
 }
 
 // p: BatchNorm A as for vpd_launch_bn_bwd_fused (dy, act, z, mean, rstd, dz + geometry); fA / fB: rows, gamma, dgamma, dbeta
@@ -1419,8 +1413,7 @@ hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p0, const BnFusedBwd& fA,
 
 // false: this shape has to take the three-launch path (vpd_launch_bn_bwd)
 bool vpd_bn_bwd_fused_ok(int M, int C, bool mask_act, bool write_g) {
-    static const int off = getenv("VPD_FUSED_BN") ? !atoi(getenv("VPD_FUSED_BN")) : 0;
-    if (off || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) return false;
+    if (!vpd_switches().fused_bn || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) return false;
     if (mask_act && !write_g) return false;             // (no caller: the masked g could not be recovered in phase 2)
     return M >= 1;
 }

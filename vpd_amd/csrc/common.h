@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include "switches.h"
 
 // Element type of activations / packed weights / activation gradients.  The library is built twice from these sources
 // (vpd_amd/csrc/Makefile): libvpdhip.so with bf16 elements (training and inference), libvpdhip_f16.so with -DVPD_ELEM_F16 = IEEE fp16
@@ -33,16 +34,13 @@ typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 // CU budget of the persistent grids (round 6): the device's CU count minus VPD_RESERVE_CUS (default 0) -- every kernel that sizes its
 // grid by "one block per CU" (conv3x3_pws / c64 / stem / streaming 1x1 kernels, the persistent weight-gradient launch, the grid-barrier
 // BatchNorm launches) asks here, so that R CUs stay free of LDS-heavy blocks for whatever co-runs with the step (RCCL's kernels under
-// data parallelism).  vpd_cu_budget_override(): a launch sequence's own budget (the weight-gradient side stream).
-inline int& vpd_cu_budget_override() { static thread_local int v = 0; return v; }
+// data parallelism).
 inline int vpd_cu_budget() {
-    if (vpd_cu_budget_override() > 0) return vpd_cu_budget_override();
     static const int n = [] {
         int dev = 0, cu = 0;
         (void)hipGetDevice(&dev);
         if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu < 1) cu = 256;
-        const char* r = getenv("VPD_RESERVE_CUS");
-        int res = r ? atoi(r) : 0;
+        int res = vpd_switches().reserve_cus;
         if (res < 0) res = 0;
         res = (res + 7) & ~7;                       // whole octets: one CU of every XCD per 8
         if (cu - res < 8) res = cu > 8 ? cu - 8 : 0;

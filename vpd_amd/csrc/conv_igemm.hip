@@ -856,7 +856,7 @@ __global__ __launch_bounds__(768) void conv3x3_c64x2_persistent_kernel(const Con
 
 // 256-pixel tiles of whole image rows whose halo fits C64X2_HPIX pixels; eval epilogue only (see the kernel's comment)
 static bool c64x2_geom(const ConvParams& p, HaloGeom* g) {
-    static const int off = getenv("VPD_C64X2") ? !atoi(getenv("VPD_C64X2")) : 0;
+    const int off = !vpd_switches().c64x2;
     const int W = p.Ws, H = p.Hs;
     if (off || conv_ep_mode(p) != 3 || W <= 0 || 256 % W != 0) return false;      // inference only (in training it measured slower)
     const int TR = 256 / W;
@@ -872,8 +872,7 @@ static hipError_t launch_c64x2(const ConvParams& p, const HaloGeom& g, hipStream
     const int ntiles = (p.M + 255) / 256;
     const int ncu = vpd_cu_budget();
     int grid = ntiles < ncu ? ntiles : ncu;
-    static const int contig = getenv("VPD_C64_CONTIG") ? atoi(getenv("VPD_C64_CONTIG")) : 1;
-    const int per = contig ? (ntiles + grid - 1) / grid : 0;
+    const int per = vpd_switches().c64_contig ? (ntiles + grid - 1) / grid : 0;
     if (per > 0) grid = (ntiles + per - 1) / per;
     const size_t lds = ((size_t)9 * 64 + 2 * C64X2_HPIX) * 64 * sizeof(bf16_t);
     ConvParams q = p;
@@ -892,8 +891,7 @@ static hipError_t launch_c64(const ConvParams& p, const HaloGeom& g, hipStream_t
     const int ncu = vpd_cu_budget();
     int grid = ntiles < ncu ? ntiles : ncu;
     // consecutive tiles per block (VPD_C64_CONTIG=0: strided); the grid shrinks to the blocks that get tiles
-    static const int contig = getenv("VPD_C64_CONTIG") ? atoi(getenv("VPD_C64_CONTIG")) : 1;
-    const int per = contig ? (ntiles + grid - 1) / grid : 0;
+    const int per = vpd_switches().c64_contig ? (ntiles + grid - 1) / grid : 0;
     if (per > 0) grid = (ntiles + per - 1) / per;
     const size_t lds = ((size_t)9 * 64 + 2 * HROWS) * 64 * sizeof(bf16_t) + 2048;
     ConvParams q = p;
@@ -1212,8 +1210,7 @@ static hipError_t launch_stem(const ConvParams& p, int TR, hipStream_t stream) {
     const long xelems = (long)p.N * p.xHp * p.xWp * 8 + 64;      // the plan allocates 256 elements of slack behind xin
     ConvParams q = p;
     // dense 64-channel output (the stem's only use): stores through LDS, 1 KiB contiguous per instruction (VPD_STEM_LDS_STORE=0: direct)
-    static const int lds_store_on = getenv("VPD_STEM_LDS_STORE") ? atoi(getenv("VPD_STEM_LDS_STORE")) : 1;
-    const int lds_store = lds_store_on && p.ypad == 0 && p.yC == 64 && p.osub == 1 && p.yWp == p.Ws && p.yHp == p.Hs;
+    const int lds_store = vpd_switches().stem_lds_store && p.ypad == 0 && p.yC == 64 && p.osub == 1 && p.yWp == p.Ws && p.yHp == p.Hs;
     if (p.pool_y) VPD_LAUNCH((conv_stem_persistent_kernel<160, 9>), dim3(grid), dim3(512), lds, stream, q, TR, ntiles, xelems, 0);
     else if (p.stats) VPD_LAUNCH((conv_stem_persistent_kernel<160, 1>), dim3(grid), dim3(512), lds, stream, q, TR, ntiles, xelems, lds_store);
     else VPD_LAUNCH((conv_stem_persistent_kernel<160, 0>), dim3(grid), dim3(512), lds, stream, q, TR, ntiles, xelems, lds_store);
@@ -1227,14 +1224,13 @@ static hipError_t launch_stem(const ConvParams& p, int TR, hipStream_t stream) {
 // (ring depths PWS_NS_C*: conv_pws.h)
 int pws_cu_count() {
     // VPD_PWS_BLOCKS: pretend the device has this many CUs (tests: many tiles per block on small problems)
-    static const int forced = getenv("VPD_PWS_BLOCKS") && atoi(getenv("VPD_PWS_BLOCKS")) > 0 ? atoi(getenv("VPD_PWS_BLOCKS")) : 0;
-    return forced ? forced : vpd_cu_budget();
+    const int forced = vpd_switches().pws_blocks;
+    return forced > 0 ? forced : vpd_cu_budget();
 }
 static bool pws_enabled(const ConvParams& p) {
-    static const int on = getenv("VPD_PWS") ? atoi(getenv("VPD_PWS")) : 1;
     const int mode = conv_ep_mode(p);
     // (global output rows below 2^21: the kernel's float-reciprocal divisions, vpd_fdiv)
-    return on && mode != 4 && mode != 5 && (long)p.N * p.Hs < VPD_FDIV_MAX;
+    return vpd_switches().pws && mode != 4 && mode != 5 && (long)p.N * p.Hs < VPD_FDIV_MAX;
 }
 template <int BM, int BN, int HROWS, int NS, int NMW, bool PIPE>
 static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
@@ -1290,10 +1286,7 @@ static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t
     } };
 #endif
     bool geo_launched = false;
-    {
-        static const int geo_on = getenv("VPD_PWS_GEO") ? atoi(getenv("VPD_PWS_GEO")) : 1;
-        geo_launched = geo_on && vpd_launch_pws_geo(BM, BN, HROWS, NS, NMW, q, g, sg, grid, block, lds, stream);
-    }
+    geo_launched = vpd_switches().pws_geo && vpd_launch_pws_geo(BM, BN, HROWS, NS, NMW, q, g, sg, grid, block, lds, stream);
     if (!geo_launched) switch (conv_ep_mode(q)) {
         case 0: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 0, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
         case 1: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 1, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
@@ -1320,8 +1313,7 @@ static hipError_t launch_ws_ns(const ConvParams& p, const HaloGeom& g, hipStream
     // (the 256 x 64 tile with eight MFMA waves -- 32 x 64 wave tiles, six fragment reads per eight MFMAs -- is LDS-read-bound:
     //  class 525 -> 590 us)
     if constexpr (BM == 256 && BN == 128 && NS == 4) {
-        static const int mw8 = getenv("VPD_WS_MW8") ? atoi(getenv("VPD_WS_MW8")) : 1;
-        if (mw8) {
+        if (vpd_switches().ws_mw8) {
             switch (conv_ep_mode(q)) {
                 case 0: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 0, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
                 case 1: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 1, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
@@ -1516,7 +1508,7 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p0) {
 
 // 1x1, stride 1, one tap, one class, no second convolution / input, plain epilogue modes, K deep enough for the ring to matter
 static bool conv1x1_ws_eligible(const ConvParams& p) {
-    static const int on = getenv("VPD_CONV1X1_WS") ? atoi(getenv("VPD_CONV1X1_WS")) : 1;
+    const int on = vpd_switches().conv1x1_ws;
     // K >= 512 (8+ steps), or 4+ steps when the launch is at most a few rounds of blocks: layer1's 256 -> 64 convs (2,048
     // blocks of four steps) stream their 168 MB faster through the gather kernel's two small blocks per CU
     const int kmin = 256, mmax = 32768;
@@ -1525,7 +1517,7 @@ static bool conv1x1_ws_eligible(const ConvParams& p) {
     if (!common) return false;
     // the merged parity classes of a stride-2 3x3 data gradient (+ the 1x1 branch's as extra K-steps of class 0) at the layer3
     // and layer4 boundaries (layer2's has 2,048 blocks of 2-8 K-steps: gather kernel)
-    static const int dgon = getenv("VPD_CONV_S2_DGRAD_WS") ? atoi(getenv("VPD_CONV_S2_DGRAD_WS")) : 1;
+    const int dgon = vpd_switches().conv_s2_dgrad_ws;
     const int dgk = 256;      // (layer2's boundary, K = 128, on the ring GEMM: measured slower, DESIGN_HISTORY.md round 4)
     if (p.ncls > 1 || p.x2 || p.osub != 1)
         return dgon && p.ncls == 4 && p.osub == 2 && p.istr == 1 && !p.alt_w && !p.accumulate && !p.ep_scale && p.Kc >= dgk &&
@@ -1536,7 +1528,7 @@ static bool conv1x1_ws_eligible(const ConvParams& p) {
         return false;
     // the stride-2 convs at the ResNet stage boundaries (3x3 forward, with the BasicBlock's 1x1 branch as second convolution):
     // 9-36 K-steps, one round of blocks with the tile choice below
-    static const int s2on = getenv("VPD_CONV_S2_WS") ? atoi(getenv("VPD_CONV_S2_WS")) : 1;
+    const int s2on = vpd_switches().conv_s2_ws;
     if (p.istr == 2) return s2on && p.taps.nr == 3 && p.taps.nc == 3 && (!p.alt_w || (p.alt_taps.nr == 1 && p.alt_taps.nc == 1));
     if (p.Kc < 512 && !(p.Kc >= kmin && p.M <= mmax)) return false;
     return p.taps.nr == 1 && p.taps.nc == 1 && p.istr == 1 && !p.alt_w;
@@ -1596,10 +1588,9 @@ static bool halo_geom(const ConvParams& p, int BM, int hrows_max, HaloGeom* g) {
     if (W >= 8) { g->kmask = 7; g->kshift = 0; g->rowmask = 0; }
     else { g->kmask = 3; g->kshift = 2; g->rowmask = 1; }
     g->rH = 1.0f / (float)H; g->rW = 1.0f / (float)W; g->rWp = 1.0f / (float)(W + 2);
-    static const int rot = getenv("VPD_PWS_ROT") ? atoi(getenv("VPD_PWS_ROT")) : 1;
     // (not in the inference epilogue: there a crop's embedding must not depend on where in the batch it sits -- a batch, its split, its
     //  ragged tail and its hipGraph launch agree bit for bit, tests/test_fullsize_gpu.py -- and the rotation is a function of the tile index)
-    g->rot = rot && p.Kc > 64 && conv_ep_mode(p) != 3;
+    g->rot = vpd_switches().pws_rot && p.Kc > 64 && conv_ep_mode(p) != 3;
     g->rnch = 1.0f / (float)(p.Kc / 64);
     return g->NHP <= hrows_max;
 }
@@ -1646,7 +1637,7 @@ extern "C" int vpd_conv_bm(int M, int Co) {
 //   3 conv3x3_ws_kernel<128,64,288>        4 conv_igemm_kernel (gather; also the legacy conv3x3_halo fallback)
 //   5 conv_stem_persistent_kernel<160>
 int vpd_conv_kernel_class(const ConvParams& p, HaloGeom* g) {
-    static const int no_ws = getenv("VPD_NO_WS") ? atoi(getenv("VPD_NO_WS")) : 0;
+    const int no_ws = vpd_switches().no_ws;
     int tr_stem;
     if (p.alt_w || p.x2) return 4;                             // two convolutions / two inputs in one launch: gather kernel only
     if (!no_ws && stem_eligible(p, &tr_stem)) return 5;        // conv_stem_persistent_kernel
@@ -1664,8 +1655,7 @@ int vpd_conv_kernel_class(const ConvParams& p, HaloGeom* g) {
             // 256 pixels x 64 channels: the FLOPs of a 128 x 128 tile for 30 % fewer staged bytes per K-step (8 KB of weights +
             // 1/9 of a 52 KB halo instead of 16 KB + 1/9 of 36 KB) where 256-pixel tiles alone would leave half the chip idle
             // (layer3 at 256 crops: 64 pixel tiles x 4 channel tiles)
-            static const int w64 = getenv("VPD_WS_256x64") ? atoi(getenv("VPD_WS_256x64")) : 1;
-            if (w64 && t128 >= 200 && (long)((p.M + 255) / 256) * (p.Co / 64) >= 200 && halo_geom(p, 256, 416, g)) return 6;
+            if (vpd_switches().ws_256x64 && t128 >= 200 && (long)((p.M + 255) / 256) * (p.Co / 64) >= 200 && halo_geom(p, 256, 416, g)) return 6;
             if (halo_geom(p, 128, 288, g)) return t128 >= 200 ? 2 : 3;    // few pixel tiles: 64-channel tiles fill the chip
         } else if (p.Kc == 64 && p.Co == 64) {
             // 64 -> 64 channels (layer1): persistent blocks with resident weights
@@ -1704,19 +1694,16 @@ bool vpd_conv_takes_bn_sums(const ConvParams& p) {
     const int kc = vpd_conv_kernel_class(p, &g);
     if (kc == 4) {      // gather kernel: the merged parity classes of a stride-2 data gradient (plain store only)
         if (p.bst_z2) return false;
-        static const int s2 = getenv("VPD_DGRAD_SUMS_S2") ? atoi(getenv("VPD_DGRAD_SUMS_S2")) : 1;
-        static const int g1 = getenv("VPD_DGRAD_SUMS_1X1") ? atoi(getenv("VPD_DGRAD_SUMS_1X1")) : 1;
         // ... or a dense stride-1 launch of it (the Bottleneck students' 1x1 convs), plain or accumulating
-        if (p.osub == 1 && p.ncls <= 1 && !p.x2) return g1 != 0;
-        return s2 && !p.accumulate && p.osub == 2;
+        if (p.osub == 1 && p.ncls <= 1 && !p.x2) return vpd_switches().dgrad_sums_1x1 != 0;
+        return vpd_switches().dgrad_sums_s2 && !p.accumulate && p.osub == 2;
     }
     if (p.x2 || p.osub != 1) return false;
     if (p.yWp != p.Ws || p.yHp != p.Hs) return false;      // (the 3x3 kernels index z / the bit map by dense pixel number)
     if (p.bst_z2) return p.accumulate && p.stats2 && (kc == 1 || kc == 2 || kc == 3 || kc == 6);      // mode 8: conv3x3_ws_kernel only
     if (kc == 0) {      // layer1's persistent kernel (not its two-group variant)
-        static const int l1 = getenv("VPD_DGRAD_SUMS_L1") ? atoi(getenv("VPD_DGRAD_SUMS_L1")) : 1;
         HaloGeom g2;
-        return l1 && !c64x2_geom(p, &g2);
+        return vpd_switches().dgrad_sums_l1 && !c64x2_geom(p, &g2);
     }
     return kc == 1 || kc == 2 || kc == 3 || kc == 6;
 }
@@ -1730,7 +1717,7 @@ hipError_t vpd_launch_conv(const ConvParams& p0, hipStream_t stream) {
     if (p0.bst_z2 && !p0.stats2) return hipErrorInvalidValue;
     ConvParams p = p0;
 #ifdef VPD_ENABLE_ABLATE
-    static const int ablate = getenv("VPD_ABLATE") ? atoi(getenv("VPD_ABLATE")) : 0;
+    const int ablate = vpd_switches().ablate;
 #else
     constexpr int ablate = 0;
 #endif

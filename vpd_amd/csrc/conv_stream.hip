@@ -700,8 +700,7 @@ hipError_t launch_stream(const ConvParams& p, hipStream_t stream) {
 
 // 1x1, one tap, one class, <= 256 input channels, whole-row pixel tiles, enough tiles for every CU to stream
 bool vpd_conv1x1_stream_eligible(const ConvParams& p) {
-    static const int on = getenv("VPD_CONV1X1_STREAM") ? atoi(getenv("VPD_CONV1X1_STREAM")) : 1;
-    if (!on) return false;
+    if (!vpd_switches().conv1x1_stream) return false;
     if (p.taps.nr != 1 || p.taps.nc != 1 || p.ncls > 1 || p.alt_w || p.x2 || p.bst_z || p.bst_z2 || p.pool_y) return false;
     if (p.osub != 1 || p.oph != 0 || p.opw != 0 || (p.istr != 1 && p.istr != 2)) return false;
     if (p.Kc != 64 && p.Kc != 128 && p.Kc != 256) return false;
@@ -738,8 +737,7 @@ hipError_t vpd_launch_conv1x1_stream(const ConvParams& p, hipStream_t stream) {
 
 // ---- the closing 1x1 convolution of a Bottleneck with its BatchNorm (conv1x1_bn_stream_kernel) ----
 bool vpd_conv1x1_bn_eligible(const ConvParams& p) {
-    static const int on = getenv("VPD_BNECK_RECOMPUTE") ? atoi(getenv("VPD_BNECK_RECOMPUTE")) : 1;
-    if (!on || !vpd_conv1x1_stream_eligible(p)) return false;
+    if (!vpd_switches().bneck_recompute || !vpd_conv1x1_stream_eligible(p)) return false;
     if (p.istr != 1 || (p.Kc != 64 && p.Kc != 128) || p.Co % 256 != 0 || p.accumulate || p.ep_scale) return false;
     return p.M % 64 == 0 && 64 % p.Ws == 0 && (p.Hs * p.Ws) % 64 == 0;
 }

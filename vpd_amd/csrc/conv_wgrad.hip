@@ -683,7 +683,7 @@ static bool wg_halo_geom(const WgradParams& p, WgHaloGeom* g) {
 
 // shape test of the halo kernel for a 3x3 stride-1 conv with Hout x Wout outputs (independent of the batch size)
 bool vpd_wgrad_halo_shape_ok(int H, int W, int stride, int Hin, int Win) {
-    static const int no_s2 = getenv("VPD_WGRAD_S2") ? !atoi(getenv("VPD_WGRAD_S2")) : 0;
+    const int no_s2 = !vpd_switches().wgrad_s2;
     if (W <= 0 || WG_CH % W != 0) return false;
     if (stride == 2 && (no_s2 || Hin != 2 * H || Win != 2 * W)) return false;
     if (stride != 1 && stride != 2) return false;
@@ -709,13 +709,13 @@ static bool wg_as_one_by_one(const WgradParams& p, WgradParams* q) {
 bool vpd_wgrad_overwrites(const WgradParams& p0) {
     int tr_stem;
     if (wg_stem_eligible(p0, &tr_stem)) return true;
-    static const int no_s2 = getenv("VPD_WGRAD_S2") ? !atoi(getenv("VPD_WGRAD_S2")) : 0;
+    const int no_s2 = !vpd_switches().wgrad_s2;
     // 1x1 convolutions on the halo kernel (centre tap), no atomics.  As ONE launch per conv it is no faster than the atomics
     // kernel (both run at the ~4 TB/s their operand streams allow; ResNet-50: 9.90 vs 9.55 ms per step, ResNet-34: +12 us),
     // but it OVERWRITES its output and adds in a fixed order.  Default: ON where the caller asks for it (WgradParams::
     // prefer_halo_1x1 -- the plan sets it for the BasicBlock students, whose three down-sampling convs were the last fp32
     // atomics of the step: the ResNet-18/34 step is now reproducible bit for bit), otherwise off; VPD_WGRAD_1X1=0/1 forces.
-    static const int env_1x1 = getenv("VPD_WGRAD_1X1") ? atoi(getenv("VPD_WGRAD_1X1")) : -1;
+    const int env_1x1 = vpd_switches().wgrad_1x1;
     const int no_1x1 = env_1x1 >= 0 ? !env_1x1 : !p0.prefer_halo_1x1;
     WgradParams p = p0;
     if (wg_as_one_by_one(p0, &p) && no_1x1) return false;
@@ -810,7 +810,7 @@ bool vpd_wgrad_group_eligible(const WgradParams& p) {
 hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stream) {
     if (n < 1 || n > WG_GROUP_MAX) return hipErrorInvalidValue;
 #ifdef VPD_ENABLE_ABLATE
-    static const int ablate = getenv("VPD_ABLATE") ? atoi(getenv("VPD_ABLATE")) : 0;
+    const int ablate = vpd_switches().ablate;
 #else
     constexpr int ablate = 0;
 #endif
@@ -868,7 +868,7 @@ hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
     if (p0.Kc % 64 != 0 || p0.Co % 64 != 0 || p0.M <= 0) return hipErrorInvalidValue;
     WgradParams p = p0;
 #ifdef VPD_ENABLE_ABLATE
-    static const int ablate = getenv("VPD_ABLATE") ? atoi(getenv("VPD_ABLATE")) : 0;
+    const int ablate = vpd_switches().ablate;
 #else
     constexpr int ablate = 0;
 #endif
@@ -1355,8 +1355,7 @@ __global__ __launch_bounds__(512) void conv_wgrad128_persistent_kernel(const Wg2
 // kind of a problem for the persistent launch: -1 not eligible, 0 3x3, 1 / 2 1x1 (pad 0: one tap at padded offset (1, 1)) on
 // 128 x 64 / 128 x 128 tiles
 static int wg2_kind_1x1(const WgradParams& p) {
-    static const int off = getenv("VPD_WG2_1X1") ? !atoi(getenv("VPD_WG2_1X1")) : 0;
-    if (off || !(p.taps.nr == 1 && p.taps.nc == 1 && p.taps.dy0 == 1 && p.taps.dx0 == 1) || p.one_by_one) return -1;
+    if (!vpd_switches().wg2_1x1 || !(p.taps.nr == 1 && p.taps.nc == 1 && p.taps.dy0 == 1 && p.taps.dx0 == 1) || p.one_by_one) return -1;
     if (p.Co % 128 || p.Kc % 64 || p.xC != p.Kc || p.dzC % 128 || p.dzpad < 1 || (p.istr != 1 && p.istr != 2)) return -1;
     if (p.xHp != p.istr * p.Hs + 2 || p.xWp != p.istr * p.Ws + 2 || p.dzHp != p.Hs + 2 * p.dzpad || p.dzWp != p.Ws + 2 * p.dzpad) return -1;
     const int W = p.Ws, H = p.Hs;
@@ -1369,8 +1368,7 @@ static int wg2_kind_1x1(const WgradParams& p) {
     if (p.Kc % 256 == 0) return 4;
     // few input channels, many output channels (a Bottleneck's closing conv): 256 x 64 / 256 x 128 tiles -- the x chunk serves twice
     // the output channels
-    static const int tco = getenv("VPD_WG2_TCO256") ? atoi(getenv("VPD_WG2_TCO256")) : 1;
-    return (p.Kc % 128 == 0 ? 2 : 1) + (tco && p.Co % 256 == 0 ? 16 : 0);
+    return (p.Kc % 128 == 0 ? 2 : 1) + (vpd_switches().wg2_tco256 && p.Co % 256 == 0 ? 16 : 0);
 }
 static inline int wg2_nb(int kind) { return kind & 15; }                     // 64-channel ci blocks per tile
 static inline int wg2_tco(int kind) { return kind >= 16 ? 256 : 128; }       // output channels per tile
@@ -1380,7 +1378,7 @@ static void wg2_geom_1x1(const WgradParams& p, WgHaloGeom* g) {
     g->TR = TR; g->multi = TR > p.Hs ? 1 : 0; g->NHP = 64; g->HR = 0; g->total_pix = p.N * p.xHp * p.xWp;
 }
 bool vpd_wgrad128_eligible(const WgradParams& p) {
-    static const int off = getenv("VPD_WG2") ? !atoi(getenv("VPD_WG2")) : 0;
+    const int off = !vpd_switches().wg2;
     if (!off && wg2_kind_1x1(p) > 0) return true;
     WgHaloGeom g;
     WgradParams q = p;

@@ -394,7 +394,7 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
     p->arena_off = bp.take((size_t)p->arena_elems * 2);
     p->wg_off = bp.take((size_t)p->wg_elems * 4);
     for (BnInfo* b : p->bns) b->fl_off = bp.take((size_t)9 * b->C * 4);
-    p->fused_bn = !(getenv("VPD_FUSED_BN") && !atoi(getenv("VPD_FUSED_BN")));
+    p->fused_bn = vpd_switches().fused_bn;
     {
         const size_t start = bp.cur;
         for (BnInfo* b : p->bns) {
@@ -489,11 +489,11 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
         }
         // grouped weight gradients: every eligible 3x3 stride-1 conv keeps its own dz until the
         // stage's grouped launch; the stage's slab holds every problem's splits at once
-        p->wg_group = !(getenv("VPD_WG_GROUP") && !atoi(getenv("VPD_WG_GROUP")));
+        p->wg_group = vpd_switches().wg_group;
         // data parallel (VPD_TRAIN_EARLY_BUCKET0): layer4's weight gradients get a launch of their own at the end of layer4's
         // backward, so that bucket 0 -- fc + layer4, 61 % of the gradient bytes -- is handed to the reducer there instead of
         // together with bucket 1 behind layer3 (single GPU: the merged launch fills the chip, +0.5 % on the step)
-        p->wg_merge34 = !(getenv("VPD_WG_MERGE") && !atoi(getenv("VPD_WG_MERGE"))) && !p->early_bucket0;
+        p->wg_merge34 = vpd_switches().wg_merge && !p->early_bucket0;
         if (p->wg_group) {
             // slabs of one LAUNCH live side by side: with wg_merge34 the stages 2 and 3 (layer3, layer4) share a launch
             size_t stage_slab[4] = {0, 0, 0, 0};
@@ -543,7 +543,7 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
             p->gslab_off = bp.take(mx * 4);
             for (int s2 = 0; s2 < 8; ++s2) p->wg2_tbl_off[s2] = bp.take(vpd_wgrad128_table_bytes());
         }
-        p->relu_bits = !(getenv("VPD_RELU_BITS") && !atoi(getenv("VPD_RELU_BITS")));
+        p->relu_bits = vpd_switches().relu_bits;
         if (p->relu_bits)
             for (auto& B : p->blocks) {
                 const ConvInfo& last = bottleneck ? B.c3 : B.c2;      // the conv whose BatchNorm feeds the block-output ReLU
@@ -553,7 +553,7 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
         // backward launches sit on the grid barrier's latency chain (14-16 us for 2-8 MB) like a BasicBlock student's; in layer1 /
         // layer2 the tensors are 4-16x larger, the launches run at the memory system's rate, and the second read of z in the data
         // gradients' epilogues costs what the shorter BatchNorm launch saves (ResNet-50 8.73 -> 8.76 ms with all stages, rounds 2 / 4)
-        p->dgrad_sums = p->relu_bits && p->fused_bn && !(getenv("VPD_DGRAD_SUMS") && !atoi(getenv("VPD_DGRAD_SUMS")));
+        p->dgrad_sums = p->relu_bits && p->fused_bn && vpd_switches().dgrad_sums;
         if (p->dgrad_sums)
             for (auto& B : p->blocks) {
                 if (bottleneck && B.stage < 2) continue;
@@ -694,8 +694,7 @@ struct AltConv { const ConvInfo* cv; bf16_t* y; const float* ep_scale; const flo
 // can `cd` ride in `c1`'s launch?  Same input, same output geometry and channel count; train mode needs per-BatchNorm
 // statistics rows (the shared rows serve one conv at a time).  VPD_DS_MERGE=0 keeps the two launches.
 bool conv_pair_ok(const Ctx& c, const ConvInfo& c1, const ConvInfo& cd, bool train) {
-    static const bool off = getenv("VPD_DS_MERGE") && !atoi(getenv("VPD_DS_MERGE"));
-    if (off || c.p->bottleneck || c1.k != 3 || cd.k != 1 || c1.stride != 2 || cd.stride != 2) return false;
+    if (!vpd_switches().ds_merge || c.p->bottleneck || c1.k != 3 || cd.k != 1 || c1.stride != 2 || cd.stride != 2) return false;
     if (c1.Hin != cd.Hin || c1.Win != cd.Win || c1.Hout != cd.Hout || c1.Wout != cd.Wout || c1.Ci != cd.Ci || c1.Co != cd.Co)
         return false;
     return !train || (c.fused(c1) && c.fused(cd));
@@ -781,8 +780,7 @@ struct BnSums { const bf16_t* z; const unsigned char* mask; double* rows; const 
 bool dgrad_takes_sums(const Ctx& c, const ConvInfo& cv, int accumulate, bool pair = false) {
     if (!c.p->dgrad_sums) return false;
     // a stride-2 conv's merged parity classes (plain store; even input dims: the classes tile the input exactly)
-    static const bool s2on = !(getenv("VPD_DGRAD_SUMS_S2") && !atoi(getenv("VPD_DGRAD_SUMS_S2")));      // (as vpd_conv_takes_bn_sums)
-    if (cv.stride != 1) return s2on && cv.stride == 2 && cv.k == 3 && !accumulate && !pair && cv.Hin % 2 == 0 && cv.Win % 2 == 0;
+    if (cv.stride != 1) return vpd_switches().dgrad_sums_s2 && cv.stride == 2 && cv.k == 3 && !accumulate && !pair && cv.Hin % 2 == 0 && cv.Win % 2 == 0;
     ConvParams q = conv_dgrad_s1_params(c, cv, c.b16(0), c.b16(0), accumulate);
     q.bst_z = c.b16(0);
     if (pair) { q.bst_z2 = c.b16(0); q.stats2 = c.stat_rows(); }
@@ -977,8 +975,7 @@ hipError_t run_bn_bwd(const Ctx& c, const ConvInfo& cv, bf16_t* dy, const bf16_t
     if (reduce_done) b.act = nullptr;        // dy already holds g (masked by the producing dgrad kernel)
     const bool fused = c.fused(cv) && !reduce_done && vpd_bn_bwd_fused_ok(b.M, b.C, b.act != nullptr, write_g != 0);
     if (dy_pooled) {
-        static const bool fold = !(getenv("VPD_POOLBWD_FOLD") && !atoi(getenv("VPD_POOLBWD_FOLD")));
-        if (fused && mask_bits && fold) { b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)(cv.Hout * cv.Wout); }
+        if (fused && mask_bits && vpd_switches().poolbwd_fold) { b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)(cv.Hout * cv.Wout); }
         else {
             hipError_t e = vpd_launch_avgpool_bwd(dy_pooled, cv.Hout, cv.Wout, cv.Co, c.n, dy, c.s);
             if (e != hipSuccess) return e;
@@ -1198,9 +1195,8 @@ int run_eval_forward(vpd_plan* p, const float* params, const float* x, int n, fl
     if (x) LCHECK(vpd_launch_pack_input(x, n, p->c_in, p->H, p->W, c.b16(p->xin_off), p->xHp, p->xWp, 3, 8, s));
     // stem: conv + folded BatchNorm + ReLU + max-pool in ONE launch when the stem kernel takes the shape and there are enough
     // images for its image-per-block walk (VPD_STEM_POOL_FUSED=0: conv, then the pooling launch)
-    static const bool fuse_pool = !(getenv("VPD_STEM_POOL_FUSED") && !atoi(getenv("VPD_STEM_POOL_FUSED")));
     bool pooled = false;
-    if (fuse_pool && n >= 64)
+    if (vpd_switches().stem_pool_fused && n >= 64)
         LCHECK(run_conv_fwd(c, p->stem, c.b16(p->xin_off), c.b16(p->z0_off), 0, false, c.bn_escale(p->stem.bn),
                             c.bn_eshift(p->stem.bn), nullptr, 1, nullptr, c.b16(p->p0_off), &pooled));
     else
@@ -1573,7 +1569,7 @@ extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, in
         return 0;
     };
     std::vector<char> bn2_sums_for(p->blocks.size(), 0);       // ... its sums taken by the next block's dgrad (BnSums)
-    static const bool pair_sums = !(getenv("VPD_DGRAD_SUMS_PAIR") && !atoi(getenv("VPD_DGRAD_SUMS_PAIR")));
+    const bool pair_sums = vpd_switches().dgrad_sums_pair;
     for (int bi = (int)p->blocks.size() - 1; bi >= 0; --bi) {
         BlockInfo& B = p->blocks[bi];
         const StageInfo& S = p->stages[B.stage];
@@ -1687,8 +1683,7 @@ extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, in
                 // the previous stage's last block: the sums of that block's bn2 are taken here
                 const BnSums* smp = nullptr;
                 BnSums sm;
-                static const bool s2sums = !(getenv("VPD_DGRAD_SUMS_S2") && !atoi(getenv("VPD_DGRAD_SUMS_S2")));
-                if (bi > 0 && p->dgrad_sums && s2sums && (B.c1.Hin % 2) == 0 && (B.c1.Win % 2) == 0) {
+                if (bi > 0 && p->dgrad_sums && vpd_switches().dgrad_sums_s2 && (B.c1.Hin % 2) == 0 && (B.c1.Win % 2) == 0) {
                     const BlockInfo& Bp = p->blocks[bi - 1];
                     if (!Bp.ds && relu_bits_ok(c, Bp.c2)) {
                         sm = BnSums{c.b16(Bp.c2.z_off), reinterpret_cast<const unsigned char*>(ws + Bp.mask_off), c.bn_rows(Bp.c2.bn), nullptr, nullptr};
