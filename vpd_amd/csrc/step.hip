@@ -1,0 +1,1038 @@
+// The passes on a plan (plan.hip): eval forward, train forward + loss, backward, the weight re-pack and the captured eval
+// graphs -- the launch sequences behind the step entry points of include/vpd_hip.h.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "plan.h"
+
+// ---------------------------------------------------------------------------
+namespace {
+
+struct Ctx {
+    vpd_plan* p;
+    char* ws;
+    hipStream_t s;
+    const float* params;
+    int n;
+    bf16_t* b16(size_t off) const { return reinterpret_cast<bf16_t*>(ws + off); }
+    float* f32(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+    unsigned char* u8(size_t off) const { return reinterpret_cast<unsigned char*>(ws + off); }
+    // a conv's dz: its own buffer when its weight gradient joins the stage's grouped launch (dz_own_off is set only then),
+    // else the stage's shared buffer `shared_off`
+    bf16_t* dz(const ConvInfo& cv, size_t shared_off) const { return b16(cv.dz_own_off ? cv.dz_own_off : shared_off); }
+    double* stat_rows() const { return reinterpret_cast<double*>(ws + p->partial_off); }
+    double* bn_rows(const BnInfo& b) const { return reinterpret_cast<double*>(ws + b.rows_off); }
+    bool fused(const ConvInfo& cv) const { return p->fused_bn && !cv.stem; }
+    float* bn_mean(const BnInfo& b) const { return f32(b.fl_off); }
+    float* bn_rstd(const BnInfo& b) const { return f32(b.fl_off) + b.C; }
+    float* bn_scale(const BnInfo& b) const { return f32(b.fl_off) + 2 * b.C; }
+    float* bn_shift(const BnInfo& b) const { return f32(b.fl_off) + 3 * b.C; }
+    float* bn_coef(const BnInfo& b) const { return f32(b.fl_off) + 4 * b.C; }
+    float* bn_escale(const BnInfo& b) const { return f32(b.fl_off) + 7 * b.C; }
+    float* bn_eshift(const BnInfo& b) const { return f32(b.fl_off) + 8 * b.C; }
+};
+
+// timing classes: 0..4 = vpd_conv_kernel_class, 5 = conv_wgrad_halo_kernel (without its slab reduce), 6 = conv_wgrad_kernel
+struct TimeScope {
+    vpd_plan* p; hipStream_t s; int idx = -1;
+    TimeScope(vpd_plan* p_, hipStream_t s_, int cls, double flops) : p(p_), s(s_) {
+        if (!p->timing) return;
+        auto get = [&]() {
+            hipEvent_t e;
+            if (!p->ev_pool.empty()) { e = p->ev_pool.back(); p->ev_pool.pop_back(); }
+            else (void)hipEventCreate(&e);
+            return e;
+        };
+        vpd_plan::TimedLaunch t{cls, flops, get(), get()};
+        p->timed.push_back(t);
+        idx = (int)p->timed.size() - 1;
+        vpd_launch_events() = {t.a, t.b};       // the scope's first matrix-kernel launch carries them (common.h)
+    }
+    ~TimeScope() {
+        if (idx < 0) return;
+        if (vpd_launch_events().start) {        // nothing was launched through VPD_LAUNCH: bracket the scope instead
+            vpd_launch_events().start = nullptr;
+            (void)hipEventRecord(p->timed[idx].a, s);
+            (void)hipEventRecord(p->timed[idx].b, s);
+        }
+    }
+};
+inline double conv_flops(const ConvInfo& cv, int n) {      // algorithmic: real taps and channels
+    return 2.0 * n * cv.Hout * cv.Wout * cv.Co * (double)cv.Ci * cv.k * cv.k;
+}
+// timing class of a conv launch of kernel class kc (vpd_conv_kernel_class): slot 7 is the stem kernel (5, 6 are the wgrads);
+// ws<256,64> shares slot 2 -- except layer1's 64 -> 64 convs, which stay in slot 0
+inline int conv_timing_class(int kc, const ConvInfo& cv) {
+    return kc == 5 ? 7 : (kc == 6 ? (cv.Co == 64 && cv.Ci == 64 ? 0 : 2) : kc);
+}
+
+// forward convolution launch; input padded activation `x` (border 1; stem: xin), output `y`
+// second convolution of the same launch (ConvParams::alt_*): a BasicBlock's 1x1 down-sampling branch beside its first 3x3
+struct AltConv { const ConvInfo* cv; bf16_t* y; const float* ep_scale; const float* ep_shift; int ep_relu; };
+// can `cd` ride in `c1`'s launch?  Same input, same output geometry and channel count; train mode needs per-BatchNorm
+// statistics rows (the shared rows serve one conv at a time).  VPD_DS_MERGE=0 keeps the two launches.
+bool conv_pair_ok(const Ctx& c, const ConvInfo& c1, const ConvInfo& cd, bool train) {
+    if (!vpd_switches().ds_merge || c.p->bottleneck || c1.k != 3 || cd.k != 1 || c1.stride != 2 || cd.stride != 2) return false;
+    if (c1.Hin != cd.Hin || c1.Win != cd.Win || c1.Hout != cd.Hout || c1.Wout != cd.Wout || c1.Ci != cd.Ci || c1.Co != cd.Co)
+        return false;
+    return !train || (c.fused(c1) && c.fused(cd));
+}
+
+// pool_y / pooled: the eval stem with scale / shift / ReLU / max-pool in the conv's epilogue (ConvParams::pool_y) when the stem
+// kernel takes the shape; *pooled tells the caller whether it did (false: plain conv into y, the pooling launch follows)
+hipError_t run_conv_fwd(const Ctx& c, const ConvInfo& cv, const bf16_t* x, bf16_t* y, int ypad, bool stats,
+                        const float* ep_scale, const float* ep_shift, const bf16_t* res, int ep_relu,
+                        const AltConv* alt = nullptr, bf16_t* pool_y = nullptr, bool* pooled = nullptr) {
+    ConvParams q;
+    memset(&q, 0, sizeof q);
+    q.x = x;
+    if (cv.stem) { q.xHp = c.p->xHp; q.xWp = c.p->xWp; q.xC = 8; }
+    else { q.xHp = cv.Hin + 2; q.xWp = cv.Win + 2; q.xC = cv.Ci; }
+    q.w = c.b16(c.p->arena_off) + cv.fwd_off;
+    q.y = y; q.yHp = cv.Hout + 2 * ypad; q.yWp = cv.Wout + 2 * ypad; q.yC = cv.Co; q.ypad = ypad;
+    q.stats = stats ? (c.fused(cv) ? c.bn_rows(cv.bn) : c.stat_rows()) : nullptr;
+    q.stat_rows = c.fused(cv) ? VPD_FUSED_ROWS : 0;
+    q.ep_scale = ep_scale; q.ep_shift = ep_shift; q.res = res; q.ep_relu = ep_relu;
+    q.rHp = cv.Hout + 2; q.rWp = cv.Wout + 2; q.rC = cv.Co; q.rpad = 1;
+    q.N = c.n; q.Hs = cv.Hout; q.Ws = cv.Wout; q.osub = 1; q.oph = 0; q.opw = 0; q.istr = cv.stride;
+    q.Kc = cv.Kc; q.Co = cv.Co; q.M = c.n * cv.Hout * cv.Wout; q.accumulate = 0;
+    q.taps = conv_taps_fwd(cv);
+    q.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
+    double flops = conv_flops(cv, c.n);
+    if (alt) {
+        const ConvInfo& av = *alt->cv;
+        q.alt_w = c.b16(c.p->arena_off) + av.fwd_off; q.alt_y = alt->y; q.alt_taps = conv_taps_fwd(av);
+        q.alt_stats = stats ? c.bn_rows(av.bn) : nullptr;
+        q.alt_ep_scale = alt->ep_scale; q.alt_ep_shift = alt->ep_shift; q.alt_ep_relu = alt->ep_relu;
+        flops += conv_flops(av, c.n);
+    }
+    if (pool_y) {
+        q.pool_y = pool_y;
+        const bool ok = vpd_conv_kernel_class(q) == 5;
+        if (!ok) { q.pool_y = nullptr; q.ep_scale = nullptr; q.ep_shift = nullptr; q.ep_relu = 0; }
+        if (pooled) *pooled = ok;
+    }
+    TimeScope ts(c.p, c.s, conv_timing_class(vpd_conv_kernel_class(q), cv), flops);
+    return vpd_launch_conv(q, c.s);
+}
+
+hipError_t run_bn_finalize(const Ctx& c, const ConvInfo& cv, float* bn_running) {
+    const int M = c.n * cv.Hout * cv.Wout;
+    const int T = VPD_STAT_ROWS;     // unused accumulator rows are zero; the producer's tile size is its own business
+    return vpd_launch_bn_finalize(c.stat_rows(), T, cv.Co, (float)M, c.params + cv.bn.w_off,
+                                  c.params + cv.bn.b_off, bn_running ? bn_running + cv.bn.rm_off : nullptr,
+                                  bn_running ? bn_running + cv.bn.rv_off : nullptr, kBnMomentum, kBnEps,
+                                  c.bn_mean(cv.bn), c.bn_rstd(cv.bn), c.bn_scale(cv.bn), c.bn_shift(cv.bn), c.s);
+}
+
+// data-gradient launch descriptor of a conv: dz (padded, border 1) -> dx (dense [n][Hin][Win][Ci]).  Stride 2: the caller
+// fills in the parity classes (run_conv_dgrad)
+ConvParams conv_dgrad_params(const Ctx& c, const ConvInfo& cv, const bf16_t* dz, bf16_t* dx, int accumulate) {
+    ConvParams q;
+    memset(&q, 0, sizeof q);
+    q.x = dz; q.xHp = cv.Hout + 2; q.xWp = cv.Wout + 2; q.xC = cv.Co;
+    q.w = c.b16(c.p->arena_off) + cv.dgr_off;
+    q.y = dx; q.yHp = cv.Hin; q.yWp = cv.Win; q.yC = cv.Ci; q.ypad = 0;
+    q.N = c.n; q.Kc = cv.Co; q.Co = cv.Ci; q.accumulate = accumulate; q.istr = 1;
+    if (cv.stride != 1) { q.osub = 2; return q; }
+    // dx[y][x] = sum_{r,t} dz[y + pad - r][x + pad - t] W[r][t]; padded coord adds 1
+    q.Hs = cv.Hin; q.Ws = cv.Win; q.osub = 1; q.oph = 0; q.opw = 0;
+    q.M = c.n * q.Hs * q.Ws;
+    q.taps.nr = cv.k; q.taps.nc = cv.k;
+    q.taps.dy0 = cv.pad + 1; q.taps.dys = -1; q.taps.dx0 = cv.pad + 1; q.taps.dxs = -1;
+    q.taps.w0 = 0; q.taps.wrs = cv.k; q.taps.wcs = 1;
+    q.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
+    return q;
+}
+
+// The sums of a BatchNorm backward (sum g, sum g * z with g = d * mask) taken in the epilogue of the data gradient that
+// produces d (ConvParams::bst_z); the BatchNorm launch is then finalize + apply only (run_bn_bwd_apply).
+// z2 / rows2: a second BatchNorm fed with the same g (the 1x1 branch of a down-sampling block), or null
+struct BnSums { const bf16_t* z; const unsigned char* mask; double* rows; const bf16_t* z2; double* rows2; };
+bool dgrad_takes_sums(const Ctx& c, const ConvInfo& cv, int accumulate, bool pair = false) {
+    if (!c.p->dgrad_sums) return false;
+    // a stride-2 conv's merged parity classes (plain store; even input dims: the classes tile the input exactly)
+    if (cv.stride != 1) return vpd_switches().dgrad_sums_s2 && cv.stride == 2 && cv.k == 3 && !accumulate && !pair && cv.Hin % 2 == 0 && cv.Win % 2 == 0;
+    ConvParams q = conv_dgrad_params(c, cv, c.b16(0), c.b16(0), accumulate);
+    q.bst_z = c.b16(0);
+    if (pair) { q.bst_z2 = c.b16(0); q.stats2 = c.stat_rows(); }
+    return vpd_conv_takes_bn_sums(q);
+}
+
+// ds / dzd: the block's 1x1 stride-2 down-sampling conv and its dz -- its data gradient lands on the even-even input pixels,
+// which are class 0 of the 3x3's: extra K-steps of those blocks instead of a read-modify-write launch of its own
+hipError_t run_conv_dgrad(const Ctx& c, const ConvInfo& cv, const bf16_t* dz, bf16_t* dx, int accumulate,
+                          const ConvInfo* ds = nullptr, const bf16_t* dzd = nullptr,
+                          const unsigned char* acc_mask = nullptr, const BnSums* sums = nullptr) {
+    ConvParams q = conv_dgrad_params(c, cv, dz, dx, accumulate);
+    if (cv.stride == 1) {
+        q.acc_mask = accumulate ? acc_mask : nullptr;
+        if (sums) {      // (the caller has checked dgrad_takes_sums)
+            q.bst_z = sums->z; q.bst_mask = sums->mask;
+            q.stats = sums->rows; q.stat_rows = VPD_FUSED_ROWS;
+            q.bst_z2 = sums->z2; q.stats2 = sums->rows2;
+        }
+        TimeScope ts(c.p, c.s, conv_timing_class(vpd_conv_kernel_class(q), cv), conv_flops(cv, c.n));
+        return vpd_launch_conv(q, c.s);
+    }
+    // stride 2: the four input-pixel parity classes are ONE launch (grid.z = class).  Only taps r with
+    // (ph + pad - r) even contribute: r = rf, rf+2, ... reading dz row  y + (ph + pad - r)/2  (+1 for the border).
+    TimeScope ts(c.p, c.s, 4, conv_flops(cv, c.n) + (ds ? conv_flops(*ds, c.n) : 0.0));
+    int ncls = 0;
+    for (int ph = 0; ph < 2; ++ph)
+        for (int pw = 0; pw < 2; ++pw) {
+            ConvClass k;
+            k.geo.Hs = (cv.Hin - ph + 1) / 2; k.geo.Ws = (cv.Win - pw + 1) / 2;
+            if (k.geo.Hs <= 0 || k.geo.Ws <= 0) continue;
+            k.geo.oph = ph; k.geo.opw = pw;
+            k.geo.M = c.n * k.geo.Hs * k.geo.Ws;
+            const int rf = (ph + cv.pad) % 2, tf = (pw + cv.pad) % 2;
+            k.taps.nr = rf < cv.k ? (cv.k - rf + 1) / 2 : 0;
+            k.taps.nc = tf < cv.k ? (cv.k - tf + 1) / 2 : 0;
+            if (k.taps.nr == 0 || k.taps.nc == 0) continue;   // caller zero-fills / overwrites those pixels
+            k.taps.dy0 = (ph + cv.pad - rf) / 2 + 1; k.taps.dys = -1;
+            k.taps.dx0 = (pw + cv.pad - tf) / 2 + 1; k.taps.dxs = -1;
+            k.taps.w0 = rf * cv.k + tf; k.taps.wrs = 2 * cv.k; k.taps.wcs = 2;
+            if (ncls == 0) {
+                q.Hs = k.geo.Hs; q.Ws = k.geo.Ws; q.M = k.geo.M; q.oph = ph; q.opw = pw; q.taps = k.taps;
+            } else {
+                q.cls[ncls - 1] = k;
+            }
+            ++ncls;
+        }
+    if (ncls == 0) return hipSuccess;
+    q.ncls = ncls;
+    if (ds) {
+        if (q.oph != 0 || q.opw != 0 || q.taps.nr != 1 || q.taps.nc != 1 || ds->Co != cv.Co) return hipErrorInvalidValue;
+        q.x2 = dzd; q.w2 = c.b16(c.p->arena_off) + ds->dgr_off; q.Kc2 = ds->Co;
+    }
+    if (sums) {      // the four classes together write every pixel of dx exactly once
+        q.bst_z = sums->z; q.bst_mask = sums->mask;
+        q.stats = sums->rows; q.stat_rows = VPD_FUSED_ROWS;
+        if (accumulate || !vpd_conv_takes_bn_sums(q)) return hipErrorInvalidValue;
+    }
+    return vpd_launch_conv(q, c.s);
+}
+
+// weight gradient of a conv in launches of its own.  The generic kernel accumulates with atomics: its range is zeroed at the start
+// of the backward, by the dry run (collect_zero) that lists it.
+hipError_t run_conv_wgrad(const Ctx& c, const ConvInfo& cv, const bf16_t* dz, const bf16_t* x, ZeroRanges* collect_zero = nullptr) {
+    WgradParams q = wgrad_params(cv, c.n, dz, x);
+    if (cv.stem) { q.dzHp = cv.Hout; q.dzWp = cv.Wout; q.dzpad = 0; q.xHp = c.p->xHp; q.xWp = c.p->xWp; q.xC = 8; }
+    q.dw = c.f32(c.p->wg_off) + cv.wg_off;
+    float* slab = c.f32(c.p->slab_off);
+    q.slab = cv.slab_off >= 0 ? slab + cv.slab_off : (cv.stem ? slab : nullptr);
+    q.prefer_halo_1x1 = !c.p->bottleneck;      // BasicBlock students: the three down-sampling 1x1 convs without atomics
+    if (cv.slab_off >= 0 && !vpd_wgrad_overwrites(q)) q.slab = nullptr;      // (an A/B switch turned the halo form off: generic kernel)
+    if (collect_zero) {
+        if (!vpd_wgrad_overwrites(q) && collect_zero->count < ZR_MAX) {
+            collect_zero->ptr[collect_zero->count] = q.dw;
+            collect_zero->n4[collect_zero->count++] = (long)cv.ntaps * cv.Co * cv.Kc / 4;
+        }
+        return hipSuccess;
+    }
+    if (vpd_wgrad_overwrites(q) && !cv.stem) {      // time the MFMA kernel alone, then sum its slab
+        hipError_t e;
+        {
+            // class 5 = the grouped per-stage launches (and single stride-1 halo launches); a stride-2 conv's own halo
+            // launch (two output tiles, 128 splits) is a different regime: class 6 with the other per-conv launches
+            TimeScope ts(c.p, c.s, cv.stride == 1 ? 5 : 6, conv_flops(cv, c.n));
+            q.defer_reduce = 1;
+            e = vpd_launch_wgrad(q, c.s);
+        }
+        if (e != hipSuccess) return e;
+        return vpd_launch_wgrad_reduce(q, c.s);
+    }
+    TimeScope ts(c.p, c.s, cv.stem ? 7 : (vpd_wgrad_overwrites(q) ? 5 : 6), conv_flops(cv, c.n));      // 7: stem kernels
+    return vpd_launch_wgrad(q, c.s);
+}
+
+BnApplyParams bn_apply_params(const Ctx& c, const ConvInfo& cv, int res_kind, const bf16_t* res, bf16_t* out, int relu) {
+    BnApplyParams a;
+    memset(&a, 0, sizeof a);
+    a.z = c.b16(cv.z_off);
+    a.res_kind = res_kind; a.res = res; a.rHp = cv.Hout + 2; a.rWp = cv.Wout + 2; a.rpad = 1;
+    a.out = out; a.oHp = cv.Hout + 2; a.oWp = cv.Wout + 2; a.opad = 1;
+    a.M = c.n * cv.Hout * cv.Wout; a.H = cv.Hout; a.W = cv.Wout; a.C = cv.Co; a.relu = relu;
+    return a;
+}
+hipError_t run_bn_apply(const Ctx& c, const ConvInfo& cv, int res_kind, const bf16_t* res, const ConvInfo* rcv,
+                        bf16_t* out, int relu) {
+    BnApplyParams a = bn_apply_params(c, cv, res_kind, res, out, relu);
+    a.scale = c.bn_scale(cv.bn); a.shift = c.bn_shift(cv.bn);
+    if (rcv) { a.rscale = c.bn_scale(rcv->bn); a.rshift = c.bn_shift(rcv->bn); }
+    return vpd_launch_bn_apply(a, c.s);
+}
+
+// train-mode convolution: dense z + per-channel statistics.  Unfused BatchNorm: the statistics go to the SHARED rows,
+// which the finalize launch right behind the conv consumes and re-zeroes; fused: to the BatchNorm's own rows.
+hipError_t run_conv_train(const Ctx& c, const ConvInfo& cv, const bf16_t* x, float* bn_running) {
+    hipError_t e = run_conv_fwd(c, cv, x, c.b16(cv.z_off), 0, true, nullptr, nullptr, nullptr, 0);
+    if (e != hipSuccess || c.fused(cv)) return e;
+    return run_bn_finalize(c, cv, bn_running);
+}
+
+// Pixel tile of the pipelined 3x3 launches next to conv `cv`'s BatchNorm (its own forward / data gradient, and -- same stage, same
+// shape -- its neighbours'), when they run in their XCD-affine tile order: the fused BatchNorm launches then take their items in
+// the matching block order (bn.hip, vpd_bn_virtual_block).  3x3 stride-1 convolutions with Ci == Co only; 0 otherwise.
+int bn_xcd_tile_px(const Ctx& c, const ConvInfo& cv) {
+    if (cv.k != 3 || cv.stride != 1 || cv.stem || cv.Ci != cv.Co) return 0;
+    const ConvParams q = conv_dgrad_params(c, cv, c.b16(0), c.b16(0), 0);
+    return vpd_conv_xcd_tile_px(q);
+}
+
+// the fused forward launch's BatchNorm side(s): conv `cv`'s BatchNorm and, when given, the residual branch's (`cv2`)
+BnFusedFwd bn_fused_fwd(const Ctx& c, const ConvInfo& cv, float* bn_running, const ConvInfo* cv2 = nullptr) {
+    BnFusedFwd f;
+    memset(&f, 0, sizeof f);
+    const BnInfo& b = cv.bn;
+    f.rows = c.bn_rows(b); f.count = (float)(c.n * cv.Hout * cv.Wout);
+    f.gamma = c.params + b.w_off; f.beta = c.params + b.b_off;
+    f.rm = bn_running ? bn_running + b.rm_off : nullptr; f.rv = bn_running ? bn_running + b.rv_off : nullptr;
+    f.mean = c.bn_mean(b); f.rstd = c.bn_rstd(b); f.scale = c.bn_scale(b); f.shift = c.bn_shift(b);
+    if (cv2) {
+        const BnFusedFwd g = bn_fused_fwd(c, *cv2, bn_running);
+        f.rows2 = g.rows; f.count2 = g.count; f.gamma2 = g.gamma; f.beta2 = g.beta; f.rm2 = g.rm; f.rv2 = g.rv;
+        f.mean2 = g.mean; f.rstd2 = g.rstd; f.scale2 = g.scale; f.shift2 = g.shift;
+    }
+    f.momentum = kBnMomentum; f.eps = kBnEps;
+    return f;
+}
+// BatchNorm (+ residual, ReLU) of a train-mode forward: statistics -> normalised padded activation.  rcv: the
+// down-sampling branch's conv (res_kind 2), whose BatchNorm is finalized here too.  One launch when fused.
+hipError_t run_bn_fwd(const Ctx& c, const ConvInfo& cv, float* bn_running, int res_kind, const bf16_t* res,
+                      const ConvInfo* rcv, bf16_t* out, int relu, unsigned char* mask_out = nullptr) {
+    if (!c.fused(cv)) return run_bn_apply(c, cv, res_kind, res, rcv, out, relu);      // (finalized by run_conv_train)
+    BnApplyParams a = bn_apply_params(c, cv, res_kind, res, out, relu);
+    a.mask_out = mask_out;
+    a.xcd_tile_px = bn_xcd_tile_px(c, cv);
+    return vpd_launch_bn_fwd_fused(a, bn_fused_fwd(c, cv, bn_running, rcv), c.s);
+}
+
+// BatchNorm backward geometry of conv cv's BatchNorm: dy (dense) -> dz (padded by dzpad)
+BnBwdParams bn_bwd_params(const Ctx& c, const ConvInfo& cv, const bf16_t* dy, bf16_t* dz, int dzpad) {
+    BnBwdParams b;
+    memset(&b, 0, sizeof b);
+    b.dy = dy; b.z = c.b16(cv.z_off);
+    b.mean = c.bn_mean(cv.bn); b.rstd = c.bn_rstd(cv.bn);
+    b.dz = dz; b.dzHp = cv.Hout + 2 * dzpad; b.dzWp = cv.Wout + 2 * dzpad; b.dzpad = dzpad;
+    b.M = c.n * cv.Hout * cv.Wout; b.H = cv.Hout; b.W = cv.Wout; b.C = cv.Co;
+    return b;
+}
+// one BatchNorm of a fused backward launch: its rows, gamma and gradients (launches with a grid barrier add sync / err)
+BnFusedBwd bn_bwd_side(const Ctx& c, const ConvInfo& cv, float* grads) {
+    BnFusedBwd f;
+    memset(&f, 0, sizeof f);
+    f.rows = c.bn_rows(cv.bn);
+    f.gamma = c.params + cv.bn.w_off; f.dgamma = grads + cv.bn.w_off; f.dbeta = grads + cv.bn.b_off;
+    f.count = (float)(c.n * cv.Hout * cv.Wout);
+    return f;
+}
+
+// act != null: ReLU mask from the stored activation (needed when a residual was added before the ReLU);
+// relu_from_z: mask recomputed as scale*z + shift > 0 (plain conv-BN-ReLU), which saves reading the activation
+// mask_bits: the ReLU mask as a bit map (fused launch only; the caller has checked relu_bits_ok): act and write_g are ignored
+bool relu_bits_ok(const Ctx& c, const ConvInfo& cv) {
+    return c.p->relu_bits && c.fused(cv) && vpd_bn_bwd_fused_ok(c.n * cv.Hout * cv.Wout, cv.Co, false, false);
+}
+// dy_pooled: dy has not been produced yet -- it is the gradient of the global average pool over cv's output (the last block of
+// the network); the fused launch with a ReLU bit map produces it itself, every other path gets the avgpool_bwd launch first
+hipError_t run_bn_bwd(const Ctx& c, const ConvInfo& cv, bf16_t* dy, const bf16_t* act, bf16_t* dz, int dzpad,
+                      int write_g, float* grads, bool relu_from_z = false, bool reduce_done = false,
+                      const unsigned char* mask_bits = nullptr, const float* dy_pooled = nullptr) {
+    BnBwdParams b = bn_bwd_params(c, cv, dy, dz, dzpad);
+    b.dy_rw = dy; b.act = act; b.aHp = cv.Hout + 2; b.aWp = cv.Wout + 2; b.apad = 1;
+    b.coef = c.bn_coef(cv.bn); b.partials = c.stat_rows(); b.write_g = write_g;
+    if (mask_bits) { b.mask_bits = mask_bits; b.act = nullptr; b.write_g = 0; write_g = 0; }
+    if (relu_from_z && !reduce_done) { b.act = nullptr; b.mscale = c.bn_scale(cv.bn); b.mshift = c.bn_shift(cv.bn); }
+    if (reduce_done) b.act = nullptr;        // dy already holds g (masked by the producing dgrad kernel)
+    const bool fused = c.fused(cv) && !reduce_done && vpd_bn_bwd_fused_ok(b.M, b.C, b.act != nullptr, write_g != 0);
+    if (dy_pooled) {
+        if (fused && mask_bits && vpd_switches().poolbwd_fold) { b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)(cv.Hout * cv.Wout); }
+        else {
+            hipError_t e = vpd_launch_avgpool_bwd(dy_pooled, cv.Hout, cv.Wout, cv.Co, c.n, dy, c.s);
+            if (e != hipSuccess) return e;
+        }
+    }
+    if (fused) {
+        BnFusedBwd f = bn_bwd_side(c, cv, grads);
+        f.sync = c.ws + cv.bn.sync_off; f.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
+        return vpd_launch_bn_bwd_fused(b, f, c.s);
+    }
+    return vpd_launch_bn_bwd(b, (float)b.M, c.params + cv.bn.w_off, grads + cv.bn.w_off, grads + cv.bn.b_off, c.s,
+                             reduce_done);
+}
+
+// BatchNorm backward whose sums were taken by the producing data gradient (BnSums): finalize + apply
+// cvB / dzB: a second BatchNorm fed with the same masked gradient (a down-sampling block's 1x1 branch), same launch
+hipError_t run_bn_bwd_apply(const Ctx& c, const ConvInfo& cv, const bf16_t* dy, bf16_t* dz, int dzpad, float* grads,
+                            const unsigned char* mask_bits, const ConvInfo* cvB = nullptr, bf16_t* dzB = nullptr) {
+    BnBwdParams b = bn_bwd_params(c, cv, dy, dz, dzpad);
+    b.mask_bits = mask_bits;
+    b.xcd_tile_px = bn_xcd_tile_px(c, cv);
+    const BnFusedBwd f = bn_bwd_side(c, cv, grads);
+    if (cvB) {
+        const BnFusedBwd fB = bn_bwd_side(c, *cvB, grads);
+        return vpd_launch_bn_bwd_apply_fused(b, f, c.s, &fB, c.b16(cvB->z_off), c.bn_mean(cvB->bn), c.bn_rstd(cvB->bn), dzB);
+    }
+    return vpd_launch_bn_bwd_apply_fused(b, f, c.s);
+}
+
+// block-output BatchNorm (A: the block's last conv) and the down-sampling branch's BatchNorm (Bc) in one launch: same dy,
+// same ReLU mask (bn_bwd_fused2_kernel).  Not applicable (bn_bwd_pair_ok false): the caller runs them one after the other
+bool bn_bwd_pair_ok(const Ctx& c, const ConvInfo& A, const ConvInfo& Bc) {
+    return c.fused(A) && c.fused(Bc) && A.Co == Bc.Co && vpd_bn_bwd_fused2_ok(c.n * A.Hout * A.Wout, A.Co);
+}
+hipError_t run_bn_bwd_pair(const Ctx& c, const ConvInfo& A, const ConvInfo& Bc, bf16_t* dy, const bf16_t* act, bf16_t* dzA,
+                           bf16_t* dzB, float* grads) {
+    BnBwdParams b = bn_bwd_params(c, A, dy, dzA, 1);
+    b.dy_rw = dy; b.act = act; b.aHp = A.Hout + 2; b.aWp = A.Wout + 2; b.apad = 1;
+    BnFusedBwd fA = bn_bwd_side(c, A, grads), fB = bn_bwd_side(c, Bc, grads);
+    fA.sync = fB.sync = c.ws + A.bn.sync_off;
+    fA.err = fB.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
+    return vpd_launch_bn_bwd_fused2(b, fA, fB, c.b16(Bc.z_off), c.bn_mean(Bc.bn), c.bn_rstd(Bc.bn), dzB, c.s);
+}
+
+// ---- a Bottleneck identity block's closing 1x1 convolution together with its BatchNorm, the convolution recomputed instead of
+// written and read back (conv_stream.hip, conv1x1_bn_stream_kernel; VPD_BNECK_RECOMPUTE=0: conv + BatchNorm launches) ----
+ConvParams conv3_params(const Ctx& c, const ConvInfo& cv, const bf16_t* x) {
+    ConvParams q;
+    memset(&q, 0, sizeof q);
+    q.x = x; q.xHp = cv.Hin + 2; q.xWp = cv.Win + 2; q.xC = cv.Ci;
+    q.w = c.b16(c.p->arena_off) + cv.fwd_off;
+    q.yHp = cv.Hout; q.yWp = cv.Wout; q.yC = cv.Co; q.ypad = 0;
+    q.N = c.n; q.Hs = cv.Hout; q.Ws = cv.Wout; q.osub = 1; q.istr = cv.stride;
+    q.Kc = cv.Kc; q.Co = cv.Co; q.M = c.n * cv.Hout * cv.Wout;
+    q.taps = conv_taps_fwd(cv);
+    return q;
+}
+bool bneck_recompute_ok(const Ctx& c, const BlockInfo& B) {
+    if (!c.p->bottleneck || B.ds || !c.p->train || !c.fused(B.c3) || !relu_bits_ok(c, B.c3)) return false;
+    if (B.c3.k != 1 || B.c3.stride != 1) return false;
+    return vpd_conv1x1_bn_eligible(conv3_params(c, B.c3, c.b16(B.a2_off)));
+}
+// ... and a DOWN-SAMPLING block whose closing 1x1 conv and 1x1 branch both have 64 input channels and stride 1 (layer1's first
+// block): both convolutions and both BatchNorms in the same launches (conv1x1_bn2_stream_kernel)
+ConvParams conv3d_params(const Ctx& c, const BlockInfo& B, const bf16_t* xin) {
+    ConvParams q = conv3_params(c, B.c3, c.b16(B.a2_off));
+    q.x2 = xin; q.w2 = c.b16(c.p->arena_off) + B.cd.fwd_off; q.Kc2 = B.cd.Kc;
+    return q;
+}
+bool bneck_recompute2_ok(const Ctx& c, const BlockInfo& B) {
+    if (!c.p->bottleneck || !B.ds || !c.p->train || !c.fused(B.c3) || !c.fused(B.cd) || !relu_bits_ok(c, B.c3)) return false;
+    if (B.c3.k != 1 || B.cd.k != 1 || B.c3.stride != 1 || B.cd.stride != 1 || B.c3.Ci != B.cd.Ci || B.c3.Co != B.cd.Co) return false;
+    if (B.c3.Hin != B.cd.Hin || B.c3.Win != B.cd.Win) return false;
+    return vpd_conv1x1_bn2_eligible(conv3d_params(c, B, c.b16(B.a2_off)));
+}
+hipError_t run_conv3d_bn_fwd(const Ctx& c, const BlockInfo& B, const bf16_t* xin, bf16_t* out, unsigned char* mask_out,
+                             float* bn_running) {
+    hipError_t e;
+    for (int k = 0; k < 2; ++k) {      // the two statistics passes
+        const ConvInfo& cv = k ? B.cd : B.c3;
+        ConvParams q = conv3_params(c, cv, k ? xin : c.b16(B.a2_off));
+        q.stats = c.bn_rows(cv.bn); q.stat_rows = VPD_FUSED_ROWS;
+        TimeScope ts(c.p, c.s, 4, 0.0);      // (a recomputation: its time counts, its FLOPs are not algorithmic work)
+        e = vpd_launch_conv1x1_bn(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, c.s);
+        if (e != hipSuccess) return e;
+    }
+    ConvParams q = conv3d_params(c, B, xin);
+    q.y = out; q.yHp = B.c3.Hout + 2; q.yWp = B.c3.Wout + 2; q.ypad = 1;
+    const BnFusedFwd f = bn_fused_fwd(c, B.c3, bn_running, &B.cd);
+    TimeScope ts(c.p, c.s, 4, conv_flops(B.c3, c.n) + conv_flops(B.cd, c.n));
+    return vpd_launch_conv1x1_bn2(q, &f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mask_out, nullptr, nullptr, 0, 1, c.s);
+}
+hipError_t run_conv3d_bn_bwd(const Ctx& c, const BlockInfo& B, const bf16_t* xin, bf16_t* dout, const unsigned char* mask_bits,
+                             bf16_t* dz3, bf16_t* dzd, float* grads) {
+    ConvParams q = conv3d_params(c, B, xin);
+    q.y = dout; q.acc_mask = mask_bits;
+    const BnFusedBwd f3 = bn_bwd_side(c, B.c3, grads), fd = bn_bwd_side(c, B.cd, grads);
+    hipError_t e;
+    {
+        TimeScope ts(c.p, c.s, 4, 0.0);      // (BatchNorm backwards: no algorithmic matrix FLOPs)
+        e = vpd_launch_conv1x1_bn2(q, nullptr, &f3, &fd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 2, c.s);
+    }
+    if (e != hipSuccess) return e;
+    TimeScope ts(c.p, c.s, 4, 0.0);
+    return vpd_launch_conv1x1_bn2(q, nullptr, &f3, &fd, c.bn_mean(B.c3.bn), c.bn_rstd(B.c3.bn), c.bn_mean(B.cd.bn), c.bn_rstd(B.cd.bn),
+                                  nullptr, dz3, dzd, 1, 3, c.s);
+}
+// forward: statistics pass, then relu(BatchNorm(conv(x)) + res) -> out (padded) + the ReLU bit map
+hipError_t run_conv3_bn_fwd(const Ctx& c, const ConvInfo& cv, const bf16_t* x, const bf16_t* res, bf16_t* out,
+                            unsigned char* mask_out, float* bn_running) {
+    ConvParams q = conv3_params(c, cv, x);
+    q.stats = c.bn_rows(cv.bn); q.stat_rows = VPD_FUSED_ROWS;
+    hipError_t e;
+    {
+        TimeScope ts(c.p, c.s, 4, 0.0);      // (the statistics pass is a recomputation: time counted, FLOPs not)
+        e = vpd_launch_conv1x1_bn(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, c.s);
+    }
+    if (e != hipSuccess) return e;
+    q.stats = nullptr; q.stat_rows = 0;
+    q.y = out; q.yHp = cv.Hout + 2; q.yWp = cv.Wout + 2; q.ypad = 1;
+    q.res = res; q.rHp = cv.Hout + 2; q.rWp = cv.Wout + 2; q.rC = cv.Co; q.rpad = 1;
+    const BnFusedFwd f = bn_fused_fwd(c, cv, bn_running);
+    TimeScope ts(c.p, c.s, 4, conv_flops(cv, c.n));
+    return vpd_launch_conv1x1_bn(q, &f, nullptr, nullptr, nullptr, mask_out, nullptr, 0, 1, c.s);
+}
+// backward: the sums of g = dout * mask and g * z, then dz = A g + B z + D -> dz (padded by 1), dgamma, dbeta
+hipError_t run_conv3_bn_bwd(const Ctx& c, const ConvInfo& cv, const bf16_t* x, bf16_t* dout, const unsigned char* mask_bits,
+                            bf16_t* dz, float* grads) {
+    ConvParams q = conv3_params(c, cv, x);
+    q.y = dout; q.acc_mask = mask_bits;
+    const BnFusedBwd f = bn_bwd_side(c, cv, grads);
+    hipError_t e;
+    {
+        TimeScope ts(c.p, c.s, 4, 0.0);      // (a BatchNorm backward: no algorithmic matrix FLOPs)
+        e = vpd_launch_conv1x1_bn(q, nullptr, &f, nullptr, nullptr, nullptr, nullptr, 0, 2, c.s);
+    }
+    if (e != hipSuccess) return e;
+    TimeScope ts(c.p, c.s, 4, 0.0);
+    return vpd_launch_conv1x1_bn(q, nullptr, &f, c.bn_mean(cv.bn), c.bn_rstd(cv.bn), nullptr, dz, 1, 3, c.s);
+}
+
+
+// encoder head shared by eval / train: avgpool + fc (+ motion MLP) (+ loss)
+int run_head(const Ctx& c, const bf16_t* last_act, float* emb_out, const float* target, bool need_grad,
+             float* loss_step, double* loss_accum) {
+    vpd_plan* p = c.p;
+    const StageInfo& S = p->stages[3];
+    LCHECK(vpd_launch_avgpool(last_act, S.H + 2, S.W + 2, 1, S.H, S.W, p->feat, c.n, c.f32(p->pooled_off), c.s));
+    // without the motion head nothing re-reads the embedding (the fc backward uses the pooled features and d(emb)): the fc
+    // GEMM writes the caller's buffer directly; with it, the head's first layer and its weight gradient read the workspace copy
+    float* emb = (emb_out && !p->motion) ? emb_out : c.f32(p->emb_off);
+    LCHECK(vpd_launch_sgemm(c.f32(p->pooled_off), c.params + p->fc.w_off, emb, c.params + p->fc.b_off, c.n, p->D, p->feat,
+                            0, 1, 0, c.s));
+    if (emb_out && emb != emb_out) LCHECK(hipMemcpyAsync(emb_out, emb, (size_t)c.n * p->D * 4, hipMemcpyDeviceToDevice, c.s));
+    if (!target) return 0;
+    const float* pred = emb;
+    int pd = p->D;
+    if (p->motion) {
+        LCHECK(vpd_launch_sgemm(emb, c.params + p->dec[0].w_off, c.f32(p->h1_off), c.params + p->dec[0].b_off, c.n, 128,
+                                p->D, 0, 1, 1, c.s));
+        LCHECK(vpd_launch_sgemm(c.f32(p->h1_off), c.params + p->dec[1].w_off, c.f32(p->h2_off),
+                                c.params + p->dec[1].b_off, c.n, 128, 128, 0, 1, 1, c.s));
+        LCHECK(vpd_launch_sgemm(c.f32(p->h2_off), c.params + p->dec[2].w_off, c.f32(p->pred_off),
+                                c.params + p->dec[2].b_off, c.n, 2 * p->D, 128, 0, 1, 0, c.s));
+        pred = c.f32(p->pred_off);
+        pd = 2 * p->D;
+    }
+    LCHECK(vpd_launch_mse(pred, target, (long)c.n * pd, need_grad ? c.f32(p->dpred_off) : nullptr, loss_step,
+                          loss_accum, c.s));
+    return 0;
+}
+
+// accumulator rows (and, fused, every BatchNorm's rows and barrier words): zeroed at the start of each train pass
+ZeroRanges accumulator_zero_ranges(const Ctx& c) {
+    ZeroRanges z;
+    memset(&z, 0, sizeof z);
+    z.ptr[0] = c.f32(c.p->partial_off); z.n4[0] = (long)c.p->partial_bytes / 16; z.count = 1;
+    if (c.p->fused_bn) { z.ptr[1] = c.f32(c.p->fused_off); z.n4[1] = (long)c.p->fused_bytes / 16; z.count = 2; }
+    return z;
+}
+
+// the stem's BatchNorm + ReLU + max-pool launch; idx: the argmax map of a train pass (eval: null)
+StemPoolParams stem_pool_params(const Ctx& c, const float* scale, const float* shift, unsigned char* idx) {
+    StemPoolParams sp;
+    memset(&sp, 0, sizeof sp);
+    sp.z = c.b16(c.p->z0_off); sp.Hz = c.p->H0; sp.Wz = c.p->W0;
+    sp.scale = scale; sp.shift = shift;
+    sp.out = c.b16(c.p->p0_off); sp.opad = 1; sp.idx = idx; sp.N = c.n; sp.Ho = c.p->H1; sp.Wo = c.p->W1; sp.C = 64;
+    return sp;
+}
+
+int run_eval_forward(vpd_plan* p, const float* params, const float* x, int n, float* emb_out, const float* target,
+                     float* loss_step, double* loss_accum, char* ws, hipStream_t s) {
+    Ctx c{p, ws, s, params, n};
+    if (x) LCHECK(vpd_launch_pack_input(x, n, p->c_in, p->H, p->W, c.b16(p->xin_off), p->xHp, p->xWp, 3, 8, s));
+    // stem: conv + folded BatchNorm + ReLU + max-pool in ONE launch when the stem kernel takes the shape and there are enough
+    // images for its image-per-block walk (VPD_STEM_POOL_FUSED=0: conv, then the pooling launch)
+    bool pooled = false;
+    if (vpd_switches().stem_pool_fused && n >= 64)
+        LCHECK(run_conv_fwd(c, p->stem, c.b16(p->xin_off), c.b16(p->z0_off), 0, false, c.bn_escale(p->stem.bn),
+                            c.bn_eshift(p->stem.bn), nullptr, 1, nullptr, c.b16(p->p0_off), &pooled));
+    else
+        LCHECK(run_conv_fwd(c, p->stem, c.b16(p->xin_off), c.b16(p->z0_off), 0, false, nullptr, nullptr, nullptr, 0));
+    if (!pooled) LCHECK(vpd_launch_stem_pool(stem_pool_params(c, c.bn_escale(p->stem.bn), c.bn_eshift(p->stem.bn), nullptr), s));
+    const bf16_t* cur = c.b16(p->p0_off);
+    for (auto& B : p->blocks) {
+        bf16_t* a1 = c.b16(B.a1_off);
+        bf16_t* idb = c.b16(p->stages[B.stage].idn_off);      // the down-sampling branch's output
+        const bool pair = B.ds && conv_pair_ok(c, B.c1, B.cd, false);      // the down-sampling 1x1 rides in conv1's launch
+        const AltConv alt{&B.cd, idb, c.bn_escale(B.cd.bn), c.bn_eshift(B.cd.bn), 0};
+        LCHECK(run_conv_fwd(c, B.c1, cur, a1, 1, false, c.bn_escale(B.c1.bn), c.bn_eshift(B.c1.bn), nullptr, 1, pair ? &alt : nullptr));
+        const bf16_t* last_in = a1;
+        if (p->bottleneck) {
+            last_in = c.b16(B.a2_off);
+            LCHECK(run_conv_fwd(c, B.c2, a1, c.b16(B.a2_off), 1, false, c.bn_escale(B.c2.bn), c.bn_eshift(B.c2.bn), nullptr, 1));
+        }
+        if (B.ds && !pair) LCHECK(run_conv_fwd(c, B.cd, cur, idb, 1, false, c.bn_escale(B.cd.bn), c.bn_eshift(B.cd.bn), nullptr, 0));
+        const ConvInfo& last = p->bottleneck ? B.c3 : B.c2;
+        LCHECK(run_conv_fwd(c, last, last_in, c.b16(B.out_off), 1, false, c.bn_escale(last.bn), c.bn_eshift(last.bn),
+                            B.ds ? idb : cur, 1));
+        cur = c.b16(B.out_off);
+    }
+    return run_head(c, cur, emb_out, target, false, loss_step, loss_accum);
+}
+
+// ---- backward ----
+// Weight gradients of the convs that keep their own dz (ConvInfo::dz_own_off) wait in `pending` for their stage's grouped
+// launch; every other conv's runs at once.  A stage's gradient bucket is handed over -- unpacked, its event recorded -- only
+// behind that launch.  (Running weight gradients or their slab sums on a second stream was measured 6 % slower in round 2 and,
+// with the persistent kernels, 1.4 % slower in round 6; confined to a CU partition 40-50 % slower:
+// profiles/r06_ab_wgrad_overlap.txt, tools/probe/wg_overlap.patch)
+struct WgradQueue {
+    const Ctx& c;
+    float* grads;
+    void** bucket_events;
+    // lazy: the caller asked for it (vpd_plan_set_lazy_grads).  With bucket events the reducer then sums the scratch ranges
+    // (vpd_plan_bucket_scratch_range) and the non-conv tensors of the flat buffer instead of the whole flat buffer
+    bool lazy;
+    struct Pending { const ConvInfo* cv; const bf16_t* dz; const bf16_t* x; };
+    std::vector<Pending> pending;
+    std::vector<int> deferred_buckets;
+
+    // wgrad of `cv` may start once everything enqueued on the stream so far (its dz: Ctx::dz) is done
+    hipError_t queue(const ConvInfo& cv, const bf16_t* dz, const bf16_t* x) {
+        if (cv.dz_own_off) {
+            pending.push_back({&cv, dz, x});
+            return hipSuccess;
+        }
+        return run_conv_wgrad(c, cv, dz, x);
+    }
+    WgradParams task(const Pending& pd) const {
+        WgradParams q = grouped_wgrad_params(*pd.cv, c.n, pd.dz, pd.x);
+        q.dw = c.f32(c.p->wg_off) + pd.cv->wg_off;
+        q.slab = c.f32(c.p->gslab_off) + pd.cv->gslab_off;
+        return q;
+    }
+    // `slot`: the stage whose table / schedule cache the 128 x 64 launch uses
+    hipError_t flush(int slot) {
+        if (pending.empty()) return hipSuccess;
+        vpd_plan* p = c.p;
+        hipError_t r = hipSuccess;
+        // persistent 128-wide tiles (conv_wgrad128_persistent_kernel) for every conv it takes: one launch per 18 problems
+        // (a ResNet-50 stage has up to 19: two balanced launches)
+        std::vector<Pending> rest;
+        {
+            std::vector<WgradParams> elig;
+            std::vector<double> fl;
+            for (const Pending& pd : pending) {
+                const WgradParams q = task(pd);
+                if (vpd_wgrad128_eligible(q)) { elig.push_back(q); fl.push_back(conv_flops(*pd.cv, c.n)); }
+                else rest.push_back(pd);
+            }
+            const int total = (int)elig.size();
+            const int nl = (total + 17) / 18;
+            int at = 0;
+            for (int l = 0; l < nl && r == hipSuccess; ++l) {
+                const int cnt = (total - at + (nl - l) - 1) / (nl - l);
+                double flops = 0.0;
+                for (int i = 0; i < cnt; ++i) flops += fl[at + i];
+                const int sl = (2 * slot + (l & 1)) & 7;
+                if (l >= 2) {      // more than 36 problems (ResNet-101's layer3): the table slots are reused -- new shapes per launch
+                    if (p->wg2_cache[sl]) { vpd_wgrad128_cache_free(p->wg2_cache[sl]); p->wg2_cache[sl] = nullptr; }
+                }
+                if (!p->wg2_cache[sl]) p->wg2_cache[sl] = vpd_wgrad128_cache_new();
+                TimeScope ts(p, c.s, 5, flops);
+                r = vpd_launch_wgrad128_group(elig.data() + at, cnt, p->wg2_cache[sl], c.ws + p->wg2_tbl_off[sl], c.s);
+                at += cnt;
+            }
+        }
+        size_t done = 0;
+        while (done < rest.size() && r == hipSuccess) {
+            WgradParams qs[12];
+            const int cnt = (int)std::min<size_t>(12, rest.size() - done);
+            double flops = 0.0;
+            // one launch of the 64 x 64 grouped kernel: one halo geometry (stage)
+            int take = 0;
+            for (int i = 0; i < cnt; ++i) {
+                if (i > 0 && rest[done + i].cv->Hout != rest[done].cv->Hout) break;
+                qs[take++] = task(rest[done + i]);
+                flops += conv_flops(*rest[done + i].cv, c.n);
+            }
+            {
+                TimeScope ts(p, c.s, 5, flops);
+                r = vpd_launch_wgrad_group(qs, take, c.s);
+            }
+            done += take;
+        }
+        pending.clear();
+        return r;
+    }
+    int unpack_bucket(int b) {
+        const vpd_plan* p = c.p;
+        int nb = (int)p->bmap_unpack[b].size() / 2;
+        if (lazy) nb = b == 3 ? p->nstem_unpack_blocks : 0;      // the stem's row-tap packing is undone here either way
+        if (nb > 0)
+            LCHECK(vpd_launch_unpack_grads(reinterpret_cast<const PackDesc*>(c.ws + p->desc_off), (int)p->descs.size(),
+                                           reinterpret_cast<const int*>(c.ws + p->bmap_unpack_off[b]), nb,
+                                           c.f32(p->wg_off), grads, c.s));
+        if (bucket_events && bucket_events[b]) LCHECK(hipEventRecord((hipEvent_t)bucket_events[b], c.s));
+        return 0;
+    }
+    // End of a stage's backward (called after every block): launch the stage's grouped weight gradients and hand its
+    // gradient bucket over -- except that layer4's (stage 3) wait for layer3's when wg_merge34: one launch then carries both
+    // stages (their tasks fill the chip together where each stage alone leaves CUs idle), and bucket 0 follows it.
+    int stage_end(int bi) {
+        const vpd_plan* p = c.p;
+        const BlockInfo& B = p->blocks[bi];
+        const bool last_of_stage = bi == 0 || p->blocks[bi - 1].stage != B.stage;
+        if (!last_of_stage) return 0;
+        if (p->wg_group && p->wg_merge34 && B.stage == 3 && bi > 0) { deferred_buckets.push_back(3 - B.stage); return 0; }
+        LCHECK(flush(B.stage));
+        for (int b : deferred_buckets)
+            if (unpack_bucket(b)) return -1;
+        deferred_buckets.clear();
+        if (bi > 0) return unpack_bucket(3 - B.stage);
+        return 0;
+    }
+};
+
+// One backward pass: the head, the blocks in reverse order, the stem.  d(out) of the current block is in G[gi]; a block
+// leaves d(out) of the previous one in G[gi] (identity: accumulated onto it) or in G[(gi + 2) % 3] (down-sampling: gi moves).
+struct Backward {
+    const Ctx& c;
+    float* grads;
+    WgradQueue wq;
+    bf16_t* G[3];
+    int gi = 0;
+    bool pool_pending = false;      // d(out) of the last block has not been written yet: d(pooled) is what there is
+    std::vector<char> bn2_sums_for;      // block bi's bn2 sums were taken by the next block's conv1 data gradient (BnSums)
+
+    Backward(const Ctx& c_, float* grads_, void** bucket_events, bool lazy)
+        : c(c_), grads(grads_), wq{c_, grads_, bucket_events, lazy},
+          G{c_.b16(c_.p->G_off[0]), c_.b16(c_.p->G_off[1]), c_.b16(c_.p->G_off[2])}, bn2_sums_for(c_.p->blocks.size(), 0) {}
+
+    const bf16_t* block_input(int bi) const { return bi == 0 ? c.b16(c.p->p0_off) : c.b16(c.p->blocks[bi - 1].out_off); }
+
+    int head() {
+        vpd_plan* p = c.p;
+        const int n = c.n;
+        hipStream_t s = c.s;
+        const float* params = c.params;
+        if (p->loss_scale != 1.f)      // (fp16 training: vpd_plan_set_loss_scale)
+            LCHECK(vpd_launch_scale(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->loss_scale, s));
+        const float* demb = c.f32(p->dpred_off);
+        if (p->motion) {
+            const LinInfo* L = p->dec;
+            // layer 5: pred = h2 W2^T + b
+            LCHECK(vpd_launch_sgemm(c.f32(p->dpred_off), c.f32(p->h2_off), grads + L[2].w_off, nullptr, L[2].out, L[2].in, n, 1, 0, 0, s));
+            LCHECK(vpd_launch_colsum(c.f32(p->dpred_off), n, L[2].out, grads + L[2].b_off, s));
+            LCHECK(vpd_launch_sgemm(c.f32(p->dpred_off), params + L[2].w_off, c.f32(p->dh2_off), nullptr, n, L[2].in, L[2].out, 0, 0, 0, s));
+            LCHECK(vpd_launch_relu_mask(c.f32(p->dh2_off), c.f32(p->h2_off), (long)n * 128, s));
+            LCHECK(vpd_launch_sgemm(c.f32(p->dh2_off), c.f32(p->h1_off), grads + L[1].w_off, nullptr, L[1].out, L[1].in, n, 1, 0, 0, s));
+            LCHECK(vpd_launch_colsum(c.f32(p->dh2_off), n, L[1].out, grads + L[1].b_off, s));
+            LCHECK(vpd_launch_sgemm(c.f32(p->dh2_off), params + L[1].w_off, c.f32(p->dh1_off), nullptr, n, L[1].in, L[1].out, 0, 0, 0, s));
+            LCHECK(vpd_launch_relu_mask(c.f32(p->dh1_off), c.f32(p->h1_off), (long)n * 128, s));
+            LCHECK(vpd_launch_sgemm(c.f32(p->dh1_off), c.f32(p->emb_off), grads + L[0].w_off, nullptr, L[0].out, L[0].in, n, 1, 0, 0, s));
+            LCHECK(vpd_launch_colsum(c.f32(p->dh1_off), n, L[0].out, grads + L[0].b_off, s));
+            LCHECK(vpd_launch_sgemm(c.f32(p->dh1_off), params + L[0].w_off, c.f32(p->demb_off), nullptr, n, L[0].in, L[0].out, 0, 0, 0, s));
+            demb = c.f32(p->demb_off);
+        }
+        LCHECK(vpd_launch_sgemm(demb, c.f32(p->pooled_off), grads + p->fc.w_off, nullptr, p->D, p->feat, n, 1, 0, 0, s));
+        LCHECK(vpd_launch_colsum(demb, n, p->D, grads + p->fc.b_off, s));
+        LCHECK(vpd_launch_sgemm(demb, params + p->fc.w_off, c.f32(p->dpooled_off), nullptr, n, p->feat, p->D, 0, 0, 0, s));
+        const StageInfo& S = p->stages[3];
+        // BasicBlock students: the last block's BatchNorm backward produces d(out) from d(pooled) itself (run_bn_bwd)
+        if (!p->bottleneck && !p->blocks.back().ds) pool_pending = true;
+        else LCHECK(vpd_launch_avgpool_bwd(c.f32(p->dpooled_off), S.H, S.W, p->feat, n, G[gi], s));
+        return 0;
+    }
+
+    // Conv `cv`'s data gradient dz -> dx, then the backward of the BatchNorm of `bc` (the conv whose output, after BatchNorm and
+    // ReLU, is cv's input) into dzb.  bc's sums ride in cv's data gradient when that launch takes them (mask_off: bc's ReLU bit
+    // map, vpd_plan_create's dgrad_sums); its BatchNorm launch then only finalizes and applies.
+    int inner_bn_bwd(const ConvInfo& cv, const bf16_t* dz, bf16_t* dx, const ConvInfo& bc, size_t mask_off, bf16_t* dzb) {
+        if (mask_off && dgrad_takes_sums(c, cv, 0)) {
+            const BnSums sm{c.b16(bc.z_off), c.u8(mask_off), c.bn_rows(bc.bn), nullptr, nullptr};
+            LCHECK(run_conv_dgrad(c, cv, dz, dx, 0, nullptr, nullptr, nullptr, &sm));
+            LCHECK(run_bn_bwd_apply(c, bc, dx, dzb, 1, grads, c.u8(mask_off)));
+        } else {
+            LCHECK(run_conv_dgrad(c, cv, dz, dx, 0));
+            LCHECK(run_bn_bwd(c, bc, dx, nullptr, dzb, 1, 0, grads, true));
+        }
+        return 0;
+    }
+
+    // BasicBlock students: block bi's conv1 data gradient produces d(out) of block bi-1 -- with a plain store when bi is a
+    // down-sampling block (its merged stride-2 launch), accumulated onto the identity path otherwise.  It takes the sums of block
+    // bi-1's bn2 (and of its 1x1 branch's BatchNorm, which sees the same g) when it can; that block's BatchNorm backward is then
+    // finalize + apply only.  Returns the sums to pass, or null, and sets bn2_sums_for[bi - 1].
+    const BnSums* prev_bn2_sums(int bi, BnSums& sm) {
+        if (bi == 0) return nullptr;
+        const BlockInfo& B = c.p->blocks[bi];
+        const BlockInfo& Bp = c.p->blocks[bi - 1];
+        if (!relu_bits_ok(c, Bp.c2)) return nullptr;
+        if (Bp.ds && !(vpd_switches().dgrad_sums_pair && c.fused(Bp.c2) && c.fused(Bp.cd) && Bp.c2.Co == Bp.cd.Co)) return nullptr;
+        if (!dgrad_takes_sums(c, B.c1, B.ds ? 0 : 1, Bp.ds)) return nullptr;      // (a stride-2 launch takes no second BatchNorm)
+        sm = BnSums{c.b16(Bp.c2.z_off), c.u8(Bp.mask_off), c.bn_rows(Bp.c2.bn), Bp.ds ? c.b16(Bp.cd.z_off) : nullptr,
+                    Bp.ds ? c.bn_rows(Bp.cd.bn) : nullptr};
+        bn2_sums_for[bi - 1] = true;
+        return &sm;
+    }
+
+    int basic_block(int bi) {
+        const BlockInfo& B = c.p->blocks[bi];
+        const StageInfo& S = c.p->stages[B.stage];
+        const bf16_t* xin = block_input(bi);
+        bf16_t* dout = G[gi];
+        bf16_t* da1 = G[(gi + 1) % 3];
+        bf16_t* dnew = G[(gi + 2) % 3];
+        bf16_t* dz2 = c.dz(B.c2, S.dz2_off[bi & 1]);
+        bf16_t* dz1 = c.dz(B.c1, S.dz1_off[bi & 1]);
+        bf16_t* dzd = B.ds ? c.dz(B.cd, S.dzd_off) : nullptr;
+        // plain (identity) blocks: ReLU mask from the forward's bit map; g = dout * mask is neither written back nor re-read --
+        // conv1's data gradient, which adds the identity path, masks dout itself (ConvParams::acc_mask)
+        const unsigned char* mbits = (!B.ds && relu_bits_ok(c, B.c2)) ? c.u8(B.mask_off) : nullptr;
+        // bn2 (+ReLU of the block output); leaves g = dout*[out>0] in dout
+        bool bn_pair = false;      // conv2's BatchNorm and the 1x1 branch's BatchNorm in one launch (same dy, same ReLU mask)
+        if (bn2_sums_for[bi]) {
+            // the next block's conv1 data gradient took the sums (a down-sampling block: both): one finalize + apply launch
+            LCHECK(run_bn_bwd_apply(c, B.c2, dout, dz2, 1, grads, c.u8(B.mask_off), B.ds ? &B.cd : nullptr, dzd));
+            bn_pair = B.ds;
+        } else if (B.ds && bn_bwd_pair_ok(c, B.c2, B.cd)) {
+            LCHECK(run_bn_bwd_pair(c, B.c2, B.cd, dout, c.b16(B.out_off), dz2, dzd, grads));
+            bn_pair = true;
+        } else {
+            LCHECK(run_bn_bwd(c, B.c2, dout, c.b16(B.out_off), dz2, 1, 1, grads, false, false, mbits,
+                              pool_pending ? c.f32(c.p->dpooled_off) : nullptr));
+            pool_pending = false;
+        }
+        LCHECK(wq.queue(B.c2, dz2, c.b16(B.a1_off)));
+        if (inner_bn_bwd(B.c2, dz2, da1, B.c1, B.mask1_off, dz1)) return -1;
+        LCHECK(wq.queue(B.c1, dz1, xin));
+        BnSums sm;
+        if (B.ds) {
+            if (!bn_pair) LCHECK(run_bn_bwd(c, B.cd, dout, nullptr, dzd, 1, 0, grads));
+            LCHECK(wq.queue(B.cd, dzd, xin));
+            if (conv_pair_ok(c, B.c1, B.cd, true)) {
+                // one launch: the 1x1 branch's data gradient is extra K-steps of the even-even class
+                LCHECK(run_conv_dgrad(c, B.c1, dz1, dnew, 0, &B.cd, dzd, nullptr, prev_bn2_sums(bi, sm)));
+            } else {
+                LCHECK(run_conv_dgrad(c, B.c1, dz1, dnew, 0));      // writes every input pixel (3x3 covers all classes)
+                LCHECK(run_conv_dgrad(c, B.cd, dzd, dnew, 1));      // adds onto the even-even pixels
+            }
+            gi = (gi + 2) % 3;
+        } else {
+            // dout holds g (or, with the bit map, d(out) and the mask is applied here): identity path + conv path
+            LCHECK(run_conv_dgrad(c, B.c1, dz1, dout, 1, nullptr, nullptr, mbits, mbits ? prev_bn2_sums(bi, sm) : nullptr));
+        }
+        return wq.stage_end(bi);
+    }
+
+    int bottleneck_block(int bi) {
+        const BlockInfo& B = c.p->blocks[bi];
+        const StageInfo& S = c.p->stages[B.stage];
+        const bf16_t* xin = block_input(bi);
+        bf16_t* dout = G[gi];
+        bf16_t* dnew = G[(gi + 2) % 3];
+        bf16_t* dz3 = c.dz(B.c3, S.dz3_off);
+        bf16_t* dz2 = c.dz(B.c2, S.dz2_off[bi & 1]);
+        bf16_t* dz1 = c.dz(B.c1, S.dz1_off[bi & 1]);
+        bf16_t* dzd = B.ds ? c.dz(B.cd, S.dzd_off) : nullptr;
+        // bn3 (+ReLU of the block output); leaves g = dout*[out>0] in dout -- or, for identity blocks with the ReLU bit map,
+        // leaves dout alone: conv1's data gradient masks it when it adds the identity path (as in the BasicBlock path)
+        const unsigned char* mb3 = (!B.ds && relu_bits_ok(c, B.c3)) ? c.u8(B.mask_off) : nullptr;
+        bool bn3_pair = false;      // down-sampling block: bn3 and the 1x1 branch's BatchNorm in one launch
+        if (B.ds && bneck_recompute2_ok(c, B)) {
+            LCHECK(run_conv3d_bn_bwd(c, B, xin, dout, c.u8(B.mask_off), dz3, dzd, grads));
+            bn3_pair = true;
+        } else if (B.ds && bn_bwd_pair_ok(c, B.c3, B.cd)) {
+            LCHECK(run_bn_bwd_pair(c, B.c3, B.cd, dout, c.b16(B.out_off), dz3, dzd, grads));
+            bn3_pair = true;
+        }
+        if (bneck_recompute_ok(c, B)) LCHECK(run_conv3_bn_bwd(c, B.c3, c.b16(B.a2_off), dout, mb3, dz3, grads));
+        else if (!bn3_pair) LCHECK(run_bn_bwd(c, B.c3, dout, c.b16(B.out_off), dz3, 1, 1, grads, false, false, mb3));
+        LCHECK(wq.queue(B.c3, dz3, c.b16(B.a2_off)));
+        // layer3 / layer4 (vpd_plan_create, dgrad_sums): the sums of bn2 / bn1 ride in the data gradients that produce their dy
+        if (inner_bn_bwd(B.c3, dz3, c.b16(c.p->T_off[0]), B.c2, B.mask2_off, dz2)) return -1;
+        LCHECK(wq.queue(B.c2, dz2, c.b16(B.a1_off)));
+        if (inner_bn_bwd(B.c2, dz2, c.b16(c.p->T_off[1]), B.c1, B.mask1_off, dz1)) return -1;
+        LCHECK(wq.queue(B.c1, dz1, xin));
+        if (B.ds) {
+            if (!bn3_pair) LCHECK(run_bn_bwd(c, B.cd, dout, nullptr, dzd, 1, 0, grads));
+            LCHECK(wq.queue(B.cd, dzd, xin));
+            LCHECK(run_conv_dgrad(c, B.c1, dz1, dnew, 0));      // 1x1 stride 1: writes every input pixel
+            LCHECK(run_conv_dgrad(c, B.cd, dzd, dnew, 1));      // adds onto the pixels the strided 1x1 reads
+            gi = (gi + 2) % 3;
+        } else {
+            // identity path + conv path = d(out) of the previous block
+            LCHECK(run_conv_dgrad(c, B.c1, dz1, dout, 1, nullptr, nullptr, mb3));
+        }
+        return wq.stage_end(bi);
+    }
+
+    int stem() {
+        const vpd_plan* p = c.p;
+        StemPoolBwdParams sb;
+        memset(&sb, 0, sizeof sb);
+        sb.dpool = G[gi]; sb.idx = c.u8(p->idx_off); sb.z = c.b16(p->z0_off);
+        sb.mean = c.bn_mean(p->stem.bn); sb.rstd = c.bn_rstd(p->stem.bn);
+        sb.scale = c.bn_scale(p->stem.bn); sb.shift = c.bn_shift(p->stem.bn);
+        sb.g = c.b16(p->g0_off); sb.partials = c.stat_rows();
+        sb.pooled = c.b16(p->p0_off); sb.ppad = 1;
+        sb.gamma_p = c.params + p->stem.bn.w_off; sb.beta_p = c.params + p->stem.bn.b_off;
+        sb.M = c.n * p->H0 * p->W0; sb.Hz = p->H0; sb.Wz = p->W0; sb.Ho = p->H1; sb.Wo = p->W1; sb.C = 64;
+        LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, c.params + p->stem.bn.w_off, grads + p->stem.bn.w_off,
+                                        grads + p->stem.bn.b_off, c.bn_coef(p->stem.bn), c.b16(p->dz0_off), c.s));
+        LCHECK(wq.queue(p->stem, c.b16(p->dz0_off), c.b16(p->xin_off)));
+        return wq.unpack_bucket(3);
+    }
+};
+
+}  // namespace
+
+// ---------------------------------------------------------------------------
+extern "C" int vpd_pack_weights(vpd_plan_t* p, const float* params, const float* bn_running, void* workspace,
+                                void* stream) {
+    if (!p || !workspace || !params) return fail("null argument");
+    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    Ctx c{p, ws, s, params, 1};
+    LCHECK(vpd_launch_pack_weights(reinterpret_cast<const PackDesc*>(ws + p->desc_off), (int)p->descs.size(),
+                                   reinterpret_cast<const int*>(ws + p->bmap_pack_off), (int)p->bmap_pack.size() / 2,
+                                   params, c.b16(p->arena_off), s));
+    if (bn_running)
+        for (BnInfo* b : p->bns)
+            LCHECK(vpd_launch_bn_fold(params + b->w_off, params + b->b_off, bn_running + b->rm_off,
+                                      bn_running + b->rv_off, kBnEps, c.bn_escale(*b), c.bn_eshift(*b), b->C, s));
+    return 0;
+}
+
+extern "C" int vpd_forward_eval(vpd_plan_t* p, const float* params, const float* x, int n, float* emb_out,
+                                const float* target, float* loss_step, double* loss_accum, void* workspace,
+                                void* stream) {
+    if (check_call(p, workspace, n)) return -1;
+    return run_eval_forward(p, params, x, n, emb_out, target, loss_step, loss_accum, (char*)workspace,
+                            (hipStream_t)stream);
+}
+
+extern "C" int vpd_forward_train(vpd_plan_t* p, const float* params, float* bn_running, const float* x,
+                                 const float* target, int n, float* emb_out, float* loss_step, double* loss_accum,
+                                 void* workspace, void* stream) {
+    if (check_call(p, workspace, n, 0)) return -1;
+    if (!p->train) return fail("plan was created with train=0");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    if (n == 0) {      // empty shard: no crops, no statistics update, zero loss (the running buffers stay as they are)
+        if (loss_step) HCHECK(hipMemsetAsync(loss_step, 0, sizeof(float), s));
+        return 0;
+    }
+    Ctx c{p, ws, s, params, n};
+    LCHECK(vpd_launch_zero_ranges(accumulator_zero_ranges(c), s));
+    if (x) LCHECK(vpd_launch_pack_input(x, n, p->c_in, p->H, p->W, c.b16(p->xin_off), p->xHp, p->xWp, 3, 8, s));
+    // stem: conv -> batch stats -> BN+ReLU+maxpool
+    LCHECK(run_conv_fwd(c, p->stem, c.b16(p->xin_off), c.b16(p->z0_off), 0, true, nullptr, nullptr, nullptr, 0));
+    LCHECK(run_bn_finalize(c, p->stem, bn_running));
+    LCHECK(vpd_launch_stem_pool(stem_pool_params(c, c.bn_scale(p->stem.bn), c.bn_shift(p->stem.bn), c.u8(p->idx_off)), s));
+    const bf16_t* cur = c.b16(p->p0_off);
+    for (auto& B : p->blocks) {
+        bf16_t* a1 = c.b16(B.a1_off);
+        bf16_t* outp = c.b16(B.out_off);
+        const bool pair = B.ds && conv_pair_ok(c, B.c1, B.cd, true);
+        if (pair) {      // conv1 and the down-sampling 1x1 in one launch (both read `cur`; statistics to their own rows)
+            const AltConv alt{&B.cd, c.b16(B.cd.z_off), nullptr, nullptr, 0};
+            LCHECK(run_conv_fwd(c, B.c1, cur, c.b16(B.c1.z_off), 0, true, nullptr, nullptr, nullptr, 0, &alt));
+        } else {
+            LCHECK(run_conv_train(c, B.c1, cur, bn_running));
+        }
+        LCHECK(run_bn_fwd(c, B.c1, bn_running, 0, nullptr, nullptr, a1, 1, B.mask1_off ? c.u8(B.mask1_off) : nullptr));
+        const bf16_t* last_in = a1;
+        if (p->bottleneck) {
+            last_in = c.b16(B.a2_off);
+            LCHECK(run_conv_train(c, B.c2, a1, bn_running));
+            LCHECK(run_bn_fwd(c, B.c2, bn_running, 0, nullptr, nullptr, c.b16(B.a2_off), 1, B.mask2_off ? c.u8(B.mask2_off) : nullptr));
+        }
+        // the block's last conv, its BatchNorm + residual + ReLU (and the down-sampling branch's conv and BatchNorm)
+        const ConvInfo& last = p->bottleneck ? B.c3 : B.c2;
+        unsigned char* mbits = p->relu_bits ? c.u8(B.mask_off) : nullptr;
+        if (bneck_recompute_ok(c, B)) {      // conv3 + bn3 + identity + ReLU: z3 is never stored
+            LCHECK(run_conv3_bn_fwd(c, B.c3, last_in, cur, outp, mbits, bn_running));
+        } else if (bneck_recompute2_ok(c, B)) {     // ... + the 1x1 branch and its BatchNorm: neither z3 nor zd is stored
+            LCHECK(run_conv3d_bn_fwd(c, B, cur, outp, mbits, bn_running));
+        } else {
+            LCHECK(run_conv_train(c, last, last_in, bn_running));
+            if (B.ds) {
+                if (!pair) LCHECK(run_conv_train(c, B.cd, cur, bn_running));
+                LCHECK(run_bn_fwd(c, last, bn_running, 2, c.b16(B.cd.z_off), &B.cd, outp, 1, mbits));
+            } else {
+                LCHECK(run_bn_fwd(c, last, bn_running, 1, cur, nullptr, outp, 1, mbits));
+            }
+        }
+        cur = outp;
+    }
+    return run_head(c, cur, emb_out, target, true, loss_step, loss_accum);
+}
+
+extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, int n, void** bucket_events,
+                            void* workspace, void* stream) {
+    if (check_call(p, workspace, n, 0)) return -1;
+    if (!p->train) return fail("plan was created with train=0");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const bool lazy = p->lazy_next;
+    p->lazy_next = false;
+    p->grads_in_scratch = lazy;
+    if (n == 0) {      // empty shard: the gradient of a sum over no crops is zero; every bucket is "ready" at once
+        // (lazy: the reducer sums the scratch ranges, and the optimizer step reads them there afterwards)
+        HCHECK(hipMemsetAsync(grads, 0, (size_t)p->nparam_padded * sizeof(float), s));
+        if (lazy) HCHECK(hipMemsetAsync(ws + p->wg_off, 0, (size_t)p->wg_elems * sizeof(float), s));
+        for (int b = 0; b < 4; ++b)
+            if (bucket_events && bucket_events[b]) HCHECK(hipEventRecord((hipEvent_t)bucket_events[b], s));
+        return 0;
+    }
+    Ctx c{p, ws, s, params, n};
+    // one launch zeroes the accumulator rows and every weight-gradient range the atomics kernel will add into
+    ZeroRanges zr = accumulator_zero_ranges(c);
+    auto dry = [&](const ConvInfo& cv) { (void)run_conv_wgrad(c, cv, nullptr, nullptr, &zr); };
+    for (auto& B : p->blocks) { dry(B.c1); dry(B.c2); if (p->bottleneck) dry(B.c3); if (B.ds) dry(B.cd); }
+    dry(p->stem);
+    if (zr.count >= ZR_MAX) {      // too many ranges (Bottleneck nets: 30-100 1x1 convs): zero the whole scratch in one range
+        const int k = p->fused_bn ? 2 : 1;
+        zr.ptr[k] = c.f32(p->wg_off); zr.n4[k] = (long)(p->wg_elems + 3) / 4; zr.count = k + 1;
+    }
+    LCHECK(vpd_launch_zero_ranges(zr, s));
+
+    Backward bw(c, grads, bucket_events, lazy);
+    if (bw.head()) return -1;
+    for (int bi = (int)p->blocks.size() - 1; bi >= 0; --bi)
+        if (p->bottleneck ? bw.bottleneck_block(bi) : bw.basic_block(bi)) return -1;
+    return bw.stem();
+}
+
+extern "C" int vpd_graph_capture_eval(vpd_plan_t* p, const float* params, const float* x, int n, float* emb_out,
+                                      void* workspace, void* stream) {
+    if (check_call(p, workspace, n)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    for (size_t i = 0; i < p->graphs.size(); ++i)
+        if (p->graphs[i].n == n) {
+            (void)hipGraphExecDestroy(p->graphs[i].e);
+            (void)hipGraphDestroy(p->graphs[i].g);
+            p->graphs.erase(p->graphs.begin() + i);
+            break;
+        }
+    HCHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    const int rc = run_eval_forward(p, params, x, n, emb_out, nullptr, nullptr, nullptr, (char*)workspace, s);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(s, &g);
+    if (rc) { if (g) (void)hipGraphDestroy(g); return -1; }
+    if (e != hipSuccess) return fail("hipStreamEndCapture", e);
+    hipGraphExec_t ge = nullptr;
+    e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
+    if (e != hipSuccess) { (void)hipGraphDestroy(g); return fail("hipGraphInstantiate", e); }
+    p->graphs.push_back({n, g, ge});
+    return 0;
+}
+
+extern "C" int vpd_graph_launch_eval(vpd_plan_t* p, int n, void* stream) {
+    for (auto& g : p->graphs)
+        if (g.n == n) {
+            HCHECK(hipGraphLaunch(g.e, (hipStream_t)stream));
+            return 0;
+        }
+    return fail("no captured eval graph for this batch size");
+}
