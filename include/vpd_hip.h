@@ -129,6 +129,51 @@ int vpd_plan_adamw_step(vpd_plan_t* plan, float* params, const float* grads, flo
  * and vpd_plan_adamw_step reads gradients x 1 / scale.  A caller that reads the flat gradient buffer itself divides by the scale. */
 int vpd_plan_set_loss_scale(vpd_plan_t* plan, float scale);
 
+/* ---- dynamic loss scaling, decided on the device ----
+ * torch.cuda.amp.GradScaler() at its defaults is what the reference trains with (train_vpd_model.py:105; scaler.scale(loss)
+ * .backward(); scaler.step(optimizer); scaler.update(): models/util.py:55-57): look for inf / NaN in the gradients, skip the
+ * optimizer step when one is found and multiply the scale by the backoff factor, multiply it by the growth factor after
+ * `growth_interval` clean steps in a row.  Here the whole decision lives in one block of DEVICE memory owned by the caller
+ * (32 bytes, 16-byte aligned); every entry point below reads and writes it in stream order and none synchronises the host. */
+typedef struct vpd_scale_state {
+    float scale;                 /* the loss scale of the next backward pass / optimizer step */
+    unsigned int found;          /* non-zero: an inf or NaN was seen in the gradients of the step in flight */
+    int growth_tracker;          /* clean steps in a row since the scale last changed */
+    int applied_steps;           /* optimizer steps actually applied (the `step` of AdamW's bias corrections, 0-based) */
+    int skipped_steps;           /* optimizer steps skipped because of a non-finite gradient */
+    int reserved[3];
+} vpd_scale_state;
+
+/* scaler.scale(loss) of models/util.py:55 with the scale on the device: while `state` is set, vpd_backward multiplies
+ * d(loss)/d(pred) by state->scale as it stands when the pass runs, instead of by the host value of vpd_plan_set_loss_scale
+ * (which keeps its meaning once `state` is NULL again).  NULL switches back. */
+int vpd_plan_set_scale_state(vpd_plan_t* plan, const vpd_scale_state* state);
+
+/* The inf / NaN search of scaler.step() (models/util.py:56; torch's _amp_foreach_non_finite_check_and_unscale_): ORs 1 into
+ * state->found if any gradient the optimizer step of `plan` is about to read is not finite.  After a lazy backward
+ * (vpd_plan_grads_pending() == 1) these are the conv weight gradients in the plan's scratch plus the ranges of `grads` that are
+ * not conv weights (BatchNorm, fc, motion head, the stem conv); otherwise grads[0 .. numel).  Elements of `grads` beyond the
+ * plan's vpd_plan_param_numel are checked in both cases.  Under data parallelism call it after the all-reduce. */
+int vpd_plan_check_grads(vpd_plan_t* plan, const float* grads, long long numel, vpd_scale_state* state, void* workspace,
+                         void* stream);
+/* The same kernel over one plain range x[0 .. n) (any alignment, n >= 0). */
+int vpd_op_check_finite(const float* x, long long n, vpd_scale_state* state, void* stream);
+
+/* optimizer.step() as scaler.step(optimizer) runs it (models/util.py:56): vpd_adamw_step / vpd_plan_adamw_step with the gradients
+ * read x 1 / state->scale, the 1-based step of the bias corrections taken as state->applied_steps + 1 -- and NOTHING written
+ * (parameters, moments, packed weights) when state->found is set.  Neither touches `state`: vpd_scale_state_update does. */
+int vpd_adamw_step_scaled(float* params, const float* grads, float* adam_m, float* adam_v, long long numel, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, const vpd_scale_state* state,
+                          void* stream);
+int vpd_plan_adamw_step_scaled(vpd_plan_t* plan, float* params, const float* grads, float* adam_m, float* adam_v,
+                               long long numel, double lr, double beta1, double beta2, double eps, double weight_decay,
+                               const vpd_scale_state* state, void* workspace, void* stream);
+
+/* scaler.update() of models/util.py:57, torch's rule (_amp_update_scale_) without a clamp: found set -> scale *= backoff,
+ * growth_tracker = 0, skipped_steps += 1; else applied_steps += 1, growth_tracker += 1 and, when it reaches growth_interval,
+ * scale *= growth, growth_tracker = 0.  Then found = 0. */
+int vpd_scale_state_update(vpd_scale_state* state, float growth, float backoff, int growth_interval, void* stream);
+
 /* Lazy gradients for the fused train step (reference: models/util.py:50-58, where nothing looks at .grad between
  * loss.backward() and optimizer.step()).  vpd_plan_set_lazy_grads(plan, 1) arms the NEXT vpd_backward: the conv weight
  * gradients then stay in the kernels' own fp32 scratch layout and vpd_plan_adamw_step reads them there, so the layout pass

@@ -46,10 +46,17 @@ def get_args():
     parser.add_argument('--dtype', default='bf16', choices=['bf16', 'fp16'],
                         help='(this build) element type of the HIP path: bf16 (default, no loss scaling) or fp16 -- the reference\'s own '
                              'GPU precision (fp16 autocast + GradScaler), here with a static loss scale (vpd_amd.models.util.LossScaler)')
+    parser.add_argument('--loss_scale', default='static', choices=['static', 'dynamic'],
+                        help='(this build, --dtype fp16 only) static: a fixed loss scale of 256 (default); dynamic: the reference\'s '
+                             'GradScaler() -- steps with inf / NaN gradients are skipped and the scale halved, doubled after 2000 '
+                             'clean steps -- decided on the device (vpd_amd.models.util.DynamicLossScaler)')
     parser.add_argument('--no_augment', action='store_true',
                         help='escape hatch: fp32 batches from the CPU loaders with h-flips only -- NOT the reference '
                              'recipe, whose datasets always augment (vpd_dataset/common.py:85-92)')
-    return parser.parse_args()
+    args = parser.parse_args()
+    if args.loss_scale == 'dynamic' and args.dtype != 'fp16':
+        parser.error('--loss_scale dynamic needs --dtype fp16 (bf16 trains without a loss scale)')
+    return args
 
 
 def get_moving_avg_loss(losses, n, key):
@@ -71,7 +78,7 @@ def load_dataset(dataset, dataset_kwargs, emb_dir, penn_dir, no_test_video):
 
 def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, motion, encoder_arch, save_dir,
          model_select_window, checkpoint_frequency, pretrained, emb_dir, penn_dir, no_test_video, min_pose_score,
-         synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16'):
+         synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static'):
     device = 'cuda'
     # The reference builds train AND val datasets with augment=True (vpd_dataset/single_frame.py:267-272,
     # common.py:85-92): ColorJitter, mask noise, RandomResizedCrop and flips are part of the recipe, so they are the
@@ -147,7 +154,9 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         torch.distributed.broadcast(encoder.engine.params, 0)
         torch.distributed.broadcast(encoder.engine.bn_running, 0)
         encoder.engine.mark_weights_changed()
-    optimizer, scaler = trainer.get_optimizer(learning_rate)
+    optimizer, scaler = trainer.get_optimizer(learning_rate, loss_scale='dynamic' if loss_scale == 'dynamic' else None)
+    dynamic = loss_scale == 'dynamic'
+    skipped_before = 0
 
     if rank == 0:
         store_json(os.path.join(save_dir, 'config.json'), {
@@ -155,7 +164,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
             'use_flow': flow_img is not None, 'motion': motion,
             'embed_time': motion,      # apply_vpd_model.py:102 reads this key; the reference never writes it
             'emb_dim': emb_dim, 'encoder_arch': encoder_arch, 'rgb_mean_std': rgb_mean_std,
-            'dtype': dtype,            # not in the reference: element type of the HIP path (bf16 | fp16 + static loss scale)
+            'dtype': dtype,            # not in the reference: element type of the HIP path (bf16 | fp16 + a loss scale)
+            'loss_scale': loss_scale if dtype == 'fp16' else None,      # fp16: static (256) | dynamic (GradScaler's rule)
             # not in the reference: which input pipeline produced the loss curves
             'augment': 'device: ColorJitter + mask noise + RandomResizedCrop + flip (reference recipe)' if gpu_augment
                        else 'cpu: h-flip only (--no_augment)'})
@@ -175,7 +185,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         if rank == 0:
             print('Epoch {} - train loss: {:0.4f} [avg: {:0.4f}] val loss: {:0.4f} [avg: {:0.4f}]'.format(
                 epoch, train_loss, get_moving_avg_loss(losses, model_select_window, 'train'), val_loss,
-                moving_avg_val_loss))
+                moving_avg_val_loss) + ('' if not dynamic else ' loss scale: {:g} skipped steps: {}'.format(
+                    scaler.get_scale(), scaler.skipped_steps - skipped_before)))
             store_json(loss_file, losses)
             if moving_avg_val_loss < best_val_loss:
                 print('New best epoch!')
@@ -183,6 +194,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
             if checkpoint_frequency is not None and epoch % checkpoint_frequency == 0:
                 print('Saving checkpoint: {}'.format(epoch))
                 trainer.save_model(save_dir, 'epoch{:04d}'.format(epoch))
+        if dynamic:
+            skipped_before = scaler.skipped_steps
         best_val_loss = min(moving_avg_val_loss, best_val_loss)
     if rank == 0:
         print('Saving last epoch: {}'.format(epoch))

@@ -9,9 +9,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VPD_LIB_PATH: A/B another build of the same ABI on the same GPU (devices differ by several % in clocks)
 LIB_PATH = os.environ.get("VPD_LIB_PATH") or os.path.join(_HERE, "libvpdhip.so")
-# the same sources built with fp16 elements (vpd_amd/csrc/Makefile, common.h "Element type"): inference only
+# the same sources built with fp16 elements (vpd_amd/csrc/Makefile, common.h "Element type"): training and inference
 LIB_PATH_F16 = os.environ.get("VPD_LIB_PATH_F16") or os.path.join(_HERE, "libvpdhip_f16.so")
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 c_int_p = C.POINTER(C.c_int)
 c_ll_p = C.POINTER(C.c_longlong)
@@ -53,6 +53,14 @@ SIGNATURES = {
     "vpd_plan_sync_errors": (C.c_int, [vp, vp, vp, C.POINTER(C.c_uint)]),
     "vpd_plan_set_lazy_grads": (C.c_int, [vp, C.c_int]),
     "vpd_plan_set_loss_scale": (C.c_int, [vp, C.c_float]),
+    "vpd_plan_set_scale_state": (C.c_int, [vp, vp]),
+    "vpd_plan_check_grads": (C.c_int, [vp, vp, C.c_longlong, vp, vp, vp]),
+    "vpd_op_check_finite": (C.c_int, [vp, C.c_longlong, vp, vp]),
+    "vpd_adamw_step_scaled": (C.c_int, [vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double,
+                                        C.c_double, vp, vp]),
+    "vpd_plan_adamw_step_scaled": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double,
+                                             C.c_double, vp, vp, vp]),
+    "vpd_scale_state_update": (C.c_int, [vp, C.c_float, C.c_float, C.c_int, vp]),
     "vpd_plan_bucket_scratch_range": (C.c_int, [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "vpd_plan_grads_pending": (C.c_int, [vp]),
     "vpd_plan_materialize_grads": (C.c_int, [vp, vp, vp, vp]),
@@ -82,7 +90,7 @@ class VpdHipError(RuntimeError):
 
 
 def lib(dtype="bf16"):
-    """Load libvpdhip.so (dtype "bf16": training and inference) or libvpdhip_f16.so ("fp16": inference), once each.
+    """Load libvpdhip.so (dtype "bf16": training and inference) or libvpdhip_f16.so ("fp16": the same, behind a loss scaler), once each.
     Raises -- never falls back -- when the library is absent, lacks a symbol or was built for another element type."""
     if dtype in _libs:
         return _libs[dtype]

@@ -8,7 +8,7 @@
 
 // Element type of activations / packed weights / activation gradients.  The library is built twice from these sources
 // (vpd_amd/csrc/Makefile): libvpdhip.so with bf16 elements (training and inference), libvpdhip_f16.so with -DVPD_ELEM_F16 = IEEE fp16
-// elements for INFERENCE (apply_vpd_model.py --dtype fp16): the reference's own GPU precision (fp16 autocast, train_vpd_model.py:79),
+// elements (--dtype fp16; training behind a loss scaler, and inference): the reference's own GPU precision (fp16 autocast, train_vpd_model.py:79),
 // the same MFMA rate (v_mfma_f32_16x16x32_f16), 8x finer rounding (11 significant bits against 8).  The type NAMES stay bf16_t /
 // bf16x8 in both builds; every conversion goes through bf2f / f2bf / pack2bf below and every matrix instruction through VPD_MFMA16.
 #ifdef VPD_ELEM_F16

@@ -1,5 +1,6 @@
 // Embedding head: global average pool, the fc / motion-MLP linears (small fp32
 // GEMMs, <0.1 % of the FLOPs), sum-MSE loss and its gradient.
+#include "../../include/vpd_hip.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -272,5 +273,18 @@ hipError_t vpd_launch_scale(float* x, long n, float s, hipStream_t stream) {
     long g = (n + 255) / 256;
     if (g > 1024) g = 1024;
     hipLaunchKernelGGL(scale_kernel, dim3((unsigned)g), dim3(256), 0, stream, x, n, s);
+    return hipGetLastError();
+}
+// ... with the scale read from a dynamic scaler's device block as it stands when the pass runs (vpd_plan_set_scale_state): the
+// host does not know it after a step the device decided to skip
+__global__ __launch_bounds__(256) void scale_by_state_kernel(float* x, long n, const vpd_scale_state* st) {
+    const float s = st->scale;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= s;
+}
+hipError_t vpd_launch_scale_by_state(float* x, long n, const vpd_scale_state* st, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    long g = (n + 255) / 256;
+    if (g > 1024) g = 1024;
+    hipLaunchKernelGGL(scale_by_state_kernel, dim3((unsigned)g), dim3(256), 0, stream, x, n, st);
     return hipGetLastError();
 }

@@ -69,6 +69,15 @@ struct PackDesc {                       // one convolution's weight tensors
     long long numel;                    // stem == 2: length of the range at src_off
 };
 struct AdamHyper { float decay, omb1, b2, omb2, step_size, inv_sqrt_bc2, eps, gscale; };      // gscale: 1 / loss scale (fp16 training), else 1
+// ... under a dynamic loss scaler (vpd_scale_state, include/vpd_hip.h): step_size, inv_sqrt_bc2 and gscale come from the device block
+struct vpd_scale_state;
+struct AdamHyperDyn { AdamHyper h; const vpd_scale_state* st; double lr, b1, b2; };
+#define FR_MAX 96
+struct FiniteRanges {                   // float ranges of any alignment and length (vpd_launch_check_finite)
+    const float* ptr[FR_MAX];
+    long n[FR_MAX];
+    int count;
+};
 
 hipError_t vpd_launch_conv(const ConvParams& p, hipStream_t stream);
 hipError_t vpd_launch_scale(float* x, long n, float s, hipStream_t stream);      // head.hip: x *= s (the loss scale on d(loss)/d(pred))
@@ -171,6 +180,16 @@ hipError_t vpd_launch_unpack_grads(const PackDesc* d_descs, int ndesc, const int
                                    const float* wg, float* grads, hipStream_t s);
 hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
                             double eps, double wd, int step, hipStream_t s, float gscale = 1.f);
+// dynamic loss scaling (vpd_scale_state): the two AdamW launches reading scale / applied steps / the non-finite word from the
+// device block, the inf / NaN search, the update rule; head.hip: d(loss)/d(pred) x the block's scale
+hipError_t vpd_launch_adamw_pack_scaled(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
+                                        float* m, float* v, bf16_t* arena, double lr, double b1, double b2, double eps,
+                                        double wd, const vpd_scale_state* st, hipStream_t s, const float* wg = nullptr);
+hipError_t vpd_launch_adamw_scaled(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
+                                   double eps, double wd, const vpd_scale_state* st, hipStream_t s);
+hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, hipStream_t s);
+hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float backoff, int interval, hipStream_t s);
+hipError_t vpd_launch_scale_by_state(float* x, long n, const vpd_scale_state* st, hipStream_t stream);
 
 #define ZR_MAX 16
 struct ZeroRanges {                     // 16-byte aligned ranges, lengths in float4

@@ -1,5 +1,6 @@
 // Layout conversion at the reference boundary (fp32 NCHW / OIHW <-> internal
 // bf16 NHWC / packed-tap weights) and the fused AdamW step.
+#include "../../include/vpd_hip.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -262,8 +263,32 @@ static AdamHyper adam_hyper(double lr, double b1, double b2, double eps, double 
                      (float)(1.0 / sqrt(bc2)), (float)eps, gscale};
 }
 
+// H: AdamHyper as the host computed it (every launch without a dynamic loss scaler), or AdamHyperDyn -- the same plus the
+// scaler's device block (vpd_scale_state, include/vpd_hip.h): gradient factor 1 / scale, bias corrections from the number of
+// steps APPLIED so far, which only the device knows after a skipped step (in double, rounded to float: adam_hyper), and when the
+// non-finite word is set the launch writes nothing at all -- scaler.step(optimizer) of models/util.py:56.
+static __device__ __forceinline__ const AdamHyper& adam_live(const AdamHyper& h, bool& live) {
+    live = true;
+    return h;
+}
+static __device__ __forceinline__ AdamHyper adam_live(const AdamHyperDyn& d, bool& live) {
+    AdamHyper h = d.h;
+    live = d.st->found == 0;
+    if (live) {
+        const double step = (double)(d.st->applied_steps + 1);
+        h.step_size = (float)(d.lr / (1.0 - pow(d.b1, step)));
+        h.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(d.b2, step)));
+        h.gscale = 1.0f / d.st->scale;
+    }
+    return h;
+}
+
+template <class H>
 __global__ __launch_bounds__(256) void adamw_kernel(float4* p, const float4* g, float4* m, float4* v, long n4,
-                                                    const AdamHyper h) {
+                                                    const H hh) {
+    bool live;
+    const AdamHyper h = adam_live(hh, live);
+    if (!live) return;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
         adamw4(pp, gg, mm, vv, h);
@@ -276,8 +301,22 @@ hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n
     const long n4 = n / 4;
     long gsz = (n4 + 255) / 256;
     if (gsz > 4096) gsz = 4096;
-    hipLaunchKernelGGL(adamw_kernel, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, (float4*)p, (const float4*)g,
+    hipLaunchKernelGGL(adamw_kernel<AdamHyper>, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, (float4*)p, (const float4*)g,
                        (float4*)m, (float4*)v, n4, adam_hyper(lr, b1, b2, eps, wd, step, gscale));
+    return hipGetLastError();
+}
+// (step 1 / gscale 1 are place-holders: adam_live replaces step_size, inv_sqrt_bc2 and gscale from the device block)
+static AdamHyperDyn adam_hyper_dyn(double lr, double b1, double b2, double eps, double wd, const vpd_scale_state* st) {
+    return AdamHyperDyn{adam_hyper(lr, b1, b2, eps, wd, 1, 1.f), st, lr, b1, b2};
+}
+hipError_t vpd_launch_adamw_scaled(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
+                                   double eps, double wd, const vpd_scale_state* st, hipStream_t s) {
+    if (n % 4) return hipErrorInvalidValue;
+    const long n4 = n / 4;
+    long gsz = (n4 + 255) / 256;
+    if (gsz > 4096) gsz = 4096;
+    hipLaunchKernelGGL(adamw_kernel<AdamHyperDyn>, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, (float4*)p,
+                       (const float4*)g, (float4*)m, (float4*)v, n4, adam_hyper_dyn(lr, b1, b2, eps, wd, st));
     return hipGetLastError();
 }
 
@@ -302,10 +341,14 @@ static __device__ __forceinline__ float4 adamw_gather_g(const float* wgc, int Co
     }
     return float4{v[0], v[1], v[2], v[3]};
 }
+template <class H>      // AdamHyper | AdamHyperDyn (a skipped step leaves the packed weights alone too: they already hold these parameters)
 __global__ __launch_bounds__(256) void adamw_pack_kernel(const PackDesc* descs, const int* blockmap, float* p,
                                                          const float* g, float* m, float* v, bf16_t* arena,
-                                                         const AdamHyper h, const float* wg) {
+                                                         const H hh, const float* wg) {
     __shared__ unsigned short tile[32][32 * 9 + 2];      // the new weights, already rounded to bf16 (18 KB: 8 blocks per CU)
+    bool live;
+    const AdamHyper h = adam_live(hh, live);
+    if (!live) return;
     const PackDesc d = descs[blockmap[2 * blockIdx.x]];
     const int chunk = blockmap[2 * blockIdx.x + 1];
     const int khw = d.kh * d.kw;
@@ -375,8 +418,91 @@ hipError_t vpd_launch_adamw_pack(const PackDesc* d_descs, const int* d_blockmap,
     if ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) |
          reinterpret_cast<size_t>(v)) & 15)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adamw_pack_kernel, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v, arena,
+    hipLaunchKernelGGL(adamw_pack_kernel<AdamHyper>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v, arena,
                        adam_hyper(lr, b1, b2, eps, wd, step, gscale), wg);
+    return hipGetLastError();
+}
+hipError_t vpd_launch_adamw_pack_scaled(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
+                                        float* m, float* v, bf16_t* arena, double lr, double b1, double b2, double eps,
+                                        double wd, const vpd_scale_state* st, hipStream_t s, const float* wg) {
+    if ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) |
+         reinterpret_cast<size_t>(v)) & 15)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(adamw_pack_kernel<AdamHyperDyn>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v,
+                       arena, adam_hyper_dyn(lr, b1, b2, eps, wd, st), wg);
+    return hipGetLastError();
+}
+
+// ---- dynamic loss scaling (vpd_scale_state): the inf / NaN search over the gradients and the scale's update rule ----
+// A float is inf or NaN exactly when its eight exponent bits are all ones.
+static __device__ __forceinline__ unsigned nonfinite1(float f) {
+    return (__float_as_uint(f) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+}
+static __device__ __forceinline__ unsigned nonfinite4(const float4& f) {
+    return nonfinite1(f.x) | nonfinite1(f.y) | nonfinite1(f.z) | nonfinite1(f.w);
+}
+// Every range of `r` (float ranges of any alignment) in one launch: a range's 16-byte aligned middle is read with 16-byte loads,
+// four in flight per thread, the up to three floats in front of it and behind it one by one.  A wave votes; a block issues ONE
+// atomic OR, and only when one of its waves found something -- a clean step (all of them but a handful) writes nothing.
+__global__ __launch_bounds__(256) void check_finite_kernel(const FiniteRanges r, unsigned* found) {
+    __shared__ unsigned blk;
+    if (threadIdx.x == 0) blk = 0u;
+    __syncthreads();
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nth = (long)gridDim.x * 256;
+    unsigned bad = 0u;
+    for (int k = 0; k < r.count; ++k) {
+        const float* x = r.ptr[k];
+        const long n = r.n[k];
+        long head = (long)((16 - (reinterpret_cast<size_t>(x) & 15)) & 15) >> 2;
+        if (head > n) head = n;
+        const float4* x4 = reinterpret_cast<const float4*>(x + head);
+        const long n4 = (n - head) >> 2;
+        long i = tid;
+        for (; i + 3 * nth < n4; i += 4 * nth) {
+            const float4 a = x4[i], b = x4[i + nth], c = x4[i + 2 * nth], d = x4[i + 3 * nth];
+            bad |= nonfinite4(a) | nonfinite4(b) | nonfinite4(c) | nonfinite4(d);
+        }
+        for (; i < n4; i += nth) bad |= nonfinite4(x4[i]);
+        const long tail = head + (n4 << 2);
+        if (tid < head) bad |= nonfinite1(x[tid]);
+        if (tid < n - tail) bad |= nonfinite1(x[tail + tid]);
+    }
+    if (__any(bad != 0u) && (threadIdx.x & 63) == 0) blk = 1u;      // (every writer stores the same value)
+    __syncthreads();
+    if (threadIdx.x == 0 && blk) atomicOr(found, 1u);
+}
+hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, hipStream_t s) {
+    long total = 0;
+    for (int k = 0; k < r.count; ++k) total += r.n[k] > 0 ? r.n[k] : 0;
+    if (r.count <= 0 || total == 0) return hipSuccess;
+    long gsz = (total / 4 + 255) / 256;      // at most 2048 blocks = 8 per CU: enough loads in flight for the fabric
+    if (gsz > 2048) gsz = 2048;
+    hipLaunchKernelGGL(check_finite_kernel, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, r, &st->found);
+    return hipGetLastError();
+}
+
+// scaler.update() (models/util.py:57) on one thread, torch's rule (_amp_update_scale_: a growth that would leave fp32's range is
+// not taken, nothing else is clamped)
+__global__ void scale_update_kernel(vpd_scale_state* st, float growth, float backoff, int interval) {
+    if (st->found) {
+        st->scale *= backoff;
+        st->growth_tracker = 0;
+        st->skipped_steps += 1;
+    } else {
+        st->applied_steps += 1;
+        const int t = st->growth_tracker + 1;
+        if (t == interval) {
+            const float grown = st->scale * growth;
+            if (grown <= 3.4028235e38f) st->scale = grown;
+            st->growth_tracker = 0;
+        } else {
+            st->growth_tracker = t;
+        }
+    }
+    st->found = 0u;
+}
+hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float backoff, int interval, hipStream_t s) {
+    hipLaunchKernelGGL(scale_update_kernel, dim3(1), dim3(1), 0, s, st, growth, backoff, interval);
     return hipGetLastError();
 }
 

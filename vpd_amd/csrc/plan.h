@@ -124,6 +124,7 @@ struct vpd_plan {
                                 // data-parallel creation flag VPD_TRAIN_EARLY_BUCKET0: per stage)
     bool early_bucket0 = false;
     float loss_scale = 1.f;     // vpd_plan_set_loss_scale: fp16 training (the reference's GradScaler, models/util.py:55-57)
+    const vpd_scale_state* scale_state = nullptr;      // vpd_plan_set_scale_state: the scale is read on the device instead (dynamic loss scaling)
     size_t wg2_tbl_off[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // task tables of the persistent weight-gradient launches (two per stage)
     void* wg2_cache[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // optional per-kernel-class timing (bench.py roofline): HIP events around every conv launch

@@ -24,7 +24,7 @@ int fail(const char* what, hipError_t e) {
 
 extern "C" const char* vpd_last_error(void) { return g_err.c_str(); }
 extern "C" const char* vpd_elem_dtype(void) { return VPD_ELEM_NAME; }      // "bf16" (libvpdhip.so) or "fp16" (libvpdhip_f16.so)
-extern "C" int vpd_abi_version(void) { return 2; }      // 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes)
+extern "C" int vpd_abi_version(void) { return 3; }      // 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state)
 
 namespace {
 
@@ -565,6 +565,118 @@ extern "C" int vpd_plan_set_loss_scale(vpd_plan_t* p, float scale) {
     if (!p) return fail("null plan");
     if (!(scale > 0.f) || !(scale < 3.0e38f)) return fail("loss scale must be a positive finite number");
     p->loss_scale = scale;
+    return 0;
+}
+
+// ---- dynamic loss scaling: every decision is taken on the device, from the caller's vpd_scale_state block (include/vpd_hip.h) ----
+extern "C" int vpd_plan_set_scale_state(vpd_plan_t* p, const vpd_scale_state* state) {
+    if (!p) return fail("null plan");
+    if (reinterpret_cast<size_t>(state) & 3) return fail("scale state must be 4-byte aligned");
+    p->scale_state = state;
+    return 0;
+}
+
+// One launch over the ranges (more than FR_MAX of them: one launch per FR_MAX)
+namespace {
+struct RangeList {
+    FiniteRanges r;
+    vpd_scale_state* st;
+    hipStream_t s;
+    RangeList(vpd_scale_state* st_, hipStream_t s_) : st(st_), s(s_) { memset(&r, 0, sizeof r); }
+    hipError_t flush() {
+        const hipError_t e = vpd_launch_check_finite(r, st, s);
+        r.count = 0;
+        return e;
+    }
+    hipError_t add(const float* x, long long n) {
+        if (n <= 0) return hipSuccess;
+        if (r.count == FR_MAX) {
+            const hipError_t e = flush();
+            if (e != hipSuccess) return e;
+        }
+        r.ptr[r.count] = x;
+        r.n[r.count++] = (long)n;
+        return hipSuccess;
+    }
+};
+}  // namespace
+
+extern "C" int vpd_op_check_finite(const float* x, long long n, vpd_scale_state* state, void* stream) {
+    if (!x || !state) return fail("null argument");
+    if (n < 0) return fail("negative length");
+    if (reinterpret_cast<size_t>(x) & 3) return fail("x must be 4-byte aligned");
+    RangeList rl(state, (hipStream_t)stream);
+    LCHECK(rl.add(x, n));
+    LCHECK(rl.flush());
+    return 0;
+}
+
+// Exactly what the optimizer step that follows will read: vpd_plan_adamw_step_scaled takes the conv weight gradients from the
+// scratch while grads_in_scratch (everything behind the stem's: the stem is always unpacked into the flat buffer) and the ranges
+// of the `stem == 2` descriptors from `grads`; otherwise all of `grads`.  The conv ranges of `grads` are STALE after a lazy
+// backward and are not looked at.
+extern "C" int vpd_plan_check_grads(vpd_plan_t* p, const float* grads, long long numel, vpd_scale_state* state, void* workspace,
+                                    void* stream) {
+    if (!p || !grads || !state || !workspace) return fail("null argument");
+    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
+    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
+    if (reinterpret_cast<size_t>(grads) & 15) return fail("grads must be 16-byte aligned");
+    RangeList rl(state, (hipStream_t)stream);
+    if (p->grads_in_scratch) {
+        const long long stem_end = (long long)p->stem.ntaps * p->stem.Co * p->stem.Kc;
+        LCHECK(rl.add(reinterpret_cast<const float*>((char*)workspace + p->wg_off) + stem_end, p->wg_elems - stem_end));
+        for (const PackDesc& d : p->descs)
+            if (d.stem == 2) LCHECK(rl.add(grads + d.src_off, d.numel));
+        LCHECK(rl.add(grads + p->nparam_padded, numel - p->nparam_padded));
+    } else {
+        LCHECK(rl.add(grads, numel));
+    }
+    LCHECK(rl.flush());
+    return 0;
+}
+
+extern "C" int vpd_adamw_step_scaled(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
+                                     double lr, double beta1, double beta2, double eps, double weight_decay,
+                                     const vpd_scale_state* state, void* stream) {
+    if (!params || !grads || !adam_m || !adam_v || !state) return fail("null argument");
+    if (numel % 4) return fail("numel must be a multiple of 4 (use vpd_plan_param_numel)");
+    LCHECK(vpd_launch_adamw_scaled(params, grads, adam_m, adam_v, (long)numel, lr, beta1, beta2, eps, weight_decay, state,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+// vpd_plan_adamw_step with the device block deciding (the stem repack runs either way: after a skipped step it rewrites the
+// values the arena already holds)
+extern "C" int vpd_plan_adamw_step_scaled(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v,
+                                          long long numel, double lr, double beta1, double beta2, double eps,
+                                          double weight_decay, const vpd_scale_state* state, void* workspace, void* stream) {
+    if (!p || !params || !grads || !adam_m || !adam_v || !state || !workspace) return fail("null argument");
+    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
+    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    LCHECK(vpd_launch_adamw_pack_scaled(reinterpret_cast<const PackDesc*>(ws + p->desc_off),
+                                        reinterpret_cast<const int*>(ws + p->bmap_adam_off), (int)p->bmap_adam.size() / 2,
+                                        params, grads, adam_m, adam_v, reinterpret_cast<bf16_t*>(ws + p->arena_off), lr, beta1,
+                                        beta2, eps, weight_decay, state, s,
+                                        p->grads_in_scratch ? reinterpret_cast<const float*>(ws + p->wg_off) : nullptr));
+    p->grads_in_scratch = false;      // consumed, applied or not (the scratch is rewritten by the next backward)
+    LCHECK(vpd_launch_pack_weights(reinterpret_cast<const PackDesc*>(ws + p->desc_off), (int)p->descs.size(),
+                                   reinterpret_cast<const int*>(ws + p->bmap_pack_off), p->nstem_pack_blocks, params,
+                                   reinterpret_cast<bf16_t*>(ws + p->arena_off), s));
+    if (numel > p->nparam_padded)
+        LCHECK(vpd_launch_adamw_scaled(params + p->nparam_padded, grads + p->nparam_padded, adam_m + p->nparam_padded,
+                                       adam_v + p->nparam_padded, (long)(numel - p->nparam_padded), lr, beta1, beta2, eps,
+                                       weight_decay, state, s));
+    return 0;
+}
+
+extern "C" int vpd_scale_state_update(vpd_scale_state* state, float growth, float backoff, int growth_interval, void* stream) {
+    if (!state) return fail("null argument");
+    if (!(growth >= 1.f) || !(growth < 3.0e38f)) return fail("growth factor must be finite and >= 1");
+    if (!(backoff > 0.f) || !(backoff <= 1.f)) return fail("backoff factor must be in (0, 1]");
+    if (growth_interval < 1) return fail("growth interval must be >= 1");
+    LCHECK(vpd_launch_scale_update(state, growth, backoff, growth_interval, (hipStream_t)stream));
     return 0;
 }
 

@@ -713,7 +713,9 @@ struct Backward {
         const int n = c.n;
         hipStream_t s = c.s;
         const float* params = c.params;
-        if (p->loss_scale != 1.f)      // (fp16 training: vpd_plan_set_loss_scale)
+        if (p->scale_state)            // (fp16 training, dynamic scaler: vpd_plan_set_scale_state)
+            LCHECK(vpd_launch_scale_by_state(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->scale_state, s));
+        else if (p->loss_scale != 1.f)      // (fp16 training: vpd_plan_set_loss_scale)
             LCHECK(vpd_launch_scale(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->loss_scale, s));
         const float* demb = c.f32(p->dpred_off);
         if (p->motion) {

@@ -147,8 +147,7 @@ class GradBucketReducer:
         messages are the scratch ranges, the rest of the flat buffer travelling as one small message behind the last;
         otherwise the flat buffer's bucket ranges.  `lazy`, if given, must agree with the plan (a flat-buffer all-reduce
         after a lazy backward would sum stale conv ranges and leave the scratch the optimizer reads unreduced)."""
-        from ._lib import lib
-        pending = bool(lib().vpd_plan_grads_pending(plan.handle))
+        pending = bool(plan.L.vpd_plan_grads_pending(plan.handle))      # (the plan's own library: the bf16 or the fp16 build)
         if lazy is not None and bool(lazy) != pending:
             raise RuntimeError("GradBucketReducer.reduce(lazy=%s) but the plan's last backward was %s" %
                                (lazy, "lazy (gradients pending in the scratch)" if pending else "eager (flat buffer complete)"))

@@ -146,9 +146,13 @@ class StudentEngine:
             raise RuntimeError("vpd_amd needs a ROCm GPU (MI355X): torch.cuda.is_available() is False; "
                                "there is no CPU fallback for the student path")
         # dtype: element type of activations / packed weights -- "bf16" (libvpdhip.so: training and inference) or "fp16"
-        # (libvpdhip_f16.so: inference only; the reference's own GPU precision, train_vpd_model.py:79)
+        # (libvpdhip_f16.so: the reference's own GPU precision, train_vpd_model.py:79; training goes through a loss scaler)
         self.dtype = dtype
         self.loss_scale = 1.0      # set by models.util.LossScaler around a backward pass + optimizer step (fp16 training)
+        # models.util.DynamicLossScaler: its device block (vpd_scale_state, int32[8]) -- `scale_state` while a scaled backward
+        # pass + optimizer step are in flight (the scale is then read on the device), `_dyn_state` from its construction on
+        self.scale_state = None
+        self._dyn_state = None
         self.L = lib(dtype)   # fail loudly right here if the HIP library is missing
         self.check = lambda rc, what="": check(rc, what, dtype)
         self.arch, self.c_in, self.emb_dim = arch, int(c_in), int(emb_dim)
@@ -175,7 +179,7 @@ class StudentEngine:
         self._nbt_pending = 0
         self.adam_m = None
         self.adam_v = None
-        self.adam_step = 0
+        self._adam_step = 0
         self.loss_step = torch.zeros(1, **z)
         self.loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
         self._plans = {}
@@ -185,6 +189,30 @@ class StudentEngine:
         self.bucket_events = None
 
     # -- helpers -------------------------------------------------------------
+    @property
+    def adam_step(self):
+        """Optimizer steps applied so far (1-based `step` of the last AdamW).  Under a DynamicLossScaler only the device knows it
+        after a skipped step: read from the scaler's block (synchronises)."""
+        if self._dyn_state is not None:
+            return int(self._dyn_state[3].item())
+        return self._adam_step
+
+    @adam_step.setter
+    def adam_step(self, value):
+        self._adam_step = int(value)
+        if self._dyn_state is not None:
+            self._dyn_state[3] = int(value)
+
+    def attach_scale_state(self, state):
+        """models.util.DynamicLossScaler: from now on the applied-step count lives in `state` (it starts at adam_step)."""
+        self._dyn_state = state
+
+    def check_grads_finite_(self, state):
+        """The non-finite search over the completed flat gradient buffer (a scaler in front of an optimizer that reads p.grad)."""
+        self.materialize_grads()
+        self.check(self.L.vpd_op_check_finite(_ptr(self._grads), self.param_numel, _ptr(state), self._stream()),
+                   "vpd_op_check_finite")
+
     @property
     def num_batches_tracked(self):
         """int64[len(bn_names)] on the device, up to date (train-mode forwards since the last read are added first)"""
@@ -332,6 +360,10 @@ class StudentEngine:
             ev = (C.c_void_p * len(events))(*[C.c_void_p(e) for e in events])
         if self.loss_scale != 1.0 or hasattr(self.L, "vpd_plan_set_loss_scale"):      # (absent only in an older A/B library)
             self.check(self.L.vpd_plan_set_loss_scale(pl.handle, float(self.loss_scale)), "vpd_plan_set_loss_scale")
+        want = None if self.scale_state is None else self.scale_state.data_ptr()
+        if getattr(pl, "scale_state_ptr", None) != want:      # (never called without a dynamic scaler)
+            self.check(self.L.vpd_plan_set_scale_state(pl.handle, _ptr(self.scale_state)), "vpd_plan_set_scale_state")
+            pl.scale_state_ptr = want
         if lazy:      # (with bucket events the reducer sums the scratch ranges: GradBucketReducer.reduce(plan, lazy=True))
             self.check(self.L.vpd_plan_set_lazy_grads(pl.handle, 1), "vpd_plan_set_lazy_grads")
         self.check(self.L.vpd_backward(pl.handle, _ptr(self.params), _ptr(self._grads), n, ev, _ptr(pl.workspace),
@@ -360,7 +392,9 @@ class StudentEngine:
         if self.adam_m is None:
             self.adam_m = torch.zeros_like(self.params)
             self.adam_v = torch.zeros_like(self.params)
-        self.adam_step += 1
+        st = self.scale_state      # a DynamicLossScaler's step in flight: search + AdamW decided on the device, no host count
+        if st is None:
+            self.adam_step = self.adam_step + 1
         pl = self._step_plan
         if pl is not None and numel < pl.param_numel:
             # an optimizer that was NOT given the motion head, behind a plan that trains it: the fused pass would update the
@@ -370,12 +404,28 @@ class StudentEngine:
             pl = None
         if pl is not None and pl.packed_version == self.weights_version() and os.environ.get("VPD_FUSED_ADAMW", "1") != "0":
             # the train plan of the last backward: AdamW + refresh of its packed bf16 weights in one pass
-            self.check(self.L.vpd_plan_adamw_step(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
-                                            _ptr(self.adam_v), max(numel, pl.param_numel), lr, betas[0], betas[1], eps,
-                                            weight_decay, self.adam_step, _ptr(pl.workspace), self._stream()),
-                  "vpd_plan_adamw_step")
+            if st is not None:
+                n_ = max(numel, pl.param_numel)
+                self.check(self.L.vpd_plan_check_grads(pl.handle, _ptr(self._grads), n_, _ptr(st), _ptr(pl.workspace),
+                                                       self._stream()), "vpd_plan_check_grads")
+                self.check(self.L.vpd_plan_adamw_step_scaled(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
+                                                             _ptr(self.adam_v), n_, lr, betas[0], betas[1], eps, weight_decay,
+                                                             _ptr(st), _ptr(pl.workspace), self._stream()),
+                           "vpd_plan_adamw_step_scaled")
+            else:
+                self.check(self.L.vpd_plan_adamw_step(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
+                                                      _ptr(self.adam_v), max(numel, pl.param_numel), lr, betas[0], betas[1], eps,
+                                                      weight_decay, self.adam_step, _ptr(pl.workspace), self._stream()),
+                           "vpd_plan_adamw_step")
             self._hip_version += 1
             pl.packed_version = self.weights_version()
+        elif st is not None:
+            self.materialize_grads()
+            self.check(self.L.vpd_op_check_finite(_ptr(self._grads), numel, _ptr(st), self._stream()), "vpd_op_check_finite")
+            self.check(self.L.vpd_adamw_step_scaled(_ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v),
+                                                    numel, lr, betas[0], betas[1], eps, weight_decay, _ptr(st),
+                                                    self._stream()), "vpd_adamw_step_scaled")
+            self._hip_version += 1
         else:
             self.unscale_grads_()      # (the flat kernel has no plan to ask for the loss scale)
             self.check(self.L.vpd_adamw_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),

@@ -55,8 +55,8 @@ class RGBF_EmbeddingModel(nn.Module):
         variants the reference's hard-coded 5 cannot express -- BASELINE configs[2] runs a 6-channel two-stream input.
         The stem is then initialised by the same recipe as add_flow_to_model (models/rgb.py:19-23): the channel mean of
         a 3-channel kaiming kernel expanded to in_channels.
-        dtype: "bf16" (default; training and inference) or "fp16" -- the reference's own GPU precision (fp16 autocast,
-        train_vpd_model.py:79) for INFERENCE: embed() / the apply loop run on libvpdhip_f16.so, train mode raises."""
+        dtype: "bf16" (default) or "fp16" -- the reference's own GPU precision (fp16 autocast, train_vpd_model.py:79): training
+        and inference run on libvpdhip_f16.so, training behind a loss scaler (ModelTrainer.get_optimizer, vpd_amd.models.util)."""
         super().__init__()
         if "effnet" in model_arch:
             raise NotImplementedError("EfficientNet students are out of scope (SURVEY.md 2.1 #3)")

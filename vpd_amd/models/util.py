@@ -1,4 +1,5 @@
-"""step(): same call sequence as reference models/util.py:50-58; LossScaler: the GradScaler of the fp16 build."""
+"""step(): same call sequence as reference models/util.py:50-58; LossScaler / DynamicLossScaler: the GradScaler of the fp16 build."""
+import ctypes as C
 import os
 
 _LAZY = os.environ.get("VPD_LAZY_GRADS", "1") != "0"      # A/B switch: 0 = step() runs the plain loss.backward()
@@ -13,7 +14,7 @@ class LossScaler:
     sums and AdamW are fp32 -- 256 keeps the stem's activation gradients normal with 2^8 of head-room below fp16's 65,504.
     scale(loss).backward() leaves every .grad scaled, as GradScaler does; step() un-scales: the fused AdamW reads gradients x 1 / scale
     in its kernel, any other optimizer gets the flat gradient buffer multiplied by 1 / scale first.  A non-finite epoch loss is
-    reported by ModelTrainer.epoch (there is no per-step inf check: it would cost a host sync per step)."""
+    reported by ModelTrainer.epoch (there is no per-step inf check here: DynamicLossScaler has one, on the device)."""
 
     def __init__(self, engine, init_scale=256.0):
         if float(init_scale) <= 0:
@@ -43,12 +44,92 @@ class LossScaler:
         return None
 
 
+class DynamicLossScaler(LossScaler):
+    """torch.cuda.amp.GradScaler() as the reference runs it (train_vpd_model.py:105, its defaults): look for inf / NaN in the
+    gradients, SKIP the optimizer step when one is found and halve the scale, double it after `growth_interval` clean steps in a row.
+
+    The whole decision runs on the device.  The scaler owns one vpd_scale_state block (include/vpd_hip.h: scale, non-finite word,
+    growth tracker, applied and skipped steps); the backward pass reads the scale from it, the non-finite search ORs into it, the
+    fused AdamW reads it -- gradients x 1 / scale, bias corrections from the APPLIED step count, nothing written when the word is
+    set -- and update() is a one-thread kernel.  With the fused optimizer (`consumes_lazy_grads`) a step costs no host
+    synchronisation; get_scale(), skipped_steps and applied_steps read the block and synchronise when asked.  Any other optimizer
+    gets the flat gradient buffer un-scaled, and the word is read on the host to call or skip optimizer.step(), as torch does.
+    Under data parallelism the search runs after the all-reduce (inf and NaN survive a sum), so every replica decides alike."""
+
+    def __init__(self, engine, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        import torch
+        super().__init__(engine, init_scale)
+        if not float(growth_factor) >= 1.0 or not 0.0 < float(backoff_factor) <= 1.0 or int(growth_interval) < 1:
+            raise ValueError("growth_factor >= 1, 0 < backoff_factor <= 1 and growth_interval >= 1 are required")
+        self._growth, self._backoff, self._interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        # vpd_scale_state: {float scale; u32 found; i32 growth_tracker, applied_steps, skipped_steps, reserved[3]}
+        host = torch.zeros(8, dtype=torch.int32)
+        host.view(torch.float32)[0] = float(init_scale)
+        host[3] = int(engine.adam_step)
+        self._state = host.to(engine.device)
+        engine.attach_scale_state(self._state)
+
+    @property
+    def state(self):
+        """the device block (int32[8]; element 0 holds the scale's float bits)"""
+        return self._state
+
+    def _ptr(self):
+        return C.c_void_p(self._state.data_ptr())
+
+    def _host(self):
+        return self._state.cpu()      # synchronises
+
+    def get_scale(self):
+        import torch
+        return float(self._host().view(torch.float32)[0])
+
+    @property
+    def growth_tracker(self):
+        return int(self._host()[2])
+
+    @property
+    def applied_steps(self):
+        return int(self._host()[3])
+
+    @property
+    def skipped_steps(self):
+        return int(self._host()[4])
+
+    def scale(self, loss):
+        if not hasattr(loss, "_t"):
+            raise TypeError("LossScaler.scale() takes the loss object of ModelTrainer's forward")
+        self._engine.scale_state = self._state      # the backward pass and the optimizer step in flight read the block
+        return loss
+
+    def step(self, optimizer):
+        import torch
+        eng = self._engine
+        if eng.scale_state is not self._state:
+            raise RuntimeError("DynamicLossScaler.step() without scale(loss).backward() before it")
+        try:
+            if getattr(optimizer, "consumes_lazy_grads", False):
+                optimizer.step()                   # (FusedAdamW -> engine.adamw_step: non-finite search + skipping AdamW, enqueued)
+            else:
+                eng.check_grads_finite_(self._state)
+                eng._grads.mul_(1.0 / self._state[:1].view(torch.float32))      # device-side reciprocal: no sync
+                if int(self._state[1].item()) == 0:                            # the one host read of this path, as torch's
+                    optimizer.step()
+        finally:
+            eng.scale_state = None
+
+    def update(self):
+        eng = self._engine
+        eng.check(eng.L.vpd_scale_state_update(self._ptr(), self._growth, self._backoff, self._interval, eng._stream()),
+                  "vpd_scale_state_update")
+
+
 def step(optimizer, scaler, loss):
     """The reference's step() (models/util.py:50-58): loss.backward(); optimizer.step() -- or, with a scaler,
     scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update() -- then optimizer.zero_grad().
 
     The bf16 build computes with fp32 accumulation and needs no loss scaling: get_optimizer() returns scaler=None there; a student
-    built with dtype="fp16" (the reference's own GPU precision) gets a LossScaler."""
+    built with dtype="fp16" (the reference's own GPU precision) gets a LossScaler (static) or a DynamicLossScaler."""
     if scaler is not None and not isinstance(scaler, LossScaler):
         raise ValueError("the HIP path takes scaler=None (bf16) or a vpd_amd.models.util.LossScaler (fp16), not %r" % type(scaler))
     # The fused loss object offers a backward that leaves the conv weight gradients in the kernels' own layout -- ONLY an

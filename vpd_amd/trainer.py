@@ -7,7 +7,7 @@ import torch
 
 from .ddp import GradBucketReducer
 from .models.module import FCNet
-from .models.util import LossScaler, step
+from .models.util import DynamicLossScaler, LossScaler, step
 
 
 class _Loss:
@@ -164,22 +164,38 @@ class ModelTrainer:
         if optimizer is not None and eng.sync_errors():
             raise RuntimeError("a fused BatchNorm launch timed out at its in-launch grid barrier (the grid was not "
                                "resident): this epoch's results are invalid; set VPD_FUSED_BN=0 to use separate launches")
-        if optimizer is not None and scaler is not None and epoch_emb_loss != epoch_emb_loss:
+        # (a DynamicLossScaler skipped the steps whose gradients overflowed: like the reference, the epoch value is reported as it is)
+        if optimizer is not None and scaler is not None and not isinstance(scaler, DynamicLossScaler) \
+                and epoch_emb_loss != epoch_emb_loss:
             raise FloatingPointError("non-finite training loss under fp16 with loss scale %g: an activation gradient left fp16's range "
-                                     "(the reference's GradScaler would have skipped those steps); use LossScaler(engine, init_scale=<smaller>)"
+                                     "(the reference's GradScaler would have skipped those steps); use LossScaler(engine, init_scale=<smaller>) or get_optimizer(lr, loss_scale='dynamic')"
                                      % scaler.get_scale())
         if self._reducer is not None:
             epoch_emb_loss, epoch_emb_n = self._reducer.all_reduce_scalars(epoch_emb_loss, epoch_emb_n)
         return epoch_emb_loss / epoch_emb_n
 
-    def get_optimizer(self, learning_rate):
+    def get_optimizer(self, learning_rate, loss_scale=None):
+        """loss_scale: None -- the default scaler of the student's element type (bf16: none; fp16: the static LossScaler, 256);
+        'dynamic' -- a DynamicLossScaler (GradScaler's defaults: skip on overflow, decided on the device); a number -- a static
+        LossScaler with that scale.  A scaler is an fp16 matter: asking for one on a bf16 student raises."""
         params = list(self.encoder.parameters())
         if hasattr(self, 'fcn_time'):
             params.extend(self.fcn_time.parameters())
         # bf16 operands with fp32 accumulation need no GradScaler: scaler None.  A student built with dtype="fp16" gets the static
         # LossScaler (the reference: GradScaler() on 'cuda', train_vpd_model.py:104-105)
         eng = self.encoder.engine
-        return FusedAdamW(params, eng, lr=learning_rate), (LossScaler(eng) if eng.dtype == "fp16" else None)
+        if loss_scale is None:
+            scaler = LossScaler(eng) if eng.dtype == "fp16" else None
+        elif eng.dtype != "fp16":
+            raise ValueError("loss_scale=%r: loss scaling belongs to a student built with dtype='fp16' (this one: %s)"
+                             % (loss_scale, eng.dtype))
+        elif isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError("loss_scale must be None, 'dynamic' or a number, not %r" % (loss_scale,))
+            scaler = DynamicLossScaler(eng)
+        else:
+            scaler = LossScaler(eng, float(loss_scale))
+        return FusedAdamW(params, eng, lr=learning_rate), scaler
 
     def save_model(self, save_dir, name):
         torch.save(self.encoder.state_dict(),
