@@ -291,6 +291,50 @@ int vpd_op_bn_forward(const void* z_bf16, const double* rows, const float* gamma
 int vpd_op_bn_backward_apply(const void* dy_bf16, const void* z_bf16, const unsigned char* mask_bits, const double* rows,
                              const float* gamma, const float* mean, const float* rstd, void* dz_padded_bf16, float* dgamma,
                              float* dbeta, int n, int H, int W, int C, void* stream);
+/* Stem BatchNorm + ReLU + MaxPool 3x3 s2 p1 in one launch (stem_pool_kernel / stem_pool_pair_kernel): z dense NHWC
+ * [n][Hz][Wz][C] -> out, NHWC padded by opad ([n][Ho+2 opad][Wo+2 opad][C], Ho = (Hz-1)/2+1; the border is not written), and,
+ * when idx is given (training), the window tap r*3+t of the FIRST maximum per output element, u8 dense [n][Ho][Wo][C]. */
+int vpd_op_stem_pool_forward(const void* z, const float* scale, const float* shift, void* out_padded, unsigned char* idx,
+                             int n, int Hz, int Wz, int C, int opad, void* stream);
+/* Backward of the same through the pool, the ReLU and the train-mode BatchNorm (vpd_launch_stem_pool_bwd: sums, finalize,
+ * dz): dpool dense [n][Ho][Wo][C], idx as written by the forward, dz dense like z.  pooled_padded (the forward's output,
+ * opad 1) or null: with it (and VPD_STEM_POOLSUMS on) the sums are taken over the pooled positions.  rows: f64 [16][2][C],
+ * zeroed (left zeroed); coef: fp32 [3][C] scratch; dgamma = sum g xhat, dbeta = sum g. */
+int vpd_op_stem_pool_backward(const void* dpool, const unsigned char* idx, const void* z, const float* mean, const float* rstd,
+                              const float* scale, const float* shift, const float* gamma, const float* beta,
+                              const void* pooled_padded, double* rows, float* coef, void* dz, float* dgamma, float* dbeta,
+                              int n, int Hz, int Wz, int C, void* stream);
+/* BatchNorm backward with its own reduction: fused = 0 the three launches (reduce, finalize, apply; rows f64 [16][2][C] zeroed,
+ * coef fp32 [3][C]), fused = 1 the single launch with a grid barrier (rows f64 [4][2][C] zeroed, sync: 2304 zeroed bytes, err:
+ * the sticky time-out counter).  ReLU mask, one at most: act_padded (the stored activation, NHWC padded by 1; with write_g the
+ * masked gradient is written back over dy), mask_bits ([n H W][C/8], fused only), mscale / mshift (mask = mscale z + mshift > 0).
+ * dy_pooled (fused with mask_bits only): dy does not exist yet, it is elem(dy_pooled[b][c] / (H W)), which the launch also
+ * writes to dy.  dz: NHWC padded by dzpad. */
+int vpd_op_bn_backward(void* dy, const void* z, const void* act_padded, const unsigned char* mask_bits, const float* mscale,
+                       const float* mshift, const float* dy_pooled, double* rows, float* coef, void* sync, unsigned* err,
+                       const float* gamma, const float* mean, const float* rstd, void* dz, int dzpad, float* dgamma,
+                       float* dbeta, int n, int H, int W, int C, int write_g, int fused, void* stream);
+/* The two BatchNorms of a down-sampling block in one launch (bn_bwd_fused2_kernel): same dy, same activation mask, each its
+ * own z, statistics, gamma, rows (f64 [4][2][C], zeroed) and outputs; dzA / dzB NHWC padded by 1.  dy is overwritten with the
+ * masked gradient when it does not stay in LDS. */
+int vpd_op_bn_backward_pair(void* dy, const void* act_padded, const void* zA, const float* meanA, const float* rstdA,
+                            const float* gammaA, double* rowsA, void* dzA, float* dgammaA, float* dbetaA, const void* zB,
+                            const float* meanB, const float* rstdB, const float* gammaB, double* rowsB, void* dzB,
+                            float* dgammaB, float* dbetaB, void* sync, unsigned* err, int n, int H, int W, int C, void* stream);
+/* Host-only: what the fused backward launcher derives for M pixels of C channels on the current device, by the launcher's own
+ * code: out4 = {blocks, g stays in LDS, z stays in LDS (pair: the first z), pair: the second z stays in LDS}. */
+int vpd_op_bn_backward_residency(int M, int C, int pair, int* out4);
+/* Head (fp32): global average pool over the interior of an NHWC activation padded by pad and its gradient
+ * dact = elem(dpooled / (H W)), dense; Y[M][N] = op(A) op(B) (+ bias[N]) (ReLU), ta: A stored [K][M], tb: B stored [N][K];
+ * out[n] = sum_m A[m][n]; d = act > 0 ? d : 0; sum-MSE: loss_step = sum (e - t)^2, loss_accum += the same, de = 2 (e - t)
+ * (de, loss_step, loss_accum: each optional). */
+int vpd_op_avgpool(const void* act_padded, int n, int H, int W, int C, int pad, float* pooled, void* stream);
+int vpd_op_avgpool_bwd(const float* dpooled, int n, int H, int W, int C, void* dact, void* stream);
+int vpd_op_sgemm(const float* A, const float* B, float* Y, const float* bias, int M, int N, int K, int ta, int tb, int relu,
+                 void* stream);
+int vpd_op_colsum(const float* A, int M, int N, float* out, void* stream);
+int vpd_op_relu_mask(float* d, const float* act, long long n, void* stream);
+int vpd_op_mse(const float* e, const float* t, long long n, float* de, float* loss_step, double* loss_accum, void* stream);
 /* dw[slice][Co][Kc] (fp32) += sum over output pixels of dz[m][co] * x[gather(m, tap)][kc].
  * slab: optional fp32 scratch of vpd_op_wgrad_slab_bytes() bytes; when given, eligible 3x3 stride-1 shapes use
  * the halo kernel (split partials in the slab + reduce), otherwise the generic kernel (fp32 atomics). */

@@ -1,0 +1,316 @@
+"""Plain float64 PyTorch references, input generators and derived error bounds shared by the operator parity tests
+(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py).  Nothing here touches the GPU or the library:
+tests/test_opref_cpu.py pins what these references rest on, so that a failure on the GPU points at the kernel."""
+import math
+
+import torch
+import torch.nn.functional as F
+
+# element type -> (torch dtype, significand bits including the hidden one, log2 of the smallest positive value)
+ELEM = {"bf16": (torch.bfloat16, 8, -133), "fp16": (torch.float16, 11, -24)}
+BN_EPS = 1e-5
+
+
+def elem_round(t, name):
+    """round to the element type, back to float32 (what the existing tests do with bf16_round)"""
+    return t.to(ELEM[name][0]).to(torch.float32)
+
+
+def ulp(x, name):
+    """spacing of the element type at |x| (float64 tensor in, float64 out); the subnormal spacing below the normal range"""
+    _, p, emin = ELEM[name]
+    e = torch.floor(torch.log2(x.double().abs().clamp_min(2.0 ** -300)))
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64), (e - (p - 1)).clamp_min(emin))
+
+
+def rel_l2(a, b):
+    a, b = a.double().flatten(), b.double().flatten()
+    return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+def nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def nchw(t):
+    return t.permute(0, 3, 1, 2).contiguous()
+
+
+# ---------------------------------------------------------------------------
+# stem: BatchNorm + ReLU + MaxPool 3x3 s2 p1
+# ---------------------------------------------------------------------------
+STEM_FWD_SHAPES = {"g64": (3, 64, 64), "g32": (8, 32, 32), "odd": (5, 33, 31), "e48": (4, 48, 48)}
+STEM_BIG = (512, 64, 64)                     # 512 * 32 * 16 * 8 = 2^21 items in the pair kernel: the 64-bit division path
+STEM_BWD_SHAPES = {"g64": (3, 64, 64), "g32": (8, 32, 32), "odd": (5, 33, 31), "e48": (4, 48, 48), "odd2": (2, 17, 35)}
+STEM_C = 64
+REGIMES = ("init", "drift")
+
+
+def stem_grid_inputs(n, H, W, C, seed):
+    """z = k/16 (|k| <= 127), scale in {0.5 .. 1.5}, shift = j/8 (|j| <= 16): z * scale + shift is exact in fp32, the result
+    is representable in bf16 and fp16 only sometimes -- but its rounding is the same single rounding from an exact value in
+    fp32 and in float64 -- and 3x3 windows tie all the time"""
+    g = torch.Generator().manual_seed(seed)
+    z = torch.randint(-127, 128, (n, C, H, W), generator=g).float() / 16.0
+    scale = torch.tensor([0.5, 0.75, 1.0, 1.25, 1.5])[torch.randint(0, 5, (C,), generator=g)]
+    shift = torch.randint(-16, 17, (C,), generator=g).float() / 8.0
+    return z, scale, shift
+
+
+def stem_params(C, regime, g):
+    """init: gamma in [0.5, 1.5], beta ~ 0.3 N(0, 1); drift: |gamma| in [0.05, 1.5] of either sign, beta in [-1, 1]"""
+    if regime == "init":
+        return torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
+    mag = 0.05 + 1.45 * torch.rand(C, generator=g)
+    sign = torch.where(torch.rand(C, generator=g) < 0.5, -1.0, 1.0)
+    return mag * sign, torch.rand(C, generator=g) * 2.0 - 1.0
+
+
+def stem_stats(z):
+    zd = z.double()
+    mean = zd.mean(dim=(0, 2, 3))
+    rstd = (zd.var(dim=(0, 2, 3), unbiased=False) + BN_EPS).rsqrt()
+    return mean, rstd
+
+
+def stem_random_inputs(n, H, W, C, seed, name, regime="init"):
+    """element-rounded randn z, fp32 gamma / beta, float64 batch statistics and the fp32 (mean, rstd, scale, shift) the kernels get"""
+    g = torch.Generator().manual_seed(seed)
+    z = elem_round(torch.randn(n, C, H, W, generator=g) * 1.3 - 0.2, name)
+    gamma, beta = stem_params(C, regime, g)
+    mean, rstd = stem_stats(z)
+    scale = gamma.double() * rstd
+    shift = beta.double() - mean * scale
+    return {"z": z, "gamma": gamma, "beta": beta, "mean": mean, "rstd": rstd, "scale": scale.float(), "shift": shift.float(), "gen": g}
+
+
+def taps_from_flat(flat, W):
+    """torch's flat arg-max index (y * W + x of the input plane) -> window tap r * 3 + t of a 3x3 s2 p1 pooling"""
+    Ho, Wo = flat.shape[-2:]
+    oy = torch.arange(Ho).view(Ho, 1)
+    ox = torch.arange(Wo).view(1, Wo)
+    r = flat // W - (2 * oy - 1)
+    t = flat % W - (2 * ox - 1)
+    return r * 3 + t
+
+
+def stem_forward_ref(z, scale, shift, name):
+    """float64: a = elem(relu(z * scale + shift)) per pixel, then max_pool2d(3, 2, 1) with torch's first-maximum indices.
+    Returns pooled [n,C,Ho,Wo] float64, taps (int64, r*3+t), a."""
+    a = (z.double() * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)).clamp_min(0)
+    a = a.to(ELEM[name][0]).double()
+    p, fi = F.max_pool2d(a, 3, 2, 1, return_indices=True)
+    return p, taps_from_flat(fi, z.shape[3]), a
+
+
+def first_max_loop(a):
+    """literal row-major scan of every 3x3 s2 p1 window of a [H][W] plane: value and tap of the FIRST maximum"""
+    H, W = a.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    val = torch.empty(Ho, Wo, dtype=a.dtype)
+    tap = torch.empty(Ho, Wo, dtype=torch.int64)
+    for oy in range(Ho):
+        for ox in range(Wo):
+            best, bi = -math.inf, 0
+            for r in range(3):
+                for t in range(3):
+                    y, x = 2 * oy - 1 + r, 2 * ox - 1 + t
+                    if 0 <= y < H and 0 <= x < W and float(a[y, x]) > best:
+                        best, bi = float(a[y, x]), r * 3 + t
+            val[oy, ox], tap[oy, ox] = best, bi
+    return val, tap
+
+
+def stem_dpool(inp, name):
+    """an incoming gradient correlated with the pooled xhat, so that the mean(g * xhat) term carries weight"""
+    z = inp["z"].double()
+    xhat = (z - inp["mean"].view(1, -1, 1, 1)) * inp["rstd"].view(1, -1, 1, 1)
+    px = F.max_pool2d(xhat, 3, 2, 1)
+    return elem_round(torch.randn(px.shape, generator=inp["gen"]) + 0.9 * px.float() + 0.3, name)
+
+
+def stem_backward_ref_A(z, gamma, beta, dpool):
+    """independent: float64 autograd of max_pool2d(relu(batch_norm(z, training=True)), 3, 2, 1) contracted with dpool.
+    Returns dz, dgamma, dbeta and torch's own window taps."""
+    zt = z.double().requires_grad_(True)
+    gt = gamma.double().requires_grad_(True)
+    bt = beta.double().requires_grad_(True)
+    a = F.batch_norm(zt, None, None, gt, bt, training=True, eps=BN_EPS).clamp_min(0)
+    p, fi = F.max_pool2d(a, 3, 2, 1, return_indices=True)
+    (p * dpool.double()).sum().backward()
+    return zt.grad, gt.grad, bt.grad, taps_from_flat(fi, z.shape[3])
+
+
+def route(dpool, taps, H, W):
+    """g[y][x] = sum of dpool over the windows whose tap points at (y, x)"""
+    n, C, Ho, Wo = dpool.shape
+    oy = torch.arange(Ho).view(Ho, 1)
+    ox = torch.arange(Wo).view(1, Wo)
+    flat = (2 * oy - 1 + taps // 3) * W + (2 * ox - 1 + taps % 3)
+    g = torch.zeros(n, C, H * W, dtype=torch.float64)
+    g.scatter_add_(2, flat.view(n, C, -1), dpool.double().reshape(n, C, -1))
+    return g.view(n, C, H, W)
+
+
+def stem_backward_ref_B(z, gamma, beta, mean, rstd, dpool, taps):
+    """closed form, routed by the given taps: g = route(dpool) * [a > 0], dz = gamma rstd (g - mean(g) - xhat mean(g xhat))"""
+    n, C, H, W = z.shape
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    xhat = (z.double() - v(mean)) * v(rstd)
+    a = v(gamma) * xhat + v(beta)
+    routed = route(dpool, taps, H, W)
+    g = routed * (a > 0)
+    M = n * H * W
+    s1, s2 = g.sum(dim=(0, 2, 3)), (g * xhat).sum(dim=(0, 2, 3))
+    dz = v(gamma) * v(rstd) * (g - v(s1) / M - xhat * v(s2) / M)
+    return {"dz": dz, "dgamma": s2, "dbeta": s1, "g": g, "routed": routed, "xhat": xhat, "a": a,
+            "abs1": g.abs().sum(dim=(0, 2, 3)), "abs2": (g * xhat).abs().sum(dim=(0, 2, 3))}
+
+
+def relu_band(z, scale, shift, a):
+    """elements whose ReLU mask an fp32 evaluation of z * scale + shift could flip: |a| < 2^-20 (|z scale| + |shift|)"""
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    return a.abs() < 2.0 ** -20 * ((z.double() * v(scale)).abs() + v(shift).abs())
+
+
+SUM_TOL = 2e-5            # sums kept in fp32 partials, combined in fp64 (test_conv_epilogue_batchnorm_sums)
+BAND_CAP = 1e-5           # share of elements that may be left out of a per-element comparison
+
+
+def dz_l2_gate(name):
+    """rel-L2 gate of an element-type dz: 3e-3 for bf16 (test_batchnorm_backward_op_matches_autograd), scaled by the ratio of the half-ulps"""
+    return 3e-3 * 2.0 ** (ELEM["bf16"][1] - ELEM[name][1])
+
+
+def bn_dz_bound(ref_dz, gamma, rstd, mean, z, g, xhat, s1, s2, ds1, ds2, M, name):
+    """per-element bound on an element-type dz = c1 (g - c2 - xhat c3): one output ulp, the propagated error bounds of the two
+    sums (ds1, ds2, per channel), and the fp32 evaluation itself -- eight roundings of 2^-24 relative to the magnitudes that
+    enter (xhat from the fp32 mean / rstd included: (|z| + |mean|) rstd in place of |xhat|)"""
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    c1 = (v(gamma) * v(rstd)).abs()
+    prop = c1 * (v(ds1) + xhat.abs() * v(ds2)) / M
+    xmag = (z.double().abs() + v(mean).abs()) * v(rstd)
+    f32 = 8 * 2.0 ** -24 * c1 * (g.abs() + v(s1).abs() / M + xmag * v(s2).abs() / M)
+    return ulp(ref_dz, name) + prop + f32
+
+
+# ---------------------------------------------------------------------------
+# BatchNorm backward (the construction of test_batchnorm_backward_op_matches_autograd)
+# ---------------------------------------------------------------------------
+def bn_backward_case(n, h, w, c, seed, name, relu=True, residual=False, autograd=True):
+    """z, a dy correlated with xhat, gamma / beta; float64 autograd of relu?(batch_norm(z) (+ res)) contracted with dy.
+    residual: the activation (and with it the mask) includes a residual, as at a block output.  autograd=False (the large
+    cases): the closed form instead, which test_opref_cpu.py holds equal to autograd to 1e-12."""
+    g = torch.Generator().manual_seed(seed)
+    z = elem_round(torch.randn(n, c, h, w, generator=g) * 1.3 - 0.2, name)
+    zn = (z - z.mean(dim=(0, 2, 3), keepdim=True)) / z.std(dim=(0, 2, 3), keepdim=True)
+    dy = elem_round(torch.randn(n, c, h, w, generator=g) + 0.9 * zn + 0.3, name)
+    del zn
+    gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.3
+    res = elem_round(torch.randn(n, c, h, w, generator=g), name) if residual else None
+    mean, rstd = stem_stats(z)
+    out = {"z": z, "dy": dy, "gamma": gamma, "beta": beta, "mean": mean, "rstd": rstd, "gen": g}
+    if autograd:
+        zt = z.double().requires_grad_(True)
+        gt = gamma.double().requires_grad_(True)
+        bt = beta.double().requires_grad_(True)
+        y = F.batch_norm(zt, None, None, gt, bt, training=True, eps=BN_EPS)
+        if residual:
+            y = y + res.double()
+        act = y.clamp_min(0) if relu else y
+        (act * dy.double()).sum().backward()
+        y = y.detach()
+        out.update(dz=zt.grad, dgamma=gt.grad, dbeta=bt.grad)
+    else:
+        v = lambda t: t.double().view(1, -1, 1, 1)
+        y = (z.double() - v(mean)) * v(rstd) * v(gamma) + v(beta)
+        if residual:
+            y = y + res.double()
+    mask = (y > 0) if relu else torch.ones_like(y, dtype=torch.bool)
+    out.update(mask=mask, act=(y.clamp_min(0) if relu else y))
+    if not autograd:
+        gm = dy.double() * mask
+        xhat = (z.double() - mean.view(1, -1, 1, 1)) * rstd.view(1, -1, 1, 1)
+        out.update(dz=bn_dz_closed_form(z, gamma, mean, rstd, gm), dgamma=(gm * xhat).sum(dim=(0, 2, 3)), dbeta=gm.sum(dim=(0, 2, 3)))
+    return out
+
+
+def bn_dz_closed_form(z, gamma, mean, rstd, gm, c3_factor=1.0):
+    """dz = gamma rstd (g - mean(g) - c3_factor xhat mean(g xhat)) in float64; c3_factor = 1.02: the resolution check's faulty reference"""
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    xhat = (z.double() - v(mean)) * v(rstd)
+    gm = gm.double()
+    return v(gamma) * v(rstd) * (gm - gm.mean(dim=(0, 2, 3), keepdim=True)
+                                 - c3_factor * xhat * (gm * xhat).mean(dim=(0, 2, 3), keepdim=True))
+
+
+def bn_case_with_mask(cs, mask):
+    """the case's reference for another ReLU mask (the sign of the STORED activation: a positive value below the element type's
+    smallest one is stored as zero), by the closed form"""
+    if torch.equal(mask, cs["mask"]):
+        return cs
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    gm = cs["dy"].double() * mask
+    xhat = (cs["z"].double() - v(cs["mean"])) * v(cs["rstd"])
+    out = dict(cs)
+    out.update(mask=mask, dz=bn_dz_closed_form(cs["z"], cs["gamma"], cs["mean"], cs["rstd"], gm),
+               dgamma=(gm * xhat).sum(dim=(0, 2, 3)), dbeta=gm.sum(dim=(0, 2, 3)))
+    return out
+
+
+def mask_bits(mask_bool):
+    """[M][C] bool -> [M][C/8] bytes, bit j of byte (m, c8) = element (m, 8 c8 + j)"""
+    m, c = mask_bool.shape
+    w = (2 ** torch.arange(8, dtype=torch.int32)).view(1, 1, 8)
+    return (mask_bool.view(m, c // 8, 8).to(torch.int32) * w).sum(dim=2).to(torch.uint8)
+
+
+# ---------------------------------------------------------------------------
+# head (fp32): integer inputs whose sums stay below 2^24 are exact in any order of additions
+# ---------------------------------------------------------------------------
+def int_matrix(shape, lo, hi, g):
+    return torch.randint(lo, hi + 1, shape, generator=g).float()
+
+
+# (M, N, K, ta, tb, bias, relu): every call shape of the train step's head -- forward fc (tb = 1; feat 512 / 2048; D 32 / 128 / a
+# ragged 40), the motion MLP (K = 32 falls back to sgemm_small_kernel), backward weight gradients (ta = 1, K = the batch) and
+# data gradients (ta = tb = 0)
+def sgemm_cases():
+    cases = []
+    for n in (1, 5, 17, 256, 1000):
+        for feat, D in ((512, 32), (512, 128), (2048, 40), (2048, 128)):
+            if n in (256, 1000) and feat == 2048 and D == 40:
+                continue
+            cases.append(("fc_n%d_f%d_d%d" % (n, feat, D), n, D, feat, 0, 1, 1, 0))
+        for D in (32, 128, 40):
+            cases.append(("mlp0_n%d_d%d" % (n, D), n, 128, D, 0, 1, 1, 1))
+            cases.append(("mlp2_n%d_d%d" % (n, D), n, 2 * D, 128, 0, 1, 1, 0))
+        cases.append(("mlp1_n%d" % n, n, 128, 128, 0, 1, 1, 1))
+    for k in (5, 6, 37, 256, 1000):                       # backward: K = the batch
+        cases.append(("wg_fc_k%d" % k, 32, 512, k, 1, 0, 0, 0))
+        cases.append(("wg_mlp2_k%d" % k, 80, 128, k, 1, 0, 0, 0))
+        cases.append(("wg_mlp0_k%d" % k, 128, 40, k, 1, 0, 0, 0))
+        cases.append(("dg_fc_n%d" % k, k, 512, 40, 0, 0, 0, 0))
+        cases.append(("dg_mlp_n%d" % k, k, 128, 256, 0, 0, 0, 0))
+    return cases
+
+
+def sgemm_operands(case, g, integer):
+    _, M, N, K, ta, tb, bias, relu = case
+    if integer:
+        # |a|, |b| <= 7: |sum| <= 49 K + 64 < 2^24 for every K here (K <= 2048)
+        A, B = int_matrix((M, K), -7, 7, g), int_matrix((K, N), -7, 7, g)
+        bv = int_matrix((N,), -64, 64, g) if bias else None
+    else:
+        A, B = torch.randn(M, K, generator=g), torch.randn(K, N, generator=g)
+        bv = torch.randn(N, generator=g) if bias else None
+    return A, B, bv
+
+
+MSE_SIZES = (4, 7, 1023, 4096, 32768, 32771, 128000)
+
+
+def mse_int_operands(n, g):
+    """integer e, t with |e - t| <= 6: sum d^2 <= 36 * 128000 < 2^24, two calls accumulated < 2^24 as well"""
+    t = int_matrix((n,), -100, 100, g)
+    return t + int_matrix((n,), -6, 6, g), t

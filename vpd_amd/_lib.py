@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VPD_LIB_PATH") or os.path.join(_HERE, "libvpdhip.so")
 # the same sources built with fp16 elements (vpd_amd/csrc/Makefile, common.h "Element type"): training and inference
 LIB_PATH_F16 = os.environ.get("VPD_LIB_PATH_F16") or os.path.join(_HERE, "libvpdhip_f16.so")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 c_int_p = C.POINTER(C.c_int)
 c_ll_p = C.POINTER(C.c_longlong)
@@ -72,6 +72,17 @@ SIGNATURES = {
     "vpd_op_conv2d_bnsums": (C.c_int, [vp] * 6 + [C.c_int] * 8 + [c_int_p, C.c_int, vp]),
     "vpd_op_bn_forward": (C.c_int, [vp] * 13 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
     "vpd_op_bn_backward_apply": (C.c_int, [vp] * 10 + [C.c_int] * 4 + [vp]),
+    "vpd_op_stem_pool_forward": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [vp]),
+    "vpd_op_stem_pool_backward": (C.c_int, [vp] * 15 + [C.c_int] * 4 + [vp]),
+    "vpd_op_bn_backward": (C.c_int, [vp] * 15 + [C.c_int] + [vp, vp] + [C.c_int] * 6 + [vp]),
+    "vpd_op_bn_backward_pair": (C.c_int, [vp] * 20 + [C.c_int] * 4 + [vp]),
+    "vpd_op_bn_backward_residency": (C.c_int, [C.c_int, C.c_int, C.c_int, c_int_p]),
+    "vpd_op_avgpool": (C.c_int, [vp] + [C.c_int] * 5 + [vp, vp]),
+    "vpd_op_avgpool_bwd": (C.c_int, [vp] + [C.c_int] * 4 + [vp, vp]),
+    "vpd_op_sgemm": (C.c_int, [vp] * 4 + [C.c_int] * 6 + [vp]),
+    "vpd_op_colsum": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "vpd_op_relu_mask": (C.c_int, [vp, vp, C.c_longlong, vp]),
+    "vpd_op_mse": (C.c_int, [vp, vp, C.c_longlong, vp, vp, vp, vp]),
     "vpd_op_wgrad": (C.c_int, [vp, vp, vp] + [C.c_int] * 13 + [c_int_p, vp, vp]),
     "vpd_op_wgrad_slab_bytes": (C.c_size_t, []),
     "vpd_op_tr_read_probe": (C.c_int, [vp, vp, vp]),

@@ -1376,6 +1376,31 @@ __global__ __launch_bounds__(1024) void bn_bwd_fused2_kernel(const BnBwdParams p
 #undef LD8
 }
 
+// Grid and LDS residency of a fused BatchNorm backward over M pixels of C channels: one 1024-thread block per CU (the whole grid
+// is resident, sync.h), each owning `ppb` consecutive pixels; nt = 2: g and z of bn_bwd_fused_kernel, nt = 3: g, zA and zB of
+// bn_bwd_fused2_kernel (one sum per tensor in the block reduction).  A tensor slice stays in LDS across the barrier while the
+// slices before it and the reduction scratch fit in 160 KB.
+BnBwdFusedGeom vpd_bn_bwd_fused_geom(int M, int C, int nt) {
+    BnBwdFusedGeom q;
+    const int ncu = vpd_cu_budget();
+    const int cv = C / 8, ppi = 1024 / cv;
+    int G = ncu;                                        // one 1024-thread block per CU: the whole grid is resident
+    int ppb = (M + G - 1) / G;
+    ppb = ((ppb + ppi - 1) / ppi) * ppi;
+    G = (M + ppb - 1) / ppb;
+    q.G = G; q.ppb = ppb;
+    q.iters = ppb / ppi;
+    const size_t red_bytes = (size_t)(cv <= 64 ? 16 : 16 / (cv / 64)) * nt * C * sizeof(float);
+    const size_t tile = (size_t)q.iters * 1024 * 16;    // bytes of one resident tensor slice
+    const size_t cap = 160 * 1024;
+    q.lds = red_bytes;
+    for (int k = 0; k < 3; ++k) {
+        q.keep[k] = k < nt && (k == 0 || q.keep[k - 1]) && red_bytes + (size_t)(k + 1) * tile <= cap;
+        if (q.keep[k]) q.lds += tile;
+    }
+    return q;
+}
+
 bool vpd_bn_bwd_fused2_ok(int M, int C) {
     return !(!vpd_switches().fused_bn || !vpd_switches().bn_pair || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) && M >= 1;
 }
@@ -1386,27 +1411,18 @@ hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p0, const BnFusedBwd& fA,
                                     const float* meanB, const float* rstdB, bf16_t* dzB, hipStream_t s) {
     BnBwdParams p = p0;
     if (!p.act) return hipErrorInvalidValue;
-    const int ncu = vpd_cu_budget();
-    const int cv = p.C / 8, ppi = 1024 / cv;
-    int G = ncu;
-    int ppb = (p.M + G - 1) / G;
-    ppb = ((ppb + ppi - 1) / ppi) * ppi;
-    G = (p.M + ppb - 1) / ppb;
-    p.ppb = ppb;
+    const BnBwdFusedGeom geo = vpd_bn_bwd_fused_geom(p.M, p.C, 3);
+    const int G = geo.G;
+    p.ppb = geo.ppb;
     BnFusedBwd2Args f;
     f.rowsA = fA.rows; f.rowsB = fB.rows; f.sync = reinterpret_cast<GridSync*>(fA.sync); f.err = fA.err;
     f.zB = zB; f.meanB = meanB; f.rstdB = rstdB;
     f.gammaA = fA.gamma; f.dgammaA = fA.dgamma; f.dbetaA = fA.dbeta;
     f.gammaB = fB.gamma; f.dgammaB = fB.dgamma; f.dbetaB = fB.dbeta;
     f.dzB = dzB; f.count = fA.count;
-    f.iters = ppb / ppi;
-    const size_t red_bytes = (size_t)(cv <= 64 ? 16 : 16 / (cv / 64)) * 3 * p.C * sizeof(float);
-    const size_t tile = (size_t)f.iters * 1024 * 16;
-    const size_t cap = 160 * 1024;
-    f.keep_g = red_bytes + tile <= cap;
-    f.keep_zA = f.keep_g && red_bytes + 2 * tile <= cap;
-    f.keep_zB = f.keep_zA && red_bytes + 3 * tile <= cap;
-    const size_t lds = red_bytes + (f.keep_g ? tile : 0) + (f.keep_zA ? tile : 0) + (f.keep_zB ? tile : 0);
+    f.iters = geo.iters;
+    f.keep_g = geo.keep[0]; f.keep_zA = geo.keep[1]; f.keep_zB = geo.keep[2];
+    const size_t lds = geo.lds;
     hipLaunchKernelGGL(bn_bwd_fused2_kernel, dim3(G), dim3(1024), lds, s, p, f);
     return hipGetLastError();
 }
@@ -1420,27 +1436,18 @@ bool vpd_bn_bwd_fused_ok(int M, int C, bool mask_act, bool write_g) {
 
 hipError_t vpd_launch_bn_bwd_fused(const BnBwdParams& p0, const BnFusedBwd& f0, hipStream_t s) {
     BnBwdParams p = p0;
-    const int ncu = vpd_cu_budget();
-    const int cv = p.C / 8, ppi = 1024 / cv;
-    int G = ncu;                                        // one 1024-thread block per CU: the whole grid is resident
-    {
-    }
-    int ppb = (p.M + G - 1) / G;
-    ppb = ((ppb + ppi - 1) / ppi) * ppi;
-    G = (p.M + ppb - 1) / ppb;
-    p.ppb = ppb;
+    const BnBwdFusedGeom geo = vpd_bn_bwd_fused_geom(p.M, p.C, 2);
+    const int G = geo.G;
+    p.ppb = geo.ppb;
     BnFusedBwdArgs f;
     f.rows = f0.rows; f.sync = reinterpret_cast<GridSync*>(f0.sync); f.err = f0.err; f.gamma = f0.gamma; f.dgamma = f0.dgamma; f.dbeta = f0.dbeta;
     f.count = f0.count;
-    f.iters = ppb / ppi;
-    const size_t red_bytes = (size_t)(cv <= 64 ? 16 : 16 / (cv / 64)) * 2 * p.C * sizeof(float);
-    const size_t tile = (size_t)f.iters * 1024 * 16;    // bytes of one resident tensor slice
-    const size_t cap = 160 * 1024;
+    f.iters = geo.iters;
     const int mask = p.mask_bits ? 3 : (p.act ? 1 : (p.mscale ? 2 : 0));
-    f.keep_g = red_bytes + tile <= cap;
-    f.keep_z = f.keep_g && red_bytes + 2 * tile <= cap;
+    f.keep_g = geo.keep[0];
+    f.keep_z = geo.keep[1];
     if (!f.keep_g && mask == 1 && !p.write_g) return hipErrorInvalidValue;
-    const size_t lds = red_bytes + (f.keep_g ? tile : 0) + (f.keep_z ? tile : 0);
+    const size_t lds = geo.lds;
     if (mask == 3) hipLaunchKernelGGL((bn_bwd_fused_kernel<3, 0>), dim3(G), dim3(1024), lds, s, p, f);
     else if (mask == 1 && p.write_g) hipLaunchKernelGGL((bn_bwd_fused_kernel<1, 1>), dim3(G), dim3(1024), lds, s, p, f);
     else if (mask == 1) hipLaunchKernelGGL((bn_bwd_fused_kernel<1, 0>), dim3(G), dim3(1024), lds, s, p, f);

@@ -53,6 +53,10 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* dpooled, 
     const int cv = C >> 3;
     const long total = (long)N * HW * cv;
     const float inv = 1.f / (float)HW;
+    // (a power-of-two H W -- every square crop -- makes the product by 1 / (H W) exact; any other map is divided: the product by the
+    //  rounded reciprocal is one fp32 ulp off the quotient now and then, which moved 1 element in 10,000 of a 3 x 5 map by an
+    //  element ulp)
+    const bool pow2 = (HW & (HW - 1)) == 0;
     for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
         const int c = (int)(it % cv) << 3;
         const long m = it / cv;
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* dpooled, 
         float v[8];
         const float* d = dpooled + (size_t)b * C + c;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = d[j] * inv;
+        for (int j = 0; j < 8; ++j) v[j] = pow2 ? d[j] * inv : d[j] / (float)HW;
         *reinterpret_cast<uint4*>(dact + (size_t)m * C + c) = pack8(v);
     }
 }

@@ -143,6 +143,10 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
 hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd, const float* mean,
                                  const float* rstd, unsigned char* mask_out, bf16_t* dz, int dzpad, int mode, hipStream_t stream);
 bool vpd_bn_bwd_fused_ok(int M, int C, bool mask_act, bool write_g);
+// what both fused backward launchers derive from (M, C) on this device: blocks, pixels per block, pixel iterations per thread, which
+// of g / z (/ the second z) stay in LDS across the grid barrier, dynamic LDS bytes (nt = 2: one BatchNorm, 3: the pair kernel)
+struct BnBwdFusedGeom { int G, ppb, iters, keep[3]; size_t lds; };
+BnBwdFusedGeom vpd_bn_bwd_fused_geom(int M, int C, int nt);
 hipError_t vpd_launch_bn_bwd_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s);
 // BatchNorm backward whose sums (sum g, sum g * z) the producing data gradient's epilogue has already added to `f.rows`
 // (ConvParams::bst_z): finalize + apply in one launch, no reduction pass, no grid barrier.  p.mask_bits is required.

@@ -24,7 +24,7 @@ int fail(const char* what, hipError_t e) {
 
 extern "C" const char* vpd_last_error(void) { return g_err.c_str(); }
 extern "C" const char* vpd_elem_dtype(void) { return VPD_ELEM_NAME; }      // "bf16" (libvpdhip.so) or "fp16" (libvpdhip_f16.so)
-extern "C" int vpd_abi_version(void) { return 3; }      // 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state)
+extern "C" int vpd_abi_version(void) { return 4; }      // 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
 
 namespace {
 
@@ -837,6 +837,151 @@ extern "C" int vpd_op_bn_backward_apply(const void* dy, const void* z, const uns
     memset(&f, 0, sizeof f);
     f.rows = const_cast<double*>(rows); f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
     LCHECK(vpd_launch_bn_bwd_apply_fused(b, f, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- stem pool, BatchNorm backward launchers, head: the product launchers unchanged, parameters from flat arguments ----
+extern "C" int vpd_op_stem_pool_forward(const void* z, const float* scale, const float* shift, void* out_padded,
+                                        unsigned char* idx, int n, int Hz, int Wz, int C, int opad, void* stream) {
+    if (!z || !scale || !shift || !out_padded) return fail("null argument");
+    if (n < 1 || Hz < 1 || Wz < 1 || C < 8 || C % 8 || opad < 0) return fail("bad shape");
+    StemPoolParams q;
+    memset(&q, 0, sizeof q);
+    q.z = (const bf16_t*)z; q.Hz = Hz; q.Wz = Wz; q.scale = scale; q.shift = shift;
+    q.out = (bf16_t*)out_padded; q.opad = opad; q.idx = idx;
+    q.N = n; q.Ho = (Hz - 1) / 2 + 1; q.Wo = (Wz - 1) / 2 + 1; q.C = C;
+    LCHECK(vpd_launch_stem_pool(q, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_stem_pool_backward(const void* dpool, const unsigned char* idx, const void* z, const float* mean,
+                                         const float* rstd, const float* scale, const float* shift, const float* gamma,
+                                         const float* beta, const void* pooled_padded, double* rows, float* coef, void* dz,
+                                         float* dgamma, float* dbeta, int n, int Hz, int Wz, int C, void* stream) {
+    if (!dpool || !idx || !z || !mean || !rstd || !scale || !shift || !gamma || !beta || !rows || !coef || !dz || !dgamma || !dbeta)
+        return fail("null argument");
+    if (n < 1 || Hz < 1 || Wz < 1 || C < 8 || C % 8 || 256 % (C / 8)) return fail("bad shape");
+    StemPoolBwdParams sb;
+    memset(&sb, 0, sizeof sb);
+    sb.dpool = (const bf16_t*)dpool; sb.idx = idx; sb.z = (const bf16_t*)z;
+    sb.mean = mean; sb.rstd = rstd; sb.scale = scale; sb.shift = shift; sb.partials = rows;
+    sb.pooled = (const bf16_t*)pooled_padded; sb.ppad = 1; sb.gamma_p = gamma; sb.beta_p = beta;
+    sb.M = n * Hz * Wz; sb.Hz = Hz; sb.Wz = Wz; sb.Ho = (Hz - 1) / 2 + 1; sb.Wo = (Wz - 1) / 2 + 1; sb.C = C;
+    LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, gamma, dgamma, dbeta, coef, (bf16_t*)dz, (hipStream_t)stream));
+    return 0;
+}
+
+static BnBwdParams op_bn_bwd_params(void* dy, const void* z, const void* act_padded, const float* mean, const float* rstd,
+                                    void* dz, int dzpad, int n, int H, int W, int C) {
+    BnBwdParams b;
+    memset(&b, 0, sizeof b);
+    b.dy = (const bf16_t*)dy; b.dy_rw = (bf16_t*)dy; b.z = (const bf16_t*)z;
+    b.act = (const bf16_t*)act_padded; b.aHp = H + 2; b.aWp = W + 2; b.apad = 1;
+    b.mean = mean; b.rstd = rstd;
+    b.dz = (bf16_t*)dz; b.dzHp = H + 2 * dzpad; b.dzWp = W + 2 * dzpad; b.dzpad = dzpad;
+    b.M = n * H * W; b.H = H; b.W = W; b.C = C;
+    return b;
+}
+
+extern "C" int vpd_op_bn_backward(void* dy, const void* z, const void* act_padded, const unsigned char* mask_bits,
+                                  const float* mscale, const float* mshift, const float* dy_pooled, double* rows, float* coef,
+                                  void* sync, unsigned* err, const float* gamma, const float* mean, const float* rstd, void* dz,
+                                  int dzpad, float* dgamma, float* dbeta, int n, int H, int W, int C, int write_g, int fused,
+                                  void* stream) {
+    if (!dy || !z || !rows || !gamma || !mean || !rstd || !dz || !dgamma || !dbeta) return fail("null argument");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || dzpad < 0) return fail("bad shape");
+    if ((mscale == nullptr) != (mshift == nullptr)) return fail("mscale and mshift come together");
+    if ((act_padded != nullptr) + (mask_bits != nullptr) + (mscale != nullptr) > 1) return fail("one ReLU mask at most");
+    if (write_g && !act_padded) return fail("write_g goes with the activation mask");
+    BnBwdParams b = op_bn_bwd_params(dy, z, act_padded, mean, rstd, dz, dzpad, n, H, W, C);
+    b.coef = coef; b.partials = rows; b.write_g = write_g; b.mscale = mscale; b.mshift = mshift; b.mask_bits = mask_bits;
+    if (!fused) {
+        if (mask_bits || dy_pooled) return fail("the three-launch path takes neither a ReLU bit map nor a pooled gradient");
+        if (!coef) return fail("the three-launch path needs coef");
+        LCHECK(vpd_launch_bn_bwd(b, (float)b.M, gamma, dgamma, dbeta, (hipStream_t)stream));
+        return 0;
+    }
+    if (!sync || !err) return fail("the fused launch needs sync and err");
+    if (!vpd_bn_bwd_fused_ok(b.M, C, act_padded != nullptr, write_g != 0)) return fail("no fused BatchNorm backward for this shape");
+    if (dy_pooled) {
+        if (!mask_bits) return fail("the folded average-pool gradient needs the ReLU bit map");
+        if ((H * W) & (H * W - 1)) return fail("the folded average-pool gradient takes a power-of-two H W (vpd_op_avgpool_bwd first otherwise)");
+        b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)(H * W);
+    }
+    BnFusedBwd f;
+    memset(&f, 0, sizeof f);
+    f.rows = rows; f.sync = sync; f.err = err; f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
+    LCHECK(vpd_launch_bn_bwd_fused(b, f, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_bn_backward_pair(void* dy, const void* act_padded, const void* zA, const float* meanA, const float* rstdA,
+                                       const float* gammaA, double* rowsA, void* dzA, float* dgammaA, float* dbetaA,
+                                       const void* zB, const float* meanB, const float* rstdB, const float* gammaB,
+                                       double* rowsB, void* dzB, float* dgammaB, float* dbetaB, void* sync, unsigned* err, int n,
+                                       int H, int W, int C, void* stream) {
+    if (!dy || !act_padded || !zA || !meanA || !rstdA || !gammaA || !rowsA || !dzA || !dgammaA || !dbetaA || !zB || !meanB ||
+        !rstdB || !gammaB || !rowsB || !dzB || !dgammaB || !dbetaB || !sync || !err)
+        return fail("null argument");
+    if (n < 1 || H < 1 || W < 1) return fail("bad shape");
+    if (!vpd_bn_bwd_fused2_ok(n * H * W, C)) return fail("no paired BatchNorm backward for this shape");
+    BnBwdParams b = op_bn_bwd_params(dy, zA, act_padded, meanA, rstdA, dzA, 1, n, H, W, C);
+    BnFusedBwd fA, fB;
+    memset(&fA, 0, sizeof fA);
+    memset(&fB, 0, sizeof fB);
+    fA.rows = rowsA; fA.gamma = gammaA; fA.dgamma = dgammaA; fA.dbeta = dbetaA; fA.count = (float)b.M;
+    fB.rows = rowsB; fB.gamma = gammaB; fB.dgamma = dgammaB; fB.dbeta = dbetaB; fB.count = (float)b.M;
+    fA.sync = fB.sync = sync; fA.err = fB.err = err;
+    LCHECK(vpd_launch_bn_bwd_fused2(b, fA, fB, (const bf16_t*)zB, meanB, rstdB, (bf16_t*)dzB, (hipStream_t)stream));
+    return 0;
+}
+
+// host-only: out4 = {blocks, g resident, z (pair: zA) resident, pair: zB resident} of the fused backward of n H W x C on this device
+extern "C" int vpd_op_bn_backward_residency(int M, int C, int pair, int* out4) {
+    if (!out4 || M < 1 || C < 64 || C > 2048 || C % 8 || 1024 % (C / 8)) return fail("bad argument");
+    const BnBwdFusedGeom q = vpd_bn_bwd_fused_geom(M, C, pair ? 3 : 2);
+    out4[0] = q.G; out4[1] = q.keep[0]; out4[2] = q.keep[1]; out4[3] = q.keep[2];
+    return 0;
+}
+
+extern "C" int vpd_op_avgpool(const void* act_padded, int n, int H, int W, int C, int pad, float* pooled, void* stream) {
+    if (!act_padded || !pooled) return fail("null argument");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || pad < 0) return fail("bad shape");
+    LCHECK(vpd_launch_avgpool((const bf16_t*)act_padded, H + 2 * pad, W + 2 * pad, pad, H, W, C, n, pooled, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_avgpool_bwd(const float* dpooled, int n, int H, int W, int C, void* dact, void* stream) {
+    if (!dpooled || !dact) return fail("null argument");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
+    LCHECK(vpd_launch_avgpool_bwd(dpooled, H, W, C, n, (bf16_t*)dact, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_sgemm(const float* A, const float* B, float* Y, const float* bias, int M, int N, int K, int ta, int tb,
+                            int relu, void* stream) {
+    if (!A || !B || !Y) return fail("null argument");
+    if (M < 1 || N < 1 || K < 1) return fail("bad shape");
+    LCHECK(vpd_launch_sgemm(A, B, Y, bias, M, N, K, ta, tb, relu, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_colsum(const float* A, int M, int N, float* out, void* stream) {
+    if (!A || !out || M < 1 || N < 1) return fail("bad argument");
+    LCHECK(vpd_launch_colsum(A, M, N, out, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_relu_mask(float* d, const float* act, long long n, void* stream) {
+    if (!d || !act || n < 1) return fail("bad argument");
+    LCHECK(vpd_launch_relu_mask(d, act, (long)n, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_mse(const float* e, const float* t, long long n, float* de, float* loss_step, double* loss_accum,
+                          void* stream) {
+    if (!e || !t || n < 1) return fail("bad argument");
+    LCHECK(vpd_launch_mse(e, t, (long)n, de, loss_step, loss_accum, (hipStream_t)stream));
     return 0;
 }
 

@@ -351,7 +351,9 @@ hipError_t run_bn_bwd(const Ctx& c, const ConvInfo& cv, bf16_t* dy, const bf16_t
     if (reduce_done) b.act = nullptr;        // dy already holds g (masked by the producing dgrad kernel)
     const bool fused = c.fused(cv) && !reduce_done && vpd_bn_bwd_fused_ok(b.M, b.C, b.act != nullptr, write_g != 0);
     if (dy_pooled) {
-        if (fused && mask_bits && vpd_switches().poolbwd_fold) { b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)(cv.Hout * cv.Wout); }
+        // (the fold multiplies by 1 / (H W), exact for a power-of-two map; any other map takes avgpool_bwd_kernel's division)
+        const int hw = cv.Hout * cv.Wout;
+        if (fused && mask_bits && vpd_switches().poolbwd_fold && (hw & (hw - 1)) == 0) { b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)hw; }
         else {
             hipError_t e = vpd_launch_avgpool_bwd(dy_pooled, cv.Hout, cv.Wout, cv.Co, c.n, dy, c.s);
             if (e != hipSuccess) return e;
