@@ -276,6 +276,20 @@ int vpd_op_conv2d_ep(const void* x_bf16, const void* w_bf16, void* y_bf16, int n
 int vpd_op_conv2d_bnsums(const void* x_bf16, const void* w_bf16, void* y_bf16, const void* bst_z_bf16,
                          const unsigned char* bst_mask, double* rows, int n, int xHp, int xWp, int xC, int Hs, int Ws,
                          int Kc, int Co, const int* tapset9, int accumulate, void* stream);
+/* ... accumulating onto y, with the sums of TWO BatchNorms fed by the same g (epilogue mode 8: the first block of a stage,
+ * whose input gradient goes to the bn2 of the block before and to the 1x1 branch's BatchNorm): rows as above, rows2 f64
+ * [4][2][Co] (pre-zeroed) receive sum g and sum g * z2. */
+int vpd_op_conv2d_bnsums2(const void* x_bf16, const void* w_bf16, void* y_bf16, const void* bst_z_bf16,
+                          const unsigned char* bst_mask, double* rows, const void* bst_z2_bf16, double* rows2, int n, int xHp,
+                          int xWp, int xC, int Hs, int Ws, int Kc, int Co, const int* tapset9, void* stream);
+/* Host-only: what the convolution launcher decides, by its own code, for the arguments of a vpd_op_conv2d* call on the current
+ * device.  flags: 1 statistics rows, 2 eval epilogue, 4 acc_mask, 8 BatchNorm sums, 16 of two BatchNorms.  out12 = {kernel class
+ * (0 conv3x3_c64_persistent, 1 256 x 128, 2 128 x 128, 3 128 x 64, 6 256 x 64 tiles of conv3x3_ws / conv3x3_pws, 4 gather family,
+ * 5 stem), persistent conv3x3_pws_kernel, image width of its compile-time-geometry instantiation or 0, conv3x3_c64x2 twin,
+ * conv1x1_ws_kernel, conv1x1_stream_kernel, legacy conv3x3_halo_kernel, tile pixels, tile channels, epilogue mode, pixel tiles
+ * of the busiest block, flags & 8: a kernel takes the sums}. */
+int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub, int oph,
+                           int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags, int* out12);
 /* BatchNorm2d in training mode as the plan runs it (one launch: finalize + apply; models/module.py:41-43 + nn.BatchNorm2d):
  * rows f64 [4][2][C] hold the per-channel sum / sum of squares of z as the producing convolution's epilogue left them;
  * writes mean, rstd, scale = gamma rstd, shift = beta - mean scale, updates running_mean / running_var (momentum, unbiased
@@ -348,7 +362,9 @@ int vpd_op_tr_read_probe(const void* tile_bf16, void* out_bf16, void* stream);
  * form vpd_backward uses per ResNet stage; reference: the weight half of loss.backward(), models/util.py:52).
  * dims: 7 ints per problem {n, H, W, Co, Ci, stride, k} (H, W: output size; stride 1 or 2; k = 3: 3x3 pad 1, k = 1: 1x1 pad 0);
  * dz[i]: zero-bordered bf16 NHWC [n][H+2][W+2][Co]; x[i]: zero-bordered bf16 NHWC [n][stride*H+2][stride*W+2][Ci]; dw[i]: fp32
- * [k*k][Co][Ci]; slab[i]: vpd_op_wgrad128_slab_floats(Co, Ci) floats; dev_table: vpd_op_wgrad128_table_bytes() bytes. */
+ * [k*k][Co][Ci]; slab[i]: vpd_op_wgrad128_slab_floats(Co, Ci) floats; dev_table: vpd_op_wgrad128_table_bytes() bytes. 
+ * The schedule is rebuilt, uploaded into `table` and the stream synchronised on EVERY call (no cache keyed by the table's address:
+ * a freed and re-allocated table would be taken for uploaded): not usable under stream capture, and not a timing entry point. */
 size_t vpd_op_wgrad128_table_bytes(void);
 size_t vpd_op_wgrad128_slab_floats(int Co, int Ci);
 int vpd_op_wgrad128_group(int nprob, const void* const* dz, const void* const* x, float* const* dw, float* const* slab,

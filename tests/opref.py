@@ -1,5 +1,5 @@
 """Plain float64 PyTorch references, input generators and derived error bounds shared by the operator parity tests
-(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py).  Nothing here touches the GPU or the library:
+(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py, test_conv_ops_gpu.py).  Nothing here touches the GPU or the library:
 tests/test_opref_cpu.py pins what these references rest on, so that a failure on the GPU points at the kernel."""
 import math
 
@@ -314,3 +314,163 @@ def mse_int_operands(n, g):
     """integer e, t with |e - t| <= 6: sum d^2 <= 36 * 128000 < 2^24, two calls accumulated < 2^24 as well"""
     t = int_matrix((n,), -100, 100, g)
     return t + int_matrix((n,), -6, 6, g), t
+
+
+# ---------------------------------------------------------------------------
+# convolution family (tests/test_conv_ops_gpu.py, tests/conv_ops_child.py)
+# ---------------------------------------------------------------------------
+# Shapes are chosen by the kernel class vpd_launch_conv gives them on a 256-CU device; the GPU test asserts that class through
+# vpd_op_conv2d_dispatch before it launches.  blk_px: the most pixels ONE block accumulates statistics over in any run of the
+# case (tiles per block x tile pixels; few-blocks runs included), which bounds the fp32 per-block partial sums.
+#            crops Ci   Co   H   W  k stride
+CONV_CASES = {
+    "c0_w32":        dict(n=64,  ci=64,  co=64,  h=32, w=32, blk_px=2 * 128, wgrad="no_group"),   # layer1's rows: 512 tiles, two per block; eval: 256 tiles of c64x2
+    "c0_w16":        dict(n=203, ci=64,  co=64,  h=16, w=16, blk_px=2 * 128),       # 406 tiles of half an image
+    "c1_w16":        dict(n=203, ci=128, co=128, h=16, w=16, blk_px=9 * 256),       # 203 tiles of one image each: 256 x 128 with VPD_PWS=0 or few blocks
+    "c1_w16_device": dict(n=300, ci=128, co=128, h=16, w=16, blk_px=2 * 256),       # 300 > 256 tiles: the eight-wave persistent kernel, two tiles per block
+    "c6_w16":        dict(n=150, ci=128, co=128, h=16, w=16, blk_px=7 * 256, wgrad=True),  # 150 < 200 tiles of 256 x 128: 256 x 64, 128 lanes x 2 channel tiles
+    "c6_w8_ragged":  dict(n=203, ci=256, co=256, h=8,  w=8,  blk_px=9 * 256),       # 50.75 tiles of four images x 4 channel tiles
+    "c6_w8_device":  dict(n=300, ci=256, co=256, h=8,  w=8,  blk_px=2 * 256),       # 75 tiles on 64 lanes
+    "c2_w4_ragged":  dict(n=403, ci=512, co=512, h=4,  w=4,  blk_px=9 * 128),       # 50.4 tiles of eight images x 4 channel tiles
+    "c3_w4":         dict(n=37,  ci=512, co=512, h=4,  w=4,  blk_px=2 * 128, wgrad=True),   # 4.6 tiles x 8 channel tiles
+    "c3_w4_device":  dict(n=320, ci=512, co=512, h=4,  w=4,  blk_px=2 * 128),       # 40 tiles on 32 lanes
+    "c3_two_chunks": dict(n=21,  ci=128, co=128, h=4,  w=4,  blk_px=3 * 128),       # two 64-channel chunks: 18 K-steps per tile
+    # stride 2 at the stage boundaries: the forward is the ring GEMM's, the data gradient four parity classes of conv_igemm_kernel
+    # in its three tile shapes (128 x 64: 64 output channels; 64 x 64: few tiles; 128 x 128: 384 tiles and more)
+    "s2_w32":        dict(n=100, ci=64,  co=128, h=32, w=32, stride=2, blk_px=256, wgrad=True),
+    "s2_w8":         dict(n=5,   ci=256, co=512, h=8,  w=8,  stride=2, blk_px=256),
+    "s2_w16_big":    dict(n=768, ci=128, co=256, h=16, w=16, stride=2, blk_px=256),
+    # stem (class 5, conv_stem_persistent_kernel): 7x7 stride 2 on the 5-channel input at the student's real size, 512 tiles of two
+    # output rows, two per block; and a 32 x 32 input (eight output rows per tile)
+    "stem_w128":     dict(n=16,  ci=5,   co=64,  h=128, w=128, k=7, stride=2, stem=True, blk_px=2 * 128),
+    "stem_w32":      dict(n=6,   ci=5,   co=64,  h=32, w=32, k=7, stride=2, stem=True, blk_px=128),
+    # 1x1 ring GEMM (conv1x1_ws_kernel): K = 512, 200 tiles of 256 x 128
+    "ring_1x1":      dict(n=50,  ci=512, co=128, h=32, w=32, k=1, blk_px=256),
+}
+for _c in CONV_CASES.values():
+    _c.setdefault("k", 3)
+    _c.setdefault("stride", 1)
+CONV_SEEDS = (11,)
+CONV_ZMAX = 3                      # |z|, |old|, |res|, |shift| of the integer regime
+
+
+def conv_geom(cs):
+    k, st = cs["k"], cs["stride"]
+    pad = k // 2
+    ho, wo = (cs["h"] + 2 * pad - k) // st + 1, (cs["w"] + 2 * pad - k) // st + 1
+    return k, st, pad, ho, wo
+
+
+def _sparse_int(shape, density, g, lo=1):
+    """integers: 0 with probability 1 - density, else +-1 .. +-lo"""
+    v = torch.randint(1, lo + 1, shape, generator=g).double() * torch.where(torch.rand(shape, generator=g) < 0.5, -1.0, 1.0)
+    return v * (torch.rand(shape, generator=g) < density)
+
+
+def conv_operands(cs, seed, regime, name="bf16"):
+    """x, w, dz and the epilogue operands (NCHW, float64 values that the element type holds exactly).
+    integer: x, dz in {-1, 0, 1} with density 1/2, w in {-1, 0, 1} with density 288 / K (K = taps x the larger channel count:
+    a sum of K products has standard deviation 12, 2^8 is beyond twenty sigma), old / res / z / shift integers up to CONV_ZMAX,
+    scale 1 or 2.  random: randn rounded to the element type, He-scaled weights, scale in [0.5, 1.5]."""
+    k, st, pad, ho, wo = conv_geom(cs)
+    n, ci, co, h, w = cs["n"], cs["ci"], cs["co"], cs["h"], cs["w"]
+    g = torch.Generator().manual_seed(seed * 1000 + n + ci + h)
+    o = {}
+    if regime == "int":
+        dens = min(0.5, 288.0 / (k * k * (ci if cs.get("stem") else max(ci, co))))
+        o["x"], o["dz"] = _sparse_int((n, ci, h, w), 0.5, g), _sparse_int((n, co, ho, wo), 0.5, g)
+        o["w"] = _sparse_int((co, ci, k, k), dens, g)
+        small = lambda shape: torch.randint(-CONV_ZMAX, CONV_ZMAX + 1, shape, generator=g).double()
+        o["scale"] = torch.randint(0, 2, (co,), generator=g).double() + 1.0
+        o["shift"] = small((co,))
+        er = lambda t: t
+    else:
+        er = lambda t: elem_round(t, name).double()
+        o["x"], o["dz"] = er(torch.randn(n, ci, h, w, generator=g)), er(torch.randn(n, co, ho, wo, generator=g))
+        o["w"] = er(torch.randn(co, ci, k, k, generator=g) * (2.0 / (ci * k * k)) ** 0.5)
+        small = lambda shape: er(torch.randn(shape, generator=g))
+        o["scale"] = (torch.rand(co, generator=g) + 0.5).float().double()
+        o["shift"] = (torch.randn(co, generator=g) * 0.3).float().double()
+    # forward side (output [n, co, ho, wo]): residual, old value; data-gradient side (output [n, ci, h, w]): old value, z, z2
+    o["res"], o["old_y"] = small((n, co, ho, wo)), small((n, co, ho, wo))
+    o["old_dx"], o["z"], o["z2"] = small((n, ci, h, w)), small((n, ci, h, w)), small((n, ci, h, w))
+    o["keep_y"] = torch.rand((n, co, ho, wo), generator=g) > 0.4          # ReLU bit maps
+    o["keep_dx"] = torch.rand((n, ci, h, w), generator=g) > 0.4
+    return o
+
+
+def conv_fwd(x, w, cs):
+    k, st, pad, _, _ = conv_geom(cs)
+    return F.conv2d(x.double(), w.double(), None, stride=st, padding=pad)
+
+
+def conv_dgrad(dz, w, cs):
+    k, st, pad, ho, wo = conv_geom(cs)
+    oph, opw = cs["h"] - ((ho - 1) * st + k - 2 * pad), cs["w"] - ((wo - 1) * st + k - 2 * pad)
+    return F.conv_transpose2d(dz.double(), w.double(), None, stride=st, padding=pad, output_padding=(oph, opw))
+
+
+def conv_wgrad(x, dz, cs):
+    k, st, pad, _, _ = conv_geom(cs)
+    return torch.nn.grad.conv2d_weight(x.double(), (cs["co"], cs["ci"], k, k), dz.double(), stride=st, padding=pad)
+
+
+def conv_eval_ep(conv, o, res, relu):
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    y = conv * v(o["scale"]) + v(o["shift"])
+    if res:
+        y = y + o["res"]
+    return y.clamp_min(0) if relu else y
+
+
+# The MFMA accumulator.  Products of two element-type values are exact in fp32 (8 + 8 or 11 + 11 significand bits).  Nothing
+# public states that the bf16 / fp16 MFMA of gfx950 rounds every internal addition to nearest, so the bound assumes the weaker
+# thing a hardware adder tree can do: each of the K additions (and the few that join partial accumulators: + 4) may TRUNCATE,
+# losing up to one ulp = 2^-23 of a partial sum whose magnitude conv(|x|, |w|) bounds.  c = 2 against round-to-nearest's 1.
+CONV_ACC_C = 2.0
+
+
+def conv_gamma(mag, K):
+    return CONV_ACC_C * (K + 4) * 2.0 ** -24 * mag
+
+
+def conv_bound(ref, gamma, name, extra=0.0):
+    """|got - ref| <= half an element ulp at |ref| + what the fp32 value may be off by, + that; extra: the epilogue's own fp32 terms"""
+    gm = gamma + extra
+    return 0.5 * ulp(ref.abs() + gm, name) + gm
+
+
+def conv_alter_tap(ref, x, w, cs, row=None):
+    """(i) tap (0, k - 1) left out for the pixels of one output row of image 0"""
+    k, st, pad, ho, wo = conv_geom(cs)
+    row = ho // 2 if row is None else row
+    w1 = torch.zeros_like(w)
+    w1[:, :, 0, k - 1] = w[:, :, 0, k - 1]
+    out = ref.clone()
+    out[0, :, row, :] -= conv_fwd(x[0:1], w1, cs)[0, :, row, :]
+    return out
+
+
+def conv_alter_chunks(ref, x, w, cs):
+    """(ii) two neighbouring 64-channel chunks of the weights swapped (fewer than 128 input channels: the two halves), image 0"""
+    c = 64 if cs["ci"] >= 128 else cs["ci"] // 2
+    w1 = w.clone()
+    w1[:, :c], w1[:, c:2 * c] = w[:, c:2 * c], w[:, :c]
+    out = ref.clone()
+    out[0:1] = conv_fwd(x[0:1], w1, cs)
+    return out
+
+
+def conv_alter_shift(conv, other):
+    """(iii) the residual / old value (already masked, where a bit map applies) one pixel to the right"""
+    return conv + torch.roll(other, 1, dims=3)
+
+
+def conv_alter_tile(ref, tile_px, tile=1):
+    """(iv) the pixels of one tile (NHWC pixel order) taken from one image further on"""
+    n, c, h, w = ref.shape
+    flat = nhwc(ref).reshape(n * h * w, c).clone()
+    px = min(tile_px, n * h * w - h * w)                 # (a case smaller than two tiles: as many pixels as there are)
+    lo = max(0, min(tile * px, n * h * w - px - h * w))
+    flat[lo:lo + px] = flat[lo + h * w:lo + h * w + px].clone()
+    return nchw(flat.view(n, h, w, c))

@@ -106,6 +106,35 @@ def test_plan_rejects_bad_arguments():
     assert L.vpd_plan_create(b"resnet34", 5, 127, 128, 128, 0, 4, 1, C.byref(h)) != 0
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_conv_dispatch_and_two_batchnorm_sums_reject_bad_arguments(dtype):
+    """ABI 5: vpd_op_conv2d_dispatch (host-only) and vpd_op_conv2d_bnsums2 return non-zero with a message on null or malformed
+    arguments, before anything is launched."""
+    from vpd_amd import _lib
+    h = _lib.lib(dtype)
+    out = (C.c_int * 12)()
+    taps = (C.c_int * 9)(3, 3, 0, 1, 0, 1, 0, 3, 1)
+    good = [4, 18, 18, 128, 16, 16, 128, 0, 16, 16, 1, 0, 0, 1, 128, 128]
+    assert h.vpd_op_conv2d_dispatch(*good, taps, 0, 1, out) == 0 and out[9] == 1 and out[7] in (128, 256)
+    assert h.vpd_op_conv2d_dispatch(*good, None, 0, 1, out) != 0 and b"null argument" in h.vpd_last_error()
+    assert h.vpd_op_conv2d_dispatch(*good, taps, 0, 1, None) != 0 and b"null argument" in h.vpd_last_error()
+    for pos, bad in ((0, 0), (14, 96), (15, 32), (10, 0), (13, 0), (6, 64)):      # crops, Kc, Co, osub, istr, yC < Co
+        args = list(good)
+        args[pos] = bad
+        assert h.vpd_op_conv2d_dispatch(*args, taps, 0, 1, out) != 0 and b"bad argument" in h.vpd_last_error(), pos
+    assert h.vpd_op_conv2d_dispatch(*good, taps, 0, 64, out) != 0 and b"bad argument" in h.vpd_last_error()
+    assert h.vpd_op_conv2d_dispatch(*good, taps, 1, 16, out) != 0 and b"second BatchNorm" in h.vpd_last_error()
+    assert h.vpd_op_conv2d_dispatch(*good, (C.c_int * 9)(0, 3, 0, 1, 0, 1, 0, 3, 1), 0, 1, out) != 0 and b"empty tap set" in h.vpd_last_error()
+    p = C.c_void_p(64)                                    # never dereferenced: every call below is rejected on the host
+    assert h.vpd_op_conv2d_bnsums2(p, p, p, p, p, p, None, p, 4, 18, 18, 128, 16, 16, 128, 128, taps, None) != 0
+    assert b"null argument" in h.vpd_last_error()
+    assert h.vpd_op_conv2d_bnsums2(p, p, p, p, p, p, p, None, 4, 18, 18, 128, 16, 16, 128, 128, taps, None) != 0
+    assert h.vpd_op_conv2d_bnsums2(None, p, p, p, p, p, p, p, 4, 18, 18, 128, 16, 16, 128, 128, taps, None) != 0
+    assert h.vpd_op_conv2d_bnsums2(p, p, p, p, p, p, p, p, 4, 18, 18, 128, 16, 16, 100, 128, taps, None) != 0
+    assert b"bad argument" in h.vpd_last_error()
+    assert h.vpd_op_conv2d_bnsums2(p, p, p, p, p, p, p, p, 4, 18, 18, 128, 16, 16, 128, 128, None, None) != 0
+
+
 def test_product_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

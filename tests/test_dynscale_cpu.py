@@ -1,5 +1,5 @@
 """Dynamic loss scaling (vpd_amd.models.util.DynamicLossScaler, vpd_scale_state in include/vpd_hip.h), the part that needs no GPU:
-both libraries export the entry points (ABI 3 onwards; 4 today), host-side argument validation, and the command line."""
+both libraries export the entry points (ABI 3 onwards; 5 today), host-side argument validation, and the command line."""
 import ctypes as C
 import os
 import subprocess
@@ -17,9 +17,9 @@ def test_both_libraries_export_the_dynamic_scaling_entry_points(dtype):
     from vpd_amd import _lib
     from vpd_amd.models.util import DynamicLossScaler, LossScaler
     assert issubclass(DynamicLossScaler, LossScaler)
-    assert _lib.ABI_VERSION == 4
+    assert _lib.ABI_VERSION == 5
     h = _lib.lib(dtype)
-    assert h.vpd_abi_version() == 4
+    assert h.vpd_abi_version() == 5
     for n in NEW:
         assert n in _lib.SIGNATURES and getattr(h, n) is not None
     # the set-state entry point: a NULL plan is an error with a message; NULL state on a plan switches back (host only)

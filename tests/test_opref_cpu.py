@@ -1,5 +1,11 @@
 """What the references of the operator parity tests (tests/opref.py) rest on, checked without a GPU, so that a failure of
-tests/test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py or test_head_ops_gpu.py points at the kernel and not at its reference."""
+tests/test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py or test_conv_ops_gpu.py points at the kernel and not
+at its reference."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -148,3 +154,116 @@ def test_float_reciprocal_division_is_exact_below_2_pow_21():
         rcp = np.float32(1.0) / np.float32(d)
         q = (mf * rcp).astype(np.int64)                      # fp32 product, truncated
         assert np.array_equal(q, m // d), d
+
+
+# ---------------------------------------------------------------------------
+# convolution family
+# ---------------------------------------------------------------------------
+CONV_IDS = list(R.CONV_CASES)
+
+
+def _tile_px(cs):
+    return 256 if cs["blk_px"] % 256 == 0 else 128
+
+
+@pytest.mark.parametrize("case", CONV_IDS)
+@pytest.mark.parametrize("seed", R.CONV_SEEDS)
+def test_conv_integer_regime_is_exact_and_representable_and_sees_the_four_faults(case, seed):
+    """From the reference alone, no element left out: every operand is a bf16 and an fp16 value; every result of every operation the
+    GPU test runs (forward, the four eval epilogues, data gradient, accumulate, masked accumulate) has magnitude <= 2^8 (bf16's
+    integers; fp16's reach 2^11); every fp32 partial sum stays below 2^24 -- a convolution's by the sum of |products|, a block's
+    statistics by (pixels it accumulates) x max^2, the BatchNorm sums by x max x |z|, a weight gradient's by the pixel count.
+    And each of the four altered references differs from the right one."""
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    cs = R.CONV_CASES[case]
+    o = R.conv_operands(cs, seed, "int")
+    for key in ("x", "w", "dz", "res", "old_y", "old_dx", "z", "z2", "scale", "shift"):
+        for name in ("bf16", "fp16"):
+            assert torch.equal(R.elem_round(o[key].float(), name).double(), o[key]), (key, name)
+    cap = 2.0 ** R.ELEM["bf16"][1]
+    conv, dx = R.conv_fwd(o["x"], o["w"], cs), R.conv_dgrad(o["dz"], o["w"], cs)
+    # (operands in {-1, 0, 1}: the sum of |products| of a convolution is at most its K)
+    assert max(float(o[k].abs().max()) for k in ("x", "w", "dz")) == 1.0 and cs["k"] ** 2 * max(cs["ci"], cs["co"]) < 2 ** 24
+    results = {"fwd": conv, "dgrad": dx, "acc": dx + o["old_dx"], "macc": dx + o["old_dx"] * o["keep_dx"]}
+    for res in (0, 1):
+        for relu in (0, 1):
+            results["ep%d%d" % (res, relu)] = R.conv_eval_ep(conv, o, res, relu)
+    pre = R.conv_eval_ep(conv, o, 1, 0)
+    for key, t in results.items():
+        assert float(t.abs().max()) <= cap, (key, float(t.abs().max()))
+        assert torch.equal(t, t.round())
+    fmax, dmax = float(conv.abs().max()), float(results["acc"].abs().max())
+    assert cs["blk_px"] * fmax * fmax < 2.0 ** 24                       # per-block sum of squares of the forward statistics
+    assert cs["blk_px"] * dmax * R.CONV_ZMAX < 2.0 ** 24                # per-block sum g z of the BatchNorm sums
+    assert cs["n"] * conv.shape[2] * conv.shape[3] < 2 ** 24            # weight gradient: at most one unit per output pixel
+    # the four faults, each visible to equality
+    assert not torch.equal(R.conv_alter_tap(conv, o["x"], o["w"], cs), conv)
+    assert not torch.equal(R.conv_alter_chunks(conv, o["x"], o["w"], cs), conv)
+    assert not torch.equal(R.conv_alter_tile(conv, _tile_px(cs)), conv)
+    assert not torch.equal(R.conv_alter_tile(dx, _tile_px(cs)), dx)
+    assert not torch.equal(R.conv_alter_shift(pre - o["res"], o["res"]), pre)
+    assert not torch.equal(R.conv_alter_shift(dx, o["old_dx"]), results["acc"])
+    assert not torch.equal(R.conv_alter_shift(dx, o["old_dx"] * o["keep_dx"]), results["macc"])
+    assert not torch.equal(dx + o["old_dx"] * torch.roll(o["keep_dx"], 1, dims=3), results["macc"])
+
+
+@pytest.mark.parametrize("case", CONV_IDS)
+@pytest.mark.parametrize("name", ["bf16", "fp16"])
+def test_conv_random_regime_bound_rejects_the_four_faults(case, name):
+    """The per-element bound of the randn regime accepts the reference evaluated in fp32 (what a correct kernel may do) and puts each
+    altered reference outside it in at least one element: a tap left out for one image row, two weight chunks swapped, the
+    residual one pixel off, one tile's pixels taken from the next image; on the data-gradient side a tile from the next image and the
+    old value / the ReLU bit map of the accumulate modes one pixel off."""
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    cs = R.CONV_CASES[case]
+    o = R.conv_operands(cs, R.CONV_SEEDS[0], "rand", name)
+    K = cs["k"] ** 2 * cs["ci"]
+    conv = R.conv_fwd(o["x"], o["w"], cs)
+    gamma = R.conv_gamma(R.conv_fwd(o["x"].abs(), o["w"].abs(), cs), K)
+    bound = R.conv_bound(conv, gamma, name)
+    stored32 = R.elem_round(F.conv2d(o["x"].float(), o["w"].float(), None, stride=cs["stride"], padding=cs["k"] // 2), name).double()
+    assert bool(((stored32 - conv).abs() <= bound).all())
+    outside = lambda alt, ref, b: bool(((alt - ref).abs() > b).any())
+    assert outside(R.conv_alter_tap(conv, o["x"], o["w"], cs), conv, bound)
+    assert outside(R.conv_alter_chunks(conv, o["x"], o["w"], cs), conv, bound)
+    assert outside(R.conv_alter_tile(conv, _tile_px(cs)), conv, bound)
+    v = lambda t: t.double().view(1, -1, 1, 1)
+    pre = R.conv_eval_ep(conv, o, 1, 0)
+    extra = 4 * 2.0 ** -24 * ((conv * v(o["scale"])).abs() + v(o["shift"]).abs() + o["res"].abs())
+    assert outside(R.conv_alter_shift(pre - o["res"], o["res"]), pre, R.conv_bound(pre, gamma * v(o["scale"]).abs(), name, extra))
+    if cs.get("stem"):
+        return
+    # data-gradient side: a tile from the next image, the old value and the ReLU bit map one pixel off
+    dx = R.conv_dgrad(o["dz"], o["w"], cs)
+    dgamma = R.conv_gamma(R.conv_dgrad(o["dz"].abs(), o["w"].abs(), cs), cs["k"] ** 2 * cs["co"])
+    assert outside(R.conv_alter_tile(dx, _tile_px(cs)), dx, R.conv_bound(dx, dgamma, name))
+    acc, macc = dx + o["old_dx"], dx + o["old_dx"] * o["keep_dx"]
+    extra = 2 * 2.0 ** -24 * (dx.abs() + o["old_dx"].abs())
+    assert outside(R.conv_alter_shift(dx, o["old_dx"]), acc, R.conv_bound(acc, dgamma, name, extra))
+    assert outside(dx + o["old_dx"] * torch.roll(o["keep_dx"], 1, dims=3), macc, R.conv_bound(macc, dgamma, name, extra))
+
+
+def test_conv_runs_dispatch_to_the_kernels_their_ids_name():
+    """vpd_op_conv2d_dispatch is host-only; without a device the launcher assumes 256 CUs, an MI355X's count: every run of the GPU
+    test must already dispatch as its id says here.  One child per switch setting (the switches are read once per process)."""
+    from tests.conv_ops_child import RUNS
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    by_env = {}
+    for run, (_, env, _, _) in RUNS.items():
+        by_env.setdefault(json.dumps(env, sort_keys=True), []).append(run)
+    seen = set()
+    for env, runs in by_env.items():
+        r = subprocess.run([sys.executable, os.path.join(repo, "tests", "conv_ops_child.py"), ",".join(runs), "dispatch"],
+                           env=dict(os.environ, **json.loads(env)), capture_output=True, text=True, timeout=300, cwd=repo)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        for ln in r.stdout.splitlines():
+            if ln.startswith("RESULT "):
+                out = json.loads(ln[len("RESULT "):])
+                assert not out["fail"], (out["run"], out["fail"])
+                seen.add(out["run"])
+    assert seen == set(RUNS)
+    # every 3x3 class in both forms, the geometry instantiations of all three widths, the gather family's tiles
+    forms = {(e["kclass"], e.get("pws"), e.get("geo")) for _, _, e, _ in RUNS.values()}
+    assert {(1, 0, None), (1, 1, 0), (2, 1, 0), (2, 0, None), (3, 1, 4), (3, 1, 0), (3, 0, None), (6, 1, 16), (6, 1, 8), (6, 1, 0),
+            (6, 0, None)} <= forms
+    assert {(d["bm"], d["bn"]) for _, _, _, d in RUNS.values() if d and d.get("ws1x1") == 0 and "bm" in d} == {(128, 128), (64, 64), (128, 64)}

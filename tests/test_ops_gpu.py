@@ -3,6 +3,7 @@ PyTorch fp32 on the CPU, on seeded inputs.  Operands are bf16 (inputs are
 rounded to bf16 first, so the comparison isolates accumulation order and the
 bf16 rounding of the output): tolerance rel-L2 <= 4e-3, stated per test."""
 import ctypes as C
+import zlib
 
 import numpy as np
 import pytest
@@ -42,12 +43,12 @@ def bf16_round(t):
     return t.to(torch.bfloat16).to(torch.float32)
 
 
-def to_padded_nhwc(x, pad_t, pad_l, pad_b, pad_r, slack=0):
-    """f32 NCHW (cpu) -> bf16 padded NHWC on the GPU (flat, with `slack` extra zero elements)."""
+def to_padded_nhwc(x, pad_t, pad_l, pad_b, pad_r, slack=0, dtype=torch.bfloat16):
+    """f32 NCHW (cpu) -> element-type (bf16) padded NHWC on the GPU (flat, with `slack` extra zero elements)."""
     n, c, h, w = x.shape
-    buf = torch.zeros(n, h + pad_t + pad_b, w + pad_l + pad_r, c, dtype=torch.bfloat16)
-    buf[:, pad_t:pad_t + h, pad_l:pad_l + w, :] = x.permute(0, 2, 3, 1).to(torch.bfloat16)
-    flat = torch.zeros(buf.numel() + slack, dtype=torch.bfloat16)
+    buf = torch.zeros(n, h + pad_t + pad_b, w + pad_l + pad_r, c, dtype=dtype)
+    buf[:, pad_t:pad_t + h, pad_l:pad_l + w, :] = x.permute(0, 2, 3, 1).to(dtype)
+    flat = torch.zeros(buf.numel() + slack, dtype=dtype)
     flat[:buf.numel()] = buf.flatten()
     return flat.cuda()
 
@@ -79,14 +80,14 @@ def run_conv(xp, wp, n, xHp, xWp, xC, yH, yW, ypad, Hs, Ws, osub, oph, opw, istr
     return y, stats
 
 
-def pack_fwd(w):
+def pack_fwd(w, dtype=torch.bfloat16):
     co, ci, kh, kw = w.shape
-    return w.permute(2, 3, 0, 1).reshape(kh * kw, co, ci).contiguous().to(torch.bfloat16).cuda()
+    return w.permute(2, 3, 0, 1).reshape(kh * kw, co, ci).contiguous().to(dtype).cuda()
 
 
-def pack_dgrad(w):
+def pack_dgrad(w, dtype=torch.bfloat16):
     co, ci, kh, kw = w.shape
-    return w.permute(2, 3, 1, 0).reshape(kh * kw, ci, co).contiguous().to(torch.bfloat16).cuda()
+    return w.permute(2, 3, 1, 0).reshape(kh * kw, ci, co).contiguous().to(dtype).cuda()
 
 
 def test_tr_read_probe():
@@ -135,7 +136,7 @@ CONV_CASES = [
 @pytest.mark.parametrize("case", CONV_CASES, ids=[c[0] for c in CONV_CASES])
 def test_conv_fwd_dgrad_wgrad(case):
     name, n, ci, co, h, w, k, stride, pad = case
-    g = torch.Generator().manual_seed(hash(name) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
     x = bf16_round(torch.randn(n, ci, h, w, generator=g))
     wt = bf16_round(torch.randn(co, ci, k, k, generator=g) * (2.0 / (ci * k * k)) ** 0.5)
     ho = (h + 2 * pad - k) // stride + 1
@@ -453,7 +454,7 @@ STREAM_CASES = [
 @pytest.mark.parametrize("case", STREAM_CASES, ids=[c[0] for c in STREAM_CASES])
 def test_conv1x1_stream_kernel(case):
     name, n, ci, co, h, w, stride = case
-    g = torch.Generator().manual_seed(hash(name) % 1000)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000)
     x = bf16_round(torch.randn(n, ci, h, w, generator=g))
     wt = bf16_round(torch.randn(co, ci, 1, 1, generator=g) * (2.0 / ci) ** 0.5)
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
@@ -508,7 +509,7 @@ def test_conv1x1_stream_kernel_eval_epilogue_and_masked_accumulate(case):
     Bottleneck's first data gradient lands on d(block output)."""
     name, n, ci, co, h, w = case
     L = _lib()
-    g = torch.Generator().manual_seed(hash(name) % 1000 + 7)
+    g = torch.Generator().manual_seed(zlib.crc32(name.encode()) % 1000 + 7)
     x = bf16_round(torch.randn(n, ci, h, w, generator=g))
     wt = bf16_round(torch.randn(co, ci, 1, 1, generator=g) * (2.0 / ci) ** 0.5)
     conv = F.conv2d(x, wt)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VPD_LIB_PATH") or os.path.join(_HERE, "libvpdhip.so")
 # the same sources built with fp16 elements (vpd_amd/csrc/Makefile, common.h "Element type"): training and inference
 LIB_PATH_F16 = os.environ.get("VPD_LIB_PATH_F16") or os.path.join(_HERE, "libvpdhip_f16.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 c_int_p = C.POINTER(C.c_int)
 c_ll_p = C.POINTER(C.c_longlong)
@@ -70,6 +70,8 @@ SIGNATURES = {
     "vpd_op_conv_bm": (C.c_int, [C.c_int, C.c_int]),
     "vpd_op_conv2d_ep": (C.c_int, [vp, vp, vp] + [C.c_int] * 13 + [c_int_p, vp, vp, vp, C.c_int, C.c_int, vp, vp]),
     "vpd_op_conv2d_bnsums": (C.c_int, [vp] * 6 + [C.c_int] * 8 + [c_int_p, C.c_int, vp]),
+    "vpd_op_conv2d_bnsums2": (C.c_int, [vp] * 8 + [C.c_int] * 8 + [c_int_p, vp]),
+    "vpd_op_conv2d_dispatch": (C.c_int, [C.c_int] * 16 + [c_int_p, C.c_int, C.c_int, c_int_p]),
     "vpd_op_bn_forward": (C.c_int, [vp] * 13 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
     "vpd_op_bn_backward_apply": (C.c_int, [vp] * 10 + [C.c_int] * 4 + [vp]),
     "vpd_op_stem_pool_forward": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [vp]),

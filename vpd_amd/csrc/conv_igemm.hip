@@ -868,12 +868,19 @@ static bool c64x2_geom(const ConvParams& p, HaloGeom* g) {
     g->rot = 0; g->rnch = 1.0f;
     return g->NHP <= C64X2_HPIX && p.M >= 256 * 256;      // at least one 256-pixel tile per CU (256 crops of 32 x 32: 1024 tiles)
 }
-static hipError_t launch_c64x2(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
-    const int ntiles = (p.M + 255) / 256;
+// Blocks of the resident-weight kernels (layer1's two, the stem): one per CU at most.  *per: consecutive tiles per block
+// (VPD_C64_CONTIG=0: 0, strided); the grid shrinks to the blocks that get tiles
+static int persistent_grid(int ntiles, int* per) {
     const int ncu = vpd_cu_budget();
     int grid = ntiles < ncu ? ntiles : ncu;
-    const int per = vpd_switches().c64_contig ? (ntiles + grid - 1) / grid : 0;
-    if (per > 0) grid = (ntiles + per - 1) / per;
+    *per = vpd_switches().c64_contig ? (ntiles + grid - 1) / grid : 0;
+    if (*per > 0) grid = (ntiles + *per - 1) / *per;
+    return grid;
+}
+static hipError_t launch_c64x2(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
+    const int ntiles = (p.M + 255) / 256;
+    int per;
+    const int grid = persistent_grid(ntiles, &per);
     const size_t lds = ((size_t)9 * 64 + 2 * C64X2_HPIX) * 64 * sizeof(bf16_t);
     ConvParams q = p;
     switch (conv_ep_mode(q)) {
@@ -888,11 +895,8 @@ static hipError_t launch_c64x2(const ConvParams& p, const HaloGeom& g, hipStream
 template <int HROWS>
 static hipError_t launch_c64(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
     const int ntiles = (p.M + 127) / 128;
-    const int ncu = vpd_cu_budget();
-    int grid = ntiles < ncu ? ntiles : ncu;
-    // consecutive tiles per block (VPD_C64_CONTIG=0: strided); the grid shrinks to the blocks that get tiles
-    const int per = vpd_switches().c64_contig ? (ntiles + grid - 1) / grid : 0;
-    if (per > 0) grid = (ntiles + per - 1) / per;
+    int per;
+    const int grid = persistent_grid(ntiles, &per);
     const size_t lds = ((size_t)9 * 64 + 2 * HROWS) * 64 * sizeof(bf16_t) + 2048;
     ConvParams q = p;
     // (the accumulate modes fetch the old values of y by dense pixel index ahead of the MFMA loop: conv_acc_prefetch)
@@ -1199,10 +1203,14 @@ static bool stem_eligible(const ConvParams& p, int* TR) {
     return rows <= 160 && p.M % 128 == 0;
 }
 
-static hipError_t launch_stem(const ConvParams& p, int TR, hipStream_t stream) {
+static int stem_grid(const ConvParams& p) {
     const int ntiles = p.M / 128;
     const int ncu = vpd_cu_budget();
-    const int grid = p.pool_y ? (p.N < ncu ? p.N : ncu) : (ntiles < ncu ? ntiles : ncu);      // pooled: whole images per block
+    return p.pool_y ? (p.N < ncu ? p.N : ncu) : (ntiles < ncu ? ntiles : ncu);      // pooled: whole images per block
+}
+static hipError_t launch_stem(const ConvParams& p, int TR, hipStream_t stream) {
+    const int ntiles = p.M / 128;
+    const int grid = stem_grid(p);
     // statistics scratch (2 KiB) + the coalesced-store staging of the four MFMA waves (4 x 32 pixels x 136 B; pooled mode:
     // two parked tiles of 128 pixels x 144 B + two carried rows of 32 x 128 B)
     const size_t lds = ((size_t)7 * 64 + 2 * 160) * 64 * sizeof(bf16_t) + 2048 +
@@ -1232,11 +1240,7 @@ static bool pws_enabled(const ConvParams& p) {
     // (global output rows below 2^21: the kernel's float-reciprocal divisions, vpd_fdiv)
     return vpd_switches().pws && mode != 4 && mode != 5 && (long)p.N * p.Hs < VPD_FDIV_MAX;
 }
-template <int BM, int BN, int HROWS, int NS, int NMW, bool PIPE>
-static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
-    constexpr int WN = BN / 64, WM = NMW / WN;
-    constexpr size_t lds = (size_t)2 * HROWS * 128 + (size_t)NS * BN * 128 + 1024 + (size_t)3 * WM * BN * 4;
-    static_assert(lds <= 160 * 1024, "LDS");
+static PwsGrid pws_grid(const ConvParams& p, int BM, int BN) {
     PwsGrid sg;
     sg.MT = (p.M + BM - 1) / BM;
     sg.NT = p.Co / BN;
@@ -1247,7 +1251,15 @@ static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t
     sg.lanes = lanes;
     sg.xcd = lanes % 8 == 0;
     sg.rNT = 1.0f / (float)sg.NT; sg.rlanes = 1.0f / (float)lanes;
-    const dim3 grid(lanes * sg.NT), block((NMW + 4) * 64);
+    return sg;
+}
+template <int BM, int BN, int HROWS, int NS, int NMW, bool PIPE>
+static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
+    constexpr int WN = BN / 64, WM = NMW / WN;
+    constexpr size_t lds = (size_t)2 * HROWS * 128 + (size_t)NS * BN * 128 + 1024 + (size_t)3 * WM * BN * 4;
+    static_assert(lds <= 160 * 1024, "LDS");
+    const PwsGrid sg = pws_grid(p, BM, BN);
+    const dim3 grid(sg.lanes * sg.NT), block((NMW + 4) * 64);
     ConvParams q = p;
 #ifdef PWS_STAMPS
     // diagnostic build: stamps of launch 30 of each kernel shape, as differences from the block's entry, median over blocks
@@ -1553,13 +1565,13 @@ static hipError_t launch_1x1_ws(const ConvParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 // tile choice: the largest tile that still gives every CU a block
-static hipError_t launch_1x1(const ConvParams& p, hipStream_t stream) {
+static void conv1x1_ws_tile(const ConvParams& p, int* bm, int* bn) {
     long t256 = (long)((p.M + 255) / 256), t128 = (long)((p.M + 127) / 128);
     for (int k = 1; k < p.ncls; ++k) { t256 += (p.cls[k - 1].geo.M + 255) / 256; t128 += (p.cls[k - 1].geo.M + 127) / 128; }
     const int nconv = p.alt_w ? 2 : 1;
-    if (p.Co % 128 == 0 && t256 * (p.Co / 128) * nconv >= 200) return launch_1x1_ws<256, 128, 3>(p, stream);
-    if (p.Co % 128 == 0 && t128 * (p.Co / 128) * nconv >= 200) return launch_1x1_ws<128, 128, 4>(p, stream);
-    return launch_1x1_ws<128, 64, 4>(p, stream);
+    if (p.Co % 128 == 0 && t256 * (p.Co / 128) * nconv >= 200) { *bm = 256; *bn = 128; }
+    else if (p.Co % 128 == 0 && t128 * (p.Co / 128) * nconv >= 200) { *bm = 128; *bn = 128; }
+    else { *bm = 128; *bn = 64; }
 }
 
 template <int BM, int BN, int HROWS, bool HALO2>
@@ -1694,6 +1706,9 @@ bool vpd_conv_takes_bn_sums(const ConvParams& p) {
     const int kc = vpd_conv_kernel_class(p, &g);
     if (kc == 4) {      // gather kernel: the merged parity classes of a stride-2 data gradient (plain store only)
         if (p.bst_z2) return false;
+        // (the legacy conv3x3_halo_kernel -- VPD_NO_WS=1, or a 3x3 whose channel counts fit no other class -- decides its epilogue at
+        //  run time and has no sums branch: with rows given it would add sum / sum of squares of d to them instead)
+        if (vpd_conv_dispatch(p).halo) return false;
         // ... or a dense stride-1 launch of it (the Bottleneck students' 1x1 convs), plain or accumulating
         if (p.osub == 1 && p.ncls <= 1 && !p.x2) return vpd_switches().dgrad_sums_1x1 != 0;
         return vpd_switches().dgrad_sums_s2 && !p.accumulate && p.osub == 2;
@@ -1707,6 +1722,64 @@ bool vpd_conv_takes_bn_sums(const ConvParams& p) {
     }
     return kc == 1 || kc == 2 || kc == 3 || kc == 6;
 }
+
+// Every decision of vpd_launch_conv that depends on the problem, the device and the switches, in one place: the launcher
+// below only maps the result to template instantiations, and vpd_op_conv2d_dispatch (plan.hip) reports it to the tests.
+ConvDispatch vpd_conv_dispatch(const ConvParams& p, HaloGeom* g) {
+    ConvDispatch d = {};
+    d.mode = conv_ep_mode(p);
+    d.kclass = vpd_conv_kernel_class(p, g);
+    d.tiles_per_block = 1;
+    const auto pws_form = [&](int bm, int bn, int hrows, int ns, int nmw, bool on) {
+        d.bm = bm; d.bn = bn;
+        d.pws = on && pws_enabled(p);
+        if (!d.pws) return;
+        const PwsGrid sg = pws_grid(p, bm, bn);
+        d.tiles_per_block = (sg.MT + sg.lanes - 1) / sg.lanes;
+        bool flip;
+        d.geo = vpd_switches().pws_geo ? vpd_pws_geo_width(bm, bn, hrows, ns, nmw, p, *g, &flip) : 0;
+    };
+    switch (d.kclass) {
+        case 0: {
+            HaloGeom g2;
+            d.c64x2 = c64x2_geom(p, &g2);      // inference: two MFMA wave groups on 256-pixel tiles
+            if (d.c64x2) *g = g2;
+            d.bm = d.c64x2 ? 256 : 128; d.bn = 64;
+            const int ntiles = (p.M + d.bm - 1) / d.bm;
+            int per;
+            const int grid = persistent_grid(ntiles, &per);
+            d.tiles_per_block = (ntiles + grid - 1) / grid;
+            return d;
+        }
+        // (eight MFMA waves, no fragment pipeline: two waves per SIMD cover each other's LDS round trips.  With ONE tile per
+        //  block conv3x3_ws_kernel, whose loaders run three bundles ahead instead of two, is 3 % faster: 25.5 vs 26.3 us)
+        case 1: pws_form(256, 128, 352, PWS_NS_C1, 8, (p.M + 255) / 256 > pws_cu_count() / (p.Co / 128)); return d;
+        case 2: pws_form(128, 128, 288, PWS_NS_C2, 4, true); return d;
+        case 3: pws_form(128, 64, 288, PWS_NS_C3, 4, true); return d;
+        case 6: pws_form(256, 64, 416, PWS_NS_C6, 4, true); return d;
+        case 5: {
+            d.bm = 128; d.bn = 64;
+            const int grid = stem_grid(p);
+            d.tiles_per_block = p.pool_y ? (p.N + grid - 1) / grid * (p.Hs * p.Ws / 128) : (p.M / 128 + grid - 1) / grid;
+            return d;
+        }
+        default: break;
+    }
+    if (vpd_conv1x1_stream_eligible(p)) { d.stream1x1 = 1; d.tiles_per_block = 0; return d; }
+    if (conv1x1_ws_eligible(p)) { d.ws1x1 = 1; conv1x1_ws_tile(p, &d.bm, &d.bn); return d; }
+    // the statistics accumulator rows only depend on the block index, so the tile choice is free
+    const int bm = vpd_conv_bm(p.M, p.Co);
+    if (halo_eligible(p) && !p.alt_w && !p.x2) {
+        if (p.Co % 128 == 0) {
+            if (bm == 128 && halo_geom(p, 128, 224, g)) { d.halo = 1; d.bm = 128; d.bn = 128; return d; }
+            if (halo_geom(p, 64, 160, g)) { d.halo = 1; d.bm = 64; d.bn = 128; return d; }
+        } else if (halo_geom(p, 128, 224, g)) { d.halo = 1; d.bm = 128; d.bn = 64; return d; }
+    }
+    if (p.Co % 128 == 0) { d.bm = d.bn = bm == 128 ? 128 : 64; }
+    else { d.bm = 128; d.bn = 64; }
+    return d;
+}
+ConvDispatch vpd_conv_dispatch(const ConvParams& p) { HaloGeom g; return vpd_conv_dispatch(p, &g); }
 
 hipError_t vpd_launch_conv(const ConvParams& p0, hipStream_t stream) {
     if (p0.Kc % 64 != 0 || p0.Co % 64 != 0 || p0.M <= 0) return hipErrorInvalidValue;
@@ -1723,59 +1796,35 @@ hipError_t vpd_launch_conv(const ConvParams& p0, hipStream_t stream) {
 #endif
     p.ablate = ablate;
     HaloGeom g;
-    switch (vpd_conv_kernel_class(p, &g)) {
-        case 0: {
-            HaloGeom g2;
-            if (c64x2_geom(p, &g2)) return launch_c64x2(p, g2, stream);      // inference: two MFMA wave groups on 256-pixel tiles
-            return launch_c64<224>(p, g, stream);
-        }
-        case 1:
-            // (eight MFMA waves, no fragment pipeline: two waves per SIMD cover each other's LDS round trips.  With ONE tile per
-            //  block conv3x3_ws_kernel, whose loaders run three bundles ahead instead of two, is 3 % faster: 25.5 vs 26.3 us)
-            if (pws_enabled(p) && (p.M + 255) / 256 > pws_cu_count() / (p.Co / 128)) {
-                return launch_pws<256, 128, 352, PWS_NS_C1, 8, false>(p, g, stream);
-            }
-            return launch_ws<256, 128, 352, 2, 2, 4>(p, g, stream);      // 88 + 64 KiB
+    const ConvDispatch d = vpd_conv_dispatch(p, &g);
+    switch (d.kclass) {
+        case 0: return d.c64x2 ? launch_c64x2(p, g, stream) : launch_c64<224>(p, g, stream);
+        case 1: return d.pws ? launch_pws<256, 128, 352, PWS_NS_C1, 8, false>(p, g, stream)
+                             : launch_ws<256, 128, 352, 2, 2, 4>(p, g, stream);      // 88 + 64 KiB
         // four ring stages (the loaders three weight tiles ahead): same-box A/B against 3 / 5 stages in
         // profiles/r02_ring_depth.txt (4 is +0.5 % on the step, 5 is slower than 3)
-        case 2:
-            if (pws_enabled(p)) {
-                return launch_pws<128, 128, 288, PWS_NS_C2, 4, true>(p, g, stream);
-            }
-            return launch_ws<128, 128, 288, 2, 2, 4>(p, g, stream);      // 72 + 64 KiB
-        case 3:
-            if (pws_enabled(p)) {
-                return launch_pws<128, 64, 288, PWS_NS_C3, 4, true>(p, g, stream);
-            }
-            return launch_ws<128, 64, 288, 2, 2, 4>(p, g, stream);       // 72 + 32 KiB
-        case 6:
-            if (pws_enabled(p)) {
-                // (round 4: layer2's 18 x 18 halo needs 328 rows, not 416, and the 22 KB that frees were given to a deeper weight ring,
-                //  NS 7 and 9 -- same-box 72.02 / 72.02 / 71.86 k crops/s for NS 7 / 9 / 5, profiles/r04_ab_layer2_ring_depth.txt: the K
-                //  loop is not bound by the loaders' bytes in flight; instantiations removed)
-                return launch_pws<256, 64, 416, PWS_NS_C6, 4, true>(p, g, stream);
-            }
-            return launch_ws<256, 64, 416, 2, 2, 4>(p, g, stream);       // 104 + 32 KiB
+        case 2: return d.pws ? launch_pws<128, 128, 288, PWS_NS_C2, 4, true>(p, g, stream)
+                             : launch_ws<128, 128, 288, 2, 2, 4>(p, g, stream);      // 72 + 64 KiB
+        case 3: return d.pws ? launch_pws<128, 64, 288, PWS_NS_C3, 4, true>(p, g, stream)
+                             : launch_ws<128, 64, 288, 2, 2, 4>(p, g, stream);       // 72 + 32 KiB
+        // (round 4: layer2's 18 x 18 halo needs 328 rows, not 416, and the 22 KB that frees were given to a deeper weight ring,
+        //  NS 7 and 9 -- same-box 72.02 / 72.02 / 71.86 k crops/s for NS 7 / 9 / 5, profiles/r04_ab_layer2_ring_depth.txt: the K
+        //  loop is not bound by the loaders' bytes in flight; instantiations removed)
+        case 6: return d.pws ? launch_pws<256, 64, 416, PWS_NS_C6, 4, true>(p, g, stream)
+                             : launch_ws<256, 64, 416, 2, 2, 4>(p, g, stream);       // 104 + 32 KiB
         case 5: { int tr; stem_eligible(p, &tr); return launch_stem(p, tr, stream); }
         default: break;
     }
-    if (vpd_conv1x1_stream_eligible(p)) return vpd_launch_conv1x1_stream(p, stream);
-    if (conv1x1_ws_eligible(p)) return launch_1x1(p, stream);
-    // the statistics accumulator rows only depend on the block index, so the tile choice is free
-    const int bm = vpd_conv_bm(p.M, p.Co);
-    if (halo_eligible(p) && !p.alt_w && !p.x2) {
-        if (p.Co % 128 == 0) {
-            if (bm == 128 && halo_geom(p, 128, 224, &g))
-                return p.Kc > 128 ? launch_halo<128, 128, 224, true>(p, g, stream)
-                                  : launch_halo<128, 128, 224, false>(p, g, stream);
-            if (halo_geom(p, 64, 160, &g)) return launch_halo<64, 128, 160, true>(p, g, stream);
-        } else if (halo_geom(p, 128, 224, &g)) {
-            return launch_halo<128, 64, 224, false>(p, g, stream);
-        }
+    if (d.stream1x1) return vpd_launch_conv1x1_stream(p, stream);
+    if (d.ws1x1) {      // tile choice: the largest tile that still gives every CU a block
+        if (d.bm == 256) return launch_1x1_ws<256, 128, 3>(p, stream);
+        return d.bn == 128 ? launch_1x1_ws<128, 128, 4>(p, stream) : launch_1x1_ws<128, 64, 4>(p, stream);
     }
-    if (p.Co % 128 == 0) {
-        if (bm == 128) return launch_cfg<128, 128, 2, 2>(p, stream);
-        return launch_cfg<64, 64, 2, 2>(p, stream);
+    if (d.halo) {
+        if (d.bn == 64) return launch_halo<128, 64, 224, false>(p, g, stream);
+        if (d.bm == 64) return launch_halo<64, 128, 160, true>(p, g, stream);
+        return p.Kc > 128 ? launch_halo<128, 128, 224, true>(p, g, stream) : launch_halo<128, 128, 224, false>(p, g, stream);
     }
-    return launch_cfg<128, 64, 2, 2>(p, stream);
+    if (d.bn == 64 && d.bm == 128) return launch_cfg<128, 64, 2, 2>(p, stream);
+    return d.bm == 128 ? launch_cfg<128, 128, 2, 2>(p, stream) : launch_cfg<64, 64, 2, 2>(p, stream);
 }

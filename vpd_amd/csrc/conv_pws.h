@@ -808,3 +808,5 @@ __global__ __launch_bounds__((NMW + 4) * 64, (NMW + 4) / 4) void conv3x3_pws_ker
 // launches the generic kernel.
 bool vpd_launch_pws_geo(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid,
                         dim3 block, size_t lds, hipStream_t stream);
+// ... and its decision alone: the image width of the instantiation that takes the launch, or 0
+int vpd_pws_geo_width(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, bool* flip_out);

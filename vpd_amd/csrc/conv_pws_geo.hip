@@ -33,22 +33,33 @@ bool launch_geo(bool flip, const ConvParams& q, const HaloGeom& g, const PwsGrid
 
 }  // namespace
 
-bool vpd_launch_pws_geo(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid,
-                        dim3 block, size_t lds, hipStream_t stream) {
+// Image width of the compile-time-geometry instantiation that takes this launch (and its tap orientation), or 0: none does
+int vpd_pws_geo_width(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, bool* flip_out) {
     const TapSet& t = q.taps;
     const bool fwd = t.dy0 == 0 && t.dys == 1 && t.dx0 == 0 && t.dxs == 1;
     const bool flip = t.dy0 == 2 && t.dys == -1 && t.dx0 == 2 && t.dxs == -1;
-    if (!fwd && !flip) return false;
+    if (!fwd && !flip) return 0;
     // (the swizzle key the kernel's bases are built from: halo_geom, conv_igemm.hip)
-    if (q.Ws >= 8 ? !(g.kmask == 7 && g.kshift == 0 && g.rowmask == 0) : !(g.kmask == 3 && g.kshift == 2 && g.rowmask == 1)) return false;
-    if (nmw == 4 && bm == 256 && bn == 64 && hrows == 416 && ns == PWS_NS_C6) {
-        if (q.Ws == 16) return launch_geo<256, 64, 416, PWS_NS_C6, 16>(flip, q, g, sg, grid, block, lds, stream);
-        if (q.Ws == 8) return launch_geo<256, 64, 416, PWS_NS_C6, 8>(flip, q, g, sg, grid, block, lds, stream);
-    } else if (nmw == 4 && bm == 128 && bn == 64 && hrows == 288 && ns == PWS_NS_C3) {
-        if (q.Ws == 4) return launch_geo<128, 64, 288, PWS_NS_C3, 4>(flip, q, g, sg, grid, block, lds, stream);
-    }
+    if (q.Ws >= 8 ? !(g.kmask == 7 && g.kshift == 0 && g.rowmask == 0) : !(g.kmask == 3 && g.kshift == 2 && g.rowmask == 1)) return 0;
+    // the epilogue modes instantiated per orientation (launch_geo above)
+    const int mode = conv_ep_mode(q);
+    if (flip ? !(mode == 0 || mode == 2 || mode == 6 || mode == 7 || mode == 8) : !(mode == 1 || mode == 3)) return 0;
+    *flip_out = flip;
+    if (nmw == 4 && bm == 256 && bn == 64 && hrows == 416 && ns == PWS_NS_C6) return q.Ws == 16 || q.Ws == 8 ? q.Ws : 0;
+    if (nmw == 4 && bm == 128 && bn == 64 && hrows == 288 && ns == PWS_NS_C3) return q.Ws == 4 ? 4 : 0;
     // (round 6, measured and removed -- profiles/r06_ab_geo8.txt: the same loop on the eight-wave 256 x 128 tile, whose 168-register
     //  budget it does not fit without spilling and whose two MFMA waves per SIMD already cover each other's reads, 676 vs 636 us per step
     //  for its class at 512 crops; with it and the 128 x 128 tile of layer4 the apply forward read 389 k against 393 k crops/s)
-    return false;
+    return 0;
+}
+
+bool vpd_launch_pws_geo(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid,
+                        dim3 block, size_t lds, hipStream_t stream) {
+    bool flip = false;
+    switch (vpd_pws_geo_width(bm, bn, hrows, ns, nmw, q, g, &flip)) {
+        case 16: return launch_geo<256, 64, 416, PWS_NS_C6, 16>(flip, q, g, sg, grid, block, lds, stream);
+        case 8: return launch_geo<256, 64, 416, PWS_NS_C6, 8>(flip, q, g, sg, grid, block, lds, stream);
+        case 4: return launch_geo<128, 64, 288, PWS_NS_C3, 4>(flip, q, g, sg, grid, block, lds, stream);
+        default: return false;
+    }
 }

@@ -86,6 +86,19 @@ bool vpd_conv1x1_stream_eligible(const ConvParams& p);
 hipError_t vpd_launch_conv1x1_stream(const ConvParams& p, hipStream_t stream);
 int vpd_conv_kernel_class(const ConvParams& p);      // 0..4, see conv_igemm.hip
 bool vpd_conv_takes_bn_sums(const ConvParams& p);
+// What vpd_launch_conv does with `p` on the current device; the launcher branches on this very struct (conv_igemm.hip)
+struct ConvDispatch {
+    int kclass;             // vpd_conv_kernel_class
+    int pws;                // classes 1, 2, 3, 6: conv3x3_pws_kernel (persistent blocks) instead of conv3x3_ws_kernel
+    int geo;                // ... its compile-time-geometry instantiation: the image width, or 0
+    int c64x2;              // class 0: the two-group inference twin conv3x3_c64x2_persistent_kernel
+    int ws1x1, stream1x1;   // class 4: conv1x1_ws_kernel (ring GEMM) / conv1x1_stream_kernel
+    int halo;               // class 4: the legacy conv3x3_halo_kernel
+    int bm, bn;             // tile (pixels x channels); 0 x 0 for the streaming kernel, which picks its own
+    int mode;               // conv_ep_mode
+    int tiles_per_block;    // pixel tiles the busiest block walks
+};
+ConvDispatch vpd_conv_dispatch(const ConvParams& p);
 // pixels per tile when `p` runs on conv3x3_pws_kernel with its XCD-affine tile order (pixel tile t on XCD t % 8), else 0
 int vpd_conv_xcd_tile_px(const ConvParams& p);         // epilogue can take the consuming BatchNorm's backward sums (bst_z)
 hipError_t vpd_launch_wgrad_reduce(const WgradParams& p, hipStream_t stream);   // slab sum of a deferred halo wgrad

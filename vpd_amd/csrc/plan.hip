@@ -24,7 +24,7 @@ int fail(const char* what, hipError_t e) {
 
 extern "C" const char* vpd_last_error(void) { return g_err.c_str(); }
 extern "C" const char* vpd_elem_dtype(void) { return VPD_ELEM_NAME; }      // "bf16" (libvpdhip.so) or "fp16" (libvpdhip_f16.so)
-extern "C" int vpd_abi_version(void) { return 4; }      // 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
+extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2; 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
 
 namespace {
 
@@ -787,10 +787,11 @@ extern "C" int vpd_op_conv2d_ep(const void* x, const void* w, void* y, int n, in
     return 0;
 }
 
-extern "C" int vpd_op_conv2d_bnsums(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask,
-                                    double* rows, int n, int xHp, int xWp, int xC, int Hs, int Ws, int Kc, int Co,
-                                    const int* tapset9, int accumulate, void* stream) {
-    if (!bst_z || !bst_mask || !rows) return fail("null argument");
+static int op_conv2d_bnsums(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask, double* rows,
+                            const void* bst_z2, double* rows2, int n, int xHp, int xWp, int xC, int Hs, int Ws, int Kc, int Co,
+                            const int* tapset9, int accumulate, void* stream) {
+    if (!x || !w || !y || !bst_z || !bst_mask || !rows || !tapset9) return fail("null argument");
+    if (n < 1 || Hs < 1 || Ws < 1 || Kc < 64 || Kc % 64 || Co < 64 || Co % 64) return fail("bad argument");
     ConvParams q;
     memset(&q, 0, sizeof q);
     q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.w = (const bf16_t*)w;
@@ -798,10 +799,58 @@ extern "C" int vpd_op_conv2d_bnsums(const void* x, const void* w, void* y, const
     q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = 1; q.istr = 1;
     q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws; q.accumulate = accumulate;
     q.bst_z = (const bf16_t*)bst_z; q.bst_mask = bst_mask; q.stats = rows; q.stat_rows = VPD_FUSED_ROWS;
+    q.bst_z2 = (const bf16_t*)bst_z2; q.stats2 = rows2;
     q.taps = tapset_from(tapset9);
     if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
     if (!vpd_conv_takes_bn_sums(q)) return fail("no kernel takes the BatchNorm sums for this shape");
     LCHECK(vpd_launch_conv(q, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_conv2d_bnsums(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask,
+                                    double* rows, int n, int xHp, int xWp, int xC, int Hs, int Ws, int Kc, int Co,
+                                    const int* tapset9, int accumulate, void* stream) {
+    return op_conv2d_bnsums(x, w, y, bst_z, bst_mask, rows, nullptr, nullptr, n, xHp, xWp, xC, Hs, Ws, Kc, Co, tapset9, accumulate, stream);
+}
+
+// epilogue mode 8: the accumulating data gradient of a stage's first block, whose d feeds TWO BatchNorms (bn2 of the block before
+// through z / rows, the 1x1 branch's through z2 / rows2) under the same ReLU bit map
+extern "C" int vpd_op_conv2d_bnsums2(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask,
+                                     double* rows, const void* bst_z2, double* rows2, int n, int xHp, int xWp, int xC, int Hs,
+                                     int Ws, int Kc, int Co, const int* tapset9, void* stream) {
+    if (!bst_z2 || !rows2) return fail("null argument");
+    return op_conv2d_bnsums(x, w, y, bst_z, bst_mask, rows, bst_z2, rows2, n, xHp, xWp, xC, Hs, Ws, Kc, Co, tapset9, 1, stream);
+}
+
+// host-only: what vpd_launch_conv decides for these arguments on the current device (ConvDispatch, kernels.h).  flags: 1 statistics
+// rows, 2 eval epilogue, 4 ReLU bit map on the old value, 8 BatchNorm sums (vpd_op_conv2d_bnsums), 16 of two BatchNorms.
+// out12 = {class, pws, geo width, c64x2, 1x1 ring GEMM, 1x1 streaming, legacy halo, tile pixels, tile channels, epilogue mode,
+// tiles per block, takes BatchNorm sums}
+extern "C" int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub,
+                                      int oph, int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags,
+                                      int* out12) {
+    if (!tapset9 || !out12) return fail("null argument");
+    if (n < 1 || Hs < 1 || Ws < 1 || xHp < 1 || xWp < 1 || xC < 1 || yC < Co || Kc < 64 || Kc % 64 || Co < 64 || Co % 64 || osub < 1 ||
+        istr < 1 || (long long)n * Hs * Ws >= (1ll << 31) || (flags & ~31))
+        return fail("bad argument");
+    if ((flags & 16) && !(flags & 8)) return fail("a second BatchNorm needs the first");
+    static const double present = 0.0;      // the launcher's decisions read pointers only as present / absent
+    ConvParams q;
+    memset(&q, 0, sizeof q);
+    q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.yHp = yHp; q.yWp = yWp; q.yC = yC; q.ypad = ypad;
+    q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = osub; q.oph = oph; q.opw = opw; q.istr = istr;
+    q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws; q.accumulate = accumulate;
+    if (flags & 1) q.stats = const_cast<double*>(&present);
+    if (flags & 2) { q.ep_scale = (const float*)&present; q.ep_shift = (const float*)&present; }
+    if (flags & 4) q.acc_mask = (const unsigned char*)&present;
+    if (flags & 8) { q.bst_z = (const bf16_t*)&present; q.bst_mask = (const unsigned char*)&present; q.stats = const_cast<double*>(&present); q.stat_rows = VPD_FUSED_ROWS; }
+    if (flags & 16) { q.bst_z2 = (const bf16_t*)&present; q.stats2 = const_cast<double*>(&present); }
+    q.taps = tapset_from(tapset9);
+    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
+    const ConvDispatch d = vpd_conv_dispatch(q);
+    const int v[12] = {d.kclass, d.pws, d.geo, d.c64x2, d.ws1x1, d.stream1x1, d.halo, d.bm, d.bn, d.mode, d.tiles_per_block,
+                       (flags & 8) ? (int)vpd_conv_takes_bn_sums(q) : 0};
+    memcpy(out12, v, sizeof v);
     return 0;
 }
 
@@ -1029,7 +1078,8 @@ extern "C" int vpd_op_wgrad128_group(int nprob, const void* const* dz, const voi
         if (!vpd_wgrad128_eligible(q)) return fail("shape not eligible for the 128 x 64 weight-gradient kernel");
         qs[i] = q;
     }
-    static void* cache = vpd_wgrad128_cache_new();      // one schedule cache for the op entry point (rebuilt when shapes change)
-    LCHECK(vpd_launch_wgrad128_group(qs, nprob, cache, dev_table, (hipStream_t)stream));
+    // no schedule cache: a cache skips the upload when shapes and table ADDRESS repeat, and a test that frees its table and gets the
+    // same address back from the allocator, overwritten in between, would launch on a stale task table (an illegal access)
+    LCHECK(vpd_launch_wgrad128_group(qs, nprob, nullptr, dev_table, (hipStream_t)stream));
     return 0;
 }
