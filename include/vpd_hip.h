@@ -356,6 +356,19 @@ int vpd_op_wgrad(const void* dz_bf16, const void* x_bf16, float* dw, int n, int 
                  int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
                  float* slab, void* stream);
 size_t vpd_op_wgrad_slab_bytes(void);
+/* A down-sampling BasicBlock's two weight gradients in ONE launch (the form vpd_backward uses at the three stage boundaries of
+ * ResNet-18/34): the 3x3 stride-2 pad-1 conv1 (dz, dw [9][Co][Kc], tapset9 = its taps as for vpd_op_wgrad) and the 1x1 stride-2 pad-0
+ * branch (dz2, dw2 [Co][Kc]) read the same x; dz2 has dz's geometry.  The branch rides on conv1's staged halo as a tenth tap.
+ * Both gradients are OVERWRITTEN, bit for bit what the two vpd_op_wgrad calls on the halo path give.  slab, slab2: fp32 scratch of
+ * vpd_op_wgrad_slab_bytes() bytes each (both required).  Fails -- nothing is launched -- for shapes the halo form does not take,
+ * with VPD_WGRAD_DS_RIDE=0, and for an LDS layout over 160 KB. */
+int vpd_op_wgrad_pair(const void* dz_bf16, const void* dz2_bf16, const void* x_bf16, float* dw, float* dw2, int n, int dzHp, int dzWp,
+                      int dzC, int dzpad, int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
+                      float* slab, float* slab2, void* stream);
+/* Host-only: dynamic LDS bytes of that launch for an Hs x Ws output (input 2 Hs x 2 Ws).  ns: stages of the dz + halo ring, 0 = the
+ * launcher's own choice.  Returns 0: fits; 1: over the 160 KB of a compute unit (the launcher refuses such a layout); -1: the output
+ * size has no halo geometry.  *bytes is set unless -1. */
+int vpd_op_wgrad_pair_lds_bytes(int Hs, int Ws, int ns, long long* bytes);
 /* dumps the ds_read_b64_tr_b16 fragments of one [128][64] bf16 tile: out [4][4][64][8] bf16 */
 int vpd_op_tr_read_probe(const void* tile_bf16, void* out_bf16, void* stream);
 /* Grouped weight gradients of `nprob` 3x3 pad-1 / 1x1 pad-0 convolutions (stride 1 or 2) on 128-channel-wide tiles in ONE persistent launch (the

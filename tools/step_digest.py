@@ -17,6 +17,7 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--arch", default="resnet34")
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"], help="element type: libvpdhip.so / libvpdhip_f16.so (static loss scale)")
     ap.add_argument("--eval-out", default=None, help="also embed the batch in eval mode and save the array here (.npy)")
     ap.add_argument("--eval-first", action="store_true", help="... before the steps (freshly initialised weights) instead of after them")
     args = ap.parse_args()
@@ -26,7 +27,7 @@ def main():
     from vpd_amd.trainer import ModelTrainer
     device = torch.device("cuda", 0)
     torch.manual_seed(0)
-    enc = RGBF_EmbeddingModel(args.arch, bench.EMB_DIM, True, device, in_channels=5)
+    enc = RGBF_EmbeddingModel(args.arch, bench.EMB_DIM, True, device, in_channels=5, dtype=args.dtype)
     enc.reset_parameters(seed=0)
     trainer = ModelTrainer(enc, motion=False)
     optimizer, scaler = trainer.get_optimizer(5e-4)

@@ -179,6 +179,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
 // tiles go to an fp32 slab with plain stores (slab[split][tap][Co][Ci]); wgrad_slab_reduce_kernel sums
 // the splits.
 // ---------------------------------------------------------------------------
+#define WG_CH 64           // pixels per chunk = two MFMA K-steps (vpd_wgrad_split assumes 64)
+#define WG_NS 3            // ring stages
+
 struct WgHaloGeom {
     int TR, multi, HR, NHP, total_pix;   // halo tiling of a 128-pixel chunk (as HaloGeom in conv_igemm.hip)
     int ksplit, cpb;                     // pixel-chunk splits and chunks per block
@@ -203,10 +206,20 @@ static __device__ __forceinline__ bf16x8 tr_frag2(const bf16_t* tile, int ra, in
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// The down-sampling block's 1x1 branch riding in its 3x3 stride-2 conv1's launch (conv_wgrad_halo_pair_kernel): the branch's dz and
+// its slab.  Everything else -- x, the shapes, the split -- is conv1's.
+struct WgPair {
+    const bf16_t* dz2;
+    float* slab2;                        // [split][Co][Ci]
+};
+
 // MFMA-wave body of conv_wgrad_halo_kernel for taps [T0, T1): ci columns 16*ctile .. +15, all 64 co.
-template <int T0, int T1, int NS>
+// BR: the wave also carries the riding 1x1 branch as a further "tap": B operand = the centre tap's x fragments, A operand from the
+// branch's dz tiles (ring2: two stages of 64 x 64), accumulated in the order of the one_by_one launch it replaces.
+template <int T0, int T1, int NS, bool BR = false>
 static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, const WgHaloGeom& g, const bf16_t* ring,
-                                                       int STAGE, int nch, int ctile, int lane, int bx, int by) {
+                                                       int STAGE, int nch, int ctile, int lane, int bx, int by,
+                                                       const bf16_t* ring2 = nullptr, float* slab2 = nullptr) {
     constexpr int NT = T1 - T0;
     // W, H: OUTPUT dims; the x halo is rows of the padded INPUT (stride S = 1 or 2: input pixel S*y + r, S*x + t)
     const int W = p.Ws, H = p.Hs, Wp = p.xWp, S = p.istr;
@@ -215,11 +228,15 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int a = 0; a < 4; ++a) acc[t][a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 acc2[4];                       // (BR) the branch's tile
+#pragma unroll
+    for (int a = 0; a < 4; ++a) acc2[a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int gq = lane >> 4, i16 = lane & 15, q = i16 >> 2, pp = i16 & 3;
     // chunk-invariant LDS element offsets (within a stage) of every transposed read of this lane.
     // dz rows are 32*ks + 8*gq + 4*h + q: the swizzle only looks at row bits 1 and 3, so k-step 1 is +32 rows.
     int offA[4][2], offB[2][NT][2];
+    [[maybe_unused]] int offC[2][2];
     {
         const int ra = 8 * gq + q;
 #pragma unroll
@@ -246,6 +263,23 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
                     const int col = ctile * 16 + 4 * pp;
                     offB[ks][t][h] = 64 * 64 + r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15));
                 }
+                if constexpr (BR) {      // the centre tap
+                    const int r = hmv + (p.taps.dy0 + p.taps.dys) * Wp + (p.taps.dx0 + p.taps.dxs);
+                    const int col = ctile * 16 + 4 * pp;
+                    offC[ks][h] = 64 * 64 + r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15));
+                }
+            }
+    }
+    if constexpr (NS == 2) {
+        // the 13-pass launches: hipcc keeps each offset as two addends (row, swizzled column) and folds them into the stage address
+        // inside the loop -- twice the registers, spilled.  Opaque values stay one register each.
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) asm volatile("" : "+v"(offB[ks][t][h]));
+                if constexpr (BR) asm volatile("" : "+v"(offC[ks][h]));
             }
     }
     typedef s16x4 __attribute__((address_space(3))) * lds_p;
@@ -262,6 +296,32 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
         __builtin_amdgcn_s_barrier();                             // READY_c
         if (VPD_ABL(p, 2)) continue;
         const bf16_t* st = ring + (c % NS) * STAGE;
+        if constexpr (BR) {
+            const bf16_t* st2 = ring2 + (c & 1) * WG_CH * 64;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                bf16x8 az[4], bx[NT];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) az[a] = frag(st + ks * 32 * 64, offA[a][0], offA[a][1]);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) bx[t] = frag(st, offB[ks][t][0], offB[ks][t][1]);
+                const bf16x8 bxc = frag(st, offC[ks][0], offC[ks][1]);
+                __builtin_amdgcn_sched_barrier(0);
+                // co tile by co tile (every accumulator still sees its k-steps in order): once a tile's MFMAs are issued its dz
+                // registers take the branch's dz fragment, whose read then hides behind the next tiles' MFMAs -- five A sets at
+                // once do not fit the 168 registers of a 12-wave block
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) acc[t][a] = VPD_MFMA16(az[a], bx[t], acc[t][a]);
+                    az[a] = frag(st2 + ks * 32 * 64, offA[a][0], offA[a][1]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a) acc2[a] = VPD_MFMA16(az[a], bxc, acc2[a]);
+            }
+            continue;
+        }
         if constexpr (NT == 4) {
             // the 4-tap wave of a SIMD reads BOTH k-steps up front and then issues its 32 MFMAs in one run, so that
             // the 5-tap wave's second read phase falls into this wave's MFMAs instead of coinciding with a read
@@ -316,19 +376,28 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * p.Kc] = acc[t][a][j];
     }
+    if constexpr (BR) {
+        float* o = slab2 + ((size_t)by * p.Co + co0) * p.Kc + ci0 + 16 * ctile + i16;
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * p.Kc] = acc2[a][j];
+    }
 }
-
-#define WG_CH 64           // pixels per chunk = two MFMA K-steps (vpd_wgrad_split assumes 64)
-#define WG_NS 3            // ring stages
-
+           // pixels per chunk = two MFMA K-steps (vpd_wgrad_split assumes 64)
 // NPASS: 32-row LDS-DMA passes of the x halo (NHP <= 32*NPASS).  (bx, by) = (output tile, pixel split) of this block.
-template <int NPASS, int NS = WG_NS>
-static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, const WgHaloGeom& g, int bx, int by) {
+// PAIR: a second dz tile per chunk (the riding 1x1 branch, WgPair) on a two-stage ring of its own behind the NS stages.  The tile of
+// chunk c+1 goes into the slot chunk c-1 used, so it is issued behind READY_c, FIRST in that bundle: the counted wait for chunk c+1
+// (at most the PER_CHUNK instructions of chunk c+2 outstanding) then covers it too.
+template <int NPASS, int NS = WG_NS, bool PAIR = false>
+static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, const WgHaloGeom& g, int bx, int by,
+                                                       const WgPair& pr = WgPair{nullptr, nullptr}) {
     constexpr int HROWS = 32 * NPASS;
     constexpr int STAGE = (WG_CH + HROWS) * 64;                   // bf16 elements per stage: dz tile, halo
     constexpr int PER_CHUNK = 2 + NPASS;                          // LDS-DMA instructions per loader wave per chunk
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16_t* ring = reinterpret_cast<bf16_t*>(smem);               // [WG_NS][dz 64x64 | halo HROWSx64]
+    bf16_t* ring = reinterpret_cast<bf16_t*>(smem);               // [NS][dz 64x64 | halo HROWSx64]
+    bf16_t* ring2 = ring + NS * STAGE;                            // (PAIR) [2][dz2 64x64]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -350,25 +419,29 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
         const int lw = wave - 8;
         const int piece = lane & 7;
         const int lrow = lane >> 3;                               // row within an 8-row wave instruction
-        auto issue = [&](int c) __attribute__((always_inline)) {
-            const int ch = chunk_begin + c;
-            bf16_t* st = ring + (c % NS) * STAGE;
-            // dz tile: 8 wave-instructions of 8 pixel rows; two per loader wave
+        // a dz tile: 8 wave-instructions of 8 pixel rows; two per loader wave
+        auto issue_dz = [&](const bf16_t* dz, bf16_t* dst, int ch) __attribute__((always_inline)) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int row = (lw + 4 * i) * 8 + lrow;
                 const int m = ch * WG_CH + row;
                 const int cpc = (((piece >> 1) ^ wg_f(row)) << 1) | (piece & 1);
-                const bf16_t* src = p.dz + cpc * 8;               // zero border row of image 0: contributes nothing
+                const bf16_t* src = dz + cpc * 8;                 // zero border row of image 0: contributes nothing
                 if (m < p.M) {
                     const int b = m / (H * W);
                     const int r = m - b * H * W;
                     const int yy = r / W;
                     const int xx = r - yy * W;
-                    src = p.dz + ((size_t)(b * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + cpc * 8;
+                    src = dz + ((size_t)(b * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + cpc * 8;
                 }
-                __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(st + (lw + 4 * i) * 8 * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(dst + (lw + 4 * i) * 8 * 64), 16, 0, 0);
             }
+        };
+        auto issue2 = [&](int c) __attribute__((always_inline)) { issue_dz(pr.dz2, ring2 + (c & 1) * WG_CH * 64, chunk_begin + c); };
+        auto issue = [&](int c) __attribute__((always_inline)) {
+            const int ch = chunk_begin + c;
+            bf16_t* st = ring + (c % NS) * STAGE;
+            issue_dz(p.dz, st, ch);
             // x halo: 4*NPASS wave-instructions; NPASS per loader wave
             const int gr0 = ch * g.TR;
             int prow0;
@@ -389,6 +462,7 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
             for (int c = 0; c < nch; ++c) __builtin_amdgcn_s_barrier();
             return;
         }
+        if (PAIR) issue2(0);
         issue(0);
         if (NS > 2 && nch > 1) issue(1);
         for (int c = 0; c < nch; ++c) {
@@ -396,6 +470,7 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
             if (NS > 2 && c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_CHUNK) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                         // READY_c (MFMA waves have finished chunk c-1)
+            if (PAIR && c + 1 < nch) issue2(c + 1);               // into the slot chunk c-1 used
             if (c + NS - 1 < nch) issue(c + NS - 1);              // into the stage chunk c-1 used
         }
         return;
@@ -403,6 +478,12 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
 
     // ------------------------- MFMA waves -------------------------
     const int ctile = wave & 3;
+    if constexpr (PAIR) {
+        // ten "taps" split 5 / 5: waves 4..7 take taps 5..8 and the branch (five accumulator sets each, as the 5-tap waves hold)
+        if (wave < 4) wgrad_mfma_half<0, 5, NS>(p, g, ring, STAGE, nch, ctile, lane, bx, by);
+        else wgrad_mfma_half<5, 9, NS, true>(p, g, ring, STAGE, nch, ctile, lane, bx, by, ring2, pr.slab2);
+        return;
+    }
     if (p.one_by_one) {
         // 1x1 convolution = the centre tap alone: waves 0..3 carry it (8 MFMAs per chunk: the launch is bound by the
         // operand stream), waves 4..7 only keep the barrier count
@@ -418,6 +499,13 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
 template <int NPASS, int NS = WG_NS>
 __global__ __launch_bounds__(768) void conv_wgrad_halo_kernel(const WgradParams p, const WgHaloGeom g) {
     wgrad_halo_body<NPASS, NS>(p, g, blockIdx.x, blockIdx.y);
+}
+
+// A down-sampling BasicBlock's 3x3 stride-2 conv1 and its 1x1 stride-2 branch in one launch: same input, same halo, same chunks,
+// same split; only dz differs.  The halo is staged once; the nine taps' partials go to p.slab, the branch's to pr.slab2.
+template <int NPASS, int NS>
+__global__ __launch_bounds__(768) void conv_wgrad_halo_pair_kernel(const WgradParams p, const WgHaloGeom g, const WgPair pr) {
+    wgrad_halo_body<NPASS, NS, true>(p, g, blockIdx.x, blockIdx.y, pr);
 }
 
 // Grouped launch: the weight gradients of SEVERAL convolutions of one ResNet stage in one grid.  A weight gradient
@@ -921,6 +1009,77 @@ hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
     const size_t lds = 64 * 1024;     // max(staging 2*2*16 KiB, reduction 64 KiB)
     VPD_LAUNCH(conv_wgrad_kernel, grid, dim3(256), lds, stream, p);
     return hipGetLastError();
+}
+
+// ---- pair launch (conv_wgrad_halo_pair_kernel): a down-sampling BasicBlock's 3x3 stride-2 conv1 (p3) with its 1x1 stride-2 branch (p1),
+// both in the caller's terms ----
+#ifndef VPD_WG_PAIR_NS
+#define VPD_WG_PAIR_NS 3      // stages of the dz + halo ring of the 10-pass pair launch (-DVPD_WG_PAIR_NS=2: two stages of everything)
+#endif
+// Dynamic LDS of a pair launch whose halo takes `npass` 32-row passes on an `ns`-stage ring, the branch's two dz tiles behind it.
+// false: more than the 160 KB of a CU -- such a layout is never launched.
+static bool wg_pair_lds(int npass, int ns, size_t* bytes) {
+    const int rows = WG_CH + 32 * (npass <= 10 ? 10 : 13);
+    *bytes = ((size_t)ns * rows + 2 * WG_CH) * 64 * sizeof(bf16_t);
+    return ns >= 2 && npass <= 13 && *bytes <= (size_t)160 * 1024;
+}
+// Host-only: the LDS bytes of the pair launch for an H x W OUTPUT (input 2H x 2W, border 1).  ns 0: the launcher's ring depth.
+// 0: fits; 1: the layout is over 160 KB (the launcher refuses it); -1: no halo geometry for this output size.
+int vpd_wgrad_pair_lds_query(int H, int W, int ns, long long* bytes) {
+    WgradParams p;
+    memset(&p, 0, sizeof p);
+    p.N = 1; p.Hs = H; p.Ws = W; p.istr = 2; p.xHp = 2 * H + 2; p.xWp = 2 * W + 2;
+    WgHaloGeom g;
+    if (H <= 0 || !wg_halo_geom(p, &g)) return -1;
+    const int npass = (g.NHP + 31) / 32;
+    size_t b = 0;
+    const bool ok = wg_pair_lds(npass, ns > 0 ? ns : (npass > 10 ? 2 : VPD_WG_PAIR_NS), &b);
+    if (bytes) *bytes = (long long)b;
+    return ok ? 0 : 1;
+}
+bool vpd_wgrad_pair_ok(const WgradParams& p3, const WgradParams& p1) {
+    if (!vpd_switches().wgrad_ds_ride) return false;
+    WgradParams q1;
+    if (!vpd_wgrad_overwrites(p3) || !vpd_wgrad_overwrites(p1) || !wg_as_one_by_one(p1, &q1)) return false;
+    if (p3.one_by_one || p3.taps.nr != 3 || p3.taps.nc != 3 || p3.istr != 2 || p3.Kc % 64 != 0 || p3.Co % 64 != 0 || p3.M <= 0) return false;
+    return p1.x == p3.x && p1.xHp == p3.xHp && p1.xWp == p3.xWp && p1.xC == p3.xC && p1.N == p3.N && p1.Hs == p3.Hs &&
+           p1.Ws == p3.Ws && p1.istr == p3.istr && p1.Kc == p3.Kc && p1.Co == p3.Co && p1.M == p3.M && p1.dzHp == p3.dzHp &&
+           p1.dzWp == p3.dzWp && p1.dzC == p3.dzC && p1.dzpad == p3.dzpad;
+}
+// one launch sums both slabs: the same split and the same groups as the two wgrad_slab_reduce_kernel launches, element by element
+hipError_t vpd_launch_wgrad_pair_reduce(const WgradParams& p3, const WgradParams& p1, hipStream_t stream) {
+    const int ksplit = vpd_wgrad_split(p3.M, p3.Co, p3.Kc, nullptr);
+    WgReduceGroup red = {};
+    red.nprob = 2;
+    red.slab[0] = reinterpret_cast<const float4*>(p3.slab); red.dw[0] = reinterpret_cast<float4*>(p3.dw);
+    red.slab[1] = reinterpret_cast<const float4*>(p1.slab); red.dw[1] = reinterpret_cast<float4*>(p1.dw);
+    red.n4[0] = (long)9 * p3.Co * p3.Kc / 4; red.n4[1] = (long)p3.Co * p3.Kc / 4;
+    red.ksplit[0] = red.ksplit[1] = ksplit;
+    const int groups = ksplit < 16 ? ksplit : 16;
+    hipLaunchKernelGGL(wgrad_slab_reduce_group_kernel, dim3((unsigned)((red.n4[0] + 63) / 64), 2), dim3(64 * groups), 0, stream, red,
+                       groups);
+    return hipGetLastError();
+}
+hipError_t vpd_launch_wgrad_pair(const WgradParams& p3, const WgradParams& p1, hipStream_t stream) {
+    if (!vpd_wgrad_pair_ok(p3, p1)) return hipErrorInvalidValue;
+    WgradParams p = p3;
+#ifdef VPD_ENABLE_ABLATE
+    p.ablate = vpd_switches().ablate;
+#else
+    p.ablate = 0;
+#endif
+    WgHaloGeom g;
+    if (!wg_halo_geom(p, &g)) return hipErrorInvalidValue;
+    const int tiles = (p.Co / 64) * (p.Kc / 64);
+    g.ksplit = vpd_wgrad_split(p.M, p.Co, p.Kc, &g.cpb);
+    const int npass = (g.NHP + 31) / 32;
+    size_t lds = 0;
+    if (!wg_pair_lds(npass, npass > 10 ? 2 : VPD_WG_PAIR_NS, &lds)) return hipErrorInvalidValue;
+    const WgPair pr{p1.dz, p1.slab};
+    if (npass <= 10) VPD_LAUNCH((conv_wgrad_halo_pair_kernel<10, VPD_WG_PAIR_NS>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g, pr);
+    else VPD_LAUNCH((conv_wgrad_halo_pair_kernel<13, 2>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g, pr);
+    if (p.defer_reduce || VPD_ABL(p, 16)) return hipGetLastError();
+    return vpd_launch_wgrad_pair_reduce(p3, p1, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -110,6 +110,14 @@ bool vpd_wgrad_group_eligible(const WgradParams& p);
 size_t vpd_wgrad_group_slab_floats(int M, int Co, int Kc, int ntaps = 9);
 hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stream);
 bool vpd_wgrad_overwrites(const WgradParams& p);
+// A down-sampling BasicBlock's 3x3 stride-2 conv1 (p3) and its 1x1 stride-2 branch (p1, prefer_halo_1x1 set) in ONE halo launch: the
+// branch rides as a tenth tap on conv1's staged halo (conv_wgrad_halo_pair_kernel; VPD_WGRAD_DS_RIDE=0: never).  _ok: both take the
+// halo path and share input, shapes and split.  The launch leaves both slabs unsummed when p3.defer_reduce; _reduce sums both in one
+// launch.  hipErrorInvalidValue when the pair does not qualify or its LDS layout is over 160 KB.
+bool vpd_wgrad_pair_ok(const WgradParams& p3, const WgradParams& p1);
+hipError_t vpd_launch_wgrad_pair(const WgradParams& p3, const WgradParams& p1, hipStream_t stream);
+hipError_t vpd_launch_wgrad_pair_reduce(const WgradParams& p3, const WgradParams& p1, hipStream_t stream);
+int vpd_wgrad_pair_lds_query(int H, int W, int ns, long long* bytes);
 // 128 x 64 tiles, persistent blocks, host-built schedule (conv_wgrad128_persistent_kernel in conv_wgrad.hip)
 bool vpd_wgrad128_eligible(const WgradParams& p);
 size_t vpd_wgrad128_table_bytes();

@@ -24,7 +24,7 @@ int fail(const char* what, hipError_t e) {
 
 extern "C" const char* vpd_last_error(void) { return g_err.c_str(); }
 extern "C" const char* vpd_elem_dtype(void) { return VPD_ELEM_NAME; }      // "bf16" (libvpdhip.so) or "fp16" (libvpdhip_f16.so)
-extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2; 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
+extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2 (+ vpd_op_wgrad_pair, vpd_op_wgrad_pair_lds_bytes: test-only additions, no existing signature changed, number kept); 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
 
 namespace {
 
@@ -1046,6 +1046,29 @@ extern "C" int vpd_op_wgrad(const void* dz, const void* x, float* dw, int n, int
     if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
     LCHECK(vpd_launch_wgrad(q, (hipStream_t)stream));
     return 0;
+}
+
+extern "C" int vpd_op_wgrad_pair(const void* dz, const void* dz2, const void* x, float* dw, float* dw2, int n, int dzHp, int dzWp,
+                                 int dzC, int dzpad, int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co,
+                                 const int* tapset9, float* slab, float* slab2, void* stream) {
+    if (!dz || !dz2 || !x || !dw || !dw2 || !tapset9 || !slab || !slab2) return fail("null argument");
+    if (n < 1 || Hs < 1 || Ws < 1) return fail("bad argument");
+    WgradParams q;
+    memset(&q, 0, sizeof q);
+    q.dz = (const bf16_t*)dz; q.dzHp = dzHp; q.dzWp = dzWp; q.dzC = dzC; q.dzpad = dzpad;
+    q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.dw = dw; q.slab = slab;
+    q.N = n; q.Hs = Hs; q.Ws = Ws; q.istr = istr; q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws;
+    WgradParams q1 = q;                       // the branch: one tap at padded offset (1, 1)
+    q1.dz = (const bf16_t*)dz2; q1.dw = dw2; q1.slab = slab2; q1.prefer_halo_1x1 = 1;
+    q1.taps.nr = 1; q1.taps.nc = 1; q1.taps.dy0 = 1; q1.taps.dys = 1; q1.taps.dx0 = 1; q1.taps.dxs = 1;
+    q1.taps.w0 = 0; q1.taps.wrs = 1; q1.taps.wcs = 1;
+    q.taps = tapset_from(tapset9);
+    if (!vpd_wgrad_pair_ok(q, q1)) return fail("not a pair the halo weight-gradient launch takes (shapes, or VPD_WGRAD_DS_RIDE=0 / VPD_WGRAD_1X1=0 / VPD_WGRAD_S2=0)");
+    LCHECK(vpd_launch_wgrad_pair(q, q1, (hipStream_t)stream));
+    return 0;
+}
+extern "C" int vpd_op_wgrad_pair_lds_bytes(int Hs, int Ws, int ns, long long* bytes) {
+    return vpd_wgrad_pair_lds_query(Hs, Ws, ns, bytes);
 }
 
 // Grouped 128 x 64 weight gradients (conv_wgrad128_persistent_kernel) of `nprob` 3x3 stride-1 pad-1 convolutions in ONE

@@ -250,6 +250,40 @@ hipError_t run_conv_wgrad(const Ctx& c, const ConvInfo& cv, const bf16_t* dz, co
     return vpd_launch_wgrad(q, c.s);
 }
 
+// A down-sampling BasicBlock's conv1 (3x3 stride 2) and 1x1 branch, as run_conv_wgrad states them: dw, slab regions and the halo
+// wish of each stay what they are.
+static void wgrad_pair_params(const Ctx& c, const ConvInfo& c1, const ConvInfo& cd, const bf16_t* dz1, const bf16_t* dzd, const bf16_t* x,
+                              WgradParams* q3, WgradParams* q1) {
+    float* slab = c.f32(c.p->slab_off);
+    const ConvInfo* cvs[2] = {&c1, &cd};
+    WgradParams* qs[2] = {q3, q1};
+    for (int i = 0; i < 2; ++i) {
+        *qs[i] = wgrad_params(*cvs[i], c.n, i ? dzd : dz1, x);
+        qs[i]->dw = c.f32(c.p->wg_off) + cvs[i]->wg_off;
+        qs[i]->slab = cvs[i]->slab_off >= 0 ? slab + cvs[i]->slab_off : nullptr;
+        qs[i]->prefer_halo_1x1 = !c.p->bottleneck;
+    }
+}
+// ... can run as ONE launch, the branch riding on conv1's staged halo (vpd_wgrad_pair_ok; VPD_WGRAD_DS_RIDE=0: two launches)
+bool wgrad_pair_ok(const Ctx& c, const ConvInfo& c1, const ConvInfo& cd) {
+    if (c1.stem || cd.stem || c1.dz_own_off || cd.dz_own_off) return false;
+    WgradParams q3, q1;
+    wgrad_pair_params(c, c1, cd, c.b16(0), c.b16(0), c.b16(0), &q3, &q1);
+    return vpd_wgrad_pair_ok(q3, q1);
+}
+hipError_t run_conv_wgrad_pair(const Ctx& c, const ConvInfo& c1, const ConvInfo& cd, const bf16_t* dz1, const bf16_t* dzd, const bf16_t* x) {
+    WgradParams q3, q1;
+    wgrad_pair_params(c, c1, cd, dz1, dzd, x, &q3, &q1);
+    hipError_t e;
+    {
+        TimeScope ts(c.p, c.s, 6, conv_flops(c1, c.n) + conv_flops(cd, c.n));      // (class 6, as each of the two launches it replaces)
+        q3.defer_reduce = 1;
+        e = vpd_launch_wgrad_pair(q3, q1, c.s);
+    }
+    if (e != hipSuccess) return e;
+    return vpd_launch_wgrad_pair_reduce(q3, q1, c.s);
+}
+
 BnApplyParams bn_apply_params(const Ctx& c, const ConvInfo& cv, int res_kind, const bf16_t* res, bf16_t* out, int relu) {
     BnApplyParams a;
     memset(&a, 0, sizeof a);
@@ -807,11 +841,14 @@ struct Backward {
         }
         LCHECK(wq.queue(B.c2, dz2, c.b16(B.a1_off)));
         if (inner_bn_bwd(B.c2, dz2, da1, B.c1, B.mask1_off, dz1)) return -1;
-        LCHECK(wq.queue(B.c1, dz1, xin));
+        // a down-sampling block: the 1x1 branch's weight gradient rides in conv1's launch, which then waits for the branch's dz
+        const bool wg_pair = B.ds && wgrad_pair_ok(c, B.c1, B.cd);
+        if (!wg_pair) LCHECK(wq.queue(B.c1, dz1, xin));
         BnSums sm;
         if (B.ds) {
             if (!bn_pair) LCHECK(run_bn_bwd(c, B.cd, dout, nullptr, dzd, 1, 0, grads));
-            LCHECK(wq.queue(B.cd, dzd, xin));
+            if (wg_pair) LCHECK(run_conv_wgrad_pair(c, B.c1, B.cd, dz1, dzd, xin));
+            else LCHECK(wq.queue(B.cd, dzd, xin));
             if (conv_pair_ok(c, B.c1, B.cd, true)) {
                 // one launch: the 1x1 branch's data gradient is extra K-steps of the even-even class
                 LCHECK(run_conv_dgrad(c, B.c1, dz1, dnew, 0, &B.cd, dzd, nullptr, prev_bn2_sums(bi, sm)));

@@ -44,6 +44,7 @@
     X(wg_merge,           "VPD_WG_MERGE",          1)          \
     X(wgrad_1x1,          "VPD_WGRAD_1X1",        -1)          \
     X(wgrad_s2,           "VPD_WGRAD_S2",          1)          \
+    X(wgrad_ds_ride,      "VPD_WGRAD_DS_RIDE",     1)          \
     X(stem_lds_store,     "VPD_STEM_LDS_STORE",    1)          \
     X(stem_pair,          "VPD_STEM_PAIR",         1)          \
     X(stem_quad,          "VPD_STEM_QUAD",         1)          \
