@@ -30,6 +30,14 @@ def get_args():
     return parser.parse_args()
 
 
+def input_route(host_fp32, jitter):
+    """(raw_u8, device jitter count): decoded u8 frames cross PCIe and every view -- [orig, J x jitter(orig), J x jitter(flip),
+    flip] -- is built on the device, --jitter included; --host_fp32 keeps the reference's route (fp32 views from the
+    DataLoader workers, jitter included)."""
+    raw_u8 = not host_fp32
+    return raw_u8, (int(jitter or 0) if raw_u8 else 0)
+
+
 def main(dataset, model_dir, out_dir, model_epoch, flow_img, jitter, no_flip, host_fp32=False, dtype='bf16'):
     device = 'cuda'
     model_params = load_json(os.path.join(model_dir, 'config.json'))
@@ -53,10 +61,11 @@ def main(dataset, model_dir, out_dir, model_epoch, flow_img, jitter, no_flip, ho
         videos, tasks = list_tennis_crops(dataset_paths.TENNIS_VIDEO_DIR, dataset_paths.TENNIS_CROP_DIR)
     else:
         videos, tasks = list_crop_dir(dataset_paths.CROPS[dataset])
-    # default: decoded u8 frames cross PCIe (82 KB instead of 655 KB per frame) and the views [orig, h-flip] are built on the
-    # device; --jitter needs the host fp32 views (ColorJitter on the normalised image, single_frame.py:366-379)
-    raw_u8 = not host_fp32 and not jitter
-    ds = FrameDataset(tasks, img_dim, rgb_mean_std, augment_jitter=jitter or 0, augment_flip=not no_flip,
+    # default: decoded u8 frames cross PCIe (82 KB per frame, whatever the view count) and the views are built on the device,
+    # the jittered ones of --jitter too (ColorJitter on the normalised image, single_frame.py:366-379: vpd_plan_stage_views_jitter);
+    # the raw dataset then carries no views of its own and the count goes to embed_dataset.  --host_fp32: fp32 views from the host
+    raw_u8, device_jitter = input_route(host_fp32, jitter)
+    ds = FrameDataset(tasks, img_dim, rgb_mean_std, augment_jitter=0 if raw_u8 else (jitter or 0), augment_flip=not no_flip,
                       flow_img_name=flow_img, raw_u8=raw_u8)
 
     model_name = 'best_epoch' if model_epoch is None else 'epoch{:04d}'.format(model_epoch)
@@ -77,7 +86,7 @@ def main(dataset, model_dir, out_dir, model_epoch, flow_img, jitter, no_flip, ho
         from vpd_amd.augment import CropAugmenter
         augmenter = CropAugmenter(device, rgb_mean_std, img_dim, use_flow)
     embed_dataset(encoder, loader, len(videos), writer=StreamingWriter(out_dir, videos, frames_per_video),
-                  augmenter=augmenter, flip=not no_flip)
+                  augmenter=augmenter, flip=not no_flip, jitter=device_jitter)
     print('Done!')
 
 

@@ -230,6 +230,25 @@ int vpd_plan_stage_crops(vpd_plan_t* plan, const unsigned char* rgb_u8, const un
 int vpd_plan_stage_views(vpd_plan_t* plan, const unsigned char* rgb_u8, const unsigned char* flow_u8, int n_frames,
                          int k_views, int height, int width, const float* mean_std6, void* workspace, void* stream);
 
+/* Jittered inference views (apply_vpd_model.py --jitter J; FrameDataset, vpd_dataset/single_frame.py:373-400).  Per frame, in
+ * the reference's order: [frame, J x jitter(frame), J x jitter(flip(frame)), flip(frame)] when flip, else [frame, J x
+ * jitter(frame)]: K = (1 + jitter) * (1 + flip) views, n_frames * K crops in the order [f0 v0, f0 v1, ..., f1 v0, ...].
+ * As in the reference, ColorJitter acts on the NORMALISED image (u8 / 255 - mean) / std, unclamped; every op clamps to [0, 1]
+ * and the result is not normalised again; the jittered views of the flipped frame carry the UNFLIPPED, un-negated flow, only
+ * the last view has the mirrored flow with x negated.  Views 0 and K - 1 are bit-identical to vpd_plan_stage_views' two.
+ * params: DEVICE array of n_frames * jitter * (1 + flip) rows, frame-major in view order; only `order` and `factor` are read
+ * (order[k] = -1 skips a slot); may be NULL when jitter == 0.  scratch: 8 floats per parameter row on the device (partial
+ * sums of the contrast op's grey mean, added in a fixed order: the output is reproducible from launch to launch).
+ * width must be a multiple of 4; at most 65535 views per call.  out_nchw: f32 [n_frames * K][3 or 5][height][width]. */
+int vpd_augment_views(const unsigned char* rgb_u8, const unsigned char* flow_u8, const vpd_aug_params* params, int n_frames,
+                      int jitter, int flip, int height, int width, const float* mean_std6, float* out_nchw, float* scratch,
+                      void* stream);
+/* Same views, written straight into the EVAL plan's stem staging buffer (height == width == the plan's image size): follow
+ * with vpd_forward_eval / vpd_graph_capture_eval with x == NULL. */
+int vpd_plan_stage_views_jitter(vpd_plan_t* plan, const unsigned char* rgb_u8, const unsigned char* flow_u8,
+                                const vpd_aug_params* params, int n_frames, int jitter, int flip, int height, int width,
+                                const float* mean_std6, float* scratch, void* workspace, void* stream);
+
 int vpd_graph_capture_eval(vpd_plan_t* plan, const float* params, const float* x, int n, float* emb_out,
                            void* workspace, void* stream);
 int vpd_graph_launch_eval(vpd_plan_t* plan, int n, void* stream);

@@ -72,14 +72,19 @@ class StreamingWriter:
                 self.flush(vid)
 
 
-def embed_dataset(encoder, loader, n_videos, progress_cb=None, use_graph=True, writer=None, augmenter=None, flip=True):
+def embed_dataset(encoder, loader, n_videos, progress_cb=None, use_graph=True, writer=None, augmenter=None, flip=True,
+                  jitter=0, generator=None):
     """loader yields {'video': int[n], 'frame': int[n], 'img': f32[n,k,C,H,W]} -> list per video, or, with
     `writer` (a StreamingWriter), pickles written as videos complete (returns None).
 
     Raw batches {'video', 'frame', 'rgb_u8': u8[n,H,W,3], 'flow_u8': u8[n,H,W,2]} (FrameDataset(raw_u8=True)) need
     `augmenter` (a vpd_amd.augment.CropAugmenter with the model's mean / std): 82 KB per frame cross PCIe instead of the
     655 KB of two fp32 views, and the views [orig, h-flip] (`flip`) are built on the device in the stem's staging buffer
-    (same values as FrameDataset's fp32 views, vpd_dataset/single_frame.py:377-400).
+    (same values as FrameDataset's fp32 views, vpd_dataset/single_frame.py:377-400).  `jitter` = J > 0 (--jitter): K =
+    (1 + J)(1 + flip) views per frame in the reference's order [orig, J x jitter(orig), J x jitter(flip(orig)), flip(orig)],
+    all built on the device from the same u8 frames; the ColorJitter decisions are drawn per batch (`generator`: a torch CPU
+    generator, or the global one) and their rows travel with the frames.  fp32 batches carry their views: `jitter` is not
+    used for them.
 
     The embeddings of batch i travel to a pinned host buffer asynchronously; the host turns batch i-1 into tuples
     (and pickles) while the GPU runs batch i."""
@@ -122,13 +127,15 @@ def embed_dataset(encoder, loader, n_videos, progress_cb=None, use_graph=True, w
     if ours:
         gc.freeze()
     try:
-        return _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, augmenter, flip, use_graph)
+        return _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, augmenter, flip, use_graph,
+                           int(jitter or 0), generator)
     finally:
         if ours:
             gc.unfreeze()
 
 
-def _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, augmenter, flip, use_graph):
+def _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, augmenter, flip, use_graph, jitter=0,
+                generator=None):
     inflight = None      # (event, host buffer, video_ids, frame_nums, n_batch, k)
     slot = 0
     for batch in loader:
@@ -138,7 +145,7 @@ def _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, aug
             if augmenter is None:
                 raise RuntimeError("raw u8 batches need embed_dataset(..., augmenter=CropAugmenter(...))")
             assert (batch.get('flow_u8') is not None) == bool(encoder.use_flow), 'Wrong number of channels'
-            n_batch, k = batch['rgb_u8'].shape[0], (2 if flip else 1)
+            n_batch, k = batch['rgb_u8'].shape[0], (1 + jitter) * (2 if flip else 1)
             # H2D on a copy stream into one of two device slots: batch i + 1 crosses PCIe while batch i's forward runs
             cur = torch.cuda.current_stream(eng.device)
             cp = eng.__dict__.setdefault("_apply_copy_stream", None) or torch.cuda.Stream(device=eng.device)
@@ -152,16 +159,30 @@ def _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, aug
                               torch.empty(tuple(batch['rgb_u8'].shape[:3]) + (2,), dtype=torch.uint8, device=eng.device)
                               if encoder.use_flow else None, None]
             rgb, flow, freed = ubuf[ukey]
+            prow = pdev = None
+            if jitter:
+                # fresh ColorJitter decisions for this batch: 64 bytes per jittered view, uploaded with the frames
+                from .augment import sample_view_params
+                prow = sample_view_params(n_batch, jitter, flip, generator)
+                pbuf = eng.__dict__.setdefault("_apply_params", {})
+                pkey = (len(prow), uslot)
+                if pkey not in pbuf:
+                    pbuf[pkey] = torch.empty((len(prow), 64), dtype=torch.uint8, device=eng.device)
+                pdev = pbuf[pkey]
             with torch.cuda.stream(cp):
                 if freed is not None:
                     cp.wait_event(freed)             # the staging launch that last read this slot is done
                 rgb.copy_(batch['rgb_u8'], non_blocking=True)
                 if flow is not None:
                     flow.copy_(batch['flow_u8'], non_blocking=True)
+                if pdev is not None:
+                    pdev.copy_(torch.from_numpy(prow.view(np.uint8).reshape(len(prow), 64)), non_blocking=True)
                 landed = torch.cuda.Event()
                 landed.record(cp)
             cur.wait_event(landed)
-            n, hw = augmenter.stage_views(eng, rgb, flow, flip)
+            stage = (lambda: augmenter.stage_views(eng, rgb, flow, flip, jitter=jitter, params=pdev)) if jitter else \
+                (lambda: augmenter.stage_views(eng, rgb, flow, flip))
+            n, hw = stage()
             ubuf[ukey][2] = torch.cuda.Event()
             ubuf[ukey][2].record(cur)
             key = ('staged', n, hw)
@@ -172,7 +193,7 @@ def _embed_loop(encoder, eng, loader, graphs, host, drain, writer, all_embs, aug
                 if ent is None:
                     out = torch.empty((n, encoder.emb_dim), dtype=torch.float32, device=eng.device)
                     ent = graphs[key] = (eng.capture_eval_graph_staged(n, hw, out), None, out)
-                    augmenter.stage_views(eng, rgb, flow, flip)      # (a larger plan may have been built: stage again)
+                    stage()      # (a larger plan may have been built: stage again)
                     ubuf[ukey][2].record(cur)
                 pl, _, out = ent
                 eng.launch_eval_graph(pl, n)

@@ -13,6 +13,10 @@ mixes Python's and torch's generators, so there is no reference random stream to
     img = aug(rgb_u8, flow_u8, mask_u8, params)           # f32 [n, 5, 128, 128] on the device == batch['img']
     # or, fused with the stem's staging (no fp32 batch at all):
     aug.stage(engine, rgb_u8, flow_u8, mask_u8, params, train=True); engine.forward_train(None, tgt, staged=(n, 128))
+
+Inference views (FrameDataset, vpd_dataset/single_frame.py:373-400) come from the same u8 frames: ``stage_views`` writes
+[orig, h-flip] and, with ``jitter=J``, [orig, J x jitter(orig), J x jitter(flip(orig)), flip(orig)] -- ColorJitter on the
+NORMALISED image, as the reference has it -- from ``sample_view_params`` rows; ``views`` returns them as an fp32 batch.
 """
 import ctypes as C
 import math
@@ -100,6 +104,32 @@ def sample_params(n, height, width, augment=True, flip=True, generator=None, see
     return p
 
 
+def view_count(jitter, flip):
+    """K = (1 + J)(1 + flip) views per frame: [orig, J x jitter(orig), J x jitter(flip(orig)), flip(orig)]."""
+    return (1 + int(jitter or 0)) * (2 if flip else 1)
+
+
+def sample_view_params(n_frames, jitter, flip, generator=None):
+    """ColorJitter decisions of the jittered inference views (FrameDataset, vpd_dataset/single_frame.py:377-386): one row per
+    jittered view, n_frames * jitter * (1 + flip) rows, frame-major in view order (a frame's J rows for jitter(orig), then
+    its J rows for jitter(flip(orig))).  Order and factors have ColorJitter.get_params' distributions (a uniformly random
+    permutation of the four ops; b, c, s, h uniform in JITTER_KWARGS' ranges), drawn in two batched calls like
+    sample_params; only `order` and `factor` are read on the device.  The reference seeds nothing: no stream to match."""
+    rows = int(n_frames) * int(jitter or 0) * (2 if flip else 1)
+    p = np.zeros(rows, dtype=AUG_DTYPE)
+    p['order'] = -1
+    p['factor'] = (1.0, 1.0, 1.0, 0.0)
+    if rows == 0:
+        return p
+    rand = lambda *shape: torch.rand(shape, generator=generator, dtype=torch.float64).numpy()
+    p['order'] = np.argsort(rand(rows, 4), axis=1).astype(np.int32)
+    jk = JITTER_KWARGS
+    lo = np.array([1 - jk['brightness'], 1 - jk['contrast'], 1 - jk['saturation'], -jk['hue']])
+    hi = np.array([1 + jk['brightness'], 1 + jk['contrast'], 1 + jk['saturation'], jk['hue']])
+    p['factor'] = (lo + rand(rows, 4) * (hi - lo)).astype(np.float32)
+    return p
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -158,10 +188,59 @@ class CropAugmenter:
                            self._scratch, train, motion)
         return n, self.img_dim
 
-    def stage_views(self, engine, rgb_u8, flow_u8, flip):
+    def _check_views(self, rgb_u8, flow_u8, jitter, flip, params):
+        """Arguments of the jittered views: frames of the model's size; `params` = sample_view_params rows (numpy) or the
+        same rows already on the device (u8 [rows, 64]).  Returns (n, h, w, device rows or None)."""
+        assert rgb_u8.dtype == torch.uint8 and rgb_u8.dim() == 4 and rgb_u8.shape[3] == 3 and rgb_u8.is_contiguous() \
+            and rgb_u8.is_cuda, 'rgb_u8 must be a contiguous device u8 [N,H,W,3]'
+        n, h, w, _ = rgb_u8.shape
+        if self.use_flow:
+            assert flow_u8 is not None and flow_u8.dtype == torch.uint8 and tuple(flow_u8.shape) == (n, h, w, 2) \
+                and flow_u8.is_contiguous() and flow_u8.is_cuda, 'flow_u8 must be a device u8 [N,H,W,2]'
+        else:
+            assert flow_u8 is None, 'flow_u8 given to a 3-channel pipeline'
+        rows = n * jitter * (2 if flip else 1)
+        if rows == 0:
+            return n, h, w, None
+        if params is None:
+            raise ValueError('jittered views need params = sample_view_params(n_frames, jitter, flip)')
+        if isinstance(params, np.ndarray):
+            assert params.dtype == AUG_DTYPE and params.shape == (rows,), \
+                'params: n_frames * jitter * (1 + flip) vpd_aug_params rows'
+            params = torch.from_numpy(params.view(np.uint8).reshape(rows, 64)).to(self.device, non_blocking=True)
+        assert params.dtype == torch.uint8 and tuple(params.shape) == (rows, 64) and params.is_contiguous() \
+            and params.is_cuda, 'params: device u8 [n_frames * jitter * (1 + flip), 64]'
+        if self._scratch is None or self._scratch.numel() < 8 * rows:       # 8 partial grey sums per parameter row
+            self._scratch = torch.empty(8 * max(rows, 256), dtype=torch.float32, device=self.device)
+        return n, h, w, params
+
+    def views(self, rgb_u8, flow_u8, jitter, flip, params, out=None, dtype="bf16"):
+        """The inference views of n decoded frames as an fp32 batch [n * K, C, H, W], K = (1 + jitter)(1 + flip), in the
+        reference's order [orig, J x jitter(orig), J x jitter(flip(orig)), flip(orig)] (FrameDataset's 'img', flattened)."""
+        jitter = int(jitter or 0)
+        n, h, w, pdev = self._check_views(rgb_u8, flow_u8, jitter, flip, params)
+        k = view_count(jitter, flip)
+        if out is None:
+            out = torch.empty((n * k, 5 if self.use_flow else 3, h, w), dtype=torch.float32, device=self.device)
+        ms = (C.c_float * 6)(*self.mean_std6)
+        check(lib(dtype).vpd_augment_views(_ptr(rgb_u8), _ptr(flow_u8), _ptr(pdev), n, jitter, 1 if flip else 0, h, w, ms,
+                                           _ptr(out), _ptr(self._scratch if pdev is not None else None),
+                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)),
+              'vpd_augment_views', dtype)
+        return out
+
+    def stage_views(self, engine, rgb_u8, flow_u8, flip, jitter=0, params=None):
         """Inference views of FrameDataset (vpd_dataset/single_frame.py:377-400) for n decoded frames, written straight into
         the EVAL plan's stem staging buffer: k = 2 views per frame in the order [orig, h-flip] (x-flow negated in the flipped
-        view) when `flip`, else the frame itself.  Returns (n * k, img_dim) for forward_eval / the staged eval graph."""
+        view) when `flip`, else the frame itself.  Returns (n * k, img_dim) for forward_eval / the staged eval graph.
+
+        jitter = J > 0: K = (1 + J)(1 + flip) views [orig, J x jitter(orig), J x jitter(flip(orig)), flip(orig)] with the
+        decisions `params` (sample_view_params rows, host or device); frames must have the model's size."""
+        jitter = int(jitter or 0)
+        if jitter:
+            n, h, w, pdev = self._check_views(rgb_u8, flow_u8, jitter, flip, params)
+            engine.stage_views_jitter(rgb_u8, flow_u8, pdev, jitter, flip, self.mean_std6, self._scratch)
+            return n * view_count(jitter, flip), self.img_dim
         n, h, w, _ = rgb_u8.shape
         k = 2 if flip else 1
         if h == self.img_dim and w == self.img_dim and w % 4 == 0 and os.environ.get("VPD_FAST_VIEWS", "1") != "0":

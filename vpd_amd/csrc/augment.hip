@@ -383,3 +383,192 @@ hipError_t vpd_launch_views(const unsigned char* rgb, const unsigned char* flow,
     hipLaunchKernelGGL(aug_views_kernel, dim3((quads + 255) / 256, F * K), dim3(256), 0, s, g);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// Jittered inference views (apply_vpd_model.py --jitter J; vpd_dataset/single_frame.py:373-400): per frame
+//   [orig, J x jitter(orig), J x jitter(flip(orig)), flip(orig)]   (with flip)      [orig, J x jitter(orig)]   (without)
+// = K = (1 + J)(1 + flip) views.  The reference's quirks are kept: ColorJitter acts on the NORMALISED image (u8 / 255 - mean) /
+// std, unclamped, whichever op comes first (every op then clamps to [0, 1] and nothing is normalised again -- a different
+// function of the pixels than the train-time kernel's jitter-then-normalise); the jittered views of the flipped image carry the
+// UNFLIPPED, un-negated flow (:388-399: only the plain flip gets flip_flow).
+//
+// Two launches, like the train pipeline: (1) fixed-order partial sums of the grey mean for the contrast op of every parameter
+// row (F * J * (1 + flip) rows); (2) one thread per quad of SOURCE pixels of one frame writes that quad into all K views: the
+// unflipped views at the quad's own place, the flipped ones back to front at the mirrored place.  The u8 source is read once
+// per frame (12 + 8 bytes per quad, + the 8 flow bytes of the mirrored quad for the jittered flips) against K x 64 (staging) or
+// K x 80 (fp32) bytes written.  A flipped view's mean is the unflipped image's (the same pixels in another order), so one
+// partial-sum row per parameter row serves both.  The normalisation is the byte table of aug_views_kernel, kept in fp32: the
+// plain views round the same values to the element type as that kernel does (bit-identical), the jitter starts from them.
+// The parameter rows are uniform over a block (grid row = frame), so the op dispatch in jitter() is scalar control flow.
+// ---------------------------------------------------------------------------
+struct JViewArgs {
+    const unsigned char* rgb; const unsigned char* flow;      // [F][H][W][3], [F][H][W][2] or null
+    const vpd_aug_params* params; const float* cmean;         // [F][J * (1 + flip)] rows, AUG_MEAN_PARTS partial sums per row
+    int F, J, flip, H, W;
+    float mean[3], std[3];
+    float* out_nchw;                                          // [F*K][3 or 5][H][W] or null
+    bf16_t* xin; int xHp, xWp, xpad;                          // [F*K][xHp][xWp][8] or null
+};
+
+// byte -> fp32 value tables: [0..2] (u / 255 - mean) / std per channel, [3] flow u / 255 - 0.5 (double, rounded) -- the
+// expressions of source_pixel(); blockDim.x == 256
+__device__ __forceinline__ void view_tables(float (*lut)[256], const float* mean, const float* std) {
+    const int t = threadIdx.x;
+    const float c = (float)t / 255.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lut[k][t] = (c - mean[k]) / std[k];
+    lut[3][t] = (float)((double)t / 255.0 - 0.5);
+    __syncthreads();
+}
+// pixel j (0..3) of an aligned 12-byte RGB block held in three dwords
+__device__ __forceinline__ Rgb quad_rgb(const unsigned w[3], int j, float (*lut)[256]) {
+    const int b = j * 3;
+    Rgb c;
+    c.r = lut[0][(w[b >> 2] >> ((b & 3) * 8)) & 0xffu];
+    c.g = lut[1][(w[(b + 1) >> 2] >> (((b + 1) & 3) * 8)) & 0xffu];
+    c.b = lut[2][(w[(b + 2) >> 2] >> (((b + 2) & 3) * 8)) & 0xffu];
+    return c;
+}
+
+// (1) grey mean of the normalised frame at the point where the contrast op of parameter row blockIdx.y runs
+__global__ __launch_bounds__(256) void aug_views_mean_kernel(const JViewArgs g, float* partial) {
+    __shared__ float lut[4][256];
+    __shared__ float sh[4];
+    const int row = blockIdx.y, part = blockIdx.x;
+    const int HW = g.H * g.W;
+    const vpd_aug_params a = g.params[row];
+    int kc = -1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (a.order[k] == 1) kc = k;
+    if (kc < 0) {                                             // block-uniform
+        if (threadIdx.x == 0) partial[row * AUG_MEAN_PARTS + part] = 0.f;
+        return;
+    }
+    view_tables(lut, g.mean, g.std);
+    const unsigned* img = reinterpret_cast<const unsigned*>(g.rgb + (size_t)(row / (g.J * (1 + g.flip))) * HW * 3);
+    const int nq = HW >> 2;                                   // quads (HW % 4 == 0: the width is a multiple of 4)
+    const int per = (nq + AUG_MEAN_PARTS - 1) / AUG_MEAN_PARTS;
+    const int beg = part * per;
+    const int end = beg + per < nq ? beg + per : nq;
+    float acc = 0.f;
+    for (int q = beg + threadIdx.x; q < end; q += 256) {
+        const unsigned w[3] = {img[3 * q], img[3 * q + 1], img[3 * q + 2]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc += grey(jitter(quad_rgb(w, j, lut), a, 0, kc, 0.f));
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[row * AUG_MEAN_PARTS + part] = sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+// four consecutive pixels of one view row: fp32 NCHW (one float4 per channel) and / or the staging row (one uint4 per pixel)
+__device__ __forceinline__ void view_store(const JViewArgs& g, int view, int y, int x, const Rgb c[4], const float fx[4],
+                                           const float fy[4]) {
+    if (g.out_nchw) {
+        const int C = g.flow ? 5 : 3;
+        const size_t plane = (size_t)g.H * g.W;
+        float* dst = g.out_nchw + (size_t)view * C * plane + (size_t)y * g.W + x;
+        *reinterpret_cast<float4*>(dst) = make_float4(c[0].r, c[1].r, c[2].r, c[3].r);
+        *reinterpret_cast<float4*>(dst + plane) = make_float4(c[0].g, c[1].g, c[2].g, c[3].g);
+        *reinterpret_cast<float4*>(dst + 2 * plane) = make_float4(c[0].b, c[1].b, c[2].b, c[3].b);
+        if (g.flow) {
+            *reinterpret_cast<float4*>(dst + 3 * plane) = make_float4(fx[0], fx[1], fx[2], fx[3]);
+            *reinterpret_cast<float4*>(dst + 4 * plane) = make_float4(fy[0], fy[1], fy[2], fy[3]);
+        }
+    }
+    if (g.xin) {
+        bf16_t* dst = g.xin + (((size_t)view * g.xHp + y + g.xpad) * g.xWp + x + g.xpad) * 8;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            uint4 o;
+            o.x = pack2bf(c[i].r, c[i].g);
+            o.y = pack2bf(c[i].b, fx[i]);
+            o.z = pack2bf(fy[i], 0.f);
+            o.w = 0u;
+            *reinterpret_cast<uint4*>(dst + i * 8) = o;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void aug_views_jitter_kernel(const JViewArgs g) {
+    __shared__ float lut[4][256];
+    view_tables(lut, g.mean, g.std);
+    const int frame = blockIdx.y;
+    const int q = blockIdx.x * 256 + threadIdx.x;             // quad of source pixels inside the frame
+    const int wq = g.W >> 2;
+    if (q >= g.H * wq) return;
+    const int y = q / wq, x0 = (q - y * wq) << 2;
+    const int xm = g.W - 4 - x0;                              // where the quad lands, back to front, in a flipped view
+    const size_t row = ((size_t)frame * g.H + y) * g.W;
+    const unsigned* pr = reinterpret_cast<const unsigned*>(g.rgb + (row + x0) * 3);
+    const unsigned w[3] = {pr[0], pr[1], pr[2]};
+    Rgb px[4], out[4];
+    float fx[4] = {0.f, 0.f, 0.f, 0.f}, fy[4] = {0.f, 0.f, 0.f, 0.f};            // flow of the quad
+    float mx[4] = {0.f, 0.f, 0.f, 0.f}, my[4] = {0.f, 0.f, 0.f, 0.f};            // flow of the mirrored quad, unflipped
+#pragma unroll
+    for (int j = 0; j < 4; ++j) px[j] = quad_rgb(w, j, lut);
+    if (g.flow) {
+        const unsigned* pf = reinterpret_cast<const unsigned*>(g.flow + (row + x0) * 2);
+        const unsigned f[2] = {pf[0], pf[1]};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            fx[j] = lut[3][(f[j >> 1] >> ((j & 1) * 16)) & 0xffu];
+            fy[j] = lut[3][(f[j >> 1] >> ((j & 1) * 16 + 8)) & 0xffu];
+        }
+        if (g.flip && g.J > 0) {
+            const unsigned* pm = reinterpret_cast<const unsigned*>(g.flow + (row + xm) * 2);
+            const unsigned m[2] = {pm[0], pm[1]};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                mx[j] = lut[3][(m[j >> 1] >> ((j & 1) * 16)) & 0xffu];
+                my[j] = lut[3][(m[j >> 1] >> ((j & 1) * 16 + 8)) & 0xffu];
+            }
+        }
+    }
+    const int K = (1 + g.J) * (1 + g.flip), rows = g.J * (1 + g.flip);
+    const int HW = g.H * g.W;
+    const int v0 = frame * K;
+    view_store(g, v0, y, x0, px, fx, fy);
+    for (int j = 0; j < g.J; ++j) {                           // jitter(orig)
+        const int r = frame * rows + j;
+        const vpd_aug_params a = g.params[r];
+        const float cmean = aug_contrast_mean(g.cmean, r, HW);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[i] = jitter(px[i], a, 0, 4, cmean);
+        view_store(g, v0 + 1 + j, y, x0, out, fx, fy);
+    }
+    if (!g.flip) return;
+    for (int j = 0; j < g.J; ++j) {                           // jitter(flip(orig)): mirrored colours over the unflipped flow
+        const int r = frame * rows + g.J + j;
+        const vpd_aug_params a = g.params[r];
+        const float cmean = aug_contrast_mean(g.cmean, r, HW);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[i] = jitter(px[3 - i], a, 0, 4, cmean);
+        view_store(g, v0 + 1 + g.J + j, y, xm, out, mx, my);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { out[i] = px[3 - i]; mx[i] = -fx[3 - i]; my[i] = fy[3 - i]; }
+    if (!g.flow) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) mx[i] = 0.f;              // (not -0: the channel is absent)
+    }
+    view_store(g, v0 + K - 1, y, xm, out, mx, my);            // flip(orig): mirrored flow, x negated
+}
+
+hipError_t vpd_launch_views_jitter(const unsigned char* rgb, const unsigned char* flow, const vpd_aug_params* params, int F,
+                                   int J, int flip, int H, int W, const float* mean_std6, float* out_nchw, bf16_t* xin,
+                                   int xHp, int xWp, int xpad, float* cmean_scratch, hipStream_t s) {
+    JViewArgs g;
+    g.rgb = rgb; g.flow = flow; g.params = params; g.cmean = cmean_scratch;
+    g.F = F; g.J = J; g.flip = flip ? 1 : 0; g.H = H; g.W = W;
+    for (int i = 0; i < 3; ++i) { g.mean[i] = mean_std6[i]; g.std[i] = mean_std6[3 + i]; }
+    g.out_nchw = out_nchw; g.xin = xin; g.xHp = xHp; g.xWp = xWp; g.xpad = xpad;
+    const int rows = J * (1 + g.flip);
+    if (rows > 0)
+        hipLaunchKernelGGL(aug_views_mean_kernel, dim3(AUG_MEAN_PARTS, F * rows), dim3(256), 0, s, g, cmean_scratch);
+    const int quads = H * (W / 4);
+    hipLaunchKernelGGL(aug_views_jitter_kernel, dim3((quads + 255) / 256, F), dim3(256), 0, s, g);
+    return hipGetLastError();
+}

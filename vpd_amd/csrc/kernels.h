@@ -232,3 +232,6 @@ hipError_t vpd_launch_augment(const unsigned char* rgb, const unsigned char* flo
                               int xpad, float* cmean_scratch, hipStream_t s);
 hipError_t vpd_launch_views(const unsigned char* rgb, const unsigned char* flow, int F, int K, int H, int W,
                             const float* mean_std6, bf16_t* xin, int xHp, int xWp, int xpad, hipStream_t s);
+hipError_t vpd_launch_views_jitter(const unsigned char* rgb, const unsigned char* flow, const vpd_aug_params* params, int F,
+                                   int J, int flip, int H, int W, const float* mean_std6, float* out_nchw, bf16_t* xin,
+                                   int xHp, int xWp, int xpad, float* cmean_scratch, hipStream_t s);

@@ -520,6 +520,49 @@ extern "C" int vpd_plan_stage_views(vpd_plan_t* p, const unsigned char* rgb_u8, 
     return 0;
 }
 
+// shared argument checks of the two jittered-view entry points (nothing is launched when one fails)
+static int check_jitter_views(const unsigned char* rgb_u8, const vpd_aug_params* params, int n_frames, int jitter, int height,
+                              int width, const float* mean_std6, const float* scratch) {
+    if (n_frames < 0 || jitter < 0) return fail("n_frames and jitter must not be negative");
+    if (!rgb_u8 || !mean_std6) return fail("null argument");
+    if (jitter > 0 && (!params || !scratch)) return fail("jittered views need params and scratch");
+    if (height < 1 || width < 1) return fail("bad shape");
+    if (width % 4) return fail("width must be a multiple of 4");
+    return 0;
+}
+
+extern "C" int vpd_augment_views(const unsigned char* rgb_u8, const unsigned char* flow_u8, const vpd_aug_params* params,
+                                 int n_frames, int jitter, int flip, int height, int width, const float* mean_std6,
+                                 float* out_nchw, float* scratch, void* stream) {
+    if (check_jitter_views(rgb_u8, params, n_frames, jitter, height, width, mean_std6, scratch)) return -1;
+    if (!out_nchw) return fail("null argument");
+    // (one grid row per frame / per parameter row: both stay below the view count)
+    if ((long)n_frames * (1 + jitter) * (flip ? 2 : 1) > 65535) return fail("n_frames * views exceeds 65535 views per call");
+    if (n_frames == 0) return 0;
+    LCHECK(vpd_launch_views_jitter(rgb_u8, flow_u8, params, n_frames, jitter, flip, height, width, mean_std6, out_nchw,
+                                   nullptr, 0, 0, 0, scratch, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_plan_stage_views_jitter(vpd_plan_t* p, const unsigned char* rgb_u8, const unsigned char* flow_u8,
+                                           const vpd_aug_params* params, int n_frames, int jitter, int flip, int height,
+                                           int width, const float* mean_std6, float* scratch, void* workspace,
+                                           void* stream) {
+    if (check_jitter_views(rgb_u8, params, n_frames, jitter, height, width, mean_std6, scratch)) return -1;
+    const long views = (long)n_frames * (1 + jitter) * (flip ? 2 : 1);
+    if (views > 65535) return fail("n_frames * views exceeds 65535 views per staging call");
+    if (check_call(p, workspace, (int)views)) return -1;
+    if (height != p->H || width != p->W) return fail("inference views are not resized: the frames must have the plan's size");
+    if ((p->c_in == 5) != (flow_u8 != nullptr)) return fail("flow_u8 must be given exactly when the plan has 5 input channels");
+    if (p->c_in != 3 && p->c_in != 5) return fail("inference views: 3 or 5 input channels");
+    if (n_frames == 0) return 0;
+    char* ws = (char*)workspace;
+    LCHECK(vpd_launch_views_jitter(rgb_u8, flow_u8, params, n_frames, jitter, flip, height, width, mean_std6, nullptr,
+                                   reinterpret_cast<bf16_t*>(ws + p->xin_off), p->xHp, p->xWp, 3, scratch,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
 extern "C" int vpd_adamw_step(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
                               double lr, double beta1, double beta2, double eps, double weight_decay, int step,
                               void* stream) {

@@ -282,14 +282,16 @@ class FrameDataset(torch.utils.data.Dataset):
     def __init__(self, tasks, img_dim, rgb_mean_std, augment_jitter=0, augment_flip=False, flow_img_name=None, raw_u8=False):
         """raw_u8: items are {'video', 'frame', 'rgb_u8': u8[H,W,3], 'flow_u8': u8[H,W,2]} -- the decoded PNGs as stored,
         82 KB per frame instead of 655 KB of fp32 views; vpd_amd.apply.embed_dataset builds the views [orig, flip] on the
-        device (normalise, flow decode, h-flip with x-flow negation).  Jittered views need the host path (ColorJitter on
-        the NORMALISED image, Appendix B.8)."""
+        device (normalise, flow decode, h-flip with x-flow negation).  Raw items carry no views at all, so a raw dataset is
+        built with augment_jitter=0 and the jitter count goes to embed_dataset(..., jitter=J), which builds the jittered
+        views on the device too (ColorJitter on the NORMALISED image, Appendix B.8); augment_jitter > 0 here is an error."""
         self.jitter_count = int(augment_jitter or 0)
         self.tasks, self.img_dim, self.rgb_mean_std = tasks, img_dim, rgb_mean_std
         self.flip, self.flow_img_name = augment_flip, flow_img_name
         self.raw_u8 = bool(raw_u8)
         if self.raw_u8 and self.jitter_count:
-            raise ValueError('raw_u8 items carry no jittered views: use the fp32 path with --jitter')
+            raise ValueError('raw_u8 items carry no views: build the raw dataset with augment_jitter=0 and pass the count to '
+                             'embed_dataset(..., jitter=J)')
 
     def __len__(self):
         return len(self.tasks)

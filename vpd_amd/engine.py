@@ -320,6 +320,19 @@ class StudentEngine:
                                          _ptr(pl.workspace), self._stream()), "vpd_plan_stage_views")
         return pl
 
+    def stage_views_jitter(self, rgb_u8, flow_u8, params_dev, jitter, flip, mean_std6, scratch):
+        """Jittered inference views [frame, J x jitter(frame), J x jitter(flip), flip] of decoded u8 frames straight into the
+        EVAL plan's stem staging buffer (vpd_plan_stage_views_jitter; params_dev: device rows of vpd_aug_params, frame-major
+        in view order)."""
+        n, h, w, _ = rgb_u8.shape
+        k = (1 + jitter) * (2 if flip else 1)
+        pl = self.plan(h, w, n * k, False, False)
+        ms = (C.c_float * 6)(*mean_std6)
+        self.check(self.L.vpd_plan_stage_views_jitter(pl.handle, _ptr(rgb_u8), _ptr(flow_u8), _ptr(params_dev), n, jitter,
+                                                      1 if flip else 0, h, w, ms, _ptr(scratch), _ptr(pl.workspace),
+                                                      self._stream()), "vpd_plan_stage_views_jitter")
+        return pl
+
     def forward_train(self, x, target=None, motion=False, accumulate_loss=True, staged=None):
         if staged is not None:      # (n, img_dim): the batch is already in the staging buffer (stage_crops)
             n, h = staged
