@@ -8,6 +8,67 @@
 #include "kernels.h"
 
 // ---------------------------------------------------------------------------
+// Steps shared by the kernels below.  All forced inline: a kernel that uses them compiles to what the written-out lines did
+// (fp contraction included: the helpers add no rounding and no reassociation).
+// ---------------------------------------------------------------------------
+// eight consecutive per-channel floats (16-byte aligned) as two float4 loads
+static __device__ __forceinline__ void ld8(float (&dst)[8], const float* src) {
+    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
+    *reinterpret_cast<float4*>(dst + 4) = *reinterpret_cast<const float4*>(src + 4);
+}
+// pixel m of a dense [N][H][W] map -> (image, row, column), and its offset (channel c) in a [N][Hp][Wp][C] tensor with a border
+struct Px { int b, y, x; };
+static __device__ __forceinline__ Px px_decode(int m, int HW, int W) {
+    Px q;
+    q.b = m / HW;
+    const int r = m - q.b * HW;
+    q.y = r / W;
+    q.x = r - q.y * W;
+    return q;
+}
+static __device__ __forceinline__ size_t px_padded(const Px& q, int Hp, int Wp, int pad, int C, int c) {
+    return ((size_t)(q.b * Hp + q.y + pad) * Wp + q.x + pad) * C + c;
+}
+// the ReLU mask on g = dy, in its three forms: the stored post-ReLU activation, scale * z + shift recomputed, one bit per element
+static __device__ __forceinline__ void mask_act(float (&g)[8], const float (&a)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) g[j] = a[j] > 0.f ? g[j] : 0.f;
+}
+static __device__ __forceinline__ void mask_affine(float (&g)[8], const float (&z)[8], const float (&msc)[8], const float (&msh)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) g[j] = (z[j] * msc[j] + msh[j]) > 0.f ? g[j] : 0.f;
+}
+static __device__ __forceinline__ void mask_bits8(float (&g)[8], unsigned bits) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) g[j] = ((bits >> j) & 1u) ? g[j] : 0.f;
+}
+// dz = c1 * (g - c2 - xhat * c3), c1 = gamma * rstd, c2 = mean(g), c3 = mean(g * xhat)
+static __device__ __forceinline__ void bn_dz(float (&o)[8], const float (&g)[8], const float (&z)[8], const float (&mu)[8],
+                                             const float (&rs)[8], const float (&c1)[8], const float (&c2)[8], const float (&c3)[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = c1[j] * (g[j] - c2[j] - (z[j] - mu[j]) * rs[j] * c3[j]);
+}
+// Tail of a 256-thread reduction block whose thread t holds the partial sums (a1 = sum g, a2 = sum g * xhat) of channel group
+// t % cv over pixel group t / cv: per channel, the pixel groups are summed in a fixed order and the two totals added to the
+// block's accumulator row of `partials` [VPD_STAT_ROWS][2][C].
+static __device__ __forceinline__ void block_sums_to_rows(const float (&a1)[8], const float (&a2)[8], double* partials, int C) {
+    __shared__ float sh[256][17];
+    const int cv = C >> 3, ppi = 256 / cv;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { sh[threadIdx.x][j] = a1[j]; sh[threadIdx.x][8 + j] = a2[j]; }
+    __syncthreads();
+    // thread t < C sums channel t (c8 = t>>3, j = t&7) over the pixel groups, for both sums
+    for (int t = threadIdx.x; t < 2 * C; t += 256) {
+        const int which = t / C;
+        const int ch = t - which * C;
+        const int q8 = ch >> 3, j = ch & 7;
+        float tot = 0.f;
+        for (int g = 0; g < ppi; ++g) tot += sh[g * cv + q8][which * 8 + j];
+        atomicAdd(&partials[((size_t)(blockIdx.x & (VPD_STAT_ROWS - 1)) * 2 + which) * C + ch], (double)tot);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // finalize of forward statistics: partials [T][2][C] -> mean, rstd, scale,
 // shift; running-stat update (momentum, unbiased var) as nn.BatchNorm2d.
 // ---------------------------------------------------------------------------
@@ -92,31 +153,23 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnApplyParams p) {
     for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
         const int m = (int)(it / cv);
         const int c = (int)(it - (long)m * cv) << 3;
-        const int b = m / HW;
-        const int r = m - b * HW;
-        const int y = r / p.W;
-        const int x = r - y * p.W;
+        const Px q = px_decode(m, HW, p.W);
         float v[8], sc[8], sh[8];
         unpack8(*reinterpret_cast<const uint4*>(p.z + (size_t)m * p.C + c), v);
-        *reinterpret_cast<float4*>(sc) = *reinterpret_cast<const float4*>(p.scale + c);
-        *reinterpret_cast<float4*>(sc + 4) = *reinterpret_cast<const float4*>(p.scale + c + 4);
-        *reinterpret_cast<float4*>(sh) = *reinterpret_cast<const float4*>(p.shift + c);
-        *reinterpret_cast<float4*>(sh + 4) = *reinterpret_cast<const float4*>(p.shift + c + 4);
+        ld8(sc, p.scale + c);
+        ld8(sh, p.shift + c);
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sh[j];
         if (p.res_kind == 1) {
             float rr[8];
-            const size_t ro = ((size_t)(b * p.rHp + y + p.rpad) * p.rWp + x + p.rpad) * p.C + c;
-            unpack8(*reinterpret_cast<const uint4*>(p.res + ro), rr);
+            unpack8(*reinterpret_cast<const uint4*>(p.res + px_padded(q, p.rHp, p.rWp, p.rpad, p.C, c)), rr);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += rr[j];
         } else if (p.res_kind == 2) {
             float rr[8];
             unpack8(*reinterpret_cast<const uint4*>(p.res + (size_t)m * p.C + c), rr);
-            *reinterpret_cast<float4*>(sc) = *reinterpret_cast<const float4*>(p.rscale + c);
-            *reinterpret_cast<float4*>(sc + 4) = *reinterpret_cast<const float4*>(p.rscale + c + 4);
-            *reinterpret_cast<float4*>(sh) = *reinterpret_cast<const float4*>(p.rshift + c);
-            *reinterpret_cast<float4*>(sh + 4) = *reinterpret_cast<const float4*>(p.rshift + c + 4);
+            ld8(sc, p.rscale + c);
+            ld8(sh, p.rshift + c);
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] += rr[j] * sc[j] + sh[j];
         }
@@ -124,8 +177,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const BnApplyParams p) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
         }
-        const size_t oo = ((size_t)(b * p.oHp + y + p.opad) * p.oWp + x + p.opad) * p.C + c;
-        vpd_store16<VPD_CP_BNF>(p.out + oo, pack8(v));
+        vpd_store16<VPD_CP_BNF>(p.out + px_padded(q, p.oHp, p.oWp, p.opad, p.C, c), pack8(v));
     }
 }
 
@@ -160,10 +212,8 @@ __global__ __launch_bounds__(256) void stem_pool_kernel(const StemPoolParams p) 
         const int b = (int)(t / Ho);
         float sc[8], sh[8], best[8];
         int bi[8];
-        *reinterpret_cast<float4*>(sc) = *reinterpret_cast<const float4*>(p.scale + c);
-        *reinterpret_cast<float4*>(sc + 4) = *reinterpret_cast<const float4*>(p.scale + c + 4);
-        *reinterpret_cast<float4*>(sh) = *reinterpret_cast<const float4*>(p.shift + c);
-        *reinterpret_cast<float4*>(sh + 4) = *reinterpret_cast<const float4*>(p.shift + c + 4);
+        ld8(sc, p.scale + c);
+        ld8(sh, p.shift + c);
 #pragma unroll
         for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; bi[j] = 0; }
         for (int r = 0; r < 3; ++r) {
@@ -202,10 +252,8 @@ __global__ __launch_bounds__(256) void stem_pool_pair_kernel(const StemPoolParam
     const long total = (long)p.N * Ho * Wk * cv;
     const int c = (int)(threadIdx.x % cv) << 3;            // blockDim is a multiple of cv: fixed per thread
     float sc[8], sh[8];
-    *reinterpret_cast<float4*>(sc) = *reinterpret_cast<const float4*>(p.scale + c);
-    *reinterpret_cast<float4*>(sc + 4) = *reinterpret_cast<const float4*>(p.scale + c + 4);
-    *reinterpret_cast<float4*>(sh) = *reinterpret_cast<const float4*>(p.shift + c);
-    *reinterpret_cast<float4*>(sh + 4) = *reinterpret_cast<const float4*>(p.shift + c + 4);
+    ld8(sc, p.scale + c);
+    ld8(sh, p.shift + c);
     // (item -> (image, row, output pair): 64-bit divisions cost more than the pooling itself; below 2^21 items the float
     //  reciprocal splits exactly, and cv is a power of two for every ResNet stem)
     const bool fast = total < VPD_FDIV_MAX && (cv & (cv - 1)) == 0;
@@ -299,7 +347,6 @@ hipError_t vpd_launch_stem_pool(const StemPoolParams& p, hipStream_t s) {
 // ---------------------------------------------------------------------------
 template <int MASK>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p) {
-    __shared__ float sh[256][17];
     const int cv = p.C >> 3;
     const int ppi = 256 / cv;                       // pixels per block iteration
     const int c8 = threadIdx.x % cv;
@@ -307,18 +354,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p)
     const int c = c8 << 3;
     const int HW = p.H * p.W;
     float mu[8], rs[8], a1[8], a2[8], msc[8], msh[8];
-    *reinterpret_cast<float4*>(mu) = *reinterpret_cast<const float4*>(p.mean + c);
-    *reinterpret_cast<float4*>(mu + 4) = *reinterpret_cast<const float4*>(p.mean + c + 4);
-    *reinterpret_cast<float4*>(rs) = *reinterpret_cast<const float4*>(p.rstd + c);
-    *reinterpret_cast<float4*>(rs + 4) = *reinterpret_cast<const float4*>(p.rstd + c + 4);
+    ld8(mu, p.mean + c);
+    ld8(rs, p.rstd + c);
 #pragma unroll
     for (int j = 0; j < 8; ++j) { msc[j] = 0.f; msh[j] = 1.f; }
-    if (MASK == 2) {
-        *reinterpret_cast<float4*>(msc) = *reinterpret_cast<const float4*>(p.mscale + c);
-        *reinterpret_cast<float4*>(msc + 4) = *reinterpret_cast<const float4*>(p.mscale + c + 4);
-        *reinterpret_cast<float4*>(msh) = *reinterpret_cast<const float4*>(p.mshift + c);
-        *reinterpret_cast<float4*>(msh + 4) = *reinterpret_cast<const float4*>(p.mshift + c + 4);
-    }
+    if (MASK == 2) { ld8(msc, p.mscale + c); ld8(msh, p.mshift + c); }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { a1[j] = 0.f; a2[j] = 0.f; }
     const int mbeg = blockIdx.x * p.ppb;
@@ -330,18 +370,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p)
             unpack8(*reinterpret_cast<const uint4*>(p.dy + (size_t)m * p.C + c), g);
             unpack8(*reinterpret_cast<const uint4*>(p.z + (size_t)m * p.C + c), z);
             if (MASK == 1) {
-                const int b = m / HW;
-                const int r = m - b * HW;
-                const int y = r / p.W;
-                const int x = r - y * p.W;
                 float a[8];
                 unpack8(*reinterpret_cast<const uint4*>(
-                            p.act + ((size_t)(b * p.aHp + y + p.apad) * p.aWp + x + p.apad) * p.C + c), a);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) g[j] = a[j] > 0.f ? g[j] : 0.f;
+                            p.act + px_padded(px_decode(m, HW, p.W), p.aHp, p.aWp, p.apad, p.C, c)), a);
+                mask_act(g, a);
             } else if (MASK == 2) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) g[j] = (z[j] * msc[j] + msh[j]) > 0.f ? g[j] : 0.f;
+                mask_affine(g, z, msc, msh);
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -349,18 +383,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p)
                 a2[j] += g[j] * ((z[j] - mu[j]) * rs[j]);
             }
         }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sh[threadIdx.x][j] = a1[j]; sh[threadIdx.x][8 + j] = a2[j]; }
-    __syncthreads();
-    // thread t < C sums channel t (c8 = t>>3, j = t&7) over the pixel groups, for both sums
-    for (int t = threadIdx.x; t < 2 * p.C; t += 256) {
-        const int which = t / p.C;
-        const int ch = t - which * p.C;
-        const int q8 = ch >> 3, j = ch & 7;
-        float tot = 0.f;
-        for (int g = 0; g < ppi; ++g) tot += sh[g * cv + q8][which * 8 + j];
-        atomicAdd(&p.partials[((size_t)(blockIdx.x & (VPD_STAT_ROWS - 1)) * 2 + which) * p.C + ch], (double)tot);
-    }
+    block_sums_to_rows(a1, a2, p.partials, p.C);
 }
 
 // pass 1b: partials -> dgamma, dbeta (fp32 grads) and the apply coefficients
@@ -388,39 +411,26 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const BnBwdParams p) 
     for (long it = (long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long)gridDim.x * blockDim.x) {
         const int m = (int)(it / cv);
         const int c = (int)(it - (long)m * cv) << 3;
-        const int b = m / HW;
-        const int r = m - b * HW;
-        const int y = r / p.W;
-        const int x = r - y * p.W;
+        const Px q = px_decode(m, HW, p.W);
         float g[8], z[8], mu[8], rs[8], c1[8], c2[8], c3[8];
         unpack8(*reinterpret_cast<const uint4*>(p.dy + (size_t)m * p.C + c), g);
         unpack8(*reinterpret_cast<const uint4*>(p.z + (size_t)m * p.C + c), z);
         if (MASK == 1) {
             float a[8];
-            unpack8(*reinterpret_cast<const uint4*>(
-                        p.act + ((size_t)(b * p.aHp + y + p.apad) * p.aWp + x + p.apad) * p.C + c), a);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = a[j] > 0.f ? g[j] : 0.f;
+            unpack8(*reinterpret_cast<const uint4*>(p.act + px_padded(q, p.aHp, p.aWp, p.apad, p.C, c)), a);
+            mask_act(g, a);
             if (WRITE_G) *reinterpret_cast<uint4*>(p.dy_rw + (size_t)m * p.C + c) = pack8(g);
         } else if (MASK == 2) {
             float msc[8], msh[8];
-            *reinterpret_cast<float4*>(msc) = *reinterpret_cast<const float4*>(p.mscale + c);
-            *reinterpret_cast<float4*>(msc + 4) = *reinterpret_cast<const float4*>(p.mscale + c + 4);
-            *reinterpret_cast<float4*>(msh) = *reinterpret_cast<const float4*>(p.mshift + c);
-            *reinterpret_cast<float4*>(msh + 4) = *reinterpret_cast<const float4*>(p.mshift + c + 4);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = (z[j] * msc[j] + msh[j]) > 0.f ? g[j] : 0.f;
+            ld8(msc, p.mscale + c);
+            ld8(msh, p.mshift + c);
+            mask_affine(g, z, msc, msh);
         }
-#define LD8(dst, src) \
-        *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src); \
-        *reinterpret_cast<float4*>(dst + 4) = *reinterpret_cast<const float4*>(src + 4);
-        LD8(mu, p.mean + c) LD8(rs, p.rstd + c) LD8(c1, p.coef + c) LD8(c2, p.coef + p.C + c) LD8(c3, p.coef + 2 * p.C + c)
-#undef LD8
+        ld8(mu, p.mean + c); ld8(rs, p.rstd + c);
+        ld8(c1, p.coef + c); ld8(c2, p.coef + p.C + c); ld8(c3, p.coef + 2 * p.C + c);
         float o[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = c1[j] * (g[j] - c2[j] - (z[j] - mu[j]) * rs[j] * c3[j]);
-        const size_t oo = ((size_t)(b * p.dzHp + y + p.dzpad) * p.dzWp + x + p.dzpad) * p.C + c;
-        vpd_store16<VPD_CP_BNB>(p.dz + oo, pack8(o));
+        bn_dz(o, g, z, mu, rs, c1, c2, c3);
+        vpd_store16<VPD_CP_BNB>(p.dz + px_padded(q, p.dzHp, p.dzWp, p.dzpad, p.C, c), pack8(o));
     }
 }
 
@@ -465,7 +475,6 @@ hipError_t vpd_launch_bn_bwd(const BnBwdParams& p0, float count, const float* ga
 // backward partial sums in one pass.  d_pool is dense [N][Ho][Wo][C].
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const StemPoolBwdParams p) {
-    __shared__ float sh[256][17];
     const int cv = p.C >> 3;
     const int ppi = 256 / cv;
     const int c8 = threadIdx.x % cv;
@@ -473,15 +482,11 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const StemPoolBwdPar
     const int c = c8 << 3;
     const int HWz = p.Hz * p.Wz;
     float mu[8], rs[8], sc[8], shf[8], a1[8], a2[8];
-#define LD8(dst, src) \
-    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src); \
-    *reinterpret_cast<float4*>(dst + 4) = *reinterpret_cast<const float4*>(src + 4);
-    LD8(mu, p.mean + c) LD8(rs, p.rstd + c) LD8(sc, p.scale + c) LD8(shf, p.shift + c)
+    ld8(mu, p.mean + c); ld8(rs, p.rstd + c); ld8(sc, p.scale + c); ld8(shf, p.shift + c);
     float c1[8], c2[8], c3[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { c1[j] = 0.f; c2[j] = 0.f; c3[j] = 0.f; }
-    if (p.pass == 2) { LD8(c1, p.coef + c) LD8(c2, p.coef + p.C + c) LD8(c3, p.coef + 2 * p.C + c) }
-#undef LD8
+    if (p.pass == 2) { ld8(c1, p.coef + c); ld8(c2, p.coef + p.C + c); ld8(c3, p.coef + 2 * p.C + c); }
 #pragma unroll
     for (int j = 0; j < 8; ++j) { a1[j] = 0.f; a2[j] = 0.f; }
     const int mbeg = blockIdx.x * p.ppb;
@@ -489,10 +494,8 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const StemPoolBwdPar
     mend = mend < p.M ? mend : p.M;
     if (pl < ppi)
         for (int m = mbeg + pl; m < mend; m += ppi) {
-            const int b = m / HWz;
-            const int r = m - b * HWz;
-            const int y = r / p.Wz;
-            const int x = r - y * p.Wz;
+            const Px q = px_decode(m, HWz, p.Wz);
+            const int b = q.b, y = q.y, x = q.x;
             float z[8], g[8], o[8];
             unpack8(*reinterpret_cast<const uint4*>(p.z + (size_t)m * p.C + c), z);
 #pragma unroll
@@ -518,29 +521,17 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const StemPoolBwdPar
                     }
                 }
             }
+            mask_affine(g, z, sc, shf);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float a = z[j] * sc[j] + shf[j];
-                g[j] = a > 0.f ? g[j] : 0.f;
-                const float xh = (z[j] - mu[j]) * rs[j];
                 a1[j] += g[j];
-                a2[j] += g[j] * xh;
-                o[j] = c1[j] * (g[j] - c2[j] - xh * c3[j]);      // pass 2 only (coefficients are 0 in pass 1)
+                a2[j] += g[j] * ((z[j] - mu[j]) * rs[j]);
             }
+            bn_dz(o, g, z, mu, rs, c1, c2, c3);                  // pass 2 only (coefficients are 0 in pass 1)
             if (p.pass == 2) *reinterpret_cast<uint4*>(p.dz + (size_t)m * p.C + c) = pack8(o);
         }
     if (p.pass == 2) return;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sh[threadIdx.x][j] = a1[j]; sh[threadIdx.x][8 + j] = a2[j]; }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 2 * p.C; t += 256) {
-        const int which = t / p.C;
-        const int ch = t - which * p.C;
-        const int q8 = ch >> 3, j = ch & 7;
-        float tot = 0.f;
-        for (int gI = 0; gI < ppi; ++gI) tot += sh[gI * cv + q8][which * 8 + j];
-        atomicAdd(&p.partials[((size_t)(blockIdx.x & (VPD_STAT_ROWS - 1)) * 2 + which) * p.C + ch], (double)tot);
-    }
+    block_sums_to_rows(a1, a2, p.partials, p.C);
 }
 
 // Pass 2 of the stem backward over 2x2 blocks of z pixels (even Hz, Wz; 3x3 stride-2 pad-1 pooling, Ho = Hz/2):
@@ -554,12 +545,8 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const StemPoolB
     const int per = 256 / cv;                       // items per block iteration
     const int Hk = p.Hz >> 1, Wk = p.Wz >> 1;
     float mu[8], rs[8], sc[8], shf[8], c1[8], c2[8], c3[8];
-#define LD8(dst, src) \
-    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src); \
-    *reinterpret_cast<float4*>(dst + 4) = *reinterpret_cast<const float4*>(src + 4);
-    LD8(mu, p.mean + c) LD8(rs, p.rstd + c) LD8(sc, p.scale + c) LD8(shf, p.shift + c)
-    LD8(c1, p.coef + c) LD8(c2, p.coef + p.C + c) LD8(c3, p.coef + 2 * p.C + c)
-#undef LD8
+    ld8(mu, p.mean + c); ld8(rs, p.rstd + c); ld8(sc, p.scale + c); ld8(shf, p.shift + c);
+    ld8(c1, p.coef + c); ld8(c2, p.coef + p.C + c); ld8(c3, p.coef + 2 * p.C + c);
     // item -> (image, quad row, quad column): two 64-bit divisions + two remainders were ~480 of an item's ~1,100 vector instructions
     // (the launch is ALU-bound: 60 us for 318 MB); item counts below 2^21 split exactly with the float reciprocal (vpd_fdiv)
     const bool fast = items < VPD_FDIV_MAX;
@@ -643,7 +630,6 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const StemPoolB
 // (260 MB, 90 us).  a is the stored bf16 activation: xhat differs from the z-based value by its rounding (2^-9
 // relative, zero mean), far below the bf16 noise of the gradients themselves.
 __global__ __launch_bounds__(256) void stem_pool_bwd_sums_kernel(const StemPoolBwdParams p) {
-    __shared__ float sh[256][17];
     const int cv = p.C >> 3;
     const int ppi = 256 / cv;
     const int c8 = threadIdx.x % cv;
@@ -681,17 +667,7 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_sums_kernel(const StemPoolB
                 a2[j] += g * ((a[j] - be[j]) * ig[j]);
             }
         }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { sh[threadIdx.x][j] = a1[j]; sh[threadIdx.x][8 + j] = a2[j]; }
-    __syncthreads();
-    for (int t = threadIdx.x; t < 2 * p.C; t += 256) {
-        const int which = t / p.C;
-        const int ch = t - which * p.C;
-        const int q8 = ch >> 3, j = ch & 7;
-        float tot = 0.f;
-        for (int gI = 0; gI < ppi; ++gI) tot += sh[gI * cv + q8][which * 8 + j];
-        atomicAdd(&p.partials[((size_t)(blockIdx.x & (VPD_STAT_ROWS - 1)) * 2 + which) * p.C + ch], (double)tot);
-    }
+    block_sums_to_rows(a1, a2, p.partials, p.C);
 }
 
 hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p0, float count, const float* gamma, float* dgamma,
@@ -940,36 +916,47 @@ hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f0,
     return hipGetLastError();
 }
 
+// NB BatchNorms fed with the same g: [0] is the one BnBwdParams describes (its z / mean / rstd / dz are copied here by the launchers)
+template <int NB>
 struct BnFusedBwdArgs {
-    double* rows;                              // this BatchNorm's accumulator rows [VPD_FUSED_ROWS][2][C], zeroed
     GridSync* sync;                            // zeroed
     unsigned* err;                             // sticky time-out counter
-    const float* gamma; float* dgamma; float* dbeta;
     float count;
-    int keep_g, keep_z, iters;                 // LDS residency of g / z across the barrier; pixel iterations per thread
+    int keep_g, keep_z[NB], iters;             // LDS residency of g / each z across the barrier; pixel iterations per thread
+    double* rows[NB];                          // each BatchNorm's accumulator rows [VPD_FUSED_ROWS][2][C], zeroed: [0] = (sum g, sum g xhat0), [1] = (-, sum g xhat1)
+    const float* gamma[NB]; float* dgamma[NB]; float* dbeta[NB];
+    const bf16_t* z[NB]; const float* mean[NB]; const float* rstd[NB];
+    bf16_t* dz[NB];                            // all in the padded geometry of p.dz
 };
 
-template <int MASK, int WRITE_G>
-__global__ __launch_bounds__(1024) void bn_bwd_fused_kernel(const BnBwdParams p, const BnFusedBwdArgs f) {
+// The body of bn_bwd_fused_kernel<MASK, WRITE_G> (NB = 1) and of bn_bwd_fused2_kernel (<1, 0, 2>): K = 1 + NB sums per channel
+// (sum g is shared), one grid barrier, NB dz outputs.
+template <int MASK, int WRITE_G, int NB>
+static __device__ __forceinline__ void bn_bwd_fused_body(const BnBwdParams& p, const BnFusedBwdArgs<NB>& f) {
     extern __shared__ uint4 smem4[];
-    const int T = 1024;
+    constexpr int T = 1024, K = 1 + NB;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = p.C, cv = C >> 3;
     const int ppi = T / cv;
     const int c8 = tid % cv, pl = tid / cv, c = c8 << 3;
     const int HW = p.H * p.W;
     uint4* sG = smem4;
-    uint4* sZ = sG + (f.keep_g ? (size_t)f.iters * T : 0);
-    float* red = reinterpret_cast<float*>(sZ + (f.keep_z ? (size_t)f.iters * T : 0));      // [16 waves][2][C], then coef [2][C]
-
-    float mu[8], rs[8], msc[8], msh[8], a1[8], a2[8];
-#define LD8(dst, src) \
-    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src); \
-    *reinterpret_cast<float4*>(dst + 4) = *reinterpret_cast<const float4*>(src + 4);
-    LD8(mu, p.mean + c) LD8(rs, p.rstd + c)
+    uint4* sZ[NB];
+    uint4* snext = sG + (f.keep_g ? (size_t)f.iters * T : 0);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { msc[j] = 0.f; msh[j] = 1.f; a1[j] = 0.f; a2[j] = 0.f; }
-    if (MASK == 2) { LD8(msc, p.mscale + c) LD8(msh, p.mshift + c) }
+    for (int n = 0; n < NB; ++n) { sZ[n] = snext; snext += f.keep_z[n] ? (size_t)f.iters * T : 0; }
+    float* red = reinterpret_cast<float*>(snext);           // [16 waves][K][C], then coef [K][C]
+
+    float mu[NB][8], rs[NB][8], msc[8], msh[8], acc[K][8];  // acc[0] = sum g, acc[1 + n] = sum g * xhat of BatchNorm n
+#pragma unroll
+    for (int n = 0; n < NB; ++n) { ld8(mu[n], f.mean[n] + c); ld8(rs[n], f.rstd[n] + c); }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { msc[j] = 0.f; msh[j] = 1.f; }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
+    if (MASK == 2) { ld8(msc, p.mscale + c); ld8(msh, p.mshift + c); }
 
     const int mbeg = blockIdx.x * p.ppb;
     int mend = mbeg + p.ppb;
@@ -977,10 +964,12 @@ __global__ __launch_bounds__(1024) void bn_bwd_fused_kernel(const BnBwdParams p,
     // ---- phase 1: g = dy * mask, per-thread partial sums; g (and z) parked in LDS ----
     int it = 0;
     for (int m = mbeg + pl; m < mend; m += ppi, ++it) {
-        float g[8], z[8];
-        const uint4 zr = *reinterpret_cast<const uint4*>(p.z + (size_t)m * C + c);
+        float g[8], z[NB][8];
+        uint4 zr[NB];
+#pragma unroll
+        for (int n = 0; n < NB; ++n) zr[n] = *reinterpret_cast<const uint4*>(f.z[n] + (size_t)m * C + c);
         uint4 gr;
-        if (MASK == 3 && !WRITE_G && p.dy_pooled) {         // dy = gradient of the global average pool, produced here
+        if (NB == 1 && MASK == 3 && !WRITE_G && p.dy_pooled) {     // dy = gradient of the global average pool, produced here
             const float* d = p.dy_pooled + (size_t)(m / HW) * C + c;
             const float4 d0 = *reinterpret_cast<const float4*>(d), d1 = *reinterpret_cast<const float4*>(d + 4);
             const float dv[8] = {d0.x * p.dy_pool_scale, d0.y * p.dy_pool_scale, d0.z * p.dy_pool_scale, d0.w * p.dy_pool_scale,
@@ -991,116 +980,133 @@ __global__ __launch_bounds__(1024) void bn_bwd_fused_kernel(const BnBwdParams p,
             gr = *reinterpret_cast<const uint4*>(p.dy + (size_t)m * C + c);
         }
         unpack8(gr, g);
-        unpack8(zr, z);
+#pragma unroll
+        for (int n = 0; n < NB; ++n) unpack8(zr[n], z[n]);
         if (MASK == 1) {
-            const int b = m / HW;
-            const int r = m - b * HW;
-            const int y = r / p.W;
-            const int x = r - y * p.W;
             float a[8];
-            unpack8(*reinterpret_cast<const uint4*>(p.act + ((size_t)(b * p.aHp + y + p.apad) * p.aWp + x + p.apad) * C + c), a);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = a[j] > 0.f ? g[j] : 0.f;
+            unpack8(*reinterpret_cast<const uint4*>(p.act + px_padded(px_decode(m, HW, p.W), p.aHp, p.aWp, p.apad, C, c)), a);
+            mask_act(g, a);
             gr = pack8(g);                                  // exact: g is dy or 0
-            if (WRITE_G) *reinterpret_cast<uint4*>(p.dy_rw + (size_t)m * C + c) = gr;
+            // WRITE_G: the next launch reads g in dy.  The pair kernel needs g in phase 2 only: parked in dy itself when it is
+            // not resident (this thread re-reads it)
+            if (WRITE_G || (NB == 2 && !f.keep_g)) *reinterpret_cast<uint4*>(p.dy_rw + (size_t)m * C + c) = gr;
         } else if (MASK == 2) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = (z[j] * msc[j] + msh[j]) > 0.f ? g[j] : 0.f;
+            mask_affine(g, z[0], msc, msh);
             gr = pack8(g);
         } else if (MASK == 3) {
-            const unsigned bits = p.mask_bits[(size_t)m * cv + c8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] = ((bits >> j) & 1u) ? g[j] : 0.f;
+            mask_bits8(g, p.mask_bits[(size_t)m * cv + c8]);
             gr = pack8(g);
         }
         if (f.keep_g) sG[(size_t)it * T + tid] = gr;
-        if (f.keep_z) sZ[(size_t)it * T + tid] = zr;
+#pragma unroll
+        for (int n = 0; n < NB; ++n)
+            if (f.keep_z[n]) sZ[n][(size_t)it * T + tid] = zr[n];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            a1[j] += g[j];
-            a2[j] += g[j] * ((z[j] - mu[j]) * rs[j]);
+            acc[0][j] += g[j];
+#pragma unroll
+            for (int n = 0; n < NB; ++n) acc[1 + n][j] += g[j] * ((z[n][j] - mu[n][j]) * rs[n][j]);
         }
     }
     // ---- block reduction in a fixed order: lanes of a wave that share a channel group, then the 16 waves ----
     if (cv < 64) {
         for (int o = cv; o < 64; o <<= 1) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { a1[j] += __shfl_xor(a1[j], o, 64); a2[j] += __shfl_xor(a2[j], o, 64); }
+            for (int j = 0; j < 8; ++j) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) acc[k][j] += __shfl_xor(acc[k][j], o, 64);
+            }
         }
     }
     // waves that hold the same channel groups: all 16 when cv <= 64, every (cv/64)-th otherwise (waves j, j + wstep, ...: their
-    // sums go to rows 0, 1, ... of `red`, [16 / wstep][2][C] floats -- 64 KB at most, also for 2,048 channels)
+    // sums go to rows 0, 1, ... of `red`, [16 / wstep][K][C] floats -- 64 KB at most for K = 2, also for 2,048 channels)
     const int wstep = cv <= 64 ? 1 : cv / 64;
     if (lane < cv) {                                        // (cv >= 64: every lane; its channel group is c8)
         const int rrow = wave / wstep;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            red[(size_t)(rrow * 2 + 0) * C + c + j] = a1[j];
-            red[(size_t)(rrow * 2 + 1) * C + c + j] = a2[j];
+#pragma unroll
+            for (int k = 0; k < K; ++k) red[(size_t)(rrow * K + k) * C + c + j] = acc[k][j];
         }
     }
     __syncthreads();
-    for (int t = tid; t < 2 * C; t += T) {
+    // sums 0 and 1 -> BatchNorm 0's rows, slots 0 and 1; sum 2 -> BatchNorm 1's rows, slot 1 (its slot 0 stays unwritten: its dbeta
+    // is BatchNorm 0's sum g).  ([NB - 1] is [1] there, and keeps the index inside the arrays where NB = 1 never takes it)
+    for (int t = tid; t < K * C; t += T) {
         const int which = t / C;
         const int ch = t - which * C;
         float tot = 0.f;
-        for (int k = 0; k < 16 / wstep; ++k) tot += red[(size_t)(k * 2 + which) * C + ch];
-        atomicAdd(&f.rows[((size_t)(blockIdx.x & (VPD_FUSED_ROWS - 1)) * 2 + which) * C + ch], (double)tot);
+        for (int k = 0; k < 16 / wstep; ++k) tot += red[(size_t)(k * K + which) * C + ch];
+        const bool second = NB == 2 && which == 2;
+        double* rows = second ? f.rows[NB - 1] : f.rows[0];
+        const int slot = second ? 1 : which;
+        atomicAdd(&rows[((size_t)(blockIdx.x & (VPD_FUSED_ROWS - 1)) * 2 + slot) * C + ch], (double)tot);
     }
     vpd_grid_barrier(f.sync, false, f.err, blockIdx.x, gridDim.x);
-    // ---- finalize: every block sums the rows of all channels (2*C*VPD_FUSED_ROWS doubles) ----
-    for (int t = tid; t < 2 * C; t += T) {
+    // ---- finalize: every block sums the rows of all channels (K*C*VPD_FUSED_ROWS doubles) ----
+    for (int t = tid; t < K * C; t += T) {
         const int which = t / C;
         const int ch = t - which * C;
+        const bool second = NB == 2 && which == 2;
+        const double* rows = second ? f.rows[NB - 1] : f.rows[0];
+        const int slot = second ? 1 : which;
         double s = 0.0;
 #pragma unroll
         for (int r = 0; r < VPD_FUSED_ROWS; ++r)
-            s += __hip_atomic_load(&f.rows[((size_t)r * 2 + which) * C + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s += __hip_atomic_load(&rows[((size_t)r * 2 + slot) * C + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         red[t] = (float)(s / (double)f.count);
         if (blockIdx.x == 0) {
-            if (which == 0) f.dbeta[ch] = (float)s;
-            else f.dgamma[ch] = (float)s;
+            if (which == 0) {
+#pragma unroll
+                for (int n = 0; n < NB; ++n) f.dbeta[n][ch] = (float)s;
+            } else {
+                f.dgamma[second ? NB - 1 : 0][ch] = (float)s;
+            }
         }
     }
     __syncthreads();
-    float c1[8], c2[8], c3[8];
+    float c1[NB][8], c2[8], c3[NB][8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        c1[j] = f.gamma[c + j] * rs[j];
         c2[j] = red[c + j];
-        c3[j] = red[C + c + j];
+#pragma unroll
+        for (int n = 0; n < NB; ++n) {
+            c1[n][j] = f.gamma[n][c + j] * rs[n][j];
+            c3[n][j] = red[(1 + n) * C + c + j];
+        }
     }
     // ---- phase 2: dz = c1 * (g - c2 - xhat * c3) ----
     it = 0;
     for (int m = mbeg + pl; m < mend; m += ppi, ++it) {
-        float g[8], z[8];
-        const uint4 zr = f.keep_z ? sZ[(size_t)it * T + tid] : *reinterpret_cast<const uint4*>(p.z + (size_t)m * C + c);
-        unpack8(zr, z);
-        if (f.keep_g) {
-            unpack8(sG[(size_t)it * T + tid], g);
-        } else {
-            // not resident: g was written back over dy by this very thread (WRITE_G), or is recomputed from dy and z
-            unpack8(*reinterpret_cast<const uint4*>(p.dy + (size_t)m * C + c), g);
-            if (MASK == 2) {
+        float g[8], z[NB][8];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) g[j] = (z[j] * msc[j] + msh[j]) > 0.f ? g[j] : 0.f;
-            } else if (MASK == 3) {
-                const unsigned bits = p.mask_bits[(size_t)m * cv + c8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) g[j] = ((bits >> j) & 1u) ? g[j] : 0.f;
-            }
+        for (int n = 0; n < NB; ++n)
+            unpack8(f.keep_z[n] ? sZ[n][(size_t)it * T + tid] : *reinterpret_cast<const uint4*>(f.z[n] + (size_t)m * C + c), z[n]);
+        unpack8(f.keep_g ? sG[(size_t)it * T + tid] : *reinterpret_cast<const uint4*>(p.dy + (size_t)m * C + c), g);
+        if (!f.keep_g) {      // not resident: g was written back over dy by this very thread (MASK 1), or is recomputed from dy and z
+            if (MASK == 2) mask_affine(g, z[0], msc, msh);
+            else if (MASK == 3) mask_bits8(g, p.mask_bits[(size_t)m * cv + c8]);
         }
-        const int b = m / HW;
-        const int r = m - b * HW;
-        const int y = r / p.W;
-        const int x = r - y * p.W;
-        float o[8];
+        const Px q = px_decode(m, HW, p.W);
+        float o[NB][8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = c1[j] * (g[j] - c2[j] - (z[j] - mu[j]) * rs[j] * c3[j]);
-        const size_t oo = ((size_t)(b * p.dzHp + y + p.dzpad) * p.dzWp + x + p.dzpad) * C + c;
-        vpd_store16<VPD_CP_BNB>(p.dz + oo, pack8(o));
+        for (int n = 0; n < NB; ++n) bn_dz(o[n], g, z[n], mu[n], rs[n], c1[n], c2, c3[n]);
+        const size_t oo = px_padded(q, p.dzHp, p.dzWp, p.dzpad, C, c);
+#pragma unroll
+        for (int n = 0; n < NB; ++n) vpd_store16<VPD_CP_BNB>(f.dz[n] + oo, pack8(o[n]));
     }
-#undef LD8
+}
+
+template <int MASK, int WRITE_G>
+__global__ __launch_bounds__(1024) void bn_bwd_fused_kernel(const BnBwdParams p, const BnFusedBwdArgs<1> f) {
+    bn_bwd_fused_body<MASK, WRITE_G, 1>(p, f);
+}
+// Two BatchNorm backwards that share their output gradient in one launch: the block-output BatchNorm of a down-sampling
+// BasicBlock (A: conv2's, ReLU mask from the stored block output) and the BatchNorm of its 1x1 branch (B: no ReLU of its
+// own, fed with the same masked gradient g).  One read of dy / act, three sums per channel (sum g shared), one grid
+// barrier, two dz outputs; g itself is not needed afterwards (both paths continue through convolutions).
+__global__ __launch_bounds__(1024) void bn_bwd_fused2_kernel(const BnBwdParams p, const BnFusedBwdArgs<2> f) {
+    bn_bwd_fused_body<1, 0, 2>(p, f);
 }
 
 // BatchNorm backward, finalize + apply only: the data-gradient convolution that produced dy has added sum g and sum g * z
@@ -1211,8 +1217,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_apply_fused_kernel(const BnBwdPar
     }
 }
 
-hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f0, hipStream_t s, const BnFusedBwd* fB,
-                                         const bf16_t* zB, const float* meanB, const float* rstdB, bf16_t* dzB) {
+hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f0, hipStream_t s, const BnBwdSecond* B) {
     if (p.C % 8 || p.C > 4096 || !p.mask_bits) return hipErrorInvalidValue;
     BnBwdApplyArgs f;
     f = BnBwdApplyArgs{};
@@ -1224,156 +1229,14 @@ hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd&
     if (g < 1) g = 1;
     const int xcd_on = vpd_bn_xcd_on();
     f.xcd_r = xcd_on ? vpd_bn_xcd_r(p.xcd_tile_px, p.C, (int)g) : 0;
-    if (fB) {
-        f.rows2 = fB->rows; f.gamma2 = fB->gamma; f.mean2 = meanB; f.rstd2 = rstdB; f.dgamma2 = fB->dgamma; f.dbeta2 = fB->dbeta;
-        f.z2 = zB; f.dz2 = dzB;
+    if (B) {
+        f.rows2 = B->f.rows; f.gamma2 = B->f.gamma; f.mean2 = B->mean; f.rstd2 = B->rstd; f.dgamma2 = B->f.dgamma; f.dbeta2 = B->f.dbeta;
+        f.z2 = B->z; f.dz2 = B->dz;
         hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<true>, dim3((unsigned)g), dim3(1024), (size_t)6 * p.C * sizeof(float), s, p, f);
     } else {
         hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<false>, dim3((unsigned)g), dim3(1024), (size_t)3 * p.C * sizeof(float), s, p, f);
     }
     return hipGetLastError();
-}
-
-// Two BatchNorm backwards that share their output gradient in one launch: the block-output BatchNorm of a down-sampling
-// BasicBlock (A: conv2's, ReLU mask from the stored block output) and the BatchNorm of its 1x1 branch (B: no ReLU of its
-// own, fed with the same masked gradient g).  One read of dy / act, three sums per channel (sum g shared), one grid
-// barrier, two dz outputs; g itself is not needed afterwards (both paths continue through convolutions).
-struct BnFusedBwd2Args {
-    double* rowsA; double* rowsB;              // [VPD_FUSED_ROWS][2][C] each, zeroed: A = (sum g, sum g xhatA), B = (-, sum g xhatB)
-    GridSync* sync; unsigned* err;
-    const bf16_t* zB; const float* meanB; const float* rstdB;
-    const float* gammaA; float* dgammaA; float* dbetaA;
-    const float* gammaB; float* dgammaB; float* dbetaB;
-    bf16_t* dzB;                               // same padded geometry as p.dz
-    float count;
-    int keep_g, keep_zA, keep_zB, iters;
-};
-
-__global__ __launch_bounds__(1024) void bn_bwd_fused2_kernel(const BnBwdParams p, const BnFusedBwd2Args f) {
-    extern __shared__ uint4 smem4[];
-    const int T = 1024;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int C = p.C, cv = C >> 3;
-    const int ppi = T / cv;
-    const int c8 = tid % cv, pl = tid / cv, c = c8 << 3;
-    const int HW = p.H * p.W;
-    uint4* sG = smem4;
-    uint4* sZA = sG + (f.keep_g ? (size_t)f.iters * T : 0);
-    uint4* sZB = sZA + (f.keep_zA ? (size_t)f.iters * T : 0);
-    float* red = reinterpret_cast<float*>(sZB + (f.keep_zB ? (size_t)f.iters * T : 0));      // [16 waves][3][C], then coef [3][C]
-
-    float muA[8], rsA[8], muB[8], rsB[8], a1[8], a2[8], a3[8];
-#define LD8(dst, src) \
-    *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src); \
-    *reinterpret_cast<float4*>(dst + 4) = *reinterpret_cast<const float4*>(src + 4);
-    LD8(muA, p.mean + c) LD8(rsA, p.rstd + c) LD8(muB, f.meanB + c) LD8(rsB, f.rstdB + c)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { a1[j] = 0.f; a2[j] = 0.f; a3[j] = 0.f; }
-    const int mbeg = blockIdx.x * p.ppb;
-    int mend = mbeg + p.ppb;
-    mend = mend < p.M ? mend : p.M;
-    int it = 0;
-    for (int m = mbeg + pl; m < mend; m += ppi, ++it) {
-        float g[8], zA[8], zB[8], a[8];
-        const uint4 zAr = *reinterpret_cast<const uint4*>(p.z + (size_t)m * C + c);
-        const uint4 zBr = *reinterpret_cast<const uint4*>(f.zB + (size_t)m * C + c);
-        uint4 gr = *reinterpret_cast<const uint4*>(p.dy + (size_t)m * C + c);
-        const int b = m / HW;
-        const int r = m - b * HW;
-        const int y = r / p.W;
-        const int x = r - y * p.W;
-        unpack8(*reinterpret_cast<const uint4*>(p.act + ((size_t)(b * p.aHp + y + p.apad) * p.aWp + x + p.apad) * C + c), a);
-        unpack8(gr, g); unpack8(zAr, zA); unpack8(zBr, zB);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) g[j] = a[j] > 0.f ? g[j] : 0.f;
-        gr = pack8(g);                                      // exact: g is dy or 0
-        if (f.keep_g) sG[(size_t)it * T + tid] = gr;
-        else *reinterpret_cast<uint4*>(p.dy_rw + (size_t)m * C + c) = gr;      // parked in dy itself (this thread re-reads it)
-        if (f.keep_zA) sZA[(size_t)it * T + tid] = zAr;
-        if (f.keep_zB) sZB[(size_t)it * T + tid] = zBr;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            a1[j] += g[j];
-            a2[j] += g[j] * ((zA[j] - muA[j]) * rsA[j]);
-            a3[j] += g[j] * ((zB[j] - muB[j]) * rsB[j]);
-        }
-    }
-    if (cv < 64) {
-        for (int o = cv; o < 64; o <<= 1) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                a1[j] += __shfl_xor(a1[j], o, 64); a2[j] += __shfl_xor(a2[j], o, 64); a3[j] += __shfl_xor(a3[j], o, 64);
-            }
-        }
-    }
-    const int wstep = cv <= 64 ? 1 : cv / 64;      // (rows of `red` by the waves that share a channel group: as bn_bwd_fused_kernel)
-    if (lane < cv) {
-        const int rrow = wave / wstep;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            red[(size_t)(rrow * 3 + 0) * C + c + j] = a1[j];
-            red[(size_t)(rrow * 3 + 1) * C + c + j] = a2[j];
-            red[(size_t)(rrow * 3 + 2) * C + c + j] = a3[j];
-        }
-    }
-    __syncthreads();
-    for (int t = tid; t < 3 * C; t += T) {
-        const int which = t / C;
-        const int ch = t - which * C;
-        float tot = 0.f;
-        for (int k = 0; k < 16 / wstep; ++k) tot += red[(size_t)(k * 3 + which) * C + ch];
-        double* rows = which == 2 ? f.rowsB : f.rowsA;
-        const int slot = which == 2 ? 1 : which;
-        atomicAdd(&rows[((size_t)(blockIdx.x & (VPD_FUSED_ROWS - 1)) * 2 + slot) * C + ch], (double)tot);
-    }
-    vpd_grid_barrier(f.sync, false, f.err, blockIdx.x, gridDim.x);
-    for (int t = tid; t < 3 * C; t += T) {
-        const int which = t / C;
-        const int ch = t - which * C;
-        const double* rows = which == 2 ? f.rowsB : f.rowsA;
-        const int slot = which == 2 ? 1 : which;
-        double s = 0.0;
-#pragma unroll
-        for (int r = 0; r < VPD_FUSED_ROWS; ++r)
-            s += __hip_atomic_load(&rows[((size_t)r * 2 + slot) * C + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        red[t] = (float)(s / (double)f.count);
-        if (blockIdx.x == 0) {
-            if (which == 0) { f.dbetaA[ch] = (float)s; f.dbetaB[ch] = (float)s; }
-            else if (which == 1) f.dgammaA[ch] = (float)s;
-            else f.dgammaB[ch] = (float)s;
-        }
-    }
-    __syncthreads();
-    float c1A[8], c1B[8], c2[8], c3A[8], c3B[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        c1A[j] = f.gammaA[c + j] * rsA[j];
-        c1B[j] = f.gammaB[c + j] * rsB[j];
-        c2[j] = red[c + j];
-        c3A[j] = red[C + c + j];
-        c3B[j] = red[2 * C + c + j];
-    }
-    it = 0;
-    for (int m = mbeg + pl; m < mend; m += ppi, ++it) {
-        float g[8], zA[8], zB[8];
-        unpack8(f.keep_zA ? sZA[(size_t)it * T + tid] : *reinterpret_cast<const uint4*>(p.z + (size_t)m * C + c), zA);
-        unpack8(f.keep_zB ? sZB[(size_t)it * T + tid] : *reinterpret_cast<const uint4*>(f.zB + (size_t)m * C + c), zB);
-        unpack8(f.keep_g ? sG[(size_t)it * T + tid] : *reinterpret_cast<const uint4*>(p.dy + (size_t)m * C + c), g);
-        const int b = m / HW;
-        const int r = m - b * HW;
-        const int y = r / p.W;
-        const int x = r - y * p.W;
-        float oA[8], oB[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            oA[j] = c1A[j] * (g[j] - c2[j] - (zA[j] - muA[j]) * rsA[j] * c3A[j]);
-            oB[j] = c1B[j] * (g[j] - c2[j] - (zB[j] - muB[j]) * rsB[j] * c3B[j]);
-        }
-        const size_t oo = ((size_t)(b * p.dzHp + y + p.dzpad) * p.dzWp + x + p.dzpad) * C + c;
-        *reinterpret_cast<uint4*>(p.dz + oo) = pack8(oA);
-        *reinterpret_cast<uint4*>(f.dzB + oo) = pack8(oB);
-    }
-#undef LD8
 }
 
 // Grid and LDS residency of a fused BatchNorm backward over M pixels of C channels: one 1024-thread block per CU (the whole grid
@@ -1405,25 +1268,31 @@ bool vpd_bn_bwd_fused2_ok(int M, int C) {
     return !(!vpd_switches().fused_bn || !vpd_switches().bn_pair || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) && M >= 1;
 }
 
-// p: BatchNorm A as for vpd_launch_bn_bwd_fused (dy, act, z, mean, rstd, dz + geometry); fA / fB: rows, gamma, dgamma, dbeta
-// of the two BatchNorms (fA.sync / err / count are used); zB / meanB / rstdB / dzB: BatchNorm B's tensors
-hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p0, const BnFusedBwd& fA, const BnFusedBwd& fB, const bf16_t* zB,
-                                    const float* meanB, const float* rstdB, bf16_t* dzB, hipStream_t s) {
+// launch arguments of bn_bwd_fused_body: BatchNorm 0 from (p, fA), whose sync / err / count serve the launch; BatchNorm 1 (NB == 2) from B
+template <int NB>
+static BnFusedBwdArgs<NB> bn_bwd_fused_args(const BnBwdParams& p, const BnFusedBwd& fA, const BnBwdSecond* B, const BnBwdFusedGeom& geo) {
+    BnFusedBwdArgs<NB> f;
+    f.sync = reinterpret_cast<GridSync*>(fA.sync); f.err = fA.err; f.count = fA.count;
+    f.iters = geo.iters;
+    f.keep_g = geo.keep[0];
+    for (int n = 0; n < NB; ++n) {
+        const BnFusedBwd& side = n ? B->f : fA;
+        f.keep_z[n] = geo.keep[1 + n];
+        f.rows[n] = side.rows; f.gamma[n] = side.gamma; f.dgamma[n] = side.dgamma; f.dbeta[n] = side.dbeta;
+        f.z[n] = n ? B->z : p.z; f.mean[n] = n ? B->mean : p.mean; f.rstd[n] = n ? B->rstd : p.rstd; f.dz[n] = n ? B->dz : p.dz;
+    }
+    return f;
+}
+
+// p: BatchNorm A as for vpd_launch_bn_bwd_fused (dy, act, z, mean, rstd, dz + geometry); fA: its rows, gamma, dgamma, dbeta
+// (fA.sync / err / count are used); B: the second BatchNorm
+hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p0, const BnFusedBwd& fA, const BnBwdSecond& B, hipStream_t s) {
     BnBwdParams p = p0;
     if (!p.act) return hipErrorInvalidValue;
     const BnBwdFusedGeom geo = vpd_bn_bwd_fused_geom(p.M, p.C, 3);
-    const int G = geo.G;
     p.ppb = geo.ppb;
-    BnFusedBwd2Args f;
-    f.rowsA = fA.rows; f.rowsB = fB.rows; f.sync = reinterpret_cast<GridSync*>(fA.sync); f.err = fA.err;
-    f.zB = zB; f.meanB = meanB; f.rstdB = rstdB;
-    f.gammaA = fA.gamma; f.dgammaA = fA.dgamma; f.dbetaA = fA.dbeta;
-    f.gammaB = fB.gamma; f.dgammaB = fB.dgamma; f.dbetaB = fB.dbeta;
-    f.dzB = dzB; f.count = fA.count;
-    f.iters = geo.iters;
-    f.keep_g = geo.keep[0]; f.keep_zA = geo.keep[1]; f.keep_zB = geo.keep[2];
-    const size_t lds = geo.lds;
-    hipLaunchKernelGGL(bn_bwd_fused2_kernel, dim3(G), dim3(1024), lds, s, p, f);
+    const BnFusedBwdArgs<2> f = bn_bwd_fused_args<2>(p, fA, &B, geo);
+    hipLaunchKernelGGL(bn_bwd_fused2_kernel, dim3(geo.G), dim3(1024), geo.lds, s, p, f);
     return hipGetLastError();
 }
 
@@ -1439,13 +1308,8 @@ hipError_t vpd_launch_bn_bwd_fused(const BnBwdParams& p0, const BnFusedBwd& f0, 
     const BnBwdFusedGeom geo = vpd_bn_bwd_fused_geom(p.M, p.C, 2);
     const int G = geo.G;
     p.ppb = geo.ppb;
-    BnFusedBwdArgs f;
-    f.rows = f0.rows; f.sync = reinterpret_cast<GridSync*>(f0.sync); f.err = f0.err; f.gamma = f0.gamma; f.dgamma = f0.dgamma; f.dbeta = f0.dbeta;
-    f.count = f0.count;
-    f.iters = geo.iters;
+    const BnFusedBwdArgs<1> f = bn_bwd_fused_args<1>(p, f0, nullptr, geo);
     const int mask = p.mask_bits ? 3 : (p.act ? 1 : (p.mscale ? 2 : 0));
-    f.keep_g = geo.keep[0];
-    f.keep_z = geo.keep[1];
     if (!f.keep_g && mask == 1 && !p.write_g) return hipErrorInvalidValue;
     const size_t lds = geo.lds;
     if (mask == 3) hipLaunchKernelGGL((bn_bwd_fused_kernel<3, 0>), dim3(G), dim3(1024), lds, s, p, f);

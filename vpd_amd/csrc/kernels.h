@@ -151,6 +151,13 @@ struct BnFusedBwd {
     double* rows; void* sync; unsigned* err;    // sync: VPD_GRID_SYNC_BYTES, zeroed; err: sticky time-out counter
     const float* gamma; float* dgamma; float* dbeta; float count;
 };
+// the second BatchNorm of a launch that serves two with the same masked gradient (a down-sampling block's 1x1 branch): same
+// shape as the first, dz in the same padded geometry; f.sync / err / count are not read (the first BatchNorm's serve the launch)
+struct BnBwdSecond {
+    BnFusedBwd f;
+    const bf16_t* z; const float* mean; const float* rstd;
+    bf16_t* dz;
+};
 #define VPD_GRID_SYNC_BYTES (18 * 128)
 hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f, hipStream_t s);
 // conv_stream.hip: a Bottleneck's closing 1x1 convolution with its train-mode BatchNorm, the convolution recomputed instead of
@@ -171,14 +178,11 @@ BnBwdFusedGeom vpd_bn_bwd_fused_geom(int M, int C, int nt);
 hipError_t vpd_launch_bn_bwd_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s);
 // BatchNorm backward whose sums (sum g, sum g * z) the producing data gradient's epilogue has already added to `f.rows`
 // (ConvParams::bst_z): finalize + apply in one launch, no reduction pass, no grid barrier.  p.mask_bits is required.
-// fB / zB / meanB / rstdB / dzB: a second BatchNorm fed with the same masked gradient (same shape, same padded dz geometry)
-hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s, const BnFusedBwd* fB = nullptr,
-                                         const bf16_t* zB = nullptr, const float* meanB = nullptr, const float* rstdB = nullptr,
-                                         bf16_t* dzB = nullptr);
+// B: a second BatchNorm fed with the same masked gradient
+hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s, const BnBwdSecond* B = nullptr);
 // two BatchNorm backwards sharing dy and the ReLU mask (a down-sampling block's conv2 BN + its 1x1 branch's BN) in one launch
 bool vpd_bn_bwd_fused2_ok(int M, int C);
-hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p, const BnFusedBwd& fA, const BnFusedBwd& fB, const bf16_t* zB,
-                                    const float* meanB, const float* rstdB, bf16_t* dzB, hipStream_t s);
+hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p, const BnFusedBwd& fA, const BnBwdSecond& B, hipStream_t s);
 
 // head.hip
 hipError_t vpd_launch_avgpool(const bf16_t* act, int Hp, int Wp, int pad, int H, int W, int C, int N, float* pooled,

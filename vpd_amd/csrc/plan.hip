@@ -1018,13 +1018,15 @@ extern "C" int vpd_op_bn_backward_pair(void* dy, const void* act_padded, const v
     if (n < 1 || H < 1 || W < 1) return fail("bad shape");
     if (!vpd_bn_bwd_fused2_ok(n * H * W, C)) return fail("no paired BatchNorm backward for this shape");
     BnBwdParams b = op_bn_bwd_params(dy, zA, act_padded, meanA, rstdA, dzA, 1, n, H, W, C);
-    BnFusedBwd fA, fB;
+    BnFusedBwd fA;
+    BnBwdSecond B;
     memset(&fA, 0, sizeof fA);
-    memset(&fB, 0, sizeof fB);
+    memset(&B, 0, sizeof B);
     fA.rows = rowsA; fA.gamma = gammaA; fA.dgamma = dgammaA; fA.dbeta = dbetaA; fA.count = (float)b.M;
-    fB.rows = rowsB; fB.gamma = gammaB; fB.dgamma = dgammaB; fB.dbeta = dbetaB; fB.count = (float)b.M;
-    fA.sync = fB.sync = sync; fA.err = fB.err = err;
-    LCHECK(vpd_launch_bn_bwd_fused2(b, fA, fB, (const bf16_t*)zB, meanB, rstdB, (bf16_t*)dzB, (hipStream_t)stream));
+    fA.sync = sync; fA.err = err;
+    B.f.rows = rowsB; B.f.gamma = gammaB; B.f.dgamma = dgammaB; B.f.dbeta = dbetaB; B.f.count = (float)b.M;
+    B.z = (const bf16_t*)zB; B.mean = meanB; B.rstd = rstdB; B.dz = (bf16_t*)dzB;
+    LCHECK(vpd_launch_bn_bwd_fused2(b, fA, B, (hipStream_t)stream));
     return 0;
 }
 

@@ -365,6 +365,10 @@ BnFusedBwd bn_bwd_side(const Ctx& c, const ConvInfo& cv, float* grads) {
     f.count = (float)(c.n * cv.Hout * cv.Wout);
     return f;
 }
+// ... as the second BatchNorm of a launch that serves two: its side, its z and statistics, its dz
+BnBwdSecond bn_bwd_second(const Ctx& c, const ConvInfo& cv, float* grads, bf16_t* dz) {
+    return BnBwdSecond{bn_bwd_side(c, cv, grads), c.b16(cv.z_off), c.bn_mean(cv.bn), c.bn_rstd(cv.bn), dz};
+}
 
 // act != null: ReLU mask from the stored activation (needed when a residual was added before the ReLU);
 // relu_from_z: mask recomputed as scale*z + shift > 0 (plain conv-BN-ReLU), which saves reading the activation
@@ -411,8 +415,8 @@ hipError_t run_bn_bwd_apply(const Ctx& c, const ConvInfo& cv, const bf16_t* dy, 
     b.xcd_tile_px = bn_xcd_tile_px(c, cv);
     const BnFusedBwd f = bn_bwd_side(c, cv, grads);
     if (cvB) {
-        const BnFusedBwd fB = bn_bwd_side(c, *cvB, grads);
-        return vpd_launch_bn_bwd_apply_fused(b, f, c.s, &fB, c.b16(cvB->z_off), c.bn_mean(cvB->bn), c.bn_rstd(cvB->bn), dzB);
+        const BnBwdSecond B = bn_bwd_second(c, *cvB, grads, dzB);
+        return vpd_launch_bn_bwd_apply_fused(b, f, c.s, &B);
     }
     return vpd_launch_bn_bwd_apply_fused(b, f, c.s);
 }
@@ -426,10 +430,10 @@ hipError_t run_bn_bwd_pair(const Ctx& c, const ConvInfo& A, const ConvInfo& Bc, 
                            bf16_t* dzB, float* grads) {
     BnBwdParams b = bn_bwd_params(c, A, dy, dzA, 1);
     b.dy_rw = dy; b.act = act; b.aHp = A.Hout + 2; b.aWp = A.Wout + 2; b.apad = 1;
-    BnFusedBwd fA = bn_bwd_side(c, A, grads), fB = bn_bwd_side(c, Bc, grads);
-    fA.sync = fB.sync = c.ws + A.bn.sync_off;
-    fA.err = fB.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
-    return vpd_launch_bn_bwd_fused2(b, fA, fB, c.b16(Bc.z_off), c.bn_mean(Bc.bn), c.bn_rstd(Bc.bn), dzB, c.s);
+    BnFusedBwd fA = bn_bwd_side(c, A, grads);
+    fA.sync = c.ws + A.bn.sync_off;
+    fA.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
+    return vpd_launch_bn_bwd_fused2(b, fA, bn_bwd_second(c, Bc, grads, dzB), c.s);
 }
 
 // ---- a Bottleneck identity block's closing 1x1 convolution together with its BatchNorm, the convolution recomputed instead of
