@@ -324,6 +324,37 @@ int vpd_op_bn_forward(const void* z_bf16, const double* rows, const float* gamma
 int vpd_op_bn_backward_apply(const void* dy_bf16, const void* z_bf16, const unsigned char* mask_bits, const double* rows,
                              const float* gamma, const float* mean, const float* rstd, void* dz_padded_bf16, float* dgamma,
                              float* dbeta, int n, int H, int W, int C, void* stream);
+/* A Bottleneck's closing 1x1 convolution TOGETHER with its train-mode BatchNorm, the convolution recomputed in every pass
+ * instead of stored (conv1x1_bn_stream_kernel and its statistics pass; models/module.py:41-47 for a Bottleneck identity block).
+ * x: bf16 NHWC padded by 1 ([n][H istr + 2][W istr + 2][Kc]), w: [Co][Kc]; z = conv(x) is never written.  rows: f64 [4][2][Co].
+ *  mode 0  rows (pre-zeroed) receive sum z and sum z^2 of the element-rounded z
+ *  mode 1  rows read; writes mean, rstd, scale, shift, updates running_mean / running_var (both or neither), out_padded =
+ *          relu(scale z + shift + res_padded) ([n][H+2][W+2][Co], res the same layout) and, when given, its ReLU bit map mask_bits
+ *          [n H W][Co/8]
+ *  mode 2  dout (dense [n H W][Co]) and mask_bits read: rows (pre-zeroed) receive sum g and sum g z, g = dout * mask
+ *  mode 3  those rows, gamma, mean, rstd, dout, mask_bits read; writes dz_padded ([n][H+2][W+2][Co]), dgamma, dbeta
+ * Returns non-zero, and launches nothing, for a null argument the mode needs and for every shape the launcher's own
+ * vpd_conv1x1_bn_eligible refuses (Kc not 64 / 128, Co no multiple of 256, stride 2, W not a divisor of 64, fewer pixel tiles
+ * than twice the CU budget, VPD_BNECK_RECOMPUTE=0). */
+int vpd_op_conv1x1_bn(int mode, const void* x_padded, const void* w, int n, int H, int W, int istr, int Kc, int Co, double* rows,
+                      const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum, float eps,
+                      float* mean, float* rstd, float* scale, float* shift, const void* res_padded, void* out_padded,
+                      unsigned char* mask_bits, const void* dout, void* dz_padded, float* dgamma, float* dbeta, void* stream);
+/* The same for a down-sampling Bottleneck whose closing convolution (x, w) and 1x1 branch (x2, w2) both have 64 input channels and
+ * stride 1 (conv1x1_bn2_stream_kernel): out = relu(BatchNorm(conv(x)) + BatchNorm2(conv2(x2))), Co = 256.  Modes 1..3 as above with
+ * one set of BatchNorm arguments per convolution (mode 2: rows and rows2 receive sum g, sum g z and sum g, sum g z2); the two
+ * statistics passes are two mode-0 calls of vpd_op_conv1x1_bn.  Refuses what vpd_conv1x1_bn2_eligible refuses. */
+int vpd_op_conv1x1_bn2(int mode, const void* x_padded, const void* w, const void* x2_padded, const void* w2, int n, int H, int W,
+                       int Kc, int Kc2, int Co, double* rows, double* rows2, const float* gamma, const float* beta,
+                       float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
+                       const float* gamma2, const float* beta2, float* running_mean2, float* running_var2, float* mean2, float* rstd2,
+                       float* scale2, float* shift2, float momentum, float eps, void* out_padded, unsigned char* mask_bits,
+                       const void* dout, void* dz_padded, void* dz2_padded, float* dgamma, float* dbeta, float* dgamma2,
+                       float* dbeta2, void* stream);
+/* Host-only: what those launchers decide for n crops of H x W pixels on the current device, by their own code.  two: the
+ * two-convolution kernel.  out5 = {eligible, pixel lanes, channel tiles, pixel tiles of the busiest block, stages of the LDS ring}
+ * (all but the first 0 when not eligible). */
+int vpd_op_conv1x1_bn_dispatch(int n, int H, int W, int Kc, int Co, int two, int* out5);
 /* Stem BatchNorm + ReLU + MaxPool 3x3 s2 p1 in one launch (stem_pool_kernel / stem_pool_pair_kernel): z dense NHWC
  * [n][Hz][Wz][C] -> out, NHWC padded by opad ([n][Ho+2 opad][Wo+2 opad][C], Ho = (Hz-1)/2+1; the border is not written), and,
  * when idx is given (training), the window tap r*3+t of the FIRST maximum per output element, u8 dense [n][Ho][Wo][C]. */

@@ -1,5 +1,5 @@
 """Child process of tests/test_conv_ops_gpu.py (and, with "dispatch", of tests/test_opref_cpu.py): the convolution launcher reads its
-switches (VPD_PWS, VPD_PWS_GEO, VPD_PWS_BLOCKS, VPD_NO_WS) once per process, so each setting of a case gets a fresh interpreter.
+switches (VPD_PWS, VPD_PWS_GEO, VPD_PWS_BLOCKS, VPD_NO_WS, VPD_RESERVE_CUS) once per process, so each setting of a case gets a fresh interpreter.
 usage: conv_ops_child.py <run id[,run id...]> <dispatch|full|light>
   dispatch  no launch: what vpd_op_conv2d_dispatch says for every operation of the run (works without a GPU: 256 CUs assumed)
   full      both libraries, both input regimes, every operation against the float64 reference
@@ -25,7 +25,9 @@ SLACK = 4096                 # elements behind every output buffer
 REL_TOL = 4e-3               # the whole-tensor gate of tests/test_ops_gpu.py, kept beside the per-element bound
 
 # run id -> (case of opref.CONV_CASES, environment, expected dispatch of the forward launch, of the data-gradient launch or None
-# for "the same").  tiles: pixel tiles of the busiest block.  Expectations hold for a 256-CU device.
+# for "the same").  tiles: pixel tiles of the busiest block; nsa: stages of the kernel's LDS ring, which `tiles` must exceed (a stage
+# is overwritten from a block's (nsa + 1)-th tile on).  Expectations hold for a 256-CU device.
+FEW = {"VPD_RESERVE_CUS": "248"}       # a budget of 8 CUs: 8 pixel lanes, so a small tensor gives every block a long walk
 RUNS = {
     "c0_w32-device":        ("c0_w32", {}, dict(kclass=0, bm=128, bn=64, tiles=2), None),
     "c0_w16-device":        ("c0_w16", {}, dict(kclass=0, bm=128, bn=64, tiles=2), None),
@@ -60,6 +62,21 @@ RUNS = {
     "stem_w128-device":     ("stem_w128", {}, dict(kclass=5, bm=128, bn=64, tiles=2), None),
     "stem_w32-device":      ("stem_w32", {}, dict(kclass=5, bm=128, bn=64, tiles=1), None),
     "ring_1x1-device":      ("ring_1x1", {}, dict(kclass=4, ws1x1=1, bm=256, bn=128), dict(kclass=4, ws1x1=0, stream1x1=1)),
+    # conv1x1_stream_kernel<KC, BM, BN, NSA>: every instantiation of the launcher's table on a ring that wraps (8 CUs), forward and
+    # data gradient with their accumulate / eval epilogues; the last run on the whole device
+    "st_64_64-few":         ("st_64_64", FEW, dict(kclass=4, stream1x1=1, bm=128, bn=64, tiles=9, nsa=6), None),
+    "st_64_128-few":        ("st_64_128", FEW, dict(kclass=4, stream1x1=1, bm=128, bn=128, tiles=9, nsa=6),
+                             dict(kclass=4, stream1x1=1, bm=128, bn=64, tiles=9, nsa=4)),
+    "st_64_256-few":        ("st_64_256", FEW, dict(kclass=4, stream1x1=1, bm=64, bn=256, tiles=12, nsa=8),
+                             dict(kclass=4, stream1x1=1, bm=64, bn=64, tiles=12, nsa=4)),
+    "st_64_256_w16-few":    ("st_64_256_w16", FEW, dict(kclass=4, stream1x1=1, bm=64, bn=256, tiles=12, nsa=8),
+                             dict(kclass=4, stream1x1=1, bm=64, bn=64, tiles=12, nsa=4)),
+    "st_128_128-few":       ("st_128_128", FEW, dict(kclass=4, stream1x1=1, bm=128, bn=128, tiles=9, nsa=4), None),
+    "st_128_256-few":       ("st_128_256", FEW, dict(kclass=4, stream1x1=1, bm=64, bn=256, tiles=12, nsa=6),
+                             dict(kclass=4, stream1x1=1, bm=32, bn=128, tiles=24, nsa=6)),
+    "st_256_512_s2-few":    ("st_256_512_s2", FEW, dict(kclass=4, stream1x1=1, bm=32, bn=128, tiles=24, nsa=6), None),
+    "st_64_256_w32-device": ("st_64_256_w32", {}, dict(kclass=4, stream1x1=1, bm=64, bn=256, tiles=3),
+                             dict(kclass=4, stream1x1=1, bm=64, bn=64, tiles=3)),
 }
 # switch variants whose outputs must be bit-identical to another run's (same products, same order of additions)
 SAME_BITS = {"c6_w16-geo_off": "c6_w16-device", "c6_w16-ws": "c6_w16-device", "c6_w8_ragged-geo_off": "c6_w8_ragged-few_blocks",
@@ -362,6 +379,10 @@ def check_dispatch(run, table, fail):
         if d["c64x2"]:
             exp = dict(kclass=0, bm=256, bn=64, tiles=1)  # the inference twin: 256-pixel tiles, one per block at 256 x 256 pixels
         for key, val in exp.items():
+            if key == "nsa":
+                if d["tiles"] <= val:
+                    fail.append("dispatch of %s: %d tiles per block do not wrap a ring of %d stages (%r)" % (op, d["tiles"], val, d))
+                continue
             if key == "geo" and val and op in ("fwd_padded",):
                 val = 0                                  # (no compile-time-geometry instantiation of the plain forward store)
             if d[key] != val:

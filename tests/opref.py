@@ -1,5 +1,5 @@
 """Plain float64 PyTorch references, input generators and derived error bounds shared by the operator parity tests
-(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py, test_conv_ops_gpu.py).  Nothing here touches the GPU or the library:
+(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py, test_conv_ops_gpu.py, test_bneck_tail_ops_gpu.py).  Nothing here touches the GPU or the library:
 tests/test_opref_cpu.py pins what these references rest on, so that a failure on the GPU points at the kernel."""
 import math
 
@@ -346,6 +346,17 @@ CONV_CASES = {
     "stem_w32":      dict(n=6,   ci=5,   co=64,  h=32, w=32, k=7, stride=2, stem=True, blk_px=128),
     # 1x1 ring GEMM (conv1x1_ws_kernel): K = 512, 200 tiles of 256 x 128
     "ring_1x1":      dict(n=50,  ci=512, co=128, h=32, w=32, k=1, blk_px=256),
+    # 1x1 streaming kernel (conv1x1_stream_kernel).  st_*: sized for a budget of 8 CUs (VPD_RESERVE_CUS=248: 8 pixel lanes, eligible
+    # from 16 pixel tiles), so that every block walks more tiles than its LDS ring has stages; the forward takes the instantiation of
+    # (ci, co), the data gradient that of (co, ci).  blk_px = tiles per block x tile pixels
+    "st_64_64":      dict(n=67,  ci=64,  co=64,  h=8,  w=16, k=1, blk_px=9 * 128),      # 67 tiles of one image, 9 per block
+    "st_64_128":     dict(n=67,  ci=64,  co=128, h=8,  w=16, k=1, blk_px=9 * 128),
+    "st_64_256":     dict(n=93,  ci=64,  co=256, h=8,  w=8,  k=1, blk_px=12 * 64),      # 93 tiles of one image, 12 per block
+    "st_64_256_w16": dict(n=23,  ci=64,  co=256, h=16, w=16, k=1, blk_px=12 * 64),      # four-row tiles, four tiles per image
+    "st_128_128":    dict(n=67,  ci=128, co=128, h=8,  w=16, k=1, blk_px=9 * 128),
+    "st_128_256":    dict(n=93,  ci=128, co=256, h=8,  w=8,  k=1, blk_px=12 * 64),      # (data gradient: 186 tiles of 32 pixels, 24 per block)
+    "st_256_512_s2": dict(n=47,  ci=256, co=512, h=16, w=32, k=1, stride=2, blk_px=24 * 32),   # 188 tiles of two output rows
+    "st_64_256_w32": dict(n=40,  ci=64,  co=256, h=32, w=32, k=1, blk_px=3 * 64),       # the whole device: 640 tiles on 256 lanes
 }
 for _c in CONV_CASES.values():
     _c.setdefault("k", 3)
@@ -474,3 +485,203 @@ def conv_alter_tile(ref, tile_px, tile=1):
     lo = max(0, min(tile * px, n * h * w - px - h * w))
     flat[lo:lo + px] = flat[lo + h * w:lo + h * w + px].clone()
     return nchw(flat.view(n, h, w, c))
+
+
+# ---------------------------------------------------------------------------
+# A Bottleneck's closing 1x1 convolution fused with its BatchNorm (conv1x1_bn_stream_kernel, conv1x1_bn2_stream_kernel;
+# tests/test_bneck_tail_ops_gpu.py, tests/bneck_tail_child.py)
+# ---------------------------------------------------------------------------
+# few: run with a budget of 8 CUs (VPD_RESERVE_CUS=248): 8 pixel lanes walk the 64-pixel tiles, more per block than the ring is
+# deep (8 stages for 64 input channels, 5 for 128 and for the two-convolution kernel).  two: the down-sampling block's kernel,
+# out = relu(BatchNorm(conv(x)) + BatchNorm2(conv2(x2))), 64 input channels each.
+TAIL_CASES = {
+    "k64_w8":      dict(n=93, ci=64,  co=256, h=8,  w=8,  few=True),      # 93 tiles, 11-12 per block
+    "k64_w16":     dict(n=23, ci=64,  co=256, h=16, w=16, few=True),      # 92 tiles of four rows, four per image
+    "k64_co512":   dict(n=93, ci=64,  co=512, h=8,  w=8,  few=True),      # two channel tiles
+    "k128_w8":     dict(n=61, ci=128, co=256, h=8,  w=8,  few=True),      # 61 tiles, 7-8 per block
+    "k128_co512":  dict(n=61, ci=128, co=512, h=8,  w=8,  few=True),
+    "two_w8":      dict(n=61, ci=64,  co=256, h=8,  w=8,  few=True, two=True),
+    "two_w16":     dict(n=23, ci=64,  co=256, h=16, w=16, few=True, two=True),
+    "k64_w32":     dict(n=40, ci=64,  co=256, h=32, w=32, few=False),     # the whole device: 640 tiles, 2-3 per block
+    "two_w32":     dict(n=40, ci=64,  co=256, h=32, w=32, few=False, two=True),
+}
+for _c in TAIL_CASES.values():
+    _c.setdefault("two", False)
+    _c.update(k=1, stride=1)
+TAIL_TILE = 64                     # pixels per tile of both kernels
+TAIL_LANES = 8                     # pixel lanes of a few-CU run
+BN_MOMENTUM = 0.1
+BN_RTOL, BN_MEAN_ATOL = 1e-5, 1e-6          # test_batchnorm_forward_op's gates on mean / rstd / scale / running statistics
+
+
+def tail_ring(cs):
+    return 5 if cs["two"] or cs["ci"] == 128 else 8
+
+
+def tail_operands(cs, seed, regime, name="bf16"):
+    """conv_operands' two regimes for the fused tail: x, w (x2, w2 of the branch), the residual (one-convolution kernel), d(out), a
+    random ReLU bit map, fp32 gamma / beta / running statistics per BatchNorm (suffix 2: the branch's)"""
+    n, ci, co, h, w = cs["n"], cs["ci"], cs["co"], cs["h"], cs["w"]
+    g = torch.Generator().manual_seed(seed * 1000 + n + ci + h + co)
+    o = {}
+    if regime == "int":
+        dens = min(0.5, 288.0 / max(ci, co))
+        xs, ws = (lambda: _sparse_int((n, ci, h, w), 0.5, g)), (lambda: _sparse_int((co, ci, 1, 1), dens, g))
+        small = lambda shape: torch.randint(-CONV_ZMAX, CONV_ZMAX + 1, shape, generator=g).double()
+        o["dout"] = _sparse_int((n, co, h, w), 0.5, g)
+    else:
+        er = lambda t: elem_round(t, name).double()
+        xs, ws = (lambda: er(torch.randn(n, ci, h, w, generator=g))), (lambda: er(torch.randn(co, ci, 1, 1, generator=g) * (2.0 / ci) ** 0.5))
+        small = lambda shape: er(torch.randn(shape, generator=g))
+        o["dout"] = er(torch.randn(n, co, h, w, generator=g))
+    o["x"], o["w"] = xs(), ws()
+    if cs["two"]:
+        o["x2"], o["w2"] = xs(), ws()
+    else:
+        o["res"] = small((n, co, h, w))
+    o["keep"] = torch.rand((n, co, h, w), generator=g) > 0.4
+    for sfx in ("", "2") if cs["two"] else ("",):
+        o["gamma" + sfx], o["beta" + sfx] = stem_params(co, "init", g)
+        o["rm" + sfx], o["rv" + sfx] = torch.randn(co, generator=g) * 0.1, torch.rand(co, generator=g) + 0.5
+    return o
+
+
+def tail_conv(x, w, name=None):
+    """z = conv1x1(x, w) in float64; name: rounded to that element type (the CPU stand-in for the unfused launch's stored z)"""
+    z = F.conv2d(x.double(), w.double())
+    return z if name is None else z.to(ELEM[name][0]).double()
+
+
+def _cv(t):
+    return t.double().view(1, -1, 1, 1)
+
+
+def tail_stats(z, gamma, beta, rm, rv):
+    """float64: the two rows (sum z, sum z^2), batch statistics, scale / shift, updated running statistics; abs1: sum |z|"""
+    M = z.shape[0] * z.shape[2] * z.shape[3]
+    s1, s2 = z.sum(dim=(0, 2, 3)), (z * z).sum(dim=(0, 2, 3))
+    mean = s1 / M
+    var = (s2 / M - mean * mean).clamp_min(0)
+    rstd = (var + BN_EPS).rsqrt()
+    scale = gamma.double() * rstd
+    return {"s1": s1, "s2": s2, "abs1": z.abs().sum(dim=(0, 2, 3)), "M": M, "mean": mean, "var": var, "rstd": rstd, "scale": scale,
+            "shift": beta.double() - mean * scale, "gamma": gamma.double(), "beta": beta.double(),
+            "rm": (1 - BN_MOMENTUM) * rm.double() + BN_MOMENTUM * mean,
+            "rv": (1 - BN_MOMENTUM) * rv.double() + BN_MOMENTUM * var * M / (M - 1)}
+
+
+def tail_pre(z, st, idx=None):
+    """z scale + shift; idx: the channel each channel takes its coefficients from (fault iii)"""
+    sc, sh = (st["scale"], st["shift"]) if idx is None else (st["scale"][idx], st["shift"][idx])
+    return z * _cv(sc) + _cv(sh)
+
+
+def tail_pre_err(z, st, exact_rows):
+    """What an fp32 evaluation of z scale + shift from fp32 coefficients may be off by, per element.
+    Coefficients (bn_finalize_channel): the rows hold sum z and sum z^2 to SUM_TOL of the sums of magnitudes (exact_rows: exactly,
+    the integer regime), mean and variance are formed in fp64; then four fp32 roundings on the way to scale (var + eps, the 1-ulp
+    reciprocal square root = two half-ulps, the product with gamma) and three more to shift (mean, mean scale, the subtraction).
+    Element: the fused multiply-add rounds once (two allowed, on |z scale| + |shift|)."""
+    u = 2.0 ** -24
+    tol = 0.0 if exact_rows else SUM_TOL
+    dmean = tol * st["abs1"] / st["M"]
+    dvar = tol * st["s2"] / st["M"] + 2 * st["mean"].abs() * dmean
+    dsc = st["gamma"].abs() * 0.5 * st["rstd"] ** 3 * dvar + 4 * u * st["scale"].abs()
+    dsh = st["scale"].abs() * (dmean + u * st["mean"].abs()) + st["mean"].abs() * dsc + 2 * u * (st["beta"].abs() + (st["mean"] * st["scale"]).abs())
+    return z.abs() * _cv(dsc) + _cv(dsh) + 2 * u * ((z * _cv(st["scale"])).abs() + _cv(st["shift"]).abs())
+
+
+def tail_out_bound(pre, err, other, name):
+    """|stored out - relu(pre)| for pre = (z scale + shift) + other (the residual, or the branch's z2 scale2 + shift2): err = the
+    terms' tail_pre_err, one more fp32 addition (two roundings allowed), half an element ulp (|relu(a) - relu(b)| <= |a - b|)"""
+    e = err + 2 * 2.0 ** -24 * ((pre - other).abs() + other.abs())
+    return 0.5 * ulp(pre.abs() + e, name) + e
+
+
+def tail_bwd(z, st, gm, idx=None):
+    """float64 backward of one BatchNorm for the masked gradient gm: rows (sum g, sum g z), dz in the kernel's form A g + B z + D
+    (equal to bn_dz_closed_form: tests/test_opref_cpu.py), dgamma, dbeta and the sums of magnitudes their tolerances scale with"""
+    M = st["M"]
+    xhat = (z - _cv(st["mean"])) * _cv(st["rstd"])
+    r1, r2 = gm.sum(dim=(0, 2, 3)), (gm * z).sum(dim=(0, 2, 3))
+    sx = (r2 - st["mean"] * r1) * st["rstd"]
+    A = st["gamma"] * st["rstd"]
+    B = -A * st["rstd"] * sx / M
+    D = -A * r1 / M - B * st["mean"]
+    if idx is not None:
+        A, B, D = A[idx], B[idx], D[idx]
+    return {"r1": r1, "r2": r2, "dz": _cv(A) * gm + _cv(B) * z + _cv(D), "dgamma": sx, "dbeta": r1, "xhat": xhat,
+            "abs1": gm.abs().sum(dim=(0, 2, 3)), "abs2": (gm * xhat).abs().sum(dim=(0, 2, 3)), "absz": (gm * z).abs().sum(dim=(0, 2, 3))}
+
+
+def tail_dz_bound(z, st, gm, b, name):
+    """bn_dz_bound for this BatchNorm, the sums good to SUM_TOL of their sums of magnitudes"""
+    return bn_dz_bound(b["dz"], st["gamma"], st["rstd"], st["mean"], z, gm, b["xhat"], b["dbeta"], b["dgamma"], SUM_TOL * b["abs1"],
+                       SUM_TOL * b["abs2"], st["M"], name)
+
+
+def tail_forward(cs, o, z, z2, exact_rows, name, idx=None, res=None):
+    """the forward chain of a case from z (and the branch's z2): statistics per BatchNorm, out = relu(pre) in float64 and the
+    per-element bound of the stored out.  idx: fault (iii); res: another residual (fault v)"""
+    st = tail_stats(z, o["gamma"], o["beta"], o["rm"], o["rv"])
+    t, err = tail_pre(z, st, idx), tail_pre_err(z, st, exact_rows)
+    if cs["two"]:
+        st2 = tail_stats(z2, o["gamma2"], o["beta2"], o["rm2"], o["rv2"])
+        other, err = tail_pre(z2, st2, idx), err + tail_pre_err(z2, st2, exact_rows)
+    else:
+        st2, other = None, (o["res"] if res is None else res)
+    pre = t + other
+    return {"st": st, "st2": st2, "pre": pre, "out": pre.clamp_min(0), "bound": tail_out_bound(pre, err, other, name)}
+
+
+def tail_backward(cs, o, z, z2, fw, mask, name, idx=None, dout=None):
+    """the backward chain under the ReLU map `mask`: per BatchNorm the rows, dz with its bound, dgamma, dbeta"""
+    gm = (o["dout"] if dout is None else dout) * mask
+    out = {"gm": gm, "b": tail_bwd(z, fw["st"], gm, idx)}
+    out["bound"] = tail_dz_bound(z, fw["st"], gm, out["b"], name)
+    if cs["two"]:
+        out["b2"] = tail_bwd(z2, fw["st2"], gm, idx)
+        out["bound2"] = tail_dz_bound(z2, fw["st2"], gm, out["b2"], name)
+    return out
+
+
+def tail_stored_mask(out, name):
+    """the forward's own bit map: the stored out is not zero"""
+    return out.to(ELEM[name][0]) != 0
+
+
+# the five faults a streaming kernel can have, as altered inputs of the chain above
+def tail_alter_tile(z, lanes, ring, tile=1):
+    """(i) one 64-pixel tile (NHWC pixel order) of z computed from the input of the tile ring x lanes further on: a ring stage
+    overwritten before it was read (a tensor with fewer tiles: from the last tile)"""
+    n, c, h, w = z.shape
+    flat = nhwc(z).reshape(n * h * w, c).clone()
+    src = min(tile + ring * lanes, n * h * w // TAIL_TILE - 1)
+    flat[tile * TAIL_TILE:(tile + 1) * TAIL_TILE] = flat[src * TAIL_TILE:(src + 1) * TAIL_TILE].clone()
+    return nchw(flat.view(n, h, w, c))
+
+
+def tail_alter_chunks(cs, o, name=None):
+    """(ii) image 0 with the two 64-channel chunks of the weights swapped (64 input channels: the two halves); two-convolution
+    kernel: x and x2 swapped.  -> altered (z, z2)"""
+    if cs["two"]:
+        return tail_conv(o["x2"], o["w"], name), tail_conv(o["x"], o["w2"], name)
+    z = tail_conv(o["x"], o["w"])
+    z = conv_alter_chunks(z, o["x"], o["w"], cs)
+    return (z if name is None else z.to(ELEM[name][0]).double()), None
+
+
+def tail_alter_coef(co, c0=8):
+    """(iii) channels c0 .. c0 + 3 take their coefficients from 16 channels further on: the index map"""
+    idx = torch.arange(co)
+    idx[c0:c0 + 4] = torch.arange(c0 + 16, c0 + 20)
+    return idx
+
+
+def tail_alter_mask(mask, tile=1):
+    """(iv) the bit map of one tile read 4 channels off"""
+    n, c, h, w = mask.shape
+    flat = nhwc(mask).reshape(n * h * w, c).clone()
+    flat[tile * TAIL_TILE:(tile + 1) * TAIL_TILE] = torch.roll(flat[tile * TAIL_TILE:(tile + 1) * TAIL_TILE], -4, dims=1)
+    return nchw(flat.view(n, h, w, c))
+# (v) the residual / d(out) one pixel to the right: conv_alter_shift

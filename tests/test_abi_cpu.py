@@ -135,6 +135,19 @@ def test_conv_dispatch_and_two_batchnorm_sums_reject_bad_arguments(dtype):
     assert h.vpd_op_conv2d_bnsums2(p, p, p, p, p, p, p, p, 4, 18, 18, 128, 16, 16, 128, 128, None, None) != 0
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_fused_tail_entry_points_are_declared_bound_and_exported(dtype):
+    """vpd_op_conv1x1_bn, vpd_op_conv1x1_bn2 and the host-only vpd_op_conv1x1_bn_dispatch: test-only additions under ABI 5 (their
+    refusals: tests/test_bneck_tail_cpu.py)"""
+    from vpd_amd import _lib
+    h = _lib.lib(dtype)
+    assert h.vpd_abi_version() == _lib.ABI_VERSION == 5
+    for n, nargs in (("vpd_op_conv1x1_bn", 28), ("vpd_op_conv1x1_bn2", 41), ("vpd_op_conv1x1_bn_dispatch", 7)):
+        assert n in header_functions() and len(_lib.SIGNATURES[n][1]) == nargs and getattr(h, n).argtypes == _lib.SIGNATURES[n][1]
+    out = (C.c_int * 5)()
+    assert h.vpd_op_conv1x1_bn_dispatch(256, 32, 32, 64, 256, 1, out) == 0 and out[0] == 1 and out[4] == 5
+
+
 def test_product_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -267,3 +267,144 @@ def test_conv_runs_dispatch_to_the_kernels_their_ids_name():
     assert {(1, 0, None), (1, 1, 0), (2, 1, 0), (2, 0, None), (3, 1, 4), (3, 1, 0), (3, 0, None), (6, 1, 16), (6, 1, 8), (6, 1, 0),
             (6, 0, None)} <= forms
     assert {(d["bm"], d["bn"]) for _, _, _, d in RUNS.values() if d and d.get("ws1x1") == 0 and "bm" in d} == {(128, 128), (64, 64), (128, 64)}
+
+
+# ---------------------------------------------------------------------------
+# the fused Bottleneck tail (conv1x1_bn_stream_kernel, conv1x1_bn2_stream_kernel)
+# ---------------------------------------------------------------------------
+TAIL_IDS = list(R.TAIL_CASES)
+
+
+def test_tail_chain_is_batch_norm_and_its_autograd():
+    """the float64 chain of the tail references -- statistics from the two sums, running statistics, the kernel's A g + B z + D form of
+    dz, dgamma = (sum g z - mean sum g) rstd -- equals torch's batch_norm and its autograd to 1e-12, residual and ReLU included"""
+    cs = dict(R.TAIL_CASES["k64_w8"], n=5)
+    o = R.tail_operands(cs, 3, "rand", "bf16")
+    z = R.tail_conv(o["x"], o["w"], "bf16")
+    fw = R.tail_forward(cs, o, z, None, False, "bf16")
+    rm, rv = o["rm"].double().clone(), o["rv"].double().clone()
+    zt, gt, bt = z.clone().requires_grad_(True), o["gamma"].double().requires_grad_(True), o["beta"].double().requires_grad_(True)
+    y = F.batch_norm(zt, rm, rv, gt, bt, training=True, momentum=R.BN_MOMENTUM, eps=R.BN_EPS) + o["res"]
+    (y.clamp_min(0) * o["dout"]).sum().backward()
+    st = fw["st"]
+    close = lambda a, b: float((a - b).abs().max()) <= 1e-12 * max(1.0, float(b.abs().max()))
+    assert close(fw["pre"], y.detach()) and close(st["rm"], rm) and close(st["rv"], rv)
+    bw = R.tail_backward(cs, o, z, None, fw, y.detach() > 0, "bf16")
+    assert close(bw["b"]["dz"], zt.grad) and close(bw["b"]["dgamma"], gt.grad) and close(bw["b"]["dbeta"], bt.grad)
+    assert close(bw["b"]["dz"], R.bn_dz_closed_form(z, o["gamma"], st["mean"], st["rstd"], bw["gm"]))
+    assert torch.equal(R.tail_alter_coef(256)[:32], torch.tensor(list(range(8)) + [24, 25, 26, 27] + list(range(12, 32))))
+
+
+def _tail_faults(cs, o, z, z2, fw, mask, name, regime):
+    """{fault: [(altered, right, bound or None = equality), ...]} over every output the GPU test compares"""
+    exact = regime == "int"
+    ring, zname = R.tail_ring(cs), (None if exact else name)
+    bw = R.tail_backward(cs, o, z, z2, fw, mask, name)
+    rows = lambda st: torch.stack([st["s1"], st["s2"]])
+    rows_tol = lambda st: None if exact else R.SUM_TOL * torch.stack([st["abs1"], st["s2"]])
+    brows = lambda b: torch.stack([b["r1"], b["r2"]])
+    brows_tol = lambda b: None if exact else R.SUM_TOL * torch.stack([b["abs1"], b["absz"]])
+
+    def everything(fz, fz2, idx=None, res=None, fmask=None, dout=None):
+        """a faulted launch sequence against the right one: the statistics rows come from the faulted z, the element-wise passes
+        apply the RIGHT coefficients (each pass is a launch of its own) to the faulted operands"""
+        f = dict(fw)
+        pre = R.tail_pre(fz, fw["st"], idx) + (R.tail_pre(fz2, fw["st2"], idx) if cs["two"] else (o["res"] if res is None else res))
+        pairs = [(pre.clamp_min(0), fw["out"], fw["bound"])]
+        fst = R.tail_stats(fz, o["gamma"], o["beta"], o["rm"], o["rv"])
+        pairs.append((rows(fst), rows(fw["st"]), rows_tol(fw["st"])))
+        gm = (o["dout"] if dout is None else dout) * (mask if fmask is None else fmask)
+        sides = [(fz, z, fw["st"], bw["b"], bw["bound"])] + ([(fz2, z2, fw["st2"], bw["b2"], bw["bound2"])] if cs["two"] else [])
+        for a, right, st, b, bound in sides:
+            fb = R.tail_bwd(a, st, gm, None)
+            pairs.append((brows(fb), brows(b), brows_tol(b)))
+            # mode 3 applies the coefficients of the RIGHT sums to the faulted operands
+            A = st["gamma"] * st["rstd"]
+            B = -A * st["rstd"] * b["dgamma"] / st["M"]
+            D = -A * b["r1"] / st["M"] - B * st["mean"]
+            if idx is not None:
+                A, B, D = A[idx], B[idx], D[idx]
+            v = lambda t: t.view(1, -1, 1, 1)
+            pairs.append((v(A) * gm + v(B) * a + v(D), b["dz"], bound))
+        return pairs
+
+    fz, fz2 = R.tail_alter_tile(z, R.TAIL_LANES, ring), (R.tail_alter_tile(z2, R.TAIL_LANES, ring) if cs["two"] else None)
+    cz, cz2 = R.tail_alter_chunks(cs, o, zname)
+    faults = {"tile": everything(fz, fz2), "chunks": everything(cz, cz2), "coef": everything(z, z2, idx=R.tail_alter_coef(cs["co"])),
+              "mask": everything(z, z2, fmask=R.tail_alter_mask(mask)), "dout": everything(z, z2, dout=torch.roll(o["dout"], 1, dims=3))}
+    if not cs["two"]:
+        faults["res"] = everything(z, z2, res=torch.roll(o["res"], 1, dims=3))
+    # what each fault must show in: a stale tile and swapped chunks everywhere, coefficients in out and dz, the bit map and d(out) in
+    # the backward sums and dz, the residual in out
+    nside = 2 if cs["two"] else 1
+    fwd, stat = [0], [1]
+    bsum, dz = [2 + 2 * i for i in range(nside)], [3 + 2 * i for i in range(nside)]
+    where = {"tile": fwd + stat + bsum + dz, "chunks": fwd + stat + bsum + dz, "coef": fwd + dz, "mask": bsum + dz, "dout": bsum + dz, "res": fwd}
+    return faults, where
+
+
+def _outside(alt, ref, bound):
+    return (not torch.equal(alt, ref)) if bound is None else bool(((alt - ref).abs() > bound).any())
+
+
+@pytest.mark.parametrize("case", TAIL_IDS)
+def test_tail_integer_regime_is_exact_and_sees_the_five_faults(case):
+    """Integer operands: x, w, residual and d(out) are bf16 and fp16 values, |z| <= 2^8, so z is the exact convolution in either
+    library; every statistics row (sum z, sum z^2, sum g, sum g z -- sums of magnitudes taken) is an integer below 2^24 and must be
+    EQUAL.  Each fault changes a row, or puts out / dz outside its bound, in every output it can reach."""
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    cs = R.TAIL_CASES[case]
+    o = R.tail_operands(cs, R.CONV_SEEDS[0], "int")
+    for key in ("x", "w", "x2", "w2", "res", "dout"):
+        if key in o:
+            for name in ("bf16", "fp16"):
+                assert torch.equal(R.elem_round(o[key].float(), name).double(), o[key]), (key, name)
+    z = R.tail_conv(o["x"], o["w"])
+    z2 = R.tail_conv(o["x2"], o["w2"]) if cs["two"] else None
+    for t in (z, z2) if cs["two"] else (z,):
+        assert float(t.abs().max()) <= 2.0 ** R.ELEM["bf16"][1] and torch.equal(t, t.round())
+        assert float((t * t).sum(dim=(0, 2, 3)).max()) < 2.0 ** 24
+        assert float((o["dout"].abs() * t.abs()).sum(dim=(0, 2, 3)).max()) < 2.0 ** 24
+    fw = R.tail_forward(cs, o, z, z2, True, "bf16")
+    own = R.tail_stored_mask(fw["out"], "bf16")
+    assert 0.2 < float(own.double().mean()) < 0.8
+    for mask in (o["keep"], own) if cs["few"] else (own,):          # (the whole-device cases: the same kernels, one map)
+        faults, where = _tail_faults(cs, o, z, z2, fw, mask, "bf16", "int")
+        for fault, pairs in faults.items():
+            for i in where[fault]:
+                assert _outside(*pairs[i]), (fault, i)
+
+
+@pytest.mark.parametrize("case", TAIL_IDS)
+@pytest.mark.parametrize("name", ["bf16", "fp16"])
+def test_tail_random_regime_bounds_accept_fp32_and_reject_the_five_faults(case, name):
+    """randn operands, z rounded to the element type (on the GPU: the unfused launch's stored z).  The bounds accept a stand-in for
+    the kernels -- fp32 coefficients from the float64 sums, fp32 element arithmetic, rounded to the element type -- and put every
+    faulted reference outside in at least one element of every output the fault can reach."""
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    cs = R.TAIL_CASES[case]
+    o = R.tail_operands(cs, R.CONV_SEEDS[0], "rand", name)
+    z = R.tail_conv(o["x"], o["w"], name)
+    z2 = R.tail_conv(o["x2"], o["w2"], name) if cs["two"] else None
+    fw = R.tail_forward(cs, o, z, z2, False, name)
+    f32 = lambda t: t.float().view(1, -1, 1, 1)
+
+    def pre32(zz, st, sfx):
+        sc = o["gamma" + sfx].float() * (st["var"] + R.BN_EPS).float().rsqrt()
+        return zz.float() * f32(sc) + f32(o["beta" + sfx].float() - st["mean"].float() * sc)
+    v32 = pre32(z, fw["st"], "") + (pre32(z2, fw["st2"], "2") if cs["two"] else o["res"].float())
+    got = R.elem_round(v32.clamp_min(0), name).double()
+    assert bool(((got - fw["out"]).abs() <= fw["bound"]).all())
+    mask = R.tail_stored_mask(fw["out"], name)
+    bw = R.tail_backward(cs, o, z, z2, fw, mask, name)
+    for zz, st, b, bound in [(z, fw["st"], bw["b"], bw["bound"])] + ([(z2, fw["st2"], bw["b2"], bw["bound2"])] if cs["two"] else []):
+        A = (st["gamma"] * st["rstd"].float().double())
+        B = -A * st["rstd"].float().double() * b["dgamma"] / st["M"]
+        D = -A * b["r1"] / st["M"] - B * st["mean"].float().double()
+        dz32 = f32(A) * bw["gm"].float() + (f32(B) * zz.float() + f32(D))
+        assert bool(((R.elem_round(dz32, name).double() - b["dz"]).abs() <= bound).all())
+    for mk in (o["keep"], mask) if cs["few"] else (mask,):
+        faults, where = _tail_faults(cs, o, z, z2, fw, mk, name, "rand")
+        for fault, pairs in faults.items():
+            for i in where[fault]:
+                assert _outside(*pairs[i]), (fault, i)

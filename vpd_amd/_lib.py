@@ -77,6 +77,9 @@ SIGNATURES = {
     "vpd_op_conv2d_dispatch": (C.c_int, [C.c_int] * 16 + [c_int_p, C.c_int, C.c_int, c_int_p]),
     "vpd_op_bn_forward": (C.c_int, [vp] * 13 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
     "vpd_op_bn_backward_apply": (C.c_int, [vp] * 10 + [C.c_int] * 4 + [vp]),
+    "vpd_op_conv1x1_bn": (C.c_int, [C.c_int, vp, vp] + [C.c_int] * 6 + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 12),
+    "vpd_op_conv1x1_bn2": (C.c_int, [C.c_int] + [vp] * 4 + [C.c_int] * 6 + [vp] * 18 + [C.c_float, C.c_float] + [vp] * 10),
+    "vpd_op_conv1x1_bn_dispatch": (C.c_int, [C.c_int] * 6 + [c_int_p]),
     "vpd_op_stem_pool_forward": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [vp]),
     "vpd_op_stem_pool_backward": (C.c_int, [vp] * 15 + [C.c_int] * 4 + [vp]),
     "vpd_op_bn_backward": (C.c_int, [vp] * 15 + [C.c_int] + [vp, vp] + [C.c_int] * 6 + [vp]),

@@ -1765,7 +1765,13 @@ ConvDispatch vpd_conv_dispatch(const ConvParams& p, HaloGeom* g) {
         }
         default: break;
     }
-    if (vpd_conv1x1_stream_eligible(p)) { d.stream1x1 = 1; d.tiles_per_block = 0; return d; }
+    if (vpd_conv1x1_stream_eligible(p)) {
+        int lanes;
+        d.stream1x1 = 1;
+        vpd_conv1x1_stream_grid(p, &d.bm, &d.bn, &lanes);
+        d.tiles_per_block = (p.M / d.bm + lanes - 1) / lanes;
+        return d;
+    }
     if (conv1x1_ws_eligible(p)) { d.ws1x1 = 1; conv1x1_ws_tile(p, &d.bm, &d.bn); return d; }
     // the statistics accumulator rows only depend on the block index, so the tile choice is free
     const int bm = vpd_conv_bm(p.M, p.Co);

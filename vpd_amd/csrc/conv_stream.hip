@@ -663,6 +663,17 @@ __global__ __launch_bounds__(768) void conv1x1_bn2_stream_kernel(const ConvParam
 
 int stream_cu_count() { return vpd_cu_budget(); }
 
+// pixel lanes (gridDim.x) of a launch with NT channel tiles on `mtiles` pixel tiles
+int stream_lanes(int mtiles, int NT) {
+    int lanes = stream_cu_count() / NT;
+    lanes -= lanes % 8;                      // blocks b and b + 8 share an XCD: the NT channel tiles of a pixel tile meet in its L2
+    if (lanes < 8) lanes = 8;
+    if (lanes > mtiles) lanes = mtiles;
+    return lanes;
+}
+// ring depths of the fused kernels (K = 64, K = 128, the two-convolution kernel)
+constexpr int BN_NSA_K64 = 8, BN_NSA_K128 = 5, BN2_NSA = 5;
+
 // tile shape for (Kc, Co): wide channel tiles take 64-pixel tiles (64 accumulator registers beside the prefetched fragments)
 void stream_shape(int Kc, int Co, int* bm, int* bn) {
     int n = Co % 256 == 0 ? 256 : Co % 128 == 0 ? 128 : 64;      // (only the instantiated widths: Co = 192 runs on 64-wide tiles)
@@ -680,11 +691,7 @@ hipError_t launch_stream(const ConvParams& p, hipStream_t stream) {
     sg.tiles_per_img = (p.Hs * p.Ws) / BM;
     sg.rows_per_tile = BM / p.Ws;
     const int NT = p.Co / BN;
-    int lanes = stream_cu_count() / NT;
-    lanes -= lanes % 8;                      // blocks b and b + 8 share an XCD: the NT channel tiles of a pixel tile meet in its L2
-    if (lanes < 8) lanes = 8;
-    if (lanes > sg.mtiles) lanes = sg.mtiles;
-    const dim3 grid(lanes, NT);
+    const dim3 grid(stream_lanes(sg.mtiles, NT), NT);
     const size_t lds = (size_t)(KC / 64) * 64 * (BN + NSA * BM) * sizeof(bf16_t);
     switch (conv_ep_mode(p)) {
         case 0: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 0>), grid, dim3(512), lds, stream, p, sg); break;
@@ -735,6 +742,12 @@ hipError_t vpd_launch_conv1x1_stream(const ConvParams& p, hipStream_t stream) {
     return hipErrorInvalidValue;
 }
 
+// host-side reporting (vpd_conv_dispatch): the tile the launcher above picks for `p` and its pixel lanes
+void vpd_conv1x1_stream_grid(const ConvParams& p, int* bm, int* bn, int* lanes) {
+    stream_shape(p.Kc, p.Co, bm, bn);
+    *lanes = stream_lanes(p.M / *bm, p.Co / *bn);
+}
+
 // ---- the closing 1x1 convolution of a Bottleneck with its BatchNorm (conv1x1_bn_stream_kernel) ----
 bool vpd_conv1x1_bn_eligible(const ConvParams& p) {
     if (!vpd_switches().bneck_recompute || !vpd_conv1x1_stream_eligible(p)) return false;
@@ -751,11 +764,7 @@ hipError_t launch_bn_stream(const ConvParams& p, const StreamBn& bn, int mode, h
     sg.tiles_per_img = (p.Hs * p.Ws) / BM;
     sg.rows_per_tile = BM / p.Ws;
     const int NT = p.Co / BN;
-    int lanes = stream_cu_count() / NT;
-    lanes -= lanes % 8;
-    if (lanes < 8) lanes = 8;
-    if (lanes > sg.mtiles) lanes = sg.mtiles;
-    const dim3 grid(lanes, NT);
+    const dim3 grid(stream_lanes(sg.mtiles, NT), NT);
     const size_t lds = (size_t)(KC / 64) * 64 * (BN + NSA * BM) * sizeof(bf16_t) + 3 * BN * sizeof(float);
     switch (mode) {
         // (four MFMA waves as the storing launch: the same pixels per lane, so the same fp32 partial sums -- the fused forward is
@@ -797,8 +806,8 @@ hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, con
             bn.dz = dz; bn.dzHp = p.Hs + 2 * dzpad; bn.dzWp = p.Ws + 2 * dzpad; bn.dzpad = dzpad;
         }
     }
-    if (p.Kc == 64) return launch_bn_stream<64, 8>(p, bn, mode, stream);
-    return launch_bn_stream<128, 5>(p, bn, mode, stream);
+    if (p.Kc == 64) return launch_bn_stream<64, BN_NSA_K64>(p, bn, mode, stream);
+    return launch_bn_stream<128, BN_NSA_K128>(p, bn, mode, stream);
 }
 
 // ---- ... of a down-sampling Bottleneck with two 64-channel stride-1 1x1 convolutions (conv1x1_bn2_stream_kernel): p.x / p.w =
@@ -838,16 +847,12 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
             bb.mean = const_cast<float*>(meanD); bb.rstd = const_cast<float*>(rstdD); bb.dz = dzD;
         }
     } else return hipErrorInvalidValue;
-    constexpr int BM = 64, BN = 256, NSA = 5;
+    constexpr int BM = 64, BN = 256, NSA = BN2_NSA;
     StreamGeo sg;
     sg.mtiles = p.M / BM;
     sg.tiles_per_img = (p.Hs * p.Ws) / BM;
     sg.rows_per_tile = BM / p.Ws;
-    int lanes = stream_cu_count();
-    lanes -= lanes % 8;
-    if (lanes < 8) lanes = 8;
-    if (lanes > sg.mtiles) lanes = sg.mtiles;
-    const dim3 grid(lanes, 1);
+    const dim3 grid(stream_lanes(sg.mtiles, 1), 1);
     const size_t lds = (size_t)2 * 64 * (BN + NSA * BM) * sizeof(bf16_t) + 6 * BN * sizeof(float);
     switch (mode) {
         case 1: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 1>), grid, dim3(768), lds, stream, p, sg, bn, bb); break;
@@ -855,4 +860,14 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
         default: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 3>), grid, dim3(768), lds, stream, p, sg, bn, bb); break;
     }
     return hipGetLastError();
+}
+
+// host-side reporting (vpd_op_conv1x1_bn_dispatch): the grid of the launches above for an eligible `p` -- pixel lanes, channel
+// tiles, pixel tiles of the busiest block, ring depth
+void vpd_conv1x1_bn_grid(const ConvParams& p, bool two, int out4[4]) {
+    const int mtiles = p.M / 64;
+    const int NT = two ? 1 : p.Co / 256;
+    const int lanes = stream_lanes(mtiles, NT);
+    out4[0] = lanes; out4[1] = NT; out4[2] = (mtiles + lanes - 1) / lanes;
+    out4[3] = two ? BN2_NSA : p.Kc == 64 ? BN_NSA_K64 : BN_NSA_K128;
 }

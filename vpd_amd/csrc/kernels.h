@@ -84,6 +84,7 @@ hipError_t vpd_launch_scale(float* x, long n, float s, hipStream_t stream);     
 // conv_stream.hip: persistent streaming kernel for 1x1 convolutions with <= 256 input channels on many pixels
 bool vpd_conv1x1_stream_eligible(const ConvParams& p);
 hipError_t vpd_launch_conv1x1_stream(const ConvParams& p, hipStream_t stream);
+void vpd_conv1x1_stream_grid(const ConvParams& p, int* bm, int* bn, int* lanes);      // (reporting: its tile and pixel lanes)
 int vpd_conv_kernel_class(const ConvParams& p);      // 0..4, see conv_igemm.hip
 bool vpd_conv_takes_bn_sums(const ConvParams& p);
 // What vpd_launch_conv does with `p` on the current device; the launcher branches on this very struct (conv_igemm.hip)
@@ -94,7 +95,7 @@ struct ConvDispatch {
     int c64x2;              // class 0: the two-group inference twin conv3x3_c64x2_persistent_kernel
     int ws1x1, stream1x1;   // class 4: conv1x1_ws_kernel (ring GEMM) / conv1x1_stream_kernel
     int halo;               // class 4: the legacy conv3x3_halo_kernel
-    int bm, bn;             // tile (pixels x channels); 0 x 0 for the streaming kernel, which picks its own
+    int bm, bn;             // tile (pixels x channels)
     int mode;               // conv_ep_mode
     int tiles_per_block;    // pixel tiles the busiest block walks
 };
@@ -170,6 +171,8 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
                                   unsigned char* mask_out, bf16_t* dz3, bf16_t* dzD, int dzpad, int mode, hipStream_t stream);
 hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd, const float* mean,
                                  const float* rstd, unsigned char* mask_out, bf16_t* dz, int dzpad, int mode, hipStream_t stream);
+// (reporting) the grid of those launches for an eligible p: {pixel lanes, channel tiles, pixel tiles of the busiest block, ring depth}
+void vpd_conv1x1_bn_grid(const ConvParams& p, bool two, int out4[4]);
 bool vpd_bn_bwd_fused_ok(int M, int C, bool mask_act, bool write_g);
 // what both fused backward launchers derive from (M, C) on this device: blocks, pixels per block, pixel iterations per thread, which
 // of g / z (/ the second z) stay in LDS across the grid barrier, dynamic LDS bytes (nt = 2: one BatchNorm, 3: the pair kernel)

@@ -24,7 +24,7 @@ int fail(const char* what, hipError_t e) {
 
 extern "C" const char* vpd_last_error(void) { return g_err.c_str(); }
 extern "C" const char* vpd_elem_dtype(void) { return VPD_ELEM_NAME; }      // "bf16" (libvpdhip.so) or "fp16" (libvpdhip_f16.so)
-extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2 (+ vpd_op_wgrad_pair, vpd_op_wgrad_pair_lds_bytes: test-only additions, no existing signature changed, number kept); 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
+extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2 (+ vpd_op_wgrad_pair, vpd_op_wgrad_pair_lds_bytes, vpd_op_conv1x1_bn, vpd_op_conv1x1_bn2, vpd_op_conv1x1_bn_dispatch: test-only additions, no existing signature changed, number kept); 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
 
 namespace {
 
@@ -929,6 +929,113 @@ extern "C" int vpd_op_bn_backward_apply(const void* dy, const void* z, const uns
     memset(&f, 0, sizeof f);
     f.rows = const_cast<double*>(rows); f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
     LCHECK(vpd_launch_bn_bwd_apply_fused(b, f, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- a Bottleneck's closing 1x1 convolution with its BatchNorm (conv_stream.hip): the launchers of step.hip's run_conv3_bn_* /
+// run_conv3d_bn_* from flat arguments.  Every refusal is the launcher's own predicate, asked before anything is launched ----
+static ConvParams op_conv1x1_bn_params(const void* x, const void* w, int n, int H, int W, int istr, int Kc, int Co) {
+    ConvParams q;
+    memset(&q, 0, sizeof q);
+    q.x = (const bf16_t*)x; q.xHp = H * istr + 2; q.xWp = W * istr + 2; q.xC = Kc; q.w = (const bf16_t*)w;
+    q.yHp = H; q.yWp = W; q.yC = Co; q.ypad = 0;
+    q.N = n; q.Hs = H; q.Ws = W; q.osub = 1; q.istr = istr;
+    q.Kc = Kc; q.Co = Co; q.M = n * H * W;
+    q.taps.nr = 1; q.taps.nc = 1; q.taps.dy0 = 1; q.taps.dys = 1; q.taps.dx0 = 1; q.taps.dxs = 1; q.taps.w0 = 0; q.taps.wrs = 1; q.taps.wcs = 1;
+    return q;
+}
+static bool op_conv1x1_bn_shape_ok(int n, int H, int W, int istr, int Kc, int Co) {
+    return n >= 1 && H >= 1 && W >= 1 && istr >= 1 && Kc >= 64 && Kc % 64 == 0 && Co >= 64 && Co % 64 == 0 &&
+           (long long)n * H * W < (1ll << 31);
+}
+
+extern "C" int vpd_op_conv1x1_bn(int mode, const void* x, const void* w, int n, int H, int W, int istr, int Kc, int Co, double* rows,
+                                 const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
+                                 float eps, float* mean, float* rstd, float* scale, float* shift, const void* res, void* out,
+                                 unsigned char* mask_bits, const void* dout, void* dz, float* dgamma, float* dbeta, void* stream) {
+    if (mode < 0 || mode > 3) return fail("mode 0 .. 3");
+    if (!x || !w || !rows) return fail("null argument");
+    if (mode == 1 && (!gamma || !beta || !mean || !rstd || !scale || !shift || !res || !out || (running_mean == nullptr) != (running_var == nullptr)))
+        return fail("null argument");
+    if (mode >= 2 && (!dout || !mask_bits)) return fail("null argument");
+    if (mode == 3 && (!gamma || !mean || !rstd || !dz || !dgamma || !dbeta)) return fail("null argument");
+    if (!op_conv1x1_bn_shape_ok(n, H, W, istr, Kc, Co)) return fail("bad argument");
+    ConvParams q = op_conv1x1_bn_params(x, w, n, H, W, istr, Kc, Co);
+    if (!vpd_conv1x1_bn_eligible(q)) return fail("conv1x1_bn_stream_kernel does not take this shape");
+    BnFusedFwd f;
+    BnFusedBwd b;
+    memset(&f, 0, sizeof f);
+    memset(&b, 0, sizeof b);
+    if (mode == 0) { q.stats = rows; q.stat_rows = VPD_FUSED_ROWS; }
+    else if (mode == 1) {
+        q.y = (bf16_t*)out; q.yHp = H + 2; q.yWp = W + 2; q.ypad = 1;
+        q.res = (const bf16_t*)res; q.rHp = H + 2; q.rWp = W + 2; q.rC = Co; q.rpad = 1;
+        f.rows = rows; f.count = (float)q.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
+        f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift; f.momentum = momentum; f.eps = eps;
+    } else {
+        q.y = (bf16_t*)const_cast<void*>(dout); q.acc_mask = mask_bits;
+        b.rows = rows; b.gamma = gamma; b.dgamma = dgamma; b.dbeta = dbeta; b.count = (float)q.M;
+    }
+    LCHECK(vpd_launch_conv1x1_bn(q, mode == 1 ? &f : nullptr, mode >= 2 ? &b : nullptr, mode == 3 ? mean : nullptr,
+                                 mode == 3 ? rstd : nullptr, mode == 1 ? mask_bits : nullptr, mode == 3 ? (bf16_t*)dz : nullptr,
+                                 mode == 3 ? 1 : 0, mode, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_conv1x1_bn2(int mode, const void* x, const void* w, const void* x2, const void* w2, int n, int H, int W, int Kc,
+                                  int Kc2, int Co, double* rows, double* rows2, const float* gamma, const float* beta,
+                                  float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
+                                  const float* gamma2, const float* beta2, float* running_mean2, float* running_var2, float* mean2,
+                                  float* rstd2, float* scale2, float* shift2, float momentum, float eps, void* out,
+                                  unsigned char* mask_bits, const void* dout, void* dz, void* dz2, float* dgamma, float* dbeta,
+                                  float* dgamma2, float* dbeta2, void* stream) {
+    if (mode < 1 || mode > 3) return fail("mode 1 .. 3");
+    if (!x || !w || !x2 || !w2 || !rows || !rows2) return fail("null argument");
+    if (mode == 1 && (!gamma || !beta || !mean || !rstd || !scale || !shift || !gamma2 || !beta2 || !mean2 || !rstd2 || !scale2 || !shift2 ||
+                      !out || (running_mean == nullptr) != (running_var == nullptr) || (running_mean == nullptr) != (running_mean2 == nullptr) ||
+                      (running_mean2 == nullptr) != (running_var2 == nullptr)))
+        return fail("null argument");
+    if (mode >= 2 && (!dout || !mask_bits)) return fail("null argument");
+    if (mode == 3 && (!gamma || !mean || !rstd || !gamma2 || !mean2 || !rstd2 || !dz || !dz2 || !dgamma || !dbeta || !dgamma2 || !dbeta2))
+        return fail("null argument");
+    if (!op_conv1x1_bn_shape_ok(n, H, W, 1, Kc, Co) || Kc2 < 1) return fail("bad argument");
+    ConvParams q = op_conv1x1_bn_params(x, w, n, H, W, 1, Kc, Co);
+    q.x2 = (const bf16_t*)x2; q.w2 = (const bf16_t*)w2; q.Kc2 = Kc2;
+    if (!vpd_conv1x1_bn2_eligible(q)) return fail("conv1x1_bn2_stream_kernel does not take this shape");
+    BnFusedFwd f;
+    BnFusedBwd b3, bd;
+    memset(&f, 0, sizeof f);
+    memset(&b3, 0, sizeof b3);
+    memset(&bd, 0, sizeof bd);
+    if (mode == 1) {
+        q.y = (bf16_t*)out; q.yHp = H + 2; q.yWp = W + 2; q.ypad = 1;
+        f.rows = rows; f.count = (float)q.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
+        f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift;
+        f.rows2 = rows2; f.count2 = (float)q.M; f.gamma2 = gamma2; f.beta2 = beta2; f.rm2 = running_mean2; f.rv2 = running_var2;
+        f.mean2 = mean2; f.rstd2 = rstd2; f.scale2 = scale2; f.shift2 = shift2;
+        f.momentum = momentum; f.eps = eps;
+    } else {
+        q.y = (bf16_t*)const_cast<void*>(dout); q.acc_mask = mask_bits;
+        b3.rows = rows; b3.gamma = gamma; b3.dgamma = dgamma; b3.dbeta = dbeta; b3.count = (float)q.M;
+        bd.rows = rows2; bd.gamma = gamma2; bd.dgamma = dgamma2; bd.dbeta = dbeta2; bd.count = (float)q.M;
+    }
+    const bool m3 = mode == 3;
+    LCHECK(vpd_launch_conv1x1_bn2(q, mode == 1 ? &f : nullptr, mode >= 2 ? &b3 : nullptr, mode >= 2 ? &bd : nullptr, m3 ? mean : nullptr,
+                                  m3 ? rstd : nullptr, m3 ? mean2 : nullptr, m3 ? rstd2 : nullptr, mode == 1 ? mask_bits : nullptr,
+                                  m3 ? (bf16_t*)dz : nullptr, m3 ? (bf16_t*)dz2 : nullptr, m3 ? 1 : 0, mode, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_conv1x1_bn_dispatch(int n, int H, int W, int Kc, int Co, int two, int* out5) {
+    if (!out5) return fail("null argument");
+    if (!op_conv1x1_bn_shape_ok(n, H, W, 1, Kc, Co)) return fail("bad argument");
+    static const double present = 0.0;      // (the predicates read pointers only as present / absent)
+    ConvParams q = op_conv1x1_bn_params(nullptr, nullptr, n, H, W, 1, Kc, Co);
+    if (two) { q.x2 = (const bf16_t*)&present; q.w2 = (const bf16_t*)&present; q.Kc2 = Kc; }
+    int v[5] = {0, 0, 0, 0, 0};
+    v[0] = two ? (int)vpd_conv1x1_bn2_eligible(q) : (int)vpd_conv1x1_bn_eligible(q);
+    if (v[0]) vpd_conv1x1_bn_grid(q, two != 0, v + 1);
+    memcpy(out5, v, sizeof v);
     return 0;
 }
 
