@@ -110,6 +110,22 @@ int vpd_forward_train(vpd_plan_t* plan, const float* params, float* bn_running, 
 int vpd_backward(vpd_plan_t* plan, const float* params, float* grads, int n, void** bucket_events,
                  void* workspace, void* stream);
 
+/* loss.backward() of models/util.py:52 for ANY loss of the embeddings: the backward pass of the graph built by the preceding
+ * vpd_forward_train (which may have been called with target == NULL) from the caller's d(loss)/d(emb) instead of the fused sum-MSE's
+ * -- what torch autograd hands to the encoder's output when the reference module is trained with a weighted, cosine or contrastive
+ * loss, reduction='mean', a head on top of the embeddings or torch's GradScaler.  The plan must be a train plan without the motion
+ * head.  d_emb: f32 [n][emb_dim], dense, on the device; it is copied into the plan's d(pred) slot and taken as it is (neither
+ * vpd_plan_set_loss_scale nor vpd_plan_set_scale_state applies: a scaled loss arrives scaled).  `grads` is overwritten as by
+ * vpd_backward; lazy gradients do not apply (a pending vpd_plan_set_lazy_grads is cleared); bucket_events as in vpd_backward.
+ * dx_nchw: NULL, or f32 [n][c_in][H][W] receiving d(loss)/d(x) (the forward's rounding of x to the element type taken as the
+ * identity) -- the stem convolution's data gradient, which training never needs; only after a forward that took an x (a batch
+ * staged by vpd_plan_stage_crops has no fp32 input).  n == 0 as in vpd_backward; dx_nchw is then not written.
+ * Fails on the host, before anything is launched, for a null plan / params / grads / d_emb / workspace, a plan with train == 0,
+ * a plan with the motion head, n outside 0..max_batch, a workspace that is not the bound one, a dx_nchw that is not 8-byte aligned
+ * and a dx_nchw after a forward that took no x. */
+int vpd_backward_ext(vpd_plan_t* plan, const float* params, float* grads, const float* d_emb, int n, float* dx_nchw,
+                     void** bucket_events, void* workspace, void* stream);
+
 /* optimizer.step() of models/util.py:53 for torch.optim.AdamW(lr) with torch defaults
  * (train_vpd_model.py:104): decoupled weight decay on every tensor. `step` is 1-based. */
 int vpd_adamw_step(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
@@ -360,6 +376,13 @@ int vpd_op_conv1x1_bn_dispatch(int n, int H, int W, int Kc, int Co, int two, int
  * when idx is given (training), the window tap r*3+t of the FIRST maximum per output element, u8 dense [n][Ho][Wo][C]. */
 int vpd_op_stem_pool_forward(const void* z, const float* scale, const float* shift, void* out_padded, unsigned char* idx,
                              int n, int Hz, int Wz, int C, int opad, void* stream);
+/* The stem convolution's data gradient (conv_stem_dgrad_kernel, the launch vpd_backward_ext makes for dx_nchw; reference: the
+ * input-gradient half of loss.backward(), models/util.py:52, through the 7x7 stride-2 padding-3 conv1 of models/module.py:58):
+ * dx = conv_transpose2d(dz, w, stride 2, padding 3, output_padding 1).  dz: element type, dense NHWC [n][H/2][W/2][64]; w_oihw: the
+ * fp32 master weight [64][c_in][7][7], rounded to the element type by the kernel (to the values vpd_pack_weights packs); dx_nchw:
+ * f32 [n][c_in][H][W], 8-byte aligned, fp32 accumulation.  Refuses null pointers, c_in outside 1..8, H or W odd or below 32, n < 1,
+ * a dx_nchw that is not 8-byte aligned. */
+int vpd_op_stem_dgrad(const void* dz, const float* w_oihw, float* dx_nchw, int n, int c_in, int H, int W, void* stream);
 /* Backward of the same through the pool, the ReLU and the train-mode BatchNorm (vpd_launch_stem_pool_bwd: sums, finalize,
  * dz): dpool dense [n][Ho][Wo][C], idx as written by the forward, dz dense like z.  pooled_padded (the forward's output,
  * opad 1) or null: with it (and VPD_STEM_POOLSUMS on) the sums are taken over the pooled positions.  rows: f64 [16][2][C],

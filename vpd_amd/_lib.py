@@ -39,6 +39,7 @@ SIGNATURES = {
     "vpd_forward_eval": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]),
     "vpd_forward_train": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]),
     "vpd_backward": (C.c_int, [vp, vp, vp, C.c_int, C.POINTER(vp), vp, vp]),
+    "vpd_backward_ext": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.POINTER(vp), vp, vp]),
     "vpd_adamw_step": (C.c_int, [vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_double, C.c_int, vp]),
     "vpd_plan_adamw_step": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -81,6 +82,7 @@ SIGNATURES = {
     "vpd_op_conv1x1_bn2": (C.c_int, [C.c_int] + [vp] * 4 + [C.c_int] * 6 + [vp] * 18 + [C.c_float, C.c_float] + [vp] * 10),
     "vpd_op_conv1x1_bn_dispatch": (C.c_int, [C.c_int] * 6 + [c_int_p]),
     "vpd_op_stem_pool_forward": (C.c_int, [vp] * 5 + [C.c_int] * 5 + [vp]),
+    "vpd_op_stem_dgrad": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     "vpd_op_stem_pool_backward": (C.c_int, [vp] * 15 + [C.c_int] * 4 + [vp]),
     "vpd_op_bn_backward": (C.c_int, [vp] * 15 + [C.c_int] + [vp, vp] + [C.c_int] * 6 + [vp]),
     "vpd_op_bn_backward_pair": (C.c_int, [vp] * 20 + [C.c_int] * 4 + [vp]),
@@ -136,7 +138,7 @@ def lib(dtype="bf16"):
             fn = getattr(h, sym)
         except AttributeError as e:
             # (an OLDER round's library, same-box A/B: the entry points added since are optional there -- engine.py asks hasattr)
-            if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale")):
+            if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext")):
                 continue
             raise VpdHipError("%s lacks symbol %s declared in include/vpd_hip.h" % (name, sym)) from e
         fn.restype = res

@@ -187,6 +187,11 @@ hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd&
 bool vpd_bn_bwd_fused2_ok(int M, int C);
 hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p, const BnFusedBwd& fA, const BnBwdSecond& B, hipStream_t s);
 
+// conv_stem_dgrad.hip: the stem convolution's data gradient, dz dense NHWC [N][H/2][W/2][64] -> dx fp32 NCHW [N][Cin][H][W]
+// (H, W even and >= 32, Cin <= 8; w_oihw: the fp32 master weight, rounded to the element type in the kernel)
+hipError_t vpd_launch_stem_dgrad(const bf16_t* dz, const float* w_oihw, float* dx_nchw, int N, int Cin, int H, int W,
+                                 hipStream_t s);
+
 // head.hip
 hipError_t vpd_launch_avgpool(const bf16_t* act, int Hp, int Wp, int pad, int H, int W, int C, int N, float* pooled,
                               hipStream_t s);

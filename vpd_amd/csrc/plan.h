@@ -119,6 +119,7 @@ struct vpd_plan {
     bool dgrad_sums = true;     // BatchNorm-backward sums in the producing data gradient's epilogue (VPD_DGRAD_SUMS=0: in the BatchNorm launch)
     bool relu_bits = true;      // block-output ReLU masks as bit maps (VPD_RELU_BITS=0: masks from the stored activation, g written back)
     bool lazy_next = false, grads_in_scratch = false;
+    bool fwd_had_x = false;     // the last vpd_forward_train took an fp32 x (vpd_backward_ext: an input gradient exists only then)
     int nstem_unpack_blocks = 0;           // leading entries of bmap_unpack[3] that belong to the stem
     bool wg_merge34 = true;     // layer4's grouped weight gradients wait for layer3's and share its launch (VPD_WG_MERGE=0, or the
                                 // data-parallel creation flag VPD_TRAIN_EARLY_BUCKET0: per stage)

@@ -1070,6 +1070,17 @@ extern "C" int vpd_op_stem_pool_backward(const void* dpool, const unsigned char*
     return 0;
 }
 
+// the stem convolution's data gradient (conv_stem_dgrad.hip): the launch vpd_backward_ext makes, from flat arguments
+extern "C" int vpd_op_stem_dgrad(const void* dz, const float* w_oihw, float* dx_nchw, int n, int c_in, int H, int W, void* stream) {
+    if (!dz || !w_oihw || !dx_nchw) return fail("null argument");
+    if (n < 1) return fail("n must be at least 1");
+    if (c_in < 1 || c_in > 8) return fail("c_in outside 1..8");
+    if (H < 32 || W < 32 || (H & 1) || (W & 1)) return fail("H and W must be even and at least 32");
+    if (reinterpret_cast<size_t>(dx_nchw) & 7) return fail("dx_nchw must be 8-byte aligned");
+    LCHECK(vpd_launch_stem_dgrad((const bf16_t*)dz, w_oihw, dx_nchw, n, c_in, H, W, (hipStream_t)stream));
+    return 0;
+}
+
 static BnBwdParams op_bn_bwd_params(void* dy, const void* z, const void* act_padded, const float* mean, const float* rstd,
                                     void* dz, int dzpad, int n, int H, int W, int C) {
     BnBwdParams b;

@@ -748,15 +748,19 @@ struct Backward {
 
     const bf16_t* block_input(int bi) const { return bi == 0 ? c.b16(c.p->p0_off) : c.b16(c.p->blocks[bi - 1].out_off); }
 
-    int head() {
+    // scaled: d(loss)/d(pred) is the fused sum-MSE's and takes the plan's loss scale (vpd_backward); the caller's own d(loss)/d(emb)
+    // of vpd_backward_ext is taken as it is
+    int head(bool scaled = true) {
         vpd_plan* p = c.p;
         const int n = c.n;
         hipStream_t s = c.s;
         const float* params = c.params;
-        if (p->scale_state)            // (fp16 training, dynamic scaler: vpd_plan_set_scale_state)
-            LCHECK(vpd_launch_scale_by_state(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->scale_state, s));
-        else if (p->loss_scale != 1.f)      // (fp16 training: vpd_plan_set_loss_scale)
-            LCHECK(vpd_launch_scale(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->loss_scale, s));
+        if (scaled) {
+            if (p->scale_state)            // (fp16 training, dynamic scaler: vpd_plan_set_scale_state)
+                LCHECK(vpd_launch_scale_by_state(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->scale_state, s));
+            else if (p->loss_scale != 1.f)      // (fp16 training: vpd_plan_set_loss_scale)
+                LCHECK(vpd_launch_scale(c.f32(p->dpred_off), (long)n * (p->motion ? 2 * p->D : p->D), p->loss_scale, s));
+        }
         const float* demb = c.f32(p->dpred_off);
         if (p->motion) {
             const LinInfo* L = p->dec;
@@ -968,6 +972,7 @@ extern "C" int vpd_forward_train(vpd_plan_t* p, const float* params, float* bn_r
         return 0;
     }
     Ctx c{p, ws, s, params, n};
+    p->fwd_had_x = x != nullptr;
     LCHECK(vpd_launch_zero_ranges(accumulator_zero_ranges(c), s));
     if (x) LCHECK(vpd_launch_pack_input(x, n, p->c_in, p->H, p->W, c.b16(p->xin_off), p->xHp, p->xWp, 3, 8, s));
     // stem: conv -> batch stats -> BN+ReLU+maxpool
@@ -1013,14 +1018,11 @@ extern "C" int vpd_forward_train(vpd_plan_t* p, const float* params, float* bn_r
     return run_head(c, cur, emb_out, target, true, loss_step, loss_accum);
 }
 
-extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, int n, void** bucket_events,
-                            void* workspace, void* stream) {
-    if (check_call(p, workspace, n, 0)) return -1;
-    if (!p->train) return fail("plan was created with train=0");
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    const bool lazy = p->lazy_next;
-    p->lazy_next = false;
+// loss.backward() for the graph of the preceding vpd_forward_train.  d_emb == null: from the fused sum-MSE's d(loss)/d(pred) in the
+// workspace (vpd_backward); else from the caller's d(loss)/d(emb) (vpd_backward_ext), with d(loss)/d(x) into dx_nchw when given
+namespace {
+int run_backward(vpd_plan* p, const float* params, float* grads, int n, void** bucket_events, char* ws, hipStream_t s, bool lazy,
+                 const float* d_emb, float* dx_nchw) {
     p->grads_in_scratch = lazy;
     if (n == 0) {      // empty shard: the gradient of a sum over no crops is zero; every bucket is "ready" at once
         // (lazy: the reducer sums the scratch ranges, and the optimizer step reads them there afterwards)
@@ -1031,6 +1033,7 @@ extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, in
         return 0;
     }
     Ctx c{p, ws, s, params, n};
+    if (d_emb) HCHECK(hipMemcpyAsync(c.f32(p->dpred_off), d_emb, (size_t)n * p->D * sizeof(float), hipMemcpyDeviceToDevice, s));
     // one launch zeroes the accumulator rows and every weight-gradient range the atomics kernel will add into
     ZeroRanges zr = accumulator_zero_ranges(c);
     auto dry = [&](const ConvInfo& cv) { (void)run_conv_wgrad(c, cv, nullptr, nullptr, &zr); };
@@ -1043,10 +1046,38 @@ extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, in
     LCHECK(vpd_launch_zero_ranges(zr, s));
 
     Backward bw(c, grads, bucket_events, lazy);
-    if (bw.head()) return -1;
+    if (bw.head(!d_emb)) return -1;
     for (int bi = (int)p->blocks.size() - 1; bi >= 0; --bi)
         if (p->bottleneck ? bw.bottleneck_block(bi) : bw.basic_block(bi)) return -1;
-    return bw.stem();
+    if (bw.stem()) return -1;
+    // the one data gradient training never needs: d(loss)/d(x) from the stem's dz (conv_stem_dgrad.hip)
+    if (dx_nchw)
+        LCHECK(vpd_launch_stem_dgrad(c.b16(p->dz0_off), params + p->stem.w_off, dx_nchw, n, p->c_in, p->H, p->W, s));
+    return 0;
+}
+}  // namespace
+
+extern "C" int vpd_backward(vpd_plan_t* p, const float* params, float* grads, int n, void** bucket_events,
+                            void* workspace, void* stream) {
+    if (check_call(p, workspace, n, 0)) return -1;
+    if (!p->train) return fail("plan was created with train=0");
+    const bool lazy = p->lazy_next;
+    p->lazy_next = false;
+    return run_backward(p, params, grads, n, bucket_events, (char*)workspace, (hipStream_t)stream, lazy, nullptr, nullptr);
+}
+
+extern "C" int vpd_backward_ext(vpd_plan_t* p, const float* params, float* grads, const float* d_emb, int n, float* dx_nchw,
+                                void** bucket_events, void* workspace, void* stream) {
+    if (!p || !params || !grads || !d_emb || !workspace) return fail("vpd_backward_ext: null plan / params / grads / d_emb / workspace");
+    if (!p->train) return fail("plan was created with train=0");
+    if (p->motion) return fail("vpd_backward_ext: the plan has the motion head (d_emb is the gradient of the encoder's output)");
+    if (n < 0 || n > p->max_batch) return fail("batch size outside 0..max_batch");
+    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
+    if (dx_nchw && (reinterpret_cast<size_t>(dx_nchw) & 7)) return fail("vpd_backward_ext: dx_nchw must be 8-byte aligned");
+    if (dx_nchw && !p->fwd_had_x)
+        return fail("vpd_backward_ext: dx_nchw needs a forward that took x (a batch staged by vpd_plan_stage_crops has no fp32 input)");
+    p->lazy_next = false;      // lazy gradients belong to the fused step
+    return run_backward(p, params, grads, n, bucket_events, (char*)workspace, (hipStream_t)stream, false, d_emb, dx_nchw);
 }
 
 extern "C" int vpd_graph_capture_eval(vpd_plan_t* p, const float* params, const float* x, int n, float* emb_out,

@@ -98,6 +98,10 @@ class _Plan:
             self.buckets.append((o.value, m.value))
         self.packed_version = None
         self.graph_sizes = set()
+        # a train plan holds ONE forward's activations: every train-mode forward bumps `fwd_count`, an autograd backward checks
+        # the count its forward saw and marks it consumed (StudentEngine.backward_ext)
+        self.fwd_count = 0
+        self.consumed = None
         # lazy gradients under data parallelism: bucket b's conv weight gradients as a view of the workspace (the kernels' own
         # layout), and the flat-buffer positions of everything else (BatchNorm, fc, motion head, the stem conv)
         self.scratch_views, self.small_idx = [], None
@@ -187,6 +191,11 @@ class StudentEngine:
         self._last = None              # (plan, n) of the last train forward, consumed by backward
         self._step_plan = None         # plan of the last backward: its packed weights are refreshed by adamw_step
         self.bucket_events = None
+        # the autograd path (models/rgb.py, backward_ext): torch's accumulate semantics of .grad on top of kernels that overwrite
+        self._last_fwd = None          # (plan, n, forward count, took an fp32 x) of the last train forward
+        self._grads_cleared = True     # nothing to add onto: the flat buffer is fresh, or an optimizer's zero_grad() said so
+        self._grads2 = None            # second flat buffer an accumulating backward writes before it is added (first use)
+        self.stem_dgrad_launches = 0   # input gradients asked for (conv_stem_dgrad_kernel launches)
 
     # -- helpers -------------------------------------------------------------
     @property
@@ -357,6 +366,8 @@ class StudentEngine:
         if n > 0:
             self._nbt_pending += 1
         self._last = (pl, n) if target is not None else None
+        pl.fwd_count += 1
+        self._last_fwd = (pl, n, pl.fwd_count, x is not None)
         return emb
 
     def backward(self, events=None, lazy=False):
@@ -381,7 +392,61 @@ class StudentEngine:
             self.check(self.L.vpd_plan_set_lazy_grads(pl.handle, 1), "vpd_plan_set_lazy_grads")
         self.check(self.L.vpd_backward(pl.handle, _ptr(self.params), _ptr(self._grads), n, ev, _ptr(pl.workspace),
                                  self._stream()), "vpd_backward")
+        pl.consumed = pl.fwd_count
+        self._grads_cleared = False        # (an autograd backward that follows without a zero_grad() adds onto these)
         return pl
+
+    def backward_ext(self, d_emb, want_dx=False, ticket=None, accumulate=False, discard=False):
+        """loss.backward() from the caller's d(loss)/d(emb) (vpd_backward_ext) through the activations of a train-mode forward of
+        the plan WITHOUT the motion head -- `ticket`: what `_last_fwd` held right after that forward (default: the last one).
+        d_emb: f32 [n, emb_dim] on the engine's device, contiguous; no loss scale is passed (a scaled loss arrives scaled).
+        accumulate: add onto the flat gradient buffer instead of overwriting it (backward into a second buffer + one add);
+        discard: leave the flat buffer alone (no parameter asks for a gradient).  want_dx: also return d(loss)/d(x), f32
+        [n, c_in, H, W] (the stem convolution's data gradient; only after a forward that took x).  Returns dx or None.
+        Raises RuntimeError when a later train-mode forward overwrote the activations, and on a second backward through the same
+        forward (the pass consumes them: retain_graph does not apply)."""
+        if ticket is None:
+            ticket = self._last_fwd
+        if ticket is None:
+            raise RuntimeError("backward_ext() without a preceding train-mode forward")
+        pl, n, count, had_x = ticket
+        if pl.motion:
+            raise RuntimeError("backward_ext() differentiates the encoder: the forward must be forward_train(..., motion=False)")
+        if pl.handle is None or pl.fwd_count != count:
+            raise RuntimeError("a later train-mode forward overwrote the activations of this forward (a train plan holds one "
+                               "forward's activations): call backward() before the next train-mode forward")
+        if pl.consumed == count:
+            raise RuntimeError("backward through this forward ran already: the pass consumes the plan's activations "
+                               "(retain_graph=True does not apply; run the forward again)")
+        assert isinstance(d_emb, torch.Tensor) and tuple(d_emb.shape) == (n, self.emb_dim), \
+            "d_emb must be f32 [%d, %d], got %s" % (n, self.emb_dim, tuple(getattr(d_emb, "shape", ())))
+        assert d_emb.dtype == torch.float32 and d_emb.device == self.params.device and d_emb.is_contiguous(), \
+            "d_emb must be a contiguous float32 tensor on %s" % (self.params.device,)
+        if want_dx and not had_x:
+            raise RuntimeError("no input gradient for a batch staged on the device (stage_crops): the forward took no fp32 x")
+        self.materialize_grads()           # a pending lazy backward (of the fused step) completes the flat buffer first
+        self._last = None                  # the fused backward() of the same forward would find its activations consumed
+        pl.consumed = count
+        into = self._grads
+        if accumulate or discard:
+            if self._grads2 is None:
+                self._grads2 = torch.zeros_like(self._grads)
+            into = self._grads2
+        dx = None
+        if want_dx and n > 0:
+            dx = torch.empty((n, self.c_in, pl.h, pl.w), dtype=torch.float32, device=self.device)
+            self.stem_dgrad_launches += 1
+        elif want_dx:
+            dx = torch.zeros((0, self.c_in, pl.h, pl.w), dtype=torch.float32, device=self.device)
+        self.check(self.L.vpd_backward_ext(pl.handle, _ptr(self.params), _ptr(into), _ptr(d_emb), n,
+                                           _ptr(dx) if n > 0 else None, None, _ptr(pl.workspace), self._stream()),
+                   "vpd_backward_ext")
+        if not discard:
+            self._step_plan = pl
+            if accumulate:
+                self._grads.add_(self._grads2)
+            self._grads_cleared = False
+        return dx
 
     def unscale_grads_(self):
         """LossScaler.step() for an optimizer that reads p.grad: the flat gradient buffer (completed first) x 1 / loss scale."""

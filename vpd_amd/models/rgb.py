@@ -47,6 +47,26 @@ def find_imagenet_weights(model_arch):
                             "checkpoint (or to a directory holding %s-*.pth)" % (model_arch, model_arch))
 
 
+class _StudentFunction(torch.autograd.Function):
+    """The train-mode encoder as one autograd node: forward = StudentEngine.forward_train(x, None, motion=False), backward =
+    StudentEngine.backward_ext (vpd_backward_ext) from autograd's d(loss)/d(emb).  The parameters are inputs so that the output
+    requires grad whatever x does; their gradients are not returned but written into the engine's flat buffer, which every
+    parameter's .grad aliases -- added onto it or overwriting it by torch's rule (RGBF_EmbeddingModel._autograd_backward)."""
+
+    @staticmethod
+    def forward(ctx, model, x, *params):
+        eng = model.engine
+        emb = eng.forward_train(x, None, motion=False)
+        ctx.model, ctx.ticket, ctx.nparams = model, eng._last_fwd, len(params)
+        return emb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_emb):
+        dx = ctx.model._autograd_backward(ctx.ticket, d_emb, ctx.needs_input_grad[1])
+        return (None, dx) + (None,) * ctx.nparams
+
+
 class RGBF_EmbeddingModel(nn.Module):
     """Basic embedding model with single frame features (HIP / MI355X)."""
 
@@ -176,14 +196,56 @@ class RGBF_EmbeddingModel(nn.Module):
                                "the HIP student must stay on its GPU")
 
     def forward(self, x):
-        """f32 [N,C,H,W] on the GPU -> f32 [N,emb_dim].  Train mode uses batch statistics and
-        updates the running ones (nn.BatchNorm2d semantics); gradients flow only through
-        ModelTrainer.epoch's fused step, not through torch autograd."""
+        """f32 [N,C,H,W] on the GPU -> f32 [N,emb_dim].  Train mode uses batch statistics and updates the running ones
+        (nn.BatchNorm2d semantics).
+
+        In train mode, with torch.is_grad_enabled() and a parameter or x requiring grad, the result is part of torch's autograd
+        graph like the reference module's (models/rgb.py:68-70): any loss of the embeddings -- a weighted or cosine distillation
+        term, reduction='mean', a torch head on top, torch.amp.GradScaler -- trains the student through loss.backward() and any
+        torch optimizer over parameters().  The backward pass is the library's (vpd_backward_ext) from autograd's d(loss)/d(emb);
+        the parameters' gradients land in the engine's flat buffer that every .grad aliases, with torch's semantics: added onto
+        .grad when it exists and was not cleared since the last backward (gradient accumulation over micro-batches), overwriting
+        it after zero_grad() -- set_to_none or FusedAdamW's; the rule holds for the module as a whole, and a backward onto a mix
+        of dropped and kept .grad raises -- and x.grad is produced when x.requires_grad (the stem
+        convolution's data gradient; otherwise that kernel is not launched).
+
+        A train plan holds ONE forward's activations.  backward() through a forward after a later train-mode forward of the
+        same image size ran raises RuntimeError, and so does a second backward through the same forward (retain_graph=True
+        included).  ModelTrainer.epoch's fused step (forward + sum-MSE + backward + AdamW without torch in between) does not go
+        through here and stays the fast path.
+
+        Out of scope: eval-mode differentiability (frozen BatchNorm: the output has no grad_fn, as under torch.no_grad());
+        double backward; FCNet as a differentiable module (put a torch head on the embeddings); data parallelism through this
+        path (ModelTrainer owns the gradient reducer)."""
         self._check_storage()
         x = x.to(self.engine.device, dtype=torch.float32).contiguous()
         if self.training:
+            if torch.is_grad_enabled():
+                params = [p for p in self.parameters() if p.requires_grad]
+                if params or x.requires_grad:
+                    return _StudentFunction.apply(self, x, *params)
             return self.engine.forward_train(x, None, motion=False)
         return self.engine.forward_eval(x)
+
+    def _autograd_backward(self, ticket, d_emb, want_dx):
+        """_StudentFunction.backward: torch's accumulate rule for .grad on top of a backward pass that overwrites.  A parameter
+        whose .grad was dropped (zero_grad(set_to_none=True)) gets its view of the flat buffer back, as
+        ModelTrainer._reattach_grads does, and the pass overwrites; so it does after FusedAdamW.zero_grad(); otherwise it adds."""
+        eng = self.engine
+        names = [k for k in eng.enc_names if self.get_parameter(k).requires_grad]
+        dropped = [k for k in names if self.get_parameter(k).grad is None]
+        if dropped and len(dropped) != len(names):
+            # one pass writes ONE flat buffer: it adds onto all of it or overwrites all of it
+            raise RuntimeError("some parameters' .grad were dropped and others kept (%s is None, %s is not): clear the module's "
+                               "gradients as a whole (zero_grad) -- the backward pass adds onto all of them or overwrites all of them"
+                               % (dropped[0], next(k for k in names if k not in dropped)))
+        if not d_emb.is_contiguous() or d_emb.dtype != torch.float32:
+            d_emb = d_emb.to(torch.float32).contiguous()
+        dx = eng.backward_ext(d_emb, want_dx, ticket, accumulate=bool(names) and not dropped and not eng._grads_cleared,
+                              discard=not names)
+        for k in dropped:
+            self.get_parameter(k).grad = eng.view(k, eng._grads)
+        return dx
 
     def embed(self, x):
         if not isinstance(x, torch.Tensor):

@@ -52,8 +52,10 @@ class FusedAdamW(torch.optim.Optimizer):
         self._engine.adamw_step(g["lr"], g["betas"], g["eps"], g["weight_decay"], numel=self._numel)
 
     def zero_grad(self, set_to_none=False):
-        # gradients live in the engine's flat buffer and are overwritten (not accumulated)
-        # by the next backward, which is what zero_grad-after-every-step amounts to
+        # gradients live in the engine's flat buffer and are overwritten (not accumulated) by the next fused backward, which is
+        # what zero_grad-after-every-step amounts to: no memory is touched.  The autograd path (RGBF_EmbeddingModel.forward)
+        # accumulates as torch does: it is told here that the buffer counts as cleared
+        self._engine._grads_cleared = True
         return None
 
 
