@@ -26,11 +26,14 @@ REL_TOL = 4e-3               # the whole-tensor gate of tests/test_ops_gpu.py, k
 
 # run id -> (case of opref.CONV_CASES, environment, expected dispatch of the forward launch, of the data-gradient launch or None
 # for "the same").  tiles: pixel tiles of the busiest block; nsa: stages of the kernel's LDS ring, which `tiles` must exceed (a stage
-# is overwritten from a block's (nsa + 1)-th tile on).  Expectations hold for a 256-CU device.
+# is overwritten from a block's (nsa + 1)-th tile on); c64x2_tiles: tiles per block of the eval epilogue's c64x2 launch, 1 when not
+# given.  Expectations hold for a 256-CU device.
 FEW = {"VPD_RESERVE_CUS": "248"}       # a budget of 8 CUs: 8 pixel lanes, so a small tensor gives every block a long walk
+WALK = {"VPD_RESERVE_CUS": "240"}      # 16 CUs: the resident-weight kernels reuse each halo buffer 16 times (8 CUs: c0_w32's sums leave 2^24)
 RUNS = {
     "c0_w32-device":        ("c0_w32", {}, dict(kclass=0, bm=128, bn=64, tiles=2), None),
     "c0_w16-device":        ("c0_w16", {}, dict(kclass=0, bm=128, bn=64, tiles=2), None),
+    "c0_w32_walk-walk":     ("c0_w32_walk", WALK, dict(kclass=0, bm=128, bn=64, tiles=32, c64x2_tiles=16), None),
     "c1_w16-ws":            ("c1_w16", {"VPD_PWS": "0"}, dict(kclass=1, pws=0, bm=256, bn=128, tiles=1), None),
     "c1_w16-few_blocks":    ("c1_w16", {"VPD_PWS_BLOCKS": "24"}, dict(kclass=1, pws=1, geo=0, bm=256, bn=128, tiles=9), None),
     "c1_w16_device-device": ("c1_w16_device", {}, dict(kclass=1, pws=1, geo=0, bm=256, bn=128, tiles=2), None),
@@ -61,6 +64,7 @@ RUNS = {
     # (its data gradient, 128 -> 512 channels on 51,200 pixels, is conv1x1_stream_kernel's: tests/test_ops_gpu.py has that kernel's cases)
     "stem_w128-device":     ("stem_w128", {}, dict(kclass=5, bm=128, bn=64, tiles=2), None),
     "stem_w32-device":      ("stem_w32", {}, dict(kclass=5, bm=128, bn=64, tiles=1), None),
+    "stem_w128_walk-walk":  ("stem_w128_walk", WALK, dict(kclass=5, bm=128, bn=64, tiles=32), None),
     "ring_1x1-device":      ("ring_1x1", {}, dict(kclass=4, ws1x1=1, bm=256, bn=128), dict(kclass=4, ws1x1=0, stream1x1=1)),
     # conv1x1_stream_kernel<KC, BM, BN, NSA>: every instantiation of the launcher's table on a ring that wraps (8 CUs), forward and
     # data gradient with their accumulate / eval epilogues; the last run on the whole device
@@ -377,8 +381,11 @@ def check_dispatch(run, table, fail):
     for op, d in table.items():
         exp = exp_f if op in ("fwd", "fwd_plain", "fwd_padded", "ep") else exp_d
         if d["c64x2"]:
-            exp = dict(kclass=0, bm=256, bn=64, tiles=1)  # the inference twin: 256-pixel tiles, one per block at 256 x 256 pixels
+            # the inference twin: 256-pixel tiles, one per block at 256 x 256 pixels
+            exp = dict(kclass=0, bm=256, bn=64, tiles=exp_f.get("c64x2_tiles", 1))
         for key, val in exp.items():
+            if key == "c64x2_tiles":
+                continue
             if key == "nsa":
                 if d["tiles"] <= val:
                     fail.append("dispatch of %s: %d tiles per block do not wrap a ring of %d stages (%r)" % (op, d["tiles"], val, d))

@@ -326,6 +326,8 @@ def mse_int_operands(n, g):
 CONV_CASES = {
     "c0_w32":        dict(n=64,  ci=64,  co=64,  h=32, w=32, blk_px=2 * 128, wgrad="no_group"),   # layer1's rows: 512 tiles, two per block; eval: 256 tiles of c64x2
     "c0_w16":        dict(n=203, ci=64,  co=64,  h=16, w=16, blk_px=2 * 128),       # 406 tiles of half an image
+    # c0_w32 again for a budget of 16 CUs (VPD_RESERVE_CUS=240): 32 tiles per block (eval: 16 of c64x2), every halo buffer reused
+    "c0_w32_walk":   dict(n=64,  ci=64,  co=64,  h=32, w=32, blk_px=32 * 128, wgrad="no_group"),
     "c1_w16":        dict(n=203, ci=128, co=128, h=16, w=16, blk_px=9 * 256),       # 203 tiles of one image each: 256 x 128 with VPD_PWS=0 or few blocks
     "c1_w16_device": dict(n=300, ci=128, co=128, h=16, w=16, blk_px=2 * 256),       # 300 > 256 tiles: the eight-wave persistent kernel, two tiles per block
     "c6_w16":        dict(n=150, ci=128, co=128, h=16, w=16, blk_px=7 * 256, wgrad=True),  # 150 < 200 tiles of 256 x 128: 256 x 64, 128 lanes x 2 channel tiles
@@ -344,6 +346,7 @@ CONV_CASES = {
     # output rows, two per block; and a 32 x 32 input (eight output rows per tile)
     "stem_w128":     dict(n=16,  ci=5,   co=64,  h=128, w=128, k=7, stride=2, stem=True, blk_px=2 * 128),
     "stem_w32":      dict(n=6,   ci=5,   co=64,  h=32, w=32, k=7, stride=2, stem=True, blk_px=128),
+    "stem_w128_walk": dict(n=16, ci=5,   co=64,  h=128, w=128, k=7, stride=2, stem=True, blk_px=32 * 128),   # 16 CUs: 32 tiles per block
     # 1x1 ring GEMM (conv1x1_ws_kernel): K = 512, 200 tiles of 256 x 128
     "ring_1x1":      dict(n=50,  ci=512, co=128, h=32, w=32, k=1, blk_px=256),
     # 1x1 streaming kernel (conv1x1_stream_kernel).  st_*: sized for a budget of 8 CUs (VPD_RESERVE_CUS=248: 8 pixel lanes, eligible

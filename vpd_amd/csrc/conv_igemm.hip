@@ -22,6 +22,14 @@
 #include "conv_epilogue.h"
 #include "kernels.h"
 
+template <int NI, int MI>
+static __device__ __forceinline__ void zero_acc(f32x4 (&acc)[NI][MI]) {
+#pragma unroll
+    for (int a = 0; a < NI; ++a)
+#pragma unroll
+        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 template <int BM, int BN, int WM, int WN, int EPM>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0) {
     static_assert(WM * WN == 4, "4 waves");
@@ -131,10 +139,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0)
     };
 
     f32x4 acc[NI][MI];
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     load_step(0);
     store_step(0);
@@ -263,10 +268,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvParams p, c
     };
 
     f32x4 acc[NI][MI];
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     const int nchunks = Ci >> 6;
     const int nsteps = nchunks * 9;
@@ -456,10 +458,7 @@ __global__ __launch_bounds__((NMW + 4) * 64, WPS) void conv3x3_ws_kernel(const C
         hbase[b] = hrow * Wp + xx;
     }
     f32x4 acc[NI][MI];
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     int s = 0;
     auto tap_body = [&](int tap, const bf16_t* cH) __attribute__((always_inline)) {
@@ -530,6 +529,118 @@ __global__ __launch_bounds__((NMW + 4) * 64, WPS) void conv3x3_ws_kernel(const C
 }
 
 // ---------------------------------------------------------------------------
+// Shared pieces of the resident-weight kernels below (layer1's two, the stem): all weight taps stay in LDS, the four loader
+// waves stage the next tile's input while the MFMA waves run the current tile out of LDS, one barrier per tile.
+// ---------------------------------------------------------------------------
+// Resident weights: tap t (in K-loop order) is weight slice slice(t), [64 rows][64 channels] at sW + t * 64 * 64 (loader wave lw)
+template <int TAPS, class SliceF>
+static __device__ __forceinline__ void resident_weights_load(const bf16_t* w, bf16_t* sW, int lw, int lane, SliceF slice) {
+    const int piece = lane & 7, lrow = lane >> 3;
+#pragma unroll
+    for (int t = 0; t < TAPS; ++t) {
+        const int wsl = slice(t);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int n = (lw + 4 * i) * 8 + lrow;
+            const bf16_t* src = w + ((size_t)wsl * 64 + n) * 64 + ((piece ^ (n & 7)) << 3);
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sW + t * 64 * 64 + (lw + 4 * i) * 8 * 64), 16, 0, 0);
+        }
+    }
+}
+
+// K loop of a tile for ONE MFMA wave per SIMD and no barrier inside a tile: nothing hides an LDS round trip except this wave's own
+// MFMAs.  Two fragment sets; half-step st+1's six ds_read_b128 are issued between the eight MFMAs of half-step st (hipcc left to
+// itself re-uses one set and waits for each pair of reads right before the MFMA that needs it: ~150 exposed cycles per 128 cycles
+// of matrix work).  ldone(st, set, i) reads fragment i of half-step st into a set: 0 -> af[0], 1 -> bfm[0], 2 -> bfm[1],
+// 3.. -> af[1..] (the order the MFMAs below first need them).
+template <int NSTEP, class LdF>
+static __device__ __forceinline__ void mfma_ksteps_pinned(f32x4 (&acc)[4][2], bf16x8 (&af)[2][4], bf16x8 (&bfm)[2][2], LdF ldone) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ldone(0, 0, i);
+#pragma unroll
+    for (int st = 0; st < NSTEP; ++st) {
+        const int cur = st & 1, nxt = cur ^ 1;
+        const bool more = st + 1 < NSTEP;
+#define PINNED_MFMA(a, b) acc[a][b] = VPD_MFMA16(af[cur][a], bfm[cur][b], acc[a][b])
+        // source order pinned by scheduling barriers: the next half-step's reads leave in pairs behind the first three MFMAs
+        PINNED_MFMA(0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) { ldone(st + 1, nxt, 0); ldone(st + 1, nxt, 1); }
+        __builtin_amdgcn_sched_barrier(0);
+        PINNED_MFMA(0, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) { ldone(st + 1, nxt, 2); ldone(st + 1, nxt, 3); }
+        __builtin_amdgcn_sched_barrier(0);
+        PINNED_MFMA(1, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) { ldone(st + 1, nxt, 4); ldone(st + 1, nxt, 5); }
+        __builtin_amdgcn_sched_barrier(0);
+        PINNED_MFMA(1, 1); PINNED_MFMA(2, 0); PINNED_MFMA(2, 1); PINNED_MFMA(3, 0); PINNED_MFMA(3, 1);
+        __builtin_amdgcn_sched_barrier(0);
+#undef PINNED_MFMA
+    }
+}
+
+// Tiles of a block of the layer1 kernels: `per` CONSECUTIVE ones (round 4).  Vertically adjacent 128-pixel tiles share two of their
+// six halo rows, and walked by one block the second read of those rows hits the XCD's L2 a few microseconds after the first;
+// strided over the grid the neighbours run at the same time on other XCDs and both reads go out to memory (1.6 x the activation
+// bytes instead of ~1.1 x).
+struct TileWalk {
+    int tbeg, tend;
+    __device__ TileWalk(int per, int ntiles) : tbeg(blockIdx.x * per), tend(tbeg + per < ntiles ? tbeg + per : ntiles) {}
+};
+
+// Halo of tile `mtile` of the layer1 kernels into dst: NINSTR LDS-DMA instructions of 8 pixels x 64 channels, dealt over the four
+// loader waves (instruction k = lw + 4 * pass)
+template <int NINSTR>
+static __device__ __forceinline__ void c64_halo_issue(const ConvParams& p, const HaloGeom& g, bf16_t* dst, int mtile, int lw, int lane) {
+    const int H = p.Hs, Wp = p.Ws + 2;
+    const int piece = lane & 7, lrow = lane >> 3;
+    const int gr0 = mtile * g.TR;
+    int prow0;
+    if (g.multi) prow0 = (gr0 / H) * (H + 2);
+    else { const int b = gr0 / H; prow0 = b * (H + 2) + (gr0 - b * H); }
+    const int gp0 = prow0 * Wp;
+#pragma unroll
+    for (int pass = 0; pass < (NINSTR + 3) / 4; ++pass) {
+        const int k = lw + 4 * pass;
+        if (NINSTR % 4 != 0 && k >= NINSTR) continue;
+        const int hp = k * 8 + lrow;
+        // halo pixel hp = (row hr, column xp) of the padded tile keeps its 16-byte pieces XOR-ed with the COLUMN's low bits
+        // (HaloGeom::kmask; 16-pixel fragments lie inside one image row here): the MFMA waves' fragment addresses then
+        // split into a per-lane constant per tap column and a wave-uniform term (c64_frag_offsets)
+        const int hr = vpd_fdiv(hp, g.rWp);
+        const int key = (hp - hr * Wp) & 7;
+        int gp = gp0 + hp;
+        gp = gp < g.total_pix ? gp : g.total_pix - 1;
+        const bf16_t* src = p.x + (size_t)gp * 64 + ((piece ^ key) << 3);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + k * 8 * 64), 16, 0, 0);
+    }
+}
+
+// Fragment offsets of an MFMA wave of the layer1 kernels whose 32 pixels start at pixel m0 of the tile.
+// lo[ic][b]: pixel-fragment LDS byte offset inside a halo buffer for tap column ic (K-half 0; K-half 1 = ^ 64).  With the
+// column-keyed swizzle the lane-dependent part is tap-ROW independent, so a tap's address is lo[ic][b] + (wave-uniform row term) --
+// one VALU add instead of five per fragment (the LDS pipe and issue slots, not the MFMAs, bound these kernels).
+// Returns the weight-fragment byte offset inside a tap's [64][64] tile (row fr, K-half 0; rows a * 16 + fr: + a * 2048).
+template <int MI>
+static __device__ __forceinline__ unsigned c64_frag_offsets(const ConvParams& p, const HaloGeom& g, int m0, int lane, unsigned (&lo)[3][MI]) {
+    const int W = p.Ws, H = p.Hs, Wp = W + 2;
+    const int fr = lane & 15, fq = lane >> 4;
+#pragma unroll
+    for (int b = 0; b < MI; ++b) {
+        const int m = m0 + b * 16 + fr;
+        const int lr = m / W;
+        const int xx = m - lr * W;
+        const int hrow = g.multi ? (lr / H) * (H + 2) + (lr % H) : lr;
+#pragma unroll
+        for (int ic = 0; ic < 3; ++ic)
+            lo[ic][b] = (unsigned)((hrow * Wp + xx) * 128) + ((((unsigned)(xx + p.taps.dx0 + ic * p.taps.dxs) & 7u) ^ (unsigned)fq) << 4);
+    }
+    return (unsigned)(fr * 128 + ((fq ^ (fr & 7)) << 4));
+}
+
+// ---------------------------------------------------------------------------
 // Persistent 64 -> 64 channel 3x3 stride-1 convolution (ResNet layer1, forward and data-gradient).
 // K is only 576, so a per-tile block would spend most of its life re-streaming the 73.7 KB of weights and
 // in prologue / epilogue latency.  Here one block per CU keeps ALL NINE weight taps resident in LDS and
@@ -543,7 +654,6 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
     constexpr int WTM = BM / WM;
     constexpr int MI = WTM / 16, NI = 4;
     constexpr int HBUF = HROWS * 64;
-    constexpr int HPASS = HROWS / 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     bf16_t* sW = reinterpret_cast<bf16_t*>(smem);                 // [9][64*64] resident weights
     bf16_t* sH = sW + 9 * BN * 64;                                // [2][HBUF]
@@ -553,57 +663,20 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int W = p.Ws, H = p.Hs, Wp = W + 2;
-    // Tile walk of a block.  per > 0: `per` CONSECUTIVE tiles (round 4) -- vertically adjacent 128-pixel tiles share two of their
-    // six halo rows, and walked by one block the second read of those rows hits the XCD's L2 a few microseconds after the first;
-    // strided over the grid (per == 0: tiles b, b + G, ...) the neighbours run at the same time on other XCDs and both
-    // reads go out to memory (1.6 x the activation bytes instead of ~1.1 x).
-    const int G = per > 0 ? 1 : gridDim.x;
-    const int tbeg = per > 0 ? blockIdx.x * per : blockIdx.x;
-    const int tend = per > 0 ? (tbeg + per < ntiles ? tbeg + per : ntiles) : ntiles;
+    const int Wp = p.Ws + 2;
+    const TileWalk tw(per, ntiles);
 
     if (wave >= 4) {
         const int lw = wave - 4;
-        const int piece = lane & 7;
-        const int lrow = lane >> 3;
-        const float rWp = g.rWp;
-        auto issue_halo = [&](int mtile, int buf) __attribute__((always_inline)) {
-            const int gr0 = mtile * g.TR;
-            int prow0;
-            if (g.multi) prow0 = (gr0 / H) * (H + 2);
-            else { const int b = gr0 / H; prow0 = b * (H + 2) + (gr0 - b * H); }
-            const int gp0 = prow0 * Wp;
-#pragma unroll
-            for (int k = 0; k < HPASS; ++k) {
-                const int hp = (lw + 4 * k) * 8 + lrow;
-                // halo pixel hp = (row hr, column xp) of the padded tile keeps its 16-byte pieces XOR-ed with the COLUMN's low bits
-                // (HaloGeom::kmask; 16-pixel fragments lie inside one image row here): the MFMA waves' fragment addresses then
-                // split into a per-lane constant per tap column and a wave-uniform term (see `lo` below)
-                const int hr = vpd_fdiv(hp, rWp);
-                const int key = (hp - hr * Wp) & 7;
-                int gp = gp0 + hp;
-                gp = gp < g.total_pix ? gp : g.total_pix - 1;
-                const bf16_t* src = p.x + (size_t)gp * 64 + ((piece ^ key) << 3);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sH + buf * HBUF + (lw + 4 * k) * 8 * 64), 16, 0, 0);
-            }
-        };
-        // resident weights: tap t (in loop order) -> slice w0 + ir*wrs + ic*wcs, rows n, 64 channels
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int wsl = p.taps.w0 + (t / 3) * p.taps.wrs + (t % 3) * p.taps.wcs;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int n = (lw + 4 * i) * 8 + lrow;
-                const bf16_t* src = p.w + ((size_t)wsl * 64 + n) * 64 + ((piece ^ (n & 7)) << 3);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sW + t * BN * 64 + (lw + 4 * i) * 8 * 64), 16, 0, 0);
-            }
-        }
-        if (tbeg < tend) issue_halo(tbeg, 0);
+        resident_weights_load<9>(p.w, sW, lw, lane, [&](int t) __attribute__((always_inline)) {
+            return p.taps.w0 + (t / 3) * p.taps.wrs + (t % 3) * p.taps.wcs; });
+        if (tw.tbeg < tw.tend) c64_halo_issue<HROWS / 8>(p, g, sH, tw.tbeg, lw, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                             // B_0
         int i = 0;
-        for (int t = tbeg; t < tend; t += G, ++i) {
-            if (t + G < tend && !VPD_ABL(p, 4)) issue_halo(t + G, (i + 1) & 1);   // buffer last read in tile i-1, finished before B_i
+        for (int t = tw.tbeg; t < tw.tend; ++t, ++i) {
+            // buffer last read in tile i-1, finished before B_i
+            if (t + 1 < tw.tend && !VPD_ABL(p, 4)) c64_halo_issue<HROWS / 8>(p, g, sH + ((i + 1) & 1) * HBUF, t + 1, lw, lane);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                         // B_{i+1}
         }
@@ -612,24 +685,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
     }
 
     const int wm = wave;                                          // WN == 1
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
-    // pixel-fragment LDS byte offsets inside a halo buffer for tap column ic (K-half 0; K-half 1 = ^ 64): with the column-keyed
-    // swizzle the lane-dependent part is tap-ROW independent, so a tap's address is lo[ic][b] + (wave-uniform row term) -- one
-    // VALU add instead of five per fragment (this kernel's LDS pipe and issue slots, not its MFMAs, bound it)
     unsigned lo[3][MI];
-#pragma unroll
-    for (int b = 0; b < MI; ++b) {
-        const int m = wm * WTM + b * 16 + fr;
-        const int lr = m / W;
-        const int xx = m - lr * W;
-        const int hrow = g.multi ? (lr / H) * (H + 2) + (lr % H) : lr;
-#pragma unroll
-        for (int ic = 0; ic < 3; ++ic)
-            lo[ic][b] = (unsigned)((hrow * Wp + xx) * 128) + ((((unsigned)(xx + p.taps.dx0 + ic * p.taps.dxs) & 7u) ^ (unsigned)fq) << 4);
-    }
-    // weight-fragment byte offset of this lane inside a tap's [64][64] tile (row fr, K-half 0; rows a * 16 + fr: + a * 2048)
-    const unsigned wl0 = (unsigned)(fr * 128 + ((fq ^ (fr & 7)) << 4));
+    const unsigned wl0 = c64_frag_offsets(p, g, wm * WTM, lane, lo);
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem;
     typedef const bf16x8 __attribute__((address_space(3)))* frag_t;
     // statistics stay in registers across this block's tiles: one reduction + 128 atomics per BLOCK, not per tile
@@ -640,23 +697,14 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
         for (int j = 0; j < 4; ++j) { st1[a][j] = 0.f; st2[a][j] = 0.f; }
     __builtin_amdgcn_s_barrier();                                 // B_0
     int i = 0;
-    for (int t = tbeg; t < tend; t += G, ++i) {
-        const bf16_t* cH = sH + (i & 1) * HBUF;
+    for (int t = tw.tbeg; t < tw.tend; ++t, ++i) {
         f32x4 acc[NI][MI];
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-#pragma unroll
-            for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         BstFrag<NI, VPD_BST_MB(MI)> bst;      // EPM 6 / 7: the epilogue's z fragments and mask bits, in flight behind the MFMA loop
         AccFrag<NI, MI> accf;                 // EPM 2 / 7: the old values of y and their mask bits, likewise
         if (EPM == 6 || EPM == 7) conv_bst_prefetch<BM, BN, WM, WN>(p, t, 0, geo, bst);
         if (EPM == 2 || EPM == 7) conv_acc_prefetch<BM, BN, WM, WN>(p, t, 0, geo, accf);
-        // ONE MFMA wave per SIMD and no barrier inside a tile: nothing hides an LDS round trip except this wave's own MFMAs.
-        // Two fragment sets; step s+1's six ds_read_b128 are issued between the eight MFMAs of step s (hipcc left to itself
-        // re-uses one set and waits for each pair of reads right before the MFMA that needs it: ~150 exposed cycles per
-        // 128 cycles of matrix work).
         bf16x8 af[2][NI], bfm[2][MI];
-        // fragment i of step st: 0 -> af[0], 1 -> bfm[0], 2 -> bfm[1], 3.. -> af[1..] (the order the MFMAs below first need them)
         // (row term of tap row ir: halo buffer + (dy * Wp + dx0) * 128, wave-uniform)
         const unsigned hbb = lds0 + (unsigned)(9 * BN * 64 * 2) + (unsigned)(i & 1) * (HBUF * 2u);
         const unsigned rowS[3] = {hbb + (unsigned)(((p.taps.dy0) * Wp + p.taps.dx0) * 128),
@@ -673,33 +721,8 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
                 af[buf][a] = *(frag_t)(size_t)(lds0 + (unsigned)(tap * BN * 64 * 2 + a * 2048) + (wl0 ^ (unsigned)(kk * 64)));
             }
         };
-        static_assert(NI == 4 && MI == 2, "fragment schedule below");
-        if (!VPD_ABL(p, 2)) {
-#pragma unroll
-            for (int i = 0; i < NI + MI; ++i) ldone(0, 0, i);
-#pragma unroll
-            for (int st = 0; st < 18; ++st) {
-                const int cur = st & 1, nxt = cur ^ 1;
-                const bool more = st + 1 < 18;
-#define C64_MFMA(a, b) acc[a][b] = VPD_MFMA16(af[cur][a], bfm[cur][b], acc[a][b])
-                // source order pinned by scheduling barriers: the next step's reads leave in pairs behind the first three MFMAs
-                C64_MFMA(0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) { ldone(st + 1, nxt, 0); ldone(st + 1, nxt, 1); }
-                __builtin_amdgcn_sched_barrier(0);
-                C64_MFMA(0, 1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) { ldone(st + 1, nxt, 2); ldone(st + 1, nxt, 3); }
-                __builtin_amdgcn_sched_barrier(0);
-                C64_MFMA(1, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) { ldone(st + 1, nxt, 4); ldone(st + 1, nxt, 5); }
-                __builtin_amdgcn_sched_barrier(0);
-                C64_MFMA(1, 1); C64_MFMA(2, 0); C64_MFMA(2, 1); C64_MFMA(3, 0); C64_MFMA(3, 1);
-                __builtin_amdgcn_sched_barrier(0);
-#undef C64_MFMA
-            }
-        }
+        static_assert(NI == 4 && MI == 2, "fragment schedule of mfma_ksteps_pinned");
+        if (!VPD_ABL(p, 2)) mfma_ksteps_pinned<18>(acc, af, bfm, ldone);
         if (!VPD_ABL(p, 8)) {
             if constexpr (EPM == 2 || EPM == 7) conv_epilogue_acc_pre<BM, BN, WM, WN, EPM>(p, acc, t, 0, st1, st2, geo, bst, accf);
             else if constexpr (EPM == 6) conv_epilogue_pre<BM, BN, WM, WN, EPM>(p, acc, t, 0, st1, st2, geo, bst);
@@ -711,7 +734,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
 }
 
 // ---------------------------------------------------------------------------
-// Two MFMA wave groups per block for the 64 -> 64 channel convolutions of the INFERENCE forward (eval epilogue).
+// Two MFMA wave groups per block for the 64 -> 64 channel convolutions of the INFERENCE forward (eval epilogue, EPM 3, only).
 // conv3x3_c64_persistent_kernel keeps ONE MFMA wave per SIMD: its 8 MFMAs per half K-step (128 cycles) sit behind ~150
 // cycles of exposed ds_read latency, and the eval epilogue (scale / shift, residual loads, ReLU, padded stores) runs with
 // the matrix cores idle.  Here a tile is 256 pixels: MFMA waves 0..3 take its first 128 pixels, waves 4..7 the second 128 --
@@ -723,6 +746,7 @@ __global__ __launch_bounds__(512) void conv3x3_c64_persistent_kernel(const ConvP
 #define C64X2_HPIX 344                           // halo pixels staged per tile (multiple of 8: one LDS-DMA instruction each)
 template <int EPM>
 __global__ __launch_bounds__(768) void conv3x3_c64x2_persistent_kernel(const ConvParams p, const HaloGeom g, int ntiles, int per) {
+    static_assert(EPM == 3, "eval epilogue only (c64x2_geom)");
     constexpr int BN = 64;
     constexpr int MI = 2, NI = 4;                                 // per wave: 32 pixels x 64 channels
     constexpr int HBUF = C64X2_HPIX * 64;
@@ -735,96 +759,48 @@ __global__ __launch_bounds__(768) void conv3x3_c64x2_persistent_kernel(const Con
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int W = p.Ws, H = p.Hs, Wp = W + 2;
-    // (tile walk as in conv3x3_c64_persistent_kernel: per > 0 = `per` consecutive tiles per block)
-    const int G = per > 0 ? 1 : gridDim.x;
-    const int tbeg = per > 0 ? blockIdx.x * per : blockIdx.x;
-    const int tend = per > 0 ? (tbeg + per < ntiles ? tbeg + per : ntiles) : ntiles;
+    const int Wp = p.Ws + 2;
+    const TileWalk tw(per, ntiles);
 
     if (wave >= 8) {
         const int lw = wave - 8;
-        const int piece = lane & 7;
-        const int lrow = lane >> 3;
-        const float rWp = 1.0f / (float)Wp;
-        auto issue_halo = [&](int mtile, int buf) __attribute__((always_inline)) {
-            const int gr0 = mtile * g.TR;
-            int prow0;
-            if (g.multi) prow0 = (gr0 / H) * (H + 2);
-            else { const int b = gr0 / H; prow0 = b * (H + 2) + (gr0 - b * H); }
-            const int gp0 = prow0 * Wp;
-            for (int k = lw; k < NINSTR; k += 4) {
-                const int hp = k * 8 + lrow;
-                const int hr = vpd_fdiv(hp, rWp);                // column-keyed swizzle, as conv3x3_c64_persistent_kernel
-                const int key = (hp - hr * Wp) & 7;
-                int gp = gp0 + hp;
-                gp = gp < g.total_pix ? gp : g.total_pix - 1;
-                const bf16_t* src = p.x + (size_t)gp * 64 + ((piece ^ key) << 3);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sH + buf * HBUF + k * 8 * 64), 16, 0, 0);
-            }
-        };
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int wsl = p.taps.w0 + (t / 3) * p.taps.wrs + (t % 3) * p.taps.wcs;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int n = (lw + 4 * i) * 8 + lrow;
-                const bf16_t* src = p.w + ((size_t)wsl * 64 + n) * 64 + ((piece ^ (n & 7)) << 3);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sW + t * BN * 64 + (lw + 4 * i) * 8 * 64), 16, 0, 0);
-            }
-        }
-        if (tbeg < tend) issue_halo(tbeg, 0);
+        resident_weights_load<9>(p.w, sW, lw, lane, [&](int t) __attribute__((always_inline)) {
+            return p.taps.w0 + (t / 3) * p.taps.wrs + (t % 3) * p.taps.wcs; });
+        if (tw.tbeg < tw.tend) c64_halo_issue<NINSTR>(p, g, sH, tw.tbeg, lw, lane);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                             // B_0
         int i = 0;
-        for (int t = tbeg; t < tend; t += G, ++i) {
-            if (t + G < tend) issue_halo(t + G, (i + 1) & 1);   // buffer last read in tile i-1, finished before B_i
+        for (int t = tw.tbeg; t < tw.tend; ++t, ++i) {
+            // buffer last read in tile i-1, finished before B_i
+            if (t + 1 < tw.tend) c64_halo_issue<NINSTR>(p, g, sH + ((i + 1) & 1) * HBUF, t + 1, lw, lane);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                         // B_{i+1}
-        }
-        if (EPM == 1) {
-            __builtin_amdgcn_s_barrier();                         // halo buffers are free for the statistics scratch
-            __builtin_amdgcn_s_barrier();                         // matches the barrier inside conv_stats_flush
         }
         return;
     }
 
     const int grp = wave >> 2;                                    // pixel half of the tile
     const int wm = wave & 3;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
-    unsigned lo[3][MI];                                           // as in conv3x3_c64_persistent_kernel
-#pragma unroll
-    for (int b = 0; b < MI; ++b) {
-        const int m = grp * 128 + wm * 32 + b * 16 + fr;
-        const int lr = m / W;
-        const int xx = m - lr * W;
-        const int hrow = g.multi ? (lr / H) * (H + 2) + (lr % H) : lr;
-#pragma unroll
-        for (int ic = 0; ic < 3; ++ic)
-            lo[ic][b] = (unsigned)((hrow * Wp + xx) * 128) + ((((unsigned)(xx + p.taps.dx0 + ic * p.taps.dxs) & 7u) ^ (unsigned)fq) << 4);
-    }
-    const unsigned wl0 = (unsigned)(fr * 128 + ((fq ^ (fr & 7)) << 4));
+    unsigned lo[3][MI];
+    const unsigned wl0 = c64_frag_offsets(p, g, grp * 128 + wm * 32, lane, lo);
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem;
     typedef const bf16x8 __attribute__((address_space(3)))* frag_t;
-    float st1[NI][4], st2[NI][4];
+    float st1[NI][4], st2[NI][4];                                 // (the epilogue's signature; the eval mode adds nothing to them)
 #pragma unroll
     for (int a = 0; a < NI; ++a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) { st1[a][j] = 0.f; st2[a][j] = 0.f; }
     __builtin_amdgcn_s_barrier();                                 // B_0
     int i = 0;
-    for (int t = tbeg; t < tend; t += G, ++i) {
-        const bf16_t* cH = sH + (i & 1) * HBUF;
+    for (int t = tw.tbeg; t < tw.tend; ++t, ++i) {
         f32x4 acc[NI][MI];
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-#pragma unroll
-            for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         const unsigned hbb = lds0 + (unsigned)(9 * BN * 64 * 2) + (unsigned)(i & 1) * (HBUF * 2u);
         // eval with a residual: its fragments are requested before the tile's nine K-steps instead of inside the epilogue
         ResFrag<NI, MI> resf;
-        const bool res_pre = EPM == 3 && p.res != nullptr;
+        const bool res_pre = p.res != nullptr;
         if (res_pre) conv_res_prefetch<128, BN, 4, 1>(p, 2 * t + grp, 0, geo, resf, grp * 4);
+        // (a plain K loop: two MFMA waves per SIMD cover each other's LDS round trips)
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const unsigned S = hbb + (unsigned)(((p.taps.dy0 + (tap / 3) * p.taps.dys) * Wp + p.taps.dx0 + (tap % 3) * p.taps.dxs) * 128);
@@ -848,10 +824,6 @@ __global__ __launch_bounds__(768) void conv3x3_c64x2_persistent_kernel(const Con
         else conv_epilogue<128, BN, 4, 1, EPM>(p, acc, 2 * t + grp, 0, st1, st2, geo, grp * 4);
         __builtin_amdgcn_s_barrier();                             // B_{i+1}
     }
-    if (EPM == 1) {
-        __builtin_amdgcn_s_barrier();                             // (loaders too) nobody reads the halo buffers any more
-        conv_stats_flush<256, BN, 8, 1>(p, st1, st2, blockIdx.x, 0, reinterpret_cast<unsigned char*>(sH));
-    }
 }
 
 // 256-pixel tiles of whole image rows whose halo fits C64X2_HPIX pixels; eval epilogue only (see the kernel's comment)
@@ -865,17 +837,17 @@ static bool c64x2_geom(const ConvParams& p, HaloGeom* g) {
     g->TR = TR;
     g->NHP = g->HR * (W + 2);
     g->total_pix = p.N * (H + 2) * (W + 2);
+    g->rWp = 1.0f / (float)(W + 2);
     g->rot = 0; g->rnch = 1.0f;
     return g->NHP <= C64X2_HPIX && p.M >= 256 * 256;      // at least one 256-pixel tile per CU (256 crops of 32 x 32: 1024 tiles)
 }
-// Blocks of the resident-weight kernels (layer1's two, the stem): one per CU at most.  *per: consecutive tiles per block
-// (VPD_C64_CONTIG=0: 0, strided); the grid shrinks to the blocks that get tiles
+// Blocks of layer1's two kernels: one per CU at most.  *per: consecutive tiles per block (TileWalk); the grid shrinks to the
+// blocks that get tiles
 static int persistent_grid(int ntiles, int* per) {
     const int ncu = vpd_cu_budget();
-    int grid = ntiles < ncu ? ntiles : ncu;
-    *per = vpd_switches().c64_contig ? (ntiles + grid - 1) / grid : 0;
-    if (*per > 0) grid = (ntiles + *per - 1) / *per;
-    return grid;
+    const int grid = ntiles < ncu ? ntiles : ncu;
+    *per = (ntiles + grid - 1) / grid;
+    return (ntiles + *per - 1) / *per;
 }
 static hipError_t launch_c64x2(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
     const int ntiles = (p.M + 255) / 256;
@@ -883,12 +855,7 @@ static hipError_t launch_c64x2(const ConvParams& p, const HaloGeom& g, hipStream
     const int grid = persistent_grid(ntiles, &per);
     const size_t lds = ((size_t)9 * 64 + 2 * C64X2_HPIX) * 64 * sizeof(bf16_t);
     ConvParams q = p;
-    switch (conv_ep_mode(q)) {
-        case 0: VPD_LAUNCH((conv3x3_c64x2_persistent_kernel<0>), dim3(grid), dim3(768), lds, stream, q, g, ntiles, per); break;
-        case 1: VPD_LAUNCH((conv3x3_c64x2_persistent_kernel<1>), dim3(grid), dim3(768), lds, stream, q, g, ntiles, per); break;
-        case 2: VPD_LAUNCH((conv3x3_c64x2_persistent_kernel<2>), dim3(grid), dim3(768), lds, stream, q, g, ntiles, per); break;
-        default: VPD_LAUNCH((conv3x3_c64x2_persistent_kernel<3>), dim3(grid), dim3(768), lds, stream, q, g, ntiles, per); break;
-    }
+    VPD_LAUNCH((conv3x3_c64x2_persistent_kernel<3>), dim3(grid), dim3(768), lds, stream, q, g, ntiles, per);      // (c64x2_geom: mode 3 only)
     return hipGetLastError();
 }
 
@@ -919,7 +886,7 @@ static hipError_t launch_c64(const ConvParams& p, const HaloGeom& g, hipStream_t
 // pixels is already bank-conflict free for ds_read_b128).  Each of the 7 kernel rows is one 64-deep K-step
 // whose pixel fragments are read straight out of the raw rows (8 column taps x 8 channels contiguous),
 // instead of the gather kernel's 7 x 128 B per output pixel (14x read amplification).  The 7 weight
-// taps (56 KiB) stay resident; structure as conv3x3_c64_persistent_kernel.
+// taps (56 KiB) stay resident; structure and shared pieces as conv3x3_c64_persistent_kernel.
 // ---------------------------------------------------------------------------
 template <int HROWS, int EPM>
 __global__ __launch_bounds__(512) void conv_stem_persistent_kernel(const ConvParams p, int TR, int ntiles, long xelems, int lds_store) {
@@ -966,16 +933,7 @@ __global__ __launch_bounds__(512) void conv_stem_persistent_kernel(const ConvPar
                 __builtin_amdgcn_global_load_lds((gptr_t)(p.x + e), (lptr_t)(sH + buf * HBUF + (lw + 4 * k) * 8 * 64), 16, 0, 0);
             }
         };
-#pragma unroll
-        for (int t = 0; t < 7; ++t) {
-            const int wsl = p.taps.w0 + t * p.taps.wrs;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int n = (lw + 4 * i) * 8 + lrow;
-                const bf16_t* src = p.w + ((size_t)wsl * 64 + n) * 64 + ((piece ^ (n & 7)) << 3);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sW + t * BN * 64 + (lw + 4 * i) * 8 * 64), 16, 0, 0);
-            }
-        }
+        resident_weights_load<7>(p.w, sW, lw, lane, [&](int t) __attribute__((always_inline)) { return p.taps.w0 + t * p.taps.wrs; });
         issue_rows(tile_at(0), 0);
         if constexpr (POOL) {
             // Pooled eval mode: the LOADER waves also run the max-pool.  The MFMA waves park a tile's activations in LDS and go
@@ -1074,15 +1032,10 @@ __global__ __launch_bounds__(512) void conv_stem_persistent_kernel(const ConvPar
         const int t = tile_at(i);
         const bf16_t* cH = sH + (i & 1) * HBUF;
         f32x4 acc[NI][MI];
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-#pragma unroll
-            for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // as in conv3x3_c64_persistent_kernel: one MFMA wave per SIMD, no barrier inside a tile -- two fragment sets, the next
-        // half-step's six reads pinned behind the first three MFMAs of the current one
-        static_assert(NI == 4 && MI == 2, "fragment schedule below");
+        zero_acc(acc);
+        static_assert(NI == 4 && MI == 2, "fragment schedule of mfma_ksteps_pinned");
         bf16x8 af[2][NI], bfm[2][MI];
-        // fragment i of half-step st = 2 * (kernel row r) + kk: 0 -> af[0], 1 -> bfm[0], 2 -> bfm[1], 3.. -> af[1..]
+        // fragment i of half-step st = 2 * (kernel row r) + kk
         auto ldone = [&](int st, int buf, int i) __attribute__((always_inline)) {
             const int r = st >> 1, kk = st & 1;
             const int chunk = kk * 4 + fq;                        // column tap t = chunk (8 channels each)
@@ -1094,29 +1047,7 @@ __global__ __launch_bounds__(512) void conv_stem_persistent_kernel(const ConvPar
                 af[buf][a] = *reinterpret_cast<const bf16x8*>(sW + r * BN * 64 + rr * 64 + ((chunk ^ (rr & 7)) << 3));
             }
         };
-#pragma unroll
-        for (int i2 = 0; i2 < NI + MI; ++i2) ldone(0, 0, i2);
-#pragma unroll
-        for (int st = 0; st < 14; ++st) {
-            const int cur = st & 1, nxt = cur ^ 1;
-            const bool more = st + 1 < 14;
-#define STEM_MFMA(a, b) acc[a][b] = VPD_MFMA16(af[cur][a], bfm[cur][b], acc[a][b])
-            STEM_MFMA(0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) { ldone(st + 1, nxt, 0); ldone(st + 1, nxt, 1); }
-            __builtin_amdgcn_sched_barrier(0);
-            STEM_MFMA(0, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) { ldone(st + 1, nxt, 2); ldone(st + 1, nxt, 3); }
-            __builtin_amdgcn_sched_barrier(0);
-            STEM_MFMA(1, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (more) { ldone(st + 1, nxt, 4); ldone(st + 1, nxt, 5); }
-            __builtin_amdgcn_sched_barrier(0);
-            STEM_MFMA(1, 1); STEM_MFMA(2, 0); STEM_MFMA(2, 1); STEM_MFMA(3, 0); STEM_MFMA(3, 1);
-            __builtin_amdgcn_sched_barrier(0);
-#undef STEM_MFMA
-        }
+        mfma_ksteps_pinned<14>(acc, af, bfm, ldone);
         if constexpr (POOL) {
             // Eval with the max-pool behind the conv.  The tile's activations a = bf16(relu(bf16(acc) * scale + shift)) -- the
             // rounding points of the two-launch path (conv stores bf16 z, stem_pool_pair_kernel rounds the activation before
@@ -1479,10 +1410,7 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p0) {
     const int fr = lane & 15;
     const int fq = lane >> 4;
     f32x4 acc[NI][MI];
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     for (int s = 0; s < nsteps; ++s) {
         __builtin_amdgcn_s_barrier();                             // READY_s
         const bf16_t* cA = ring + (s % NS) * STAGE;

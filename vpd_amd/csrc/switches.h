@@ -31,7 +31,6 @@
     X(pws_rot,            "VPD_PWS_ROT",           1)          \
     X(reserve_cus,        "VPD_RESERVE_CUS",       0)          \
     X(c64x2,              "VPD_C64X2",             1)          \
-    X(c64_contig,         "VPD_C64_CONTIG",        1)          \
     X(conv1x1_ws,         "VPD_CONV1X1_WS",        1)          \
     X(conv_s2_ws,         "VPD_CONV_S2_WS",        1)          \
     X(conv_s2_dgrad_ws,   "VPD_CONV_S2_DGRAD_WS",  1)          \
