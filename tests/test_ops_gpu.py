@@ -243,44 +243,65 @@ WG128_GROUPS = {
     "stride2_32to16_with_stride1": [(6, 16, 16, 128, 64, 2), (6, 16, 16, 128, 128, 1)],
     "stride2_16to8_and_8to4_ragged": [(5, 8, 8, 256, 128, 2), (5, 4, 4, 512, 256, 2), (5, 4, 4, 512, 512, 1)],
     # 1x1 convolutions as tasks of the same launch: Bottleneck shapes (128 x 128 and 128 x 64 tiles, ragged chunks, splits),
-    # the stride-2 down-sampling branch, mixed with a 3x3 problem
-    "one_by_one_bottleneck": [(9, 16, 16, 128, 512, 1, 1), (9, 16, 16, 512, 128, 1, 1), (5, 8, 8, 256, 64, 1, 1)],
+    # the stride-2 down-sampling branch, mixed with a 3x3 problem; (5, 8, 8, 128, 128, 1, 1): 128 x 128 tiles without the 256-channel variant
+    "one_by_one_bottleneck": [(9, 16, 16, 128, 512, 1, 1), (9, 16, 16, 512, 128, 1, 1), (5, 8, 8, 256, 64, 1, 1), (5, 8, 8, 128, 128, 1, 1)],
     "one_by_one_stride2_with_3x3": [(6, 16, 16, 128, 64, 2, 1), (5, 4, 4, 512, 256, 2, 1), (6, 16, 16, 128, 128, 1, 3), (33, 8, 8, 1024, 256, 1, 1)],
 }
+
+
+WG128_SENT = -12352.0        # no integer-regime sum (an integer, |v| <= 40 * 256) and no randn sum comes near it by accident
+WG128_SLACK = 4096           # floats behind every gradient buffer
 
 
 @pytest.mark.parametrize("name", list(WG128_GROUPS), ids=list(WG128_GROUPS))
 def test_wgrad128_group(name):
     """conv_wgrad128_persistent_kernel (128 x 64 tiles, persistent blocks, host-built schedule): every problem of a grouped
-    launch against torch's conv2d weight gradient on the same bf16-rounded operands."""
+    launch, in two regimes.  randn: against torch's conv2d weight gradient on the same bf16-rounded operands, rel-L2.  int:
+    operands from {-1, 0, 1} at density 1/2, so every partial sum is an integer of at most M = 40 * 256 < 2^24 whatever the split
+    and the order of the additions: every gradient EQUAL to float64 conv2d_weight.  Both: the gradient buffers are pre-filled
+    with a sentinel, every element must be written and the 4,096 floats of slack behind each must keep the sentinel."""
+    from tests import opref as R
     L = _lib()
-    probs = WG128_GROUPS[name]
+    probs = [pr if len(pr) == 7 else pr + (3,) for pr in WG128_GROUPS[name]]
     g = torch.Generator().manual_seed(len(name))
-    keep, refs = [], []
-    dzs, xs, dws, slabs, dims = [], [], [], [], []
-    probs = [pr if len(pr) == 7 else pr + (3,) for pr in probs]
-    for (n, h, w, co, ci, st, ks) in probs:
-        x = bf16_round(torch.randn(n, ci, st * h, st * w, generator=g))
-        dz = bf16_round(torch.randn(n, co, h, w, generator=g))
-        wr = torch.zeros(co, ci, ks, ks, requires_grad=True)
-        F.conv2d(x, wr, None, stride=st, padding=ks // 2).backward(dz)
-        refs.append(wr.grad)
-        xp, dzp = to_padded_nhwc(x, 1, 1, 1, 1), to_padded_nhwc(dz, 1, 1, 1, 1)
-        dw = torch.full((ks * ks, co, ci), float("nan"), dtype=torch.float32, device="cuda")      # the kernel OVERWRITES
-        slab = torch.empty(max(int(L.vpd_op_wgrad128_slab_floats(co, ci)), 4), dtype=torch.float32, device="cuda")
-        keep += [xp, dzp, dw, slab]
-        dzs.append(dzp.data_ptr()); xs.append(xp.data_ptr()); dws.append(dw.data_ptr()); slabs.append(slab.data_ptr())
-        dims += [n, h, w, co, ci, st, ks]
     k = len(probs)
     arr = lambda v: (C.c_void_p * k)(*v)
     table = torch.empty(int(L.vpd_op_wgrad128_table_bytes()), dtype=torch.uint8, device="cuda")
-    _check(L.vpd_op_wgrad128_group(k, arr(dzs), arr(xs), arr(dws), arr(slabs), (C.c_int * (7 * k))(*dims), ptr(table),
-                                   stream()))
-    torch.cuda.synchronize()
-    for i, (n, h, w, co, ci, st, ks) in enumerate(probs):
-        got = keep[4 * i + 2].cpu().view(ks, ks, co, ci).permute(2, 3, 0, 1)
-        assert torch.isfinite(got).all(), (name, i)
-        assert rel_l2(got, refs[i]) < REL_TOL, (name, i, rel_l2(got, refs[i]))
+    for regime in ("randn", "int"):
+        keep, refs = [], []
+        dzs, xs, dws, slabs, dims = [], [], [], [], []
+        for (n, h, w, co, ci, st, ks) in probs:
+            assert n * h * w <= 40 * 256
+            if regime == "int":
+                x, dz = R._sparse_int((n, ci, st * h, st * w), 0.5, g).float(), R._sparse_int((n, co, h, w), 0.5, g).float()
+                refs.append(R.conv_wgrad(x, dz, dict(ci=ci, co=co, k=ks, stride=st, h=st * h, w=st * w)))
+            else:
+                x = bf16_round(torch.randn(n, ci, st * h, st * w, generator=g))
+                dz = bf16_round(torch.randn(n, co, h, w, generator=g))
+                wr = torch.zeros(co, ci, ks, ks, requires_grad=True)
+                F.conv2d(x, wr, None, stride=st, padding=ks // 2).backward(dz)
+                refs.append(wr.grad)
+            xp, dzp = to_padded_nhwc(x, 1, 1, 1, 1), to_padded_nhwc(dz, 1, 1, 1, 1)
+            dw = torch.full((ks * ks * co * ci + WG128_SLACK,), WG128_SENT, dtype=torch.float32, device="cuda")      # the kernel OVERWRITES
+            slab = torch.empty(max(int(L.vpd_op_wgrad128_slab_floats(co, ci)), 4), dtype=torch.float32, device="cuda")
+            keep += [xp, dzp, dw, slab]
+            dzs.append(dzp.data_ptr()); xs.append(xp.data_ptr()); dws.append(dw.data_ptr()); slabs.append(slab.data_ptr())
+            dims += [n, h, w, co, ci, st, ks]
+        _check(L.vpd_op_wgrad128_group(k, arr(dzs), arr(xs), arr(dws), arr(slabs), (C.c_int * (7 * k))(*dims), ptr(table),
+                                       stream()))
+        torch.cuda.synchronize()
+        for i, (n, h, w, co, ci, st, ks) in enumerate(probs):
+            m = ks * ks * co * ci
+            buf = keep[4 * i + 2].cpu()
+            assert bool((buf[m:] == WG128_SENT).all()), (name, regime, i, "the slack behind the gradient lost its sentinel")
+            assert not bool((buf[:m] == WG128_SENT).any()), (name, regime, i, "elements left unwritten")
+            got = buf[:m].view(ks, ks, co, ci).permute(2, 3, 0, 1)
+            assert torch.isfinite(got).all(), (name, regime, i)
+            if regime == "int":
+                bad = int((got.double() != refs[i]).sum())
+                assert bad == 0, (name, i, "%d elements differ from float64, max |d| %g" % (bad, float((got.double() - refs[i]).abs().max())))
+            else:
+                assert rel_l2(got, refs[i]) < REL_TOL, (name, i, rel_l2(got, refs[i]))
 
 
 # ---------------------------------------------------------------------------

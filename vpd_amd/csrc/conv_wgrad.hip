@@ -1,51 +1,72 @@
-// Weight-gradient convolution on bf16 MFMA (gfx950).
+// Weight gradients of the convolutions on bf16 / fp16 MFMA (gfx950).
 //
-//   dw[tap][co][kc] += sum_m dz[m][co] * x[gather(m, tap)][kc]      (fp32)
+//   dw[tap][co][kc] = sum_m dz[m][co] * x[gather(m, tap)][kc]      (fp32)
 //
-// GEMM view: rows = co, cols = kc (input channels of one tap), K = output pixels.
-// Both operands are stored channel-contiguous (NHWC) while the reduction runs
-// over pixels, so both MFMA fragments are fetched from LDS with the CDNA4
-// transposing read ds_read_b64_tr_b16 (no software transpose).  LDS tiles are
-// [128 pixels][64 channels] bf16 (128-B rows); 32-B granules are XOR-swizzled
-// so the 8 rows a 32-lane half touches land on 8 distinct bank groups.
+// GEMM view: rows = co, cols = kc (input channels of one tap), K = output pixels.  Both operands are stored channel-contiguous (NHWC)
+// while the reduction runs over pixels, so both MFMA fragments are fetched from LDS with the CDNA4 transposing read
+// ds_read_b64_tr_b16 (wg_tr_read; no software transpose).  LDS tiles are [pixels][64 channels] (128-B rows); 32-B granules are
+// XOR-swizzled (wg_swz_off, wg_src_piece) so the 8 rows a 32-lane half touches land on 8 distinct bank groups.
 //
-// One block = one (co tile 64, kc tile 64, tap) over `chunks_per_block`
-// 128-pixel chunks; the 4 waves split every chunk's pixels (32 each) and their
-// 64x64 partial tiles are summed through LDS before one fp32 atomic per
-// element.
-#include <stdio.h>
-#include <stdlib.h>
-
+// The file's five kernels, each described where it is defined:
+//   conv_wgrad_kernel                     any tap set, 64 x 64 tiles, fp32 atomics               ("Atomics kernel")
+//   conv_wgrad_halo_kernel (+ _pair_,     3x3 / 1x1 on a staged x halo, 64 x 64 tiles, loader     ("halo form")
+//     _grouped_ variants of one body)     waves + MFMA waves, split partials in a slab
+//   conv_wgrad_stem_kernel                the 7x7 stride-2 stem on raw input rows, same waves     ("Stem weight gradient")
+//   conv_wgrad128_persistent_kernel       128-wide tiles, persistent blocks, host-built schedule  ("wg2")
+//   wgrad_slab_reduce_group_kernel        sums the split partials of one or more problems         (WgReduceGroup)
+// Host side: wg_route() decides which kernel takes a problem; every eligibility test and launcher is stated on it.
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
 #include <utility>
 #include <vector>
 #include "common.h"
 
-static __device__ __forceinline__ int wg_swz(int r, int c16) {
-    // element offset of 16-B piece c16 (0..7) of row r in a [128][64] bf16 tile
-    const int f = ((r >> 1) & 1) | (((r >> 3) & 1) << 1);
-    return r * 64 + ((((c16 >> 1) ^ f) << 4) | ((c16 & 1) << 3));
-}
+typedef const void __attribute__((address_space(1)))* wg_gptr_t;
+typedef void __attribute__((address_space(3)))* wg_lptr_t;
+typedef const char __attribute__((address_space(3)))* wg_lds_cp;
 
-static __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int rbase, int ctile, int lane) {
-    // MFMA 16x16x32 operand with the K index on LDS rows:
-    //   element j of lane l = tile[row rbase + 8*(l>>4) + j][col ctile*16 + (l&15)]
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-    const int col = ctile * 16 + 4 * pp;               // 4 consecutive columns = 8 bytes
-    const int r0 = rbase + 8 * g + q;
-    const int r1 = r0 + 4;
-    const int f0 = ((r0 >> 1) & 1) | (((r0 >> 3) & 1) << 1);
-    const int f1 = ((r1 >> 1) & 1) | (((r1 >> 3) & 1) << 1);
-    const int o0 = r0 * 64 + ((((col >> 4) ^ f0) << 4) | (col & 15));
-    const int o1 = r1 * 64 + ((((col >> 4) ^ f1) << 4) | (col & 15));
+// The 32-byte-granule swizzle of a [rows][64] tile.  Reader side: element offset of column `col` of row `r`; loader side: the 16-B
+// source piece that lane piece `piece` (0..7) of row `r` fetches, so that a linear LDS-DMA write lands swizzled.
+static __device__ __forceinline__ int wg_f(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); }
+static __device__ __forceinline__ int wg_swz_off(int r, int col) { return r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15)); }
+static __device__ __forceinline__ int wg_src_piece(int r, int piece) { return (((piece >> 1) ^ wg_f(r)) << 1) | (piece & 1); }
+
+// One MFMA 16x16x32 operand with the K index on LDS rows: two transposing reads of four rows each (k = 8g + q and 8g + 4 + q).
+static __device__ __forceinline__ bf16x8 wg_tr_read(wg_lds_cp lo_addr, wg_lds_cp hi_addr) {
     typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tile + o0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tile + o1));
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)lo_addr);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)hi_addr);
     s16x8 v;
     v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
     v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
     return __builtin_bit_cast(bf16x8, v);
+}
+static __device__ __forceinline__ bf16x8 wg_tr_read(const bf16_t* tile, int o0, int o1) {      // element offsets into a tile in LDS
+    return wg_tr_read((wg_lds_cp)(const char*)(tile + o0), (wg_lds_cp)(const char*)(tile + o1));
+}
+
+// Stores N 16 x 16 fp32 accumulator tiles (16-row groups a = 0..N-1 of one 16-column strip) into a [co][ci] matrix: `o` points at
+// (row 0, this lane's column), gq = lane >> 4.
+template <int N>
+static __device__ __forceinline__ void wg_store_tile(float* o, size_t row_stride, const f32x4 (&acc)[N], int gq) {
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * row_stride] = acc[a][j];
+}
+
+// ---------------------------------------------------------------------------
+// Atomics kernel: any tap set.  One block = one (co tile 64, kc tile 64, tap) over `chunks_per_block` 128-pixel chunks, staged
+// through registers into two [128][64] tiles per operand; the 4 waves split every chunk's pixels (32 each) and their 64x64 partial
+// tiles are summed through LDS before one fp32 atomic per element.
+// ---------------------------------------------------------------------------
+static __device__ __forceinline__ bf16x8 tr_frag(const bf16_t* tile, int rbase, int ctile, int lane) {
+    // element j of lane l = tile[row rbase + 8*(l>>4) + j][col ctile*16 + (l&15)]
+    const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
+    const int col = ctile * 16 + 4 * pp;               // 4 consecutive columns = 8 bytes
+    const int r0 = rbase + 8 * g + q;
+    return wg_tr_read(tile, wg_swz_off(r0, col), wg_swz_off(r0 + 4, col));
 }
 
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p) {
@@ -105,7 +126,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int r = row0 + 32 * i;
-            const int o = wg_swz(r, piece);
+            const int o = wg_swz_off(r, piece * 8);
             *reinterpret_cast<u32x4*>(dZ + o) = rz[i];
             *reinterpret_cast<u32x4*>(dX + o) = rx[i];
         }
@@ -176,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
 // precomputed swizzled offsets.  The x halo is loaded once and serves all nine taps (139 FLOP per
 // staged byte instead of 32).  One barrier per chunk: READY_c = "chunk c has landed" and, because the
 // MFMA waves only arrive after finishing chunk c-1, also "the stage of chunk c-1 is free".  Partial
-// tiles go to an fp32 slab with plain stores (slab[split][tap][Co][Ci]); wgrad_slab_reduce_kernel sums
+// tiles go to an fp32 slab with plain stores (slab[split][tap][Co][Ci]); wgrad_slab_reduce_group_kernel sums
 // the splits.
 // ---------------------------------------------------------------------------
 #define WG_CH 64           // pixels per chunk = two MFMA K-steps (vpd_wgrad_split assumes 64)
@@ -186,25 +207,6 @@ struct WgHaloGeom {
     int TR, multi, HR, NHP, total_pix;   // halo tiling of a 128-pixel chunk (as HaloGeom in conv_igemm.hip)
     int ksplit, cpb;                     // pixel-chunk splits and chunks per block
 };
-
-typedef const void __attribute__((address_space(1)))* wg_gptr_t;
-typedef void __attribute__((address_space(3)))* wg_lptr_t;
-
-static __device__ __forceinline__ int wg_f(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); }
-
-// MFMA operand (K on LDS rows) from two explicit 4-row blocks: row ra (k = 8g+q) and row rb (k = 8g+4+q)
-static __device__ __forceinline__ bf16x8 tr_frag2(const bf16_t* tile, int ra, int rb, int ctile, int pp) {
-    const int col = ctile * 16 + 4 * pp;
-    const int o0 = ra * 64 + ((((col >> 4) ^ wg_f(ra)) << 4) | (col & 15));
-    const int o1 = rb * 64 + ((((col >> 4) ^ wg_f(rb)) << 4) | (col & 15));
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tile + o0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(tile + o1));
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 // The down-sampling block's 1x1 branch riding in its 3x3 stride-2 conv1's launch (conv_wgrad_halo_pair_kernel): the branch's dz and
 // its slab.  Everything else -- x, the shapes, the split -- is conv1's.
@@ -243,9 +245,7 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int r = ra + 4 * h;
-                const int col = a * 16 + 4 * pp;
-                offA[a][h] = r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15));
+                offA[a][h] = wg_swz_off(ra + 4 * h, a * 16 + 4 * pp);
             }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -260,13 +260,11 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
                 for (int t = 0; t < NT; ++t) {
                     const int tt = T0 + t;
                     const int r = hmv + (p.taps.dy0 + (tt / 3) * p.taps.dys) * Wp + (p.taps.dx0 + (tt % 3) * p.taps.dxs);
-                    const int col = ctile * 16 + 4 * pp;
-                    offB[ks][t][h] = 64 * 64 + r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15));
+                    offB[ks][t][h] = 64 * 64 + wg_swz_off(r, ctile * 16 + 4 * pp);
                 }
                 if constexpr (BR) {      // the centre tap
                     const int r = hmv + (p.taps.dy0 + p.taps.dys) * Wp + (p.taps.dx0 + p.taps.dxs);
-                    const int col = ctile * 16 + 4 * pp;
-                    offC[ks][h] = 64 * 64 + r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15));
+                    offC[ks][h] = 64 * 64 + wg_swz_off(r, ctile * 16 + 4 * pp);
                 }
             }
     }
@@ -282,15 +280,6 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
                 if constexpr (BR) asm volatile("" : "+v"(offC[ks][h]));
             }
     }
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    auto frag = [&](const bf16_t* st, int o0, int o1) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(st + o0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(st + o1));
-        s16x8 v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-        v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return __builtin_bit_cast(bf16x8, v);
-    };
 
     for (int c = 0; c < nch; ++c) {
         __builtin_amdgcn_s_barrier();                             // READY_c
@@ -302,10 +291,10 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
             for (int ks = 0; ks < 2; ++ks) {
                 bf16x8 az[4], bx[NT];
 #pragma unroll
-                for (int a = 0; a < 4; ++a) az[a] = frag(st + ks * 32 * 64, offA[a][0], offA[a][1]);
+                for (int a = 0; a < 4; ++a) az[a] = wg_tr_read(st + ks * 32 * 64, offA[a][0], offA[a][1]);
 #pragma unroll
-                for (int t = 0; t < NT; ++t) bx[t] = frag(st, offB[ks][t][0], offB[ks][t][1]);
-                const bf16x8 bxc = frag(st, offC[ks][0], offC[ks][1]);
+                for (int t = 0; t < NT; ++t) bx[t] = wg_tr_read(st, offB[ks][t][0], offB[ks][t][1]);
+                const bf16x8 bxc = wg_tr_read(st, offC[ks][0], offC[ks][1]);
                 __builtin_amdgcn_sched_barrier(0);
                 // co tile by co tile (every accumulator still sees its k-steps in order): once a tile's MFMAs are issued its dz
                 // registers take the branch's dz fragment, whose read then hides behind the next tiles' MFMAs -- five A sets at
@@ -314,7 +303,7 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
                 for (int a = 0; a < 4; ++a) {
 #pragma unroll
                     for (int t = 0; t < NT; ++t) acc[t][a] = VPD_MFMA16(az[a], bx[t], acc[t][a]);
-                    az[a] = frag(st2 + ks * 32 * 64, offA[a][0], offA[a][1]);
+                    az[a] = wg_tr_read(st2 + ks * 32 * 64, offA[a][0], offA[a][1]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
@@ -330,9 +319,9 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-                for (int a = 0; a < 4; ++a) az[ks][a] = frag(st + ks * 32 * 64, offA[a][0], offA[a][1]);
+                for (int a = 0; a < 4; ++a) az[ks][a] = wg_tr_read(st + ks * 32 * 64, offA[a][0], offA[a][1]);
 #pragma unroll
-                for (int t = 0; t < NT; ++t) bx[ks][t] = frag(st, offB[ks][t][0], offB[ks][t][1]);
+                for (int t = 0; t < NT; ++t) bx[ks][t] = wg_tr_read(st, offB[ks][t][0], offB[ks][t][1]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -348,9 +337,9 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 az[4], bx[NT];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) az[a] = frag(st + ks * 32 * 64, offA[a][0], offA[a][1]);
+            for (int a = 0; a < 4; ++a) az[a] = wg_tr_read(st + ks * 32 * 64, offA[a][0], offA[a][1]);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) bx[t] = frag(st, offB[ks][t][0], offB[ks][t][1]);
+            for (int t = 0; t < NT; ++t) bx[t] = wg_tr_read(st, offB[ks][t][0], offB[ks][t][1]);
             __builtin_amdgcn_sched_barrier(0);      // keep the reads ahead of the MFMA block (hipcc would sink them)
 #pragma unroll
             for (int t = 0; t < NT; ++t)
@@ -370,21 +359,64 @@ static __device__ __forceinline__ void wgrad_mfma_half(const WgradParams& p, con
     for (int t = 0; t < NT; ++t) {
         const int tt = T0 + t;
         const int wsl = p.one_by_one ? 0 : p.taps.w0 + (tt / 3) * p.taps.wrs + (tt % 3) * p.taps.wcs;
-        float* o = slab + ((size_t)wsl * p.Co + co0) * p.Kc + ci0 + 16 * ctile + i16;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * p.Kc] = acc[t][a][j];
+        wg_store_tile(slab + ((size_t)wsl * p.Co + co0) * p.Kc + ci0 + 16 * ctile + i16, p.Kc, acc[t], gq);
     }
-    if constexpr (BR) {
-        float* o = slab2 + ((size_t)by * p.Co + co0) * p.Kc + ci0 + 16 * ctile + i16;
+    if constexpr (BR) wg_store_tile(slab2 + ((size_t)by * p.Co + co0) * p.Kc + ci0 + 16 * ctile + i16, p.Kc, acc2, gq);
+}
+// The 64-pixel chunks [*begin, *begin + n) of pixel split `split` at `cpb` chunks per split; returns n (>= 1 by construction of the splits).
+static __device__ __forceinline__ int wg_chunk_range(int M, int split, int cpb, int* begin) {
+    const int nchunks_total = (M + WG_CH - 1) / WG_CH;
+    *begin = split * cpb;
+    const int end = *begin + cpb < nchunks_total ? *begin + cpb : nchunks_total;
+    return end - *begin;
+}
+// Loader waves (conv_wgrad_halo_kernel and conv_wgrad_stem_kernel): loader wave lw (0..3) issues a quarter of every tile.
+// One dz tile [64 px][64 co] of chunk `ch`: 8 wave-instructions of 8 pixel rows, two per loader wave.  Rows past M read `zero`, 64
+// zero channels of a border pixel, and contribute nothing.  (A functor over references to the kernel's own variables, as a lambda
+// in the kernel body would be: the same code as a free function taking values costs the halo kernels two registers.)
+struct WgIssueDz {
+    const WgradParams& p;
+    const int& co0;
+    const int& lw;
+    const int& piece;
+    const int& lrow;
+    __device__ __forceinline__ void operator()(const bf16_t* dz, const bf16_t* zero, bf16_t* dst, int ch) const {
+        const int W = p.Ws, H = p.Hs;
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * p.Kc] = acc2[a][j];
+        for (int i = 0; i < 2; ++i) {
+            const int row = (lw + 4 * i) * 8 + lrow;
+            const int m = ch * WG_CH + row;
+            const int cpc = wg_src_piece(row, piece);
+            const bf16_t* src = zero + cpc * 8;
+            if (m < p.M) {
+                const int b = m / (H * W);
+                const int r = m - b * H * W;
+                const int yy = r / W;
+                const int xx = r - yy * W;
+                src = dz + ((size_t)(b * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + cpc * 8;
+            }
+            __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(dst + (lw + 4 * i) * 8 * 64), 16, 0, 0);
+        }
+    }
+};
+// The ring schedule of a loader wave over the nch chunks of its block: issue(c) requests chunk c into stage c % NS with PER_CHUNK
+// LDS-DMA instructions; chunks 0 and 1 up front, then per chunk a counted wait, the READY_c barrier and chunk c + NS - 1 into the stage
+// chunk c - 1 used.  PAIR: issue2(c) requests the riding branch's dz tile of chunk c into its two-stage ring (see wgrad_halo_body).
+template <int NS, int PER_CHUNK, bool PAIR, class Issue, class Issue2>
+static __device__ __forceinline__ void wg_loader_ring(int nch, Issue issue, Issue2 issue2) {
+    if (PAIR) issue2(0);
+    issue(0);
+    if (NS > 2 && nch > 1) issue(1);
+    for (int c = 0; c < nch; ++c) {
+        // chunk c has landed when at most the instructions of the NS - 2 younger chunks are still outstanding
+        if (NS > 2 && c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_CHUNK) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                             // READY_c (MFMA waves have finished chunk c-1)
+        if (PAIR && c + 1 < nch) issue2(c + 1);                   // into the slot chunk c-1 used
+        if (c + NS - 1 < nch) issue(c + NS - 1);                  // into the stage chunk c-1 used
     }
 }
-           // pixels per chunk = two MFMA K-steps (vpd_wgrad_split assumes 64)
+
 // NPASS: 32-row LDS-DMA passes of the x halo (NHP <= 32*NPASS).  (bx, by) = (output tile, pixel split) of this block.
 // PAIR: a second dz tile per chunk (the riding 1x1 branch, WgPair) on a two-stage ring of its own behind the NS stages.  The tile of
 // chunk c+1 goes into the slot chunk c-1 used, so it is issued behind READY_c, FIRST in that bundle: the counted wait for chunk c+1
@@ -404,44 +436,24 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
     // waves 0..7: MFMA (ci tile = wave & 3, tap half = wave >> 2: two MFMA waves share each SIMD so one computes
     // while the other waits for its LDS reads); waves 8..11: loaders
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int W = p.Ws, H = p.Hs, Wp = p.xWp, S = p.istr;
+    const int H = p.Hs, Wp = p.xWp, S = p.istr;
     const int kct = p.Kc >> 6;
     const int co0 = (bx / kct) * 64;
     const int ci0 = (bx % kct) * 64;
-    const int nchunks_total = (p.M + WG_CH - 1) / WG_CH;
-    const int chunk_begin = by * g.cpb;
-    int chunk_end = chunk_begin + g.cpb;
-    chunk_end = chunk_end < nchunks_total ? chunk_end : nchunks_total;
-    const int nch = chunk_end - chunk_begin;                      // >= 1 by construction of ksplit
+    int chunk_begin;
+    const int nch = wg_chunk_range(p.M, by, g.cpb, &chunk_begin);
 
     if (wave >= 8) {
         // ------------------------- loader waves -------------------------
         const int lw = wave - 8;
         const int piece = lane & 7;
         const int lrow = lane >> 3;                               // row within an 8-row wave instruction
-        // a dz tile: 8 wave-instructions of 8 pixel rows; two per loader wave
-        auto issue_dz = [&](const bf16_t* dz, bf16_t* dst, int ch) __attribute__((always_inline)) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = (lw + 4 * i) * 8 + lrow;
-                const int m = ch * WG_CH + row;
-                const int cpc = (((piece >> 1) ^ wg_f(row)) << 1) | (piece & 1);
-                const bf16_t* src = dz + cpc * 8;                 // zero border row of image 0: contributes nothing
-                if (m < p.M) {
-                    const int b = m / (H * W);
-                    const int r = m - b * H * W;
-                    const int yy = r / W;
-                    const int xx = r - yy * W;
-                    src = dz + ((size_t)(b * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + cpc * 8;
-                }
-                __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(dst + (lw + 4 * i) * 8 * 64), 16, 0, 0);
-            }
-        };
-        auto issue2 = [&](int c) __attribute__((always_inline)) { issue_dz(pr.dz2, ring2 + (c & 1) * WG_CH * 64, chunk_begin + c); };
+        const WgIssueDz issue_dz{p, co0, lw, piece, lrow};
+        auto issue2 = [&](int c) __attribute__((always_inline)) { issue_dz(pr.dz2, pr.dz2, ring2 + (c & 1) * WG_CH * 64, chunk_begin + c); };
         auto issue = [&](int c) __attribute__((always_inline)) {
             const int ch = chunk_begin + c;
             bf16_t* st = ring + (c % NS) * STAGE;
-            issue_dz(p.dz, st, ch);
+            issue_dz(p.dz, p.dz, st, ch);      // zero: the border row of image 0
             // x halo: 4*NPASS wave-instructions; NPASS per loader wave
             const int gr0 = ch * g.TR;
             int prow0;
@@ -453,7 +465,7 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
                 const int hp = (lw + 4 * i) * 8 + lrow;
                 int gp = gp0 + hp;
                 gp = gp < g.total_pix ? gp : g.total_pix - 1;
-                const int cpc = (((piece >> 1) ^ wg_f(hp)) << 1) | (piece & 1);
+                const int cpc = wg_src_piece(hp, piece);
                 const bf16_t* src = p.x + (size_t)gp * p.xC + ci0 + cpc * 8;
                 __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(st + WG_CH * 64 + (lw + 4 * i) * 8 * 64), 16, 0, 0);
             }
@@ -462,17 +474,7 @@ static __device__ __forceinline__ void wgrad_halo_body(const WgradParams& p, con
             for (int c = 0; c < nch; ++c) __builtin_amdgcn_s_barrier();
             return;
         }
-        if (PAIR) issue2(0);
-        issue(0);
-        if (NS > 2 && nch > 1) issue(1);
-        for (int c = 0; c < nch; ++c) {
-            // chunk c has landed when at most the instructions of the NS - 2 younger chunks are still outstanding
-            if (NS > 2 && c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_CHUNK) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                         // READY_c (MFMA waves have finished chunk c-1)
-            if (PAIR && c + 1 < nch) issue2(c + 1);               // into the slot chunk c-1 used
-            if (c + NS - 1 < nch) issue(c + NS - 1);              // into the stage chunk c-1 used
-        }
+        wg_loader_ring<NS, PER_CHUNK, PAIR>(nch, issue, issue2);
         return;
     }
 
@@ -516,7 +518,6 @@ __global__ __launch_bounds__(768) void conv_wgrad_halo_pair_kernel(const WgradPa
 #define WG_GROUP_MAX 18
 struct WgGroup {
     int nprob;
-    int xcd_remap;                             // 1: blocks of one XCD take CONSECUTIVE tasks (see the kernel)
     int task_begin[WG_GROUP_MAX + 1];          // first task of each problem
     int tiles[WG_GROUP_MAX];
     WgradParams p[WG_GROUP_MAX];
@@ -528,8 +529,7 @@ __global__ __launch_bounds__(768) void conv_wgrad_halo_grouped_kernel(const WgGr
     // dz / x chunks (different channel slices).  Workgroups go to the 8 XCDs round-robin (block b -> XCD b % 8, each
     // with its own L2), so block b takes task (b % 8) * (grid / 8) + b / 8: the tiles that share pixels then run on
     // one XCD at the same time and their operands come from its L2 instead of 4-8 separate trips to HBM.
-    int t = blockIdx.x;
-    if (grp.xcd_remap) t = (t & 7) * (gridDim.x >> 3) + (t >> 3);
+    const int t = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
     if (t >= grp.task_begin[grp.nprob]) return;                   // grid padded to a multiple of 8
     int pi = 0;
     for (int i = 1; i < grp.nprob; ++i)
@@ -541,12 +541,18 @@ __global__ __launch_bounds__(768) void conv_wgrad_halo_grouped_kernel(const WgGr
 
 // slab sums of a group in one launch: blockIdx.y = problem (problems whose blocks wrote the gradient directly have ksplit 1
 // and are skipped by the launcher)
+// dw[e] = sum over all splits of slab[split][e].  A block owns 64 float4 outputs; its `groups` thread groups each sum every
+// groups-th split (coalesced 1-KiB rows), then one LDS pass adds the groups.
 struct WgReduceGroup {
     int nprob;
     const float4* slab[WG_GROUP_MAX];
     float4* dw[WG_GROUP_MAX];
     long n4[WG_GROUP_MAX];
     int ksplit[WG_GROUP_MAX];
+    void add(const float* slab_, float* dw_, long nfloats, int ksplit_) {
+        slab[nprob] = reinterpret_cast<const float4*>(slab_); dw[nprob] = reinterpret_cast<float4*>(dw_);
+        n4[nprob] = nfloats / 4; ksplit[nprob++] = ksplit_;
+    }
 };
 __global__ __launch_bounds__(1024) void wgrad_slab_reduce_group_kernel(const WgReduceGroup r, int groups) {
     __shared__ float4 sh[16][64];
@@ -572,6 +578,19 @@ __global__ __launch_bounds__(1024) void wgrad_slab_reduce_group_kernel(const WgR
         }
         r.dw[pi][i] = a;
     }
+}
+// the slab sums of `red` (at most WG_GROUP_MAX problems; none: no launch): the thread groups are those of the problem with the most splits
+static void wg_launch_reduce(const WgReduceGroup& red, hipStream_t stream) {
+    if (red.nprob < 1) return;
+    int max_ks = 1;
+    long max_n4 = 0;
+    for (int i = 0; i < red.nprob; ++i) {
+        max_n4 = red.n4[i] > max_n4 ? red.n4[i] : max_n4;
+        max_ks = red.ksplit[i] > max_ks ? red.ksplit[i] : max_ks;
+    }
+    const int groups = max_ks < 16 ? max_ks : 16;
+    hipLaunchKernelGGL(wgrad_slab_reduce_group_kernel, dim3((unsigned)((max_n4 + 63) / 64), red.nprob), dim3(64 * groups), 0, stream,
+                       red, groups);
 }
 
 
@@ -602,9 +621,7 @@ static __device__ __forceinline__ void wgrad_stem_half(const WgradParams& p, con
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                const int r = ra + 4 * h;
-                const int col = a * 16 + 4 * pp;
-                offA[a][h] = r * 64 + ((((col >> 4) ^ wg_f(r)) << 4) | (col & 15));
+                offA[a][h] = wg_swz_off(ra + 4 * h, a * 16 + 4 * pp);
             }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -616,15 +633,6 @@ static __device__ __forceinline__ void wgrad_stem_half(const WgradParams& p, con
                 baseB[ks][h] = 64 * 64 + (2 * lr * Wp + 2 * xx) * 8 + ctile * 16 + 4 * pp;
             }
     }
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    auto frag = [&](const bf16_t* st, int o0, int o1) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(st + o0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(st + o1));
-        s16x8 v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-        v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return __builtin_bit_cast(bf16x8, v);
-    };
     for (int c = 0; c < nch; ++c) {
         __builtin_amdgcn_s_barrier();                             // READY_c
         const bf16_t* st = ring + (c % 3) * STAGE;
@@ -632,11 +640,11 @@ static __device__ __forceinline__ void wgrad_stem_half(const WgradParams& p, con
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 az[4], bx[NT];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) az[a] = frag(st + ks * 32 * 64, offA[a][0], offA[a][1]);
+            for (int a = 0; a < 4; ++a) az[a] = wg_tr_read(st + ks * 32 * 64, offA[a][0], offA[a][1]);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int ro = (R0 + t) * Wp * 8;
-                bx[t] = frag(st, baseB[ks][0] + ro, baseB[ks][1] + ro);
+                bx[t] = wg_tr_read(st, baseB[ks][0] + ro, baseB[ks][1] + ro);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -650,11 +658,7 @@ static __device__ __forceinline__ void wgrad_stem_half(const WgradParams& p, con
     float* slab = p.slab + (size_t)blockIdx.y * 7 * 64 * 64;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        float* o = slab + ((size_t)(R0 + t) * 64) * 64 + 16 * ctile + i16;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * 64] = acc[t][a][j];
+        wg_store_tile(slab + ((size_t)(R0 + t) * 64) * 64 + 16 * ctile + i16, 64, acc[t], gq);
     }
 }
 
@@ -667,35 +671,20 @@ __global__ __launch_bounds__(768) void conv_wgrad_stem_kernel(const WgradParams 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int W0 = p.Ws, H0 = p.Hs;
-    const int nchunks_total = (p.M + 63) / 64;
-    const int chunk_begin = blockIdx.y * cpb;
-    int chunk_end = chunk_begin + cpb;
-    chunk_end = chunk_end < nchunks_total ? chunk_end : nchunks_total;
-    const int nch = chunk_end - chunk_begin;
+    const int H0 = p.Hs;
+    int chunk_begin;
+    const int nch = wg_chunk_range(p.M, blockIdx.y, cpb, &chunk_begin);
 
     if (wave >= 8) {
         const int lw = wave - 8;
         const int piece = lane & 7;
         const int lrow = lane >> 3;
+        const int co0 = 0;                                        // all 64 output channels
+        const WgIssueDz issue_dz{p, co0, lw, piece, lrow};
         auto issue = [&](int c) __attribute__((always_inline)) {
             const int ch = chunk_begin + c;
             bf16_t* st = ring + (c % 3) * STAGE;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = (lw + 4 * i) * 8 + lrow;
-                const int m = ch * 64 + row;
-                const int cpc = (((piece >> 1) ^ wg_f(row)) << 1) | (piece & 1);
-                const bf16_t* src = p.x + cpc * 8;                 // top border rows of image 0 are zero
-                if (m < p.M) {
-                    const int b = m / (H0 * W0);
-                    const int r = m - b * H0 * W0;
-                    const int yy = r / W0;
-                    const int xx = r - yy * W0;
-                    src = p.dz + ((size_t)(b * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + cpc * 8;
-                }
-                __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(st + (lw + 4 * i) * 8 * 64), 16, 0, 0);
-            }
+            issue_dz(p.dz, p.x, st, ch);      // zero: the top border rows of image 0 of the INPUT (dz has no border)
             const int gr0 = ch * TR;
             const int b = gr0 / H0, y0 = gr0 - b * H0;
             const long e0 = ((long)(b * p.xHp + 2 * y0) * p.xWp) * 8;
@@ -707,19 +696,21 @@ __global__ __launch_bounds__(768) void conv_wgrad_stem_kernel(const WgradParams 
                 __builtin_amdgcn_global_load_lds((wg_gptr_t)(p.x + e), (wg_lptr_t)(st + 64 * 64 + (lw + 4 * i) * 8 * 64), 16, 0, 0);
             }
         };
-        issue(0);
-        if (nch > 1) issue(1);
-        for (int c = 0; c < nch; ++c) {
-            if (c + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_CHUNK) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (c + 2 < nch) issue(c + 2);
-        }
+        wg_loader_ring<3, PER_CHUNK, false>(nch, issue, [](int) {});
         return;
     }
     const int ctile = wave & 3;
     if (wave < 4) wgrad_stem_half<0, 4>(p, ring, STAGE, nch, ctile, lane);
     else wgrad_stem_half<4, 7>(p, ring, STAGE, nch, ctile, lane);
+}
+
+// ---- host side of the atomics, halo and stem kernels: routing, geometry, launchers ----
+static int wg_ablate() {
+#ifdef VPD_ENABLE_ABLATE
+    return vpd_switches().ablate;
+#else
+    return 0;
+#endif
 }
 
 static bool wg_stem_eligible(const WgradParams& p, int* TR) {
@@ -732,58 +723,32 @@ static bool wg_stem_eligible(const WgradParams& p, int* TR) {
     return ((2 * *TR + 5) * p.xWp + 7) / 8 <= 128;
 }
 
-// dw[e] = sum over all splits of slab[split][e].  A block owns 64 float4 outputs; its `groups` thread
-// groups each sum every groups-th split (coalesced 1-KiB rows), then one LDS pass adds the groups.
-__global__ __launch_bounds__(1024) void wgrad_slab_reduce_kernel(const float4* slab, float4* dw, long n4, int ksplit,
-                                                                 int groups) {
-    __shared__ float4 sh[16][64];
-    const int o = threadIdx.x & 63, gi = threadIdx.x >> 6;
-    const long i = (long)blockIdx.x * 64 + o;
-    float4 a = {0.f, 0.f, 0.f, 0.f};
-    if (i < n4)
-        for (int s = gi; s < ksplit; s += groups) {
-            const float4 v = slab[(long)s * n4 + i];
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-    sh[gi][o] = a;
-    __syncthreads();
-    if (gi == 0 && i < n4) {
-        for (int k = 1; k < groups; ++k) {
-            const float4 v = sh[k][o];
-            a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-        }
-        dw[i] = a;
-    }
-}
-
-// halo of a 64-output-pixel chunk: rows of the padded INPUT plane(s); stride 1 or 2 (3x3, pad 1)
-static bool wg_halo_geom(const WgradParams& p, WgHaloGeom* g) {
-    const int W = p.Ws, H = p.Hs, S = p.istr;
+// Tiling of H x W OUTPUT planes (stride S, padded input planes xHp x xWp) into 64-pixel chunks of whole rows: TR rows per chunk, or
+// (multi) TR / H whole images; HR x xWp = NHP padded input pixels hold the 3x3 halo of a chunk.
+static bool wg_chunk_tiling(int H, int W, int S, int xHp, int xWp, WgHaloGeom* g) {
     if (W <= 0 || WG_CH % W != 0 || (S != 1 && S != 2)) return false;
     const int TR = WG_CH / W;
     if (TR <= H) { if (H % TR != 0) return false; g->multi = 0; g->HR = S * (TR - 1) + 3; }
-    else { if (TR % H != 0) return false; g->multi = 1; g->HR = (TR / H) * p.xHp; }
+    else { if (TR % H != 0) return false; g->multi = 1; g->HR = (TR / H) * xHp; }
     g->TR = TR;
-    g->NHP = g->HR * p.xWp;
+    g->NHP = g->HR * xWp;
+    return true;
+}
+// ... whose halo the halo kernel can stage (5 passes at stride 1, 13 at stride 2)
+static bool wg_halo_tiling(int H, int W, int S, int xHp, int xWp, WgHaloGeom* g) {
+    return wg_chunk_tiling(H, W, S, xHp, xWp, g) && g->NHP <= (S == 1 ? 160 : 416);
+}
+static bool wg_halo_geom(const WgradParams& p, WgHaloGeom* g) {
     g->total_pix = p.N * p.xHp * p.xWp;
-    return g->NHP <= (S == 1 ? 160 : 416);
+    return wg_halo_tiling(p.Hs, p.Ws, p.istr, p.xHp, p.xWp, g);
 }
-
-// shape test of the halo kernel for a 3x3 stride-1 conv with Hout x Wout outputs (independent of the batch size)
+// shape test of the halo kernel for a 3x3 pad-1 conv with H x W outputs (independent of the batch size)
 bool vpd_wgrad_halo_shape_ok(int H, int W, int stride, int Hin, int Win) {
-    const int no_s2 = !vpd_switches().wgrad_s2;
-    if (W <= 0 || WG_CH % W != 0) return false;
-    if (stride == 2 && (no_s2 || Hin != 2 * H || Win != 2 * W)) return false;
-    if (stride != 1 && stride != 2) return false;
-    const int TR = WG_CH / W;
-    int HR;
-    if (TR <= H) { if (H % TR != 0) return false; HR = stride * (TR - 1) + 3; }
-    else { if (TR % H != 0) return false; HR = (TR / H) * (Hin + 2); }
-    return HR * (Win + 2) <= (stride == 1 ? 160 : 416);
+    if (stride == 2 && (!vpd_switches().wgrad_s2 || Hin != 2 * H || Win != 2 * W)) return false;
+    WgHaloGeom g;
+    return wg_halo_tiling(H, W, stride, Hin + 2, Win + 2, &g);
 }
 
-// true when vpd_launch_wgrad will take the halo + slab path, which OVERWRITES dw (no pre-zeroing needed)
-static bool wg_stem_eligible(const WgradParams& p, int* TR);
 // A 1x1 pad-0 convolution in the caller's terms (one tap at padded offset (1, 1)) rewritten as the centre tap of the
 // 3x3 halo form; false when `p` is not such a conv.
 static bool wg_as_one_by_one(const WgradParams& p, WgradParams* q) {
@@ -794,39 +759,72 @@ static bool wg_as_one_by_one(const WgradParams& p, WgradParams* q) {
     q->one_by_one = 1;
     return true;
 }
-bool vpd_wgrad_overwrites(const WgradParams& p0) {
-    int tr_stem;
-    if (wg_stem_eligible(p0, &tr_stem)) return true;
-    const int no_s2 = !vpd_switches().wgrad_s2;
+
+// Which kernel takes a problem stated in the caller's terms.  Every kernel but the atomics one OVERWRITES dw (no pre-zeroing needed).
+enum WgKernel { WG_ATOMICS, WG_STEM, WG_HALO_3X3, WG_HALO_1X1 };
+struct WgRoute {
+    WgKernel kernel;
+    WgradParams p;                       // as the kernel takes it: a 1x1 on the halo kernel is rewritten (wg_as_one_by_one)
+    WgHaloGeom g;                        // halo kernels: the tiling (ksplit, cpb left to the launcher)
+    int tr_stem;                         // stem kernel: output rows per chunk
+    bool halo() const { return kernel == WG_HALO_3X3 || kernel == WG_HALO_1X1; }
+};
+static WgRoute wg_route(const WgradParams& p0) {
+    WgRoute r;
+    r.kernel = WG_ATOMICS; r.p = p0; r.g = WgHaloGeom{}; r.tr_stem = 0;
+    if (wg_stem_eligible(p0, &r.tr_stem)) { r.kernel = WG_STEM; return r; }
+    WgradParams p = p0;
     // 1x1 convolutions on the halo kernel (centre tap), no atomics.  As ONE launch per conv it is no faster than the atomics
     // kernel (both run at the ~4 TB/s their operand streams allow; ResNet-50: 9.90 vs 9.55 ms per step, ResNet-34: +12 us),
     // but it OVERWRITES its output and adds in a fixed order.  Default: ON where the caller asks for it (WgradParams::
     // prefer_halo_1x1 -- the plan sets it for the BasicBlock students, whose three down-sampling convs were the last fp32
     // atomics of the step: the ResNet-18/34 step is now reproducible bit for bit), otherwise off; VPD_WGRAD_1X1=0/1 forces.
-    const int env_1x1 = vpd_switches().wgrad_1x1;
-    const int no_1x1 = env_1x1 >= 0 ? !env_1x1 : !p0.prefer_halo_1x1;
-    WgradParams p = p0;
-    if (wg_as_one_by_one(p0, &p) && no_1x1) return false;
-    WgHaloGeom g;
+    if (wg_as_one_by_one(p0, &p)) {
+        const int env_1x1 = vpd_switches().wgrad_1x1;
+        if (env_1x1 >= 0 ? !env_1x1 : !p0.prefer_halo_1x1) return r;
+    }
     const bool s1 = p.istr == 1 && p.xHp == p.Hs + 2 && p.xWp == p.Ws + 2;
     // stride 2 (3x3 pad 1 / 1x1 pad 0, even input): taps 0..2 in padded input coordinates, forward order only
-    const bool s2 = !no_s2 && p.istr == 2 && p.xHp == 2 * p.Hs + 2 && p.xWp == 2 * p.Ws + 2 && p.taps.dy0 == 0 &&
+    const bool s2 = vpd_switches().wgrad_s2 && p.istr == 2 && p.xHp == 2 * p.Hs + 2 && p.xWp == 2 * p.Ws + 2 && p.taps.dy0 == 0 &&
                     p.taps.dys == 1 && p.taps.dx0 == 0 && p.taps.dxs == 1;
-    return p.slab && p.taps.nr == 3 && p.taps.nc == 3 && (s1 || s2) && p.xC == p.Kc && p.taps.dy0 >= 0 &&
-           p.taps.dy0 + 2 * p.taps.dys >= 0 && p.taps.dy0 <= 2 &&
-           p.taps.dy0 + 2 * p.taps.dys <= 2 && p.taps.dx0 >= 0 && p.taps.dx0 + 2 * p.taps.dxs >= 0 && p.taps.dx0 <= 2 &&
-           p.taps.dx0 + 2 * p.taps.dxs <= 2 && wg_halo_geom(p, &g);
+    if (!(p.slab && p.taps.nr == 3 && p.taps.nc == 3 && (s1 || s2) && p.xC == p.Kc && p.taps.dy0 >= 0 &&
+          p.taps.dy0 + 2 * p.taps.dys >= 0 && p.taps.dy0 <= 2 &&
+          p.taps.dy0 + 2 * p.taps.dys <= 2 && p.taps.dx0 >= 0 && p.taps.dx0 + 2 * p.taps.dxs >= 0 && p.taps.dx0 <= 2 &&
+          p.taps.dx0 + 2 * p.taps.dxs <= 2 && wg_halo_geom(p, &r.g)))
+        return r;
+    r.kernel = p.one_by_one ? WG_HALO_1X1 : WG_HALO_3X3;
+    r.p = p;
+    return r;
 }
+// ... for a test that does not depend on the slab address
+static WgRoute wg_route_any_slab(const WgradParams& p) {
+    WgradParams q = p;
+    if (!q.slab) q.slab = reinterpret_cast<float*>(16);
+    return wg_route(q);
+}
+bool vpd_wgrad_overwrites(const WgradParams& p) { return wg_route(p).kernel != WG_ATOMICS; }
 
 size_t vpd_wgrad_slab_bytes() { return (size_t)256 * 9 * 64 * 64 * sizeof(float); }   // ksplit * tiles <= 256
 
 hipError_t vpd_launch_wgrad_reduce(const WgradParams& p, hipStream_t stream) {
-    const int ksplit = vpd_wgrad_split(p.M, p.Co, p.Kc, nullptr);
-    const long n4 = (long)(p.taps.nr == 1 ? 1 : 9) * p.Co * p.Kc / 4;
-    const int groups = ksplit < 16 ? ksplit : 16;
-    hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(64 * groups), 0, stream,
-                       (const float4*)p.slab, (float4*)p.dw, n4, ksplit, groups);
+    WgReduceGroup red = {};
+    red.add(p.slab, p.dw, (long)(p.taps.nr == 1 ? 1 : 9) * p.Co * p.Kc, vpd_wgrad_split(p.M, p.Co, p.Kc, nullptr));
+    wg_launch_reduce(red, stream);
     return hipGetLastError();
+}
+
+// Dynamic LDS of a halo launch: `ns` stages of a dz tile and `npass` 32-row halo passes; (pair) the branch's two dz tiles behind them
+static size_t wg_ring_lds(int npass, int ns, bool pair) {
+    return ((size_t)ns * (WG_CH + 32 * npass) + (pair ? 2 * WG_CH : 0)) * 64 * sizeof(bf16_t);
+}
+// f(integral_constant<int, NPASS>) for the instantiation that stages `npass` halo passes: 3, 4, 5 (stride 1), 10 or 13 (stride 2)
+template <class F>
+static void wg_npass_dispatch(int npass, F f) {
+    if (npass <= 3) f(std::integral_constant<int, 3>{});
+    else if (npass == 4) f(std::integral_constant<int, 4>{});
+    else if (npass == 5) f(std::integral_constant<int, 5>{});
+    else if (npass <= 10) f(std::integral_constant<int, 10>{});
+    else f(std::integral_constant<int, 13>{});
 }
 
 // ---- grouped launch (see WgGroup) ----
@@ -834,10 +832,7 @@ hipError_t vpd_launch_wgrad_reduce(const WgradParams& p, hipStream_t stream) {
 // first costs a 9*64*64 fp32 partial written to the slab and read back.  Tasks run in rounds of one per CU, so the cost
 // of a choice is  rounds * (chunks_per_task * t_chunk + t_fixed) + slab bytes * 2 / bandwidth (+ the reduce launch),
 // with the measured t_chunk 1.0 us (grouped launches: 124-242 us for 252 x 114 ... 176 x 256 chunk tasks), t_fixed 4 us,
-// 4.5 TB/s.  Every task size from 8 to 512 chunks is tried; VPD_WG_GROUP_CPB pins the size instead.
-static int wg_group_cpb_env() {
-    return 0;
-}
+// 4.5 TB/s.  Every task size from 8 to 512 chunks is tried.
 // splits a problem may use at most: its slab share is capped at 16 MB (plan-time allocation)
 int vpd_wgrad_group_max_splits(int Co, int Kc, int ntaps) {
     const size_t per = (size_t)ntaps * Co * Kc * 4;
@@ -845,35 +840,36 @@ int vpd_wgrad_group_max_splits(int Co, int Kc, int ntaps) {
     if (cap > 64) cap = 64;
     return cap < 2 ? 1 : (int)cap;
 }
-size_t vpd_wgrad_group_slab_floats(int M, int Co, int Kc, int ntaps) {
-    (void)M;
+size_t vpd_wgrad_group_slab_floats(int, int Co, int Kc, int ntaps) {
     const int cap = vpd_wgrad_group_max_splits(Co, Kc, ntaps);
     return cap <= 1 ? 0 : (size_t)cap * ntaps * Co * Kc;
 }
+// splits of `nch` chunks (at most `cap`) for tasks of about `target` chunks: equal tasks of *cpb chunks, the last one maybe shorter
+static int wg_split_for_target(int nch, int cap, double target, int* cpb) {
+    int k = (int)(nch / target + 0.5);
+    k = k < 1 ? 1 : (k > cap ? cap : k);
+    *cpb = (nch + k - 1) / k;
+    return (nch + *cpb - 1) / *cpb;
+}
 static void wg_group_choose(const WgradParams* ps, int n, int* ksplit) {
     int nch[WG_GROUP_MAX], tiles[WG_GROUP_MAX], cap[WG_GROUP_MAX];
-    double work = 0.0;
     for (int i = 0; i < n; ++i) {
         nch[i] = (ps[i].M + WG_CH - 1) / WG_CH;
         tiles[i] = (ps[i].Co / 64) * (ps[i].Kc / 64);
         cap[i] = vpd_wgrad_group_max_splits(ps[i].Co, ps[i].Kc, 9);
         if (cap[i] > nch[i]) cap[i] = nch[i];
-        work += (double)nch[i] * tiles[i];
     }
     const double t_chunk = 1.0, t_fixed = 4.0, bw = 4.5e6;       // us, us, bytes per us
     double best = 1e30;
-    auto eval = [&](double target) {
+    for (int target = 8; target <= 512; target += (target < 128 ? 1 : 4)) {
         int ks[WG_GROUP_MAX];
         long tasks = 0;
         int max_cpb = 0;
         double slab = 0.0;
         bool any = false;
         for (int i = 0; i < n; ++i) {
-            int k = (int)(nch[i] / target + 0.5);
-            k = k < 1 ? 1 : (k > cap[i] ? cap[i] : k);
-            const int cpb = (nch[i] + k - 1) / k;
-            k = (nch[i] + cpb - 1) / cpb;
-            ks[i] = k;
+            int cpb;
+            const int k = ks[i] = wg_split_for_target(nch[i], cap[i], (double)target, &cpb);
             tasks += (long)tiles[i] * k;
             max_cpb = cpb > max_cpb ? cpb : max_cpb;
             if (k > 1) { slab += (double)k * 9 * ps[i].Co * ps[i].Kc * 4; any = true; }
@@ -883,32 +879,19 @@ static void wg_group_choose(const WgradParams* ps, int n, int* ksplit) {
             best = cost;
             for (int i = 0; i < n; ++i) ksplit[i] = ks[i];
         }
-    };
-    if (wg_group_cpb_env() > 0) { eval((double)wg_group_cpb_env()); return; }
-    (void)work;
-    for (int cpb = 8; cpb <= 512; cpb += (cpb < 128 ? 1 : 4)) eval((double)cpb);
+    }
 }
-bool vpd_wgrad_group_eligible(const WgradParams& p) {
-    WgHaloGeom g;
-    WgradParams q = p;
-    if (!q.slab) q.slab = reinterpret_cast<float*>(16);          // eligibility does not depend on the slab address
-    return vpd_wgrad_overwrites(q) && wg_halo_geom(q, &g);
-}
+bool vpd_wgrad_group_eligible(const WgradParams& p) { return wg_route_any_slab(p).halo(); }
 // ps[i].slab must point to vpd_wgrad_group_slab_floats() floats of its own (ignored when that is 0)
 hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stream) {
     if (n < 1 || n > WG_GROUP_MAX) return hipErrorInvalidValue;
-#ifdef VPD_ENABLE_ABLATE
-    const int ablate = vpd_switches().ablate;
-#else
-    constexpr int ablate = 0;
-#endif
+    const int ablate = wg_ablate();
     WgGroup grp = {};
     WgReduceGroup red = {};
     grp.nprob = n;
     int ks[WG_GROUP_MAX];
     wg_group_choose(ps, n, ks);
-    int tasks = 0, npass = 0, max_ks = 1;
-    long max_n4 = 0;
+    int tasks = 0, npass = 0;
     for (int i = 0; i < n; ++i) {
         WgradParams p = ps[i];
         p.ablate = ablate;
@@ -921,15 +904,7 @@ hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stre
         g.ksplit = ks[i];
         g.cpb = (nchunks + g.ksplit - 1) / g.ksplit;
         if (g.ksplit <= 1) p.slab = p.dw;                         // split 0 of a 1-split problem IS the gradient
-        else {
-            red.slab[red.nprob] = reinterpret_cast<const float4*>(p.slab);
-            red.dw[red.nprob] = reinterpret_cast<float4*>(p.dw);
-            red.n4[red.nprob] = (long)9 * p.Co * p.Kc / 4;
-            red.ksplit[red.nprob] = g.ksplit;
-            max_n4 = red.n4[red.nprob] > max_n4 ? red.n4[red.nprob] : max_n4;
-            max_ks = g.ksplit > max_ks ? g.ksplit : max_ks;
-            ++red.nprob;
-        }
+        else red.add(p.slab, p.dw, (long)9 * p.Co * p.Kc, g.ksplit);
         grp.tiles[i] = (p.Co / 64) * (p.Kc / 64);
         grp.task_begin[i] = tasks;
         tasks += grp.tiles[i] * g.ksplit;
@@ -937,61 +912,44 @@ hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stre
         grp.g[i] = g;
     }
     grp.task_begin[n] = tasks;
-    const int remap = 1;      // (tasks that share pixels on one XCD's L2)
-    grp.xcd_remap = remap;
-    const int grid = remap ? ((tasks + 7) / 8) * 8 : tasks;
-    const size_t lds = (size_t)WG_NS * (WG_CH + 32 * (npass <= 3 ? 3 : npass)) * 64 * sizeof(bf16_t);
-    if (npass <= 3) VPD_LAUNCH(conv_wgrad_halo_grouped_kernel<3>, dim3(grid), dim3(768), lds, stream, grp);
-    else if (npass == 4) VPD_LAUNCH(conv_wgrad_halo_grouped_kernel<4>, dim3(grid), dim3(768), lds, stream, grp);
-    else VPD_LAUNCH(conv_wgrad_halo_grouped_kernel<5>, dim3(grid), dim3(768), lds, stream, grp);
-    if (red.nprob > 0 && !(ablate & 16)) {
-        const int groups = max_ks < 16 ? max_ks : 16;
-        hipLaunchKernelGGL(wgrad_slab_reduce_group_kernel, dim3((unsigned)((max_n4 + 63) / 64), red.nprob), dim3(64 * groups),
-                           0, stream, red, groups);
-    }
+    const int grid = ((tasks + 7) / 8) * 8;                       // (the kernel's XCD remap wants a multiple of 8)
+    // a stage's stride-1 convolutions: 3..5 passes (the group has no instantiation beyond 5)
+    const size_t lds = wg_ring_lds(npass <= 3 ? 3 : npass, WG_NS, false);
+    wg_npass_dispatch(npass, [&](auto np) {
+        constexpr int NP = decltype(np)::value > 5 ? 5 : decltype(np)::value;
+        VPD_LAUNCH(conv_wgrad_halo_grouped_kernel<NP>, dim3(grid), dim3(768), lds, stream, grp);
+    });
+    if (!(ablate & 16)) wg_launch_reduce(red, stream);
     return hipGetLastError();
 }
 
 hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
     if (p0.Kc % 64 != 0 || p0.Co % 64 != 0 || p0.M <= 0) return hipErrorInvalidValue;
-    WgradParams p = p0;
-#ifdef VPD_ENABLE_ABLATE
-    const int ablate = vpd_switches().ablate;
-#else
-    constexpr int ablate = 0;
-#endif
-    p.ablate = ablate;
-    int tr_stem;
-    if (wg_stem_eligible(p, &tr_stem)) {
+    const WgRoute r = wg_route(p0);
+    WgradParams p = r.p;
+    p.ablate = wg_ablate();
+    if (r.kernel == WG_STEM) {
         const int nchunks = p.M / 64;
         int ksplit = nchunks < 256 ? nchunks : 256;
         const int cpb = (nchunks + ksplit - 1) / ksplit;
         ksplit = (nchunks + cpb - 1) / cpb;
-        const size_t lds = (size_t)3 * (64 + 128) * 64 * sizeof(bf16_t);
         const long xelems = (long)p.N * p.xHp * p.xWp * 8 + 64;
-        VPD_LAUNCH(conv_wgrad_stem_kernel, dim3(1, ksplit), dim3(768), lds, stream, p, tr_stem, cpb, xelems);
-        const long n4 = (long)7 * 64 * 64 / 4;
-        const int groups = ksplit < 16 ? ksplit : 16;
-        hipLaunchKernelGGL(wgrad_slab_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(64 * groups), 0, stream,
-                           (const float4*)p.slab, (float4*)p.dw, n4, ksplit, groups);
+        VPD_LAUNCH(conv_wgrad_stem_kernel, dim3(1, ksplit), dim3(768), wg_ring_lds(4, 3, false), stream, p, r.tr_stem, cpb, xelems);
+        WgReduceGroup red = {};
+        red.add(p.slab, p.dw, (long)7 * 64 * 64, ksplit);
+        wg_launch_reduce(red, stream);
         return hipGetLastError();
     }
-    WgHaloGeom g;
-    if (vpd_wgrad_overwrites(p)) {
-        WgradParams q1;
-        if (wg_as_one_by_one(p, &q1)) p = q1;
-    }
-    if (vpd_wgrad_overwrites(p0) && wg_halo_geom(p, &g)) {
+    if (r.halo()) {
+        WgHaloGeom g = r.g;
         const int tiles = (p.Co / 64) * (p.Kc / 64);
         g.ksplit = vpd_wgrad_split(p.M, p.Co, p.Kc, &g.cpb);
         const int npass = (g.NHP + 31) / 32;            // 3..5 (stride 1), up to 10 / 13 (stride 2)
-        const int ns = npass > 10 ? 2 : WG_NS;          // the 13-pass halo (layer4.0: four whole input planes) leaves room for two stages
-        const size_t lds = (size_t)ns * (WG_CH + 32 * (npass <= 5 ? npass : (npass <= 10 ? 10 : 13))) * 64 * sizeof(bf16_t);
-        if (npass <= 3) VPD_LAUNCH(conv_wgrad_halo_kernel<3>, dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g);
-        else if (npass == 4) VPD_LAUNCH(conv_wgrad_halo_kernel<4>, dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g);
-        else if (npass == 5) VPD_LAUNCH(conv_wgrad_halo_kernel<5>, dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g);
-        else if (npass <= 10) VPD_LAUNCH((conv_wgrad_halo_kernel<10, 3>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g);
-        else VPD_LAUNCH((conv_wgrad_halo_kernel<13, 2>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g);
+        wg_npass_dispatch(npass, [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            constexpr int NS = NP > 10 ? 2 : WG_NS;     // the 13-pass halo (layer4.0: four whole input planes) leaves room for two stages
+            VPD_LAUNCH((conv_wgrad_halo_kernel<NP, NS>), dim3(tiles, g.ksplit), dim3(768), wg_ring_lds(NP, NS, false), stream, p, g);
+        });
         if (p.defer_reduce || VPD_ABL(p, 16)) return hipGetLastError();
         return vpd_launch_wgrad_reduce(p0, stream);
     }
@@ -1016,68 +974,62 @@ hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
 #ifndef VPD_WG_PAIR_NS
 #define VPD_WG_PAIR_NS 3      // stages of the dz + halo ring of the 10-pass pair launch (-DVPD_WG_PAIR_NS=2: two stages of everything)
 #endif
-// Dynamic LDS of a pair launch whose halo takes `npass` 32-row passes on an `ns`-stage ring, the branch's two dz tiles behind it.
-// false: more than the 160 KB of a CU -- such a layout is never launched.
+// Dynamic LDS of a pair launch whose halo takes `npass` 32-row passes on an `ns`-stage ring (ns 0: the launcher's ring depth), the
+// branch's two dz tiles behind it.  false: more than the 160 KB of a CU -- such a layout is never launched.
 static bool wg_pair_lds(int npass, int ns, size_t* bytes) {
-    const int rows = WG_CH + 32 * (npass <= 10 ? 10 : 13);
-    *bytes = ((size_t)ns * rows + 2 * WG_CH) * 64 * sizeof(bf16_t);
+    if (ns <= 0) ns = npass > 10 ? 2 : VPD_WG_PAIR_NS;
+    *bytes = wg_ring_lds(npass <= 10 ? 10 : 13, ns, true);
     return ns >= 2 && npass <= 13 && *bytes <= (size_t)160 * 1024;
 }
 // Host-only: the LDS bytes of the pair launch for an H x W OUTPUT (input 2H x 2W, border 1).  ns 0: the launcher's ring depth.
 // 0: fits; 1: the layout is over 160 KB (the launcher refuses it); -1: no halo geometry for this output size.
 int vpd_wgrad_pair_lds_query(int H, int W, int ns, long long* bytes) {
-    WgradParams p;
-    memset(&p, 0, sizeof p);
-    p.N = 1; p.Hs = H; p.Ws = W; p.istr = 2; p.xHp = 2 * H + 2; p.xWp = 2 * W + 2;
     WgHaloGeom g;
-    if (H <= 0 || !wg_halo_geom(p, &g)) return -1;
-    const int npass = (g.NHP + 31) / 32;
+    if (H <= 0 || !wg_halo_tiling(H, W, 2, 2 * H + 2, 2 * W + 2, &g)) return -1;
     size_t b = 0;
-    const bool ok = wg_pair_lds(npass, ns > 0 ? ns : (npass > 10 ? 2 : VPD_WG_PAIR_NS), &b);
+    const bool ok = wg_pair_lds((g.NHP + 31) / 32, ns, &b);
     if (bytes) *bytes = (long long)b;
     return ok ? 0 : 1;
 }
-bool vpd_wgrad_pair_ok(const WgradParams& p3, const WgradParams& p1) {
-    if (!vpd_switches().wgrad_ds_ride) return false;
-    WgradParams q1;
-    if (!vpd_wgrad_overwrites(p3) || !vpd_wgrad_overwrites(p1) || !wg_as_one_by_one(p1, &q1)) return false;
-    if (p3.one_by_one || p3.taps.nr != 3 || p3.taps.nc != 3 || p3.istr != 2 || p3.Kc % 64 != 0 || p3.Co % 64 != 0 || p3.M <= 0) return false;
-    return p1.x == p3.x && p1.xHp == p3.xHp && p1.xWp == p3.xWp && p1.xC == p3.xC && p1.N == p3.N && p1.Hs == p3.Hs &&
-           p1.Ws == p3.Ws && p1.istr == p3.istr && p1.Kc == p3.Kc && p1.Co == p3.Co && p1.M == p3.M && p1.dzHp == p3.dzHp &&
-           p1.dzWp == p3.dzWp && p1.dzC == p3.dzC && p1.dzpad == p3.dzpad;
+// p3's route when (p3, p1) can share a launch, else the atomics route
+static WgRoute wg_pair_route(const WgradParams& p3, const WgradParams& p1) {
+    WgRoute none = {};
+    none.kernel = WG_ATOMICS;
+    if (!vpd_switches().wgrad_ds_ride) return none;
+    const WgRoute r3 = wg_route(p3);
+    if (r3.kernel != WG_HALO_3X3 || wg_route(p1).kernel != WG_HALO_1X1 || p1.one_by_one) return none;
+    if (p3.istr != 2 || p3.Kc % 64 != 0 || p3.Co % 64 != 0 || p3.M <= 0) return none;
+    const bool same = p1.x == p3.x && p1.xHp == p3.xHp && p1.xWp == p3.xWp && p1.xC == p3.xC && p1.N == p3.N && p1.Hs == p3.Hs &&
+                      p1.Ws == p3.Ws && p1.istr == p3.istr && p1.Kc == p3.Kc && p1.Co == p3.Co && p1.M == p3.M && p1.dzHp == p3.dzHp &&
+                      p1.dzWp == p3.dzWp && p1.dzC == p3.dzC && p1.dzpad == p3.dzpad;
+    return same ? r3 : none;
 }
-// one launch sums both slabs: the same split and the same groups as the two wgrad_slab_reduce_kernel launches, element by element
+bool vpd_wgrad_pair_ok(const WgradParams& p3, const WgradParams& p1) { return wg_pair_route(p3, p1).halo(); }
+// one launch sums both slabs: the same split and the same thread groups as a launch of vpd_launch_wgrad_reduce each, element by element
 hipError_t vpd_launch_wgrad_pair_reduce(const WgradParams& p3, const WgradParams& p1, hipStream_t stream) {
     const int ksplit = vpd_wgrad_split(p3.M, p3.Co, p3.Kc, nullptr);
     WgReduceGroup red = {};
-    red.nprob = 2;
-    red.slab[0] = reinterpret_cast<const float4*>(p3.slab); red.dw[0] = reinterpret_cast<float4*>(p3.dw);
-    red.slab[1] = reinterpret_cast<const float4*>(p1.slab); red.dw[1] = reinterpret_cast<float4*>(p1.dw);
-    red.n4[0] = (long)9 * p3.Co * p3.Kc / 4; red.n4[1] = (long)p3.Co * p3.Kc / 4;
-    red.ksplit[0] = red.ksplit[1] = ksplit;
-    const int groups = ksplit < 16 ? ksplit : 16;
-    hipLaunchKernelGGL(wgrad_slab_reduce_group_kernel, dim3((unsigned)((red.n4[0] + 63) / 64), 2), dim3(64 * groups), 0, stream, red,
-                       groups);
+    red.add(p3.slab, p3.dw, (long)9 * p3.Co * p3.Kc, ksplit);
+    red.add(p1.slab, p1.dw, (long)p3.Co * p3.Kc, ksplit);
+    wg_launch_reduce(red, stream);
     return hipGetLastError();
 }
 hipError_t vpd_launch_wgrad_pair(const WgradParams& p3, const WgradParams& p1, hipStream_t stream) {
-    if (!vpd_wgrad_pair_ok(p3, p1)) return hipErrorInvalidValue;
-    WgradParams p = p3;
-#ifdef VPD_ENABLE_ABLATE
-    p.ablate = vpd_switches().ablate;
-#else
-    p.ablate = 0;
-#endif
-    WgHaloGeom g;
-    if (!wg_halo_geom(p, &g)) return hipErrorInvalidValue;
+    const WgRoute r = wg_pair_route(p3, p1);
+    if (!r.halo()) return hipErrorInvalidValue;
+    WgradParams p = r.p;
+    p.ablate = wg_ablate();
+    WgHaloGeom g = r.g;
     const int tiles = (p.Co / 64) * (p.Kc / 64);
     g.ksplit = vpd_wgrad_split(p.M, p.Co, p.Kc, &g.cpb);
     const int npass = (g.NHP + 31) / 32;
     size_t lds = 0;
-    if (!wg_pair_lds(npass, npass > 10 ? 2 : VPD_WG_PAIR_NS, &lds)) return hipErrorInvalidValue;
+    if (!wg_pair_lds(npass, 0, &lds)) return hipErrorInvalidValue;
     const WgPair pr{p1.dz, p1.slab};
-    if (npass <= 10) VPD_LAUNCH((conv_wgrad_halo_pair_kernel<10, VPD_WG_PAIR_NS>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g, pr);
-    else VPD_LAUNCH((conv_wgrad_halo_pair_kernel<13, 2>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g, pr);
+    wg_npass_dispatch(npass, [&](auto np) {
+        constexpr int NP = decltype(np)::value <= 10 ? 10 : 13;
+        VPD_LAUNCH((conv_wgrad_halo_pair_kernel<NP, (NP > 10 ? 2 : VPD_WG_PAIR_NS)>), dim3(tiles, g.ksplit), dim3(768), lds, stream, p, g, pr);
+    });
     if (p.defer_reduce || VPD_ABL(p, 16)) return hipGetLastError();
     return vpd_launch_wgrad_pair_reduce(p3, p1, stream);
 }
@@ -1101,12 +1053,12 @@ hipError_t vpd_launch_wgrad_pair(const WgradParams& p3, const WgradParams& p1, h
 // ---------------------------------------------------------------------------
 #define WG2_NS 4
 #define WG2_MAX 18
+static_assert(WG2_MAX <= WG_GROUP_MAX, "WgReduceGroup holds one entry per problem of a launch");
 struct Wg2Group {
     int nprob;
     const int4* tasks;                         // device: (problem, tile, split, -)
     const int* blk_begin;                      // device: [grid + 1] first task of each block
     int stage_elems;                           // bf16 elements of the whole ring (the launch's dynamic LDS)
-    int skew;                                  // see wg2_task
     int kind[WG2_MAX];                         // 0: 3x3 (wg2_task); 1 / 2 / 4: 1x1 on 128 x 64 / 128 x 128 / 128 x 256 tiles (wg2_task_1x1); + 16: 256 output channels per tile
     WgradParams p[WG2_MAX];
     WgHaloGeom g[WG2_MAX];
@@ -1135,8 +1087,75 @@ static __device__ __forceinline__ void wg2_lds_dma16(const void* gsrc, unsigned 
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_byte_addr) : "memory");
 }
 
+// The chunks of a task and the running position of the NEXT chunk to issue: c chunks issued so far; image index b and first
+// output row y (non-multi) of that chunk.
+struct Wg2Walk {
+    int chunk_begin, nch, ipc, c, b, y;
+    __device__ __forceinline__ Wg2Walk(const WgradParams& p, const WgHaloGeom& g, int split) {
+        nch = wg_chunk_range(p.M, split, g.cpb, &chunk_begin);
+        const int cpi = g.multi ? 1 : p.Hs / g.TR;                    // chunks per image (non-multi)
+        ipc = g.multi ? g.TR / p.Hs : 1;                              // images per chunk (multi)
+        c = 0;
+        if (g.multi) { b = chunk_begin * ipc; y = 0; }
+        else { b = chunk_begin / cpi; y = (chunk_begin - b * cpi) * g.TR; }
+    }
+    __device__ __forceinline__ void advance(const WgradParams& p, const WgHaloGeom& g) {
+        ++c;
+        if (g.multi) b += ipc;
+        else { y += g.TR; if (y >= p.Hs) { y = 0; ++b; } }
+    }
+};
+// dz LDS-DMA instruction i of a chunk (64-channel block i >> 3 from channel co0 on, pixel rows (i & 7) * 8 ..): the chunk-invariant
+// element offset of this lane's 16 bytes from the chunk's first pixel, and its pixel row in the chunk
+static __device__ __forceinline__ void wg2_dz_lane(const WgradParams& p, const WgHaloGeom& g, int i, int co0, int lane, int* zlane, int* zrow) {
+    const int piece = lane & 7, row = (i & 7) * 8 + (lane >> 3);
+    const int lr = row / p.Ws, xx = row - lr * p.Ws;
+    const int img = g.multi ? lr / p.Hs : 0, yy = g.multi ? lr % p.Hs : lr;
+    *zlane = ((img * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + (i >> 3) * 64 + wg_src_piece(row, piece) * 8;
+    *zrow = row;
+}
+// the NZ dz instructions of this wave for the walk's next chunk, into the stage at LDS byte address st_lds
+template <int NZ>
+static __device__ __forceinline__ void wg2_issue_dz(const WgradParams& p, const Wg2Walk& w, int wave, const int (&zlane)[NZ],
+                                                    const int (&zrow)[NZ], unsigned st_lds) {
+    const int ch = w.chunk_begin + w.c;
+    const bf16_t* zb = p.dz + ((size_t)w.b * p.dzHp + w.y) * p.dzWp * p.dzC;
+#pragma unroll
+    for (int k = 0; k < NZ; ++k) {
+        const int i = wave * NZ + k;
+        const bf16_t* src = (ch * WG_CH + zrow[k] < p.M) ? zb + zlane[k]
+                                                         : p.dz + (zlane[k] & 63);      // zero border pixel (0, 0) of image 0
+        wg2_lds_dma16(src, st_lds + (unsigned)(i * 8 * 64 * 2));
+    }
+}
+// The pipeline of a task on an NS-stage ring (`per` LDS-DMA instructions per wave and chunk): issue() requests the walk's next chunk
+// and ADVANCES w (w.c chunks issued so far),
+// compute(c, mid) consumes chunk c and calls mid() between its two k-steps.
+template <class Issue, class Compute>
+static __device__ __forceinline__ void wg2_pipeline(int NS, int per, int cohalf, Wg2Walk& w, Issue issue, Compute compute) {
+    // every wave is done with the previous task's ring (and its stores are on their way) before new tiles land in it
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < NS - 1 && k < w.nch) issue();
+    for (int c = 0; c < w.nch; ++c) {
+        // this wave's share of chunk c has landed when at most its instructions of the younger chunks are outstanding
+        int ahead = w.nch - 1 - c;
+        ahead = ahead < NS - 2 ? ahead : NS - 2;
+        wg2_wait_allow(ahead * per);                                  // (NS == 2: 0; NS == 4: per <= 5 by eligibility)
+        __builtin_amdgcn_s_barrier();                                 // READY_c: all shares landed; everyone finished chunk c-1
+        // chunk c + NS - 1 goes into the stage chunk c - 1 used.  The second wave of every SIMD requests its share between the
+        // two k-steps instead, so that the two waves stop running their read / MFMA phases in lockstep (same-box A/B 490 ->
+        // 458 us per step for the class; profiles/r02_negative_results.txt has the variants)
+        const bool do_issue = w.c < w.nch;
+        if (do_issue && !cohalf) issue();
+        compute(c, [&]() __attribute__((always_inline)) { if (do_issue && cohalf) issue(); });
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (already true after the last chunk's wait: belt and braces)
+}
+
 static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHaloGeom& g, int tile, int split,
-                                                bf16_t* ring, int lds_elems, int skew) {
+                                                bf16_t* ring, int lds_elems) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // 0..7
@@ -1145,11 +1164,7 @@ static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHa
     const int kct = p.Kc >> 6;
     const int co0 = (tile / kct) * 128;
     const int ci0 = (tile % kct) * 64;
-    const int nchunks_total = (p.M + WG_CH - 1) / WG_CH;
-    const int chunk_begin = split * g.cpb;
-    int chunk_end = chunk_begin + g.cpb;
-    chunk_end = chunk_end < nchunks_total ? chunk_end : nchunks_total;
-    const int nch = chunk_end - chunk_begin;
+    Wg2Walk w(p, g, split);
     const int nhi = (g.NHP + 7) >> 3;                                 // halo LDS-DMA instructions per chunk (8 pixels each)
     const int nh_mine = (nhi - wave + 7) >> 3;                        // this wave's: wave, wave + 8, ...
     const int per = 2 + nh_mine;                                      // its LDS-DMA instructions per chunk
@@ -1160,53 +1175,24 @@ static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHa
 
     // ---- LDS-DMA side: chunk-invariant per-lane element offsets (32-bit), the chunk's part is wave-uniform (64-bit) ----
     const int piece = lane & 7, lrow = lane >> 3;
-    const int TR = g.TR;
-    const int cpi = g.multi ? 1 : H / TR;                             // chunks per image (non-multi)
-    const int ipc = g.multi ? TR / H : 1;                             // images per chunk (multi)
     int zlane[2], zrow[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int i = wave * 2 + k;                                   // dz instruction: co half i >> 3 (= cohalf), rows (i & 7) * 8 ..
-        const int row = (i & 7) * 8 + lrow;
-        const int lr = row / W, xx = row - lr * W;
-        const int cpc = (((piece >> 1) ^ wg_f(row)) << 1) | (piece & 1);
-        const int img = g.multi ? lr / H : 0, yy = g.multi ? lr % H : lr;
-        zlane[k] = ((img * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + cohalf * 64 + cpc * 8;
-        zrow[k] = row;
-    }
-    // running position of the NEXT chunk to issue
-    int is_c = 0;                                                     // chunks issued so far
-    int is_b, is_y;                                                   // image index and first output row (non-multi) of that chunk
-    {
-        const int ch = chunk_begin;
-        if (g.multi) { is_b = ch * ipc; is_y = 0; }
-        else { is_b = ch / cpi; is_y = (ch - is_b * cpi) * TR; }
-    }
+    for (int k = 0; k < 2; ++k) wg2_dz_lane(p, g, wave * 2 + k, co0, lane, &zlane[k], &zrow[k]);      // (block i >> 3 = cohalf)
     const unsigned ring_lds = (unsigned)(size_t)(wg_lptr_t)ring;      // LDS byte address of the ring
     auto issue = [&]() __attribute__((always_inline)) {
-        const int ch = chunk_begin + is_c;
-        const unsigned st_lds = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)((is_c & (NS - 1)) * STAGE * 2));
-        const bf16_t* zb = p.dz + ((size_t)is_b * p.dzHp + is_y) * p.dzWp * p.dzC;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int i = wave * 2 + k;
-            const bf16_t* src = (ch * WG_CH + zrow[k] < p.M) ? zb + zlane[k]
-                                                             : p.dz + (zlane[k] & 63);      // zero border pixel (0, 0) of image 0
-            wg2_lds_dma16(src, st_lds + (unsigned)(i * 8 * 64 * 2));
-        }
-        const int gp0 = (is_b * p.xHp + S * is_y) * Wp;
+        const unsigned st_lds = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)((w.c & (NS - 1)) * STAGE * 2));
+        wg2_issue_dz<2>(p, w, wave, zlane, zrow, st_lds);
+        const int gp0 = (w.b * p.xHp + S * w.y) * Wp;
         const bf16_t* xb = p.x + ci0;
         for (int k = 0; k < nh_mine; ++k) {
             const int hp = (wave + 8 * k) * 8 + lrow;
-            const int cpc = (((piece >> 1) ^ wg_f(hp)) << 1) | (piece & 1);
+            const int cpc = wg_src_piece(hp, piece);
             int gp = gp0 + hp;
             gp = gp < g.total_pix ? gp : g.total_pix - 1;
             const bf16_t* src = xb + (size_t)gp * p.xC + cpc * 8;
             wg2_lds_dma16(src, st_lds + (unsigned)((128 + (wave + 8 * k) * 8) * 64 * 2));
         }
-        ++is_c;
-        if (g.multi) is_b += ipc;
-        else { is_y += TR; if (is_y >= H) { is_y = 0; ++is_b; } }
+        w.advance(p, g);
     };
 
     // ---- MFMA side: chunk-invariant LDS BYTE offsets (within a stage) of this lane's transposed reads.  A (dz) operand:
@@ -1220,7 +1206,7 @@ static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHa
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int r = ra + 4 * h;
-            offA0[h] = 2 * (cohalf * 64 * 64 + r * 64 + ((wg_f(r) << 4) | (4 * pp)));
+            offA0[h] = 2 * (cohalf * 64 * 64 + wg_swz_off(r, 4 * pp));
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -1239,60 +1225,36 @@ static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHa
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int r = hmv[h] + (p.taps.dy0 + (t / 3) * p.taps.dys) * Wp + (p.taps.dx0 + (t % 3) * p.taps.dxs);
-                    const unsigned o = 2u * (unsigned)(r * 64 + (((ctile ^ wg_f(r)) << 4) | (4 * pp)));      // from the halo's base
+                    const unsigned o = 2u * (unsigned)wg_swz_off(r, ctile * 16 + 4 * pp);      // from the halo's base
                     v |= o << (16 * h);
                 }
                 offB[ks][t] = v;
             }
         }
     }
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    typedef const char __attribute__((address_space(3))) * lds_cp;
-    auto frag2 = [&](lds_cp a0, lds_cp a1) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)a0);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)a1);
-        s16x8 v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-        v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return __builtin_bit_cast(bf16x8, v);
-    };
     f32x4 acc[9][4];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int a = 0; a < 4; ++a) acc[t][a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // every wave is done with the previous task's ring (and its stores are on their way) before new tiles land in it
-    __builtin_amdgcn_s_barrier();
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        if (k < NS - 1 && k < nch) issue();
-    for (int c = 0; c < nch; ++c) {
-        // this wave's share of chunk c has landed when at most its instructions of the younger chunks are outstanding
-        int ahead = nch - 1 - c;
-        ahead = ahead < NS - 2 ? ahead : NS - 2;
-        wg2_wait_allow(ahead * per);                                  // (NS == 2: 0; NS == 4: per <= 5 by eligibility)
-        __builtin_amdgcn_s_barrier();                                 // READY_c: all shares landed; everyone finished chunk c-1
-        // chunk c + NS - 1 goes into the stage chunk c - 1 used.  skew: the second wave of every SIMD requests its share
-        // between the two k-steps instead, so that the two waves stop running their read / MFMA phases in lockstep
-        const bool do_issue = is_c < nch;
-        if (do_issue && !(skew && cohalf)) issue();
-        const lds_cp sb = (lds_cp)(const char*)(ring + (c & (NS - 1)) * STAGE);
+    wg2_pipeline(NS, per, cohalf, w, issue, [&](int c, auto mid) __attribute__((always_inline)) {
+        const wg_lds_cp sb = (wg_lds_cp)(const char*)(ring + (c & (NS - 1)) * STAGE);
         // Explicit software pipeline of the LDS reads (pinned with sched_barrier: left alone, hipcc waits for every B
         // fragment right before its four MFMAs): the A fragments of both k-steps are resident (the second set is read
         // during the first k-step's last taps), the B fragment of tap t + 2 is requested before the MFMAs of tap t.
         auto ldA = [&](int ks, int a) __attribute__((always_inline)) {
-            const lds_cp a0 = sb + ks * 32 * 128 + offA0[0], a1 = sb + ks * 32 * 128 + offA0[1];
-            return frag2((lds_cp)((unsigned)(size_t)a0 ^ (unsigned)(a << 5)), (lds_cp)((unsigned)(size_t)a1 ^ (unsigned)(a << 5)));
+            const wg_lds_cp a0 = sb + ks * 32 * 128 + offA0[0], a1 = sb + ks * 32 * 128 + offA0[1];
+            return wg_tr_read((wg_lds_cp)(size_t)((unsigned)(size_t)a0 ^ (unsigned)(a << 5)), (wg_lds_cp)(size_t)((unsigned)(size_t)a1 ^ (unsigned)(a << 5)));
         };
         auto ldB = [&](int ks, int t) __attribute__((always_inline)) {
             const unsigned v = offB[ks][t];
-            return frag2(sb + 128 * 128 + (v & 0xffffu), sb + 128 * 128 + (v >> 16));
+            return wg_tr_read(sb + 128 * 128 + (v & 0xffffu), sb + 128 * 128 + (v >> 16));
         };
         {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                if (ks == 1 && do_issue && skew && cohalf) issue();
+                if (ks == 1) mid();
                 bf16x8 az[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) az[a] = ldA(ks, a);
@@ -1309,18 +1271,13 @@ static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHa
                 }
             }
         }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (already true after the last chunk's wait: belt and braces)
+    });
     // acc[t][a][j] = partial dW[tap t][co0 + 64*cohalf + a*16 + 4*gq + j][ci0 + 16*ctile + i16]
     float* out = g.ksplit > 1 ? p.slab + (size_t)split * 9 * p.Co * p.Kc : p.dw;
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
         const int wsl = p.taps.w0 + (t / 3) * p.taps.wrs + (t % 3) * p.taps.wcs;
-        float* o = out + ((size_t)wsl * p.Co + co0 + cohalf * 64) * p.Kc + ci0 + 16 * ctile + i16;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * p.Kc] = acc[t][a][j];
+        wg_store_tile(out + ((size_t)wsl * p.Co + co0 + cohalf * 64) * p.Kc + ci0 + 16 * ctile + i16, p.Kc, acc[t], gq);
     }
 }
 
@@ -1335,8 +1292,8 @@ static __device__ __forceinline__ void wg2_task(const WgradParams& p, const WgHa
 #define WG2_NS256 2
 #endif
 template <int TCI, int TCO = 128>
-static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const WgHaloGeom& g, int tile, int split, bf16_t* ring,
-                                                    int skew) {
+static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const WgHaloGeom& g, int tile, int split,
+                                                    bf16_t* ring) {
     constexpr int NB = TCI / 64;
     constexpr int NZ = TCO / 64;                                      // dz blocks of [64 px][64 co]; a wave owns NZ / 2 of them
     constexpr int NA = NZ * 2;                                        // 16-channel co groups per wave
@@ -1351,54 +1308,27 @@ static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const 
     const int kct = p.Kc / TCI;
     const int co0 = (tile / kct) * TCO;
     const int ci0 = (tile % kct) * TCI;
-    const int nchunks_total = (p.M + WG_CH - 1) / WG_CH;
-    const int chunk_begin = split * g.cpb;
-    int chunk_end = chunk_begin + g.cpb;
-    chunk_end = chunk_end < nchunks_total ? chunk_end : nchunks_total;
-    const int nch = chunk_end - chunk_begin;
+    Wg2Walk w(p, g, split);
 
     const int piece = lane & 7, lrow = lane >> 3;
-    const int TR = g.TR;
-    const int cpi = g.multi ? 1 : H / TR;
-    const int ipc = g.multi ? TR / H : 1;
     int zlane[NZ], zrow[NZ], xlane[NB];
 #pragma unroll
-    for (int k = 0; k < NZ; ++k) {
-        const int i = wave * NZ + k;                                  // dz instruction: block i >> 3, rows (i & 7) * 8 ..
-        const int row = (i & 7) * 8 + lrow;
-        const int lr = row / W, xx = row - lr * W;
-        const int cpc = (((piece >> 1) ^ wg_f(row)) << 1) | (piece & 1);
-        const int img = g.multi ? lr / H : 0, yy = g.multi ? lr % H : lr;
-        zlane[k] = ((img * p.dzHp + yy + p.dzpad) * p.dzWp + xx + p.dzpad) * p.dzC + co0 + (i >> 3) * 64 + cpc * 8;
-        zrow[k] = row;
-    }
+    for (int k = 0; k < NZ; ++k) wg2_dz_lane(p, g, wave * NZ + k, co0, lane, &zlane[k], &zrow[k]);
 #pragma unroll
     for (int k = 0; k < NB; ++k) {
         const int j = wave * NB + k;                                  // x instruction: block j >> 3, rows (j & 7) * 8 ..
         const int row = (j & 7) * 8 + lrow;
         const int lr = row / W, xx = row - lr * W;
-        const int cpc = (((piece >> 1) ^ wg_f(row)) << 1) | (piece & 1);
+        const int cpc = wg_src_piece(row, piece);
         const int img = g.multi ? lr / H : 0, yy = g.multi ? lr % H : lr;
         xlane[k] = ((img * p.xHp + S * yy + 1) * p.xWp + S * xx + 1) * p.xC + ci0 + (j >> 3) * 64 + cpc * 8;
     }
-    int is_c = 0, is_b, is_y;
-    {
-        const int ch = chunk_begin;
-        if (g.multi) { is_b = ch * ipc; is_y = 0; }
-        else { is_b = ch / cpi; is_y = (ch - is_b * cpi) * TR; }
-    }
     const unsigned ring_lds = (unsigned)(size_t)(wg_lptr_t)ring;
     auto issue = [&]() __attribute__((always_inline)) {
-        const int ch = chunk_begin + is_c;
-        const unsigned st_lds = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)((is_c % NS) * STAGE * 2));
-        const bf16_t* zb = p.dz + ((size_t)is_b * p.dzHp + is_y) * p.dzWp * p.dzC;
-        const bf16_t* xb = p.x + ((size_t)is_b * p.xHp + S * is_y) * p.xWp * p.xC;
-#pragma unroll
-        for (int k = 0; k < NZ; ++k) {
-            const int i = wave * NZ + k;
-            const bf16_t* src = (ch * WG_CH + zrow[k] < p.M) ? zb + zlane[k] : p.dz + (zlane[k] & 63);      // zero border pixel
-            wg2_lds_dma16(src, st_lds + (unsigned)(i * 8 * 64 * 2));
-        }
+        const int ch = w.chunk_begin + w.c;
+        const unsigned st_lds = __builtin_amdgcn_readfirstlane(ring_lds + (unsigned)((w.c % NS) * STAGE * 2));
+        wg2_issue_dz<NZ>(p, w, wave, zlane, zrow, st_lds);
+        const bf16_t* xb = p.x + ((size_t)w.b * p.xHp + S * w.y) * p.xWp * p.xC;
 #pragma unroll
         for (int k = 0; k < NB; ++k) {
             const int j = wave * NB + k;
@@ -1406,9 +1336,7 @@ static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const 
             const bf16_t* src = (ch * WG_CH + (j & 7) * 8 + lrow < p.M) ? xb + xlane[k] : p.x + (xlane[k] & 63);
             wg2_lds_dma16(src, st_lds + (unsigned)((TCO + j * 8) * 64 * 2));
         }
-        ++is_c;
-        if (g.multi) is_b += ipc;
-        else { is_y += TR; if (is_y >= H) { is_y = 0; ++is_b; } }
+        w.advance(p, g);
     };
 
     const int gq = lane >> 4, i16 = lane & 15, q = i16 >> 2, pp = i16 & 3;
@@ -1418,53 +1346,33 @@ static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const 
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int r = ra + 4 * h;
-            offA0[h] = 2 * (cohalf * (TCO / 2) * 64 + r * 64 + ((wg_f(r) << 4) | (4 * pp)));
-            offB0[h] = 2 * (TCO * 64 + r * 64 + (((ctile ^ wg_f(r)) << 4) | (4 * pp)));
+            offA0[h] = 2 * (cohalf * (TCO / 2) * 64 + wg_swz_off(r, 4 * pp));
+            offB0[h] = 2 * (TCO * 64 + wg_swz_off(r, ctile * 16 + 4 * pp));
         }
     }
-    typedef s16x4 __attribute__((address_space(3))) * lds_p;
-    typedef const char __attribute__((address_space(3))) * lds_cp;
-    auto frag2 = [&](lds_cp a0, lds_cp a1) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)a0);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)a1);
-        s16x8 v;
-        v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-        v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-        return __builtin_bit_cast(bf16x8, v);
-    };
     f32x4 acc[NB][NA];
 #pragma unroll
     for (int u = 0; u < NB; ++u)
 #pragma unroll
         for (int a = 0; a < NA; ++a) acc[u][a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    __builtin_amdgcn_s_barrier();                                     // the previous task is done with the ring
-#pragma unroll
-    for (int k = 0; k < NS - 1; ++k)
-        if (k < nch) issue();
-    for (int c = 0; c < nch; ++c) {
-        int ahead = nch - 1 - c;
-        ahead = ahead < NS - 2 ? ahead : NS - 2;
-        wg2_wait_allow(ahead * PER);
-        __builtin_amdgcn_s_barrier();
-        const bool do_issue = is_c < nch;
-        if (do_issue && !(skew && cohalf)) issue();
-        const lds_cp sb = (lds_cp)(const char*)(ring + (c % NS) * STAGE);
+    wg2_pipeline(NS, PER, cohalf, w, issue, [&](int c, auto mid) __attribute__((always_inline)) {
+        const wg_lds_cp sb = (wg_lds_cp)(const char*)(ring + (c % NS) * STAGE);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if (ks == 1 && do_issue && skew && cohalf) issue();
+            if (ks == 1) mid();
             bf16x8 bx[NB];
-            const lds_cp a0 = sb + ks * 32 * 128 + offA0[0], a1 = sb + ks * 32 * 128 + offA0[1];
+            const wg_lds_cp a0 = sb + ks * 32 * 128 + offA0[0], a1 = sb + ks * 32 * 128 + offA0[1];
 #pragma unroll
             for (int u = 0; u < NB; ++u)
-                bx[u] = frag2(sb + u * 64 * 128 + ks * 32 * 128 + offB0[0], sb + u * 64 * 128 + ks * 32 * 128 + offB0[1]);
+                bx[u] = wg_tr_read(sb + u * 64 * 128 + ks * 32 * 128 + offB0[0], sb + u * 64 * 128 + ks * 32 * 128 + offB0[1]);
 #pragma unroll
             for (int zb = 0; zb < NZ / 2; ++zb) {      // this wave's dz blocks, one at a time (four co groups of fragments live)
                 bf16x8 az[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a)      // (16-channel group a of the block by the XOR)
-                    az[a] = frag2((lds_cp)(((unsigned)(size_t)a0 ^ (unsigned)(a << 5)) + zb * 64 * 128),
-                                  (lds_cp)(((unsigned)(size_t)a1 ^ (unsigned)(a << 5)) + zb * 64 * 128));
+                    az[a] = wg_tr_read((wg_lds_cp)(size_t)(((unsigned)(size_t)a0 ^ (unsigned)(a << 5)) + zb * 64 * 128),
+                                       (wg_lds_cp)(size_t)(((unsigned)(size_t)a1 ^ (unsigned)(a << 5)) + zb * 64 * 128));
 #pragma unroll
                 for (int u = 0; u < NB; ++u)
 #pragma unroll
@@ -1472,8 +1380,7 @@ static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const 
                         acc[u][zb * 4 + a] = VPD_MFMA16(az[a], bx[u], acc[u][zb * 4 + a]);
             }
         }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    });
     // acc[u][a][j] = partial dW[co0 + (TCO/2)*cohalf + a*16 + 4*gq + j][ci0 + 64*u + 16*ctile + i16]
     float* out = g.ksplit > 1 ? p.slab + (size_t)split * p.Co * p.Kc : p.dw;
 #pragma unroll
@@ -1484,11 +1391,7 @@ static __device__ __forceinline__ void wg2_task_1x1(const WgradParams& p, const 
             for (int a = 0; a < NA; ++a) *reinterpret_cast<f32x4*>(o + a * 16) = acc[u][a];
             continue;
         }
-        float* o = out + (size_t)(co0 + cohalf * (TCO / 2)) * p.Kc + ci0 + 64 * u + 16 * ctile + i16;
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[(size_t)(a * 16 + 4 * gq + j) * p.Kc] = acc[u][a][j];
+        wg_store_tile(out + (size_t)(co0 + cohalf * (TCO / 2)) * p.Kc + ci0 + 64 * u + 16 * ctile + i16, p.Kc, acc[u], gq);
     }
 }
 
@@ -1501,26 +1404,25 @@ __global__ __launch_bounds__(512) void conv_wgrad128_persistent_kernel(const Wg2
         const int pi = __builtin_amdgcn_readfirstlane(tk.x);
         const int tile = __builtin_amdgcn_readfirstlane(tk.y), split = __builtin_amdgcn_readfirstlane(tk.z);
         const int kind = grp.kind[pi];
-        if (kind == 0) wg2_task(grp.p[pi], grp.g[pi], tile, split, ring, grp.stage_elems, grp.skew);
-        else if (kind == 1) wg2_task_1x1<64>(grp.p[pi], grp.g[pi], tile, split, ring, grp.skew);
-        else if (kind == 2) wg2_task_1x1<128>(grp.p[pi], grp.g[pi], tile, split, ring, grp.skew);
-        else if (kind == 4) wg2_task_1x1<256>(grp.p[pi], grp.g[pi], tile, split, ring, grp.skew);
-        else if (kind == 17) wg2_task_1x1<64, 256>(grp.p[pi], grp.g[pi], tile, split, ring, grp.skew);
-        else wg2_task_1x1<128, 256>(grp.p[pi], grp.g[pi], tile, split, ring, grp.skew);
+        if (kind == 0) wg2_task(grp.p[pi], grp.g[pi], tile, split, ring, grp.stage_elems);
+        else if (kind == 1) wg2_task_1x1<64>(grp.p[pi], grp.g[pi], tile, split, ring);
+        else if (kind == 2) wg2_task_1x1<128>(grp.p[pi], grp.g[pi], tile, split, ring);
+        else if (kind == 4) wg2_task_1x1<256>(grp.p[pi], grp.g[pi], tile, split, ring);
+        else if (kind == 17) wg2_task_1x1<64, 256>(grp.p[pi], grp.g[pi], tile, split, ring);
+        else wg2_task_1x1<128, 256>(grp.p[pi], grp.g[pi], tile, split, ring);
     }
 }
 
 // ---- host side: eligibility, split choice, LPT schedule ----
-// kind of a problem for the persistent launch: -1 not eligible, 0 3x3, 1 / 2 1x1 (pad 0: one tap at padded offset (1, 1)) on
-// 128 x 64 / 128 x 128 tiles
-static int wg2_kind_1x1(const WgradParams& p) {
+// kind of a problem for the persistent launch and its chunk geometry: -1 not eligible, 0 3x3, else 1x1 (pad 0: one tap at padded
+// offset (1, 1)) on tiles of 128 co x 64 / 128 / 256 ci (1 / 2 / 4), + 16: 256 co
+static int wg2_kind_1x1(const WgradParams& p, WgHaloGeom* g) {
     if (!vpd_switches().wg2_1x1 || !(p.taps.nr == 1 && p.taps.nc == 1 && p.taps.dy0 == 1 && p.taps.dx0 == 1) || p.one_by_one) return -1;
     if (p.Co % 128 || p.Kc % 64 || p.xC != p.Kc || p.dzC % 128 || p.dzpad < 1 || (p.istr != 1 && p.istr != 2)) return -1;
     if (p.xHp != p.istr * p.Hs + 2 || p.xWp != p.istr * p.Ws + 2 || p.dzHp != p.Hs + 2 * p.dzpad || p.dzWp != p.Ws + 2 * p.dzpad) return -1;
-    const int W = p.Ws, H = p.Hs;
-    if (W <= 0 || WG_CH % W) return -1;
-    const int TR = WG_CH / W;
-    if (TR <= H ? H % TR != 0 : TR % H != 0) return -1;
+    *g = WgHaloGeom{};
+    if (!wg_chunk_tiling(p.Hs, p.Ws, p.istr, p.xHp, p.xWp, g)) return -1;
+    g->NHP = 64; g->HR = 0; g->total_pix = p.N * p.xHp * p.xWp;      // no halo: the 64 pixels of the chunk
     // 128 x 256 tiles: a dz chunk serves four ci blocks.  These tasks are bound by the bytes they stream (the tiles of a pixel range
     // do not run close enough in time to meet in an XCD's 4 MB L2): ResNet-50's grouped launches 1,240 -> 955 us per step, same
     // box.  256 x 256 tiles (64 KB stages, 128 accumulator registers) were slower again, 976 vs 925 us: fewer tiles, more splits
@@ -1531,25 +1433,23 @@ static int wg2_kind_1x1(const WgradParams& p) {
 }
 static inline int wg2_nb(int kind) { return kind & 15; }                     // 64-channel ci blocks per tile
 static inline int wg2_tco(int kind) { return kind >= 16 ? 256 : 128; }       // output channels per tile
-static void wg2_geom_1x1(const WgradParams& p, WgHaloGeom* g) {
-    memset(g, 0, sizeof *g);
-    const int TR = WG_CH / p.Ws;
-    g->TR = TR; g->multi = TR > p.Hs ? 1 : 0; g->NHP = 64; g->HR = 0; g->total_pix = p.N * p.xHp * p.xWp;
-}
-bool vpd_wgrad128_eligible(const WgradParams& p) {
-    const int off = !vpd_switches().wg2;
-    if (!off && wg2_kind_1x1(p) > 0) return true;
-    WgHaloGeom g;
-    WgradParams q = p;
-    if (!q.slab) q.slab = reinterpret_cast<float*>(16);
-    if (off || p.Co % 128 != 0 || p.Kc % 64 != 0 || (p.istr != 1 && p.istr != 2) || p.one_by_one || p.dzpad < 1 || p.dzC % 128 != 0)
-        return false;
-    if (p.istr == 2 && p.taps.nr != 3) return false;
-    if (!(vpd_wgrad_overwrites(q) && wg_halo_geom(q, &g))) return false;
-    const int nhi = (g.NHP + 7) / 8;
+static int wg2_kind(const WgradParams& p, WgHaloGeom* g) {
+    if (!vpd_switches().wg2) return -1;
+    const int k1 = wg2_kind_1x1(p, g);
+    if (k1 > 0) return k1;
+    if (p.Co % 128 != 0 || p.Kc % 64 != 0 || (p.istr != 1 && p.istr != 2) || p.one_by_one || p.dzpad < 1 || p.dzC % 128 != 0) return -1;
+    if (p.istr == 2 && p.taps.nr != 3) return -1;
+    const WgRoute r = wg_route_any_slab(p);
+    if (!r.halo()) return -1;
+    *g = r.g;
+    const int nhi = (g->NHP + 7) / 8;
     // stride 1: four ring stages with at most 5 LDS-DMA instructions per wave and chunk (the counted vmcnt waits);
     // stride 2: two stages that fit 160 KB
-    return p.istr == 1 ? nhi <= 24 : 2 * (128 + 8 * nhi) * 128 <= 160 * 1024;
+    return (p.istr == 1 ? nhi <= 24 : 2 * (128 + 8 * nhi) * 128 <= 160 * 1024) ? 0 : -1;
+}
+bool vpd_wgrad128_eligible(const WgradParams& p) {
+    WgHaloGeom g;
+    return wg2_kind(p, &g) >= 0;
 }
 
 struct Wg2Schedule {
@@ -1597,55 +1497,46 @@ static void wg2_build(const WgradParams* ps, const WgHaloGeom* gs, int n, int G,
     // per-chunk time of a 128 x 64 task: the larger of the MFMA time (1.15 us) and the stream (16 KB + halo at ~21 GB/s
     // per CU when every CU streams); per-task fixed cost; slab bytes written and read back at 4.5 TB/s
     const double t_fixed = 5.0, bw = 4.5e6;
-    const int cpb_env = 0;
-    double best = 1e30;
-    int best_ks[WG2_MAX];
     auto tchunk = [&](int i) {
         const int kind = kinds ? kinds[i] : 0;
         if (kind) return (wg2_tco(kind) / 8.0 + 8.0 * wg2_nb(kind)) / 21.0;      // 1x1: the stream alone
         const double st = (16.0 + (gs[i].NHP + 7) / 8) / 21.0;
         return st > 1.15 ? st : 1.15;
     };
-    auto eval = [&](double target) {
-        int ks[WG2_MAX];
-        std::vector<std::pair<double, int>> tl;
-        double slab = 0.0;
-        bool any = false;
-        for (int i = 0; i < n; ++i) {
-            int k = (int)(nch[i] / target + 0.5);
-            k = k < 1 ? 1 : (k > cap[i] ? cap[i] : k);
-            const int cpb = (nch[i] + k - 1) / k;
-            k = (nch[i] + cpb - 1) / cpb;
-            ks[i] = k;
-            for (int s = 0; s < k; ++s) {
-                const int c1 = (s + 1) * cpb < nch[i] ? (s + 1) * cpb : nch[i];
-                for (int t = 0; t < tiles[i]; ++t) tl.push_back({(c1 - s * cpb) * tchunk(i) + t_fixed, 0});
-            }
-            if (k > 1) { slab += (double)k * ntap[i] * ps[i].Co * ps[i].Kc * 4; any = true; }
-        }
-        std::stable_sort(tl.begin(), tl.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
-        const double cost = wg2_lpt(tl, G, order, nullptr) + 2.0 * slab / bw + (any ? 3.0 : 0.0);
-        if (cost < best) { best = cost; for (int i = 0; i < n; ++i) best_ks[i] = ks[i]; }
-    };
-    if (cpb_env > 0) eval((double)cpb_env);
-    else for (int cpb = 8; cpb <= 1024; cpb += (cpb < 128 ? 2 : 8)) eval((double)cpb);
-    // final task list: problem-major, split-major, tile-fastest; stable sort by length (longest first); LPT deal
+    // task list of the splits ks[]: problem-major, split-major, tile-fastest; then stable sort by length (longest first)
     struct T { int prob, tile, split; };
     std::vector<T> tv;
     std::vector<std::pair<double, int>> tl;
-    for (int i = 0; i < n; ++i) {
-        const int k = best_ks[i];
-        const int cpb = (nch[i] + k - 1) / k;
-        out->ksplit[i] = k;
-        for (int s = 0; s < k; ++s) {
-            const int c1 = (s + 1) * cpb < nch[i] ? (s + 1) * cpb : nch[i];
-            for (int t = 0; t < tiles[i]; ++t) {
-                tl.push_back({(c1 - s * cpb) * tchunk(i) + t_fixed, (int)tv.size()});
-                tv.push_back({i, t, s});
+    auto list_tasks = [&](const int* ks) {
+        tv.clear();
+        tl.clear();
+        for (int i = 0; i < n; ++i) {
+            const int cpb = (nch[i] + ks[i] - 1) / ks[i];
+            for (int s = 0; s < ks[i]; ++s) {
+                const int c1 = (s + 1) * cpb < nch[i] ? (s + 1) * cpb : nch[i];
+                for (int t = 0; t < tiles[i]; ++t) {
+                    tl.push_back({(c1 - s * cpb) * tchunk(i) + t_fixed, (int)tv.size()});
+                    tv.push_back({i, t, s});
+                }
             }
         }
+        std::stable_sort(tl.begin(), tl.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
+    };
+    double best = 1e30;
+    for (int target = 8; target <= 1024; target += (target < 128 ? 2 : 8)) {
+        int ks[WG2_MAX];
+        double slab = 0.0;
+        bool any = false;
+        for (int i = 0; i < n; ++i) {
+            int cpb;
+            ks[i] = wg_split_for_target(nch[i], cap[i], (double)target, &cpb);
+            if (ks[i] > 1) { slab += (double)ks[i] * ntap[i] * ps[i].Co * ps[i].Kc * 4; any = true; }
+        }
+        list_tasks(ks);
+        const double cost = wg2_lpt(tl, G, order, nullptr) + 2.0 * slab / bw + (any ? 3.0 : 0.0);
+        if (cost < best) { best = cost; for (int i = 0; i < n; ++i) out->ksplit[i] = ks[i]; }
     }
-    std::stable_sort(tl.begin(), tl.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first > b.first; });
+    list_tasks(out->ksplit);      // the final list; LPT deal
     std::vector<int> owner;
     out->est_us = wg2_lpt(tl, G, order, &owner);
     std::vector<std::vector<int>> per(G);
@@ -1707,17 +1598,11 @@ hipError_t vpd_launch_wgrad128_group(const WgradParams* ps, int n, void* cache_v
     Wg2Group grp = {};
     WgReduceGroup red = {};
     grp.nprob = n;
-    int nhi_max = 0;
     int kinds[WG2_MAX];
     for (int i = 0; i < n; ++i) {
-        if (!vpd_wgrad128_eligible(ps[i])) return hipErrorInvalidValue;
         grp.p[i] = ps[i];
-        const int k1 = wg2_kind_1x1(ps[i]);
-        kinds[i] = grp.kind[i] = k1 > 0 ? k1 : 0;
-        if (k1 > 0) { wg2_geom_1x1(ps[i], &grp.g[i]); continue; }
-        if (!wg_halo_geom(ps[i], &grp.g[i])) return hipErrorInvalidValue;
-        const int nhi = (grp.g[i].NHP + 7) / 8;
-        nhi_max = nhi > nhi_max ? nhi : nhi_max;
+        kinds[i] = grp.kind[i] = wg2_kind(ps[i], &grp.g[i]);
+        if (kinds[i] < 0) return hipErrorInvalidValue;
     }
     Wg2Cache local;
     Wg2Cache* c = cache_v ? static_cast<Wg2Cache*>(cache_v) : &local;
@@ -1749,34 +1634,17 @@ hipError_t vpd_launch_wgrad128_group(const WgradParams* ps, int n, void* cache_v
         }
         grp.stage_elems = (int)need;
     }
-    // skew on: same-box A/B 490 -> 458 us per step for the class (profiles/r02_negative_results.txt has the variants)
-    grp.skew = 1;
-    int max_ks = 1;
-    long max_n4 = 0;
     for (int i = 0; i < n; ++i) {
         WgHaloGeom& g = grp.g[i];
         const int nchunks = (ps[i].M + WG_CH - 1) / WG_CH;
         g.ksplit = sch.ksplit[i];
         g.cpb = (nchunks + g.ksplit - 1) / g.ksplit;
-        if (g.ksplit > 1) {
-            red.slab[red.nprob] = reinterpret_cast<const float4*>(ps[i].slab);
-            red.dw[red.nprob] = reinterpret_cast<float4*>(ps[i].dw);
-            red.n4[red.nprob] = (long)(kinds[i] ? 1 : 9) * ps[i].Co * ps[i].Kc / 4;
-            red.ksplit[red.nprob] = g.ksplit;
-            max_n4 = red.n4[red.nprob] > max_n4 ? red.n4[red.nprob] : max_n4;
-            max_ks = g.ksplit > max_ks ? g.ksplit : max_ks;
-            ++red.nprob;
-            if (red.nprob > WG_GROUP_MAX) return hipErrorInvalidValue;
-        }
+        if (g.ksplit > 1) red.add(ps[i].slab, ps[i].dw, (long)(kinds[i] ? 1 : 9) * ps[i].Co * ps[i].Kc, g.ksplit);
     }
     const size_t lds = (size_t)grp.stage_elems * sizeof(bf16_t);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     VPD_LAUNCH(conv_wgrad128_persistent_kernel, dim3(sch.grid), dim3(512), lds, stream, grp);
-    if (red.nprob > 0) {
-        const int groups = max_ks < 16 ? max_ks : 16;
-        hipLaunchKernelGGL(wgrad_slab_reduce_group_kernel, dim3((unsigned)((max_n4 + 63) / 64), red.nprob), dim3(64 * groups),
-                           0, stream, red, groups);
-    }
+    wg_launch_reduce(red, stream);
     return hipGetLastError();
 }
 
@@ -1792,7 +1660,7 @@ __global__ __launch_bounds__(256) void tr_read_probe_kernel(const bf16_t* tile, 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = row0 + 32 * i;
-        *reinterpret_cast<uint4*>(s + wg_swz(r, piece)) = *reinterpret_cast<const uint4*>(tile + r * 64 + piece * 8);
+        *reinterpret_cast<uint4*>(s + wg_swz_off(r, piece * 8)) = *reinterpret_cast<const uint4*>(tile + r * 64 + piece * 8);
     }
     __syncthreads();
     const int lane = tid & 63, wave = tid >> 6;

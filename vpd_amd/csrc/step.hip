@@ -226,15 +226,16 @@ hipError_t run_conv_wgrad(const Ctx& c, const ConvInfo& cv, const bf16_t* dz, co
     float* slab = c.f32(c.p->slab_off);
     q.slab = cv.slab_off >= 0 ? slab + cv.slab_off : (cv.stem ? slab : nullptr);
     q.prefer_halo_1x1 = !c.p->bottleneck;      // BasicBlock students: the three down-sampling 1x1 convs without atomics
-    if (cv.slab_off >= 0 && !vpd_wgrad_overwrites(q)) q.slab = nullptr;      // (an A/B switch turned the halo form off: generic kernel)
+    const bool overwrites = vpd_wgrad_overwrites(q);       // (no slab: never)
+    if (cv.slab_off >= 0 && !overwrites) q.slab = nullptr;      // (an A/B switch turned the halo form off: generic kernel)
     if (collect_zero) {
-        if (!vpd_wgrad_overwrites(q) && collect_zero->count < ZR_MAX) {
+        if (!overwrites && collect_zero->count < ZR_MAX) {
             collect_zero->ptr[collect_zero->count] = q.dw;
             collect_zero->n4[collect_zero->count++] = (long)cv.ntaps * cv.Co * cv.Kc / 4;
         }
         return hipSuccess;
     }
-    if (vpd_wgrad_overwrites(q) && !cv.stem) {      // time the MFMA kernel alone, then sum its slab
+    if (overwrites && !cv.stem) {      // time the MFMA kernel alone, then sum its slab
         hipError_t e;
         {
             // class 5 = the grouped per-stage launches (and single stride-1 halo launches); a stride-2 conv's own halo
@@ -246,7 +247,7 @@ hipError_t run_conv_wgrad(const Ctx& c, const ConvInfo& cv, const bf16_t* dz, co
         if (e != hipSuccess) return e;
         return vpd_launch_wgrad_reduce(q, c.s);
     }
-    TimeScope ts(c.p, c.s, cv.stem ? 7 : (vpd_wgrad_overwrites(q) ? 5 : 6), conv_flops(cv, c.n));      // 7: stem kernels
+    TimeScope ts(c.p, c.s, cv.stem ? 7 : (overwrites ? 5 : 6), conv_flops(cv, c.n));      // 7: stem kernels
     return vpd_launch_wgrad(q, c.s);
 }
 
