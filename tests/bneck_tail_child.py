@@ -4,7 +4,9 @@ usage: bneck_tail_child.py <run id[,run id...]> <dispatch|full>
   dispatch  no launch: what vpd_op_conv1x1_bn_dispatch says for the run (works without a GPU: 256 CUs assumed)
   full      both libraries, both input regimes, every mode of vpd_op_conv1x1_bn / vpd_op_conv1x1_bn2 against the float64 chain of
             tests/opref.py (tail_forward, tail_backward)
-Prints one line "RESULT <json>" per run: {"run", "fail": [...], "dispatch": {...}, "record": {...}}; the parent asserts on it."""
+Prints one line "RESULT <json>" per run: {"run", "fail": [...], "dispatch": {...}, "record": {...}}; the parent asserts on it.
+record["<library>/<regime>/digests"]: sha256 of every buffer the fused launches wrote, slack included -- not asserted on; it is what
+lets two builds of the libraries (VPD_LIB_PATH / VPD_LIB_PATH_F16) be compared bit for bit."""
 import ctypes as C
 import json
 import os
@@ -18,7 +20,7 @@ if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
 from tests import opref as R  # noqa: E402
-from tests.conv_ops_child import FEW, SENT, SLACK, Geo, Ops, ptr, stream  # noqa: E402
+from tests.conv_ops_child import FEW, SENT, SLACK, Geo, Ops, ptr, sha, stream  # noqa: E402
 
 OUT5 = ("eligible", "lanes", "channel_tiles", "tiles", "ring")
 # run id -> (case of opref.TAIL_CASES, environment, what vpd_op_conv1x1_bn_dispatch must report on a 256-CU device)
@@ -31,6 +33,7 @@ RUNS = {
     "two_w8-few":       ("two_w8", FEW, dict(eligible=1, lanes=8, channel_tiles=1, tiles=8, ring=5)),
     "two_w16-few":      ("two_w16", FEW, dict(eligible=1, lanes=8, channel_tiles=1, tiles=12, ring=5)),
     "k64_w32-device":   ("k64_w32", {}, dict(eligible=1, lanes=256, channel_tiles=1, tiles=3, ring=8)),
+    "k128_w32-device":  ("k128_w32", {}, dict(eligible=1, lanes=256, channel_tiles=1, tiles=3, ring=5)),
     "two_w32-device":   ("two_w32", {}, dict(eligible=1, lanes=256, channel_tiles=1, tiles=3, ring=5)),
 }
 MASK_SENT = 0xA5
@@ -81,6 +84,7 @@ def run_case(ops, cs, o, regime, name, fail, record):
     sides = ("", "2") if two else ("",)
     bad = lambda what: fail.append(tag + what)
     nul = None
+    dig = record.setdefault(tag + "digests", {})
 
     # ---- operands on the device; z: the unfused launch's stored output, itself checked against the float64 convolution ----
     xp, wf, zdev, z = {}, {}, {}, {}
@@ -131,6 +135,7 @@ def run_case(ops, cs, o, regime, name, fail, record):
         ops.check(L.vpd_op_conv1x1_bn(0, ptr(xp[s]), ptr(wf[s]), n, h, w, 1, ci, co, ptr(rows[s]), nul, nul, nul, nul, F(R.BN_MOMENTUM),
                                       F(R.BN_EPS), nul, nul, nul, nul, nul, nul, nul, nul, nul, nul, nul, stream()))
         torch.cuda.synchronize()
+        dig["rows" + s] = sha(rows[s])
         st = stat[s]
         rows_check("rows" + s, rows[s], torch.stack([st["s1"], st["s2"]]), torch.stack([st["abs1"], st["s2"]]))
 
@@ -153,6 +158,8 @@ def run_case(ops, cs, o, regime, name, fail, record):
                                       vp("", "rv"), F(R.BN_MOMENTUM), F(R.BN_EPS), vp("", "mean"), vp("", "rstd"), vp("", "scale"), vp("", "shift"),
                                       ptr(resp), ptr(out), ptr(maskb), nul, nul, nul, nul, stream()))
     torch.cuda.synchronize()
+    dig.update({"out": sha(out), "mask": sha(maskb)})
+    dig.update({k + s: sha(t.t) for s in sides for k, t in vec[s].items()})
     got, kept = ops.read(out, n, h, w, co, 1)
     if not kept:
         bad("out: wrote outside the interior")
@@ -222,6 +229,7 @@ def run_case(ops, cs, o, regime, name, fail, record):
             torch.cuda.synchronize()
             if not m3:
                 for s in sides:
+                    dig["%s/rows%s" % (which, s)] = sha(brow[s])
                     b = side_ref[s][0]
                     rows_check("%s/rows%s" % (which, s), brow[s], torch.stack([b["r1"], b["r2"]]), torch.stack([b["abs1"], b["absz"]]))
         if not torch.equal(doutd.cpu(), dt_dout):
@@ -229,6 +237,7 @@ def run_case(ops, cs, o, regime, name, fail, record):
         same = True
         for s in sides:
             b, bound = side_ref[s]
+            dig.update({"%s/dz%s" % (which, s): sha(dz[s]), "%s/dgamma%s" % (which, s): sha(dg[s].t), "%s/dbeta%s" % (which, s): sha(db[s].t)})
             gdz, kept = ops.read(dz[s], n, h, w, co, 1)
             if not kept:
                 bad("%s/dz%s: wrote outside the interior" % (which, s))

@@ -506,6 +506,7 @@ TAIL_CASES = {
     "two_w8":      dict(n=61, ci=64,  co=256, h=8,  w=8,  few=True, two=True),
     "two_w16":     dict(n=23, ci=64,  co=256, h=16, w=16, few=True, two=True),
     "k64_w32":     dict(n=40, ci=64,  co=256, h=32, w=32, few=False),     # the whole device: 640 tiles, 2-3 per block
+    "k128_w32":    dict(n=40, ci=128, co=256, h=32, w=32, few=False),     # ... on the 5-stage ring: fewer tiles than it runs ahead
     "two_w32":     dict(n=40, ci=64,  co=256, h=32, w=32, few=False, two=True),
 }
 for _c in TAIL_CASES.values():

@@ -5,8 +5,8 @@ tests/test_opref_cpu.py).
 
 A block of these kernels walks its 64-pixel tiles through an LDS ring of 8 (64 input channels) or 5 stages; a stage is reused only
 from the block's ninth / sixth tile on.  The few-CU runs (VPD_RESERVE_CUS=248: 8 pixel lanes) give every block 8 to 12 tiles of a
-tensor of a few MB; the child asserts that through vpd_op_conv1x1_bn_dispatch before it launches anything.  Two more runs use the
-whole device.
+tensor of a few MB; the child asserts that through vpd_op_conv1x1_bn_dispatch before it launches anything.  Three more runs use the
+whole device; one of them gives K = 128 blocks fewer tiles (2-3) than the 5-stage ring runs ahead.
 
 Integer operands: the statistics rows of modes 0 and 2 must be EQUAL to the float64 sums.  Both regimes: out and dz per element
 within bounds derived from the fp32 arithmetic (opref.tail_out_bound, bn_dz_bound), the bit map equal to [stored out != 0], the

@@ -19,6 +19,15 @@ static __host__ __device__ __forceinline__ int conv_ep_mode(const ConvParams& p)
     return p.ep_scale ? 3 : (p.accumulate ? 2 : (p.stats ? 1 : 0));
 }
 
+// a wave's accumulator tile := 0 (in front of a tile's K loop)
+template <int NI, int MI>
+static __device__ __forceinline__ void zero_acc(f32x4 (&acc)[NI][MI]) {
+#pragma unroll
+    for (int a = 0; a < NI; ++a)
+#pragma unroll
+        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // Output pixel m of the sub-grid -> element offset of its first channel in y.  Dense outputs (train-mode z, data gradients:
 // y is [M][yC] in sub-grid order) need no split at all; otherwise image / row / column by float-reciprocal division.
 struct PixSplit {
@@ -63,6 +72,17 @@ static __device__ __forceinline__ void frag_pair_swap(uint2& X, uint2& Y) {
 }
 // element offset, inside the wave's channel range, of this lane's 16 bytes of the pair (a, a + 1), a even
 static __device__ __forceinline__ int frag_pair_chan(int a, int fq) { return (a + (fq & 1)) * 16 + (fq >> 1) * 8; }
+// One pair as loaded 16 bytes wide -> the MFMA layout: X = group a, Y = group a + 1 ...
+static __device__ __forceinline__ void frag_pair_unpack(const uint4& q, uint2& X, uint2& Y) {
+    X = uint2{q.x, q.y};
+    Y = uint2{q.z, q.w};
+    frag_pair_swap(X, Y);
+}
+// ... and back: the 16 bytes this lane stores at frag_pair_chan(a, fq) (X, Y clobbered)
+static __device__ __forceinline__ uint4 frag_pair_pack(uint2& X, uint2& Y) {
+    frag_pair_swap(X, Y);
+    return uint4{X.x, X.y, Y.x, Y.y};
+}
 // One pixel's fragments of a bf16 tensor for NI channel groups, as loaded: pairs 16 bytes wide in the exchanged layout, a
 // trailing odd group 8 bytes wide in the MFMA layout.  `base` = the pixel's first channel of this wave's channel range.
 template <int NI>
@@ -82,11 +102,7 @@ static __device__ __forceinline__ void frag_row_load(FragRow<NI>& f, const bf16_
 template <int NI>
 static __device__ __forceinline__ void frag_row_unpack(const FragRow<NI>& f, uint2 (&v)[NI]) {
 #pragma unroll
-    for (int a = 0; a + 1 < NI; a += 2) {
-        v[a] = uint2{f.q[a / 2].x, f.q[a / 2].y};
-        v[a + 1] = uint2{f.q[a / 2].z, f.q[a / 2].w};
-        frag_pair_swap(v[a], v[a + 1]);
-    }
+    for (int a = 0; a + 1 < NI; a += 2) frag_pair_unpack(f.q[a / 2], v[a], v[a + 1]);
     if constexpr ((NI & 1) != 0) v[NI - 1] = uint2{f.q[NI / 2].x, f.q[NI / 2].y};
 }
 // ... and the store of NI packed groups (MFMA layout in, clobbered)
@@ -94,8 +110,8 @@ template <int NI>
 static __device__ __forceinline__ void frag_row_store(bf16_t* base, uint2 (&v)[NI], int fq, bool valid) {
 #pragma unroll
     for (int a = 0; a + 1 < NI; a += 2) {
-        frag_pair_swap(v[a], v[a + 1]);
-        if (valid) vpd_store16<VPD_CP_EPI>(base + frag_pair_chan(a, fq), uint4{v[a].x, v[a].y, v[a + 1].x, v[a + 1].y});
+        const uint4 ov = frag_pair_pack(v[a], v[a + 1]);
+        if (valid) vpd_store16<VPD_CP_EPI>(base + frag_pair_chan(a, fq), ov);
     }
     if constexpr ((NI & 1) != 0) {
         if (valid) *reinterpret_cast<uint2*>(base + (NI - 1) * 16 + 4 * fq) = v[NI - 1];

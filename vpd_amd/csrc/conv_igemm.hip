@@ -22,14 +22,6 @@
 #include "conv_epilogue.h"
 #include "kernels.h"
 
-template <int NI, int MI>
-static __device__ __forceinline__ void zero_acc(f32x4 (&acc)[NI][MI]) {
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
 template <int BM, int BN, int WM, int WN, int EPM>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0) {
     static_assert(WM * WN == 4, "4 waves");

@@ -44,33 +44,92 @@ struct StreamGeo {
     int rows_per_tile;      // BM / Ws
 };
 
-// The loader waves' part of a block (the four waves behind the MFMA waves, lw = 0..3): the resident weight tile, then the block's pixel tiles through
-// the ring.  PRE: extra workgroup barriers the MFMA waves run before their first tile (a coefficient prologue), matched here
-// once the first AHEAD tiles are on their way.  Returns in front of the END barrier.
+// LDS of a block: the resident weights [KC / 64][BN][64], NSA ring stages [KC / 64][BM][64], then `coef_rows` rows of BN floats
+// (the fused kernels' per-channel coefficients)
+constexpr size_t stream_lds_bytes(int KC, int BM, int BN, int NSA, int coef_rows = 0) {
+    return (size_t)(KC / 64) * 64 * (BN + NSA * BM) * sizeof(bf16_t) + (size_t)coef_rows * BN * sizeof(float);
+}
+
+// What a wave of a streaming block knows about itself: NMW MFMA waves (4 or 8: WM pixel waves x WN channel waves) in front of four
+// loader waves, the carve-up of the block's LDS and the block's pixel tiles first, first + lanes, ... (ntile of them).
+template <int KC_, int BM_, int BN_, int NSA_, int NMW_>
+struct StreamBlock {
+    static constexpr int KC = KC_, BM = BM_, BN = BN_, NSA = NSA_, NMW = NMW_;
+    static constexpr int KCH = KC / 64;
+    static constexpr int WN = BN >= 256 ? 4 : BN / 64, WM = NMW / WN;
+    static constexpr int WTM = BM / WM, WTN = BN / WN, MI = WTM / 16, NI = WTN / 16;
+    static constexpr int WELEMS = KCH * BN * 64, ASTAGE = KCH * BM * 64;
+    unsigned char* smem;
+    bf16_t* sW; bf16_t* ring; float* coef;
+    int tid, lane, wave, n0, lanes, first, ntile;
+    int wm, wn, fr, fq, nw;      // MFMA waves: pixel wave, channel wave, fragment row / quarter, first channel of the wave
+
+    __device__ __forceinline__ StreamBlock(const StreamGeo& sg) {
+        extern __shared__ __attribute__((aligned(16))) unsigned char stream_smem[];
+        smem = stream_smem;
+        sW = reinterpret_cast<bf16_t*>(smem);
+        ring = sW + WELEMS;
+        coef = reinterpret_cast<float*>(ring + NSA * ASTAGE);
+        tid = threadIdx.x;
+        lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        n0 = blockIdx.y * BN;
+        lanes = gridDim.x;
+        first = blockIdx.x;
+        ntile = first < sg.mtiles ? (sg.mtiles - first + lanes - 1) / lanes : 0;
+        wm = wave % WM; wn = wave / WM;
+        fr = lane & 15; fq = lane >> 4;
+        nw = n0 + wn * WTN;
+    }
+    // asked BEFORE a wave makes its StreamBlock: the loader branch and the MFMA branch of a kernel each construct their own (one
+    // object in front of the branch keeps two more VGPRs live in nearly every instantiation -- a property of the compiler at hand:
+    // profiles/stream_shared_resources.txt is the table to regenerate when the toolchain changes)
+    static __device__ __forceinline__ bool loader() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) >= NMW; }
+    __device__ __forceinline__ int mtile(int it) const { return first + it * lanes; }
+    // (MFMA waves) the pixel of fragment row fr in pixel group b of a tile
+    __device__ __forceinline__ int pixel(int mtile, int b) const { return mtile * BM + wm * WTM + b * 16 + fr; }
+    __device__ __forceinline__ const bf16_t* stage(int it) const { return ring + (it % NSA) * ASTAGE; }
+    // coefficient row k: this lane's four channels of group a
+    __device__ __forceinline__ float4 coef4(int k, int a) const {
+        return *reinterpret_cast<const float4*>(coef + k * BN + wn * WTN + a * 16 + 4 * fq);
+    }
+};
+
+template <int N>
+static __device__ __forceinline__ void stream_barriers() {
+#pragma unroll
+    for (int k = 0; k < N; ++k) __builtin_amdgcn_s_barrier();
+}
+
+// The loader waves' part of a block (the four waves behind the MFMA waves, lw = 0..3): the resident weight tile, then the block's
+// pixel tiles through the ring, then the END barrier.  The MFMA waves run workgroup barriers of their own around that, which the
+// loaders must run too:
+//   PRE   before their first tile (a coefficient prologue), matched here once the first AHEAD tiles are on their way,
+//   TAIL  behind the END barrier (stream_tail_barriers).
 // DUAL: two convolutions of 64 input channels each on the same pixels (same padded geometry): chunk 0 = (p.x, p.w), chunk 1 =
 // (p.x2, p.w2) -- a down-sampling Bottleneck's closing 1x1 and its 1x1 branch (conv1x1_bn2_stream_kernel)
-template <int KC, int BM, int BN, int NSA, int PRE = 0, bool DUAL = false>
-static __device__ __forceinline__ void stream_loader(const ConvParams& p, const StreamGeo& sg, bf16_t* sW, bf16_t* ring, int n0,
-                                                     int first, int lanes, int ntile, int lw, int lane) {
-    constexpr int KCH = KC / 64;
-    constexpr int ASTAGE = KCH * BM * 64;
-    constexpr int A_PER = BM / 32;
+template <class B, int PRE, int TAIL, bool DUAL = false>
+static __device__ __forceinline__ void stream_loader(const ConvParams& p, const StreamGeo& sg, const B& blk) {
+    constexpr int KCH = B::KCH, BM = B::BM, BN = B::BN, NSA = B::NSA;
+    constexpr int A_PER = BM / 32;                     // LDS-DMA instructions per loader wave, chunk and tile
     constexpr int PER_TILE = A_PER * KCH;
     constexpr int W_PER = BN / 32;
     constexpr int AHEAD = NSA - 1;
-    const int piece = lane & 7;
-    const int lrow = lane >> 3;
+    static_assert(NSA >= 2 && AHEAD * PER_TILE < 64, "ring depth");
+    static_assert(!DUAL || B::KC == 128, "DUAL: two chunks of 64 channels");
+    const int lw = blk.wave - B::NMW;
+    const int piece = blk.lane & 7;
+    const int lrow = blk.lane >> 3;
     // weights: [BN][Kc] rows n0 .. of the one tap, chunk by chunk
     const bf16_t* const wsrc = p.w + (size_t)p.taps.w0 * p.Co * p.Kc;
-    static_assert(!DUAL || KC == 128, "DUAL: two chunks of 64 channels");
 #pragma unroll
     for (int cc = 0; cc < KCH; ++cc)
 #pragma unroll
         for (int i = 0; i < W_PER; ++i) {
             const int n = (lw + 4 * i) * 8 + lrow;
-            const bf16_t* const ws = DUAL ? (cc ? p.w2 : p.w) + (size_t)(n0 + n) * 64 : wsrc + (size_t)(n0 + n) * p.Kc + cc * 64;
+            const bf16_t* const ws = DUAL ? (cc ? p.w2 : p.w) + (size_t)(blk.n0 + n) * 64 : wsrc + (size_t)(blk.n0 + n) * p.Kc + cc * 64;
             __builtin_amdgcn_global_load_lds((gptr_t)(ws + ((piece ^ (n & 7)) << 3)),
-                                             (lptr_t)(sW + (cc * BN + (lw + 4 * i) * 8) * 64), 16, 0, 0);
+                                             (lptr_t)(blk.sW + (cc * BN + (lw + 4 * i) * 8) * 64), 16, 0, 0);
         }
     // this lane's pixel rows of a tile: offsets from the tile's first pixel (same in every tile)
     int aoff[A_PER];
@@ -83,12 +142,12 @@ static __device__ __forceinline__ void stream_loader(const ConvParams& p, const 
     }
     const int tap_off = (p.taps.dy0 * p.xWp + p.taps.dx0) * p.xC;
     auto issue = [&](int it) __attribute__((always_inline)) {
-        const int t = first + it * lanes;
+        const int t = blk.mtile(it);
         const int b = t / sg.tiles_per_img;
         const int r0 = (t - b * sg.tiles_per_img) * sg.rows_per_tile;
         const size_t toff = (size_t)((b * p.xHp + r0 * p.istr) * p.xWp) * p.xC + tap_off;
         const bf16_t* const src = p.x + toff;
-        bf16_t* const st = ring + (it % NSA) * ASTAGE;
+        bf16_t* const st = blk.ring + (it % NSA) * B::ASTAGE;
 #pragma unroll
         for (int cc = 0; cc < KCH; ++cc)
 #pragma unroll
@@ -98,18 +157,18 @@ static __device__ __forceinline__ void stream_loader(const ConvParams& p, const 
     };
 #pragma unroll
     for (int it = 0; it < AHEAD; ++it)
-        if (it < ntile) issue(it);
-#pragma unroll
-    for (int k = 0; k < PRE; ++k) __builtin_amdgcn_s_barrier();
-    for (int it = 0; it < ntile; ++it) {
+        if (it < blk.ntile) issue(it);
+    stream_barriers<PRE>();
+    for (int it = 0; it < blk.ntile; ++it) {
         // tile `it` (and the weights, issued before everything) must have landed; the tiles issued behind it may be in flight
-        int behind = ntile - 1 - it;
+        int behind = blk.ntile - 1 - it;
         behind = behind < AHEAD - 1 ? behind : AHEAD - 1;
         stream_wait_tiles<PER_TILE, AHEAD - 1>(behind);
         __builtin_amdgcn_s_barrier();                         // READY_it (stage (it - 1) % NSA is free again)
-        if (it + AHEAD < ntile) issue(it + AHEAD);
+        if (it + AHEAD < blk.ntile) issue(it + AHEAD);
     }
-    if (ntile == 0) stream_wait_vm<0>();
+    if (blk.ntile == 0) stream_wait_vm<0>();
+    stream_barriers<1 + TAIL>();                              // END, and the MFMA waves' barriers behind it
 }
 
 // One pixel tile out of LDS: acc[a][b] += W[channels wn*WTN + 16a ..][K] . X[pixels wm*WTM + 16b ..][K]
@@ -142,108 +201,87 @@ static __device__ __forceinline__ void stream_mma(const bf16_t* sW, const bf16_t
 }
 
 // per-lane partial sums -> 16 pixel lanes (DPP) -> WM pixel waves (LDS) -> ONE fp64 atomic per channel and block into accumulator
-// row blockIdx.x % rows.  MFMA waves only; contains ONE block barrier, which the loader waves match.
-template <int BN, int WM, int WN>      // WM * WN MFMA waves
-static __device__ __forceinline__ void stream_stats_flush(double* rows, int stat_rows, int Co, int n0, float (&st1)[BN / WN / 16][4],
-                                                          float (&st2)[BN / WN / 16][4], unsigned char* smem) {
-    constexpr int WTN = BN / WN, NI = WTN / 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave % WM, wn = wave / WM, fr = lane & 15, fq = lane >> 4;
-    float* red = reinterpret_cast<float*>(smem);              // [WM][2][BN] (the ring is idle now)
+// row blockIdx.x % rows.  MFMA waves only, behind the END barrier; contains ONE workgroup barrier.
+template <class B>
+static __device__ __forceinline__ void stream_stats_flush(double* rows, int stat_rows, int Co, const B& blk, float (&st1)[B::NI][4],
+                                                          float (&st2)[B::NI][4]) {
+    constexpr int BN = B::BN, WM = B::WM, NI = B::NI;
+    float* red = reinterpret_cast<float*>(blk.smem);          // [WM][2][BN] (the ring is idle now)
 #pragma unroll
     for (int a = 0; a < NI; ++a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float u = row16_sum(st1[a][j]), v = row16_sum(st2[a][j]);
-            if (fr == 0) {
-                const int c = wn * WTN + a * 16 + 4 * fq + j;
-                red[(wm * 2 + 0) * BN + c] = u;
-                red[(wm * 2 + 1) * BN + c] = v;
+            if (blk.fr == 0) {
+                const int c = blk.wn * B::WTN + a * 16 + 4 * blk.fq + j;
+                red[(blk.wm * 2 + 0) * BN + c] = u;
+                red[(blk.wm * 2 + 1) * BN + c] = v;
             }
         }
     __syncthreads();
     if (rows) {
         const int rmask = (stat_rows ? stat_rows : VPD_STAT_ROWS) - 1;
-        for (int i = tid; i < 2 * BN; i += WM * WN * 64) {
+        for (int i = blk.tid; i < 2 * BN; i += B::NMW * 64) {
             const int which = i / BN;
             const int c = i - which * BN;
             float t = 0.f;
 #pragma unroll
             for (int w = 0; w < WM; ++w) t += red[(w * 2 + which) * BN + c];
-            atomicAdd(&rows[((size_t)((int)blockIdx.x & rmask) * 2 + which) * Co + n0 + c], (double)t);
+            atomicAdd(&rows[((size_t)((int)blockIdx.x & rmask) * 2 + which) * Co + blk.n0 + c], (double)t);
         }
     }
 }
+// ... of two BatchNorms that share sum g (st1): the second flush reuses `red`, so a barrier stands between them
+template <class B>
+static __device__ __forceinline__ void stream_stats_flush2(double* rows3, double* rowsD, int stat_rows, int Co, const B& blk,
+                                                           float (&st1)[B::NI][4], float (&st2)[B::NI][4], float (&st3)[B::NI][4]) {
+    stream_stats_flush(rows3, stat_rows, Co, blk, st1, st2);
+    __syncthreads();
+    stream_stats_flush(rowsD, stat_rows, Co, blk, st1, st3);
+}
+// Workgroup barriers the MFMA waves run behind the END barrier, which the loader waves run too (stream_loader's TAIL): those of
+// the statistics flush above for `nconv` BatchNorms -- one per flush and one between two
+constexpr int stream_tail_barriers(bool flush, int nconv) { return flush ? 2 * nconv - 1 : 0; }
 
 template <int KC, int BM, int BN, int NSA, int EPM, int NMW = 4>      // NMW MFMA waves (4 or 8) + 4 loader waves
 __global__ __launch_bounds__((NMW + 4) * 64) void conv1x1_stream_kernel(const ConvParams p, const StreamGeo sg) {
-    constexpr int KCH = KC / 64;
-    constexpr int WN = BN >= 256 ? 4 : BN / 64;
-    constexpr int WM = NMW / WN;
-    constexpr int WTM = BM / WM, WTN = BN / WN;
-    constexpr int MI = WTM / 16, NI = WTN / 16;
-    constexpr int WELEMS = KCH * BN * 64;              // resident weights [KCH][BN][64]
-    constexpr int ASTAGE = KCH * BM * 64;              // one ring stage   [KCH][BM][64]
-    constexpr int A_PER = BM / 32;                     // LDS-DMA instructions per loader wave, chunk and tile
-    constexpr int PER_TILE = A_PER * KCH;
-    constexpr int W_PER = BN / 32;
-    constexpr int AHEAD = NSA - 1;
-    static_assert(NSA >= 2 && AHEAD * PER_TILE < 64, "ring depth");
-    static_assert((size_t)(WELEMS + NSA * ASTAGE) * 2 <= 160 * 1024, "LDS");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16_t* const sW = reinterpret_cast<bf16_t*>(smem);
-    bf16_t* const ring = sW + WELEMS;
-
+    using B = StreamBlock<KC, BM, BN, NSA, NMW>;
+    constexpr int WM = B::WM, WN = B::WN, MI = B::MI, NI = B::NI;
+    constexpr bool FLUSH = EPM == 1 || EPM == 4;
+    static_assert(stream_lds_bytes(KC, BM, BN, NSA) <= 160 * 1024, "LDS");
     const ConvGeo geo = {p.Hs, p.Ws, p.M, p.oph, p.opw};
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n0 = blockIdx.y * BN;
-    const int lanes = gridDim.x;
-    const int first = blockIdx.x;
-    const int ntile = first < sg.mtiles ? (sg.mtiles - first + lanes - 1) / lanes : 0;      // tiles of this block
-
-    if (wave >= NMW) {
-        stream_loader<KC, BM, BN, NSA>(p, sg, sW, ring, n0, first, lanes, ntile, wave - NMW, lane);
-        __builtin_amdgcn_s_barrier();                             // END
-        if (EPM == 1 || EPM == 4) __builtin_amdgcn_s_barrier();   // matches the barrier inside the statistics flush
+    if (B::loader()) {
+        stream_loader<B, 0, stream_tail_barriers(FLUSH, 1)>(p, sg, B(sg));
         return;
     }
-
-    const int wm = wave % WM;
-    const int wn = wave / WM;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
+    const B blk(sg);
     float st1[NI][4], st2[NI][4];
 #pragma unroll
     for (int a = 0; a < NI; ++a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) { st1[a][j] = 0.f; st2[a][j] = 0.f; }
-    for (int it = 0; it < ntile; ++it) {
-        const int mtile = first + it * lanes;
+    for (int it = 0; it < blk.ntile; ++it) {
+        const int mtile = blk.mtile(it);
         // fragments of the other tensors the epilogue reads: requested before the tile's barrier
         ResFrag<NI, MI> resf;
         AccFrag<NI, MI> accf;
-        if (EPM == 3 && p.res) conv_res_prefetch<BM, BN, WM, WN>(p, mtile, n0, geo, resf);
-        if (EPM == 2) conv_acc_prefetch<BM, BN, WM, WN>(p, mtile, n0, geo, accf);
+        if (EPM == 3 && p.res) conv_res_prefetch<BM, BN, WM, WN>(p, mtile, blk.n0, geo, resf);
+        if (EPM == 2) conv_acc_prefetch<BM, BN, WM, WN>(p, mtile, blk.n0, geo, accf);
         f32x4 acc[NI][MI];
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-#pragma unroll
-            for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         __builtin_amdgcn_s_barrier();                             // READY_it
-        stream_mma<KC, BM, BN, WM, WN>(sW, ring + (it % NSA) * ASTAGE, acc, wm, wn, fr, fq);
+        stream_mma<KC, BM, BN, WM, WN>(blk.sW, blk.stage(it), acc, blk.wm, blk.wn, blk.fr, blk.fq);
         if (EPM == 3 && p.res) {
-            conv_epilogue_res_pre<BM, BN, WM, WN, EPM>(p, acc, mtile, n0, st1, st2, geo, resf);
+            conv_epilogue_res_pre<BM, BN, WM, WN, EPM>(p, acc, mtile, blk.n0, st1, st2, geo, resf);
         } else if (EPM == 2) {
             BstFrag<NI, VPD_BST_MB(MI)> none;
-            conv_epilogue_acc_pre<BM, BN, WM, WN, EPM>(p, acc, mtile, n0, st1, st2, geo, none, accf);
+            conv_epilogue_acc_pre<BM, BN, WM, WN, EPM>(p, acc, mtile, blk.n0, st1, st2, geo, none, accf);
         } else {
-            conv_epilogue<BM, BN, WM, WN, EPM>(p, acc, mtile, n0, st1, st2, geo);
+            conv_epilogue<BM, BN, WM, WN, EPM>(p, acc, mtile, blk.n0, st1, st2, geo);
         }
     }
     __builtin_amdgcn_s_barrier();                                 // END
-    if (EPM == 1 || EPM == 4) stream_stats_flush<BN, WM, WN>(p.stats, p.stat_rows, p.Co, n0, st1, st2, smem);
+    if (FLUSH) stream_stats_flush(p.stats, p.stat_rows, p.Co, blk, st1, st2);
 }
 
 // ---------------------------------------------------------------------------
@@ -262,16 +300,64 @@ __global__ __launch_bounds__((NMW + 4) * 64) void conv1x1_stream_kernel(const Co
 // the backward has bn_bwd_apply_fused_kernel's arithmetic.  64 x 256 tiles (eight MFMA waves x 32 pixels x 64 channels; the statistics
 // pass keeps the storing launch's four), Kc = 64 / 128.
 // ---------------------------------------------------------------------------
-struct StreamBn {
-    const double* rows; float count;                       // MODE 1 / 3: the sums to finalize ([VPD_FUSED_ROWS][2][Co])
+constexpr int TAIL_BM = 64, TAIL_BN = 256, TAIL_NMW = 8;      // the fused kernels' tile and MFMA waves (2 pixel x 4 channel waves)
+constexpr int TAIL_THREADS = (TAIL_NMW + 4) * 64;
+
+struct StreamBnSide {                                      // one BatchNorm
+    const double* rows;                                    // MODE 1 / 3: the sums to finalize ([VPD_FUSED_ROWS][2][Co])
     const float* gamma; const float* beta;
     float* mean; float* rstd; float* scale; float* shift;  // MODE 1: written (first lane); MODE 3: mean / rstd read
-    float* rm; float* rv; float momentum, eps;             // MODE 1: running statistics (may be null)
-    unsigned char* mask_out;                               // MODE 1: ReLU bit map [M][Co / 8] (may be null)
+    float* rm; float* rv;                                  // MODE 1: running statistics (may be null)
     double* rows_out;                                      // MODE 2: rows to add sum g / sum g z to
     float* dgamma; float* dbeta;                           // MODE 3 (first lane)
-    bf16_t* dz; int dzHp, dzWp, dzpad;                     // MODE 3: output (p.y = d(out), dense, with p.acc_mask = the bit map)
+    bf16_t* dz;                                            // MODE 3: output (p.y = d(out), dense, with p.acc_mask = the bit map)
 };
+struct StreamBn {
+    float count, momentum, eps;
+    unsigned char* mask_out;                               // MODE 1: ReLU bit map [M][Co / 8] (may be null)
+    int dzHp, dzWp, dzpad;                                 // MODE 3: geometry of every side's dz
+    StreamBnSide s;                                        // the closing convolution's BatchNorm
+};
+
+// ---- coefficient prologues: one channel `ch` per thread ----
+// MODE 1: scale / shift of the channel; the blocks of the first pixel lane publish the BatchNorm's vectors
+static __device__ __forceinline__ void stream_bn_finalize(const StreamBnSide& s, const StreamBn& bn, int Co, int ch, float* coef_scale,
+                                                          float* coef_shift) {
+    float mu, r, sc, sh; double var;
+    bn_finalize_channel(s.rows, Co, ch, bn.count, bn.eps, s.gamma[ch], s.beta[ch], &mu, &r, &sc, &sh, &var);
+    *coef_scale = sc; *coef_shift = sh;
+    if (blockIdx.x == 0) {
+        s.mean[ch] = mu; s.rstd[ch] = r; s.scale[ch] = sc; s.shift[ch] = sh;
+        if (s.rm) {
+            const double unb = bn.count > 1.f ? var * (double)bn.count / ((double)bn.count - 1.0) : var;
+            s.rm[ch] = (1.f - bn.momentum) * s.rm[ch] + bn.momentum * mu;
+            s.rv[ch] = (1.f - bn.momentum) * s.rv[ch] + bn.momentum * (float)unb;
+        }
+    }
+}
+// MODE 3: A / B / D into three coefficient rows of BN floats at `coef`, entry i; dgamma / dbeta from the first lane
+template <int BN>
+static __device__ __forceinline__ void stream_bn_bwd_coef(const StreamBnSide& s, const StreamBn& bn, int Co, int ch, float* coef, int i) {
+    bn_bwd_apply_coef(s.rows, Co, ch, bn.count, s.gamma[ch], s.mean[ch], s.rstd[ch], coef, coef + BN, coef + 2 * BN, s.dgamma, s.dbeta,
+                      blockIdx.x == 0, i);
+}
+
+// ---- a lane's four channels of one group ----
+static __device__ __forceinline__ void stream_unpack4(const uint2& v, float (&f)[4]) {
+    f[0] = bf2f((unsigned short)(v.x & 0xffff)); f[1] = bf2f((unsigned short)(v.x >> 16));
+    f[2] = bf2f((unsigned short)(v.y & 0xffff)); f[3] = bf2f((unsigned short)(v.y >> 16));
+}
+// a coefficient row of StreamBlock::coef4 (kept as the float4 it is loaded as and taken apart at its use: the same rows as an
+// indexable vector type put the two-convolution MODE 3 kernel into scratch)
+static __device__ __forceinline__ void stream_coef4(const float4& k, float (&c)[4]) { c[0] = k.x; c[1] = k.y; c[2] = k.z; c[3] = k.w; }
+static __device__ __forceinline__ uint2 stream_pack4(const float (&v)[4]) { return uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])}; }
+// z as the unfused path stores it
+static __device__ __forceinline__ void stream_round4(const f32x4& acc, float (&z)[4]) {
+    stream_unpack4(uint2{pack2bf(acc[0], acc[1]), pack2bf(acc[2], acc[3])}, z);
+}
+// g = d(out) * mask: this lane's four bits of group a in the pixel's bits of the wave's channel range, and channel j of them
+static __device__ __forceinline__ unsigned stream_mask4(unsigned long long mbits, int a, int fq) { return (unsigned)(mbits >> (a * 16 + 4 * fq)); }
+static __device__ __forceinline__ float stream_masked_g(unsigned bits, int j, float d) { return ((bits >> j) & 1u) ? d : 0.f; }
 
 static __device__ __forceinline__ unsigned stream_relu_bits(const uint4& ov) {
     // [half != 0] of eight stored non-negative bf16 values as one byte (bn_fwd_fused_kernel's form)
@@ -286,67 +372,77 @@ static __device__ __forceinline__ unsigned stream_relu_bits(const uint4& ov) {
     return (acc | (acc >> 15)) & 0xffu;
 }
 
-template <int KC, int NSA, int MODE>
-__global__ __launch_bounds__(768) void conv1x1_bn_stream_kernel(const ConvParams p, const StreamGeo sg, const StreamBn bn) {
-    // eight MFMA waves (two per SIMD: one's fragment reads and epilogue arithmetic under the other's MFMAs -- with four, the
-    // statistics passes ran at 1.8-3 TB/s on phases that do not overlap inside one wave) x 32 pixels x 64 channels
-    constexpr int BM = 64, BN = 256, WM = 2, WN = 4, NMW = 8;
-    constexpr int KCH = KC / 64;
-    constexpr int WTM = BM / WM, WTN = BN / WN, MI = WTM / 16, NI = WTN / 16;
-    constexpr int WELEMS = KCH * BN * 64, ASTAGE = KCH * BM * 64;
-    static_assert((size_t)(WELEMS + NSA * ASTAGE) * 2 + 3 * BN * 4 <= 160 * 1024, "LDS");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16_t* const sW = reinterpret_cast<bf16_t*>(smem);
-    bf16_t* const ring = sW + WELEMS;
-    float* const coef = reinterpret_cast<float*>(ring + NSA * ASTAGE);      // [3][BN]
-    const ConvGeo geo = {p.Hs, p.Ws, p.M, p.oph, p.opw};
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n0 = blockIdx.y * BN;
-    const int lanes = gridDim.x;
-    const int first = blockIdx.x;
-    const int ntile = first < sg.mtiles ? (sg.mtiles - first + lanes - 1) / lanes : 0;
-    constexpr int PRE = (MODE == 1 || MODE == 3) ? 1 : 0;
-    if (wave >= NMW) {
-        stream_loader<KC, BM, BN, NSA, PRE>(p, sg, sW, ring, n0, first, lanes, ntile, wave - NMW, lane);
-        __builtin_amdgcn_s_barrier();                             // END
-        if (MODE == 2) __builtin_amdgcn_s_barrier();              // statistics flush
-        return;
-    }
-    const int wm = wave % WM;
-    const int wn = wave / WM;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
-    const int nw = n0 + wn * WTN;
-    // ---- coefficient prologue: one channel per thread (the first BN of the MFMA waves' threads) ----
-    if (MODE == 1 && tid < BN) {
-        const int ch = n0 + tid;
-        float mu, r, sc, sh; double var;
-        bn_finalize_channel(bn.rows, p.Co, ch, bn.count, bn.eps, bn.gamma[ch], bn.beta[ch], &mu, &r, &sc, &sh, &var);
-        coef[tid] = sc; coef[BN + tid] = sh;
-        if (blockIdx.x == 0) {
-            bn.mean[ch] = mu; bn.rstd[ch] = r; bn.scale[ch] = sc; bn.shift[ch] = sh;
-            if (bn.rm) {
-                const double unb = bn.count > 1.f ? var * (double)bn.count / ((double)bn.count - 1.0) : var;
-                bn.rm[ch] = (1.f - bn.momentum) * bn.rm[ch] + bn.momentum * mu;
-                bn.rv[ch] = (1.f - bn.momentum) * bn.rv[ch] + bn.momentum * (float)unb;
+// element offset of output pixel m (every row of a tile is a pixel: M % BM == 0) in the padded tensor a MODE writes: p.y
+// (MODE 1) or every side's dz (MODE 3)
+template <int MODE>
+static __device__ __forceinline__ size_t stream_out_off(const ConvParams& p, const StreamBn& bn, const PixSplit& ps, int m) {
+    int bi, yy, xx;
+    pix_split(ps, m, bi, yy, xx);
+    if (MODE == 1) return ((size_t)(bi * p.yHp + yy + p.ypad) * p.yWp + (xx + p.ypad)) * p.yC;
+    return ((size_t)(bi * bn.dzHp + yy + bn.dzpad) * bn.dzWp + (xx + bn.dzpad)) * p.Co;
+}
+// MODE 1: eight channels from `chan` on of pixel m (element offset off in p.y) and their byte of the ReLU bit map
+static __device__ __forceinline__ void stream_store_out(const ConvParams& p, const StreamBn& bn, size_t off, int m, int chan, const uint4& ov) {
+    vpd_store16<VPD_CP_EPI>(p.y + off + chan, ov);
+    if (bn.mask_out) bn.mask_out[(size_t)m * (p.Co >> 3) + (chan >> 3)] = (unsigned char)stream_relu_bits(ov);
+}
+// MODE 2 of one convolution of the two-convolution kernel: sum g -> sg (WITH_G), sum g z -> sz, z rounded as stored (the
+// one-convolution kernel forms the same sums inside its one tile loop: through this function its K = 64 instantiation lost a wave)
+template <bool WITH_G, int NI, int MI>
+static __device__ __forceinline__ void stream_bwd_sums(const f32x4 (&acc)[NI][MI], const AccFrag<NI, MI>& accf, int fq, float (&sg)[NI][4],
+                                                       float (&sz)[NI][4]) {
+#pragma unroll
+    for (int b = 0; b < MI; ++b)
+#pragma unroll
+        for (int a0 = 0; a0 < NI; a0 += 2) {
+            uint2 dv[2];
+            frag_pair_unpack(accf.old[b].q[a0 / 2], dv[0], dv[1]);
+#pragma unroll
+            for (int ai = 0; ai < 2; ++ai) {
+                const int a = a0 + ai;
+                float z[4], d[4];
+                stream_round4(acc[a][b], z);
+                stream_unpack4(dv[ai], d);
+                const unsigned bits = stream_mask4(accf.bits[b], a, fq);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float g = stream_masked_g(bits, j, d[j]);
+                    if (WITH_G) sg[a][j] += g;
+                    sz[a][j] += g * z[j];
+                }
             }
         }
-    } else if (MODE == 3 && tid < BN) {
-        const int ch = n0 + tid;
-        bn_bwd_apply_coef(bn.rows, p.Co, ch, bn.count, bn.gamma[ch], bn.mean[ch], bn.rstd[ch], coef, coef + BN, coef + 2 * BN,
-                          bn.dgamma, bn.dbeta, blockIdx.x == 0, tid);
+}
+
+template <int KC, int NSA, int MODE>
+__global__ __launch_bounds__(TAIL_THREADS) void conv1x1_bn_stream_kernel(const ConvParams p, const StreamGeo sg, const StreamBn bn) {
+    // eight MFMA waves (two per SIMD: one's fragment reads and epilogue arithmetic under the other's MFMAs -- with four, the
+    // statistics passes ran at 1.8-3 TB/s on phases that do not overlap inside one wave) x 32 pixels x 64 channels
+    using B = StreamBlock<KC, TAIL_BM, TAIL_BN, NSA, TAIL_NMW>;
+    constexpr int BM = B::BM, BN = B::BN, WM = B::WM, WN = B::WN, MI = B::MI, NI = B::NI;
+    constexpr int PRE = MODE == 2 ? 0 : 1;
+    static_assert(stream_lds_bytes(KC, BM, BN, NSA, 3) <= 160 * 1024, "LDS");
+    if (B::loader()) {
+        stream_loader<B, PRE, stream_tail_barriers(MODE == 2, 1)>(p, sg, B(sg));
+        return;
     }
-    float4 k0[NI] = {}, k1[NI] = {}, k2[NI] = {};      // this lane's channels' coefficients: (scale, shift) or (A, B, D)
+    const B blk(sg);
+    const int fq = blk.fq;
+    // ---- coefficient prologue (the first BN of the MFMA waves' threads): (scale, shift) or (A, B, D) ----
+    if (PRE && blk.tid < BN) {
+        const int ch = blk.n0 + blk.tid;
+        if (MODE == 1) stream_bn_finalize(bn.s, bn, p.Co, ch, blk.coef + blk.tid, blk.coef + BN + blk.tid);
+        else stream_bn_bwd_coef<BN>(bn.s, bn, p.Co, ch, blk.coef, blk.tid);
+    }
+    float4 k0[NI] = {}, k1[NI] = {}, k2[NI] = {};      // this lane's channels' coefficients
     if (PRE) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int a = 0; a < NI; ++a) {
-            k0[a] = *reinterpret_cast<const float4*>(coef + wn * WTN + a * 16 + 4 * fq);
-            k1[a] = *reinterpret_cast<const float4*>(coef + BN + wn * WTN + a * 16 + 4 * fq);
-            if (MODE == 3) k2[a] = *reinterpret_cast<const float4*>(coef + 2 * BN + wn * WTN + a * 16 + 4 * fq);
+            k0[a] = blk.coef4(0, a);
+            k1[a] = blk.coef4(1, a);
+            if (MODE == 3) k2[a] = blk.coef4(2, a);
         }
     }
     float st1[NI][4], st2[NI][4];
@@ -354,46 +450,35 @@ __global__ __launch_bounds__(768) void conv1x1_bn_stream_kernel(const ConvParams
     for (int a = 0; a < NI; ++a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) { st1[a][j] = 0.f; st2[a][j] = 0.f; }
+    const ConvGeo geo = {p.Hs, p.Ws, p.M, p.oph, p.opw};
     const PixSplit ps = pix_split_init(p, geo);
-    for (int it = 0; it < ntile; ++it) {
-        const int mtile = first + it * lanes;
+    for (int it = 0; it < blk.ntile; ++it) {
+        const int mtile = blk.mtile(it);
         ResFrag<NI, MI> resf;      // MODE 1: the identity path (padded activation)
         AccFrag<NI, MI> accf;      // MODE 2 / 3: d(out) (dense) and its ReLU bits
-        if (MODE == 1) conv_res_prefetch<BM, BN, WM, WN>(p, mtile, n0, geo, resf);
-        else conv_acc_prefetch<BM, BN, WM, WN>(p, mtile, n0, geo, accf);
+        if (MODE == 1) conv_res_prefetch<BM, BN, WM, WN>(p, mtile, blk.n0, geo, resf);
+        else conv_acc_prefetch<BM, BN, WM, WN>(p, mtile, blk.n0, geo, accf);
         f32x4 acc[NI][MI];
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-#pragma unroll
-            for (int b = 0; b < MI; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
         __builtin_amdgcn_s_barrier();                             // READY_it
-        stream_mma<KC, BM, BN, WM, WN>(sW, ring + (it % NSA) * ASTAGE, acc, wm, wn, fr, fq);
+        stream_mma<KC, BM, BN, WM, WN>(blk.sW, blk.stage(it), acc, blk.wm, blk.wn, blk.fr, fq);
 #pragma unroll
         for (int b = 0; b < MI; ++b) {
-            const int m = mtile * BM + wm * WTM + b * 16 + fr;    // (M % BM == 0: every row is a pixel)
-            int bi, yy, xx;
-            pix_split(ps, m, bi, yy, xx);
-            const FragRow<NI>& other = MODE == 1 ? resf.r[b] : accf.old[b];
-            const unsigned long long mbits = MODE == 1 ? 0ull : accf.bits[b];
+            const int m = blk.pixel(mtile, b);
+            const size_t poff = stream_out_off<MODE>(p, bn, ps, m);
 #pragma unroll
             for (int a0 = 0; a0 < NI; a0 += 2) {
-                uint2 ov2[2], ovs[2];
-                ov2[0] = uint2{other.q[a0 / 2].x, other.q[a0 / 2].y};
-                ov2[1] = uint2{other.q[a0 / 2].z, other.q[a0 / 2].w};
-                frag_pair_swap(ov2[0], ov2[1]);                   // back to the MFMA layout
+                uint2 ov2[2], ovs[2];      // the residual (MODE 1) or d(out) (MODE 2 / 3), back in the MFMA layout; what leaves
+                frag_pair_unpack(MODE == 1 ? resf.r[b].q[a0 / 2] : accf.old[b].q[a0 / 2], ov2[0], ov2[1]);
 #pragma unroll
                 for (int ai = 0; ai < 2; ++ai) {
                     const int a = a0 + ai;
-                    // z3 as the unfused path stores it
-                    const unsigned z01 = pack2bf(acc[a][b][0], acc[a][b][1]), z23 = pack2bf(acc[a][b][2], acc[a][b][3]);
-                    const float z[4] = {bf2f((unsigned short)(z01 & 0xffff)), bf2f((unsigned short)(z01 >> 16)),
-                                        bf2f((unsigned short)(z23 & 0xffff)), bf2f((unsigned short)(z23 >> 16))};
-                    const float o[4] = {bf2f((unsigned short)(ov2[ai].x & 0xffff)), bf2f((unsigned short)(ov2[ai].x >> 16)),
-                                        bf2f((unsigned short)(ov2[ai].y & 0xffff)), bf2f((unsigned short)(ov2[ai].y >> 16))};
-                    const float c0[4] = {k0[a].x, k0[a].y, k0[a].z, k0[a].w};
-                    const float c1[4] = {k1[a].x, k1[a].y, k1[a].z, k1[a].w};
-                    const float c2[4] = {k2[a].x, k2[a].y, k2[a].z, k2[a].w};
-                    float v[4];
+                    float z[4], o[4], v[4], c0[4], c1[4], c2[4];
+                    stream_round4(acc[a][b], z);
+                    stream_unpack4(ov2[ai], o);
+                    stream_coef4(k0[a], c0);
+                    stream_coef4(k1[a], c1);
+                    stream_coef4(k2[a], c2);
                     if (MODE == 1) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
@@ -401,33 +486,26 @@ __global__ __launch_bounds__(768) void conv1x1_bn_stream_kernel(const ConvParams
                             v[j] = v[j] > 0.f ? v[j] : 0.f;
                         }
                     } else {
-                        const unsigned bits = (unsigned)(mbits >> (a * 16 + 4 * fq));
+                        const unsigned bits = stream_mask4(accf.bits[b], a, fq);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const float g = ((bits >> j) & 1u) ? o[j] : 0.f;
+                            const float g = stream_masked_g(bits, j, o[j]);
                             if (MODE == 2) { st1[a][j] += g; st2[a][j] += g * z[j]; }
                             else v[j] = __builtin_fmaf(c0[j], g, __builtin_fmaf(c1[j], z[j], c2[j]));
                         }
                     }
-                    if (MODE != 2) ovs[ai] = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+                    if (MODE != 2) ovs[ai] = stream_pack4(v);
                 }
                 if (MODE == 2) continue;
-                frag_pair_swap(ovs[0], ovs[1]);
-                const uint4 ov = uint4{ovs[0].x, ovs[0].y, ovs[1].x, ovs[1].y};
-                const int chan = frag_pair_chan(a0, fq);
-                if (MODE == 1) {
-                    bf16_t* const dpix = p.y + ((size_t)(bi * p.yHp + yy + p.ypad) * p.yWp + (xx + p.ypad)) * p.yC + nw;
-                    vpd_store16<VPD_CP_EPI>(dpix + chan, ov);
-                    if (bn.mask_out) bn.mask_out[(size_t)m * (p.Co >> 3) + ((nw + chan) >> 3)] = (unsigned char)stream_relu_bits(ov);
-                } else {
-                    bf16_t* const dpix = bn.dz + ((size_t)(bi * bn.dzHp + yy + bn.dzpad) * bn.dzWp + (xx + bn.dzpad)) * p.Co + nw;
-                    vpd_store16<VPD_CP_EPI>(dpix + chan, ov);
-                }
+                const uint4 ov = frag_pair_pack(ovs[0], ovs[1]);
+                const int c = blk.nw + frag_pair_chan(a0, fq);
+                if (MODE == 1) stream_store_out(p, bn, poff, m, c, ov);
+                else vpd_store16<VPD_CP_EPI>(bn.s.dz + poff + c, ov);
             }
         }
     }
     __builtin_amdgcn_s_barrier();                                 // END
-    if (MODE == 2) stream_stats_flush<BN, WM, WN>(bn.rows_out, VPD_FUSED_ROWS, p.Co, n0, st1, st2, smem);
+    if (MODE == 2) stream_stats_flush(bn.s.rows_out, VPD_FUSED_ROWS, p.Co, blk, st1, st2);
 }
 
 // ---------------------------------------------------------------------------
@@ -439,72 +517,29 @@ __global__ __launch_bounds__(768) void conv1x1_bn_stream_kernel(const ConvParams
 //   MODE 3: dz3 = A3 g + B3 z3 + D3, dzd = Ad g + Bd zd + Dd -> two padded tensors; dgamma / dbeta of both
 // (the statistics passes are two launches of conv1x1_stream_kernel<.., 4>, one per convolution)
 // ---------------------------------------------------------------------------
-struct StreamBnB {                                          // the branch's BatchNorm (fields as in StreamBn)
-    const double* rows; const float* gamma; const float* beta;
-    float* mean; float* rstd; float* scale; float* shift; float* rm; float* rv;
-    double* rows_out; float* dgamma; float* dbeta; bf16_t* dz;
-};
-
 template <int NSA, int MODE>
-__global__ __launch_bounds__(768) void conv1x1_bn2_stream_kernel(const ConvParams p, const StreamGeo sg, const StreamBn bn,
-                                                                 const StreamBnB bb) {
-    constexpr int BM = 64, BN = 256, WM = 2, WN = 4, NMW = 8;
-    constexpr int WTM = BM / WM, WTN = BN / WN, MI = WTM / 16, NI = WTN / 16;
-    constexpr int WELEMS = 2 * BN * 64, ASTAGE = 2 * BM * 64;
-    static_assert((size_t)(WELEMS + NSA * ASTAGE) * 2 + 6 * BN * 4 <= 160 * 1024, "LDS");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16_t* const sW = reinterpret_cast<bf16_t*>(smem);
-    bf16_t* const ring = sW + WELEMS;
-    float* const coef = reinterpret_cast<float*>(ring + NSA * ASTAGE);      // [6][BN]
-    const ConvGeo geo = {p.Hs, p.Ws, p.M, p.oph, p.opw};
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n0 = blockIdx.y * BN;
-    const int lanes = gridDim.x;
-    const int first = blockIdx.x;
-    const int ntile = first < sg.mtiles ? (sg.mtiles - first + lanes - 1) / lanes : 0;
-    constexpr int PRE = (MODE == 1 || MODE == 3) ? 1 : 0;
-    if (wave >= NMW) {
-        stream_loader<128, BM, BN, NSA, PRE, true>(p, sg, sW, ring, n0, first, lanes, ntile, wave - NMW, lane);
-        __builtin_amdgcn_s_barrier();                             // END
-        if (MODE == 2) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }
+__global__ __launch_bounds__(TAIL_THREADS) void conv1x1_bn2_stream_kernel(const ConvParams p, const StreamGeo sg, const StreamBn bn,
+                                                                          const StreamBnSide bd) {      // bn.s: BatchNorm3, bd: the branch's
+    using B = StreamBlock<128, TAIL_BM, TAIL_BN, NSA, TAIL_NMW>;      // chunk 0: conv3, chunk 1: the branch
+    constexpr int BM = B::BM, BN = B::BN, WM = B::WM, WN = B::WN, MI = B::MI, NI = B::NI;
+    constexpr int PRE = MODE == 2 ? 0 : 1;
+    constexpr int NK = MODE == 1 ? 2 : 3;              // coefficient rows per BatchNorm: (scale, shift) or (A, B, D)
+    static_assert(stream_lds_bytes(128, BM, BN, NSA, 6) <= 160 * 1024, "LDS");
+    if (B::loader()) {
+        stream_loader<B, PRE, stream_tail_barriers(MODE == 2, 2), true>(p, sg, B(sg));
         return;
     }
-    const int wm = wave % WM;
-    const int wn = wave / WM;
-    const int fr = lane & 15;
-    const int fq = lane >> 4;
-    const int nw = n0 + wn * WTN;
-    if (MODE == 1 && tid < BN) {
-        const int ch = n0 + tid;
-        float mu, r, sc, sh; double var;
-        bn_finalize_channel(bn.rows, p.Co, ch, bn.count, bn.eps, bn.gamma[ch], bn.beta[ch], &mu, &r, &sc, &sh, &var);
-        coef[tid] = sc; coef[BN + tid] = sh;
-        if (blockIdx.x == 0) {
-            bn.mean[ch] = mu; bn.rstd[ch] = r; bn.scale[ch] = sc; bn.shift[ch] = sh;
-            if (bn.rm) {
-                const double unb = bn.count > 1.f ? var * (double)bn.count / ((double)bn.count - 1.0) : var;
-                bn.rm[ch] = (1.f - bn.momentum) * bn.rm[ch] + bn.momentum * mu;
-                bn.rv[ch] = (1.f - bn.momentum) * bn.rv[ch] + bn.momentum * (float)unb;
-            }
+    const B blk(sg);
+    const int fq = blk.fq;
+    if (PRE && blk.tid < BN) {
+        const int ch = blk.n0 + blk.tid;
+        if (MODE == 1) {
+            stream_bn_finalize(bn.s, bn, p.Co, ch, blk.coef + blk.tid, blk.coef + BN + blk.tid);
+            stream_bn_finalize(bd, bn, p.Co, ch, blk.coef + 2 * BN + blk.tid, blk.coef + 3 * BN + blk.tid);
+        } else {
+            stream_bn_bwd_coef<BN>(bn.s, bn, p.Co, ch, blk.coef, blk.tid);
+            stream_bn_bwd_coef<BN>(bd, bn, p.Co, ch, blk.coef + 3 * BN, blk.tid);
         }
-        bn_finalize_channel(bb.rows, p.Co, ch, bn.count, bn.eps, bb.gamma[ch], bb.beta[ch], &mu, &r, &sc, &sh, &var);
-        coef[2 * BN + tid] = sc; coef[3 * BN + tid] = sh;
-        if (blockIdx.x == 0) {
-            bb.mean[ch] = mu; bb.rstd[ch] = r; bb.scale[ch] = sc; bb.shift[ch] = sh;
-            if (bb.rm) {
-                const double unb = bn.count > 1.f ? var * (double)bn.count / ((double)bn.count - 1.0) : var;
-                bb.rm[ch] = (1.f - bn.momentum) * bb.rm[ch] + bn.momentum * mu;
-                bb.rv[ch] = (1.f - bn.momentum) * bb.rv[ch] + bn.momentum * (float)unb;
-            }
-        }
-    } else if (MODE == 3 && tid < BN) {
-        const int ch = n0 + tid;
-        bn_bwd_apply_coef(bn.rows, p.Co, ch, bn.count, bn.gamma[ch], bn.mean[ch], bn.rstd[ch], coef, coef + BN, coef + 2 * BN,
-                          bn.dgamma, bn.dbeta, blockIdx.x == 0, tid);
-        bn_bwd_apply_coef(bb.rows, p.Co, ch, bn.count, bb.gamma[ch], bb.mean[ch], bb.rstd[ch], coef + 3 * BN, coef + 4 * BN,
-                          coef + 5 * BN, bb.dgamma, bb.dbeta, blockIdx.x == 0, tid);
     }
     if (PRE) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -515,157 +550,90 @@ __global__ __launch_bounds__(768) void conv1x1_bn2_stream_kernel(const ConvParam
     for (int a = 0; a < NI; ++a)
 #pragma unroll
         for (int j = 0; j < 4; ++j) { st1[a][j] = 0.f; st2[a][j] = 0.f; st3[a][j] = 0.f; }
+    const ConvGeo geo = {p.Hs, p.Ws, p.M, p.oph, p.opw};
     const PixSplit ps = pix_split_init(p, geo);
-    auto rounded = [](const f32x4& v, float (&z)[4]) __attribute__((always_inline)) {      // as the unfused path stores it
-        const unsigned z01 = pack2bf(v[0], v[1]), z23 = pack2bf(v[2], v[3]);
-        z[0] = bf2f((unsigned short)(z01 & 0xffff)); z[1] = bf2f((unsigned short)(z01 >> 16));
-        z[2] = bf2f((unsigned short)(z23 & 0xffff)); z[3] = bf2f((unsigned short)(z23 >> 16));
-    };
-    auto cf = [&](int k, int a) __attribute__((always_inline)) {      // coefficient row k, this lane's four channels of group a
-        return *reinterpret_cast<const float4*>(coef + k * BN + wn * WTN + a * 16 + 4 * fq);
-    };
-    for (int it = 0; it < ntile; ++it) {
-        const int mtile = first + it * lanes;
+    for (int it = 0; it < blk.ntile; ++it) {
+        const int mtile = blk.mtile(it);
         AccFrag<NI, MI> accf;      // MODE 2 / 3: d(out) (dense) and its ReLU bits
-        if (MODE != 1) conv_acc_prefetch<BM, BN, WM, WN>(p, mtile, n0, geo, accf);
+        if (MODE != 1) conv_acc_prefetch<BM, BN, WM, WN>(p, mtile, blk.n0, geo, accf);
         f32x4 acc3[NI][MI], accd[NI][MI];
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-#pragma unroll
-            for (int b = 0; b < MI; ++b) { acc3[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; accd[a][b] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+        zero_acc(acc3);
+        zero_acc(accd);
         __builtin_amdgcn_s_barrier();                             // READY_it
-        const bf16_t* const stg = ring + (it % NSA) * ASTAGE;
+        const bf16_t* const stg = blk.stage(it);
         if (MODE == 2) {
             // one accumulator set at a time (three sum sets of 16 registers beside it): conv3's sums, then the branch's
-            auto sums = [&](f32x4 (&acc)[NI][MI], bool with_g, float (&sz)[NI][4]) __attribute__((always_inline)) {
-#pragma unroll
-                for (int b = 0; b < MI; ++b)
-#pragma unroll
-                    for (int a0 = 0; a0 < NI; a0 += 2) {
-                        uint2 dv[2];
-                        dv[0] = uint2{accf.old[b].q[a0 / 2].x, accf.old[b].q[a0 / 2].y};
-                        dv[1] = uint2{accf.old[b].q[a0 / 2].z, accf.old[b].q[a0 / 2].w};
-                        frag_pair_swap(dv[0], dv[1]);
-#pragma unroll
-                        for (int ai = 0; ai < 2; ++ai) {
-                            const int a = a0 + ai;
-                            float z[4];
-                            rounded(acc[a][b], z);
-                            const float d[4] = {bf2f((unsigned short)(dv[ai].x & 0xffff)), bf2f((unsigned short)(dv[ai].x >> 16)),
-                                                bf2f((unsigned short)(dv[ai].y & 0xffff)), bf2f((unsigned short)(dv[ai].y >> 16))};
-                            const unsigned bits = (unsigned)(accf.bits[b] >> (a * 16 + 4 * fq));
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                const float g = ((bits >> j) & 1u) ? d[j] : 0.f;
-                                if (with_g) st1[a][j] += g;
-                                sz[a][j] += g * z[j];
-                            }
-                        }
-                    }
-            };
-            stream_mma<64, BM, BN, WM, WN>(sW, stg, acc3, wm, wn, fr, fq);
-            sums(acc3, true, st2);
-#pragma unroll
-            for (int a = 0; a < NI; ++a)
-#pragma unroll
-                for (int b = 0; b < MI; ++b) acc3[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-            stream_mma<64, BM, BN, WM, WN>(sW + BN * 64, stg + BM * 64, acc3, wm, wn, fr, fq);
-            sums(acc3, false, st3);
+            stream_mma<64, BM, BN, WM, WN>(blk.sW, stg, acc3, blk.wm, blk.wn, blk.fr, fq);
+            stream_bwd_sums<true>(acc3, accf, fq, st1, st2);
+            zero_acc(acc3);
+            stream_mma<64, BM, BN, WM, WN>(blk.sW + BN * 64, stg + BM * 64, acc3, blk.wm, blk.wn, blk.fr, fq);
+            stream_bwd_sums<false>(acc3, accf, fq, st1, st3);
             continue;
         }
-        stream_mma<64, BM, BN, WM, WN>(sW, stg, acc3, wm, wn, fr, fq);
-        stream_mma<64, BM, BN, WM, WN>(sW + BN * 64, stg + BM * 64, accd, wm, wn, fr, fq);
+        stream_mma<64, BM, BN, WM, WN>(blk.sW, stg, acc3, blk.wm, blk.wn, blk.fr, fq);
+        stream_mma<64, BM, BN, WM, WN>(blk.sW + BN * 64, stg + BM * 64, accd, blk.wm, blk.wn, blk.fr, fq);
         size_t poff[MI];           // this lane's pixels in the padded outputs (out, or dz3 / dzd: same geometry)
 #pragma unroll
-        for (int b = 0; b < MI; ++b) {
-            const int m = mtile * BM + wm * WTM + b * 16 + fr;
-            int bi, yy, xx;
-            pix_split(ps, m, bi, yy, xx);
-            if (MODE == 1) poff[b] = ((size_t)(bi * p.yHp + yy + p.ypad) * p.yWp + (xx + p.ypad)) * p.yC + nw;
-            else poff[b] = ((size_t)(bi * bn.dzHp + yy + bn.dzpad) * bn.dzWp + (xx + bn.dzpad)) * p.Co + nw;
-        }
+        for (int b = 0; b < MI; ++b) poff[b] = stream_out_off<MODE>(p, bn, ps, blk.pixel(mtile, b));
 #pragma unroll
         for (int a0 = 0; a0 < NI; a0 += 2) {
-            float4 k[2][6];
-            if (MODE == 1) {
+            // the pair's coefficient rows, BatchNorm3's NK then the branch's NK: MODE 1 (scale3, shift3, scaleD, shiftD),
+            // MODE 3 (A3, B3, D3, Ad, Bd, Dd) -- so a side's first two rows are [0], [1] / [NK], [NK + 1] and D is its last
+            float4 kq[2][2 * NK];
 #pragma unroll
-                for (int ai = 0; ai < 2; ++ai)
+            for (int ai = 0; ai < 2; ++ai)
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) k[ai][q] = cf(q, a0 + ai);
-            } else if (MODE == 3) {
-#pragma unroll
-                for (int ai = 0; ai < 2; ++ai)
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) k[ai][q] = cf(q, a0 + ai);
-            }
+                for (int q = 0; q < 2 * NK; ++q) kq[ai][q] = blk.coef4(q, a0 + ai);
+            const int c = blk.nw + frag_pair_chan(a0, fq);
 #pragma unroll
             for (int b = 0; b < MI; ++b) {
-                const int m = mtile * BM + wm * WTM + b * 16 + fr;
                 uint2 dv[2], o3[2], od[2];
-                if (MODE != 1) {
-                    dv[0] = uint2{accf.old[b].q[a0 / 2].x, accf.old[b].q[a0 / 2].y};
-                    dv[1] = uint2{accf.old[b].q[a0 / 2].z, accf.old[b].q[a0 / 2].w};
-                    frag_pair_swap(dv[0], dv[1]);
-                }
+                if (MODE == 3) frag_pair_unpack(accf.old[b].q[a0 / 2], dv[0], dv[1]);
 #pragma unroll
                 for (int ai = 0; ai < 2; ++ai) {
                     const int a = a0 + ai;
-                    float z3[4], zd[4], v[4], w[4];
-                    rounded(acc3[a][b], z3);
-                    rounded(accd[a][b], zd);
+                    float z3[4], zd[4], v[4], w[4], k[2 * NK][4];
+#pragma unroll
+                    for (int q = 0; q < 2 * NK; ++q) stream_coef4(kq[ai][q], k[q]);
+                    stream_round4(acc3[a][b], z3);
+                    stream_round4(accd[a][b], zd);
                     if (MODE == 1) {
-                        const float s3[4] = {k[ai][0].x, k[ai][0].y, k[ai][0].z, k[ai][0].w}, h3[4] = {k[ai][1].x, k[ai][1].y, k[ai][1].z, k[ai][1].w};
-                        const float sd[4] = {k[ai][2].x, k[ai][2].y, k[ai][2].z, k[ai][2].w}, hd[4] = {k[ai][3].x, k[ai][3].y, k[ai][3].z, k[ai][3].w};
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            v[j] = __builtin_fmaf(z3[j], s3[j], h3[j]) + __builtin_fmaf(zd[j], sd[j], hd[j]);
+                            v[j] = __builtin_fmaf(z3[j], k[0][j], k[1][j]) + __builtin_fmaf(zd[j], k[NK][j], k[NK + 1][j]);
                             v[j] = v[j] > 0.f ? v[j] : 0.f;
                         }
-                        o3[ai] = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
                     } else {
-                        const float d[4] = {bf2f((unsigned short)(dv[ai].x & 0xffff)), bf2f((unsigned short)(dv[ai].x >> 16)),
-                                            bf2f((unsigned short)(dv[ai].y & 0xffff)), bf2f((unsigned short)(dv[ai].y >> 16))};
-                        const unsigned bits = (unsigned)(accf.bits[b] >> (a * 16 + 4 * fq));
-                        const float A3[4] = {k[ai][0].x, k[ai][0].y, k[ai][0].z, k[ai][0].w}, B3[4] = {k[ai][1].x, k[ai][1].y, k[ai][1].z, k[ai][1].w};
-                        const float D3[4] = {k[ai][2].x, k[ai][2].y, k[ai][2].z, k[ai][2].w}, Ad[4] = {k[ai][3].x, k[ai][3].y, k[ai][3].z, k[ai][3].w};
-                        const float Bd[4] = {k[ai][4].x, k[ai][4].y, k[ai][4].z, k[ai][4].w}, Dd[4] = {k[ai][5].x, k[ai][5].y, k[ai][5].z, k[ai][5].w};
+                        float d[4];
+                        stream_unpack4(dv[ai], d);
+                        const unsigned bits = stream_mask4(accf.bits[b], a, fq);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const float g = ((bits >> j) & 1u) ? d[j] : 0.f;
-                            v[j] = __builtin_fmaf(A3[j], g, __builtin_fmaf(B3[j], z3[j], D3[j]));
-                            w[j] = __builtin_fmaf(Ad[j], g, __builtin_fmaf(Bd[j], zd[j], Dd[j]));
+                            const float g = stream_masked_g(bits, j, d[j]);
+                            v[j] = __builtin_fmaf(k[0][j], g, __builtin_fmaf(k[1][j], z3[j], k[NK - 1][j]));
+                            w[j] = __builtin_fmaf(k[NK][j], g, __builtin_fmaf(k[NK + 1][j], zd[j], k[2 * NK - 1][j]));
                         }
-                        o3[ai] = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
-                        od[ai] = uint2{pack2bf(w[0], w[1]), pack2bf(w[2], w[3])};
+                        od[ai] = stream_pack4(w);
                     }
+                    o3[ai] = stream_pack4(v);
                 }
-                const int chan = frag_pair_chan(a0, fq);
-                frag_pair_swap(o3[0], o3[1]);
-                const uint4 ov = uint4{o3[0].x, o3[0].y, o3[1].x, o3[1].y};
+                const uint4 ov = frag_pair_pack(o3[0], o3[1]);
                 if (MODE == 1) {
-                    vpd_store16<VPD_CP_EPI>(p.y + poff[b] + chan, ov);
-                    if (bn.mask_out) bn.mask_out[(size_t)m * (p.Co >> 3) + ((nw + chan) >> 3)] = (unsigned char)stream_relu_bits(ov);
+                    stream_store_out(p, bn, poff[b], blk.pixel(mtile, b), c, ov);
                 } else {
-                    vpd_store16<VPD_CP_EPI>(bn.dz + poff[b] + chan, ov);
-                    frag_pair_swap(od[0], od[1]);
-                    vpd_store16<VPD_CP_EPI>(bb.dz + poff[b] + chan, uint4{od[0].x, od[0].y, od[1].x, od[1].y});
+                    vpd_store16<VPD_CP_EPI>(bn.s.dz + poff[b] + c, ov);
+                    vpd_store16<VPD_CP_EPI>(bd.dz + poff[b] + c, frag_pair_pack(od[0], od[1]));
                 }
             }
         }
     }
     __builtin_amdgcn_s_barrier();                                 // END
-    if (MODE == 2) {
-        stream_stats_flush<BN, WM, WN>(bn.rows_out, VPD_FUSED_ROWS, p.Co, n0, st1, st2, smem);
-        __syncthreads();
-        stream_stats_flush<BN, WM, WN>(bb.rows_out, VPD_FUSED_ROWS, p.Co, n0, st1, st3, smem);
-    }
+    if (MODE == 2) stream_stats_flush2(bn.s.rows_out, bd.rows_out, VPD_FUSED_ROWS, p.Co, blk, st1, st2, st3);
 }
-
-int stream_cu_count() { return vpd_cu_budget(); }
 
 // pixel lanes (gridDim.x) of a launch with NT channel tiles on `mtiles` pixel tiles
 int stream_lanes(int mtiles, int NT) {
-    int lanes = stream_cu_count() / NT;
+    int lanes = vpd_cu_budget() / NT;
     lanes -= lanes % 8;                      // blocks b and b + 8 share an XCD: the NT channel tiles of a pixel tile meet in its L2
     if (lanes < 8) lanes = 8;
     if (lanes > mtiles) lanes = mtiles;
@@ -684,15 +652,20 @@ void stream_shape(int Kc, int Co, int* bm, int* bn) {
     *bm = n == 256 ? 64 : (Kc == 256 ? (n == 64 ? 64 : 32) : 128);
 }
 
-template <int KC, int BM, int BN, int NSA>
-hipError_t launch_stream(const ConvParams& p, hipStream_t stream) {
+StreamGeo stream_geo(const ConvParams& p, int BM) {
     StreamGeo sg;
     sg.mtiles = p.M / BM;
     sg.tiles_per_img = (p.Hs * p.Ws) / BM;
     sg.rows_per_tile = BM / p.Ws;
+    return sg;
+}
+
+template <int KC, int BM, int BN, int NSA>
+hipError_t launch_stream(const ConvParams& p, hipStream_t stream) {
+    const StreamGeo sg = stream_geo(p, BM);
     const int NT = p.Co / BN;
     const dim3 grid(stream_lanes(sg.mtiles, NT), NT);
-    const size_t lds = (size_t)(KC / 64) * 64 * (BN + NSA * BM) * sizeof(bf16_t);
+    constexpr size_t lds = stream_lds_bytes(KC, BM, BN, NSA);
     switch (conv_ep_mode(p)) {
         case 0: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 0>), grid, dim3(512), lds, stream, p, sg); break;
         case 1: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 1>), grid, dim3(512), lds, stream, p, sg); break;
@@ -717,7 +690,7 @@ bool vpd_conv1x1_stream_eligible(const ConvParams& p) {
     stream_shape(p.Kc, p.Co, &bm, &bn);
     if (p.Co % bn != 0) return false;
     if (p.Ws <= 0 || bm % p.Ws != 0 || (p.Hs * p.Ws) % bm != 0) return false;
-    if (p.M != p.N * p.Hs * p.Ws || p.M / bm < 2 * stream_cu_count()) return false;
+    if (p.M != p.N * p.Hs * p.Ws || p.M / bm < 2 * vpd_cu_budget()) return false;
     if (p.M >= VPD_FDIV_MAX) return false;
     return (long)p.N * p.xHp * p.xWp * p.xC < (1l << 31) && (long)p.Co * p.Kc * (p.taps.w0 + 1) < (1l << 31);
 }
@@ -751,28 +724,55 @@ void vpd_conv1x1_stream_grid(const ConvParams& p, int* bm, int* bn, int* lanes) 
 // ---- the closing 1x1 convolution of a Bottleneck with its BatchNorm (conv1x1_bn_stream_kernel) ----
 bool vpd_conv1x1_bn_eligible(const ConvParams& p) {
     if (!vpd_switches().bneck_recompute || !vpd_conv1x1_stream_eligible(p)) return false;
-    if (p.istr != 1 || (p.Kc != 64 && p.Kc != 128) || p.Co % 256 != 0 || p.accumulate || p.ep_scale) return false;
-    return p.M % 64 == 0 && 64 % p.Ws == 0 && (p.Hs * p.Ws) % 64 == 0;
+    if (p.istr != 1 || (p.Kc != 64 && p.Kc != 128) || p.Co % TAIL_BN != 0 || p.accumulate || p.ep_scale) return false;
+    return p.M % TAIL_BM == 0 && TAIL_BM % p.Ws == 0 && (p.Hs * p.Ws) % TAIL_BM == 0;
 }
 
 namespace {
+// what the BatchNorms of a launch share; mode 3 writes every dz padded by dzpad
+StreamBn stream_bn(float count, float momentum, float eps, unsigned char* mask_out, const ConvParams& p, int dzpad) {
+    StreamBn bn;
+    memset(&bn, 0, sizeof bn);
+    bn.count = count; bn.momentum = momentum; bn.eps = eps; bn.mask_out = mask_out;
+    bn.dzHp = p.Hs + 2 * dzpad; bn.dzWp = p.Ws + 2 * dzpad; bn.dzpad = dzpad;
+    return bn;
+}
+// mode 1: one BatchNorm of a BnFusedFwd (its first or its second field set)
+StreamBnSide stream_side_fwd(const double* rows, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
+                             float* shift, float* rm, float* rv) {
+    StreamBnSide s;
+    memset(&s, 0, sizeof s);
+    s.rows = rows; s.gamma = gamma; s.beta = beta; s.mean = mean; s.rstd = rstd; s.scale = scale; s.shift = shift; s.rm = rm; s.rv = rv;
+    return s;
+}
+// mode 2: the rows to add to; mode 3: the same rows to finalize, with the forward's mean / rstd and the dz to write
+StreamBnSide stream_side_bwd(const BnFusedBwd& b, const float* mean, const float* rstd, bf16_t* dz, int mode) {
+    StreamBnSide s;
+    memset(&s, 0, sizeof s);
+    if (mode == 2) { s.rows_out = b.rows; return s; }
+    s.rows = b.rows; s.gamma = b.gamma; s.dgamma = b.dgamma; s.dbeta = b.dbeta;
+    s.mean = const_cast<float*>(mean); s.rstd = const_cast<float*>(rstd); s.dz = dz;
+    return s;
+}
+// modes 2 and 3 read p.y = d(out), dense, with its bit map
+bool stream_bwd_operands(const ConvParams& p) {
+    return p.y && p.acc_mask && p.ypad == 0 && p.yC == p.Co && p.yHp == p.Hs && p.yWp == p.Ws;
+}
+
 template <int KC, int NSA>
 hipError_t launch_bn_stream(const ConvParams& p, const StreamBn& bn, int mode, hipStream_t stream) {
-    constexpr int BM = 64, BN = 256;
-    StreamGeo sg;
-    sg.mtiles = p.M / BM;
-    sg.tiles_per_img = (p.Hs * p.Ws) / BM;
-    sg.rows_per_tile = BM / p.Ws;
+    constexpr int BM = TAIL_BM, BN = TAIL_BN;
+    const StreamGeo sg = stream_geo(p, BM);
     const int NT = p.Co / BN;
-    const dim3 grid(stream_lanes(sg.mtiles, NT), NT);
-    const size_t lds = (size_t)(KC / 64) * 64 * (BN + NSA * BM) * sizeof(bf16_t) + 3 * BN * sizeof(float);
+    const dim3 grid(stream_lanes(sg.mtiles, NT), NT), block(TAIL_THREADS);
+    constexpr size_t lds = stream_lds_bytes(KC, BM, BN, NSA, 3);
     switch (mode) {
         // (four MFMA waves as the storing launch: the same pixels per lane, so the same fp32 partial sums -- the fused forward is
         //  bit-identical to conv + BatchNorm launches; eight waves were no faster here, 16.4-18.2 vs 17.8-19.4 us)
         case 0: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 4>), grid, dim3(512), lds, stream, p, sg); break;
-        case 1: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 1>), grid, dim3(768), lds, stream, p, sg, bn); break;
-        case 2: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 2>), grid, dim3(768), lds, stream, p, sg, bn); break;
-        case 3: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 3>), grid, dim3(768), lds, stream, p, sg, bn); break;
+        case 1: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 1>), grid, block, lds, stream, p, sg, bn); break;
+        case 2: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 2>), grid, block, lds, stream, p, sg, bn); break;
+        case 3: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 3>), grid, block, lds, stream, p, sg, bn); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -786,25 +786,18 @@ hipError_t launch_bn_stream(const ConvParams& p, const StreamBn& bn, int mode, h
 hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd, const float* mean,
                                  const float* rstd, unsigned char* mask_out, bf16_t* dz, int dzpad, int mode, hipStream_t stream) {
     if (!vpd_conv1x1_bn_eligible(p)) return hipErrorInvalidValue;
-    StreamBn bn;
-    memset(&bn, 0, sizeof bn);
+    StreamBn bn = stream_bn(0.f, 0.f, 0.f, nullptr, p, 0);
     if (mode == 0) {
         if (!p.stats || p.stat_rows != VPD_FUSED_ROWS) return hipErrorInvalidValue;
     } else if (mode == 1) {
         if (!fwd || !p.res || !p.y || p.ypad != 1 || p.yC != p.Co || p.rC != p.Co) return hipErrorInvalidValue;
-        bn.rows = fwd->rows; bn.count = fwd->count; bn.gamma = fwd->gamma; bn.beta = fwd->beta;
-        bn.mean = fwd->mean; bn.rstd = fwd->rstd; bn.scale = fwd->scale; bn.shift = fwd->shift;
-        bn.rm = fwd->rm; bn.rv = fwd->rv; bn.momentum = fwd->momentum; bn.eps = fwd->eps;
-        bn.mask_out = mask_out;
+        bn = stream_bn(fwd->count, fwd->momentum, fwd->eps, mask_out, p, 0);
+        bn.s = stream_side_fwd(fwd->rows, fwd->gamma, fwd->beta, fwd->mean, fwd->rstd, fwd->scale, fwd->shift, fwd->rm, fwd->rv);
     } else {
-        if (!bwd || !p.y || !p.acc_mask || p.ypad != 0 || p.yC != p.Co || p.yHp != p.Hs || p.yWp != p.Ws) return hipErrorInvalidValue;
-        if (mode == 2) bn.rows_out = bwd->rows;
-        else {
-            if (!dz || !mean || !rstd) return hipErrorInvalidValue;
-            bn.rows = bwd->rows; bn.count = bwd->count; bn.gamma = bwd->gamma; bn.dgamma = bwd->dgamma; bn.dbeta = bwd->dbeta;
-            bn.mean = const_cast<float*>(mean); bn.rstd = const_cast<float*>(rstd);
-            bn.dz = dz; bn.dzHp = p.Hs + 2 * dzpad; bn.dzWp = p.Ws + 2 * dzpad; bn.dzpad = dzpad;
-        }
+        if (!bwd || !stream_bwd_operands(p)) return hipErrorInvalidValue;
+        if (mode == 3 && (!dz || !mean || !rstd)) return hipErrorInvalidValue;
+        bn = stream_bn(bwd->count, 0.f, 0.f, nullptr, p, dzpad);
+        bn.s = stream_side_bwd(*bwd, mean, rstd, dz, mode);
     }
     if (p.Kc == 64) return launch_bn_stream<64, BN_NSA_K64>(p, bn, mode, stream);
     return launch_bn_stream<128, BN_NSA_K128>(p, bn, mode, stream);
@@ -814,7 +807,7 @@ hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, con
 // the closing convolution, p.x2 / p.w2 = the branch (same padded input geometry).  fwd: rows / ... = BatchNorm3, rows2 / ... = the
 // branch's; bwd3 / bwdD likewise.  Modes 1..3 as vpd_launch_conv1x1_bn (the statistics passes are two mode-0 launches of that).
 bool vpd_conv1x1_bn2_eligible(const ConvParams& p) {
-    if (!(p.x2 && p.w2 && p.Kc == 64 && p.Kc2 == 64 && p.Co == 256)) return false;
+    if (!(p.x2 && p.w2 && p.Kc == 64 && p.Kc2 == 64 && p.Co == TAIL_BN)) return false;
     ConvParams q = p;
     q.x2 = nullptr; q.w2 = nullptr; q.Kc2 = 0;
     return vpd_conv1x1_bn_eligible(q);
@@ -824,40 +817,27 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
                                   unsigned char* mask_out, bf16_t* dz3, bf16_t* dzD, int dzpad, int mode, hipStream_t stream) {
     if (!vpd_conv1x1_bn2_eligible(p)) return hipErrorInvalidValue;
     StreamBn bn;
-    StreamBnB bb;
-    memset(&bn, 0, sizeof bn);
-    memset(&bb, 0, sizeof bb);
+    StreamBnSide bd;
     if (mode == 1) {
         if (!fwd || !fwd->rows2 || !p.y || p.ypad != 1 || p.yC != p.Co) return hipErrorInvalidValue;
-        bn.rows = fwd->rows; bn.count = fwd->count; bn.gamma = fwd->gamma; bn.beta = fwd->beta;
-        bn.mean = fwd->mean; bn.rstd = fwd->rstd; bn.scale = fwd->scale; bn.shift = fwd->shift;
-        bn.rm = fwd->rm; bn.rv = fwd->rv; bn.momentum = fwd->momentum; bn.eps = fwd->eps; bn.mask_out = mask_out;
-        bb.rows = fwd->rows2; bb.gamma = fwd->gamma2; bb.beta = fwd->beta2;
-        bb.mean = fwd->mean2; bb.rstd = fwd->rstd2; bb.scale = fwd->scale2; bb.shift = fwd->shift2; bb.rm = fwd->rm2; bb.rv = fwd->rv2;
+        bn = stream_bn(fwd->count, fwd->momentum, fwd->eps, mask_out, p, 0);
+        bn.s = stream_side_fwd(fwd->rows, fwd->gamma, fwd->beta, fwd->mean, fwd->rstd, fwd->scale, fwd->shift, fwd->rm, fwd->rv);
+        bd = stream_side_fwd(fwd->rows2, fwd->gamma2, fwd->beta2, fwd->mean2, fwd->rstd2, fwd->scale2, fwd->shift2, fwd->rm2, fwd->rv2);
     } else if (mode == 2 || mode == 3) {
-        if (!bwd3 || !bwdD || !p.y || !p.acc_mask || p.ypad != 0 || p.yC != p.Co || p.yHp != p.Hs || p.yWp != p.Ws) return hipErrorInvalidValue;
-        bn.count = bwd3->count;
-        if (mode == 2) { bn.rows_out = bwd3->rows; bb.rows_out = bwdD->rows; }
-        else {
-            if (!dz3 || !dzD || !mean3 || !rstd3 || !meanD || !rstdD) return hipErrorInvalidValue;
-            bn.rows = bwd3->rows; bn.gamma = bwd3->gamma; bn.dgamma = bwd3->dgamma; bn.dbeta = bwd3->dbeta;
-            bn.mean = const_cast<float*>(mean3); bn.rstd = const_cast<float*>(rstd3);
-            bn.dz = dz3; bn.dzHp = p.Hs + 2 * dzpad; bn.dzWp = p.Ws + 2 * dzpad; bn.dzpad = dzpad;
-            bb.rows = bwdD->rows; bb.gamma = bwdD->gamma; bb.dgamma = bwdD->dgamma; bb.dbeta = bwdD->dbeta;
-            bb.mean = const_cast<float*>(meanD); bb.rstd = const_cast<float*>(rstdD); bb.dz = dzD;
-        }
+        if (!bwd3 || !bwdD || !stream_bwd_operands(p)) return hipErrorInvalidValue;
+        if (mode == 3 && (!dz3 || !dzD || !mean3 || !rstd3 || !meanD || !rstdD)) return hipErrorInvalidValue;
+        bn = stream_bn(bwd3->count, 0.f, 0.f, nullptr, p, dzpad);
+        bn.s = stream_side_bwd(*bwd3, mean3, rstd3, dz3, mode);
+        bd = stream_side_bwd(*bwdD, meanD, rstdD, dzD, mode);
     } else return hipErrorInvalidValue;
-    constexpr int BM = 64, BN = 256, NSA = BN2_NSA;
-    StreamGeo sg;
-    sg.mtiles = p.M / BM;
-    sg.tiles_per_img = (p.Hs * p.Ws) / BM;
-    sg.rows_per_tile = BM / p.Ws;
-    const dim3 grid(stream_lanes(sg.mtiles, 1), 1);
-    const size_t lds = (size_t)2 * 64 * (BN + NSA * BM) * sizeof(bf16_t) + 6 * BN * sizeof(float);
+    constexpr int BM = TAIL_BM, BN = TAIL_BN, NSA = BN2_NSA;
+    const StreamGeo sg = stream_geo(p, BM);
+    const dim3 grid(stream_lanes(sg.mtiles, 1), 1), block(TAIL_THREADS);
+    constexpr size_t lds = stream_lds_bytes(128, BM, BN, NSA, 6);
     switch (mode) {
-        case 1: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 1>), grid, dim3(768), lds, stream, p, sg, bn, bb); break;
-        case 2: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 2>), grid, dim3(768), lds, stream, p, sg, bn, bb); break;
-        default: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 3>), grid, dim3(768), lds, stream, p, sg, bn, bb); break;
+        case 1: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 1>), grid, block, lds, stream, p, sg, bn, bd); break;
+        case 2: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 2>), grid, block, lds, stream, p, sg, bn, bd); break;
+        default: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 3>), grid, block, lds, stream, p, sg, bn, bd); break;
     }
     return hipGetLastError();
 }
@@ -865,8 +845,8 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
 // host-side reporting (vpd_op_conv1x1_bn_dispatch): the grid of the launches above for an eligible `p` -- pixel lanes, channel
 // tiles, pixel tiles of the busiest block, ring depth
 void vpd_conv1x1_bn_grid(const ConvParams& p, bool two, int out4[4]) {
-    const int mtiles = p.M / 64;
-    const int NT = two ? 1 : p.Co / 256;
+    const int mtiles = p.M / TAIL_BM;
+    const int NT = two ? 1 : p.Co / TAIL_BN;
     const int lanes = stream_lanes(mtiles, NT);
     out4[0] = lanes; out4[1] = NT; out4[2] = (mtiles + lanes - 1) / lanes;
     out4[3] = two ? BN2_NSA : p.Kc == 64 ? BN_NSA_K64 : BN_NSA_K128;
