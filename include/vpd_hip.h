@@ -461,6 +461,34 @@ int vpd_op_wgrad128_group(int nprob, const void* const* dz, const void* const* x
 int vpd_op_wgrad128_schedule(int n, const int* dims4, int G, int* ksplit, int* blk_begin, int* tasks, int cap,
                              double* est_us);
 
+/* ---- the reference boundary one launch at a time (test-only additions under ABI 5; tests/test_boundary_ops_gpu.py).  Element
+ * pointers are void* of the build's element type.  Every call returns non-zero with a vpd_last_error message on null or malformed
+ * arguments, before anything is launched.  The three that need descriptors build them, and their block maps, with the code
+ * vpd_plan_create uses, upload them for the launch and synchronise the stream before they return. ---- */
+/* x: f32 [n][c][H][W] (c in 1..8, 4-byte aligned) -> out: elements [n][Hp][Wp][8], 16-byte aligned; pixel (y, x) goes to
+ * (y + pad, x + pad), channels c..7 of it are zeroed, nothing else is written (Hp >= H + pad, Wp >= W + pad). */
+int vpd_op_pack_input(const float* x_f32_nchw, int n, int c, int H, int W, void* out, int Hp, int Wp, int pad, void* stream);
+/* master: f32 OIHW [Co][Ci][k][k] -> fwd_out: elements [tap][Co][Ci], dgr_out (or null): elements [tap][Ci][Co]; Co, Ci multiples
+ * of 32, k in 1..3.  stem = 1 (k = 7, Ci in 1..8, dgr_out null): fwd_out is [r][Co][64], entry t * 8 + c, zero for t = 7 or c >= Ci. */
+int vpd_op_pack_weights(const float* master, int Co, int Ci, int k, int stem, void* fwd_out, void* dgr_out, void* stream);
+/* wg: f32 weight-gradient scratch [tap][Co][Kc] (the stem: [r][Co][Kc], entry t * 8 + c) -> grads_out: f32 OIHW [Co][Ci][k][k]. */
+int vpd_op_unpack_grads(const float* wg, int Co, int Ci, int k, int Kc, int stem, float* grads_out, void* stream);
+/* The fused AdamW + repack launch of vpd_plan_adamw_step (and nothing else: no stem repack) over a synthetic flat buffer of `numel`
+ * floats (a multiple of 4): conv i has dims3[3i .. 3i+2] = {Co, Ci, k} and lies at offsets[i] (a multiple of 4 floats, ascending,
+ * no overlap); whatever lies in front of, between and behind the convs is updated as plain ranges.  params, grads, adam_m, adam_v:
+ * 16-byte aligned f32 [numel].  arena: elements, conv i's forward layout at 2 (n_0 + .. + n_{i-1}), n_i = Co Ci k k, its
+ * data-gradient layout n_i behind it.  wg (or null): f32 scratch, conv i's [tap][Co][Ci] gradient at n_0 + .. + n_{i-1}; with it
+ * the convs' gradients are read there and `grads` only over the plain ranges.  gscale multiplies every gradient read. */
+int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* offsets, long long numel, float* params, const float* grads,
+                      float* adam_m, float* adam_v, void* arena, const float* wg, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, int step, float gscale, void* stream);
+/* The weight gradients' slab sums, nprob (1..18) problems in one launch: dws[i][e] = sum over s < ksplits[i] of
+ * slabs[i][s * nfloats[i] + e]; nfloats[i] a multiple of 4, pointers 16-byte aligned. */
+int vpd_op_wgrad_reduce(int nprob, const float* const* slabs, float* const* dws, const long long* nfloats, const int* ksplits,
+                        void* stream);
+/* Zeroes count (0..16; 0: no launch) ranges of n4s[i] float4 at the 16-byte aligned ptrs[i] in one launch. */
+int vpd_op_zero_ranges(float* const* ptrs, const long long* n4s, int count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

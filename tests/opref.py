@@ -1,5 +1,6 @@
 """Plain float64 PyTorch references, input generators and derived error bounds shared by the operator parity tests
-(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py, test_conv_ops_gpu.py, test_bneck_tail_ops_gpu.py).  Nothing here touches the GPU or the library:
+(test_stem_ops_gpu.py, test_bn_backward_ops_gpu.py, test_head_ops_gpu.py, test_conv_ops_gpu.py, test_bneck_tail_ops_gpu.py,
+test_boundary_ops_gpu.py).  Nothing here touches the GPU or the library:
 tests/test_opref_cpu.py pins what these references rest on, so that a failure on the GPU points at the kernel."""
 import math
 
@@ -689,3 +690,229 @@ def tail_alter_mask(mask, tile=1):
     flat[tile * TAIL_TILE:(tile + 1) * TAIL_TILE] = torch.roll(flat[tile * TAIL_TILE:(tile + 1) * TAIL_TILE], -4, dims=1)
     return nchw(flat.view(n, h, w, c))
 # (v) the residual / d(out) one pixel to the right: conv_alter_shift
+
+
+# ---------------------------------------------------------------------------
+# the reference boundary (tests/test_boundary_ops_gpu.py): input packing, weight repack, gradient unpack, AdamW, slab sums, range zeroing
+# ---------------------------------------------------------------------------
+# sentinel bit patterns no operation here can produce: a NaN with a payload (element buffers; no input is a NaN) and an odd float
+SENTINEL_BITS = {"bf16": 0x7FA5, "fp16": 0x7E55}
+SENTINEL_F32 = 12345.678
+
+
+def sentinel_elems(shape, name):
+    return torch.full(shape if isinstance(shape, tuple) else (shape,), SENTINEL_BITS[name], dtype=torch.int16).view(ELEM[name][0])
+
+
+def bits(t):
+    """the bit pattern of an element-type or fp32 tensor as integers"""
+    return t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+#                   n  H  W   -> which kernel vpd_launch_pack_input takes (16-byte aligned x)
+PACK_INPUT_ROWS = ((3, 4, 64), (2, 8, 128))            # W % 64 == 0 and H W % 256 == 0, C in 3, 5, 6: pack_input_rows_kernel
+PACK_INPUT_ROWS_FALLBACK = ((2, 6, 64),)               # W % 64 == 0 but H W % 256 != 0: pack_input_kernel
+PACK_INPUT_QUAD = ((3, 5, 12), (2, 7, 20))             # W % 4 == 0: pack_input_kernel<3|5|6>, <0> for C 1, 4, 8
+PACK_INPUT_PIXEL = ((2, 5, 31), (1, 3, 33))            # W % 4 != 0: pack_input_px_kernel
+PACK_INPUT_MISALIGNED = ((2, 4, 16),)                  # ... and any W behind an x that is not 16-byte aligned
+# the quad kernel's items are n H W / 4: below 2^21 the float-reciprocal split (vpd_fdiv), from 2^21 on 64-bit divisions
+PACK_INPUT_BELOW = (8097, 37, 28)                      # 2,097,123 items, W / 4 = 7
+PACK_INPUT_WORKLOAD = (512, 128, 128)                  # 2^21 pixel quads: the rows kernel at the workload's size
+PACK_INPUT_ABOVE = (2400, 30, 120)                     # 2,160,000 items, W % 64 != 0: the quad kernel's 64-bit path
+FDIV_MAX = 1 << 21
+
+
+def pack_input_geoms(H, W):
+    """(Hp, Wp, pad): the plan's input geometry and a symmetric one"""
+    return ((H + 6, W + 8, 3), (H + 2, W + 2, 1))
+
+
+def pack_input_values(shape, name, g):
+    """randn mixed with what a conversion gets wrong: exact ties of the element type (half-way between two neighbours: round to
+    even), +-0, element-type subnormals and their ties, values around and beyond the fp16 maximum (65504; 65520 is the tie that
+    rounds to inf), fp32's largest.  Large tensors draw from a pool of 2^20 such values."""
+    n = 1
+    for s in shape:
+        n *= s
+    m = min(n, 1 << 20)
+    x = torch.randn(m, generator=g)
+    kind = torch.randint(0, 16, (m,), generator=g)
+    base = elem_round(x, name).double()
+    tie = (base + 0.5 * ulp(base, name)).float()                    # p + 1 significand bits: exact in fp32
+    x = torch.where(kind == 0, tie, x)
+    x = torch.where(kind == 1, torch.zeros(m), x)
+    x = torch.where(kind == 2, -torch.zeros(m), x)
+    tiny = 2.0 ** ELEM[name][2]
+    k = torch.randint(-15, 16, (m,), generator=g).double() * 0.5    # multiples of half the subnormal step
+    x = torch.where(kind == 3, (k * tiny).float(), x)
+    big = torch.tensor([65504.0, 65519.0, 65520.0, -65520.0, 65536.0, 7.0e4, -1.0e5, 3.4028235e38, -3.0e38, 65488.0, 65512.0])
+    x = torch.where(kind == 4, big[torch.randint(0, big.numel(), (m,), generator=g)], x)
+    if m < n:
+        x = x[torch.randint(0, m, (n,), generator=g)]
+    return x.view(shape)
+
+
+def pack_input_ref(x, Hp, Wp, pad, name):
+    """out[b][y + pad][x + pad][c] = elem(x[b][c][y][x]), channels C..7 of those pixels zero; everything else untouched.
+    Returns (out [n][Hp][Wp][8] in the element type, zero where untouched; written [n][Hp][Wp] bool)"""
+    n, C, H, W = x.shape
+    out = torch.zeros(n, Hp, Wp, 8, dtype=ELEM[name][0])
+    out[:, pad:pad + H, pad:pad + W, :C] = x.permute(0, 2, 3, 1).to(ELEM[name][0])
+    written = torch.zeros(n, Hp, Wp, dtype=torch.bool)
+    written[:, pad:pad + H, pad:pad + W] = True
+    return out, written
+
+
+PACK_WEIGHTS_CASES = ((32, 32, 3), (64, 96, 3), (96, 32, 1), (64, 64, 1))      # (Co, Ci, k)
+PACK_STEM_CI = (3, 5, 6)
+UNPACK_CASES = ((32, 32, 3, 32, 0), (64, 32, 1, 32, 0), (64, 5, 7, 64, 1))     # (Co, Ci, k, Kc, stem): 9 whole chunks; 2; a ragged last one
+
+
+def stem_rowtap(w, Kc=64):
+    """OIHW [Co][c][7][7] -> [r][Co][Kc], entry t * 8 + c (zero elsewhere): the stem's row-tap layout, in w's dtype"""
+    Co, Ci, kh, kw = w.shape
+    out = torch.zeros(kh, Co, Kc // 8, 8, dtype=w.dtype)
+    out[:, :, :kw, :Ci] = w.permute(2, 0, 3, 1)                     # [r][co][t][c]
+    return out.view(kh, Co, Kc)
+
+
+def pack_weights_ref(w, name, stem=False):
+    """fp32 OIHW -> (forward layout [tap][Co][Ci], data-gradient layout [tap][Ci][Co]) in the element type, tap = r * k + t.
+    The stem: ([r][Co][t * 8 + c] with zero fill for t = 7 and c >= Ci, None)."""
+    dt = ELEM[name][0]
+    if stem:
+        return stem_rowtap(w).to(dt), None
+    Co, Ci, k, _ = w.shape
+    return (w.permute(2, 3, 0, 1).reshape(k * k, Co, Ci).to(dt).contiguous(),
+            w.permute(2, 3, 1, 0).reshape(k * k, Ci, Co).to(dt).contiguous())
+
+
+def wgrad_scratch_layout(gr, Kc, stem=False, fill=0.0):
+    """fp32 OIHW gradient -> the weight-gradient scratch [tap][Co][Kc] (entries ci < Ci; the stem: stem_rowtap), `fill` elsewhere"""
+    Co, Ci, k, _ = gr.shape
+    if stem:
+        out = torch.full((k, Co, Kc // 8, 8), fill, dtype=gr.dtype)
+        out[:, :, :k, :Ci] = gr.permute(2, 0, 3, 1)
+        return out.view(k, Co, Kc)
+    out = torch.full((k * k, Co, Kc), fill, dtype=gr.dtype)
+    out[:, :, :Ci] = gr.permute(2, 3, 0, 1).reshape(k * k, Co, Ci)
+    return out
+
+
+def unpack_grads_ref(wg, Co, Ci, k, Kc, stem=False):
+    """the inverse on fp32: scratch [tap][Co][Kc] -> OIHW [Co][Ci][k][k]"""
+    if stem:
+        return wg.view(k, Co, Kc // 8, 8)[:, :, :k, :Ci].permute(1, 3, 0, 2).contiguous()
+    return wg.view(k, k, Co, Kc)[:, :, :, :Ci].permute(2, 3, 0, 1).contiguous()
+
+
+# ---- AdamW ----
+U32 = 2.0 ** -24
+ADAM_HYPERS = {"torch": dict(lr=5e-4, b1=0.9, b2=0.999, eps=1e-8, wd=0.01),       # train_vpd_model.py's: torch's defaults
+               "strong": dict(lr=1e-2, b1=0.8, b2=0.99, eps=1e-6, wd=0.1)}        # lr wd = 1e-3: a 0.1 % change of wd is 4 u of p
+ADAM_STEPS = (1, 2, 3, 1000, 100000)
+ADAM_N = 1 << 18                             # elements per regime: 256 blocks of the flat kernel
+ADAM_LONG = 4 * (256 * 4096 + 5)             # more than one pass of the flat kernel's capped grid (4096 blocks x 256 float4)
+
+
+def adamw_ref(p, g, m, v, lr, b1, b2, eps, wd, step, gscale=1.0):
+    """One AdamW step in float64 from the fp32 operands and the double hyper-parameters, as torch.optim.AdamW states it
+    (decoupled decay, lerp of the first moment, denominator sqrt(v) / sqrt(bc2) + eps).  Returns float64 (p', m', v')."""
+    p, m, v = p.double(), m.double(), v.double()
+    G = g.double() * gscale
+    p = p * (1.0 - lr * wd)
+    m = m + (G - m) * (1.0 - b1)
+    v = v * b2 + (1.0 - b2) * G * G
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    denom = v.sqrt() / math.sqrt(bc2) + eps
+    return p - (lr / bc1) * m / denom, m, v
+
+
+def adamw_bounds(p, g, m, v, lr, b1, b2, eps, wd, step, gscale=1.0):
+    """Per-element bounds of |fp32 kernel - adamw_ref| for (p', m', v'): first-order running errors of adamw1 (optim.hip), u = 2^-24,
+    G = g gscale (exact: gscale is a power of two), one rounding (relative u) per fp32 operation and per double hyper-parameter
+    rounded to float; fmaf rounds once, division and square root are correctly rounded, nothing is contracted or reassociated.
+      m' = fma(fl(G - m), fl(1 - b1), m): the difference and the factor each put u (1 - b1) |G - m| on the product, the fma u |m'|:
+           e_m = u (2 (1 - b1) |G - m| + |m'|).
+      v' = fma(fl(fl(1 - b2) G), G, fl(v fl(b2))): both addends are non-negative and carry 2 u each (factor, product), the fma u v':
+           e_v = 2 u v' + u v' = 3 u v'.
+      p1 = fl(p fl(1 - lr wd)): 2 u |decay p|.
+      den = fma(fl(sqrt(v')), fl(1 / sqrt(bc2)), eps): v' is 3 u off, its root 1.5 u, + u (sqrt) + u (factor) on the first addend,
+           u (fl(eps)) on the second, u for the fma: at most 4.5 u den.
+      p' = fma(-fl(lr / bc1), fl(m' / den), p1): the update U = step_size m' / den carries u (factor) + u (division) + 4.5 u (den)
+           relative and step_size / den e_m from m'; the fma u |p'|:
+           e_p = u (2 |decay p| + |p'| + step_size / den (2 (1 - b1) |G - m| + 7.5 |m'|)), stated with 8 |m'|.
+    Each is multiplied by 1.25 for the second-order terms (products of these, u^2), plus one fp32 subnormal step for results
+    that round in the subnormal range."""
+    pd, md, vd = p.double(), m.double(), v.double()
+    G = g.double() * gscale
+    p1, m1, v1 = adamw_ref(p, g, m, v, lr, b1, b2, eps, wd, step, gscale)
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    den = v1.sqrt() / math.sqrt(bc2) + eps
+    dm = 2.0 * (1.0 - b1) * (G - md).abs()
+    e_m = U32 * (dm + m1.abs())
+    e_v = 3.0 * U32 * v1
+    e_p = U32 * (2.0 * (pd * (1.0 - lr * wd)).abs() + p1.abs() + (lr / bc1) / den * (dm + 8.0 * m1.abs()))
+    sub = 2.0 ** -149
+    return 1.25 * e_p + sub, 1.25 * e_m + sub, 1.25 * e_v + sub
+
+
+def adamw_inputs(n, step, seed):
+    """fp32 (p, g, m, v) of n elements for the regime of `step`: per-element gradient scales 10^-6 .. 100, moments of the size a
+    run at that scale has after step - 1 steps (zero before the first), a tenth of the gradients zero, a tenth of the moments zero"""
+    g_ = torch.Generator().manual_seed(seed * 1000003 + step)
+    scale = torch.pow(torch.tensor(10.0), torch.rand(n, generator=g_) * 8.0 - 6.0)
+    p = torch.randn(n, generator=g_) * torch.where(torch.rand(n, generator=g_) < 0.5, 0.05, 1.0)
+    g = torch.randn(n, generator=g_) * scale
+    g = torch.where(torch.rand(n, generator=g_) < 0.1, torch.zeros(n), g)
+    if step == 1:
+        m, v = torch.zeros(n), torch.zeros(n)
+    else:
+        fill = min(1.0, (step - 1) / 10.0)
+        m = torch.randn(n, generator=g_) * scale * 0.5 * fill
+        v = (torch.randn(n, generator=g_) * scale) ** 2 * min(1.0, (step - 1) / 1000.0) + (m * m) * 1e-3
+        z = torch.rand(n, generator=g_) < 0.1
+        m, v = torch.where(z, torch.zeros(n), m), torch.where(z, torch.zeros(n), v)
+    return p, g, m, v
+
+
+# two synthetic flat buffers of vpd_op_adamw_pack: ((Co, Ci, k) ...) with the plain ranges in front of, between and behind them:
+# one shorter than a 2048-float chunk, one that is no multiple of 256, one longer than a chunk; k = 2 takes the general gather
+ADAM_PACK_BUFFERS = {
+    "a": dict(convs=((32, 32, 3), (64, 32, 1), (32, 64, 2)), gaps=(100, 2048 + 700, 4, 36)),
+    "b": dict(convs=((64, 64, 1), (32, 96, 3)), gaps=(0, 5000, 2048)),
+}
+
+
+def adam_pack_layout(name):
+    """-> (dims [(Co, Ci, k)], offsets, numel): gap i lies in front of conv i, the last one behind; every gap is a multiple of 4"""
+    b = ADAM_PACK_BUFFERS[name]
+    offs, at = [], 0
+    for (Co, Ci, k), gap in zip(b["convs"], b["gaps"]):
+        at += gap
+        offs.append(at)
+        at += Co * Ci * k * k
+    at += b["gaps"][-1]
+    assert at % 4 == 0 and all(o % 4 == 0 for o in offs)
+    return list(b["convs"]), offs, at
+
+
+# ---- slab sums ----
+SLAB_KSPLITS = (1, 2, 3, 15, 16, 17, 33)
+SLAB_LENGTHS = (9 * 64 * 64, 64 * 64, 4 * 100)
+SLAB_GROUP = ((9 * 64 * 64, 1), (64 * 64, 5), (4 * 100, 33))      # one launch: the thread groups of the widest serve all
+
+
+def slab_partials(n, ksplit, integer, g):
+    """[ksplit][n] fp32 partials: integers with |sum| <= 33 * 1000 < 2^24 (every fp32 sum exact in any order), or randn"""
+    if integer:
+        return torch.randint(-1000, 1001, (ksplit, n), generator=g).float()
+    return torch.randn(ksplit, n, generator=g)
+
+
+def slab_sum_ref(slab):
+    """float64 sum over the splits, and the bound of an fp32 sum of ksplit terms in any order: ksplit u sum |partials|"""
+    return slab.double().sum(0), slab.shape[0] * U32 * slab.double().abs().sum(0)
+
+
+ZERO_RANGE_CASES = {1: (1,), 3: (1, 512 * 256 + 77, 300), 16: tuple([1, 7, 256, 257, 1000, 3, 64, 5000] * 2)}      # float4 per range

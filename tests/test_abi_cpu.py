@@ -148,6 +148,120 @@ def test_fused_tail_entry_points_are_declared_bound_and_exported(dtype):
     assert h.vpd_op_conv1x1_bn_dispatch(256, 32, 32, 64, 256, 1, out) == 0 and out[0] == 1 and out[4] == 5
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_boundary_entry_points_are_bound_and_reject_bad_arguments(dtype):
+    """vpd_op_pack_input, vpd_op_pack_weights, vpd_op_unpack_grads, vpd_op_adamw_pack, vpd_op_wgrad_reduce, vpd_op_zero_ranges:
+    test-only additions under ABI 5; every refusal is taken on the host, with a message, before anything is launched"""
+    from vpd_amd import _lib
+    h = _lib.lib(dtype)
+    assert h.vpd_abi_version() == _lib.ABI_VERSION == 5
+    for n, nargs in (("vpd_op_pack_input", 10), ("vpd_op_pack_weights", 8), ("vpd_op_unpack_grads", 8), ("vpd_op_adamw_pack", 18),
+                     ("vpd_op_wgrad_reduce", 6), ("vpd_op_zero_ranges", 4)):
+        assert n in header_functions() and len(_lib.SIGNATURES[n][1]) == nargs and getattr(h, n).argtypes == _lib.SIGNATURES[n][1]
+    p = C.c_void_p(64)                                    # never dereferenced: every call below is rejected on the host
+    odd = C.c_void_p(72)                                  # 8-byte aligned only
+
+    def refused(rc, msg):
+        return rc != 0 and msg in h.vpd_last_error()
+    # pack_input
+    assert refused(h.vpd_op_pack_input(None, 2, 5, 4, 8, p, 10, 16, 3, None), b"null argument")
+    assert refused(h.vpd_op_pack_input(p, 2, 5, 4, 8, None, 10, 16, 3, None), b"null argument")
+    assert refused(h.vpd_op_pack_input(p, 2, 9, 4, 8, p, 10, 16, 3, None), b"c outside 1..8")
+    assert refused(h.vpd_op_pack_input(p, 2, 0, 4, 8, p, 10, 16, 3, None), b"c outside 1..8")
+    for bad in ((0, 4, 8, 10, 16, 3), (2, 0, 8, 10, 16, 3), (2, 4, 0, 10, 16, 3), (2, 4, 8, 6, 16, 3), (2, 4, 8, 10, 10, 3),
+                (2, 4, 8, 10, 16, -1), (70000, 200, 200, 206, 208, 3)):
+        n, H, W, Hp, Wp, pad = bad
+        assert refused(h.vpd_op_pack_input(p, n, 5, H, W, p, Hp, Wp, pad, None), b"bad shape"), bad
+    assert refused(h.vpd_op_pack_input(C.c_void_p(66), 2, 5, 4, 8, p, 10, 16, 3, None), b"aligned")
+    assert refused(h.vpd_op_pack_input(p, 2, 5, 4, 8, odd, 10, 16, 3, None), b"aligned")
+    # pack_weights / unpack_grads
+    assert refused(h.vpd_op_pack_weights(None, 32, 32, 3, 0, p, p, None), b"null argument")
+    assert refused(h.vpd_op_pack_weights(p, 32, 32, 3, 0, None, p, None), b"null argument")
+    for Co, Ci, k, stem, msg in ((48, 32, 3, 0, b"multiples of 32"), (32, 16, 3, 0, b"multiples of 32"), (32, 32, 4, 0, b"k must be"),
+                                 (32, 32, 0, 0, b"k must be"), (64, 9, 7, 1, b"the stem is"), (64, 5, 3, 1, b"the stem is"),
+                                 (64, 5, 7, 2, b"stem is 0 or 1")):
+        assert refused(h.vpd_op_pack_weights(p, Co, Ci, k, stem, p, None, None), msg), (Co, Ci, k, stem)
+        assert refused(h.vpd_op_unpack_grads(p, Co, Ci, k, 64, stem, p, None), msg), (Co, Ci, k, stem)
+    assert refused(h.vpd_op_pack_weights(p, 64, 5, 7, 1, p, p, None), b"no data-gradient layout")
+    assert refused(h.vpd_op_pack_weights(p, 32, 32, 3, 0, odd, None, None), b"aligned")
+    assert refused(h.vpd_op_pack_weights(p, 32, 32, 3, 0, p, odd, None), b"aligned")
+    assert refused(h.vpd_op_unpack_grads(None, 32, 32, 3, 32, 0, p, None), b"null argument")
+    assert refused(h.vpd_op_unpack_grads(p, 32, 32, 3, 32, 0, None, None), b"null argument")
+    assert refused(h.vpd_op_unpack_grads(p, 32, 64, 3, 32, 0, p, None), b"Kc is too small")
+    assert refused(h.vpd_op_unpack_grads(p, 64, 5, 7, 48, 1, p, None), b"Kc is too small")
+    # adamw_pack
+    dims = (C.c_int * 6)(32, 32, 3, 64, 32, 1)
+    offs = (C.c_longlong * 2)(100, 100 + 9216 + 8)
+    numel = 100 + 9216 + 8 + 2048 + 4
+    hyp = (5e-4, 0.9, 0.999, 1e-8, 0.01)
+
+    def adam(nconv=2, dims=dims, offs=offs, numel=numel, ptrs=(p, p, p, p, p, None), step=1):
+        return h.vpd_op_adamw_pack(nconv, dims, offs, numel, *ptrs, *hyp, step, 1.0, None)
+    for i in range(5):
+        ptrs = [p, p, p, p, p, None]
+        ptrs[i] = None
+        assert refused(adam(ptrs=ptrs), b"null argument"), i
+    assert refused(adam(dims=None), b"null argument") and refused(adam(offs=None), b"null argument")
+    assert refused(adam(nconv=-1), b"nconv outside") and refused(adam(nconv=65), b"nconv outside")
+    assert refused(adam(numel=numel + 2), b"multiple of 4") and refused(adam(numel=0), b"multiple of 4")
+    assert refused(adam(step=0), b"1-based")
+    assert refused(adam(ptrs=(p, p, p, p, odd, None)), b"16-byte aligned") and refused(adam(ptrs=(p, p, p, p, p, odd)), b"16-byte aligned")
+    assert refused(adam(dims=(C.c_int * 6)(32, 32, 3, 64, 48, 1)), b"multiples of 32")
+    assert refused(adam(offs=(C.c_longlong * 2)(102, 9400)), b"multiple of 4 floats")
+    assert refused(adam(offs=(C.c_longlong * 2)(100, 9000)), b"ascend")                 # overlap
+    assert refused(adam(offs=(C.c_longlong * 2)(9400, 100)), b"ascend")
+    assert refused(adam(numel=10000), b"ascend")                                      # the last conv ends behind numel
+    # wgrad_reduce
+    pp = (C.c_void_p * 2)(64, 128)
+    nf = (C.c_longlong * 2)(400, 4096)
+    ks = (C.c_int * 2)(3, 1)
+    assert refused(h.vpd_op_wgrad_reduce(2, None, pp, nf, ks, None), b"null argument")
+    assert refused(h.vpd_op_wgrad_reduce(2, pp, None, nf, ks, None), b"null argument")
+    assert refused(h.vpd_op_wgrad_reduce(2, pp, pp, None, ks, None), b"null argument")
+    assert refused(h.vpd_op_wgrad_reduce(2, pp, pp, nf, None, None), b"null argument")
+    assert refused(h.vpd_op_wgrad_reduce(2, (C.c_void_p * 2)(64, None), pp, nf, ks, None), b"null argument")
+    assert refused(h.vpd_op_wgrad_reduce(0, pp, pp, nf, ks, None), b"nprob outside") and refused(h.vpd_op_wgrad_reduce(19, pp, pp, nf, ks, None), b"nprob outside")
+    assert refused(h.vpd_op_wgrad_reduce(2, pp, pp, (C.c_longlong * 2)(402, 4096), ks, None), b"multiple of 4")
+    assert refused(h.vpd_op_wgrad_reduce(2, pp, pp, (C.c_longlong * 2)(400, 0), ks, None), b"multiple of 4")
+    assert refused(h.vpd_op_wgrad_reduce(2, pp, pp, nf, (C.c_int * 2)(3, 0), None), b"ksplit >= 1")
+    assert refused(h.vpd_op_wgrad_reduce(2, (C.c_void_p * 2)(64, 72), pp, nf, ks, None), b"16-byte aligned")
+    # zero_ranges
+    assert h.vpd_op_zero_ranges(None, None, 0, None) == 0                             # count 0: nothing to do, nothing looked at
+    assert refused(h.vpd_op_zero_ranges(pp, nf, -1, None), b"count outside") and refused(h.vpd_op_zero_ranges(pp, nf, 17, None), b"count outside")
+    assert refused(h.vpd_op_zero_ranges(None, nf, 2, None), b"null argument") and refused(h.vpd_op_zero_ranges(pp, None, 2, None), b"null argument")
+    assert refused(h.vpd_op_zero_ranges((C.c_void_p * 2)(64, None), nf, 2, None), b"null argument")
+    assert refused(h.vpd_op_zero_ranges((C.c_void_p * 2)(64, 72), nf, 2, None), b"16-byte aligned")
+    assert refused(h.vpd_op_zero_ranges(pp, (C.c_longlong * 2)(4, -1), 2, None), b"not negative")
+    # the public flat AdamW refuses a length that is no multiple of 4
+    assert refused(h.vpd_adamw_step(p, p, p, p, 4102, *hyp, 1, None), b"multiple of 4")
+    assert refused(h.vpd_adamw_step_scaled(p, p, p, p, 4102, *hyp, p, None), b"multiple of 4")
+
+
+ARCHS = ("resnet18", "resnet34", "resnet50", "resnet101", "wide_resnet50_2", "wide_resnet101_2")
+
+
+@pytest.mark.parametrize("arch", ARCHS)
+@pytest.mark.parametrize("c_in", [3, 5])
+def test_every_conv_tensor_of_a_plan_starts_at_a_multiple_of_four_floats(arch, c_in):
+    """adamw_pack_kernel reads and writes a conv's OIHW rows 16 bytes at a time and -- unlike pack_weights_kernel -- has no
+    unaligned fallback: every 4-dimensional tensor of every architecture the plan accepts lies at a multiple of 4 floats"""
+    from vpd_amd._lib import check, lib
+    L = lib()
+    h = C.c_void_p()
+    check(L.vpd_plan_create(arch.encode(), c_in, 128, 128, 128, 1, 4, 1, C.byref(h)), "create")
+    kind, dec, off, numel, ndim = C.c_int(), C.c_int(), C.c_longlong(), C.c_longlong(), C.c_int()
+    dims = (C.c_int * 4)()
+    convs = 0
+    for i in range(L.vpd_plan_num_tensors(h)):
+        check(L.vpd_plan_tensor_info(h, i, C.byref(kind), C.byref(dec), C.byref(off), C.byref(numel), C.byref(ndim), dims), "info")
+        if ndim.value == 4:
+            assert kind.value == 0 and off.value % 4 == 0, (i, off.value)
+            assert numel.value == dims[0] * dims[1] * dims[2] * dims[3]
+            convs += 1
+    assert convs >= 20 and L.vpd_plan_param_numel(h) % 4 == 0
+    L.vpd_plan_destroy(h)
+
+
 def test_product_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

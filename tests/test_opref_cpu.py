@@ -408,3 +408,223 @@ def test_tail_random_regime_bounds_accept_fp32_and_reject_the_five_faults(case, 
         for fault, pairs in faults.items():
             for i in where[fault]:
                 assert _outside(*pairs[i]), (fault, i)
+
+
+# ---------------------------------------------------------------------------
+# the reference boundary (tests/test_boundary_ops_gpu.py)
+# ---------------------------------------------------------------------------
+def _pack_input_shapes():
+    return (R.PACK_INPUT_ROWS + R.PACK_INPUT_ROWS_FALLBACK + R.PACK_INPUT_QUAD + R.PACK_INPUT_PIXEL + R.PACK_INPUT_MISALIGNED +
+            (R.PACK_INPUT_BELOW, R.PACK_INPUT_WORKLOAD, R.PACK_INPUT_ABOVE))
+
+
+def test_pack_input_cases_take_the_routes_they_are_named_for():
+    """the launcher's conditions (vpd_launch_pack_input) restated on the case tables, and the item counts around 2^21"""
+    for n, H, W in R.PACK_INPUT_ROWS + (R.PACK_INPUT_WORKLOAD,):
+        assert W % 64 == 0 and (H * W) % 256 == 0
+    for n, H, W in R.PACK_INPUT_ROWS_FALLBACK:
+        assert W % 64 == 0 and (H * W) % 256 != 0
+    for n, H, W in R.PACK_INPUT_QUAD + (R.PACK_INPUT_BELOW, R.PACK_INPUT_ABOVE):
+        assert W % 4 == 0 and W % 64 != 0
+    for n, H, W in R.PACK_INPUT_PIXEL:
+        assert W % 4 != 0
+    items = lambda s: s[0] * s[1] * s[2] // 4
+    assert items(R.PACK_INPUT_BELOW) < R.FDIV_MAX <= items(R.PACK_INPUT_WORKLOAD) and R.PACK_INPUT_BELOW[2] // 4 == 7
+    assert R.FDIV_MAX - items(R.PACK_INPUT_BELOW) < 64                     # the last items of the fast path are reached
+    assert items(R.PACK_INPUT_ABOVE) >= R.FDIV_MAX
+
+
+def test_float_reciprocal_division_is_exact_for_the_pack_input_divisors():
+    """vpd_fdiv in numpy float32: int((m + 0.5f) * (1.0f / d)) == m // d for every m < 2^21, for d = 1 .. 128 and every divisor
+    (W / 4 and H) of the quad-kernel cases -- so the 64-bit path is needed from 2^21 items on, and only there"""
+    divs = set(range(1, 129))
+    for n, H, W in _pack_input_shapes():
+        divs |= {H, max(W // 4, 1)}
+    m = np.arange(R.FDIV_MAX, dtype=np.int64)
+    mf = m.astype(np.float32) + np.float32(0.5)
+    for d in sorted(divs):
+        q = (mf * (np.float32(1.0) / np.float32(d))).astype(np.int64)
+        assert np.array_equal(q, m // d), d
+
+
+@pytest.mark.parametrize("name", ["bf16", "fp16"])
+def test_pack_input_reference_is_a_literal_loop_and_sees_a_channel_left_unzeroed(name):
+    g = torch.Generator().manual_seed(3)
+    dt = R.ELEM[name][0]
+    x = R.pack_input_values((2, 5, 3, 6), name, g)
+    out, written = R.pack_input_ref(x, 3 + 6, 6 + 8, 3, name)
+    for b in range(2):
+        for yy in range(9):
+            for xx in range(14):
+                inside = 3 <= yy < 6 and 3 <= xx < 9
+                assert bool(written[b, yy, xx]) == inside
+                for c in range(8):
+                    want = x[b, c, yy - 3, xx - 3].to(dt) if inside and c < 5 else torch.zeros((), dtype=dt)
+                    assert int(R.bits(out[b, yy, xx, c].view(1))[0]) == int(R.bits(want.view(1))[0])
+    # the inputs hold what they promise: ties, both zeros, element-type subnormals, fp16 overflow to inf as torch rounds it
+    big = R.pack_input_values((1 << 16,), name, g)
+    e = big.to(dt)
+    assert bool((R.bits(big) == 0).any()) and bool((R.bits(big) == -2 ** 31).any())      # +0 and -0
+    assert bool(((big != 0) & (big.abs() < 2.0 ** (R.ELEM[name][2] + R.ELEM[name][1] - 1))).any())
+    assert bool(torch.isinf(e).any()) and not bool(torch.isnan(e).any())
+    assert float(torch.tensor(65519.0).to(torch.float16)) == 65504.0 and bool(torch.isinf(torch.tensor(65520.0).to(torch.float16)))
+    assert not bool((R.bits(e) == R.SENTINEL_BITS[name]).any())
+    # resolution: channel 5 of the interior not zeroed (it keeps the sentinel) is seen by the whole-buffer comparison of bits
+    sent = R.sentinel_elems((2, 9, 14, 8), name)
+    want = torch.where(written.unsqueeze(-1), out, sent)
+    wrong = want.clone()
+    wrong[:, 3:6, 3:9, 5] = sent[:, 3:6, 3:9, 5]
+    assert not torch.equal(R.bits(wrong), R.bits(want))
+    assert bool((R.bits(want)[:, 3:6, 3:9, 5:] == 0).all()) and bool((R.bits(want)[:, 0] == R.SENTINEL_BITS[name]).all())
+
+
+@pytest.mark.parametrize("name", ["bf16", "fp16"])
+def test_pack_weights_reference_is_a_literal_loop_unpack_is_its_inverse_and_a_transposed_tap_shows(name):
+    g = torch.Generator().manual_seed(5)
+    dt = R.ELEM[name][0]
+    w = torch.randn(4, 3, 3, 3, generator=g)
+    fwd, dgr = R.pack_weights_ref(w, name)
+    for r in range(3):
+        for t in range(3):
+            for co in range(4):
+                for ci in range(3):
+                    assert fwd[r * 3 + t, co, ci] == w[co, ci, r, t].to(dt) == dgr[r * 3 + t, ci, co]
+    ws = torch.randn(6, 5, 7, 7, generator=g)
+    sf, none = R.pack_weights_ref(ws, name, stem=True)
+    assert none is None and sf.shape == (7, 6, 64)
+    for r in range(7):
+        for co in range(6):
+            for t in range(8):
+                for c in range(8):
+                    want = ws[co, c, r, t].to(dt) if t < 7 and c < 5 else 0.0
+                    assert sf[r, co, t * 8 + c] == want
+    # unpack(pack-layout(x)) == x on fp32, whatever fills the unused columns
+    for Co, Ci, k, Kc, stem in R.UNPACK_CASES + ((32, 32, 2, 40, 0),):
+        gr = torch.randn(Co, Ci, k, k, generator=g)
+        wg = R.wgrad_scratch_layout(gr, Kc, bool(stem), fill=float("nan"))
+        assert torch.equal(R.unpack_grads_ref(wg, Co, Ci, k, Kc, bool(stem)), gr)
+    assert torch.equal(R.wgrad_scratch_layout(ws, 64, True), R.stem_rowtap(ws))
+    # resolution: ONE tap transposed ((r, t) = (0, 1) <-> (1, 0)) changes both layouts, in those two taps only
+    wt = w.clone()
+    wt[:, :, 0, 1], wt[:, :, 1, 0] = w[:, :, 1, 0], w[:, :, 0, 1]
+    f2, d2 = R.pack_weights_ref(wt, name)
+    assert not torch.equal(R.bits(f2), R.bits(fwd)) and not torch.equal(R.bits(d2), R.bits(dgr))
+    assert torch.equal(f2[1], fwd[3]) and torch.equal(f2[3], fwd[1]) and torch.equal(f2[4:], fwd[4:])
+
+
+def _adamw1_f32(p, g, m, v, lr, b1, b2, eps, wd, step, gscale=1.0):
+    """adamw1 + adam_hyper of vpd_amd/csrc/optim.hip in numpy float32, operation by operation (fmaf: the exact product of two
+    floats in float64, one addition, rounded to float)"""
+    f = np.float32
+    decay, omb1, b2f, omb2 = f(1.0 - lr * wd), f(1.0 - b1), f(b2), f(1.0 - b2)
+    step_size, isb, epsf = f(lr / (1.0 - b1 ** step)), f(1.0 / np.sqrt(1.0 - b2 ** step)), f(eps)
+    fma = lambda a, b, c: (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f)
+    p, g, m, v = (t.numpy().astype(f) for t in (p, g, m, v))
+    g = g * f(gscale)
+    p = p * decay
+    m = fma(g - m, omb1, m)
+    v = fma(omb2 * g, g, v * b2f)
+    den = fma(np.sqrt(v), isb, epsf)
+    p = fma(-step_size, m / den, p)
+    return torch.from_numpy(p), torch.from_numpy(m), torch.from_numpy(v)
+
+
+def test_adamw_reference_is_torch_optim_adamw_in_float64():
+    g = torch.Generator().manual_seed(9)
+    for hp in R.ADAM_HYPERS.values():
+        p0 = torch.randn(4096, generator=g)
+        ref = torch.nn.Parameter(p0.double().clone())
+        opt = torch.optim.AdamW([ref], lr=hp["lr"], betas=(hp["b1"], hp["b2"]), eps=hp["eps"], weight_decay=hp["wd"])
+        p, m, v = p0.double(), torch.zeros(4096, dtype=torch.float64), torch.zeros(4096, dtype=torch.float64)
+        for t in (1, 2, 3):
+            gr = torch.randn(4096, generator=g) * 10.0 ** (t - 2)
+            ref.grad = gr.double()
+            opt.step()
+            p, m, v = R.adamw_ref(p, gr, m, v, step=t, **hp)
+            st = opt.state[ref]
+            for a, b in ((p, ref.detach()), (m, st["exp_avg"]), (v, st["exp_avg_sq"])):
+                assert float(((a - b).abs() / b.abs().clamp_min(1e-300)).max()) <= 1e-12
+
+
+ADAM_REGIMES = [(h, s) for h in R.ADAM_HYPERS for s in R.ADAM_STEPS]
+
+
+@pytest.mark.parametrize("hyper,step", ADAM_REGIMES)
+def test_adamw_bounds_hold_an_fp32_transcription_and_reject_perturbed_hyper_parameters(hyper, step):
+    """on the GPU tests' own inputs: the fp32 transcription of adamw1 stays inside every bound (ratio <= 1), and a reference with
+    one hyper-parameter 0.1 % off (the step number: 1 off) leaves at least a quarter of some output outside its bound -- where the
+    change exists in exact arithmetic at all: weight decay moves p by lr wd / 1000 relative, 5e-9 = u / 12 for torch's defaults
+    (the `strong` set makes it 1e-6 = 17 u), and the bias corrections of steps t and t - 1 are the same doubles at t = 100,000"""
+    hp = R.ADAM_HYPERS[hyper]
+    ins = R.adamw_inputs(R.ADAM_N, step, 1)
+    got = _adamw1_f32(*ins, step=step, **hp)
+    ref = R.adamw_ref(*ins, step=step, **hp)
+    bnd = R.adamw_bounds(*ins, step=step, **hp)
+    ratios = [float(((a.double() - b).abs() / c).max()) for a, b, c in zip(got, ref, bnd)]
+    print("adamw %s step %d: max error / bound p %.3f m %.3f v %.3f" % ((hyper, step) + tuple(ratios)))
+    assert max(ratios) <= 1.0, ratios
+
+    def outside(**change):
+        h2 = dict(hp, step=step)
+        h2.update(change)
+        off = R.adamw_ref(*ins, **h2)
+        return max(float(((a.double() - b).abs() > c).float().mean()) for a, b, c in zip(got, off, bnd))
+    for key in ("lr", "b1", "b2"):
+        assert outside(**{key: hp[key] * 1.001}) >= 0.25, key
+        assert outside(**{key: hp[key] * 0.999}) >= 0.25, key
+    if hyper == "strong":
+        assert outside(wd=hp["wd"] * 1.001) >= 0.25 and outside(wd=hp["wd"] * 0.999) >= 0.25
+    # the step number: wherever a bias correction of the neighbouring step differs by more than 1e-5 relative (170 u) in exact
+    # arithmetic -- steps 1, 2, 3 of both sets and step 1,000 with b2 = 0.999 (0.999^1000 = 0.37); beyond, they converge to 1
+    def corrections(t):
+        return (1.0 / (1.0 - hp["b1"] ** t), 1.0 / np.sqrt(1.0 - hp["b2"] ** t))
+    for other in (step + 1, step - 1):
+        if other < 1:
+            continue
+        rel = max(abs(a / b - 1.0) for a, b in zip(corrections(other), corrections(step)))
+        assert (rel >= 1e-5) == (step <= 3 or (hyper, step) == ("torch", 1000)), (other, rel)
+        if rel >= 1e-5:
+            assert outside(step=other) >= 0.25, other                          # (step - 1: the bias correction of step t - 1)
+
+
+def test_adamw_gradient_scale_by_a_power_of_two_is_exact_in_the_transcription():
+    hp = R.ADAM_HYPERS["torch"]
+    p, g, m, v = R.adamw_inputs(1 << 14, 3, 2)
+    a = _adamw1_f32(p, g, m, v, step=3, **hp)
+    b = _adamw1_f32(p, g * 4096.0, m, v, step=3, gscale=2.0 ** -12, **hp)
+    assert all(torch.equal(R.bits(x), R.bits(y)) for x, y in zip(a, b))
+
+
+def test_adam_pack_buffers_have_the_plain_ranges_the_cases_ask_for():
+    for name in R.ADAM_PACK_BUFFERS:
+        dims, offs, numel = R.adam_pack_layout(name)
+        assert numel % 4 == 0 and all(o % 4 == 0 for o in offs)
+        assert {k for _, _, k in dims} >= {1, 3}
+    gaps = [x for b in R.ADAM_PACK_BUFFERS.values() for x in b["gaps"]]
+    assert any(0 < x < 2048 for x in gaps) and any(x % 256 for x in gaps) and any(x > 2048 for x in gaps)
+    assert any(k == 2 for b in R.ADAM_PACK_BUFFERS.values() for _, _, k in b["convs"])   # khw = 4: the general gather
+
+
+@pytest.mark.parametrize("ksplit", R.SLAB_KSPLITS)
+def test_slab_sum_reference_is_exact_on_integers_and_its_bound_sees_a_dropped_split(ksplit):
+    g = torch.Generator().manual_seed(ksplit)
+    n = R.SLAB_LENGTHS[-1]
+    s = R.slab_partials(n, ksplit, True, g)
+    ref, _ = R.slab_sum_ref(s)
+    assert float(s.abs().sum(0).max()) < 2 ** 24
+    for order in (range(ksplit), reversed(range(ksplit))):                     # fp32 sums of these integers: exact in any order
+        acc = torch.zeros(n)
+        for i in order:
+            acc = acc + s[i]
+        assert torch.equal(acc.double(), ref)
+    s = R.slab_partials(n, ksplit, False, g)
+    ref, bound = R.slab_sum_ref(s)
+    acc = torch.zeros(n)
+    for i in range(ksplit):
+        acc = acc + s[i]
+    assert bool(((acc.double() - ref).abs() <= bound).all())
+    if ksplit > 1:                                                             # one split dropped: outside nearly everywhere
+        dropped = s[:-1].double().sum(0)
+        assert float(((dropped - ref).abs() > bound).float().mean()) > 0.95
+        si = R.slab_partials(n, ksplit, True, g)
+        assert float((si[:-1].double().sum(0) != si.double().sum(0)).float().mean()) > 0.99

@@ -103,6 +103,12 @@ SIGNATURES = {
     "vpd_op_wgrad128_group": (C.c_int, [C.c_int, vp, vp, vp, vp, c_int_p, vp, vp]),
     "vpd_op_wgrad128_schedule": (C.c_int, [C.c_int, c_int_p, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int,
                                            C.POINTER(C.c_double)]),
+    "vpd_op_pack_input": (C.c_int, [vp] + [C.c_int] * 4 + [vp] + [C.c_int] * 3 + [vp]),
+    "vpd_op_pack_weights": (C.c_int, [vp] + [C.c_int] * 4 + [vp, vp, vp]),
+    "vpd_op_unpack_grads": (C.c_int, [vp] + [C.c_int] * 5 + [vp, vp]),
+    "vpd_op_adamw_pack": (C.c_int, [C.c_int, c_int_p, c_ll_p, C.c_longlong] + [vp] * 6 + [C.c_double] * 5 + [C.c_int, C.c_float, vp]),
+    "vpd_op_wgrad_reduce": (C.c_int, [C.c_int, C.POINTER(vp), C.POINTER(vp), c_ll_p, c_int_p, vp]),
+    "vpd_op_zero_ranges": (C.c_int, [C.POINTER(vp), c_ll_p, C.c_int, vp]),
 }
 
 _libs = {}

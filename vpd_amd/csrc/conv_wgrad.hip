@@ -592,6 +592,16 @@ static void wg_launch_reduce(const WgReduceGroup& red, hipStream_t stream) {
     hipLaunchKernelGGL(wgrad_slab_reduce_group_kernel, dim3((unsigned)((max_n4 + 63) / 64), red.nprob), dim3(64 * groups), 0, stream,
                        red, groups);
 }
+// the same launch from flat arguments (vpd_op_wgrad_reduce: the operator tests)
+int vpd_wgrad_reduce_max() { return WG_GROUP_MAX; }
+hipError_t vpd_launch_wgrad_reduce(int nprob, const float* const* slabs, float* const* dws, const long long* nfloats,
+                                   const int* ksplits, hipStream_t stream) {
+    if (nprob < 1 || nprob > WG_GROUP_MAX) return hipErrorInvalidValue;
+    WgReduceGroup red = {};
+    for (int i = 0; i < nprob; ++i) red.add(slabs[i], dws[i], (long)nfloats[i], ksplits[i]);
+    wg_launch_reduce(red, stream);
+    return hipGetLastError();
+}
 
 
 // ---------------------------------------------------------------------------

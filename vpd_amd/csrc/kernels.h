@@ -235,6 +235,10 @@ struct ZeroRanges {                     // 16-byte aligned ranges, lengths in fl
     int count;
 };
 hipError_t vpd_launch_zero_ranges(const ZeroRanges& z, hipStream_t s);
+// conv_wgrad.hip: the slab sums of up to vpd_wgrad_reduce_max() problems in one launch (wg_launch_reduce from flat arguments)
+int vpd_wgrad_reduce_max();
+hipError_t vpd_launch_wgrad_reduce(int nprob, const float* const* slabs, float* const* dws, const long long* nfloats,
+                                   const int* ksplits, hipStream_t stream);
 
 // augment.hip (declared with the public vpd_aug_params of include/vpd_hip.h)
 struct vpd_aug_params;

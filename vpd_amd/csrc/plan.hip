@@ -24,7 +24,7 @@ int fail(const char* what, hipError_t e) {
 
 extern "C" const char* vpd_last_error(void) { return g_err.c_str(); }
 extern "C" const char* vpd_elem_dtype(void) { return VPD_ELEM_NAME; }      // "bf16" (libvpdhip.so) or "fp16" (libvpdhip_f16.so)
-extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2 (+ vpd_op_wgrad_pair, vpd_op_wgrad_pair_lds_bytes, vpd_op_conv1x1_bn, vpd_op_conv1x1_bn2, vpd_op_conv1x1_bn_dispatch: test-only additions, no existing signature changed, number kept); 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
+extern "C" int vpd_abi_version(void) { return 5; }      // 5: vpd_op_conv2d_dispatch, vpd_op_conv2d_bnsums2 (+ vpd_op_wgrad_pair, vpd_op_wgrad_pair_lds_bytes, vpd_op_conv1x1_bn, vpd_op_conv1x1_bn2, vpd_op_conv1x1_bn_dispatch, vpd_op_pack_input, vpd_op_pack_weights, vpd_op_unpack_grads, vpd_op_adamw_pack, vpd_op_wgrad_reduce, vpd_op_zero_ranges: test-only additions, no existing signature changed, number kept); 2: round 5/6 entry points (vpd_op_conv2d_ep, train flag word, 8 timing classes); 3: dynamic loss scaling (vpd_scale_state); 4: operator entry points of the stem pool, the BatchNorm backward launchers and the head
 
 namespace {
 
@@ -51,11 +51,69 @@ void add_tensor(vpd_plan* p, int kind, int is_dec, long long numel, int ndim, in
     p->nparam += numel;
 }
 
+// packed-weight geometry of a conv: the stem keeps one tap per kernel ROW, its 7 column taps x 8 channels in a 64-wide K
+void set_pack_geom(ConvInfo& c, int Ci, int Co, int k, bool stem) {
+    c.Ci = Ci; c.Co = Co; c.k = k; c.stem = stem;
+    if (stem) { c.Kc = 64; c.ntaps = k; } else { c.Kc = Ci; c.ntaps = k * k; }
+}
+
+// ---- pack descriptors + block maps: the tables of pack_weights_kernel, unpack_grads_kernel and adamw_pack_kernel (optim.hip).
+// vpd_plan_create builds the plan's with these two functions, the vpd_op_pack_weights / vpd_op_unpack_grads / vpd_op_adamw_pack
+// entry points build a test's: one construction, so that an operator test runs the maps the train step runs ----
+// Appends c's descriptor, its blocks of the pack map and of `bmap_unpack` (a bucket's unpack map); returns the descriptor's index.
+int push_pack_desc(std::vector<PackDesc>& descs, std::vector<int>& bmap_pack, std::vector<int>& bmap_unpack, const ConvInfo& c) {
+    PackDesc d;
+    d.src_off = c.w_off; d.fwd_off = c.fwd_off; d.dgr_off = c.dgr_off; d.wg_off = c.wg_off;
+    d.Co = c.Co; d.Ci = c.Ci; d.kh = c.k; d.kw = c.k; d.Kc = c.Kc; d.ntaps = c.ntaps; d.stem = c.stem ? 1 : 0;
+    d.numel = 0;
+    const int id = (int)descs.size();
+    descs.push_back(d);
+    const long long nf = (long long)c.ntaps * c.Co * c.Kc;
+    const long long ns = (long long)c.Co * c.Ci * c.k * c.k;
+    const long long npk = nf > ns ? nf : ns;
+    // pack kernel: 32x32 (co x ci) tiles for ordinary convs, PACK_CHUNK element chunks for the stem
+    const long long npack = c.stem ? (npk + 1023) / 1024 : (long long)(c.Co / 32) * (c.Ci / 32);
+    for (long long ch = 0; ch < npack; ++ch) { bmap_pack.push_back(id); bmap_pack.push_back((int)ch); }
+    const long long uchunk = 1024;     // PACK_CHUNK of unpack_grads_kernel
+    for (long long ch = 0; ch * uchunk < ns; ++ch) { bmap_unpack.push_back(id); bmap_unpack.push_back((int)ch); }
+    return id;
+}
+// Block map of the fused AdamW + repack launch over [0, nparam_padded): every conv tile as in the pack map -- not descriptor
+// `stem_id`'s (-1: there is none), whose blocks are counted into nstem_pack_blocks instead -- then the ranges that are not one of
+// the other descriptors' conv weights, in 2048-float chunks (ADAM_PLAIN_CHUNK of optim.hip), as `stem == 2` descriptors appended
+// to `descs`.
+void build_adam_map(std::vector<PackDesc>& descs, const std::vector<int>& bmap_pack, int stem_id, long long nparam_padded,
+                    std::vector<int>& bmap_adam, int& nstem_pack_blocks) {
+    const int nconv = (int)descs.size();
+    // (the stem is a plain range here, packed by a 28-block pack_weights_kernel launch afterwards.  Round 4 tried ONE
+    //  block of this launch for it -- update, then the row-tap packing, which gathers across the whole tensor: its ~30 dependent
+    //  round trips under the launch's 5 TB/s of traffic made it the launch's pole, 155 vs 131 us, profiles/r04_small_folds.txt)
+    for (size_t i = 0; i + 1 < bmap_pack.size(); i += 2) {
+        if (bmap_pack[i] == stem_id) { nstem_pack_blocks++; continue; }
+        bmap_adam.push_back(bmap_pack[i]); bmap_adam.push_back(bmap_pack[i + 1]);
+    }
+    std::vector<std::pair<long long, long long>> convs;                   // (offset, numel), ascending
+    for (int i = 0; i < nconv; ++i)
+        if (i != stem_id) convs.push_back({descs[i].src_off, (long long)descs[i].Co * descs[i].Ci * descs[i].kh * descs[i].kw});
+    std::sort(convs.begin(), convs.end());
+    long long pos = 0;
+    auto plain = [&](long long a, long long b) {
+        if (b <= a) return;
+        PackDesc d = {};
+        d.src_off = a; d.numel = b - a; d.stem = 2; d.kh = d.kw = 1; d.dgr_off = -1;
+        const int id = (int)descs.size();
+        descs.push_back(d);
+        for (long long ch = 0; ch * 2048 < b - a; ++ch) { bmap_adam.push_back(id); bmap_adam.push_back((int)ch); }
+    };
+    for (auto& cv : convs) { plain(pos, cv.first); pos = cv.first + cv.second; }
+    plain(pos, nparam_padded);
+}
+
 void add_conv(vpd_plan* p, ConvInfo& c, int Ci, int Co, int k, int stride, int pad, int Hin, int Win, bool stem) {
-    c.Ci = Ci; c.Co = Co; c.k = k; c.stride = stride; c.pad = pad; c.Hin = Hin; c.Win = Win; c.stem = stem;
+    set_pack_geom(c, Ci, Co, k, stem);
+    c.stride = stride; c.pad = pad; c.Hin = Hin; c.Win = Win;
     c.Hout = (Hin + 2 * pad - k) / stride + 1;
     c.Wout = (Win + 2 * pad - k) / stride + 1;
-    if (stem) { c.Kc = 64; c.ntaps = k; } else { c.Kc = Ci; c.ntaps = k * k; }
     add_tensor(p, 0, 0, (long long)Co * Ci * k * k, 4, Co, Ci, k, k, &c.w_off);
     c.bn.C = Co;
     add_tensor(p, 1, 0, Co, 1, Co, 0, 0, 0, &c.bn.w_off);
@@ -172,26 +230,8 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
     p->bucket_off[2] = stage_first_tensor_off[1]; p->bucket_numel[2] = stage_first_tensor_off[2] - stage_first_tensor_off[1];
     p->bucket_off[3] = 0; p->bucket_numel[3] = stage_first_tensor_off[1];
 
-    // ---- pack descriptors + block maps ----
-    auto push_desc = [&](const ConvInfo& c, int bucket) {
-        PackDesc d;
-        d.src_off = c.w_off; d.fwd_off = c.fwd_off; d.dgr_off = c.dgr_off; d.wg_off = c.wg_off;
-        d.Co = c.Co; d.Ci = c.Ci; d.kh = c.k; d.kw = c.k; d.Kc = c.Kc; d.ntaps = c.ntaps; d.stem = c.stem ? 1 : 0;
-        d.numel = 0;
-        const int id = (int)p->descs.size();
-        p->descs.push_back(d);
-        const long long nf = (long long)c.ntaps * c.Co * c.Kc;
-        const long long ns = (long long)c.Co * c.Ci * c.k * c.k;
-        const long long npk = nf > ns ? nf : ns;
-        // pack kernel: 32x32 (co x ci) tiles for ordinary convs, PACK_CHUNK element chunks for the stem
-        const long long npack = c.stem ? (npk + 1023) / 1024 : (long long)(c.Co / 32) * (c.Ci / 32);
-        for (long long ch = 0; ch < npack; ++ch) { p->bmap_pack.push_back(id); p->bmap_pack.push_back((int)ch); }
-        const long long uchunk = 1024;     // PACK_CHUNK of unpack_grads_kernel
-        for (long long ch = 0; ch * uchunk < ns; ++ch) {
-            p->bmap_unpack[bucket].push_back(id);
-            p->bmap_unpack[bucket].push_back((int)ch);
-        }
-    };
+    // ---- pack descriptors + block maps (push_pack_desc, build_adam_map above) ----
+    auto push_desc = [&](const ConvInfo& c, int bucket) { push_pack_desc(p->descs, p->bmap_pack, p->bmap_unpack[bucket], c); };
     push_desc(p->stem, 3);
     p->nstem_unpack_blocks = (int)p->bmap_unpack[3].size() / 2;
     for (int b = 0; b < 4; ++b) { p->bucket_wg_off[b] = -1; p->bucket_wg_numel[b] = 0; }
@@ -221,33 +261,8 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
         }
         if (at != p->wg_elems) { delete p; return fail("internal: weight-gradient scratch size mismatch"); }
     }
-    {
-        // block map of vpd_plan_adamw_step: every conv tile as in the pack map (not the stem), then the ranges
-        // of [0, nparam_padded) that are not conv weights, in 2048-float chunks (ADAM_PLAIN_CHUNK of optim.hip)
-        const int nconv = (int)p->descs.size();
-        // (descs[0] is the stem: a plain range here, packed by a 28-block pack_weights_kernel launch afterwards.  Round 4 tried ONE
-        //  block of this launch for it -- update, then the row-tap packing, which gathers across the whole tensor: its ~30 dependent
-        //  round trips under the launch's 5 TB/s of traffic made it the launch's pole, 155 vs 131 us, profiles/r04_small_folds.txt)
-        for (size_t i = 0; i + 1 < p->bmap_pack.size(); i += 2) {
-            if (p->bmap_pack[i] == 0) { p->nstem_pack_blocks++; continue; }
-            p->bmap_adam.push_back(p->bmap_pack[i]); p->bmap_adam.push_back(p->bmap_pack[i + 1]);
-        }
-        std::vector<std::pair<long long, long long>> convs;                   // (offset, numel), ascending
-        for (int i = 1; i < nconv; ++i)
-            convs.push_back({p->descs[i].src_off, (long long)p->descs[i].Co * p->descs[i].Ci * p->descs[i].kh * p->descs[i].kw});
-        std::sort(convs.begin(), convs.end());
-        long long pos = 0;
-        auto plain = [&](long long a, long long b) {
-            if (b <= a) return;
-            PackDesc d = {};
-            d.src_off = a; d.numel = b - a; d.stem = 2; d.kh = d.kw = 1; d.dgr_off = -1;
-            const int id = (int)p->descs.size();
-            p->descs.push_back(d);
-            for (long long ch = 0; ch * 2048 < b - a; ++ch) { p->bmap_adam.push_back(id); p->bmap_adam.push_back((int)ch); }
-        };
-        for (auto& cv : convs) { plain(pos, cv.first); pos = cv.first + cv.second; }
-        plain(pos, p->nparam_padded);
-    }
+    // block map of vpd_plan_adamw_step (descs[0] is the stem)
+    build_adam_map(p->descs, p->bmap_pack, 0, p->nparam_padded, p->bmap_adam, p->nstem_pack_blocks);
 
     // ---- workspace layout ----
     Bump bp;
@@ -1267,5 +1282,154 @@ extern "C" int vpd_op_wgrad128_group(int nprob, const void* const* dz, const voi
     // no schedule cache: a cache skips the upload when shapes and table ADDRESS repeat, and a test that frees its table and gets the
     // same address back from the allocator, overwritten in between, would launch on a stale task table (an illegal access)
     LCHECK(vpd_launch_wgrad128_group(qs, nprob, nullptr, dev_table, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- the reference boundary one launch at a time (optim.hip: input packing, weight repack, gradient unpack, AdamW + repack,
+// range zeroing) and the weight gradients' slab sums (conv_wgrad.hip).  The descriptors and block maps are push_pack_desc's and
+// build_adam_map's, uploaded for the one launch: the stream is synchronised before they are freed (not timing entry points) ----
+namespace {
+struct DevTables {
+    PackDesc* descs = nullptr;
+    int* bmap = nullptr;
+    ~DevTables() { (void)hipFree(descs); (void)hipFree(bmap); }
+    hipError_t upload(const std::vector<PackDesc>& d, const std::vector<int>& m, hipStream_t s) {
+        hipError_t e = hipMalloc((void**)&descs, d.size() * sizeof(PackDesc));
+        if (e == hipSuccess) e = hipMalloc((void**)&bmap, m.size() * sizeof(int));
+        if (e == hipSuccess) e = hipMemcpyAsync(descs, d.data(), d.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(bmap, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice, s);
+        return e;
+    }
+};
+inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
+// the shapes the tile kernels take: 32 x 32 (co x ci) tiles of at most 9 taps; the stem: 7 x 7 with at most 8 channels
+const char* op_conv_shape_error(int Co, int Ci, int k, int stem) {
+    if (stem != 0 && stem != 1) return "stem is 0 or 1";
+    if (stem) return (k == 7 && Ci >= 1 && Ci <= 8 && Co >= 1) ? nullptr : "the stem is 7x7 with 1..8 input channels";
+    if (Co < 32 || Co % 32 || Ci < 32 || Ci % 32) return "Co and Ci must be multiples of 32";
+    if (k < 1 || k > 3) return "k must be 1, 2 or 3";
+    return nullptr;
+}
+}  // namespace
+
+extern "C" int vpd_op_pack_input(const float* x_f32_nchw, int n, int c, int H, int W, void* out, int Hp, int Wp, int pad,
+                                 void* stream) {
+    if (!x_f32_nchw || !out) return fail("null argument");
+    if (c < 1 || c > 8) return fail("c outside 1..8");
+    if (n < 1 || H < 1 || W < 1 || pad < 0 || Hp < H + pad || Wp < W + pad) return fail("bad shape");
+    if ((long long)n * Hp * Wp >= (1ll << 31) || (long long)n * H * W >= (1ll << 31)) return fail("bad shape");
+    if (!aligned(x_f32_nchw, 4) || !aligned(out, 16)) return fail("x must be 4-byte aligned, out 16-byte aligned");
+    LCHECK(vpd_launch_pack_input(x_f32_nchw, n, c, H, W, (bf16_t*)out, Hp, Wp, pad, 8, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_pack_weights(const float* master, int Co, int Ci, int k, int stem, void* fwd_out, void* dgr_out,
+                                   void* stream) {
+    if (!master || !fwd_out) return fail("null argument");
+    if (const char* e = op_conv_shape_error(Co, Ci, k, stem)) return fail(e);
+    if (stem && dgr_out) return fail("the stem has no data-gradient layout");
+    if (!aligned(master, 4) || !aligned(fwd_out, 16) || !aligned(dgr_out, 16)) return fail("master must be 4-byte aligned, the layouts 16-byte aligned");
+    // one arena pointer, element offsets from it: the lower of the two outputs
+    bf16_t* f = (bf16_t*)fwd_out;
+    bf16_t* d = (bf16_t*)dgr_out;
+    bf16_t* arena = (d && d < f) ? d : f;
+    ConvInfo cv;
+    set_pack_geom(cv, Ci, Co, k, stem != 0);
+    cv.w_off = 0; cv.fwd_off = f - arena; cv.dgr_off = d ? d - arena : -1;
+    std::vector<PackDesc> descs;
+    std::vector<int> bmap, unused;
+    push_pack_desc(descs, bmap, unused, cv);
+    hipStream_t s = (hipStream_t)stream;
+    DevTables t;
+    HCHECK(t.upload(descs, bmap, s));
+    LCHECK(vpd_launch_pack_weights(t.descs, (int)descs.size(), t.bmap, (int)bmap.size() / 2, master, arena, s));
+    HCHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int vpd_op_unpack_grads(const float* wg, int Co, int Ci, int k, int Kc, int stem, float* grads_out, void* stream) {
+    if (!wg || !grads_out) return fail("null argument");
+    if (const char* e = op_conv_shape_error(Co, Ci, k, stem)) return fail(e);
+    if (stem ? Kc < 8 * k : Kc < Ci) return fail("Kc is too small for the scratch layout");
+    if (!aligned(wg, 4) || !aligned(grads_out, 4)) return fail("wg and grads_out must be 4-byte aligned");
+    ConvInfo cv;
+    set_pack_geom(cv, Ci, Co, k, stem != 0);
+    cv.Kc = Kc;
+    cv.w_off = 0; cv.wg_off = 0;
+    std::vector<PackDesc> descs;
+    std::vector<int> unused, bmap;
+    push_pack_desc(descs, unused, bmap, cv);
+    hipStream_t s = (hipStream_t)stream;
+    DevTables t;
+    HCHECK(t.upload(descs, bmap, s));
+    LCHECK(vpd_launch_unpack_grads(t.descs, (int)descs.size(), t.bmap, (int)bmap.size() / 2, wg, grads_out, s));
+    HCHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* offsets, long long numel, float* params,
+                                 const float* grads, float* adam_m, float* adam_v, void* arena, const float* wg, double lr,
+                                 double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
+                                 void* stream) {
+    if (!params || !grads || !adam_m || !adam_v || !arena || (nconv > 0 && (!dims3 || !offsets))) return fail("null argument");
+    if (nconv < 0 || nconv > 64) return fail("nconv outside 0..64");
+    if (numel < 4 || numel % 4) return fail("numel must be a positive multiple of 4");
+    if (step < 1) return fail("step is 1-based");
+    if (!aligned(arena, 16) || !aligned(wg, 16)) return fail("arena and wg must be 16-byte aligned");
+    std::vector<PackDesc> descs;
+    std::vector<int> bmap_pack, unused, bmap_adam;
+    long long arena_at = 0, wg_at = 0, prev_end = 0;
+    for (int i = 0; i < nconv; ++i) {
+        const int Co = dims3[3 * i], Ci = dims3[3 * i + 1], k = dims3[3 * i + 2];
+        if (const char* e = op_conv_shape_error(Co, Ci, k, 0)) return fail(e);
+        const long long ns = (long long)Co * Ci * k * k;
+        // (adamw_pack_kernel reads and writes a conv's OIHW rows 16 bytes at a time and has no unaligned fallback)
+        if (offsets[i] % 4) return fail("a conv's offset must be a multiple of 4 floats");
+        if (offsets[i] < prev_end || offsets[i] + ns > numel) return fail("conv ranges must ascend, not overlap and lie inside numel");
+        prev_end = offsets[i] + ns;
+        ConvInfo cv;
+        set_pack_geom(cv, Ci, Co, k, false);
+        cv.w_off = offsets[i];
+        cv.fwd_off = arena_at; cv.dgr_off = arena_at + ns; arena_at += 2 * ns;      // as add_conv lays the arena out
+        cv.wg_off = wg_at; wg_at += ns;
+        push_pack_desc(descs, bmap_pack, unused, cv);
+    }
+    int nstem = 0;
+    build_adam_map(descs, bmap_pack, -1, numel, bmap_adam, nstem);
+    hipStream_t s = (hipStream_t)stream;
+    DevTables t;
+    HCHECK(t.upload(descs, bmap_adam, s));
+    LCHECK(vpd_launch_adamw_pack(t.descs, t.bmap, (int)bmap_adam.size() / 2, params, grads, adam_m, adam_v, (bf16_t*)arena, lr,
+                                 beta1, beta2, eps, weight_decay, step, s, wg, gscale));
+    HCHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int vpd_op_wgrad_reduce(int nprob, const float* const* slabs, float* const* dws, const long long* nfloats,
+                                   const int* ksplits, void* stream) {
+    if (!slabs || !dws || !nfloats || !ksplits) return fail("null argument");
+    if (nprob < 1 || nprob > vpd_wgrad_reduce_max()) return fail("nprob outside 1..18");
+    for (int i = 0; i < nprob; ++i) {
+        if (!slabs[i] || !dws[i]) return fail("null argument");
+        if (nfloats[i] < 4 || nfloats[i] % 4 || ksplits[i] < 1) return fail("a problem needs a positive multiple of 4 floats and ksplit >= 1");
+        if (!aligned(slabs[i], 16) || !aligned(dws[i], 16)) return fail("slabs and dws must be 16-byte aligned");
+    }
+    LCHECK(vpd_launch_wgrad_reduce(nprob, slabs, dws, nfloats, ksplits, (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_op_zero_ranges(float* const* ptrs, const long long* n4s, int count, void* stream) {
+    if (count < 0 || count > ZR_MAX) return fail("count outside 0..16");
+    if (count == 0) return 0;
+    if (!ptrs || !n4s) return fail("null argument");
+    ZeroRanges z;
+    memset(&z, 0, sizeof z);
+    for (int i = 0; i < count; ++i) {
+        if (!ptrs[i]) return fail("null argument");
+        if (n4s[i] < 0 || !aligned(ptrs[i], 16)) return fail("ranges must be 16-byte aligned, lengths not negative");
+        z.ptr[i] = ptrs[i]; z.n4[i] = (long)n4s[i];
+    }
+    z.count = count;
+    LCHECK(vpd_launch_zero_ranges(z, (hipStream_t)stream));
     return 0;
 }
