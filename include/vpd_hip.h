@@ -206,6 +206,22 @@ int vpd_plan_bucket_scratch_range(const vpd_plan_t* plan, int bucket, long long*
 int vpd_plan_grads_pending(const vpd_plan_t* plan);
 int vpd_plan_materialize_grads(vpd_plan_t* plan, float* grads, void* workspace, void* stream);
 
+/* Frozen BatchNorm for a TRAIN plan (the reference gets it from model.eval() with grad enabled: F.batch_norm(training=False) under
+ * autograd): while on, vpd_forward_train normalises every BatchNorm with bn_running -- mean = running_mean, 1 / std =
+ * 1 / sqrt(running_var + 1e-5) -- reads bn_running (now required) and leaves it unwritten; the convolutions still add their batch
+ * sums to the plan's accumulator rows, which are consumed as always.  The forward records the mode it ran in on the plan, and
+ * vpd_backward / vpd_backward_ext of that graph use the RECORDED mode (dz = gamma / std * g; dgamma, dbeta as ever), whatever the
+ * flag says by then.  n == 0 stays legal.  Fails on the host for a null plan and for a plan with train == 0 (vpd_forward_eval runs
+ * on folded running statistics already). */
+int vpd_plan_set_bn_frozen(vpd_plan_t* plan, int on);
+
+/* Parameter gradients of vpd_backward_ext (default 1 = on).  Off: the pass computes data gradients only -- d(loss)/d(x) into
+ * dx_nchw, bit-identical to the full pass's -- and launches no weight-gradient kernel, slab sum, gradient unpack or head weight
+ * gradient.  `grads` must still be non-null (the documented refusal stays) but is not written, for n == 0 too; the BatchNorm
+ * launches store dgamma / dbeta into the plan's idle weight-gradient scratch.  bucket_events, if given, are still recorded.
+ * vpd_backward is not affected.  Works in both BatchNorm modes.  Fails for a null plan and for a plan with train == 0. */
+int vpd_plan_set_param_grads(vpd_plan_t* plan, int on);
+
 /* hipGraph-captured eval forward for a fixed batch size (apply_vpd_model.py:152-168 inner
  * loop at BATCH_SIZE crops per call).  Capture binds the pointers given here. */
 /* ---- train-time input pipeline on the device (the step right before the hot path) ----
@@ -334,12 +350,44 @@ int vpd_op_bn_forward(const void* z_bf16, const double* rows, const float* gamma
                       float* running_var, float* mean, float* rstd, float* scale, float* shift, const void* res_padded_bf16,
                       void* out_padded_bf16, unsigned char* mask_bits, int n, int H, int W, int C, int relu, float momentum,
                       float eps, void* stream);
+/* Frozen BatchNorm for the single-operator entry points (a test hook; process-wide, default off; read by these entry points
+ * only, never by a plan: vpd_plan_set_bn_frozen is the plan's switch).  While on:
+ *  vpd_op_bn_forward, vpd_op_bn_forward2, vpd_op_bn_finalize, vpd_op_conv1x1_bn / vpd_op_conv1x1_bn2 mode 1: mean = running_mean,
+ *      rstd = 1 / sqrt(running_var + eps) (the launch's own instruction), scale / shift from those; all four vectors are written
+ *      as always; running_mean / running_var are REQUIRED, read, and not written; the rows are not used (vpd_op_bn_finalize still
+ *      zeroes them)
+ *  vpd_op_bn_backward (both paths), vpd_op_bn_backward_pair, vpd_op_bn_backward_apply, vpd_op_stem_pool_backward,
+ *      vpd_op_conv1x1_bn / vpd_op_conv1x1_bn2 mode 3: dz = gamma rstd g -- the two batch-mean terms are dropped; dgamma = sum g xhat
+ *      and dbeta = sum g as always, with the mean / rstd the caller passes (the frozen forward's)
+ * Modes 0 and 2 of the streaming entry points only take sums and do not depend on it.  Returns 0. */
+int vpd_op_set_bn_frozen(int on);
+/* vpd_op_bn_forward with the BatchNorm of a down-sampling branch in the same launch (bn_fwd_fused_kernel, res_kind 2):
+ * out = relu?(BatchNorm(z) + BatchNorm2(z2)), z2 dense like z, rows2 / gamma2 / ... its own; running statistics of both
+ * BatchNorms or of neither. */
+int vpd_op_bn_forward2(const void* z_bf16, const double* rows, const float* gamma, const float* beta, float* running_mean,
+                       float* running_var, float* mean, float* rstd, float* scale, float* shift, const void* z2_bf16,
+                       const double* rows2, const float* gamma2, const float* beta2, float* running_mean2, float* running_var2,
+                       float* mean2, float* rstd2, float* scale2, float* shift2, void* out_padded_bf16, unsigned char* mask_bits,
+                       int n, int H, int W, int C, int relu, float momentum, float eps, void* stream);
+/* The finalize launch of the stem's BatchNorm and of the VPD_FUSED_BN=0 path (bn_finalize_kernel): rows f64 [16][2][C] hold the
+ * sum / sum of squares over `count` pixels and are left zeroed; writes mean, rstd (fp64 1 / sqrt), scale, shift and updates
+ * running_mean / running_var (both or neither) as vpd_op_bn_forward does. */
+int vpd_op_bn_finalize(double* rows, const float* gamma, const float* beta, float* running_mean, float* running_var, float* mean,
+                       float* rstd, float* scale, float* shift, int count, int C, float momentum, float eps, void* stream);
 /* BatchNorm backward, finalize + apply in one launch (bn_bwd_apply_fused_kernel): rows f64 [4][2][C] hold sum g and sum g * z
  * with g = dy * mask (what vpd_op_conv2d_bnsums leaves there); writes dz = gamma rstd (g - mean(g) - xhat mean(g xhat)) into
  * the bf16 NHWC tensor padded by 1, dgamma = sum g xhat, dbeta = sum g. */
 int vpd_op_bn_backward_apply(const void* dy_bf16, const void* z_bf16, const unsigned char* mask_bits, const double* rows,
                              const float* gamma, const float* mean, const float* rstd, void* dz_padded_bf16, float* dgamma,
                              float* dbeta, int n, int H, int W, int C, void* stream);
+/* The same launch for TWO BatchNorms fed with one masked gradient (bn_bwd_apply_fused_kernel<true>: the last BatchNorm of a
+ * down-sampling block and its 1x1 branch's): z2 dense like z; rows2 f64 [4][2][C] holds sum g again and sum g * z2 (as
+ * vpd_op_conv2d_bnsums2 leaves them); its own gamma2 / mean2 / rstd2 and outputs dz2_padded / dgamma2 / dbeta2. */
+int vpd_op_bn_backward_apply2(const void* dy_bf16, const void* z_bf16, const unsigned char* mask_bits, const double* rows,
+                              const float* gamma, const float* mean, const float* rstd, void* dz_padded_bf16, float* dgamma,
+                              float* dbeta, const void* z2_bf16, const double* rows2, const float* gamma2, const float* mean2,
+                              const float* rstd2, void* dz2_padded_bf16, float* dgamma2, float* dbeta2, int n, int H, int W, int C,
+                              void* stream);
 /* A Bottleneck's closing 1x1 convolution TOGETHER with its train-mode BatchNorm, the convolution recomputed in every pass
  * instead of stored (conv1x1_bn_stream_kernel and its statistics pass; models/module.py:41-47 for a Bottleneck identity block).
  * x: bf16 NHWC padded by 1 ([n][H istr + 2][W istr + 2][Kc]), w: [Co][Kc]; z = conv(x) is never written.  rows: f64 [4][2][Co].

@@ -7,7 +7,13 @@ tools/bench_loss_scale.py):
     fused     ModelTrainer's step: forward + sum-MSE + lazy backward + FusedAdamW, no torch in between
     autograd  enc(img); F.mse_loss(reduction='sum'); loss.backward(); FusedAdamW.step(); zero_grad()
     autograd+dx  the same with img.requires_grad (the stem convolution's data gradient is launched too)
-  After all are warm, regions of --steps steps alternate fused, autograd, autograd+dx, fused, ...  A region is timed with device
+    frozen       autograd+dx after freeze_bn(): BatchNorm on running statistics (the same launches, no statistics update)
+    frozen-noopt frozen without the optimizer step (backward + zero_grad only): what frozen-data is to be compared with
+    frozen-data  frozen with every parameter requires_grad_(False): d(loss)/d(img) alone (vpd_plan_set_param_grads(0): no
+                 weight-gradient launch, no optimizer step -- the gradient of a fixed student)
+  The frozen students first take --warmup train-mode steps, so that their running statistics are those of a trained network and not
+  the 0 / 1 of a fresh one (activations that vanish or blow up run at other clocks on a power-limited device).
+  After all are warm, regions of --steps steps alternate fused, autograd, autograd+dx, frozen, frozen-noopt, frozen-data, fused, ...  A region is timed with device
   events, with one synchronise at its end.  Printed: every region, the spread among the fused regions (the yardstick's own noise)
   and the differences, which count as real only where they exceed that spread.
 
@@ -48,7 +54,7 @@ def main():
     img, emb = bench.synthetic_batch(args.batch, device, seed=1, c_in=5, mean_std=RGB_MEAN_STD["diving48"], target_dim=bench.EMB_DIM)
     img_dx = img.clone().requires_grad_()
 
-    def make():
+    def make(kind="fused"):
         torch.manual_seed(0)
         enc = RGBF_EmbeddingModel("resnet34", bench.EMB_DIM, True, device)
         enc.reset_parameters(seed=0)
@@ -57,20 +63,30 @@ def main():
         enc.train()
         return enc, tr, opt
 
+    def freeze(kind, m):
+        m[0].freeze_bn()
+        if kind == "frozen-data":
+            for q in m[0].parameters():
+                q.requires_grad_(False)
+
     def run(kind, m, n):
         enc, tr, opt = m
         for _ in range(n):
             if kind == "fused":
                 step(opt, None, tr._forward_loss(img, emb, train=True))
+            elif kind in ("frozen-data", "frozen-noopt"):
+                F.mse_loss(enc(img_dx), emb, reduction="sum").backward()
+                opt.zero_grad()
+                img_dx.grad = None
             else:
-                x = img_dx if kind == "autograd+dx" else img
+                x = img if kind == "autograd" else img_dx
                 F.mse_loss(enc(x), emb, reduction="sum").backward()
                 opt.step()
                 opt.zero_grad()
                 if x.grad is not None:
                     x.grad = None
 
-    kinds = ("fused", "autograd", "autograd+dx")
+    kinds = ("fused", "autograd", "autograd+dx", "frozen", "frozen-noopt", "frozen-data")
     if args.trace_steps:
         m = make()
         run("autograd+dx", m, args.warmup)
@@ -79,8 +95,11 @@ def main():
         torch.cuda.synchronize()
         print(json.dumps({"traced_autograd_dx_steps": args.trace_steps, "stem_dgrad_launches": m[0].engine.stem_dgrad_launches}))
         return
-    ms = {k: make() for k in kinds}
+    ms = {k: make(k) for k in kinds}
     for k in kinds:
+        if k.startswith("frozen"):
+            run("autograd", ms[k], args.warmup)      # train-mode steps: realistic running statistics to freeze
+            freeze(k, ms[k])
         run(k, ms[k], args.warmup)
     torch.cuda.synchronize()
     print("box", gpu_unique_id(0))
@@ -103,6 +122,10 @@ def main():
         print("%-11s: median %.2f us/step, min %.2f, max %.2f; minus fused: %.2f us/step (%.2f %% of the fused step), which %s the fused regions' own spread"
               % (k, med(times[k]), min(times[k]), max(times[k]), d, 100 * d / med(f), "exceeds" if abs(d) > spread else "is within"))
     print("autograd+dx - autograd: %.2f us/step" % (med(times["autograd+dx"]) - med(times["autograd"])))
+    a = times["autograd+dx"]
+    n = times["frozen-noopt"]
+    print("frozen - autograd+dx: %.2f us/step (autograd+dx's own spread: %.2f us); frozen-data - frozen-noopt: %.2f us/step (frozen-noopt's own spread: %.2f us)"
+          % (med(times["frozen"]) - med(a), max(a) - min(a), med(times["frozen-data"]) - med(n), max(n) - min(n)))
     print("fused loss at the end: %.4f" % float(ms["fused"][0].engine.loss_step.item()))
     assert all(ms[k][0].engine.sync_errors() == 0 for k in kinds)
 

@@ -68,6 +68,8 @@ SIGNATURES = {
     "vpd_plan_bucket_scratch_range": (C.c_int, [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "vpd_plan_grads_pending": (C.c_int, [vp]),
     "vpd_plan_materialize_grads": (C.c_int, [vp, vp, vp, vp]),
+    "vpd_plan_set_bn_frozen": (C.c_int, [vp, C.c_int]),
+    "vpd_plan_set_param_grads": (C.c_int, [vp, C.c_int]),
     "vpd_plan_set_timing": (C.c_int, [vp, C.c_int]),
     "vpd_plan_read_timing": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int]),
     "vpd_op_conv2d": (C.c_int, [vp, vp, vp, vp] + [C.c_int] * 16 + [c_int_p, C.c_int, vp]),
@@ -77,7 +79,11 @@ SIGNATURES = {
     "vpd_op_conv2d_bnsums2": (C.c_int, [vp] * 8 + [C.c_int] * 8 + [c_int_p, vp]),
     "vpd_op_conv2d_dispatch": (C.c_int, [C.c_int] * 16 + [c_int_p, C.c_int, C.c_int, c_int_p]),
     "vpd_op_bn_forward": (C.c_int, [vp] * 13 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
+    "vpd_op_set_bn_frozen": (C.c_int, [C.c_int]),
+    "vpd_op_bn_forward2": (C.c_int, [vp] * 22 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
+    "vpd_op_bn_finalize": (C.c_int, [vp] * 9 + [C.c_int, C.c_int, C.c_float, C.c_float, vp]),
     "vpd_op_bn_backward_apply": (C.c_int, [vp] * 10 + [C.c_int] * 4 + [vp]),
+    "vpd_op_bn_backward_apply2": (C.c_int, [vp] * 18 + [C.c_int] * 4 + [vp]),
     "vpd_op_conv1x1_bn": (C.c_int, [C.c_int, vp, vp] + [C.c_int] * 6 + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 12),
     "vpd_op_conv1x1_bn2": (C.c_int, [C.c_int] + [vp] * 4 + [C.c_int] * 6 + [vp] * 18 + [C.c_float, C.c_float] + [vp] * 10),
     "vpd_op_conv1x1_bn_dispatch": (C.c_int, [C.c_int] * 6 + [c_int_p]),
@@ -136,15 +142,16 @@ def lib(dtype="bf16"):
     # name): two runtimes in one process, and the library's sees no device
     import torch  # noqa: F401
     h = C.CDLL(path)
-    # VPD_LIB_PATH (same-box A/B against an OLDER build of the library, tools/build_head_lib.sh): the operator-level test entry
+    # VPD_LIB_PATH / VPD_LIB_PATH_F16 (same-box A/B against an OLDER build of the library, tools/build_head_lib.sh): the operator-level test entry
     # points that build does not have yet are skipped; the in-tree library must export every declared symbol
-    ab_build = "VPD_LIB_PATH" in os.environ and dtype == "bf16"
+    ab_build = ("VPD_LIB_PATH" if dtype == "bf16" else "VPD_LIB_PATH_F16") in os.environ
     for sym, (res, args) in SIGNATURES.items():
         try:
             fn = getattr(h, sym)
         except AttributeError as e:
             # (an OLDER round's library, same-box A/B: the entry points added since are optional there -- engine.py asks hasattr)
-            if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext")):
+            if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext",
+                                                                 "vpd_plan_set_bn_frozen", "vpd_plan_set_param_grads")):
                 continue
             raise VpdHipError("%s lacks symbol %s declared in include/vpd_hip.h" % (name, sym)) from e
         fn.restype = res

@@ -117,9 +117,36 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(
     }
 }
 
+// Frozen BatchNorm: the running statistics in the batch statistics' place -- mean = running_mean, rstd = 1 / sqrt(running_var + eps)
+// by bn_finalize_kernel's own fp64 instruction, scale / shift from those; running_mean / running_var are read and not written.  The
+// rows are consumed (read and left zeroed) as bn_finalize_kernel consumes them: the convolution in front has added its batch sums.
+// A kernel of its own, so that bn_finalize_kernel stays the code it was.
+__global__ __launch_bounds__(64) void bn_finalize_frozen_kernel(
+    double* partials, int C, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ running_mean, const float* __restrict__ running_var, float eps,
+    float* mean, float* rstd, float* scale, float* shift) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    double s1, s2;
+    stat_rows_take(partials, C, c, &s1, &s2);
+    const float mu = running_mean[c];
+    const float r = (float)(1.0 / sqrt((double)running_var[c] + (double)eps));
+    const float sc = gamma[c] * r;
+    mean[c] = mu;
+    rstd[c] = r;
+    scale[c] = sc;
+    shift[c] = __builtin_fmaf(-mu, sc, beta[c]);
+}
+
 hipError_t vpd_launch_bn_finalize(double* partials, int T, int C, float count, const float* gamma,
                                   const float* beta, float* rm, float* rv, float momentum, float eps,
-                                  float* mean, float* rstd, float* scale, float* shift, hipStream_t s) {
+                                  float* mean, float* rstd, float* scale, float* shift, hipStream_t s, bool frozen) {
+    if (frozen) {
+        if (!rm || !rv) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(bn_finalize_frozen_kernel, dim3((C + 63) / 64), dim3(64), 0, s, partials, C, gamma, beta, rm, rv, eps,
+                           mean, rstd, scale, shift);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, s, partials, T, C, count, gamma,
                        beta, rm, rv, momentum, eps, mean, rstd, scale, shift);
     return hipGetLastError();
@@ -387,9 +414,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const BnBwdParams p)
 }
 
 // pass 1b: partials -> dgamma, dbeta (fp32 grads) and the apply coefficients
+// frozen (the forward normalised with running statistics): mean and rstd are constants, so c2 = c3 = 0 and dz = c1 g; dgamma and
+// dbeta are the same sums.  (Cross-check: count = +inf in the two divisions below gives the same.)
 __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(
     double* partials, int T, int C, float count, const float* __restrict__ gamma,
-    const float* __restrict__ rstd, float* dgamma, float* dbeta, float* coef) {
+    const float* __restrict__ rstd, float* dgamma, float* dbeta, float* coef, int frozen) {
     (void)T;
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= C) return;
@@ -398,8 +427,8 @@ __global__ __launch_bounds__(64) void bn_bwd_finalize_kernel(
     dbeta[c] = (float)s1;
     dgamma[c] = (float)s2;
     coef[c] = gamma[c] * rstd[c];
-    coef[C + c] = (float)(s1 / (double)count);
-    coef[2 * C + c] = (float)(s2 / (double)count);
+    coef[C + c] = frozen ? 0.f : (float)(s1 / (double)count);
+    coef[2 * C + c] = frozen ? 0.f : (float)(s2 / (double)count);
 }
 
 // pass 2: dz = c1 * (g - c2 - xhat * c3); optionally write g back over dy
@@ -448,7 +477,7 @@ int vpd_bn_bwd_blocks(int M, int C, int* ppb_out) {
 }
 
 hipError_t vpd_launch_bn_bwd(const BnBwdParams& p0, float count, const float* gamma, float* dgamma, float* dbeta,
-                             hipStream_t s, bool reduce_done) {
+                             hipStream_t s, bool reduce_done, bool frozen) {
     BnBwdParams p = p0;
     if (p.C % 8 || p.C > 2048 || 256 % (p.C / 8)) return hipErrorInvalidValue;
     const int T = vpd_bn_bwd_blocks(p.M, p.C, &p.ppb);
@@ -461,7 +490,7 @@ hipError_t vpd_launch_bn_bwd(const BnBwdParams& p0, float count, const float* ga
     }
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((p.C + 63) / 64), dim3(64), 0, s, p.partials,
                        VPD_STAT_ROWS, p.C, count,
-                       gamma, p.rstd, dgamma, dbeta, p.coef);
+                       gamma, p.rstd, dgamma, dbeta, p.coef, frozen ? 1 : 0);
     const dim3 ag(ew_grid((long)p.M * (p.C / 8)));
     if (mask == 1 && p.write_g) hipLaunchKernelGGL((bn_bwd_apply_kernel<1, 1>), ag, dim3(256), 0, s, p);
     else if (mask == 1) hipLaunchKernelGGL((bn_bwd_apply_kernel<1, 0>), ag, dim3(256), 0, s, p);
@@ -671,7 +700,7 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_sums_kernel(const StemPoolB
 }
 
 hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p0, float count, const float* gamma, float* dgamma,
-                                    float* dbeta, float* coef, bf16_t* dz, hipStream_t s) {
+                                    float* dbeta, float* coef, bf16_t* dz, hipStream_t s, bool frozen) {
     // Two passes over (d_pool, argmax, z): pass 1 = the BN-backward sums of g (max-pool routing + ReLU mask, never
     // materialised); finalize; pass 2 recomputes g and writes dz.  Saves writing and re-reading the 134 MB g tensor.
     StemPoolBwdParams p = p0;
@@ -688,7 +717,7 @@ hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p0, float count, co
     }
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((p.C + 63) / 64), dim3(64), 0, s, p.partials,
                        VPD_STAT_ROWS, p.C, count,
-                       gamma, p.rstd, dgamma, dbeta, coef);
+                       gamma, p.rstd, dgamma, dbeta, coef, frozen ? 1 : 0);
     p.pass = 2;
     if (vpd_switches().stem_quad && !(p.Hz & 1) && !(p.Wz & 1) && p.Ho == p.Hz / 2 && p.Wo == p.Wz / 2) {
         const int per = 256 / (p.C / 8);
@@ -757,6 +786,9 @@ struct BnFusedFwdArgs {
     int xcd_r;                                 // vpd_bn_virtual_block
 };
 
+// FROZEN (BnFusedFwd::frozen): both BatchNorms normalise with rm / rv, read only, instead of their rows.  An instantiation, not a
+// kernel argument: the launch is at its scalar-register limit, and <false> is the kernel it was, instruction for instruction.
+template <bool FROZEN>
 __global__ __launch_bounds__(1024) void bn_fwd_fused_kernel(const BnApplyParams p, const BnFusedFwdArgs f) {
     extern __shared__ float sm[];                      // scale[C] shift[C] (rscale[C] rshift[C])
     const int C = p.C;
@@ -803,22 +835,22 @@ __global__ __launch_bounds__(1024) void bn_fwd_fused_kernel(const BnApplyParams 
     if (have) load_item(it, zc, rc, oo, c);
     for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
         float mu, r, sc, sh; double var;
-        bn_finalize_channel(f.rows, C, ch, f.count, f.eps, f.gamma[ch], f.beta[ch], &mu, &r, &sc, &sh, &var);
+        bn_finalize_channel(f.rows, C, ch, f.count, f.eps, f.gamma[ch], f.beta[ch], &mu, &r, &sc, &sh, &var, FROZEN, f.rm, f.rv);
         s_sc[ch] = sc; s_sh[ch] = sh;
         if (blockIdx.x == 0) {
             f.mean[ch] = mu; f.rstd[ch] = r; f.scale[ch] = sc; f.shift[ch] = sh;
-            if (f.rm) {
+            if (f.rm && !FROZEN) {
                 const double unb = f.count > 1.f ? var * (double)f.count / ((double)f.count - 1.0) : var;
                 f.rm[ch] = (1.f - f.momentum) * f.rm[ch] + f.momentum * mu;
                 f.rv[ch] = (1.f - f.momentum) * f.rv[ch] + f.momentum * (float)unb;
             }
         }
         if (f.rows2) {
-            bn_finalize_channel(f.rows2, C, ch, f.count2, f.eps, f.gamma2[ch], f.beta2[ch], &mu, &r, &sc, &sh, &var);
+            bn_finalize_channel(f.rows2, C, ch, f.count2, f.eps, f.gamma2[ch], f.beta2[ch], &mu, &r, &sc, &sh, &var, FROZEN, f.rm2, f.rv2);
             s_rsc[ch] = sc; s_rsh[ch] = sh;
             if (blockIdx.x == 0) {
                 f.mean2[ch] = mu; f.rstd2[ch] = r; f.scale2[ch] = sc; f.shift2[ch] = sh;
-                if (f.rm2) {
+                if (f.rm2 && !FROZEN) {
                     const double unb = f.count2 > 1.f ? var * (double)f.count2 / ((double)f.count2 - 1.0) : var;
                     f.rm2[ch] = (1.f - f.momentum) * f.rm2[ch] + f.momentum * mu;
                     f.rv2[ch] = (1.f - f.momentum) * f.rv2[ch] + f.momentum * (float)unb;
@@ -896,6 +928,7 @@ __global__ __launch_bounds__(1024) void bn_fwd_fused_kernel(const BnApplyParams 
 
 hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f0, hipStream_t s) {
     if (p.C % 8 || p.C > 4096) return hipErrorInvalidValue;
+    if (f0.frozen && (!f0.rm || !f0.rv || (f0.rows2 && (!f0.rm2 || !f0.rv2)))) return hipErrorInvalidValue;
     BnFusedFwdArgs f;
     f.rows = f0.rows; f.count = f0.count; f.gamma = f0.gamma; f.beta = f0.beta; f.rm = f0.rm; f.rv = f0.rv;
     f.mean = f0.mean; f.rstd = f0.rstd; f.scale = f0.scale; f.shift = f0.shift;
@@ -912,7 +945,8 @@ hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f0,
 #ifdef VPD_ENABLE_ABLATE      // tools/bench_bn_chain.py: the operator-level entry point knows no neighbouring convolution
     if (vpd_switches().bn_xcd_force >= 0) f.xcd_r = vpd_bn_xcd_r(vpd_switches().bn_xcd_force, p.C, (int)g);
 #endif
-    hipLaunchKernelGGL(bn_fwd_fused_kernel, dim3((unsigned)g), dim3(1024), (size_t)4 * p.C * sizeof(float), s, p, f);
+    if (f0.frozen) hipLaunchKernelGGL(bn_fwd_fused_kernel<true>, dim3((unsigned)g), dim3(1024), (size_t)4 * p.C * sizeof(float), s, p, f);
+    else hipLaunchKernelGGL(bn_fwd_fused_kernel<false>, dim3((unsigned)g), dim3(1024), (size_t)4 * p.C * sizeof(float), s, p, f);
     return hipGetLastError();
 }
 
@@ -927,6 +961,7 @@ struct BnFusedBwdArgs {
     const float* gamma[NB]; float* dgamma[NB]; float* dbeta[NB];
     const bf16_t* z[NB]; const float* mean[NB]; const float* rstd[NB];
     bf16_t* dz[NB];                            // all in the padded geometry of p.dz
+    int frozen;                                // the forward used running statistics: c2 = c3 = 0 (every BatchNorm of the launch)
 };
 
 // The body of bn_bwd_fused_kernel<MASK, WRITE_G> (NB = 1) and of bn_bwd_fused2_kernel (<1, 0, 2>): K = 1 + NB sums per channel
@@ -1054,7 +1089,8 @@ static __device__ __forceinline__ void bn_bwd_fused_body(const BnBwdParams& p, c
 #pragma unroll
         for (int r = 0; r < VPD_FUSED_ROWS; ++r)
             s += __hip_atomic_load(&rows[((size_t)r * 2 + slot) * C + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        red[t] = (float)(s / (double)f.count);
+        // (frozen: mean and rstd are constants of the forward, the two mean terms are gone -- as count = +inf would make them)
+        red[t] = f.frozen ? 0.f : (float)(s / (double)f.count);
         if (blockIdx.x == 0) {
             if (which == 0) {
 #pragma unroll
@@ -1121,6 +1157,7 @@ struct BnBwdApplyArgs {
     const double* rows2; const float* gamma2; const float* mean2; const float* rstd2; float* dgamma2; float* dbeta2;
     const bf16_t* z2; bf16_t* dz2;
     int xcd_r;                                 // vpd_bn_virtual_block
+    int frozen;                                // bn_bwd_apply_coef: B = D = 0 (both BatchNorms)
 };
 template <bool PAIR>
 __global__ __launch_bounds__(1024) void bn_bwd_apply_fused_kernel(const BnBwdParams p, const BnBwdApplyArgs f) {
@@ -1165,10 +1202,10 @@ __global__ __launch_bounds__(1024) void bn_bwd_apply_fused_kernel(const BnBwdPar
     if (have) load_item(it, gc, zc, z2c, bc, oo, c);
     for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
         bn_bwd_apply_coef(f.rows, C, ch, f.count, f.gamma[ch], f.mean[ch], f.rstd[ch], sA, sB, sD, f.dgamma, f.dbeta,
-                          blockIdx.x == 0);
+                          blockIdx.x == 0, -1, f.frozen);
         if (PAIR)
             bn_bwd_apply_coef(f.rows2, C, ch, f.count, f.gamma2[ch], f.mean2[ch], f.rstd2[ch], sA + 3 * C, sB + 3 * C,
-                              sD + 3 * C, f.dgamma2, f.dbeta2, blockIdx.x == 0);
+                              sD + 3 * C, f.dgamma2, f.dbeta2, blockIdx.x == 0, -1, f.frozen);
     }
     __syncthreads();
     // fast path: the stride (grid x 1024) is a multiple of C / 8 -- a thread's channel slice, and with it its 24 (48) coefficients, is
@@ -1222,7 +1259,7 @@ hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd&
     BnBwdApplyArgs f;
     f = BnBwdApplyArgs{};
     f.rows = f0.rows; f.count = f0.count; f.gamma = f0.gamma; f.mean = p.mean; f.rstd = p.rstd;
-    f.dgamma = f0.dgamma; f.dbeta = f0.dbeta;
+    f.dgamma = f0.dgamma; f.dbeta = f0.dbeta; f.frozen = f0.frozen;
     const long items = (long)p.M * (p.C / 8);
     long g = (items + 1023) / 1024;
     if (g > 256) g = 256;      // (one 1024-thread block per CU: same-box -10 us per step against two; 192 or fewer: +110 us)
@@ -1272,7 +1309,7 @@ bool vpd_bn_bwd_fused2_ok(int M, int C) {
 template <int NB>
 static BnFusedBwdArgs<NB> bn_bwd_fused_args(const BnBwdParams& p, const BnFusedBwd& fA, const BnBwdSecond* B, const BnBwdFusedGeom& geo) {
     BnFusedBwdArgs<NB> f;
-    f.sync = reinterpret_cast<GridSync*>(fA.sync); f.err = fA.err; f.count = fA.count;
+    f.sync = reinterpret_cast<GridSync*>(fA.sync); f.err = fA.err; f.count = fA.count; f.frozen = fA.frozen;
     f.iters = geo.iters;
     f.keep_g = geo.keep[0];
     for (int n = 0; n < NB; ++n) {

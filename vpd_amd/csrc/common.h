@@ -200,10 +200,14 @@ struct ConvParams {
 };
 
 // One channel of a train-mode BatchNorm from its fp64 accumulator rows [VPD_FUSED_ROWS][2][C] (sum z, sum z^2): mean, 1 / std,
-// scale = gamma / std, shift = beta - mean * scale (bn_fwd_fused_kernel)
+// scale = gamma / std, shift = beta - mean * scale (bn_fwd_fused_kernel).
+// frozen: the BatchNorm normalises with its running statistics instead -- mean = rm[ch], 1 / std from rv[ch] + eps by the same
+// v_rsq_f32, scale / shift from those -- and the caller leaves rm / rv unwritten.  The batch values are formed first and then replaced
+// (a few dozen instructions per channel, once per block): the unfrozen path stays the code it was, registers included.
 static __device__ __forceinline__ void bn_finalize_channel(const double* rows, int C, int ch, float count, float eps,
                                                            float gamma, float beta, float* mu_o, float* r_o, float* sc_o,
-                                                           float* sh_o, double* var_o) {
+                                                           float* sh_o, double* var_o, int frozen = 0, const float* rm = nullptr,
+                                                           const float* rv = nullptr) {
     double s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int t = 0; t < VPD_FUSED_ROWS; ++t) {
@@ -219,15 +223,26 @@ static __device__ __forceinline__ void bn_finalize_channel(const double* rows, i
     var = var > 0.0 ? var : 0.0;
     const float r = __builtin_amdgcn_rsqf((float)(var + (double)eps));
     const float sc = gamma * r;
-    *mu_o = (float)mu; *r_o = r; *sc_o = sc; *sh_o = beta - (float)mu * sc; *var_o = var;
+    // (the fma written out: it is what the compiler made of beta - mean * scale while this function had one path, and what it stopped
+    //  making of it with two -- the last bit of shift, and with it of every activation, must not depend on that)
+    *mu_o = (float)mu; *r_o = r; *sc_o = sc; *sh_o = __builtin_fmaf(-(float)mu, sc, beta); *var_o = var;
+    if (frozen) {
+        const float fmu = rm[ch];
+        const double fvar = (double)rv[ch];
+        const float fr = __builtin_amdgcn_rsqf((float)(fvar + (double)eps));
+        const float fsc = gamma * fr;
+        *mu_o = fmu; *r_o = fr; *sc_o = fsc; *sh_o = __builtin_fmaf(-fmu, fsc, beta); *var_o = fvar;
+    }
 }
 
 // One channel of a BatchNorm backward whose sums (sum g, sum g * z; g = dy * ReLU mask) sit in its fp64 rows [VPD_FUSED_ROWS][2][C]:
 // dz = A g + B z + D with A = gamma rstd, B = -A rstd mean(g xhat), D = -A mean(g) - B mean; dgamma = sum g xhat, dbeta = sum g
 // (bn_bwd_apply_fused_kernel, conv1x1_bn_stream_kernel).
+// frozen: mean / rstd are constants of the forward (running statistics), so the two mean terms drop out: B = D = 0, dz = A g;
+// dgamma / dbeta are the same sums.  (Cross-check: it is what count = +inf gives in the formulas above.)
 static __device__ __forceinline__ void bn_bwd_apply_coef(const double* rows, int C, int ch, float count, float gamma, float mean,
                                                          float rstd, float* A, float* B, float* D, float* dgamma, float* dbeta,
-                                                         bool write, int oi = -1) {
+                                                         bool write, int oi = -1, int frozen = 0) {
     if (oi < 0) oi = ch;                                           // A / B / D are indexed by oi (default: the channel)
     double s1 = 0.0, sz = 0.0;
 #pragma unroll
@@ -239,8 +254,8 @@ static __device__ __forceinline__ void bn_bwd_apply_coef(const double* rows, int
     const double sx = (sz - mu * s1) * rs;                         // sum g * xhat
     const double a = (double)gamma * rs;
     const double b = -a * rs * (sx / (double)count);
-    A[oi] = (float)a; B[oi] = (float)b;
-    D[oi] = (float)(-a * (s1 / (double)count) - b * mu);
+    A[oi] = (float)a; B[oi] = frozen ? 0.f : (float)b;
+    D[oi] = frozen ? 0.f : (float)(-a * (s1 / (double)count) - b * mu);
     if (write) { dbeta[ch] = (float)s1; dgamma[ch] = (float)sx; }
 }
 // Pixel-chunk split of the halo weight-gradient kernel (64-pixel chunks): shared by the launcher and by the

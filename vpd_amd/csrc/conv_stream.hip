@@ -316,6 +316,7 @@ struct StreamBn {
     float count, momentum, eps;
     unsigned char* mask_out;                               // MODE 1: ReLU bit map [M][Co / 8] (may be null)
     int dzHp, dzWp, dzpad;                                 // MODE 3: geometry of every side's dz
+    int frozen;                                            // MODE 1: mean / rstd from rm / rv (read only); MODE 3: B = D = 0 (every side)
     StreamBnSide s;                                        // the closing convolution's BatchNorm
 };
 
@@ -324,11 +325,11 @@ struct StreamBn {
 static __device__ __forceinline__ void stream_bn_finalize(const StreamBnSide& s, const StreamBn& bn, int Co, int ch, float* coef_scale,
                                                           float* coef_shift) {
     float mu, r, sc, sh; double var;
-    bn_finalize_channel(s.rows, Co, ch, bn.count, bn.eps, s.gamma[ch], s.beta[ch], &mu, &r, &sc, &sh, &var);
+    bn_finalize_channel(s.rows, Co, ch, bn.count, bn.eps, s.gamma[ch], s.beta[ch], &mu, &r, &sc, &sh, &var, bn.frozen, s.rm, s.rv);
     *coef_scale = sc; *coef_shift = sh;
     if (blockIdx.x == 0) {
         s.mean[ch] = mu; s.rstd[ch] = r; s.scale[ch] = sc; s.shift[ch] = sh;
-        if (s.rm) {
+        if (s.rm && !bn.frozen) {
             const double unb = bn.count > 1.f ? var * (double)bn.count / ((double)bn.count - 1.0) : var;
             s.rm[ch] = (1.f - bn.momentum) * s.rm[ch] + bn.momentum * mu;
             s.rv[ch] = (1.f - bn.momentum) * s.rv[ch] + bn.momentum * (float)unb;
@@ -339,7 +340,7 @@ static __device__ __forceinline__ void stream_bn_finalize(const StreamBnSide& s,
 template <int BN>
 static __device__ __forceinline__ void stream_bn_bwd_coef(const StreamBnSide& s, const StreamBn& bn, int Co, int ch, float* coef, int i) {
     bn_bwd_apply_coef(s.rows, Co, ch, bn.count, s.gamma[ch], s.mean[ch], s.rstd[ch], coef, coef + BN, coef + 2 * BN, s.dgamma, s.dbeta,
-                      blockIdx.x == 0, i);
+                      blockIdx.x == 0, i, bn.frozen);
 }
 
 // ---- a lane's four channels of one group ----
@@ -791,12 +792,15 @@ hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, con
         if (!p.stats || p.stat_rows != VPD_FUSED_ROWS) return hipErrorInvalidValue;
     } else if (mode == 1) {
         if (!fwd || !p.res || !p.y || p.ypad != 1 || p.yC != p.Co || p.rC != p.Co) return hipErrorInvalidValue;
+        if (fwd->frozen && (!fwd->rm || !fwd->rv)) return hipErrorInvalidValue;
         bn = stream_bn(fwd->count, fwd->momentum, fwd->eps, mask_out, p, 0);
+        bn.frozen = fwd->frozen;
         bn.s = stream_side_fwd(fwd->rows, fwd->gamma, fwd->beta, fwd->mean, fwd->rstd, fwd->scale, fwd->shift, fwd->rm, fwd->rv);
     } else {
         if (!bwd || !stream_bwd_operands(p)) return hipErrorInvalidValue;
         if (mode == 3 && (!dz || !mean || !rstd)) return hipErrorInvalidValue;
         bn = stream_bn(bwd->count, 0.f, 0.f, nullptr, p, dzpad);
+        bn.frozen = bwd->frozen;
         bn.s = stream_side_bwd(*bwd, mean, rstd, dz, mode);
     }
     if (p.Kc == 64) return launch_bn_stream<64, BN_NSA_K64>(p, bn, mode, stream);
@@ -820,13 +824,16 @@ hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, co
     StreamBnSide bd;
     if (mode == 1) {
         if (!fwd || !fwd->rows2 || !p.y || p.ypad != 1 || p.yC != p.Co) return hipErrorInvalidValue;
+        if (fwd->frozen && (!fwd->rm || !fwd->rv || !fwd->rm2 || !fwd->rv2)) return hipErrorInvalidValue;
         bn = stream_bn(fwd->count, fwd->momentum, fwd->eps, mask_out, p, 0);
+        bn.frozen = fwd->frozen;
         bn.s = stream_side_fwd(fwd->rows, fwd->gamma, fwd->beta, fwd->mean, fwd->rstd, fwd->scale, fwd->shift, fwd->rm, fwd->rv);
         bd = stream_side_fwd(fwd->rows2, fwd->gamma2, fwd->beta2, fwd->mean2, fwd->rstd2, fwd->scale2, fwd->shift2, fwd->rm2, fwd->rv2);
     } else if (mode == 2 || mode == 3) {
         if (!bwd3 || !bwdD || !stream_bwd_operands(p)) return hipErrorInvalidValue;
         if (mode == 3 && (!dz3 || !dzD || !mean3 || !rstd3 || !meanD || !rstdD)) return hipErrorInvalidValue;
         bn = stream_bn(bwd3->count, 0.f, 0.f, nullptr, p, dzpad);
+        bn.frozen = bwd3->frozen;
         bn.s = stream_side_bwd(*bwd3, mean3, rstd3, dz3, mode);
         bd = stream_side_bwd(*bwdD, meanD, rstdD, dzD, mode);
     } else return hipErrorInvalidValue;

@@ -127,18 +127,20 @@ void vpd_wgrad128_cache_free(void* cache);
 hipError_t vpd_launch_wgrad128_group(const WgradParams* ps, int n, void* cache, void* dev_table, hipStream_t stream);
 bool vpd_wgrad_halo_shape_ok(int Hout, int Wout, int stride = 1, int Hin = 0, int Win = 0);
 
+// frozen (vpd_launch_bn_finalize, vpd_launch_bn_bwd, vpd_launch_stem_pool_bwd): the BatchNorm runs on its running statistics --
+// forward: mean / rstd from rm / rv, which are not written; backward: c2 = c3 = 0
 hipError_t vpd_launch_bn_finalize(double* partials, int T, int C, float count, const float* gamma,
                                   const float* beta, float* rm, float* rv, float momentum, float eps,
-                                  float* mean, float* rstd, float* scale, float* shift, hipStream_t s);
+                                  float* mean, float* rstd, float* scale, float* shift, hipStream_t s, bool frozen = false);
 hipError_t vpd_launch_bn_fold(const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
                               float* scale, float* shift, int C, hipStream_t s);
 hipError_t vpd_launch_bn_apply(const BnApplyParams& p, hipStream_t s);
 hipError_t vpd_launch_stem_pool(const StemPoolParams& p, hipStream_t s);
 int vpd_bn_bwd_blocks(int M, int C, int* ppb_out);
 hipError_t vpd_launch_bn_bwd(const BnBwdParams& p, float count, const float* gamma, float* dgamma, float* dbeta,
-                             hipStream_t s, bool reduce_done = false);
+                             hipStream_t s, bool reduce_done = false, bool frozen = false);
 hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p, float count, const float* gamma, float* dgamma,
-                                    float* dbeta, float* coef, bf16_t* dz, hipStream_t s);
+                                    float* dbeta, float* coef, bf16_t* dz, hipStream_t s, bool frozen = false);
 
 // fused BatchNorm passes (bn.hip): per-BatchNorm accumulator rows [VPD_FUSED_ROWS][2][C] of doubles, zeroed by the caller
 struct BnFusedFwd {
@@ -147,10 +149,16 @@ struct BnFusedFwd {
     double* rows2; float count2; const float* gamma2; const float* beta2; float* rm2; float* rv2;      // residual BN or null
     float* mean2; float* rstd2; float* scale2; float* shift2;
     float momentum, eps;
+    // frozen BatchNorm: mean = rm, rstd = 1 / sqrt(rv + eps) (both BatchNorms; rm / rv are then required, read and left unwritten);
+    // mean / rstd / scale / shift are stored as always, so the backward's masks and xhat see what the forward used
+    int frozen;
 };
 struct BnFusedBwd {
     double* rows; void* sync; unsigned* err;    // sync: VPD_GRID_SYNC_BYTES, zeroed; err: sticky time-out counter
     const float* gamma; float* dgamma; float* dbeta; float count;
+    // the forward was frozen: dz = gamma rstd g (the batch-mean terms drop out), dgamma / dbeta unchanged.  A launch that serves
+    // two BatchNorms takes the first one's flag for both
+    int frozen;
 };
 // the second BatchNorm of a launch that serves two with the same masked gradient (a down-sampling block's 1x1 branch): same
 // shape as the first, dz in the same padded geometry; f.sync / err / count are not read (the first BatchNorm's serve the launch)

@@ -32,6 +32,7 @@ struct BnInfo {
     size_t fl_off = 0;                   // float scratch in ws: mean,rstd,scale,shift,coef[3],escale,eshift (9C)
     size_t rows_off = 0;                 // fused passes: this BatchNorm's own accumulator rows [VPD_FUSED_ROWS][2][C] doubles
     size_t sync_off = 0;                 // ... and the grid-barrier words of its fused backward launch
+    long long sink_off = 0;              // data-only backward: this BatchNorm's [2][C] floats (dgamma, dbeta) in the weight-gradient scratch
 };
 struct ConvInfo {
     int Ci = 0, Co = 0, k = 0, stride = 1, pad = 0;
@@ -119,6 +120,10 @@ struct vpd_plan {
     bool dgrad_sums = true;     // BatchNorm-backward sums in the producing data gradient's epilogue (VPD_DGRAD_SUMS=0: in the BatchNorm launch)
     bool relu_bits = true;      // block-output ReLU masks as bit maps (VPD_RELU_BITS=0: masks from the stored activation, g written back)
     bool lazy_next = false, grads_in_scratch = false;
+    // frozen BatchNorm (vpd_plan_set_bn_frozen): vpd_forward_train normalises with the running statistics and leaves them alone.
+    // fwd_bn_frozen is the mode the last forward RAN in: the backward of that graph reads it, not the current flag
+    bool bn_frozen = false, fwd_bn_frozen = false;
+    bool param_grads = true;    // vpd_plan_set_param_grads(0): vpd_backward_ext computes data gradients only and leaves `grads` alone
     bool fwd_had_x = false;     // the last vpd_forward_train took an fp32 x (vpd_backward_ext: an input gradient exists only then)
     int nstem_unpack_blocks = 0;           // leading entries of bmap_unpack[3] that belong to the stem
     bool wg_merge34 = true;     // layer4's grouped weight gradients wait for layer3's and share its launch (VPD_WG_MERGE=0, or the

@@ -210,6 +210,12 @@ extern "C" int vpd_plan_create(const char* arch, int c_in, int img_h, int img_w,
         if (bottleneck) p->bns.push_back(&B.c3.bn);
         if (B.ds) p->bns.push_back(&B.cd.bn);
     }
+    // data-only backward (vpd_plan_set_param_grads): every BatchNorm's dgamma / dbeta land in [2][C] floats of its own at the front of
+    // the weight-gradient scratch (each BatchNorm follows a convolution with more than 2 weights per output channel: it fits)
+    {
+        long long at = 0;
+        for (BnInfo* b : p->bns) { b->sink_off = at; at += 2LL * b->C; }
+    }
     if (h < 1 || w < 1) { delete p; return fail("image too small for 5 stride-2 stages"); }
     stage_first_tensor_off[4] = p->nparam;
     p->fc.in = p->feat; p->fc.out = emb_dim;
@@ -743,6 +749,18 @@ extern "C" int vpd_plan_set_lazy_grads(vpd_plan_t* p, int on) {
     p->lazy_next = on != 0;
     return 0;
 }
+extern "C" int vpd_plan_set_bn_frozen(vpd_plan_t* p, int on) {
+    if (!p) return fail("null plan");
+    if (!p->train) return fail("vpd_plan_set_bn_frozen: plan was created with train=0 (an inference plan folds the running statistics already)");
+    p->bn_frozen = on != 0;
+    return 0;
+}
+extern "C" int vpd_plan_set_param_grads(vpd_plan_t* p, int on) {
+    if (!p) return fail("null plan");
+    if (!p->train) return fail("vpd_plan_set_param_grads: plan was created with train=0");
+    p->param_grads = on != 0;
+    return 0;
+}
 extern "C" int vpd_plan_grads_pending(const vpd_plan_t* p) { return p && p->grads_in_scratch ? 1 : 0; }
 extern "C" int vpd_plan_materialize_grads(vpd_plan_t* p, float* grads, void* workspace, void* stream) {
     if (!p || !grads || !workspace) return fail("null argument");
@@ -798,6 +816,10 @@ extern "C" int vpd_plan_read_timing(vpd_plan_t* p, double* out, int nclasses) {
 // ---------------------------------------------------------------------------
 // single-operator entry points for the parity tests
 // ---------------------------------------------------------------------------
+// frozen BatchNorm for the BatchNorm entry points below (vpd_op_set_bn_frozen): process-wide, read by them alone -- no plan looks here
+static int g_op_bn_frozen = 0;
+extern "C" int vpd_op_set_bn_frozen(int on) { g_op_bn_frozen = on != 0; return 0; }
+
 extern "C" int vpd_op_conv_bm(int M, int Co) { return vpd_conv_bm(M, Co); }
 extern "C" size_t vpd_op_wgrad_slab_bytes(void) { return vpd_wgrad_slab_bytes(); }
 
@@ -927,7 +949,55 @@ extern "C" int vpd_op_bn_forward(const void* z, const double* rows, const float*
     memset(&f, 0, sizeof f);
     f.rows = const_cast<double*>(rows); f.count = (float)a.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
     f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift; f.momentum = momentum; f.eps = eps;
+    f.frozen = g_op_bn_frozen;
+    if (f.frozen && (!running_mean || !running_var)) return fail("a frozen BatchNorm needs running_mean and running_var");
     LCHECK(vpd_launch_bn_fwd_fused(a, f, (hipStream_t)stream));
+    return 0;
+}
+
+// ... with the BatchNorm of a down-sampling branch in the same launch (res_kind 2): out = relu?(BatchNorm(z) + BatchNorm2(z2)), z2
+// dense like z, no ReLU of its own.  Both BatchNorms take the hook's mode; running statistics of both or of neither.
+extern "C" int vpd_op_bn_forward2(const void* z, const double* rows, const float* gamma, const float* beta, float* running_mean,
+                                  float* running_var, float* mean, float* rstd, float* scale, float* shift, const void* z2,
+                                  const double* rows2, const float* gamma2, const float* beta2, float* running_mean2,
+                                  float* running_var2, float* mean2, float* rstd2, float* scale2, float* shift2, void* out,
+                                  unsigned char* mask_bits, int n, int H, int W, int C, int relu, float momentum, float eps,
+                                  void* stream) {
+    if (!z || !rows || !gamma || !beta || !mean || !rstd || !scale || !shift || !out || !z2 || !rows2 || !gamma2 || !beta2 || !mean2 ||
+        !rstd2 || !scale2 || !shift2)
+        return fail("null argument");
+    const int nrun = (running_mean != nullptr) + (running_var != nullptr) + (running_mean2 != nullptr) + (running_var2 != nullptr);
+    if (nrun != 0 && nrun != 4) return fail("running statistics of both BatchNorms or of neither");
+    if (g_op_bn_frozen && nrun != 4) return fail("a frozen BatchNorm needs running_mean and running_var");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
+    BnApplyParams a;
+    memset(&a, 0, sizeof a);
+    a.z = (const bf16_t*)z;
+    a.res_kind = 2; a.res = (const bf16_t*)z2; a.rHp = H + 2; a.rWp = W + 2; a.rpad = 1;
+    a.out = (bf16_t*)out; a.oHp = H + 2; a.oWp = W + 2; a.opad = 1;
+    a.M = n * H * W; a.H = H; a.W = W; a.C = C; a.relu = relu; a.mask_out = mask_bits;
+    BnFusedFwd f;
+    memset(&f, 0, sizeof f);
+    f.rows = const_cast<double*>(rows); f.count = (float)a.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
+    f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift;
+    f.rows2 = const_cast<double*>(rows2); f.count2 = (float)a.M; f.gamma2 = gamma2; f.beta2 = beta2; f.rm2 = running_mean2; f.rv2 = running_var2;
+    f.mean2 = mean2; f.rstd2 = rstd2; f.scale2 = scale2; f.shift2 = shift2;
+    f.momentum = momentum; f.eps = eps; f.frozen = g_op_bn_frozen;
+    LCHECK(vpd_launch_bn_fwd_fused(a, f, (hipStream_t)stream));
+    return 0;
+}
+
+// the stem's and the VPD_FUSED_BN=0 path's finalize launch (bn_finalize_kernel) on the shared rows [VPD_STAT_ROWS][2][C], which it
+// zeroes: mean / rstd / scale / shift, and the running statistics -- updated, or under the hook read and left alone
+extern "C" int vpd_op_bn_finalize(double* rows, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                                  float* mean, float* rstd, float* scale, float* shift, int count, int C, float momentum, float eps,
+                                  void* stream) {
+    if (!rows || !gamma || !beta || !mean || !rstd || !scale || !shift) return fail("null argument");
+    if ((running_mean == nullptr) != (running_var == nullptr)) return fail("running_mean and running_var come together");
+    if (g_op_bn_frozen && !running_mean) return fail("a frozen BatchNorm needs running_mean and running_var");
+    if (count < 1 || C < 1) return fail("bad shape");
+    LCHECK(vpd_launch_bn_finalize(rows, VPD_STAT_ROWS, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps, mean,
+                                  rstd, scale, shift, (hipStream_t)stream, g_op_bn_frozen != 0));
     return 0;
 }
 
@@ -943,7 +1013,36 @@ extern "C" int vpd_op_bn_backward_apply(const void* dy, const void* z, const uns
     BnFusedBwd f;
     memset(&f, 0, sizeof f);
     f.rows = const_cast<double*>(rows); f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
+    f.frozen = g_op_bn_frozen;
     LCHECK(vpd_launch_bn_bwd_apply_fused(b, f, (hipStream_t)stream));
+    return 0;
+}
+
+// ... for TWO BatchNorms fed with the same masked gradient (bn_bwd_apply_fused_kernel<true>: a down-sampling block's last BatchNorm
+// and its 1x1 branch's, whose sums the next block's data gradient took): rows2 holds sum g (unused) and sum g * z2
+extern "C" int vpd_op_bn_backward_apply2(const void* dy, const void* z, const unsigned char* mask_bits, const double* rows,
+                                         const float* gamma, const float* mean, const float* rstd, void* dz, float* dgamma,
+                                         float* dbeta, const void* z2, const double* rows2, const float* gamma2, const float* mean2,
+                                         const float* rstd2, void* dz2, float* dgamma2, float* dbeta2, int n, int H, int W, int C,
+                                         void* stream) {
+    if (!dy || !z || !mask_bits || !rows || !gamma || !mean || !rstd || !dz || !dgamma || !dbeta || !z2 || !rows2 || !gamma2 || !mean2 ||
+        !rstd2 || !dz2 || !dgamma2 || !dbeta2)
+        return fail("null argument");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
+    BnBwdParams b;
+    memset(&b, 0, sizeof b);
+    b.dy = (const bf16_t*)dy; b.z = (const bf16_t*)z; b.mean = mean; b.rstd = rstd;
+    b.dz = (bf16_t*)dz; b.dzHp = H + 2; b.dzWp = W + 2; b.dzpad = 1;
+    b.M = n * H * W; b.H = H; b.W = W; b.C = C; b.mask_bits = mask_bits;
+    BnFusedBwd f;
+    BnBwdSecond B;
+    memset(&f, 0, sizeof f);
+    memset(&B, 0, sizeof B);
+    f.rows = const_cast<double*>(rows); f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
+    f.frozen = g_op_bn_frozen;
+    B.f.rows = const_cast<double*>(rows2); B.f.gamma = gamma2; B.f.dgamma = dgamma2; B.f.dbeta = dbeta2; B.f.count = (float)b.M;
+    B.z = (const bf16_t*)z2; B.mean = mean2; B.rstd = rstd2; B.dz = (bf16_t*)dz2;
+    LCHECK(vpd_launch_bn_bwd_apply_fused(b, f, (hipStream_t)stream, &B));
     return 0;
 }
 
@@ -987,9 +1086,11 @@ extern "C" int vpd_op_conv1x1_bn(int mode, const void* x, const void* w, int n, 
         q.res = (const bf16_t*)res; q.rHp = H + 2; q.rWp = W + 2; q.rC = Co; q.rpad = 1;
         f.rows = rows; f.count = (float)q.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
         f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift; f.momentum = momentum; f.eps = eps;
+        f.frozen = g_op_bn_frozen;
+        if (f.frozen && !running_mean) return fail("a frozen BatchNorm needs running_mean and running_var");
     } else {
         q.y = (bf16_t*)const_cast<void*>(dout); q.acc_mask = mask_bits;
-        b.rows = rows; b.gamma = gamma; b.dgamma = dgamma; b.dbeta = dbeta; b.count = (float)q.M;
+        b.rows = rows; b.gamma = gamma; b.dgamma = dgamma; b.dbeta = dbeta; b.count = (float)q.M; b.frozen = g_op_bn_frozen;
     }
     LCHECK(vpd_launch_conv1x1_bn(q, mode == 1 ? &f : nullptr, mode >= 2 ? &b : nullptr, mode == 3 ? mean : nullptr,
                                  mode == 3 ? rstd : nullptr, mode == 1 ? mask_bits : nullptr, mode == 3 ? (bf16_t*)dz : nullptr,
@@ -1028,8 +1129,10 @@ extern "C" int vpd_op_conv1x1_bn2(int mode, const void* x, const void* w, const 
         f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift;
         f.rows2 = rows2; f.count2 = (float)q.M; f.gamma2 = gamma2; f.beta2 = beta2; f.rm2 = running_mean2; f.rv2 = running_var2;
         f.mean2 = mean2; f.rstd2 = rstd2; f.scale2 = scale2; f.shift2 = shift2;
-        f.momentum = momentum; f.eps = eps;
+        f.momentum = momentum; f.eps = eps; f.frozen = g_op_bn_frozen;
+        if (f.frozen && !running_mean) return fail("a frozen BatchNorm needs running_mean and running_var");
     } else {
+        b3.frozen = g_op_bn_frozen; bd.frozen = g_op_bn_frozen;
         q.y = (bf16_t*)const_cast<void*>(dout); q.acc_mask = mask_bits;
         b3.rows = rows; b3.gamma = gamma; b3.dgamma = dgamma; b3.dbeta = dbeta; b3.count = (float)q.M;
         bd.rows = rows2; bd.gamma = gamma2; bd.dgamma = dgamma2; bd.dbeta = dbeta2; bd.count = (float)q.M;
@@ -1081,7 +1184,7 @@ extern "C" int vpd_op_stem_pool_backward(const void* dpool, const unsigned char*
     sb.mean = mean; sb.rstd = rstd; sb.scale = scale; sb.shift = shift; sb.partials = rows;
     sb.pooled = (const bf16_t*)pooled_padded; sb.ppad = 1; sb.gamma_p = gamma; sb.beta_p = beta;
     sb.M = n * Hz * Wz; sb.Hz = Hz; sb.Wz = Wz; sb.Ho = (Hz - 1) / 2 + 1; sb.Wo = (Wz - 1) / 2 + 1; sb.C = C;
-    LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, gamma, dgamma, dbeta, coef, (bf16_t*)dz, (hipStream_t)stream));
+    LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, gamma, dgamma, dbeta, coef, (bf16_t*)dz, (hipStream_t)stream, g_op_bn_frozen != 0));
     return 0;
 }
 
@@ -1123,7 +1226,7 @@ extern "C" int vpd_op_bn_backward(void* dy, const void* z, const void* act_padde
     if (!fused) {
         if (mask_bits || dy_pooled) return fail("the three-launch path takes neither a ReLU bit map nor a pooled gradient");
         if (!coef) return fail("the three-launch path needs coef");
-        LCHECK(vpd_launch_bn_bwd(b, (float)b.M, gamma, dgamma, dbeta, (hipStream_t)stream));
+        LCHECK(vpd_launch_bn_bwd(b, (float)b.M, gamma, dgamma, dbeta, (hipStream_t)stream, false, g_op_bn_frozen != 0));
         return 0;
     }
     if (!sync || !err) return fail("the fused launch needs sync and err");
@@ -1136,6 +1239,7 @@ extern "C" int vpd_op_bn_backward(void* dy, const void* z, const void* act_padde
     BnFusedBwd f;
     memset(&f, 0, sizeof f);
     f.rows = rows; f.sync = sync; f.err = err; f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
+    f.frozen = g_op_bn_frozen;
     LCHECK(vpd_launch_bn_bwd_fused(b, f, (hipStream_t)stream));
     return 0;
 }
@@ -1156,7 +1260,7 @@ extern "C" int vpd_op_bn_backward_pair(void* dy, const void* act_padded, const v
     memset(&fA, 0, sizeof fA);
     memset(&B, 0, sizeof B);
     fA.rows = rowsA; fA.gamma = gammaA; fA.dgamma = dgammaA; fA.dbeta = dbetaA; fA.count = (float)b.M;
-    fA.sync = sync; fA.err = err;
+    fA.sync = sync; fA.err = err; fA.frozen = g_op_bn_frozen;
     B.f.rows = rowsB; B.f.gamma = gammaB; B.f.dgamma = dgammaB; B.f.dbeta = dbetaB; B.f.count = (float)b.M;
     B.z = (const bf16_t*)zB; B.mean = meanB; B.rstd = rstdB; B.dz = (bf16_t*)dzB;
     LCHECK(vpd_launch_bn_bwd_fused2(b, fA, B, (hipStream_t)stream));

@@ -17,6 +17,8 @@ struct Ctx {
     hipStream_t s;
     const float* params;
     int n;
+    bool frozen = false;             // BatchNorm on running statistics: the plan's flag in a forward, the forward's recorded mode in a backward
+    bool data_only = false;          // backward without parameter gradients (vpd_plan_set_param_grads): dgamma / dbeta go to the sink
     bf16_t* b16(size_t off) const { return reinterpret_cast<bf16_t*>(ws + off); }
     float* f32(size_t off) const { return reinterpret_cast<float*>(ws + off); }
     unsigned char* u8(size_t off) const { return reinterpret_cast<unsigned char*>(ws + off); }
@@ -33,6 +35,10 @@ struct Ctx {
     float* bn_coef(const BnInfo& b) const { return f32(b.fl_off) + 4 * b.C; }
     float* bn_escale(const BnInfo& b) const { return f32(b.fl_off) + 7 * b.C; }
     float* bn_eshift(const BnInfo& b) const { return f32(b.fl_off) + 8 * b.C; }
+    // where a BatchNorm backward stores dgamma / dbeta: the flat gradient buffer, or -- data_only -- the BatchNorm's own slot of
+    // the weight-gradient scratch, which no launch of such a pass touches otherwise
+    float* bn_dgamma(const BnInfo& b, float* grads) const { return data_only ? f32(p->wg_off) + b.sink_off : grads + b.w_off; }
+    float* bn_dbeta(const BnInfo& b, float* grads) const { return data_only ? f32(p->wg_off) + b.sink_off + b.C : grads + b.b_off; }
 };
 
 // timing classes: 0..4 = vpd_conv_kernel_class, 5 = conv_wgrad_halo_kernel (without its slab reduce), 6 = conv_wgrad_kernel
@@ -125,7 +131,7 @@ hipError_t run_bn_finalize(const Ctx& c, const ConvInfo& cv, float* bn_running) 
     return vpd_launch_bn_finalize(c.stat_rows(), T, cv.Co, (float)M, c.params + cv.bn.w_off,
                                   c.params + cv.bn.b_off, bn_running ? bn_running + cv.bn.rm_off : nullptr,
                                   bn_running ? bn_running + cv.bn.rv_off : nullptr, kBnMomentum, kBnEps,
-                                  c.bn_mean(cv.bn), c.bn_rstd(cv.bn), c.bn_scale(cv.bn), c.bn_shift(cv.bn), c.s);
+                                  c.bn_mean(cv.bn), c.bn_rstd(cv.bn), c.bn_scale(cv.bn), c.bn_shift(cv.bn), c.s, c.frozen);
 }
 
 // data-gradient launch descriptor of a conv: dz (padded, border 1) -> dx (dense [n][Hin][Win][Ci]).  Stride 2: the caller
@@ -333,7 +339,7 @@ BnFusedFwd bn_fused_fwd(const Ctx& c, const ConvInfo& cv, float* bn_running, con
         f.rows2 = g.rows; f.count2 = g.count; f.gamma2 = g.gamma; f.beta2 = g.beta; f.rm2 = g.rm; f.rv2 = g.rv;
         f.mean2 = g.mean; f.rstd2 = g.rstd; f.scale2 = g.scale; f.shift2 = g.shift;
     }
-    f.momentum = kBnMomentum; f.eps = kBnEps;
+    f.momentum = kBnMomentum; f.eps = kBnEps; f.frozen = c.frozen;
     return f;
 }
 // BatchNorm (+ residual, ReLU) of a train-mode forward: statistics -> normalised padded activation.  rcv: the
@@ -362,8 +368,8 @@ BnFusedBwd bn_bwd_side(const Ctx& c, const ConvInfo& cv, float* grads) {
     BnFusedBwd f;
     memset(&f, 0, sizeof f);
     f.rows = c.bn_rows(cv.bn);
-    f.gamma = c.params + cv.bn.w_off; f.dgamma = grads + cv.bn.w_off; f.dbeta = grads + cv.bn.b_off;
-    f.count = (float)(c.n * cv.Hout * cv.Wout);
+    f.gamma = c.params + cv.bn.w_off; f.dgamma = c.bn_dgamma(cv.bn, grads); f.dbeta = c.bn_dbeta(cv.bn, grads);
+    f.count = (float)(c.n * cv.Hout * cv.Wout); f.frozen = c.frozen;
     return f;
 }
 // ... as the second BatchNorm of a launch that serves two: its side, its z and statistics, its dz
@@ -403,8 +409,8 @@ hipError_t run_bn_bwd(const Ctx& c, const ConvInfo& cv, bf16_t* dy, const bf16_t
         f.sync = c.ws + cv.bn.sync_off; f.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
         return vpd_launch_bn_bwd_fused(b, f, c.s);
     }
-    return vpd_launch_bn_bwd(b, (float)b.M, c.params + cv.bn.w_off, grads + cv.bn.w_off, grads + cv.bn.b_off, c.s,
-                             reduce_done);
+    return vpd_launch_bn_bwd(b, (float)b.M, c.params + cv.bn.w_off, c.bn_dgamma(cv.bn, grads), c.bn_dbeta(cv.bn, grads), c.s,
+                             reduce_done, c.frozen);
 }
 
 // BatchNorm backward whose sums were taken by the producing data gradient (BnSums): finalize + apply
@@ -637,6 +643,7 @@ struct WgradQueue {
 
     // wgrad of `cv` may start once everything enqueued on the stream so far (its dz: Ctx::dz) is done
     hipError_t queue(const ConvInfo& cv, const bf16_t* dz, const bf16_t* x) {
+        if (c.data_only) return hipSuccess;      // no parameter asks for a gradient: dz feeds the data gradient only
         if (cv.dz_own_off) {
             pending.push_back({&cv, dz, x});
             return hipSuccess;
@@ -706,6 +713,7 @@ struct WgradQueue {
     int unpack_bucket(int b) {
         const vpd_plan* p = c.p;
         int nb = (int)p->bmap_unpack[b].size() / 2;
+        if (c.data_only) nb = 0;      // nothing to hand over; the bucket's event is still recorded
         if (lazy) nb = b == 3 ? p->nstem_unpack_blocks : 0;      // the stem's row-tap packing is undone here either way
         if (nb > 0)
             LCHECK(vpd_launch_unpack_grads(reinterpret_cast<const PackDesc*>(c.ws + p->desc_off), (int)p->descs.size(),
@@ -779,8 +787,10 @@ struct Backward {
             LCHECK(vpd_launch_sgemm(c.f32(p->dh1_off), params + L[0].w_off, c.f32(p->demb_off), nullptr, n, L[0].in, L[0].out, 0, 0, 0, s));
             demb = c.f32(p->demb_off);
         }
-        LCHECK(vpd_launch_sgemm(demb, c.f32(p->pooled_off), grads + p->fc.w_off, nullptr, p->D, p->feat, n, 1, 0, 0, s));
-        LCHECK(vpd_launch_colsum(demb, n, p->D, grads + p->fc.b_off, s));
+        if (!c.data_only) {      // (data_only comes through vpd_backward_ext, which refuses the motion head: the branch above is not taken)
+            LCHECK(vpd_launch_sgemm(demb, c.f32(p->pooled_off), grads + p->fc.w_off, nullptr, p->D, p->feat, n, 1, 0, 0, s));
+            LCHECK(vpd_launch_colsum(demb, n, p->D, grads + p->fc.b_off, s));
+        }
         LCHECK(vpd_launch_sgemm(demb, params + p->fc.w_off, c.f32(p->dpooled_off), nullptr, n, p->feat, p->D, 0, 0, 0, s));
         const StageInfo& S = p->stages[3];
         // BasicBlock students: the last block's BatchNorm backward produces d(out) from d(pooled) itself (run_bn_bwd)
@@ -856,7 +866,7 @@ struct Backward {
         BnSums sm;
         if (B.ds) {
             if (!bn_pair) LCHECK(run_bn_bwd(c, B.cd, dout, nullptr, dzd, 1, 0, grads));
-            if (wg_pair) LCHECK(run_conv_wgrad_pair(c, B.c1, B.cd, dz1, dzd, xin));
+            if (wg_pair && !c.data_only) LCHECK(run_conv_wgrad_pair(c, B.c1, B.cd, dz1, dzd, xin));
             else LCHECK(wq.queue(B.cd, dzd, xin));
             if (conv_pair_ok(c, B.c1, B.cd, true)) {
                 // one launch: the 1x1 branch's data gradient is extra K-steps of the even-even class
@@ -926,8 +936,8 @@ struct Backward {
         sb.pooled = c.b16(p->p0_off); sb.ppad = 1;
         sb.gamma_p = c.params + p->stem.bn.w_off; sb.beta_p = c.params + p->stem.bn.b_off;
         sb.M = c.n * p->H0 * p->W0; sb.Hz = p->H0; sb.Wz = p->W0; sb.Ho = p->H1; sb.Wo = p->W1; sb.C = 64;
-        LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, c.params + p->stem.bn.w_off, grads + p->stem.bn.w_off,
-                                        grads + p->stem.bn.b_off, c.bn_coef(p->stem.bn), c.b16(p->dz0_off), c.s));
+        LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, c.params + p->stem.bn.w_off, c.bn_dgamma(p->stem.bn, grads),
+                                        c.bn_dbeta(p->stem.bn, grads), c.bn_coef(p->stem.bn), c.b16(p->dz0_off), c.s, c.frozen));
         LCHECK(wq.queue(p->stem, c.b16(p->dz0_off), c.b16(p->xin_off)));
         return wq.unpack_bucket(3);
     }
@@ -966,13 +976,15 @@ extern "C" int vpd_forward_train(vpd_plan_t* p, const float* params, float* bn_r
                                  void* workspace, void* stream) {
     if (check_call(p, workspace, n, 0)) return -1;
     if (!p->train) return fail("plan was created with train=0");
+    if (p->bn_frozen && !bn_running) return fail("vpd_forward_train: a frozen BatchNorm (vpd_plan_set_bn_frozen) needs bn_running");
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
+    p->fwd_bn_frozen = p->bn_frozen;      // the mode of THIS graph: its backward asks here, whatever the flag says by then
     if (n == 0) {      // empty shard: no crops, no statistics update, zero loss (the running buffers stay as they are)
         if (loss_step) HCHECK(hipMemsetAsync(loss_step, 0, sizeof(float), s));
         return 0;
     }
-    Ctx c{p, ws, s, params, n};
+    Ctx c{p, ws, s, params, n, p->bn_frozen};
     p->fwd_had_x = x != nullptr;
     LCHECK(vpd_launch_zero_ranges(accumulator_zero_ranges(c), s));
     if (x) LCHECK(vpd_launch_pack_input(x, n, p->c_in, p->H, p->W, c.b16(p->xin_off), p->xHp, p->xWp, 3, 8, s));
@@ -1025,21 +1037,26 @@ namespace {
 int run_backward(vpd_plan* p, const float* params, float* grads, int n, void** bucket_events, char* ws, hipStream_t s, bool lazy,
                  const float* d_emb, float* dx_nchw) {
     p->grads_in_scratch = lazy;
+    // data gradients only (vpd_plan_set_param_grads(0), vpd_backward_ext): no weight-gradient launch, no slab sum, no unpack, no
+    // head weight gradient; `grads` is not written -- the BatchNorm launches store dgamma / dbeta into the idle weight-gradient scratch
+    const bool data_only = d_emb && !p->param_grads;
     if (n == 0) {      // empty shard: the gradient of a sum over no crops is zero; every bucket is "ready" at once
         // (lazy: the reducer sums the scratch ranges, and the optimizer step reads them there afterwards)
-        HCHECK(hipMemsetAsync(grads, 0, (size_t)p->nparam_padded * sizeof(float), s));
+        if (!data_only) HCHECK(hipMemsetAsync(grads, 0, (size_t)p->nparam_padded * sizeof(float), s));
         if (lazy) HCHECK(hipMemsetAsync(ws + p->wg_off, 0, (size_t)p->wg_elems * sizeof(float), s));
         for (int b = 0; b < 4; ++b)
             if (bucket_events && bucket_events[b]) HCHECK(hipEventRecord((hipEvent_t)bucket_events[b], s));
         return 0;
     }
-    Ctx c{p, ws, s, params, n};
+    Ctx c{p, ws, s, params, n, p->fwd_bn_frozen, data_only};
     if (d_emb) HCHECK(hipMemcpyAsync(c.f32(p->dpred_off), d_emb, (size_t)n * p->D * sizeof(float), hipMemcpyDeviceToDevice, s));
     // one launch zeroes the accumulator rows and every weight-gradient range the atomics kernel will add into
     ZeroRanges zr = accumulator_zero_ranges(c);
     auto dry = [&](const ConvInfo& cv) { (void)run_conv_wgrad(c, cv, nullptr, nullptr, &zr); };
-    for (auto& B : p->blocks) { dry(B.c1); dry(B.c2); if (p->bottleneck) dry(B.c3); if (B.ds) dry(B.cd); }
-    dry(p->stem);
+    if (!data_only) {
+        for (auto& B : p->blocks) { dry(B.c1); dry(B.c2); if (p->bottleneck) dry(B.c3); if (B.ds) dry(B.cd); }
+        dry(p->stem);
+    }
     if (zr.count >= ZR_MAX) {      // too many ranges (Bottleneck nets: 30-100 1x1 convs): zero the whole scratch in one range
         const int k = p->fused_bn ? 2 : 1;
         zr.ptr[k] = c.f32(p->wg_off); zr.n4[k] = (long)(p->wg_elems + 3) / 4; zr.count = k + 1;

@@ -102,6 +102,8 @@ class _Plan:
         # the count its forward saw and marks it consumed (StudentEngine.backward_ext)
         self.fwd_count = 0
         self.consumed = None
+        # what the plan was last told (vpd_plan_set_bn_frozen / vpd_plan_set_param_grads): the library's defaults
+        self.bn_frozen, self.param_grads = False, True
         # lazy gradients under data parallelism: bucket b's conv weight gradients as a view of the workspace (the kernels' own
         # layout), and the flat-buffer positions of everything else (BatchNorm, fc, motion head, the stem conv)
         self.scratch_views, self.small_idx = [], None
@@ -196,6 +198,7 @@ class StudentEngine:
         self._grads_cleared = True     # nothing to add onto: the flat buffer is fresh, or an optimizer's zero_grad() said so
         self._grads2 = None            # second flat buffer an accumulating backward writes before it is added (first use)
         self.stem_dgrad_launches = 0   # input gradients asked for (conv_stem_dgrad_kernel launches)
+        self.bn_frozen = False         # freeze_bn(): train-mode forwards normalise with the running statistics and leave them alone
 
     # -- helpers -------------------------------------------------------------
     @property
@@ -290,6 +293,19 @@ class StudentEngine:
         assert x.dim() == 4 and x.shape[1] == c_in, "expected f32 [N,%d,H,W], got %s" % (c_in, tuple(x.shape))
         assert x.dtype == torch.float32 and x.is_contiguous() and x.is_cuda
 
+    def freeze_bn(self, mode=True):
+        """Frozen BatchNorm for the train plans (vpd_plan_set_bn_frozen): from the next train-mode forward on, every BatchNorm
+        normalises with its running statistics and does not update them; the backward of a forward uses the mode that forward
+        ran in.  Eval plans are not concerned (they fold the running statistics already)."""
+        if mode and not hasattr(self.L, "vpd_plan_set_bn_frozen"):      # (absent only in an older A/B library)
+            raise RuntimeError("this libvpdhip has no frozen BatchNorm (vpd_plan_set_bn_frozen)")
+        self.bn_frozen = bool(mode)
+
+    def _plan_flag(self, pl, attr, setter, on):
+        if getattr(pl, attr) != on:
+            self.check(getattr(self.L, setter)(pl.handle, int(on)), setter)
+            setattr(pl, attr, on)
+
     # -- forward / backward / step ---------------------------------------------
     def forward_eval(self, x, target=None, motion=False, out=None, accumulate_loss=True, staged=None):
         if staged is not None:
@@ -356,15 +372,18 @@ class StudentEngine:
             want = (n, self.emb_dim * (2 if motion else 1))
             assert tuple(target.shape) == want and target.dtype == torch.float32 and target.is_contiguous(), \
                 "target must be f32 %s" % (want,)
+        frozen = self.bn_frozen
+        self._plan_flag(pl, "bn_frozen", "vpd_plan_set_bn_frozen", frozen)
         self.check(self.L.vpd_forward_train(pl.handle, _ptr(self.params), _ptr(self.bn_running), _ptr(x), _ptr(target), n,
                                       _ptr(emb), _ptr(self.loss_step),
                                       _ptr(self.loss_accum) if accumulate_loss else None,
                                       _ptr(pl.workspace), self._stream()), "vpd_forward_train")
-        # BN running stats were rewritten by HIP kernels: packed eval scale/shift are stale
-        self._hip_version += 1
-        pl.packed_version = (self.params._version, self.bn_running._version, self._hip_version)
-        if n > 0:
-            self._nbt_pending += 1
+        if not frozen:      # (a frozen forward read the running statistics and left them: nothing is stale, nothing was tracked)
+            # BN running stats were rewritten by HIP kernels: packed eval scale/shift are stale
+            self._hip_version += 1
+            pl.packed_version = (self.params._version, self.bn_running._version, self._hip_version)
+            if n > 0:
+                self._nbt_pending += 1
         self._last = (pl, n) if target is not None else None
         pl.fwd_count += 1
         self._last_fwd = (pl, n, pl.fwd_count, x is not None)
@@ -401,7 +420,8 @@ class StudentEngine:
         the plan WITHOUT the motion head -- `ticket`: what `_last_fwd` held right after that forward (default: the last one).
         d_emb: f32 [n, emb_dim] on the engine's device, contiguous; no loss scale is passed (a scaled loss arrives scaled).
         accumulate: add onto the flat gradient buffer instead of overwriting it (backward into a second buffer + one add);
-        discard: leave the flat buffer alone (no parameter asks for a gradient).  want_dx: also return d(loss)/d(x), f32
+        discard: leave the flat buffer alone (no parameter asks for a gradient): the pass then computes data gradients only
+        (vpd_plan_set_param_grads(0): no weight-gradient launch, nothing written to a gradient buffer).  want_dx: also return d(loss)/d(x), f32
         [n, c_in, H, W] (the stem convolution's data gradient; only after a forward that took x).  Returns dx or None.
         Raises RuntimeError when a later train-mode forward overwrote the activations, and on a second backward through the same
         forward (the pass consumes them: retain_graph does not apply)."""
@@ -428,7 +448,10 @@ class StudentEngine:
         self._last = None                  # the fused backward() of the same forward would find its activations consumed
         pl.consumed = count
         into = self._grads
-        if accumulate or discard:
+        data_only = discard and hasattr(self.L, "vpd_plan_set_param_grads")      # (absent only in an older A/B library)
+        if hasattr(self.L, "vpd_plan_set_param_grads"):
+            self._plan_flag(pl, "param_grads", "vpd_plan_set_param_grads", not data_only)
+        if accumulate or (discard and not data_only):      # (data_only: `into` must be non-null but is not written)
             if self._grads2 is None:
                 self._grads2 = torch.zeros_like(self._grads)
             into = self._grads2

@@ -197,7 +197,7 @@ class RGBF_EmbeddingModel(nn.Module):
 
     def forward(self, x):
         """f32 [N,C,H,W] on the GPU -> f32 [N,emb_dim].  Train mode uses batch statistics and updates the running ones
-        (nn.BatchNorm2d semantics).
+        (nn.BatchNorm2d semantics) unless freeze_bn() is on, see below.
 
         In train mode, with torch.is_grad_enabled() and a parameter or x requiring grad, the result is part of torch's autograd
         graph like the reference module's (models/rgb.py:68-70): any loss of the embeddings -- a weighted or cosine distillation
@@ -214,8 +214,15 @@ class RGBF_EmbeddingModel(nn.Module):
         included).  ModelTrainer.epoch's fused step (forward + sum-MSE + backward + AdamW without torch in between) does not go
         through here and stays the fast path.
 
-        Out of scope: eval-mode differentiability (frozen BatchNorm: the output has no grad_fn, as under torch.no_grad());
-        double backward; FCNet as a differentiable module (put a torch head on the embeddings); data parallelism through this
+        Frozen BatchNorm is opt-in: after freeze_bn() a train-mode forward normalises with the RUNNING statistics and leaves them
+        and num_batches_tracked alone -- on this autograd route, on the plain route under no_grad() and in ModelTrainer.epoch's
+        fused step -- and its backward differentiates that function (dz = gamma / std * g).  That is fine-tuning on frozen
+        statistics, and the gradient of what embed() computes (saliency, adversarial crops, a module trained through a fixed
+        student; with every parameter requires_grad_(False) the pass computes data gradients only).  The reference gets this from
+        model.eval() with grad enabled; here eval() stays what it is -- the folded inference plan, a plain tensor -- so that a
+        forgotten no_grad() never moves inference onto the train plan.
+
+        Out of scope: double backward; FCNet as a differentiable module (put a torch head on the embeddings); data parallelism through this
         path (ModelTrainer owns the gradient reducer)."""
         self._check_storage()
         x = x.to(self.engine.device, dtype=torch.float32).contiguous()
@@ -226,6 +233,15 @@ class RGBF_EmbeddingModel(nn.Module):
                     return _StudentFunction.apply(self, x, *params)
             return self.engine.forward_train(x, None, motion=False)
         return self.engine.forward_eval(x)
+
+    def freeze_bn(self, mode=True):
+        """Train-mode forwards use the running BatchNorm statistics (and do not update them) while on; see forward().  Returns self."""
+        self.engine.freeze_bn(mode)
+        return self
+
+    @property
+    def bn_frozen(self):
+        return self.engine.bn_frozen
 
     def _autograd_backward(self, ticket, d_emb, want_dx):
         """_StudentFunction.backward: torch's accumulate rule for .grad on top of a backward pass that overwrites.  A parameter
