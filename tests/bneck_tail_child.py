@@ -71,6 +71,30 @@ class Vec:
         return c[:self.co].double(), bool((c[self.co:] == SENT).all())
 
 
+def _side(side, *names):
+    """a BatchNorm's device pointers in the order named; what the dict does not hold goes as null"""
+    return [ptr((side or {}).get(k)) for k in names]
+
+
+def op_tail(ops, mode, dims, x, w, rows, side=None, res=None, out=None, mask=None, dout=None):
+    """vpd_op_conv1x1_bn (stride 1): dims = (n, h, w, ci, co); side: the BatchNorm's tensors by name among gamma beta rm rv mean rstd
+    scale shift dz dgamma dbeta, each mode passing the ones it wants read or written"""
+    n, h, wd, ci, co = dims
+    ops.check(ops.L.vpd_op_conv1x1_bn(mode, ptr(x), ptr(w), n, h, wd, 1, ci, co, ptr(rows), *_side(side, "gamma", "beta", "rm", "rv"),
+                                      F(R.BN_MOMENTUM), F(R.BN_EPS), *_side(side, "mean", "rstd", "scale", "shift"), ptr(res), ptr(out),
+                                      ptr(mask), ptr(dout), *_side(side, "dz", "dgamma", "dbeta"), stream()))
+
+
+def op_tail2(ops, mode, dims, x, w, rows, side, side2, out=None, mask=None, dout=None):
+    """vpd_op_conv1x1_bn2: x / w / rows map a side key ("" the closing convolution, "2" the branch) to its tensor; side / side2 as op_tail's"""
+    n, h, wd, ci, co = dims
+    fwd = ("gamma", "beta", "rm", "rv", "mean", "rstd", "scale", "shift")
+    ops.check(ops.L.vpd_op_conv1x1_bn2(mode, ptr(x[""]), ptr(w[""]), ptr(x["2"]), ptr(w["2"]), n, h, wd, ci, ci, co, ptr(rows[""]), ptr(rows["2"]),
+                                       *_side(side, *fwd), *_side(side2, *fwd), F(R.BN_MOMENTUM), F(R.BN_EPS), ptr(out), ptr(mask), ptr(dout),
+                                       *_side(side, "dz"), *_side(side2, "dz"), *_side(side, "dgamma", "dbeta"), *_side(side2, "dgamma", "dbeta"),
+                                       stream()))
+
+
 def close(got, want, rtol, atol=0.0):
     return bool(((got - want).abs() <= atol + rtol * want.abs()).all())
 
@@ -80,6 +104,7 @@ def run_case(ops, cs, o, regime, name, fail, record):
     L, T = ops.L, ops.T
     n, ci, co, h, w, two = cs["n"], cs["ci"], cs["co"], cs["h"], cs["w"], cs["two"]
     M, G, exact = n * h * w, Geo(cs), regime == "int"
+    dims = (n, h, w, ci, co)
     tag = "%s/%s/" % (name, regime)
     sides = ("", "2") if two else ("",)
     bad = lambda what: fail.append(tag + what)
@@ -132,8 +157,7 @@ def run_case(ops, cs, o, regime, name, fail, record):
     rows = {}
     for s in sides:
         rows[s] = torch.zeros(4, 2, co, dtype=torch.float64, device="cuda")
-        ops.check(L.vpd_op_conv1x1_bn(0, ptr(xp[s]), ptr(wf[s]), n, h, w, 1, ci, co, ptr(rows[s]), nul, nul, nul, nul, F(R.BN_MOMENTUM),
-                                      F(R.BN_EPS), nul, nul, nul, nul, nul, nul, nul, nul, nul, nul, nul, stream()))
+        op_tail(ops, 0, dims, xp[s], wf[s], rows[s])
         torch.cuda.synchronize()
         dig["rows" + s] = sha(rows[s])
         st = stat[s]
@@ -147,16 +171,12 @@ def run_case(ops, cs, o, regime, name, fail, record):
     maskb = torch.full((M * co // 8 + SLACK,), MASK_SENT, dtype=torch.uint8, device="cuda")
     resp = None if two else ops.padded(o["res"])
     vp = lambda s, k: ptr(vec[s][k].t)
+    vec_t = lambda s: {k: v.t for k, v in vec[s].items()}
+    fwd_side = lambda s: dict(vec_t(s), gamma=gam[s], beta=bet[s])
     if two:
-        ops.check(L.vpd_op_conv1x1_bn2(1, ptr(xp[""]), ptr(wf[""]), ptr(xp["2"]), ptr(wf["2"]), n, h, w, ci, ci, co, ptr(rows[""]), ptr(rows["2"]),
-                                       ptr(gam[""]), ptr(bet[""]), vp("", "rm"), vp("", "rv"), vp("", "mean"), vp("", "rstd"), vp("", "scale"),
-                                       vp("", "shift"), ptr(gam["2"]), ptr(bet["2"]), vp("2", "rm"), vp("2", "rv"), vp("2", "mean"),
-                                       vp("2", "rstd"), vp("2", "scale"), vp("2", "shift"), F(R.BN_MOMENTUM), F(R.BN_EPS), ptr(out), ptr(maskb),
-                                       nul, nul, nul, nul, nul, nul, nul, stream()))
+        op_tail2(ops, 1, dims, xp, wf, rows, fwd_side(""), fwd_side("2"), out=out, mask=maskb)
     else:
-        ops.check(L.vpd_op_conv1x1_bn(1, ptr(xp[""]), ptr(wf[""]), n, h, w, 1, ci, co, ptr(rows[""]), ptr(gam[""]), ptr(bet[""]), vp("", "rm"),
-                                      vp("", "rv"), F(R.BN_MOMENTUM), F(R.BN_EPS), vp("", "mean"), vp("", "rstd"), vp("", "scale"), vp("", "shift"),
-                                      ptr(resp), ptr(out), ptr(maskb), nul, nul, nul, nul, stream()))
+        op_tail(ops, 1, dims, xp[""], wf[""], rows[""], fwd_side(""), res=resp, out=out, mask=maskb)
     torch.cuda.synchronize()
     dig.update({"out": sha(out), "mask": sha(maskb)})
     dig.update({k + s: sha(t.t) for s in sides for k, t in vec[s].items()})
@@ -216,16 +236,12 @@ def run_case(ops, cs, o, regime, name, fail, record):
         dg, db = {s: Vec(co) for s in sides}, {s: Vec(co) for s in sides}
         for mode in (2, 3):
             m3 = mode == 3
+            bwd_side = lambda s: dict(gamma=gam[s], mean=vec[s]["mean"].t, rstd=vec[s]["rstd"].t, dz=dz[s] if m3 else None,
+                                      dgamma=dg[s].t, dbeta=db[s].t)
             if two:
-                ops.check(L.vpd_op_conv1x1_bn2(mode, ptr(xp[""]), ptr(wf[""]), ptr(xp["2"]), ptr(wf["2"]), n, h, w, ci, ci, co, ptr(brow[""]),
-                                               ptr(brow["2"]), ptr(gam[""]), nul, nul, nul, vp("", "mean"), vp("", "rstd"), nul, nul,
-                                               ptr(gam["2"]), nul, nul, nul, vp("2", "mean"), vp("2", "rstd"), nul, nul, F(R.BN_MOMENTUM),
-                                               F(R.BN_EPS), nul, ptr(bits), ptr(doutd), ptr(dz[""]) if m3 else nul, ptr(dz["2"]) if m3 else nul,
-                                               ptr(dg[""].t), ptr(db[""].t), ptr(dg["2"].t), ptr(db["2"].t), stream()))
+                op_tail2(ops, mode, dims, xp, wf, brow, bwd_side(""), bwd_side("2"), mask=bits, dout=doutd)
             else:
-                ops.check(L.vpd_op_conv1x1_bn(mode, ptr(xp[""]), ptr(wf[""]), n, h, w, 1, ci, co, ptr(brow[""]), ptr(gam[""]), nul, nul, nul,
-                                              F(R.BN_MOMENTUM), F(R.BN_EPS), vp("", "mean"), vp("", "rstd"), nul, nul, nul, nul, ptr(bits), ptr(doutd),
-                                              ptr(dz[""]) if m3 else nul, ptr(dg[""].t), ptr(db[""].t), stream()))
+                op_tail(ops, mode, dims, xp[""], wf[""], brow[""], bwd_side(""), mask=bits, dout=doutd)
             torch.cuda.synchronize()
             if not m3:
                 for s in sides:

@@ -18,7 +18,7 @@ if REPO not in sys.path:
 
 from tests import opref as R  # noqa: E402
 from tests import opref_frozen as Z  # noqa: E402
-from tests.bneck_tail_child import F, MASK_SENT, Vec, dispatch  # noqa: E402
+from tests.bneck_tail_child import MASK_SENT, Vec, dispatch, op_tail, op_tail2  # noqa: E402
 from tests.conv_ops_child import SLACK, Geo, Ops, ptr, stream  # noqa: E402
 
 
@@ -26,9 +26,9 @@ def run_case(ops, cs, name, fail, record):
     L, T = ops.L, ops.T
     n, ci, co, h, w, two = cs["n"], cs["ci"], cs["co"], cs["h"], cs["w"], cs["two"]
     M, G = n * h * w, Geo(cs)
+    dims = (n, h, w, ci, co)
     sides = ("", "2") if two else ("",)
     bad = lambda what: fail.append("%s: %s" % (name, what))
-    nul = None
     o = R.tail_operands(cs, R.CONV_SEEDS[0], "rand", name)
     g = torch.Generator().manual_seed(co + n)
     for s in sides:      # statistics far from the batch's own and from 0 / 1, gamma of either sign
@@ -43,7 +43,7 @@ def run_case(ops, cs, name, fail, record):
         z[s], _ = ops.read(y, n, h, w, co, 0)
     gam, bet = {s: f32(o["gamma" + s]) for s in sides}, {s: f32(o["beta" + s]) for s in sides}
     vec = {s: {k: Vec(co, o[k + s] if k in ("rm", "rv") else None) for k in ("mean", "rstd", "scale", "shift", "rm", "rv")} for s in sides}
-    vp = lambda s, k: ptr(vec[s][k].t)
+    vec_t = lambda s: {k: v.t for k, v in vec[s].items()}
     before = {s: {k: vec[s][k].t.clone() for k in ("rm", "rv")} for s in sides}
 
     def rows_check(what, rows, want, mags):
@@ -59,8 +59,7 @@ def run_case(ops, cs, name, fail, record):
         rows = {}
         for s in sides:
             rows[s] = torch.zeros(4, 2, co, dtype=torch.float64, device="cuda")
-            ops.check(L.vpd_op_conv1x1_bn(0, ptr(xp[s]), ptr(wf[s]), n, h, w, 1, ci, co, ptr(rows[s]), nul, nul, nul, nul, F(R.BN_MOMENTUM),
-                                          F(R.BN_EPS), nul, nul, nul, nul, nul, nul, nul, nul, nul, nul, nul, stream()))
+            op_tail(ops, 0, dims, xp[s], wf[s], rows[s])
             torch.cuda.synchronize()
             zz = z[s]
             rows_check("mode0/rows" + s, rows[s], torch.stack([zz.sum(dim=(0, 2, 3)), (zz * zz).sum(dim=(0, 2, 3))]),
@@ -69,16 +68,11 @@ def run_case(ops, cs, name, fail, record):
         out = ops.out_buffer(n, h, w, co, 1)
         maskb = torch.full((M * co // 8 + SLACK,), MASK_SENT, dtype=torch.uint8, device="cuda")
         resp = None if two else ops.padded(o["res"])
+        fwd_side = lambda s: dict(vec_t(s), gamma=gam[s], beta=bet[s])
         if two:
-            ops.check(L.vpd_op_conv1x1_bn2(1, ptr(xp[""]), ptr(wf[""]), ptr(xp["2"]), ptr(wf["2"]), n, h, w, ci, ci, co, ptr(rows[""]), ptr(rows["2"]),
-                                           ptr(gam[""]), ptr(bet[""]), vp("", "rm"), vp("", "rv"), vp("", "mean"), vp("", "rstd"), vp("", "scale"),
-                                           vp("", "shift"), ptr(gam["2"]), ptr(bet["2"]), vp("2", "rm"), vp("2", "rv"), vp("2", "mean"),
-                                           vp("2", "rstd"), vp("2", "scale"), vp("2", "shift"), F(R.BN_MOMENTUM), F(R.BN_EPS), ptr(out), ptr(maskb),
-                                           nul, nul, nul, nul, nul, nul, nul, stream()))
+            op_tail2(ops, 1, dims, xp, wf, rows, fwd_side(""), fwd_side("2"), out=out, mask=maskb)
         else:
-            ops.check(L.vpd_op_conv1x1_bn(1, ptr(xp[""]), ptr(wf[""]), n, h, w, 1, ci, co, ptr(rows[""]), ptr(gam[""]), ptr(bet[""]), vp("", "rm"),
-                                          vp("", "rv"), F(R.BN_MOMENTUM), F(R.BN_EPS), vp("", "mean"), vp("", "rstd"), vp("", "scale"), vp("", "shift"),
-                                          ptr(resp), ptr(out), ptr(maskb), nul, nul, nul, nul, stream()))
+            op_tail(ops, 1, dims, xp[""], wf[""], rows[""], fwd_side(""), res=resp, out=out, mask=maskb)
         torch.cuda.synchronize()
         got, kept = ops.read(out, n, h, w, co, 1)
         if not kept:
@@ -125,16 +119,12 @@ def run_case(ops, cs, name, fail, record):
         dg, db = {s: Vec(co) for s in sides}, {s: Vec(co) for s in sides}
         for mode in (2, 3):
             m3 = mode == 3
+            bwd_side = lambda s: dict(gamma=gam[s], mean=vec[s]["mean"].t, rstd=vec[s]["rstd"].t, dz=dz[s] if m3 else None,
+                                      dgamma=dg[s].t, dbeta=db[s].t)
             if two:
-                ops.check(L.vpd_op_conv1x1_bn2(mode, ptr(xp[""]), ptr(wf[""]), ptr(xp["2"]), ptr(wf["2"]), n, h, w, ci, ci, co, ptr(brow[""]),
-                                               ptr(brow["2"]), ptr(gam[""]), nul, nul, nul, vp("", "mean"), vp("", "rstd"), nul, nul,
-                                               ptr(gam["2"]), nul, nul, nul, vp("2", "mean"), vp("2", "rstd"), nul, nul, F(R.BN_MOMENTUM),
-                                               F(R.BN_EPS), nul, ptr(bits), ptr(doutd), ptr(dz[""]) if m3 else nul, ptr(dz["2"]) if m3 else nul,
-                                               ptr(dg[""].t), ptr(db[""].t), ptr(dg["2"].t), ptr(db["2"].t), stream()))
+                op_tail2(ops, mode, dims, xp, wf, brow, bwd_side(""), bwd_side("2"), mask=bits, dout=doutd)
             else:
-                ops.check(L.vpd_op_conv1x1_bn(mode, ptr(xp[""]), ptr(wf[""]), n, h, w, 1, ci, co, ptr(brow[""]), ptr(gam[""]), nul, nul, nul,
-                                              F(R.BN_MOMENTUM), F(R.BN_EPS), vp("", "mean"), vp("", "rstd"), nul, nul, nul, nul, ptr(bits), ptr(doutd),
-                                              ptr(dz[""]) if m3 else nul, ptr(dg[""].t), ptr(db[""].t), stream()))
+                op_tail(ops, mode, dims, xp[""], wf[""], brow[""], bwd_side(""), mask=bits, dout=doutd)
             torch.cuda.synchronize()
             if not m3:
                 for s in sides:

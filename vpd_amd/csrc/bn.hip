@@ -774,17 +774,19 @@ static int vpd_bn_xcd_r(int tile_px, int C, int grid) {
     return (R >= 1 && R <= 32 && 32 % R == 0) ? R : 0;
 }
 
-struct BnFusedFwdArgs {
-    double* rows; float count;                 // this BatchNorm's accumulator rows [VPD_FUSED_ROWS][2][C]
+struct BnFwdSideArgs {                          // one BatchNorm: BnFwdSide with the launch's count beside its rows
+    double* rows; float count;                 // accumulator rows [VPD_FUSED_ROWS][2][C]
     const float* gamma; const float* beta; float* rm; float* rv;
     float* mean; float* rstd; float* scale; float* shift;
-    // residual BatchNorm (res_kind 2) or rows2 == null
-    double* rows2; float count2;
-    const float* gamma2; const float* beta2; float* rm2; float* rv2;
-    float* mean2; float* rstd2; float* scale2; float* shift2;
+};
+struct BnFusedFwdArgs {
+    BnFwdSideArgs s[2];                        // [1]: the residual BatchNorm (res_kind 2) or rows == null
     float momentum, eps;
     int xcd_r;                                 // vpd_bn_virtual_block
 };
+static BnFwdSideArgs bn_fwd_side_args(const BnFwdSide& h, float count) {
+    return BnFwdSideArgs{h.rows, count, h.gamma, h.beta, h.rm, h.rv, h.mean, h.rstd, h.scale, h.shift};
+}
 
 // FROZEN (BnFusedFwd::frozen): both BatchNorms normalise with rm / rv, read only, instead of their rows.  An instantiation, not a
 // kernel argument: the launch is at its scalar-register limit, and <false> is the kernel it was, instruction for instruction.
@@ -835,25 +837,25 @@ __global__ __launch_bounds__(1024) void bn_fwd_fused_kernel(const BnApplyParams 
     if (have) load_item(it, zc, rc, oo, c);
     for (int ch = threadIdx.x; ch < C; ch += blockDim.x) {
         float mu, r, sc, sh; double var;
-        bn_finalize_channel(f.rows, C, ch, f.count, f.eps, f.gamma[ch], f.beta[ch], &mu, &r, &sc, &sh, &var, FROZEN, f.rm, f.rv);
+        bn_finalize_channel(f.s[0].rows, C, ch, f.s[0].count, f.eps, f.s[0].gamma[ch], f.s[0].beta[ch], &mu, &r, &sc, &sh, &var, FROZEN, f.s[0].rm, f.s[0].rv);
         s_sc[ch] = sc; s_sh[ch] = sh;
         if (blockIdx.x == 0) {
-            f.mean[ch] = mu; f.rstd[ch] = r; f.scale[ch] = sc; f.shift[ch] = sh;
-            if (f.rm && !FROZEN) {
-                const double unb = f.count > 1.f ? var * (double)f.count / ((double)f.count - 1.0) : var;
-                f.rm[ch] = (1.f - f.momentum) * f.rm[ch] + f.momentum * mu;
-                f.rv[ch] = (1.f - f.momentum) * f.rv[ch] + f.momentum * (float)unb;
+            f.s[0].mean[ch] = mu; f.s[0].rstd[ch] = r; f.s[0].scale[ch] = sc; f.s[0].shift[ch] = sh;
+            if (f.s[0].rm && !FROZEN) {
+                const double unb = f.s[0].count > 1.f ? var * (double)f.s[0].count / ((double)f.s[0].count - 1.0) : var;
+                f.s[0].rm[ch] = (1.f - f.momentum) * f.s[0].rm[ch] + f.momentum * mu;
+                f.s[0].rv[ch] = (1.f - f.momentum) * f.s[0].rv[ch] + f.momentum * (float)unb;
             }
         }
-        if (f.rows2) {
-            bn_finalize_channel(f.rows2, C, ch, f.count2, f.eps, f.gamma2[ch], f.beta2[ch], &mu, &r, &sc, &sh, &var, FROZEN, f.rm2, f.rv2);
+        if (f.s[1].rows) {
+            bn_finalize_channel(f.s[1].rows, C, ch, f.s[1].count, f.eps, f.s[1].gamma[ch], f.s[1].beta[ch], &mu, &r, &sc, &sh, &var, FROZEN, f.s[1].rm, f.s[1].rv);
             s_rsc[ch] = sc; s_rsh[ch] = sh;
             if (blockIdx.x == 0) {
-                f.mean2[ch] = mu; f.rstd2[ch] = r; f.scale2[ch] = sc; f.shift2[ch] = sh;
-                if (f.rm2 && !FROZEN) {
-                    const double unb = f.count2 > 1.f ? var * (double)f.count2 / ((double)f.count2 - 1.0) : var;
-                    f.rm2[ch] = (1.f - f.momentum) * f.rm2[ch] + f.momentum * mu;
-                    f.rv2[ch] = (1.f - f.momentum) * f.rv2[ch] + f.momentum * (float)unb;
+                f.s[1].mean[ch] = mu; f.s[1].rstd[ch] = r; f.s[1].scale[ch] = sc; f.s[1].shift[ch] = sh;
+                if (f.s[1].rm && !FROZEN) {
+                    const double unb = f.s[1].count > 1.f ? var * (double)f.s[1].count / ((double)f.s[1].count - 1.0) : var;
+                    f.s[1].rm[ch] = (1.f - f.momentum) * f.s[1].rm[ch] + f.momentum * mu;
+                    f.s[1].rv[ch] = (1.f - f.momentum) * f.s[1].rv[ch] + f.momentum * (float)unb;
                 }
             }
         }
@@ -928,12 +930,9 @@ __global__ __launch_bounds__(1024) void bn_fwd_fused_kernel(const BnApplyParams 
 
 hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f0, hipStream_t s) {
     if (p.C % 8 || p.C > 4096) return hipErrorInvalidValue;
-    if (f0.frozen && (!f0.rm || !f0.rv || (f0.rows2 && (!f0.rm2 || !f0.rv2)))) return hipErrorInvalidValue;
+    if (f0.frozen && (!f0.s[0].rm || !f0.s[0].rv || (f0.s[1].rows && (!f0.s[1].rm || !f0.s[1].rv)))) return hipErrorInvalidValue;
     BnFusedFwdArgs f;
-    f.rows = f0.rows; f.count = f0.count; f.gamma = f0.gamma; f.beta = f0.beta; f.rm = f0.rm; f.rv = f0.rv;
-    f.mean = f0.mean; f.rstd = f0.rstd; f.scale = f0.scale; f.shift = f0.shift;
-    f.rows2 = f0.rows2; f.count2 = f0.count2; f.gamma2 = f0.gamma2; f.beta2 = f0.beta2; f.rm2 = f0.rm2; f.rv2 = f0.rv2;
-    f.mean2 = f0.mean2; f.rstd2 = f0.rstd2; f.scale2 = f0.scale2; f.shift2 = f0.shift2;
+    for (int n = 0; n < 2; ++n) f.s[n] = bn_fwd_side_args(f0.s[n], f0.count);
     f.momentum = f0.momentum; f.eps = f0.eps;
     const long items = (long)p.M * (p.C / 8);
     long g = (items + 1023) / 1024;
@@ -1254,21 +1253,23 @@ __global__ __launch_bounds__(1024) void bn_bwd_apply_fused_kernel(const BnBwdPar
     }
 }
 
-hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f0, hipStream_t s, const BnBwdSecond* B) {
+hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f0, hipStream_t s) {
     if (p.C % 8 || p.C > 4096 || !p.mask_bits) return hipErrorInvalidValue;
+    const BnBwdSide& A = f0.s[0];
+    const BnBwdSide& B = f0.s[1];
     BnBwdApplyArgs f;
     f = BnBwdApplyArgs{};
-    f.rows = f0.rows; f.count = f0.count; f.gamma = f0.gamma; f.mean = p.mean; f.rstd = p.rstd;
-    f.dgamma = f0.dgamma; f.dbeta = f0.dbeta; f.frozen = f0.frozen;
+    f.rows = A.rows; f.count = f0.count; f.gamma = A.gamma; f.mean = p.mean; f.rstd = p.rstd;
+    f.dgamma = A.dgamma; f.dbeta = A.dbeta; f.frozen = f0.frozen;
     const long items = (long)p.M * (p.C / 8);
     long g = (items + 1023) / 1024;
     if (g > 256) g = 256;      // (one 1024-thread block per CU: same-box -10 us per step against two; 192 or fewer: +110 us)
     if (g < 1) g = 1;
     const int xcd_on = vpd_bn_xcd_on();
     f.xcd_r = xcd_on ? vpd_bn_xcd_r(p.xcd_tile_px, p.C, (int)g) : 0;
-    if (B) {
-        f.rows2 = B->f.rows; f.gamma2 = B->f.gamma; f.mean2 = B->mean; f.rstd2 = B->rstd; f.dgamma2 = B->f.dgamma; f.dbeta2 = B->f.dbeta;
-        f.z2 = B->z; f.dz2 = B->dz;
+    if (B.rows) {
+        f.rows2 = B.rows; f.gamma2 = B.gamma; f.mean2 = B.mean; f.rstd2 = B.rstd; f.dgamma2 = B.dgamma; f.dbeta2 = B.dbeta;
+        f.z2 = B.z; f.dz2 = B.dz;
         hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<true>, dim3((unsigned)g), dim3(1024), (size_t)6 * p.C * sizeof(float), s, p, f);
     } else {
         hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<false>, dim3((unsigned)g), dim3(1024), (size_t)3 * p.C * sizeof(float), s, p, f);
@@ -1305,30 +1306,31 @@ bool vpd_bn_bwd_fused2_ok(int M, int C) {
     return !(!vpd_switches().fused_bn || !vpd_switches().bn_pair || C % 8 || C < 64 || C > 2048 || 1024 % (C / 8)) && M >= 1;
 }
 
-// launch arguments of bn_bwd_fused_body: BatchNorm 0 from (p, fA), whose sync / err / count serve the launch; BatchNorm 1 (NB == 2) from B
+// launch arguments of bn_bwd_fused_body: BatchNorm 0's z / mean / rstd / dz from p, BatchNorm 1's (NB == 2) from its side
 template <int NB>
-static BnFusedBwdArgs<NB> bn_bwd_fused_args(const BnBwdParams& p, const BnFusedBwd& fA, const BnBwdSecond* B, const BnBwdFusedGeom& geo) {
+static BnFusedBwdArgs<NB> bn_bwd_fused_args(const BnBwdParams& p, const BnFusedBwd& f0, const BnBwdFusedGeom& geo) {
     BnFusedBwdArgs<NB> f;
-    f.sync = reinterpret_cast<GridSync*>(fA.sync); f.err = fA.err; f.count = fA.count; f.frozen = fA.frozen;
+    f.sync = reinterpret_cast<GridSync*>(f0.sync); f.err = f0.err; f.count = f0.count; f.frozen = f0.frozen;
     f.iters = geo.iters;
     f.keep_g = geo.keep[0];
     for (int n = 0; n < NB; ++n) {
-        const BnFusedBwd& side = n ? B->f : fA;
+        BnBwdSide side = f0.s[n];
+        if (n == 0) { side.z = p.z; side.mean = p.mean; side.rstd = p.rstd; side.dz = p.dz; }
         f.keep_z[n] = geo.keep[1 + n];
         f.rows[n] = side.rows; f.gamma[n] = side.gamma; f.dgamma[n] = side.dgamma; f.dbeta[n] = side.dbeta;
-        f.z[n] = n ? B->z : p.z; f.mean[n] = n ? B->mean : p.mean; f.rstd[n] = n ? B->rstd : p.rstd; f.dz[n] = n ? B->dz : p.dz;
+        f.z[n] = side.z; f.mean[n] = side.mean; f.rstd[n] = side.rstd; f.dz[n] = side.dz;
     }
     return f;
 }
 
-// p: BatchNorm A as for vpd_launch_bn_bwd_fused (dy, act, z, mean, rstd, dz + geometry); fA: its rows, gamma, dgamma, dbeta
-// (fA.sync / err / count are used); B: the second BatchNorm
-hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p0, const BnFusedBwd& fA, const BnBwdSecond& B, hipStream_t s) {
+// p: BatchNorm A as for vpd_launch_bn_bwd_fused (dy, act, z, mean, rstd, dz + geometry); f.s[0]: its rows, gamma, dgamma, dbeta;
+// f.s[1]: the second BatchNorm
+hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p0, const BnFusedBwd& f0, hipStream_t s) {
     BnBwdParams p = p0;
     if (!p.act) return hipErrorInvalidValue;
     const BnBwdFusedGeom geo = vpd_bn_bwd_fused_geom(p.M, p.C, 3);
     p.ppb = geo.ppb;
-    const BnFusedBwdArgs<2> f = bn_bwd_fused_args<2>(p, fA, &B, geo);
+    const BnFusedBwdArgs<2> f = bn_bwd_fused_args<2>(p, f0, geo);
     hipLaunchKernelGGL(bn_bwd_fused2_kernel, dim3(geo.G), dim3(1024), geo.lds, s, p, f);
     return hipGetLastError();
 }
@@ -1345,7 +1347,7 @@ hipError_t vpd_launch_bn_bwd_fused(const BnBwdParams& p0, const BnFusedBwd& f0, 
     const BnBwdFusedGeom geo = vpd_bn_bwd_fused_geom(p.M, p.C, 2);
     const int G = geo.G;
     p.ppb = geo.ppb;
-    const BnFusedBwdArgs<1> f = bn_bwd_fused_args<1>(p, f0, nullptr, geo);
+    const BnFusedBwdArgs<1> f = bn_bwd_fused_args<1>(p, f0, geo);
     const int mask = p.mask_bits ? 3 : (p.act ? 1 : (p.mscale ? 2 : 0));
     if (!f.keep_g && mask == 1 && !p.write_g) return hipErrorInvalidValue;
     const size_t lds = geo.lds;

@@ -1644,7 +1644,7 @@ bool vpd_conv_takes_bn_sums(const ConvParams& p) {
 }
 
 // Every decision of vpd_launch_conv that depends on the problem, the device and the switches, in one place: the launcher
-// below only maps the result to template instantiations, and vpd_op_conv2d_dispatch (plan.hip) reports it to the tests.
+// below only maps the result to template instantiations, and vpd_op_conv2d_dispatch (ops.hip) reports it to the tests.
 ConvDispatch vpd_conv_dispatch(const ConvParams& p, HaloGeom* g) {
     ConvDispatch d = {};
     d.mode = conv_ep_mode(p);

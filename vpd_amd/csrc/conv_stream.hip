@@ -730,7 +730,7 @@ bool vpd_conv1x1_bn_eligible(const ConvParams& p) {
 }
 
 namespace {
-// what the BatchNorms of a launch share; mode 3 writes every dz padded by dzpad
+// what the BatchNorms of a launch share; BN_TAIL_BWD_APPLY writes every dz padded by dzpad
 StreamBn stream_bn(float count, float momentum, float eps, unsigned char* mask_out, const ConvParams& p, int dzpad) {
     StreamBn bn;
     memset(&bn, 0, sizeof bn);
@@ -738,112 +738,114 @@ StreamBn stream_bn(float count, float momentum, float eps, unsigned char* mask_o
     bn.dzHp = p.Hs + 2 * dzpad; bn.dzWp = p.Ws + 2 * dzpad; bn.dzpad = dzpad;
     return bn;
 }
-// mode 1: one BatchNorm of a BnFusedFwd (its first or its second field set)
-StreamBnSide stream_side_fwd(const double* rows, const float* gamma, const float* beta, float* mean, float* rstd, float* scale,
-                             float* shift, float* rm, float* rv) {
+// BN_TAIL_FWD: one BatchNorm of a BnFusedFwd
+StreamBnSide stream_side_fwd(const BnFwdSide& f) {
     StreamBnSide s;
     memset(&s, 0, sizeof s);
-    s.rows = rows; s.gamma = gamma; s.beta = beta; s.mean = mean; s.rstd = rstd; s.scale = scale; s.shift = shift; s.rm = rm; s.rv = rv;
+    s.rows = f.rows; s.gamma = f.gamma; s.beta = f.beta; s.mean = f.mean; s.rstd = f.rstd; s.scale = f.scale; s.shift = f.shift;
+    s.rm = f.rm; s.rv = f.rv;
     return s;
 }
-// mode 2: the rows to add to; mode 3: the same rows to finalize, with the forward's mean / rstd and the dz to write
-StreamBnSide stream_side_bwd(const BnFusedBwd& b, const float* mean, const float* rstd, bf16_t* dz, int mode) {
+// BN_TAIL_BWD_SUMS: the rows to add to; BN_TAIL_BWD_APPLY: the same rows to finalize, with the forward's mean / rstd and the dz to write
+StreamBnSide stream_side_bwd(const BnBwdSide& b, BnTailPass pass) {
     StreamBnSide s;
     memset(&s, 0, sizeof s);
-    if (mode == 2) { s.rows_out = b.rows; return s; }
+    if (pass == BN_TAIL_BWD_SUMS) { s.rows_out = b.rows; return s; }
     s.rows = b.rows; s.gamma = b.gamma; s.dgamma = b.dgamma; s.dbeta = b.dbeta;
-    s.mean = const_cast<float*>(mean); s.rstd = const_cast<float*>(rstd); s.dz = dz;
+    s.mean = const_cast<float*>(b.mean); s.rstd = const_cast<float*>(b.rstd); s.dz = b.dz;
     return s;
 }
-// modes 2 and 3 read p.y = d(out), dense, with its bit map
+// what a forward / a backward launch's BatchNorms share
+StreamBn stream_bn_fwd(const BnTailLaunch& t, const ConvParams& p) {
+    StreamBn bn = stream_bn(t.fwd->count, t.fwd->momentum, t.fwd->eps, t.mask_out, p, 0);
+    bn.frozen = t.fwd->frozen;
+    return bn;
+}
+StreamBn stream_bn_bwd(const BnTailLaunch& t, const ConvParams& p) {
+    StreamBn bn = stream_bn(t.bwd->count, 0.f, 0.f, nullptr, p, t.dzpad);
+    bn.frozen = t.bwd->frozen;
+    return bn;
+}
+bool stream_side_apply_ok(const BnBwdSide& b) { return b.dz && b.mean && b.rstd; }
+// the backward passes read p.y = d(out), dense, with its bit map
 bool stream_bwd_operands(const ConvParams& p) {
     return p.y && p.acc_mask && p.ypad == 0 && p.yC == p.Co && p.yHp == p.Hs && p.yWp == p.Ws;
 }
 
 template <int KC, int NSA>
-hipError_t launch_bn_stream(const ConvParams& p, const StreamBn& bn, int mode, hipStream_t stream) {
+hipError_t launch_bn_stream(const ConvParams& p, const StreamBn& bn, BnTailPass pass, hipStream_t stream) {
     constexpr int BM = TAIL_BM, BN = TAIL_BN;
     const StreamGeo sg = stream_geo(p, BM);
     const int NT = p.Co / BN;
     const dim3 grid(stream_lanes(sg.mtiles, NT), NT), block(TAIL_THREADS);
     constexpr size_t lds = stream_lds_bytes(KC, BM, BN, NSA, 3);
-    switch (mode) {
+    switch (pass) {
         // (four MFMA waves as the storing launch: the same pixels per lane, so the same fp32 partial sums -- the fused forward is
         //  bit-identical to conv + BatchNorm launches; eight waves were no faster here, 16.4-18.2 vs 17.8-19.4 us)
-        case 0: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 4>), grid, dim3(512), lds, stream, p, sg); break;
-        case 1: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 1>), grid, block, lds, stream, p, sg, bn); break;
-        case 2: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 2>), grid, block, lds, stream, p, sg, bn); break;
-        case 3: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 3>), grid, block, lds, stream, p, sg, bn); break;
+        case BN_TAIL_STATS: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 4>), grid, dim3(512), lds, stream, p, sg); break;
+        case BN_TAIL_FWD: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 1>), grid, block, lds, stream, p, sg, bn); break;
+        case BN_TAIL_BWD_SUMS: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 2>), grid, block, lds, stream, p, sg, bn); break;
+        case BN_TAIL_BWD_APPLY: VPD_LAUNCH((conv1x1_bn_stream_kernel<KC, NSA, 3>), grid, block, lds, stream, p, sg, bn); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 }  // namespace
 
-// mode 0: statistics of z = conv(x) into p.stats (VPD_FUSED_ROWS rows), nothing stored
-// mode 1: out = relu(BatchNorm(z) + p.res) into p.y (padded) + ReLU bit map; finalizes f.rows (mean / rstd / scale / shift / running)
-// mode 2: sums of the BatchNorm backward (g = p.y * p.acc_mask; p.y dense d(out)) into f.rows
-// mode 3: dz = A g + B z + D into `dz` (padded by dzpad); dgamma / dbeta
-hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd, const float* mean,
-                                 const float* rstd, unsigned char* mask_out, bf16_t* dz, int dzpad, int mode, hipStream_t stream) {
+// one pass (BnTailPass, kernels.h) of the tail: t.fwd->s[0] / t.bwd->s[0] is the BatchNorm
+hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnTailLaunch& t, hipStream_t stream) {
     if (!vpd_conv1x1_bn_eligible(p)) return hipErrorInvalidValue;
     StreamBn bn = stream_bn(0.f, 0.f, 0.f, nullptr, p, 0);
-    if (mode == 0) {
+    if (t.pass == BN_TAIL_STATS) {
         if (!p.stats || p.stat_rows != VPD_FUSED_ROWS) return hipErrorInvalidValue;
-    } else if (mode == 1) {
-        if (!fwd || !p.res || !p.y || p.ypad != 1 || p.yC != p.Co || p.rC != p.Co) return hipErrorInvalidValue;
-        if (fwd->frozen && (!fwd->rm || !fwd->rv)) return hipErrorInvalidValue;
-        bn = stream_bn(fwd->count, fwd->momentum, fwd->eps, mask_out, p, 0);
-        bn.frozen = fwd->frozen;
-        bn.s = stream_side_fwd(fwd->rows, fwd->gamma, fwd->beta, fwd->mean, fwd->rstd, fwd->scale, fwd->shift, fwd->rm, fwd->rv);
+    } else if (t.pass == BN_TAIL_FWD) {
+        if (!t.fwd || !p.res || !p.y || p.ypad != 1 || p.yC != p.Co || p.rC != p.Co) return hipErrorInvalidValue;
+        if (t.fwd->frozen && (!t.fwd->s[0].rm || !t.fwd->s[0].rv)) return hipErrorInvalidValue;
+        bn = stream_bn_fwd(t, p);
+        bn.s = stream_side_fwd(t.fwd->s[0]);
     } else {
-        if (!bwd || !stream_bwd_operands(p)) return hipErrorInvalidValue;
-        if (mode == 3 && (!dz || !mean || !rstd)) return hipErrorInvalidValue;
-        bn = stream_bn(bwd->count, 0.f, 0.f, nullptr, p, dzpad);
-        bn.frozen = bwd->frozen;
-        bn.s = stream_side_bwd(*bwd, mean, rstd, dz, mode);
+        if (!t.bwd || !stream_bwd_operands(p)) return hipErrorInvalidValue;
+        if (t.pass == BN_TAIL_BWD_APPLY && !stream_side_apply_ok(t.bwd->s[0])) return hipErrorInvalidValue;
+        bn = stream_bn_bwd(t, p);
+        bn.s = stream_side_bwd(t.bwd->s[0], t.pass);
     }
-    if (p.Kc == 64) return launch_bn_stream<64, BN_NSA_K64>(p, bn, mode, stream);
-    return launch_bn_stream<128, BN_NSA_K128>(p, bn, mode, stream);
+    if (p.Kc == 64) return launch_bn_stream<64, BN_NSA_K64>(p, bn, t.pass, stream);
+    return launch_bn_stream<128, BN_NSA_K128>(p, bn, t.pass, stream);
 }
 
 // ---- ... of a down-sampling Bottleneck with two 64-channel stride-1 1x1 convolutions (conv1x1_bn2_stream_kernel): p.x / p.w =
-// the closing convolution, p.x2 / p.w2 = the branch (same padded input geometry).  fwd: rows / ... = BatchNorm3, rows2 / ... = the
-// branch's; bwd3 / bwdD likewise.  Modes 1..3 as vpd_launch_conv1x1_bn (the statistics passes are two mode-0 launches of that).
+// the closing convolution, p.x2 / p.w2 = the branch (same padded input geometry).  t.fwd / t.bwd: s[0] = BatchNorm3, s[1] = the
+// branch's.  Every pass but BN_TAIL_STATS (the statistics passes are two launches of vpd_launch_conv1x1_bn).
 bool vpd_conv1x1_bn2_eligible(const ConvParams& p) {
     if (!(p.x2 && p.w2 && p.Kc == 64 && p.Kc2 == 64 && p.Co == TAIL_BN)) return false;
     ConvParams q = p;
     q.x2 = nullptr; q.w2 = nullptr; q.Kc2 = 0;
     return vpd_conv1x1_bn_eligible(q);
 }
-hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd3, const BnFusedBwd* bwdD,
-                                  const float* mean3, const float* rstd3, const float* meanD, const float* rstdD,
-                                  unsigned char* mask_out, bf16_t* dz3, bf16_t* dzD, int dzpad, int mode, hipStream_t stream) {
+hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnTailLaunch& t, hipStream_t stream) {
     if (!vpd_conv1x1_bn2_eligible(p)) return hipErrorInvalidValue;
     StreamBn bn;
     StreamBnSide bd;
-    if (mode == 1) {
-        if (!fwd || !fwd->rows2 || !p.y || p.ypad != 1 || p.yC != p.Co) return hipErrorInvalidValue;
-        if (fwd->frozen && (!fwd->rm || !fwd->rv || !fwd->rm2 || !fwd->rv2)) return hipErrorInvalidValue;
-        bn = stream_bn(fwd->count, fwd->momentum, fwd->eps, mask_out, p, 0);
-        bn.frozen = fwd->frozen;
-        bn.s = stream_side_fwd(fwd->rows, fwd->gamma, fwd->beta, fwd->mean, fwd->rstd, fwd->scale, fwd->shift, fwd->rm, fwd->rv);
-        bd = stream_side_fwd(fwd->rows2, fwd->gamma2, fwd->beta2, fwd->mean2, fwd->rstd2, fwd->scale2, fwd->shift2, fwd->rm2, fwd->rv2);
-    } else if (mode == 2 || mode == 3) {
-        if (!bwd3 || !bwdD || !stream_bwd_operands(p)) return hipErrorInvalidValue;
-        if (mode == 3 && (!dz3 || !dzD || !mean3 || !rstd3 || !meanD || !rstdD)) return hipErrorInvalidValue;
-        bn = stream_bn(bwd3->count, 0.f, 0.f, nullptr, p, dzpad);
-        bn.frozen = bwd3->frozen;
-        bn.s = stream_side_bwd(*bwd3, mean3, rstd3, dz3, mode);
-        bd = stream_side_bwd(*bwdD, meanD, rstdD, dzD, mode);
+    if (t.pass == BN_TAIL_FWD) {
+        if (!t.fwd || !t.fwd->s[1].rows || !p.y || p.ypad != 1 || p.yC != p.Co) return hipErrorInvalidValue;
+        if (t.fwd->frozen && (!t.fwd->s[0].rm || !t.fwd->s[0].rv || !t.fwd->s[1].rm || !t.fwd->s[1].rv)) return hipErrorInvalidValue;
+        bn = stream_bn_fwd(t, p);
+        bn.s = stream_side_fwd(t.fwd->s[0]);
+        bd = stream_side_fwd(t.fwd->s[1]);
+    } else if (t.pass == BN_TAIL_BWD_SUMS || t.pass == BN_TAIL_BWD_APPLY) {
+        if (!t.bwd || !t.bwd->s[1].rows || !stream_bwd_operands(p)) return hipErrorInvalidValue;
+        if (t.pass == BN_TAIL_BWD_APPLY && !(stream_side_apply_ok(t.bwd->s[0]) && stream_side_apply_ok(t.bwd->s[1]))) return hipErrorInvalidValue;
+        bn = stream_bn_bwd(t, p);
+        bn.s = stream_side_bwd(t.bwd->s[0], t.pass);
+        bd = stream_side_bwd(t.bwd->s[1], t.pass);
     } else return hipErrorInvalidValue;
     constexpr int BM = TAIL_BM, BN = TAIL_BN, NSA = BN2_NSA;
     const StreamGeo sg = stream_geo(p, BM);
     const dim3 grid(stream_lanes(sg.mtiles, 1), 1), block(TAIL_THREADS);
     constexpr size_t lds = stream_lds_bytes(128, BM, BN, NSA, 6);
-    switch (mode) {
-        case 1: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 1>), grid, block, lds, stream, p, sg, bn, bd); break;
-        case 2: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 2>), grid, block, lds, stream, p, sg, bn, bd); break;
+    switch (t.pass) {
+        case BN_TAIL_FWD: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 1>), grid, block, lds, stream, p, sg, bn, bd); break;
+        case BN_TAIL_BWD_SUMS: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 2>), grid, block, lds, stream, p, sg, bn, bd); break;
         default: VPD_LAUNCH((conv1x1_bn2_stream_kernel<NSA, 3>), grid, block, lds, stream, p, sg, bn, bd); break;
     }
     return hipGetLastError();

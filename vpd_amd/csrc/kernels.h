@@ -1,5 +1,7 @@
 // Host-side launcher declarations for the HIP kernels (internal to libvpdhip).
 #pragma once
+#include <string.h>
+
 #include <vector>
 
 #include "common.h"
@@ -142,43 +144,52 @@ hipError_t vpd_launch_bn_bwd(const BnBwdParams& p, float count, const float* gam
 hipError_t vpd_launch_stem_pool_bwd(const StemPoolBwdParams& p, float count, const float* gamma, float* dgamma,
                                     float* dbeta, float* coef, bf16_t* dz, hipStream_t s, bool frozen = false);
 
-// fused BatchNorm passes (bn.hip): per-BatchNorm accumulator rows [VPD_FUSED_ROWS][2][C] of doubles, zeroed by the caller
-struct BnFusedFwd {
-    double* rows; float count; const float* gamma; const float* beta; float* rm; float* rv;
+// fused BatchNorm passes (bn.hip, conv_stream.hip).  A launch serves one BatchNorm or two (a down-sampling block's own and its 1x1
+// branch's: s[1], absent when its rows are null); what the kernels take once -- count, frozen, the barrier words -- the launch owns.
+// rows: per-BatchNorm accumulator rows [VPD_FUSED_ROWS][2][C] of doubles, zeroed by the caller
+struct BnFwdSide {
+    double* rows; const float* gamma; const float* beta; float* rm; float* rv;
     float* mean; float* rstd; float* scale; float* shift;
-    double* rows2; float count2; const float* gamma2; const float* beta2; float* rm2; float* rv2;      // residual BN or null
-    float* mean2; float* rstd2; float* scale2; float* shift2;
-    float momentum, eps;
-    // frozen BatchNorm: mean = rm, rstd = 1 / sqrt(rv + eps) (both BatchNorms; rm / rv are then required, read and left unwritten);
+};
+struct BnFusedFwd {
+    BnFwdSide s[2];
+    float count, momentum, eps;
+    // frozen BatchNorm: mean = rm, rstd = 1 / sqrt(rv + eps) (every side; rm / rv are then required, read and left unwritten);
     // mean / rstd / scale / shift are stored as always, so the backward's masks and xhat see what the forward used
     int frozen;
 };
-struct BnFusedBwd {
-    double* rows; void* sync; unsigned* err;    // sync: VPD_GRID_SYNC_BYTES, zeroed; err: sticky time-out counter
-    const float* gamma; float* dgamma; float* dbeta; float count;
-    // the forward was frozen: dz = gamma rstd g (the batch-mean terms drop out), dgamma / dbeta unchanged.  A launch that serves
-    // two BatchNorms takes the first one's flag for both
-    int frozen;
+// z / mean / rstd / dz: the bn.hip launchers take s[0]'s from their BnBwdParams (a kernel argument) and read these for s[1] only, dz in
+// the same padded geometry; the Bottleneck-tail launchers recompute z and read mean / rstd / dz of every side
+struct BnBwdSide {
+    double* rows; const float* gamma; float* dgamma; float* dbeta;
+    const bf16_t* z; const float* mean; const float* rstd; bf16_t* dz;
 };
-// the second BatchNorm of a launch that serves two with the same masked gradient (a down-sampling block's 1x1 branch): same
-// shape as the first, dz in the same padded geometry; f.sync / err / count are not read (the first BatchNorm's serve the launch)
-struct BnBwdSecond {
-    BnFusedBwd f;
-    const bf16_t* z; const float* mean; const float* rstd;
-    bf16_t* dz;
+struct BnFusedBwd {
+    BnBwdSide s[2];
+    float count;
+    int frozen;                                 // the forward was frozen: dz = gamma rstd g (the batch-mean terms drop out), dgamma / dbeta unchanged
+    void* sync; unsigned* err;                  // launches with a grid barrier: VPD_GRID_SYNC_BYTES, zeroed; sticky time-out counter
 };
 #define VPD_GRID_SYNC_BYTES (18 * 128)
 hipError_t vpd_launch_bn_fwd_fused(const BnApplyParams& p, const BnFusedFwd& f, hipStream_t s);
 // conv_stream.hip: a Bottleneck's closing 1x1 convolution with its train-mode BatchNorm, the convolution recomputed instead of
-// written and read back (modes: 0 statistics only, 1 forward apply, 2 backward sums, 3 backward apply)
+// written and read back, one pass per launch
+enum BnTailPass {
+    BN_TAIL_STATS = 0,          // statistics of z = conv(x) into p.stats (VPD_FUSED_ROWS rows), nothing stored
+    BN_TAIL_FWD = 1,            // out = relu(BatchNorm(z) + p.res) into p.y (padded) + ReLU bit map; finalizes fwd's rows
+    BN_TAIL_BWD_SUMS = 2,       // sums of the BatchNorm backward (g = p.y * p.acc_mask; p.y dense d(out)) into bwd's rows
+    BN_TAIL_BWD_APPLY = 3,      // dz = A g + B z + D into each side's dz (padded by dzpad); dgamma / dbeta
+};
+struct BnTailLaunch {
+    BnTailPass pass;
+    const BnFusedFwd* fwd; unsigned char* mask_out;      // BN_TAIL_FWD (mask_out [M][Co / 8] may be null)
+    const BnFusedBwd* bwd; int dzpad;                    // BN_TAIL_BWD_*
+};
 bool vpd_conv1x1_bn_eligible(const ConvParams& p);
 // ... of a down-sampling Bottleneck whose closing 1x1 conv (p.x, p.w) and 1x1 branch (p.x2, p.w2) both have 64 input channels, stride 1
 bool vpd_conv1x1_bn2_eligible(const ConvParams& p);
-hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd3, const BnFusedBwd* bwdD,
-                                  const float* mean3, const float* rstd3, const float* meanD, const float* rstdD,
-                                  unsigned char* mask_out, bf16_t* dz3, bf16_t* dzD, int dzpad, int mode, hipStream_t stream);
-hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnFusedFwd* fwd, const BnFusedBwd* bwd, const float* mean,
-                                 const float* rstd, unsigned char* mask_out, bf16_t* dz, int dzpad, int mode, hipStream_t stream);
+hipError_t vpd_launch_conv1x1_bn(const ConvParams& p, const BnTailLaunch& t, hipStream_t stream);
+hipError_t vpd_launch_conv1x1_bn2(const ConvParams& p, const BnTailLaunch& t, hipStream_t stream);      // (no BN_TAIL_STATS: two launches of the above)
 // (reporting) the grid of those launches for an eligible p: {pixel lanes, channel tiles, pixel tiles of the busiest block, ring depth}
 void vpd_conv1x1_bn_grid(const ConvParams& p, bool two, int out4[4]);
 bool vpd_bn_bwd_fused_ok(int M, int C, bool mask_act, bool write_g);
@@ -187,13 +198,70 @@ bool vpd_bn_bwd_fused_ok(int M, int C, bool mask_act, bool write_g);
 struct BnBwdFusedGeom { int G, ppb, iters, keep[3]; size_t lds; };
 BnBwdFusedGeom vpd_bn_bwd_fused_geom(int M, int C, int nt);
 hipError_t vpd_launch_bn_bwd_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s);
-// BatchNorm backward whose sums (sum g, sum g * z) the producing data gradient's epilogue has already added to `f.rows`
+// BatchNorm backward whose sums (sum g, sum g * z) the producing data gradient's epilogue has already added to the rows
 // (ConvParams::bst_z): finalize + apply in one launch, no reduction pass, no grid barrier.  p.mask_bits is required.
-// B: a second BatchNorm fed with the same masked gradient
-hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s, const BnBwdSecond* B = nullptr);
+// f.s[1] present: a second BatchNorm fed with the same masked gradient
+hipError_t vpd_launch_bn_bwd_apply_fused(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s);
 // two BatchNorm backwards sharing dy and the ReLU mask (a down-sampling block's conv2 BN + its 1x1 branch's BN) in one launch
 bool vpd_bn_bwd_fused2_ok(int M, int C);
-hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p, const BnFusedBwd& fA, const BnBwdSecond& B, hipStream_t s);
+hipError_t vpd_launch_bn_bwd_fused2(const BnBwdParams& p, const BnFusedBwd& f, hipStream_t s);
+
+// ---- geometry constructors: the descriptors above as the step (step.hip) and the operator entry points (ops.hip) fill them ----
+// dense z [n][H][W][C] -> BatchNorm (+ res, ReLU) -> out padded by 1; res: padded by 1 (res_kind 1) or dense like z (2)
+inline BnApplyParams vpd_bn_apply_params(const bf16_t* z, int res_kind, const bf16_t* res, bf16_t* out, int n, int H, int W, int C,
+                                         int relu) {
+    BnApplyParams a;
+    memset(&a, 0, sizeof a);
+    a.z = z;
+    a.res_kind = res_kind; a.res = res; a.rHp = H + 2; a.rWp = W + 2; a.rpad = 1;
+    a.out = out; a.oHp = H + 2; a.oWp = W + 2; a.opad = 1;
+    a.M = n * H * W; a.H = H; a.W = W; a.C = C; a.relu = relu;
+    return a;
+}
+// dense dy [n][H][W][C] -> BatchNorm backward -> dz padded by dzpad
+inline BnBwdParams vpd_bn_bwd_params(const bf16_t* dy, const bf16_t* z, const float* mean, const float* rstd, bf16_t* dz, int dzpad,
+                                     int n, int H, int W, int C) {
+    BnBwdParams b;
+    memset(&b, 0, sizeof b);
+    b.dy = dy; b.z = z; b.mean = mean; b.rstd = rstd;
+    b.dz = dz; b.dzHp = H + 2 * dzpad; b.dzWp = W + 2 * dzpad; b.dzpad = dzpad;
+    b.M = n * H * W; b.H = H; b.W = W; b.C = C;
+    return b;
+}
+// ... whose dy may be rewritten with g, its ReLU mask the stored activation (padded by 1) or null
+inline void vpd_bn_bwd_set_act(BnBwdParams& b, bf16_t* dy_rw, const bf16_t* act) {
+    b.dy_rw = dy_rw; b.act = act; b.aHp = b.H + 2; b.aWp = b.W + 2; b.apad = 1;
+}
+// padded x -> Hs x Ws output pixels per image through `taps`, every pixel of a dense y [n][Hs][Ws][Co] (y itself: the caller's)
+inline ConvParams vpd_conv_params(const bf16_t* x, int xHp, int xWp, int xC, const bf16_t* w, int n, int Hs, int Ws, int istr, int Kc,
+                                  int Co, const TapSet& taps) {
+    ConvParams q;
+    memset(&q, 0, sizeof q);
+    q.x = x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.w = w;
+    q.yHp = Hs; q.yWp = Ws; q.yC = Co; q.ypad = 0;
+    q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = 1; q.istr = istr;
+    q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws;
+    q.taps = taps;
+    return q;
+}
+inline void vpd_conv_set_y(ConvParams& q, bf16_t* y, int ypad) {      // y padded by ypad
+    q.y = y; q.yHp = q.Hs + 2 * ypad; q.yWp = q.Ws + 2 * ypad; q.ypad = ypad;
+}
+inline void vpd_conv_set_res(ConvParams& q, const bf16_t* res) {      // residual shaped like the output, padded by 1
+    q.res = res; q.rHp = q.Hs + 2; q.rWp = q.Ws + 2; q.rC = q.Co; q.rpad = 1;
+}
+inline void vpd_conv_set_bn_rows(ConvParams& q, double* rows) {       // statistics into a fused BatchNorm's own rows
+    q.stats = rows; q.stat_rows = VPD_FUSED_ROWS;
+}
+inline TapSet vpd_taps_1x1() {      // one tap at padded offset (1, 1): a 1x1 convolution of an input with a border of 1
+    TapSet t;
+    t.nr = 1; t.nc = 1; t.dy0 = 1; t.dys = 1; t.dx0 = 1; t.dxs = 1; t.w0 = 0; t.wrs = 1; t.wcs = 1;
+    return t;
+}
+// a Bottleneck's closing 1x1 convolution (the tail launchers above): x padded by 1 with Kc channels, H x W output pixels
+inline ConvParams vpd_conv1x1_params(const bf16_t* x, const bf16_t* w, int n, int H, int W, int istr, int Kc, int Co) {
+    return vpd_conv_params(x, H * istr + 2, W * istr + 2, Kc, w, n, H, W, istr, Kc, Co, vpd_taps_1x1());
+}
 
 // conv_stem_dgrad.hip: the stem convolution's data gradient, dz dense NHWC [N][H/2][W/2][64] -> dx fp32 NCHW [N][Cin][H][W]
 // (H, W even and >= 32, Cin <= 8; w_oihw: the fp32 master weight, rounded to the element type in the kernel)

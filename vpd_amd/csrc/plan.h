@@ -1,5 +1,5 @@
-// Private to plan.hip (the plan: topology, workspace layout, tables, query / setter entry points) and step.hip (the passes that
-// launch on it).  Not part of the public ABI.
+// Private to plan.hip (the plan: topology, workspace layout, tables, query / setter entry points), step.hip (the passes that
+// launch on it) and ops.hip (the single-operator entry points).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -143,6 +143,12 @@ struct vpd_plan {
 // min_n = 0 for the train-step entry points: a data-parallel rank whose shard of a ragged last batch is empty still
 // takes part in the step (zero loss, zero gradients, bucket events recorded) so that the collective stays matched
 int check_call(const vpd_plan* p, const void* ws, int n, int min_n = 1);
+
+// plan.hip: the pack descriptors and block maps of a plan, and -- one construction -- of the operator entry points (ops.hip)
+void set_pack_geom(ConvInfo& c, int Ci, int Co, int k, bool stem);
+int push_pack_desc(std::vector<PackDesc>& descs, std::vector<int>& bmap_pack, std::vector<int>& bmap_unpack, const ConvInfo& c);
+void build_adam_map(std::vector<PackDesc>& descs, const std::vector<int>& bmap_pack, int stem_id, long long nparam_padded,
+                    std::vector<int>& bmap_adam, int& nstem_pack_blocks);
 
 inline TapSet conv_taps_fwd(const ConvInfo& c) {
     TapSet t;

@@ -1,6 +1,7 @@
 // Network plan: owns the static description of the student (ResNet-18/34 BasicBlock or
 // ResNet-50/101 / wide Bottleneck encoder + optional motion MLP), the workspace layout and tables, and the query, setter,
-// workspace, optimizer and single-operator entry points of include/vpd_hip.h.  The passes that launch on it: step.hip.
+// workspace and optimizer entry points of include/vpd_hip.h.  The passes that launch on it: step.hip; the single-operator entry
+// points of the parity tests: ops.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -50,6 +51,8 @@ void add_tensor(vpd_plan* p, int kind, int is_dec, long long numel, int ndim, in
     *off_out = p->nparam;
     p->nparam += numel;
 }
+
+}  // namespace
 
 // packed-weight geometry of a conv: the stem keeps one tap per kernel ROW, its 7 column taps x 8 channels in a 64-wide K
 void set_pack_geom(ConvInfo& c, int Ci, int Co, int k, bool stem) {
@@ -108,6 +111,8 @@ void build_adam_map(std::vector<PackDesc>& descs, const std::vector<int>& bmap_p
     for (auto& cv : convs) { plain(pos, cv.first); pos = cv.first + cv.second; }
     plain(pos, nparam_padded);
 }
+
+namespace {
 
 void add_conv(vpd_plan* p, ConvInfo& c, int Ci, int Co, int k, int stride, int pad, int Hin, int Win, bool stem) {
     set_pack_geom(c, Ci, Co, k, stem);
@@ -813,727 +818,3 @@ extern "C" int vpd_plan_read_timing(vpd_plan_t* p, double* out, int nclasses) {
     return 0;
 }
 
-// ---------------------------------------------------------------------------
-// single-operator entry points for the parity tests
-// ---------------------------------------------------------------------------
-// frozen BatchNorm for the BatchNorm entry points below (vpd_op_set_bn_frozen): process-wide, read by them alone -- no plan looks here
-static int g_op_bn_frozen = 0;
-extern "C" int vpd_op_set_bn_frozen(int on) { g_op_bn_frozen = on != 0; return 0; }
-
-extern "C" int vpd_op_conv_bm(int M, int Co) { return vpd_conv_bm(M, Co); }
-extern "C" size_t vpd_op_wgrad_slab_bytes(void) { return vpd_wgrad_slab_bytes(); }
-
-static TapSet tapset_from(const int* t) {
-    TapSet ts;
-    ts.nr = t[0]; ts.nc = t[1]; ts.dy0 = t[2]; ts.dys = t[3]; ts.dx0 = t[4]; ts.dxs = t[5];
-    ts.w0 = t[6]; ts.wrs = t[7]; ts.wcs = t[8];
-    return ts;
-}
-
-extern "C" int vpd_op_conv2d(const void* x, const void* w, void* y, double* stats, int n, int xHp, int xWp, int xC,
-                             int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub, int oph, int opw, int istr,
-                             int Kc, int Co, const int* tapset9, int accumulate, void* stream) {
-    ConvParams q;
-    memset(&q, 0, sizeof q);
-    q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.w = (const bf16_t*)w;
-    q.y = (bf16_t*)y; q.yHp = yHp; q.yWp = yWp; q.yC = yC; q.ypad = ypad; q.stats = stats;
-    q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = osub; q.oph = oph; q.opw = opw; q.istr = istr;
-    q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws; q.accumulate = accumulate;
-    q.taps = tapset_from(tapset9);
-    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
-    LCHECK(vpd_launch_conv(q, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_conv2d_ep(const void* x, const void* w, void* y, int n, int xHp, int xWp, int xC, int yHp, int yWp,
-                                int yC, int ypad, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
-                                const float* ep_scale, const float* ep_shift, const void* res_padded, int ep_relu,
-                                int accumulate, const unsigned char* acc_mask, void* stream) {
-    if ((ep_scale == nullptr) != (ep_shift == nullptr)) return fail("ep_scale and ep_shift come together");
-    if (ep_scale && accumulate) return fail("eval epilogue or accumulate, not both");
-    if (res_padded && !ep_scale) return fail("a residual needs the eval epilogue");
-    if (acc_mask && (!accumulate || ypad != 0 || yC != Co || yHp != Hs || yWp != Ws)) return fail("acc_mask: accumulate onto a dense y");
-    ConvParams q;
-    memset(&q, 0, sizeof q);
-    q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.w = (const bf16_t*)w;
-    q.y = (bf16_t*)y; q.yHp = yHp; q.yWp = yWp; q.yC = yC; q.ypad = ypad;
-    q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = 1; q.istr = istr;
-    q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws; q.accumulate = accumulate; q.acc_mask = acc_mask;
-    q.ep_scale = ep_scale; q.ep_shift = ep_shift; q.ep_relu = ep_relu;
-    if (res_padded) { q.res = (const bf16_t*)res_padded; q.rHp = Hs + 2; q.rWp = Ws + 2; q.rC = Co; q.rpad = 1; }
-    q.taps = tapset_from(tapset9);
-    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
-    LCHECK(vpd_launch_conv(q, (hipStream_t)stream));
-    return 0;
-}
-
-static int op_conv2d_bnsums(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask, double* rows,
-                            const void* bst_z2, double* rows2, int n, int xHp, int xWp, int xC, int Hs, int Ws, int Kc, int Co,
-                            const int* tapset9, int accumulate, void* stream) {
-    if (!x || !w || !y || !bst_z || !bst_mask || !rows || !tapset9) return fail("null argument");
-    if (n < 1 || Hs < 1 || Ws < 1 || Kc < 64 || Kc % 64 || Co < 64 || Co % 64) return fail("bad argument");
-    ConvParams q;
-    memset(&q, 0, sizeof q);
-    q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.w = (const bf16_t*)w;
-    q.y = (bf16_t*)y; q.yHp = Hs; q.yWp = Ws; q.yC = Co; q.ypad = 0;
-    q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = 1; q.istr = 1;
-    q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws; q.accumulate = accumulate;
-    q.bst_z = (const bf16_t*)bst_z; q.bst_mask = bst_mask; q.stats = rows; q.stat_rows = VPD_FUSED_ROWS;
-    q.bst_z2 = (const bf16_t*)bst_z2; q.stats2 = rows2;
-    q.taps = tapset_from(tapset9);
-    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
-    if (!vpd_conv_takes_bn_sums(q)) return fail("no kernel takes the BatchNorm sums for this shape");
-    LCHECK(vpd_launch_conv(q, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_conv2d_bnsums(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask,
-                                    double* rows, int n, int xHp, int xWp, int xC, int Hs, int Ws, int Kc, int Co,
-                                    const int* tapset9, int accumulate, void* stream) {
-    return op_conv2d_bnsums(x, w, y, bst_z, bst_mask, rows, nullptr, nullptr, n, xHp, xWp, xC, Hs, Ws, Kc, Co, tapset9, accumulate, stream);
-}
-
-// epilogue mode 8: the accumulating data gradient of a stage's first block, whose d feeds TWO BatchNorms (bn2 of the block before
-// through z / rows, the 1x1 branch's through z2 / rows2) under the same ReLU bit map
-extern "C" int vpd_op_conv2d_bnsums2(const void* x, const void* w, void* y, const void* bst_z, const unsigned char* bst_mask,
-                                     double* rows, const void* bst_z2, double* rows2, int n, int xHp, int xWp, int xC, int Hs,
-                                     int Ws, int Kc, int Co, const int* tapset9, void* stream) {
-    if (!bst_z2 || !rows2) return fail("null argument");
-    return op_conv2d_bnsums(x, w, y, bst_z, bst_mask, rows, bst_z2, rows2, n, xHp, xWp, xC, Hs, Ws, Kc, Co, tapset9, 1, stream);
-}
-
-// host-only: what vpd_launch_conv decides for these arguments on the current device (ConvDispatch, kernels.h).  flags: 1 statistics
-// rows, 2 eval epilogue, 4 ReLU bit map on the old value, 8 BatchNorm sums (vpd_op_conv2d_bnsums), 16 of two BatchNorms.
-// out12 = {class, pws, geo width, c64x2, 1x1 ring GEMM, 1x1 streaming, legacy halo, tile pixels, tile channels, epilogue mode,
-// tiles per block, takes BatchNorm sums}
-extern "C" int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub,
-                                      int oph, int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags,
-                                      int* out12) {
-    if (!tapset9 || !out12) return fail("null argument");
-    if (n < 1 || Hs < 1 || Ws < 1 || xHp < 1 || xWp < 1 || xC < 1 || yC < Co || Kc < 64 || Kc % 64 || Co < 64 || Co % 64 || osub < 1 ||
-        istr < 1 || (long long)n * Hs * Ws >= (1ll << 31) || (flags & ~31))
-        return fail("bad argument");
-    if ((flags & 16) && !(flags & 8)) return fail("a second BatchNorm needs the first");
-    static const double present = 0.0;      // the launcher's decisions read pointers only as present / absent
-    ConvParams q;
-    memset(&q, 0, sizeof q);
-    q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.yHp = yHp; q.yWp = yWp; q.yC = yC; q.ypad = ypad;
-    q.N = n; q.Hs = Hs; q.Ws = Ws; q.osub = osub; q.oph = oph; q.opw = opw; q.istr = istr;
-    q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws; q.accumulate = accumulate;
-    if (flags & 1) q.stats = const_cast<double*>(&present);
-    if (flags & 2) { q.ep_scale = (const float*)&present; q.ep_shift = (const float*)&present; }
-    if (flags & 4) q.acc_mask = (const unsigned char*)&present;
-    if (flags & 8) { q.bst_z = (const bf16_t*)&present; q.bst_mask = (const unsigned char*)&present; q.stats = const_cast<double*>(&present); q.stat_rows = VPD_FUSED_ROWS; }
-    if (flags & 16) { q.bst_z2 = (const bf16_t*)&present; q.stats2 = const_cast<double*>(&present); }
-    q.taps = tapset_from(tapset9);
-    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
-    const ConvDispatch d = vpd_conv_dispatch(q);
-    const int v[12] = {d.kclass, d.pws, d.geo, d.c64x2, d.ws1x1, d.stream1x1, d.halo, d.bm, d.bn, d.mode, d.tiles_per_block,
-                       (flags & 8) ? (int)vpd_conv_takes_bn_sums(q) : 0};
-    memcpy(out12, v, sizeof v);
-    return 0;
-}
-
-extern "C" int vpd_op_bn_forward(const void* z, const double* rows, const float* gamma, const float* beta, float* running_mean,
-                                 float* running_var, float* mean, float* rstd, float* scale, float* shift, const void* res,
-                                 void* out, unsigned char* mask_bits, int n, int H, int W, int C, int relu, float momentum,
-                                 float eps, void* stream) {
-    if (!z || !rows || !gamma || !beta || !mean || !rstd || !scale || !shift || !out) return fail("null argument");
-    BnApplyParams a;
-    memset(&a, 0, sizeof a);
-    a.z = (const bf16_t*)z;
-    a.res_kind = res ? 1 : 0; a.res = (const bf16_t*)res; a.rHp = H + 2; a.rWp = W + 2; a.rpad = 1;
-    a.out = (bf16_t*)out; a.oHp = H + 2; a.oWp = W + 2; a.opad = 1;
-    a.M = n * H * W; a.H = H; a.W = W; a.C = C; a.relu = relu; a.mask_out = mask_bits;
-    BnFusedFwd f;
-    memset(&f, 0, sizeof f);
-    f.rows = const_cast<double*>(rows); f.count = (float)a.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
-    f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift; f.momentum = momentum; f.eps = eps;
-    f.frozen = g_op_bn_frozen;
-    if (f.frozen && (!running_mean || !running_var)) return fail("a frozen BatchNorm needs running_mean and running_var");
-    LCHECK(vpd_launch_bn_fwd_fused(a, f, (hipStream_t)stream));
-    return 0;
-}
-
-// ... with the BatchNorm of a down-sampling branch in the same launch (res_kind 2): out = relu?(BatchNorm(z) + BatchNorm2(z2)), z2
-// dense like z, no ReLU of its own.  Both BatchNorms take the hook's mode; running statistics of both or of neither.
-extern "C" int vpd_op_bn_forward2(const void* z, const double* rows, const float* gamma, const float* beta, float* running_mean,
-                                  float* running_var, float* mean, float* rstd, float* scale, float* shift, const void* z2,
-                                  const double* rows2, const float* gamma2, const float* beta2, float* running_mean2,
-                                  float* running_var2, float* mean2, float* rstd2, float* scale2, float* shift2, void* out,
-                                  unsigned char* mask_bits, int n, int H, int W, int C, int relu, float momentum, float eps,
-                                  void* stream) {
-    if (!z || !rows || !gamma || !beta || !mean || !rstd || !scale || !shift || !out || !z2 || !rows2 || !gamma2 || !beta2 || !mean2 ||
-        !rstd2 || !scale2 || !shift2)
-        return fail("null argument");
-    const int nrun = (running_mean != nullptr) + (running_var != nullptr) + (running_mean2 != nullptr) + (running_var2 != nullptr);
-    if (nrun != 0 && nrun != 4) return fail("running statistics of both BatchNorms or of neither");
-    if (g_op_bn_frozen && nrun != 4) return fail("a frozen BatchNorm needs running_mean and running_var");
-    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
-    BnApplyParams a;
-    memset(&a, 0, sizeof a);
-    a.z = (const bf16_t*)z;
-    a.res_kind = 2; a.res = (const bf16_t*)z2; a.rHp = H + 2; a.rWp = W + 2; a.rpad = 1;
-    a.out = (bf16_t*)out; a.oHp = H + 2; a.oWp = W + 2; a.opad = 1;
-    a.M = n * H * W; a.H = H; a.W = W; a.C = C; a.relu = relu; a.mask_out = mask_bits;
-    BnFusedFwd f;
-    memset(&f, 0, sizeof f);
-    f.rows = const_cast<double*>(rows); f.count = (float)a.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
-    f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift;
-    f.rows2 = const_cast<double*>(rows2); f.count2 = (float)a.M; f.gamma2 = gamma2; f.beta2 = beta2; f.rm2 = running_mean2; f.rv2 = running_var2;
-    f.mean2 = mean2; f.rstd2 = rstd2; f.scale2 = scale2; f.shift2 = shift2;
-    f.momentum = momentum; f.eps = eps; f.frozen = g_op_bn_frozen;
-    LCHECK(vpd_launch_bn_fwd_fused(a, f, (hipStream_t)stream));
-    return 0;
-}
-
-// the stem's and the VPD_FUSED_BN=0 path's finalize launch (bn_finalize_kernel) on the shared rows [VPD_STAT_ROWS][2][C], which it
-// zeroes: mean / rstd / scale / shift, and the running statistics -- updated, or under the hook read and left alone
-extern "C" int vpd_op_bn_finalize(double* rows, const float* gamma, const float* beta, float* running_mean, float* running_var,
-                                  float* mean, float* rstd, float* scale, float* shift, int count, int C, float momentum, float eps,
-                                  void* stream) {
-    if (!rows || !gamma || !beta || !mean || !rstd || !scale || !shift) return fail("null argument");
-    if ((running_mean == nullptr) != (running_var == nullptr)) return fail("running_mean and running_var come together");
-    if (g_op_bn_frozen && !running_mean) return fail("a frozen BatchNorm needs running_mean and running_var");
-    if (count < 1 || C < 1) return fail("bad shape");
-    LCHECK(vpd_launch_bn_finalize(rows, VPD_STAT_ROWS, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps, mean,
-                                  rstd, scale, shift, (hipStream_t)stream, g_op_bn_frozen != 0));
-    return 0;
-}
-
-extern "C" int vpd_op_bn_backward_apply(const void* dy, const void* z, const unsigned char* mask_bits, const double* rows,
-                                        const float* gamma, const float* mean, const float* rstd, void* dz, float* dgamma,
-                                        float* dbeta, int n, int H, int W, int C, void* stream) {
-    if (!dy || !z || !mask_bits || !rows || !gamma || !mean || !rstd || !dz || !dgamma || !dbeta) return fail("null argument");
-    BnBwdParams b;
-    memset(&b, 0, sizeof b);
-    b.dy = (const bf16_t*)dy; b.z = (const bf16_t*)z; b.mean = mean; b.rstd = rstd;
-    b.dz = (bf16_t*)dz; b.dzHp = H + 2; b.dzWp = W + 2; b.dzpad = 1;
-    b.M = n * H * W; b.H = H; b.W = W; b.C = C; b.mask_bits = mask_bits;
-    BnFusedBwd f;
-    memset(&f, 0, sizeof f);
-    f.rows = const_cast<double*>(rows); f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
-    f.frozen = g_op_bn_frozen;
-    LCHECK(vpd_launch_bn_bwd_apply_fused(b, f, (hipStream_t)stream));
-    return 0;
-}
-
-// ... for TWO BatchNorms fed with the same masked gradient (bn_bwd_apply_fused_kernel<true>: a down-sampling block's last BatchNorm
-// and its 1x1 branch's, whose sums the next block's data gradient took): rows2 holds sum g (unused) and sum g * z2
-extern "C" int vpd_op_bn_backward_apply2(const void* dy, const void* z, const unsigned char* mask_bits, const double* rows,
-                                         const float* gamma, const float* mean, const float* rstd, void* dz, float* dgamma,
-                                         float* dbeta, const void* z2, const double* rows2, const float* gamma2, const float* mean2,
-                                         const float* rstd2, void* dz2, float* dgamma2, float* dbeta2, int n, int H, int W, int C,
-                                         void* stream) {
-    if (!dy || !z || !mask_bits || !rows || !gamma || !mean || !rstd || !dz || !dgamma || !dbeta || !z2 || !rows2 || !gamma2 || !mean2 ||
-        !rstd2 || !dz2 || !dgamma2 || !dbeta2)
-        return fail("null argument");
-    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
-    BnBwdParams b;
-    memset(&b, 0, sizeof b);
-    b.dy = (const bf16_t*)dy; b.z = (const bf16_t*)z; b.mean = mean; b.rstd = rstd;
-    b.dz = (bf16_t*)dz; b.dzHp = H + 2; b.dzWp = W + 2; b.dzpad = 1;
-    b.M = n * H * W; b.H = H; b.W = W; b.C = C; b.mask_bits = mask_bits;
-    BnFusedBwd f;
-    BnBwdSecond B;
-    memset(&f, 0, sizeof f);
-    memset(&B, 0, sizeof B);
-    f.rows = const_cast<double*>(rows); f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
-    f.frozen = g_op_bn_frozen;
-    B.f.rows = const_cast<double*>(rows2); B.f.gamma = gamma2; B.f.dgamma = dgamma2; B.f.dbeta = dbeta2; B.f.count = (float)b.M;
-    B.z = (const bf16_t*)z2; B.mean = mean2; B.rstd = rstd2; B.dz = (bf16_t*)dz2;
-    LCHECK(vpd_launch_bn_bwd_apply_fused(b, f, (hipStream_t)stream, &B));
-    return 0;
-}
-
-// ---- a Bottleneck's closing 1x1 convolution with its BatchNorm (conv_stream.hip): the launchers of step.hip's run_conv3_bn_* /
-// run_conv3d_bn_* from flat arguments.  Every refusal is the launcher's own predicate, asked before anything is launched ----
-static ConvParams op_conv1x1_bn_params(const void* x, const void* w, int n, int H, int W, int istr, int Kc, int Co) {
-    ConvParams q;
-    memset(&q, 0, sizeof q);
-    q.x = (const bf16_t*)x; q.xHp = H * istr + 2; q.xWp = W * istr + 2; q.xC = Kc; q.w = (const bf16_t*)w;
-    q.yHp = H; q.yWp = W; q.yC = Co; q.ypad = 0;
-    q.N = n; q.Hs = H; q.Ws = W; q.osub = 1; q.istr = istr;
-    q.Kc = Kc; q.Co = Co; q.M = n * H * W;
-    q.taps.nr = 1; q.taps.nc = 1; q.taps.dy0 = 1; q.taps.dys = 1; q.taps.dx0 = 1; q.taps.dxs = 1; q.taps.w0 = 0; q.taps.wrs = 1; q.taps.wcs = 1;
-    return q;
-}
-static bool op_conv1x1_bn_shape_ok(int n, int H, int W, int istr, int Kc, int Co) {
-    return n >= 1 && H >= 1 && W >= 1 && istr >= 1 && Kc >= 64 && Kc % 64 == 0 && Co >= 64 && Co % 64 == 0 &&
-           (long long)n * H * W < (1ll << 31);
-}
-
-extern "C" int vpd_op_conv1x1_bn(int mode, const void* x, const void* w, int n, int H, int W, int istr, int Kc, int Co, double* rows,
-                                 const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
-                                 float eps, float* mean, float* rstd, float* scale, float* shift, const void* res, void* out,
-                                 unsigned char* mask_bits, const void* dout, void* dz, float* dgamma, float* dbeta, void* stream) {
-    if (mode < 0 || mode > 3) return fail("mode 0 .. 3");
-    if (!x || !w || !rows) return fail("null argument");
-    if (mode == 1 && (!gamma || !beta || !mean || !rstd || !scale || !shift || !res || !out || (running_mean == nullptr) != (running_var == nullptr)))
-        return fail("null argument");
-    if (mode >= 2 && (!dout || !mask_bits)) return fail("null argument");
-    if (mode == 3 && (!gamma || !mean || !rstd || !dz || !dgamma || !dbeta)) return fail("null argument");
-    if (!op_conv1x1_bn_shape_ok(n, H, W, istr, Kc, Co)) return fail("bad argument");
-    ConvParams q = op_conv1x1_bn_params(x, w, n, H, W, istr, Kc, Co);
-    if (!vpd_conv1x1_bn_eligible(q)) return fail("conv1x1_bn_stream_kernel does not take this shape");
-    BnFusedFwd f;
-    BnFusedBwd b;
-    memset(&f, 0, sizeof f);
-    memset(&b, 0, sizeof b);
-    if (mode == 0) { q.stats = rows; q.stat_rows = VPD_FUSED_ROWS; }
-    else if (mode == 1) {
-        q.y = (bf16_t*)out; q.yHp = H + 2; q.yWp = W + 2; q.ypad = 1;
-        q.res = (const bf16_t*)res; q.rHp = H + 2; q.rWp = W + 2; q.rC = Co; q.rpad = 1;
-        f.rows = rows; f.count = (float)q.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
-        f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift; f.momentum = momentum; f.eps = eps;
-        f.frozen = g_op_bn_frozen;
-        if (f.frozen && !running_mean) return fail("a frozen BatchNorm needs running_mean and running_var");
-    } else {
-        q.y = (bf16_t*)const_cast<void*>(dout); q.acc_mask = mask_bits;
-        b.rows = rows; b.gamma = gamma; b.dgamma = dgamma; b.dbeta = dbeta; b.count = (float)q.M; b.frozen = g_op_bn_frozen;
-    }
-    LCHECK(vpd_launch_conv1x1_bn(q, mode == 1 ? &f : nullptr, mode >= 2 ? &b : nullptr, mode == 3 ? mean : nullptr,
-                                 mode == 3 ? rstd : nullptr, mode == 1 ? mask_bits : nullptr, mode == 3 ? (bf16_t*)dz : nullptr,
-                                 mode == 3 ? 1 : 0, mode, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_conv1x1_bn2(int mode, const void* x, const void* w, const void* x2, const void* w2, int n, int H, int W, int Kc,
-                                  int Kc2, int Co, double* rows, double* rows2, const float* gamma, const float* beta,
-                                  float* running_mean, float* running_var, float* mean, float* rstd, float* scale, float* shift,
-                                  const float* gamma2, const float* beta2, float* running_mean2, float* running_var2, float* mean2,
-                                  float* rstd2, float* scale2, float* shift2, float momentum, float eps, void* out,
-                                  unsigned char* mask_bits, const void* dout, void* dz, void* dz2, float* dgamma, float* dbeta,
-                                  float* dgamma2, float* dbeta2, void* stream) {
-    if (mode < 1 || mode > 3) return fail("mode 1 .. 3");
-    if (!x || !w || !x2 || !w2 || !rows || !rows2) return fail("null argument");
-    if (mode == 1 && (!gamma || !beta || !mean || !rstd || !scale || !shift || !gamma2 || !beta2 || !mean2 || !rstd2 || !scale2 || !shift2 ||
-                      !out || (running_mean == nullptr) != (running_var == nullptr) || (running_mean == nullptr) != (running_mean2 == nullptr) ||
-                      (running_mean2 == nullptr) != (running_var2 == nullptr)))
-        return fail("null argument");
-    if (mode >= 2 && (!dout || !mask_bits)) return fail("null argument");
-    if (mode == 3 && (!gamma || !mean || !rstd || !gamma2 || !mean2 || !rstd2 || !dz || !dz2 || !dgamma || !dbeta || !dgamma2 || !dbeta2))
-        return fail("null argument");
-    if (!op_conv1x1_bn_shape_ok(n, H, W, 1, Kc, Co) || Kc2 < 1) return fail("bad argument");
-    ConvParams q = op_conv1x1_bn_params(x, w, n, H, W, 1, Kc, Co);
-    q.x2 = (const bf16_t*)x2; q.w2 = (const bf16_t*)w2; q.Kc2 = Kc2;
-    if (!vpd_conv1x1_bn2_eligible(q)) return fail("conv1x1_bn2_stream_kernel does not take this shape");
-    BnFusedFwd f;
-    BnFusedBwd b3, bd;
-    memset(&f, 0, sizeof f);
-    memset(&b3, 0, sizeof b3);
-    memset(&bd, 0, sizeof bd);
-    if (mode == 1) {
-        q.y = (bf16_t*)out; q.yHp = H + 2; q.yWp = W + 2; q.ypad = 1;
-        f.rows = rows; f.count = (float)q.M; f.gamma = gamma; f.beta = beta; f.rm = running_mean; f.rv = running_var;
-        f.mean = mean; f.rstd = rstd; f.scale = scale; f.shift = shift;
-        f.rows2 = rows2; f.count2 = (float)q.M; f.gamma2 = gamma2; f.beta2 = beta2; f.rm2 = running_mean2; f.rv2 = running_var2;
-        f.mean2 = mean2; f.rstd2 = rstd2; f.scale2 = scale2; f.shift2 = shift2;
-        f.momentum = momentum; f.eps = eps; f.frozen = g_op_bn_frozen;
-        if (f.frozen && !running_mean) return fail("a frozen BatchNorm needs running_mean and running_var");
-    } else {
-        b3.frozen = g_op_bn_frozen; bd.frozen = g_op_bn_frozen;
-        q.y = (bf16_t*)const_cast<void*>(dout); q.acc_mask = mask_bits;
-        b3.rows = rows; b3.gamma = gamma; b3.dgamma = dgamma; b3.dbeta = dbeta; b3.count = (float)q.M;
-        bd.rows = rows2; bd.gamma = gamma2; bd.dgamma = dgamma2; bd.dbeta = dbeta2; bd.count = (float)q.M;
-    }
-    const bool m3 = mode == 3;
-    LCHECK(vpd_launch_conv1x1_bn2(q, mode == 1 ? &f : nullptr, mode >= 2 ? &b3 : nullptr, mode >= 2 ? &bd : nullptr, m3 ? mean : nullptr,
-                                  m3 ? rstd : nullptr, m3 ? mean2 : nullptr, m3 ? rstd2 : nullptr, mode == 1 ? mask_bits : nullptr,
-                                  m3 ? (bf16_t*)dz : nullptr, m3 ? (bf16_t*)dz2 : nullptr, m3 ? 1 : 0, mode, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_conv1x1_bn_dispatch(int n, int H, int W, int Kc, int Co, int two, int* out5) {
-    if (!out5) return fail("null argument");
-    if (!op_conv1x1_bn_shape_ok(n, H, W, 1, Kc, Co)) return fail("bad argument");
-    static const double present = 0.0;      // (the predicates read pointers only as present / absent)
-    ConvParams q = op_conv1x1_bn_params(nullptr, nullptr, n, H, W, 1, Kc, Co);
-    if (two) { q.x2 = (const bf16_t*)&present; q.w2 = (const bf16_t*)&present; q.Kc2 = Kc; }
-    int v[5] = {0, 0, 0, 0, 0};
-    v[0] = two ? (int)vpd_conv1x1_bn2_eligible(q) : (int)vpd_conv1x1_bn_eligible(q);
-    if (v[0]) vpd_conv1x1_bn_grid(q, two != 0, v + 1);
-    memcpy(out5, v, sizeof v);
-    return 0;
-}
-
-// ---- stem pool, BatchNorm backward launchers, head: the product launchers unchanged, parameters from flat arguments ----
-extern "C" int vpd_op_stem_pool_forward(const void* z, const float* scale, const float* shift, void* out_padded,
-                                        unsigned char* idx, int n, int Hz, int Wz, int C, int opad, void* stream) {
-    if (!z || !scale || !shift || !out_padded) return fail("null argument");
-    if (n < 1 || Hz < 1 || Wz < 1 || C < 8 || C % 8 || opad < 0) return fail("bad shape");
-    StemPoolParams q;
-    memset(&q, 0, sizeof q);
-    q.z = (const bf16_t*)z; q.Hz = Hz; q.Wz = Wz; q.scale = scale; q.shift = shift;
-    q.out = (bf16_t*)out_padded; q.opad = opad; q.idx = idx;
-    q.N = n; q.Ho = (Hz - 1) / 2 + 1; q.Wo = (Wz - 1) / 2 + 1; q.C = C;
-    LCHECK(vpd_launch_stem_pool(q, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_stem_pool_backward(const void* dpool, const unsigned char* idx, const void* z, const float* mean,
-                                         const float* rstd, const float* scale, const float* shift, const float* gamma,
-                                         const float* beta, const void* pooled_padded, double* rows, float* coef, void* dz,
-                                         float* dgamma, float* dbeta, int n, int Hz, int Wz, int C, void* stream) {
-    if (!dpool || !idx || !z || !mean || !rstd || !scale || !shift || !gamma || !beta || !rows || !coef || !dz || !dgamma || !dbeta)
-        return fail("null argument");
-    if (n < 1 || Hz < 1 || Wz < 1 || C < 8 || C % 8 || 256 % (C / 8)) return fail("bad shape");
-    StemPoolBwdParams sb;
-    memset(&sb, 0, sizeof sb);
-    sb.dpool = (const bf16_t*)dpool; sb.idx = idx; sb.z = (const bf16_t*)z;
-    sb.mean = mean; sb.rstd = rstd; sb.scale = scale; sb.shift = shift; sb.partials = rows;
-    sb.pooled = (const bf16_t*)pooled_padded; sb.ppad = 1; sb.gamma_p = gamma; sb.beta_p = beta;
-    sb.M = n * Hz * Wz; sb.Hz = Hz; sb.Wz = Wz; sb.Ho = (Hz - 1) / 2 + 1; sb.Wo = (Wz - 1) / 2 + 1; sb.C = C;
-    LCHECK(vpd_launch_stem_pool_bwd(sb, (float)sb.M, gamma, dgamma, dbeta, coef, (bf16_t*)dz, (hipStream_t)stream, g_op_bn_frozen != 0));
-    return 0;
-}
-
-// the stem convolution's data gradient (conv_stem_dgrad.hip): the launch vpd_backward_ext makes, from flat arguments
-extern "C" int vpd_op_stem_dgrad(const void* dz, const float* w_oihw, float* dx_nchw, int n, int c_in, int H, int W, void* stream) {
-    if (!dz || !w_oihw || !dx_nchw) return fail("null argument");
-    if (n < 1) return fail("n must be at least 1");
-    if (c_in < 1 || c_in > 8) return fail("c_in outside 1..8");
-    if (H < 32 || W < 32 || (H & 1) || (W & 1)) return fail("H and W must be even and at least 32");
-    if (reinterpret_cast<size_t>(dx_nchw) & 7) return fail("dx_nchw must be 8-byte aligned");
-    LCHECK(vpd_launch_stem_dgrad((const bf16_t*)dz, w_oihw, dx_nchw, n, c_in, H, W, (hipStream_t)stream));
-    return 0;
-}
-
-static BnBwdParams op_bn_bwd_params(void* dy, const void* z, const void* act_padded, const float* mean, const float* rstd,
-                                    void* dz, int dzpad, int n, int H, int W, int C) {
-    BnBwdParams b;
-    memset(&b, 0, sizeof b);
-    b.dy = (const bf16_t*)dy; b.dy_rw = (bf16_t*)dy; b.z = (const bf16_t*)z;
-    b.act = (const bf16_t*)act_padded; b.aHp = H + 2; b.aWp = W + 2; b.apad = 1;
-    b.mean = mean; b.rstd = rstd;
-    b.dz = (bf16_t*)dz; b.dzHp = H + 2 * dzpad; b.dzWp = W + 2 * dzpad; b.dzpad = dzpad;
-    b.M = n * H * W; b.H = H; b.W = W; b.C = C;
-    return b;
-}
-
-extern "C" int vpd_op_bn_backward(void* dy, const void* z, const void* act_padded, const unsigned char* mask_bits,
-                                  const float* mscale, const float* mshift, const float* dy_pooled, double* rows, float* coef,
-                                  void* sync, unsigned* err, const float* gamma, const float* mean, const float* rstd, void* dz,
-                                  int dzpad, float* dgamma, float* dbeta, int n, int H, int W, int C, int write_g, int fused,
-                                  void* stream) {
-    if (!dy || !z || !rows || !gamma || !mean || !rstd || !dz || !dgamma || !dbeta) return fail("null argument");
-    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || dzpad < 0) return fail("bad shape");
-    if ((mscale == nullptr) != (mshift == nullptr)) return fail("mscale and mshift come together");
-    if ((act_padded != nullptr) + (mask_bits != nullptr) + (mscale != nullptr) > 1) return fail("one ReLU mask at most");
-    if (write_g && !act_padded) return fail("write_g goes with the activation mask");
-    BnBwdParams b = op_bn_bwd_params(dy, z, act_padded, mean, rstd, dz, dzpad, n, H, W, C);
-    b.coef = coef; b.partials = rows; b.write_g = write_g; b.mscale = mscale; b.mshift = mshift; b.mask_bits = mask_bits;
-    if (!fused) {
-        if (mask_bits || dy_pooled) return fail("the three-launch path takes neither a ReLU bit map nor a pooled gradient");
-        if (!coef) return fail("the three-launch path needs coef");
-        LCHECK(vpd_launch_bn_bwd(b, (float)b.M, gamma, dgamma, dbeta, (hipStream_t)stream, false, g_op_bn_frozen != 0));
-        return 0;
-    }
-    if (!sync || !err) return fail("the fused launch needs sync and err");
-    if (!vpd_bn_bwd_fused_ok(b.M, C, act_padded != nullptr, write_g != 0)) return fail("no fused BatchNorm backward for this shape");
-    if (dy_pooled) {
-        if (!mask_bits) return fail("the folded average-pool gradient needs the ReLU bit map");
-        if ((H * W) & (H * W - 1)) return fail("the folded average-pool gradient takes a power-of-two H W (vpd_op_avgpool_bwd first otherwise)");
-        b.dy_pooled = dy_pooled; b.dy_pool_scale = 1.f / (float)(H * W);
-    }
-    BnFusedBwd f;
-    memset(&f, 0, sizeof f);
-    f.rows = rows; f.sync = sync; f.err = err; f.gamma = gamma; f.dgamma = dgamma; f.dbeta = dbeta; f.count = (float)b.M;
-    f.frozen = g_op_bn_frozen;
-    LCHECK(vpd_launch_bn_bwd_fused(b, f, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_bn_backward_pair(void* dy, const void* act_padded, const void* zA, const float* meanA, const float* rstdA,
-                                       const float* gammaA, double* rowsA, void* dzA, float* dgammaA, float* dbetaA,
-                                       const void* zB, const float* meanB, const float* rstdB, const float* gammaB,
-                                       double* rowsB, void* dzB, float* dgammaB, float* dbetaB, void* sync, unsigned* err, int n,
-                                       int H, int W, int C, void* stream) {
-    if (!dy || !act_padded || !zA || !meanA || !rstdA || !gammaA || !rowsA || !dzA || !dgammaA || !dbetaA || !zB || !meanB ||
-        !rstdB || !gammaB || !rowsB || !dzB || !dgammaB || !dbetaB || !sync || !err)
-        return fail("null argument");
-    if (n < 1 || H < 1 || W < 1) return fail("bad shape");
-    if (!vpd_bn_bwd_fused2_ok(n * H * W, C)) return fail("no paired BatchNorm backward for this shape");
-    BnBwdParams b = op_bn_bwd_params(dy, zA, act_padded, meanA, rstdA, dzA, 1, n, H, W, C);
-    BnFusedBwd fA;
-    BnBwdSecond B;
-    memset(&fA, 0, sizeof fA);
-    memset(&B, 0, sizeof B);
-    fA.rows = rowsA; fA.gamma = gammaA; fA.dgamma = dgammaA; fA.dbeta = dbetaA; fA.count = (float)b.M;
-    fA.sync = sync; fA.err = err; fA.frozen = g_op_bn_frozen;
-    B.f.rows = rowsB; B.f.gamma = gammaB; B.f.dgamma = dgammaB; B.f.dbeta = dbetaB; B.f.count = (float)b.M;
-    B.z = (const bf16_t*)zB; B.mean = meanB; B.rstd = rstdB; B.dz = (bf16_t*)dzB;
-    LCHECK(vpd_launch_bn_bwd_fused2(b, fA, B, (hipStream_t)stream));
-    return 0;
-}
-
-// host-only: out4 = {blocks, g resident, z (pair: zA) resident, pair: zB resident} of the fused backward of n H W x C on this device
-extern "C" int vpd_op_bn_backward_residency(int M, int C, int pair, int* out4) {
-    if (!out4 || M < 1 || C < 64 || C > 2048 || C % 8 || 1024 % (C / 8)) return fail("bad argument");
-    const BnBwdFusedGeom q = vpd_bn_bwd_fused_geom(M, C, pair ? 3 : 2);
-    out4[0] = q.G; out4[1] = q.keep[0]; out4[2] = q.keep[1]; out4[3] = q.keep[2];
-    return 0;
-}
-
-extern "C" int vpd_op_avgpool(const void* act_padded, int n, int H, int W, int C, int pad, float* pooled, void* stream) {
-    if (!act_padded || !pooled) return fail("null argument");
-    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || pad < 0) return fail("bad shape");
-    LCHECK(vpd_launch_avgpool((const bf16_t*)act_padded, H + 2 * pad, W + 2 * pad, pad, H, W, C, n, pooled, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_avgpool_bwd(const float* dpooled, int n, int H, int W, int C, void* dact, void* stream) {
-    if (!dpooled || !dact) return fail("null argument");
-    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
-    LCHECK(vpd_launch_avgpool_bwd(dpooled, H, W, C, n, (bf16_t*)dact, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_sgemm(const float* A, const float* B, float* Y, const float* bias, int M, int N, int K, int ta, int tb,
-                            int relu, void* stream) {
-    if (!A || !B || !Y) return fail("null argument");
-    if (M < 1 || N < 1 || K < 1) return fail("bad shape");
-    LCHECK(vpd_launch_sgemm(A, B, Y, bias, M, N, K, ta, tb, relu, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_colsum(const float* A, int M, int N, float* out, void* stream) {
-    if (!A || !out || M < 1 || N < 1) return fail("bad argument");
-    LCHECK(vpd_launch_colsum(A, M, N, out, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_relu_mask(float* d, const float* act, long long n, void* stream) {
-    if (!d || !act || n < 1) return fail("bad argument");
-    LCHECK(vpd_launch_relu_mask(d, act, (long)n, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_mse(const float* e, const float* t, long long n, float* de, float* loss_step, double* loss_accum,
-                          void* stream) {
-    if (!e || !t || n < 1) return fail("bad argument");
-    LCHECK(vpd_launch_mse(e, t, (long)n, de, loss_step, loss_accum, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_wgrad(const void* dz, const void* x, float* dw, int n, int dzHp, int dzWp, int dzC, int dzpad,
-                            int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
-                            float* slab, void* stream) {
-    WgradParams q;
-    memset(&q, 0, sizeof q);
-    q.dz = (const bf16_t*)dz; q.dzHp = dzHp; q.dzWp = dzWp; q.dzC = dzC; q.dzpad = dzpad;
-    q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.dw = dw; q.slab = slab;
-    q.N = n; q.Hs = Hs; q.Ws = Ws; q.istr = istr; q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws;
-    q.taps = tapset_from(tapset9);
-    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
-    LCHECK(vpd_launch_wgrad(q, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_wgrad_pair(const void* dz, const void* dz2, const void* x, float* dw, float* dw2, int n, int dzHp, int dzWp,
-                                 int dzC, int dzpad, int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co,
-                                 const int* tapset9, float* slab, float* slab2, void* stream) {
-    if (!dz || !dz2 || !x || !dw || !dw2 || !tapset9 || !slab || !slab2) return fail("null argument");
-    if (n < 1 || Hs < 1 || Ws < 1) return fail("bad argument");
-    WgradParams q;
-    memset(&q, 0, sizeof q);
-    q.dz = (const bf16_t*)dz; q.dzHp = dzHp; q.dzWp = dzWp; q.dzC = dzC; q.dzpad = dzpad;
-    q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.dw = dw; q.slab = slab;
-    q.N = n; q.Hs = Hs; q.Ws = Ws; q.istr = istr; q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws;
-    WgradParams q1 = q;                       // the branch: one tap at padded offset (1, 1)
-    q1.dz = (const bf16_t*)dz2; q1.dw = dw2; q1.slab = slab2; q1.prefer_halo_1x1 = 1;
-    q1.taps.nr = 1; q1.taps.nc = 1; q1.taps.dy0 = 1; q1.taps.dys = 1; q1.taps.dx0 = 1; q1.taps.dxs = 1;
-    q1.taps.w0 = 0; q1.taps.wrs = 1; q1.taps.wcs = 1;
-    q.taps = tapset_from(tapset9);
-    if (!vpd_wgrad_pair_ok(q, q1)) return fail("not a pair the halo weight-gradient launch takes (shapes, or VPD_WGRAD_DS_RIDE=0 / VPD_WGRAD_1X1=0 / VPD_WGRAD_S2=0)");
-    LCHECK(vpd_launch_wgrad_pair(q, q1, (hipStream_t)stream));
-    return 0;
-}
-extern "C" int vpd_op_wgrad_pair_lds_bytes(int Hs, int Ws, int ns, long long* bytes) {
-    return vpd_wgrad_pair_lds_query(Hs, Ws, ns, bytes);
-}
-
-// Grouped 128 x 64 weight gradients (conv_wgrad128_persistent_kernel) of `nprob` 3x3 stride-1 pad-1 convolutions in ONE
-// launch.  dims: 7 ints per problem {n, H, W, Co, Ci, stride, k} (H, W: OUTPUT size; stride 1 or 2; k = 3: 3x3 pad 1, k = 1: 1x1
-// pad 0); dz[i]: padded bf16 [n][H+2][W+2][Co]; x[i]: padded bf16 [n][stride*H+2][stride*W+2][Ci]; dw[i]: fp32 [k*k][Co][Ci]; slab[i]: fp32 scratch of vpd_op_wgrad128_slab_floats(Co, Ci) floats;
-// dev_table: vpd_op_wgrad128_table_bytes() of device memory.
-extern "C" size_t vpd_op_wgrad128_table_bytes(void) { return vpd_wgrad128_table_bytes(); }
-extern "C" size_t vpd_op_wgrad128_slab_floats(int Co, int Ci) { return vpd_wgrad_group_slab_floats(0, Co, Ci, 1) > vpd_wgrad_group_slab_floats(0, Co, Ci, 9) ? vpd_wgrad_group_slab_floats(0, Co, Ci, 1) : vpd_wgrad_group_slab_floats(0, Co, Ci, 9); }
-extern "C" int vpd_op_wgrad128_group(int nprob, const void* const* dz, const void* const* x, float* const* dw,
-                                     float* const* slab, const int* dims, void* dev_table, void* stream) {
-    if (nprob < 1 || nprob > 18 || !dz || !x || !dw || !slab || !dims || !dev_table) return fail("bad argument");
-    WgradParams qs[18];
-    for (int i = 0; i < nprob; ++i) {
-        const int n = dims[7 * i], H = dims[7 * i + 1], W = dims[7 * i + 2], Co = dims[7 * i + 3], Ci = dims[7 * i + 4];
-        const int S = dims[7 * i + 5], ksz = dims[7 * i + 6];
-        if ((S != 1 && S != 2) || (ksz != 1 && ksz != 3)) return fail("stride must be 1 or 2, k 1 or 3");
-        WgradParams q;
-        memset(&q, 0, sizeof q);
-        q.dz = (const bf16_t*)dz[i]; q.dzHp = H + 2; q.dzWp = W + 2; q.dzC = Co; q.dzpad = 1;
-        q.x = (const bf16_t*)x[i]; q.xHp = S * H + 2; q.xWp = S * W + 2; q.xC = Ci;
-        q.dw = dw[i]; q.slab = slab[i];
-        q.N = n; q.Hs = H; q.Ws = W; q.istr = S; q.Kc = Ci; q.Co = Co; q.M = n * H * W;
-        if (ksz == 3) {
-            q.taps.nr = 3; q.taps.nc = 3; q.taps.dy0 = 0; q.taps.dys = 1; q.taps.dx0 = 0; q.taps.dxs = 1;
-            q.taps.w0 = 0; q.taps.wrs = 3; q.taps.wcs = 1;
-        } else {
-            q.taps.nr = 1; q.taps.nc = 1; q.taps.dy0 = 1; q.taps.dys = 1; q.taps.dx0 = 1; q.taps.dxs = 1;
-            q.taps.w0 = 0; q.taps.wrs = 1; q.taps.wcs = 1;
-        }
-        if (!vpd_wgrad128_eligible(q)) return fail("shape not eligible for the 128 x 64 weight-gradient kernel");
-        qs[i] = q;
-    }
-    // no schedule cache: a cache skips the upload when shapes and table ADDRESS repeat, and a test that frees its table and gets the
-    // same address back from the allocator, overwritten in between, would launch on a stale task table (an illegal access)
-    LCHECK(vpd_launch_wgrad128_group(qs, nprob, nullptr, dev_table, (hipStream_t)stream));
-    return 0;
-}
-
-// ---- the reference boundary one launch at a time (optim.hip: input packing, weight repack, gradient unpack, AdamW + repack,
-// range zeroing) and the weight gradients' slab sums (conv_wgrad.hip).  The descriptors and block maps are push_pack_desc's and
-// build_adam_map's, uploaded for the one launch: the stream is synchronised before they are freed (not timing entry points) ----
-namespace {
-struct DevTables {
-    PackDesc* descs = nullptr;
-    int* bmap = nullptr;
-    ~DevTables() { (void)hipFree(descs); (void)hipFree(bmap); }
-    hipError_t upload(const std::vector<PackDesc>& d, const std::vector<int>& m, hipStream_t s) {
-        hipError_t e = hipMalloc((void**)&descs, d.size() * sizeof(PackDesc));
-        if (e == hipSuccess) e = hipMalloc((void**)&bmap, m.size() * sizeof(int));
-        if (e == hipSuccess) e = hipMemcpyAsync(descs, d.data(), d.size() * sizeof(PackDesc), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(bmap, m.data(), m.size() * sizeof(int), hipMemcpyHostToDevice, s);
-        return e;
-    }
-};
-inline bool aligned(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-// the shapes the tile kernels take: 32 x 32 (co x ci) tiles of at most 9 taps; the stem: 7 x 7 with at most 8 channels
-const char* op_conv_shape_error(int Co, int Ci, int k, int stem) {
-    if (stem != 0 && stem != 1) return "stem is 0 or 1";
-    if (stem) return (k == 7 && Ci >= 1 && Ci <= 8 && Co >= 1) ? nullptr : "the stem is 7x7 with 1..8 input channels";
-    if (Co < 32 || Co % 32 || Ci < 32 || Ci % 32) return "Co and Ci must be multiples of 32";
-    if (k < 1 || k > 3) return "k must be 1, 2 or 3";
-    return nullptr;
-}
-}  // namespace
-
-extern "C" int vpd_op_pack_input(const float* x_f32_nchw, int n, int c, int H, int W, void* out, int Hp, int Wp, int pad,
-                                 void* stream) {
-    if (!x_f32_nchw || !out) return fail("null argument");
-    if (c < 1 || c > 8) return fail("c outside 1..8");
-    if (n < 1 || H < 1 || W < 1 || pad < 0 || Hp < H + pad || Wp < W + pad) return fail("bad shape");
-    if ((long long)n * Hp * Wp >= (1ll << 31) || (long long)n * H * W >= (1ll << 31)) return fail("bad shape");
-    if (!aligned(x_f32_nchw, 4) || !aligned(out, 16)) return fail("x must be 4-byte aligned, out 16-byte aligned");
-    LCHECK(vpd_launch_pack_input(x_f32_nchw, n, c, H, W, (bf16_t*)out, Hp, Wp, pad, 8, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_pack_weights(const float* master, int Co, int Ci, int k, int stem, void* fwd_out, void* dgr_out,
-                                   void* stream) {
-    if (!master || !fwd_out) return fail("null argument");
-    if (const char* e = op_conv_shape_error(Co, Ci, k, stem)) return fail(e);
-    if (stem && dgr_out) return fail("the stem has no data-gradient layout");
-    if (!aligned(master, 4) || !aligned(fwd_out, 16) || !aligned(dgr_out, 16)) return fail("master must be 4-byte aligned, the layouts 16-byte aligned");
-    // one arena pointer, element offsets from it: the lower of the two outputs
-    bf16_t* f = (bf16_t*)fwd_out;
-    bf16_t* d = (bf16_t*)dgr_out;
-    bf16_t* arena = (d && d < f) ? d : f;
-    ConvInfo cv;
-    set_pack_geom(cv, Ci, Co, k, stem != 0);
-    cv.w_off = 0; cv.fwd_off = f - arena; cv.dgr_off = d ? d - arena : -1;
-    std::vector<PackDesc> descs;
-    std::vector<int> bmap, unused;
-    push_pack_desc(descs, bmap, unused, cv);
-    hipStream_t s = (hipStream_t)stream;
-    DevTables t;
-    HCHECK(t.upload(descs, bmap, s));
-    LCHECK(vpd_launch_pack_weights(t.descs, (int)descs.size(), t.bmap, (int)bmap.size() / 2, master, arena, s));
-    HCHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-extern "C" int vpd_op_unpack_grads(const float* wg, int Co, int Ci, int k, int Kc, int stem, float* grads_out, void* stream) {
-    if (!wg || !grads_out) return fail("null argument");
-    if (const char* e = op_conv_shape_error(Co, Ci, k, stem)) return fail(e);
-    if (stem ? Kc < 8 * k : Kc < Ci) return fail("Kc is too small for the scratch layout");
-    if (!aligned(wg, 4) || !aligned(grads_out, 4)) return fail("wg and grads_out must be 4-byte aligned");
-    ConvInfo cv;
-    set_pack_geom(cv, Ci, Co, k, stem != 0);
-    cv.Kc = Kc;
-    cv.w_off = 0; cv.wg_off = 0;
-    std::vector<PackDesc> descs;
-    std::vector<int> unused, bmap;
-    push_pack_desc(descs, unused, bmap, cv);
-    hipStream_t s = (hipStream_t)stream;
-    DevTables t;
-    HCHECK(t.upload(descs, bmap, s));
-    LCHECK(vpd_launch_unpack_grads(t.descs, (int)descs.size(), t.bmap, (int)bmap.size() / 2, wg, grads_out, s));
-    HCHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-extern "C" int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* offsets, long long numel, float* params,
-                                 const float* grads, float* adam_m, float* adam_v, void* arena, const float* wg, double lr,
-                                 double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
-                                 void* stream) {
-    if (!params || !grads || !adam_m || !adam_v || !arena || (nconv > 0 && (!dims3 || !offsets))) return fail("null argument");
-    if (nconv < 0 || nconv > 64) return fail("nconv outside 0..64");
-    if (numel < 4 || numel % 4) return fail("numel must be a positive multiple of 4");
-    if (step < 1) return fail("step is 1-based");
-    if (!aligned(arena, 16) || !aligned(wg, 16)) return fail("arena and wg must be 16-byte aligned");
-    std::vector<PackDesc> descs;
-    std::vector<int> bmap_pack, unused, bmap_adam;
-    long long arena_at = 0, wg_at = 0, prev_end = 0;
-    for (int i = 0; i < nconv; ++i) {
-        const int Co = dims3[3 * i], Ci = dims3[3 * i + 1], k = dims3[3 * i + 2];
-        if (const char* e = op_conv_shape_error(Co, Ci, k, 0)) return fail(e);
-        const long long ns = (long long)Co * Ci * k * k;
-        // (adamw_pack_kernel reads and writes a conv's OIHW rows 16 bytes at a time and has no unaligned fallback)
-        if (offsets[i] % 4) return fail("a conv's offset must be a multiple of 4 floats");
-        if (offsets[i] < prev_end || offsets[i] + ns > numel) return fail("conv ranges must ascend, not overlap and lie inside numel");
-        prev_end = offsets[i] + ns;
-        ConvInfo cv;
-        set_pack_geom(cv, Ci, Co, k, false);
-        cv.w_off = offsets[i];
-        cv.fwd_off = arena_at; cv.dgr_off = arena_at + ns; arena_at += 2 * ns;      // as add_conv lays the arena out
-        cv.wg_off = wg_at; wg_at += ns;
-        push_pack_desc(descs, bmap_pack, unused, cv);
-    }
-    int nstem = 0;
-    build_adam_map(descs, bmap_pack, -1, numel, bmap_adam, nstem);
-    hipStream_t s = (hipStream_t)stream;
-    DevTables t;
-    HCHECK(t.upload(descs, bmap_adam, s));
-    LCHECK(vpd_launch_adamw_pack(t.descs, t.bmap, (int)bmap_adam.size() / 2, params, grads, adam_m, adam_v, (bf16_t*)arena, lr,
-                                 beta1, beta2, eps, weight_decay, step, s, wg, gscale));
-    HCHECK(hipStreamSynchronize(s));
-    return 0;
-}
-
-extern "C" int vpd_op_wgrad_reduce(int nprob, const float* const* slabs, float* const* dws, const long long* nfloats,
-                                   const int* ksplits, void* stream) {
-    if (!slabs || !dws || !nfloats || !ksplits) return fail("null argument");
-    if (nprob < 1 || nprob > vpd_wgrad_reduce_max()) return fail("nprob outside 1..18");
-    for (int i = 0; i < nprob; ++i) {
-        if (!slabs[i] || !dws[i]) return fail("null argument");
-        if (nfloats[i] < 4 || nfloats[i] % 4 || ksplits[i] < 1) return fail("a problem needs a positive multiple of 4 floats and ksplit >= 1");
-        if (!aligned(slabs[i], 16) || !aligned(dws[i], 16)) return fail("slabs and dws must be 16-byte aligned");
-    }
-    LCHECK(vpd_launch_wgrad_reduce(nprob, slabs, dws, nfloats, ksplits, (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_op_zero_ranges(float* const* ptrs, const long long* n4s, int count, void* stream) {
-    if (count < 0 || count > ZR_MAX) return fail("count outside 0..16");
-    if (count == 0) return 0;
-    if (!ptrs || !n4s) return fail("null argument");
-    ZeroRanges z;
-    memset(&z, 0, sizeof z);
-    for (int i = 0; i < count; ++i) {
-        if (!ptrs[i]) return fail("null argument");
-        if (n4s[i] < 0 || !aligned(ptrs[i], 16)) return fail("ranges must be 16-byte aligned, lengths not negative");
-        z.ptr[i] = ptrs[i]; z.n4[i] = (long)n4s[i];
-    }
-    z.count = count;
-    LCHECK(vpd_launch_zero_ranges(z, (hipStream_t)stream));
-    return 0;
-}

@@ -292,13 +292,7 @@ hipError_t run_conv_wgrad_pair(const Ctx& c, const ConvInfo& c1, const ConvInfo&
 }
 
 BnApplyParams bn_apply_params(const Ctx& c, const ConvInfo& cv, int res_kind, const bf16_t* res, bf16_t* out, int relu) {
-    BnApplyParams a;
-    memset(&a, 0, sizeof a);
-    a.z = c.b16(cv.z_off);
-    a.res_kind = res_kind; a.res = res; a.rHp = cv.Hout + 2; a.rWp = cv.Wout + 2; a.rpad = 1;
-    a.out = out; a.oHp = cv.Hout + 2; a.oWp = cv.Wout + 2; a.opad = 1;
-    a.M = c.n * cv.Hout * cv.Wout; a.H = cv.Hout; a.W = cv.Wout; a.C = cv.Co; a.relu = relu;
-    return a;
+    return vpd_bn_apply_params(c.b16(cv.z_off), res_kind, res, out, c.n, cv.Hout, cv.Wout, cv.Co, relu);
 }
 hipError_t run_bn_apply(const Ctx& c, const ConvInfo& cv, int res_kind, const bf16_t* res, const ConvInfo* rcv,
                         bf16_t* out, int relu) {
@@ -325,21 +319,22 @@ int bn_xcd_tile_px(const Ctx& c, const ConvInfo& cv) {
     return vpd_conv_xcd_tile_px(q);
 }
 
-// the fused forward launch's BatchNorm side(s): conv `cv`'s BatchNorm and, when given, the residual branch's (`cv2`)
+// conv `cv`'s BatchNorm as one side of a fused forward launch
+BnFwdSide bn_fwd_side(const Ctx& c, const ConvInfo& cv, float* bn_running) {
+    const BnInfo& b = cv.bn;
+    BnFwdSide f;
+    f.rows = c.bn_rows(b); f.gamma = c.params + b.w_off; f.beta = c.params + b.b_off;
+    f.rm = bn_running ? bn_running + b.rm_off : nullptr; f.rv = bn_running ? bn_running + b.rv_off : nullptr;
+    f.mean = c.bn_mean(b); f.rstd = c.bn_rstd(b); f.scale = c.bn_scale(b); f.shift = c.bn_shift(b);
+    return f;
+}
+// the fused forward launch: conv `cv`'s BatchNorm and, when given, the residual branch's (`cv2`, same shape)
 BnFusedFwd bn_fused_fwd(const Ctx& c, const ConvInfo& cv, float* bn_running, const ConvInfo* cv2 = nullptr) {
     BnFusedFwd f;
     memset(&f, 0, sizeof f);
-    const BnInfo& b = cv.bn;
-    f.rows = c.bn_rows(b); f.count = (float)(c.n * cv.Hout * cv.Wout);
-    f.gamma = c.params + b.w_off; f.beta = c.params + b.b_off;
-    f.rm = bn_running ? bn_running + b.rm_off : nullptr; f.rv = bn_running ? bn_running + b.rv_off : nullptr;
-    f.mean = c.bn_mean(b); f.rstd = c.bn_rstd(b); f.scale = c.bn_scale(b); f.shift = c.bn_shift(b);
-    if (cv2) {
-        const BnFusedFwd g = bn_fused_fwd(c, *cv2, bn_running);
-        f.rows2 = g.rows; f.count2 = g.count; f.gamma2 = g.gamma; f.beta2 = g.beta; f.rm2 = g.rm; f.rv2 = g.rv;
-        f.mean2 = g.mean; f.rstd2 = g.rstd; f.scale2 = g.scale; f.shift2 = g.shift;
-    }
-    f.momentum = kBnMomentum; f.eps = kBnEps; f.frozen = c.frozen;
+    f.s[0] = bn_fwd_side(c, cv, bn_running);
+    if (cv2) f.s[1] = bn_fwd_side(c, *cv2, bn_running);
+    f.count = (float)(c.n * cv.Hout * cv.Wout); f.momentum = kBnMomentum; f.eps = kBnEps; f.frozen = c.frozen;
     return f;
 }
 // BatchNorm (+ residual, ReLU) of a train-mode forward: statistics -> normalised padded activation.  rcv: the
@@ -355,26 +350,26 @@ hipError_t run_bn_fwd(const Ctx& c, const ConvInfo& cv, float* bn_running, int r
 
 // BatchNorm backward geometry of conv cv's BatchNorm: dy (dense) -> dz (padded by dzpad)
 BnBwdParams bn_bwd_params(const Ctx& c, const ConvInfo& cv, const bf16_t* dy, bf16_t* dz, int dzpad) {
-    BnBwdParams b;
-    memset(&b, 0, sizeof b);
-    b.dy = dy; b.z = c.b16(cv.z_off);
-    b.mean = c.bn_mean(cv.bn); b.rstd = c.bn_rstd(cv.bn);
-    b.dz = dz; b.dzHp = cv.Hout + 2 * dzpad; b.dzWp = cv.Wout + 2 * dzpad; b.dzpad = dzpad;
-    b.M = c.n * cv.Hout * cv.Wout; b.H = cv.Hout; b.W = cv.Wout; b.C = cv.Co;
-    return b;
+    return vpd_bn_bwd_params(dy, c.b16(cv.z_off), c.bn_mean(cv.bn), c.bn_rstd(cv.bn), dz, dzpad, c.n, cv.Hout, cv.Wout, cv.Co);
 }
-// one BatchNorm of a fused backward launch: its rows, gamma and gradients (launches with a grid barrier add sync / err)
-BnFusedBwd bn_bwd_side(const Ctx& c, const ConvInfo& cv, float* grads) {
+// conv `cv`'s BatchNorm as one side of a fused backward launch; dz: where a launch that reads the side's own writes it
+BnBwdSide bn_bwd_side(const Ctx& c, const ConvInfo& cv, float* grads, bf16_t* dz) {
+    return BnBwdSide{c.bn_rows(cv.bn), c.params + cv.bn.w_off, c.bn_dgamma(cv.bn, grads), c.bn_dbeta(cv.bn, grads),
+                     c.b16(cv.z_off), c.bn_mean(cv.bn), c.bn_rstd(cv.bn), dz};
+}
+// the fused backward launch of cv's BatchNorm and, when given, a second one of the same shape (launches with a grid barrier add
+// sync / err)
+BnFusedBwd bn_fused_bwd(const Ctx& c, const ConvInfo& cv, float* grads, bf16_t* dz = nullptr, const ConvInfo* cvB = nullptr,
+                        bf16_t* dzB = nullptr) {
     BnFusedBwd f;
     memset(&f, 0, sizeof f);
-    f.rows = c.bn_rows(cv.bn);
-    f.gamma = c.params + cv.bn.w_off; f.dgamma = c.bn_dgamma(cv.bn, grads); f.dbeta = c.bn_dbeta(cv.bn, grads);
+    f.s[0] = bn_bwd_side(c, cv, grads, dz);
+    if (cvB) f.s[1] = bn_bwd_side(c, *cvB, grads, dzB);
     f.count = (float)(c.n * cv.Hout * cv.Wout); f.frozen = c.frozen;
     return f;
 }
-// ... as the second BatchNorm of a launch that serves two: its side, its z and statistics, its dz
-BnBwdSecond bn_bwd_second(const Ctx& c, const ConvInfo& cv, float* grads, bf16_t* dz) {
-    return BnBwdSecond{bn_bwd_side(c, cv, grads), c.b16(cv.z_off), c.bn_mean(cv.bn), c.bn_rstd(cv.bn), dz};
+void bn_bwd_barrier(const Ctx& c, const ConvInfo& cv, BnFusedBwd& f) {
+    f.sync = c.ws + cv.bn.sync_off; f.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
 }
 
 // act != null: ReLU mask from the stored activation (needed when a residual was added before the ReLU);
@@ -389,7 +384,7 @@ hipError_t run_bn_bwd(const Ctx& c, const ConvInfo& cv, bf16_t* dy, const bf16_t
                       int write_g, float* grads, bool relu_from_z = false, bool reduce_done = false,
                       const unsigned char* mask_bits = nullptr, const float* dy_pooled = nullptr) {
     BnBwdParams b = bn_bwd_params(c, cv, dy, dz, dzpad);
-    b.dy_rw = dy; b.act = act; b.aHp = cv.Hout + 2; b.aWp = cv.Wout + 2; b.apad = 1;
+    vpd_bn_bwd_set_act(b, dy, act);
     b.coef = c.bn_coef(cv.bn); b.partials = c.stat_rows(); b.write_g = write_g;
     if (mask_bits) { b.mask_bits = mask_bits; b.act = nullptr; b.write_g = 0; write_g = 0; }
     if (relu_from_z && !reduce_done) { b.act = nullptr; b.mscale = c.bn_scale(cv.bn); b.mshift = c.bn_shift(cv.bn); }
@@ -405,8 +400,8 @@ hipError_t run_bn_bwd(const Ctx& c, const ConvInfo& cv, bf16_t* dy, const bf16_t
         }
     }
     if (fused) {
-        BnFusedBwd f = bn_bwd_side(c, cv, grads);
-        f.sync = c.ws + cv.bn.sync_off; f.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
+        BnFusedBwd f = bn_fused_bwd(c, cv, grads);
+        bn_bwd_barrier(c, cv, f);
         return vpd_launch_bn_bwd_fused(b, f, c.s);
     }
     return vpd_launch_bn_bwd(b, (float)b.M, c.params + cv.bn.w_off, c.bn_dgamma(cv.bn, grads), c.bn_dbeta(cv.bn, grads), c.s,
@@ -420,12 +415,7 @@ hipError_t run_bn_bwd_apply(const Ctx& c, const ConvInfo& cv, const bf16_t* dy, 
     BnBwdParams b = bn_bwd_params(c, cv, dy, dz, dzpad);
     b.mask_bits = mask_bits;
     b.xcd_tile_px = bn_xcd_tile_px(c, cv);
-    const BnFusedBwd f = bn_bwd_side(c, cv, grads);
-    if (cvB) {
-        const BnBwdSecond B = bn_bwd_second(c, *cvB, grads, dzB);
-        return vpd_launch_bn_bwd_apply_fused(b, f, c.s, &B);
-    }
-    return vpd_launch_bn_bwd_apply_fused(b, f, c.s);
+    return vpd_launch_bn_bwd_apply_fused(b, bn_fused_bwd(c, cv, grads, dz, cvB, dzB), c.s);
 }
 
 // block-output BatchNorm (A: the block's last conv) and the down-sampling branch's BatchNorm (Bc) in one launch: same dy,
@@ -436,25 +426,16 @@ bool bn_bwd_pair_ok(const Ctx& c, const ConvInfo& A, const ConvInfo& Bc) {
 hipError_t run_bn_bwd_pair(const Ctx& c, const ConvInfo& A, const ConvInfo& Bc, bf16_t* dy, const bf16_t* act, bf16_t* dzA,
                            bf16_t* dzB, float* grads) {
     BnBwdParams b = bn_bwd_params(c, A, dy, dzA, 1);
-    b.dy_rw = dy; b.act = act; b.aHp = A.Hout + 2; b.aWp = A.Wout + 2; b.apad = 1;
-    BnFusedBwd fA = bn_bwd_side(c, A, grads);
-    fA.sync = c.ws + A.bn.sync_off;
-    fA.err = reinterpret_cast<unsigned*>(c.ws + c.p->syncerr_off);
-    return vpd_launch_bn_bwd_fused2(b, fA, bn_bwd_second(c, Bc, grads, dzB), c.s);
+    vpd_bn_bwd_set_act(b, dy, act);
+    BnFusedBwd f = bn_fused_bwd(c, A, grads, dzA, &Bc, dzB);
+    bn_bwd_barrier(c, A, f);
+    return vpd_launch_bn_bwd_fused2(b, f, c.s);
 }
 
 // ---- a Bottleneck identity block's closing 1x1 convolution together with its BatchNorm, the convolution recomputed instead of
 // written and read back (conv_stream.hip, conv1x1_bn_stream_kernel; VPD_BNECK_RECOMPUTE=0: conv + BatchNorm launches) ----
 ConvParams conv3_params(const Ctx& c, const ConvInfo& cv, const bf16_t* x) {
-    ConvParams q;
-    memset(&q, 0, sizeof q);
-    q.x = x; q.xHp = cv.Hin + 2; q.xWp = cv.Win + 2; q.xC = cv.Ci;
-    q.w = c.b16(c.p->arena_off) + cv.fwd_off;
-    q.yHp = cv.Hout; q.yWp = cv.Wout; q.yC = cv.Co; q.ypad = 0;
-    q.N = c.n; q.Hs = cv.Hout; q.Ws = cv.Wout; q.osub = 1; q.istr = cv.stride;
-    q.Kc = cv.Kc; q.Co = cv.Co; q.M = c.n * cv.Hout * cv.Wout;
-    q.taps = conv_taps_fwd(cv);
-    return q;
+    return vpd_conv1x1_params(x, c.b16(c.p->arena_off) + cv.fwd_off, c.n, cv.Hout, cv.Wout, cv.stride, cv.Kc, cv.Co);
 }
 bool bneck_recompute_ok(const Ctx& c, const BlockInfo& B) {
     if (!c.p->bottleneck || B.ds || !c.p->train || !c.fused(B.c3) || !relu_bits_ok(c, B.c3)) return false;
@@ -474,70 +455,56 @@ bool bneck_recompute2_ok(const Ctx& c, const BlockInfo& B) {
     if (B.c3.Hin != B.cd.Hin || B.c3.Win != B.cd.Win) return false;
     return vpd_conv1x1_bn2_eligible(conv3d_params(c, B, c.b16(B.a2_off)));
 }
+// one pass of the tail on conv `cv` (two: the pair launch of a down-sampling block), in timing class 4
+hipError_t launch_tail(const Ctx& c, const ConvParams& q, const BnTailLaunch& t, bool two, double flops) {
+    TimeScope ts(c.p, c.s, 4, flops);
+    return two ? vpd_launch_conv1x1_bn2(q, t, c.s) : vpd_launch_conv1x1_bn(q, t, c.s);
+}
+// the statistics pass (a recomputation: its time counts, its FLOPs are not algorithmic work)
+hipError_t run_conv3_bn_stats(const Ctx& c, const ConvInfo& cv, const bf16_t* x) {
+    ConvParams q = conv3_params(c, cv, x);
+    vpd_conv_set_bn_rows(q, c.bn_rows(cv.bn));
+    return launch_tail(c, q, BnTailLaunch{BN_TAIL_STATS, nullptr, nullptr, nullptr, 0}, false, 0.0);
+}
+// the two backward passes: sums, then apply with every dz padded by 1 (BatchNorm backwards: no algorithmic matrix FLOPs)
+hipError_t run_tail_bwd(const Ctx& c, const ConvParams& q, const BnFusedBwd& f, bool two) {
+    hipError_t e = launch_tail(c, q, BnTailLaunch{BN_TAIL_BWD_SUMS, nullptr, nullptr, &f, 0}, two, 0.0);
+    if (e != hipSuccess) return e;
+    return launch_tail(c, q, BnTailLaunch{BN_TAIL_BWD_APPLY, nullptr, nullptr, &f, 1}, two, 0.0);
+}
 hipError_t run_conv3d_bn_fwd(const Ctx& c, const BlockInfo& B, const bf16_t* xin, bf16_t* out, unsigned char* mask_out,
                              float* bn_running) {
-    hipError_t e;
-    for (int k = 0; k < 2; ++k) {      // the two statistics passes
-        const ConvInfo& cv = k ? B.cd : B.c3;
-        ConvParams q = conv3_params(c, cv, k ? xin : c.b16(B.a2_off));
-        q.stats = c.bn_rows(cv.bn); q.stat_rows = VPD_FUSED_ROWS;
-        TimeScope ts(c.p, c.s, 4, 0.0);      // (a recomputation: its time counts, its FLOPs are not algorithmic work)
-        e = vpd_launch_conv1x1_bn(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, c.s);
-        if (e != hipSuccess) return e;
-    }
+    hipError_t e = run_conv3_bn_stats(c, B.c3, c.b16(B.a2_off));
+    if (e == hipSuccess) e = run_conv3_bn_stats(c, B.cd, xin);
+    if (e != hipSuccess) return e;
     ConvParams q = conv3d_params(c, B, xin);
-    q.y = out; q.yHp = B.c3.Hout + 2; q.yWp = B.c3.Wout + 2; q.ypad = 1;
+    vpd_conv_set_y(q, out, 1);
     const BnFusedFwd f = bn_fused_fwd(c, B.c3, bn_running, &B.cd);
-    TimeScope ts(c.p, c.s, 4, conv_flops(B.c3, c.n) + conv_flops(B.cd, c.n));
-    return vpd_launch_conv1x1_bn2(q, &f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mask_out, nullptr, nullptr, 0, 1, c.s);
+    return launch_tail(c, q, BnTailLaunch{BN_TAIL_FWD, &f, mask_out, nullptr, 0}, true, conv_flops(B.c3, c.n) + conv_flops(B.cd, c.n));
 }
 hipError_t run_conv3d_bn_bwd(const Ctx& c, const BlockInfo& B, const bf16_t* xin, bf16_t* dout, const unsigned char* mask_bits,
                              bf16_t* dz3, bf16_t* dzd, float* grads) {
     ConvParams q = conv3d_params(c, B, xin);
     q.y = dout; q.acc_mask = mask_bits;
-    const BnFusedBwd f3 = bn_bwd_side(c, B.c3, grads), fd = bn_bwd_side(c, B.cd, grads);
-    hipError_t e;
-    {
-        TimeScope ts(c.p, c.s, 4, 0.0);      // (BatchNorm backwards: no algorithmic matrix FLOPs)
-        e = vpd_launch_conv1x1_bn2(q, nullptr, &f3, &fd, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 2, c.s);
-    }
-    if (e != hipSuccess) return e;
-    TimeScope ts(c.p, c.s, 4, 0.0);
-    return vpd_launch_conv1x1_bn2(q, nullptr, &f3, &fd, c.bn_mean(B.c3.bn), c.bn_rstd(B.c3.bn), c.bn_mean(B.cd.bn), c.bn_rstd(B.cd.bn),
-                                  nullptr, dz3, dzd, 1, 3, c.s);
+    return run_tail_bwd(c, q, bn_fused_bwd(c, B.c3, grads, dz3, &B.cd, dzd), true);
 }
 // forward: statistics pass, then relu(BatchNorm(conv(x)) + res) -> out (padded) + the ReLU bit map
 hipError_t run_conv3_bn_fwd(const Ctx& c, const ConvInfo& cv, const bf16_t* x, const bf16_t* res, bf16_t* out,
                             unsigned char* mask_out, float* bn_running) {
-    ConvParams q = conv3_params(c, cv, x);
-    q.stats = c.bn_rows(cv.bn); q.stat_rows = VPD_FUSED_ROWS;
-    hipError_t e;
-    {
-        TimeScope ts(c.p, c.s, 4, 0.0);      // (the statistics pass is a recomputation: time counted, FLOPs not)
-        e = vpd_launch_conv1x1_bn(q, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, c.s);
-    }
+    hipError_t e = run_conv3_bn_stats(c, cv, x);
     if (e != hipSuccess) return e;
-    q.stats = nullptr; q.stat_rows = 0;
-    q.y = out; q.yHp = cv.Hout + 2; q.yWp = cv.Wout + 2; q.ypad = 1;
-    q.res = res; q.rHp = cv.Hout + 2; q.rWp = cv.Wout + 2; q.rC = cv.Co; q.rpad = 1;
+    ConvParams q = conv3_params(c, cv, x);
+    vpd_conv_set_y(q, out, 1);
+    vpd_conv_set_res(q, res);
     const BnFusedFwd f = bn_fused_fwd(c, cv, bn_running);
-    TimeScope ts(c.p, c.s, 4, conv_flops(cv, c.n));
-    return vpd_launch_conv1x1_bn(q, &f, nullptr, nullptr, nullptr, mask_out, nullptr, 0, 1, c.s);
+    return launch_tail(c, q, BnTailLaunch{BN_TAIL_FWD, &f, mask_out, nullptr, 0}, false, conv_flops(cv, c.n));
 }
 // backward: the sums of g = dout * mask and g * z, then dz = A g + B z + D -> dz (padded by 1), dgamma, dbeta
 hipError_t run_conv3_bn_bwd(const Ctx& c, const ConvInfo& cv, const bf16_t* x, bf16_t* dout, const unsigned char* mask_bits,
                             bf16_t* dz, float* grads) {
     ConvParams q = conv3_params(c, cv, x);
     q.y = dout; q.acc_mask = mask_bits;
-    const BnFusedBwd f = bn_bwd_side(c, cv, grads);
-    hipError_t e;
-    {
-        TimeScope ts(c.p, c.s, 4, 0.0);      // (a BatchNorm backward: no algorithmic matrix FLOPs)
-        e = vpd_launch_conv1x1_bn(q, nullptr, &f, nullptr, nullptr, nullptr, nullptr, 0, 2, c.s);
-    }
-    if (e != hipSuccess) return e;
-    TimeScope ts(c.p, c.s, 4, 0.0);
-    return vpd_launch_conv1x1_bn(q, nullptr, &f, c.bn_mean(cv.bn), c.bn_rstd(cv.bn), nullptr, dz, 1, 3, c.s);
+    return run_tail_bwd(c, q, bn_fused_bwd(c, cv, grads, dz), false);
 }
 
 
