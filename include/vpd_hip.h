@@ -477,6 +477,25 @@ int vpd_op_wgrad(const void* dz_bf16, const void* x_bf16, float* dw, int n, int 
                  int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
                  float* slab, void* stream);
 size_t vpd_op_wgrad_slab_bytes(void);
+/* Host-only: what the launcher behind vpd_op_wgrad decides for that geometry, by its own routing and split code; nothing is
+ * launched and no device is needed.  has_slab: a slab is given; prefer_halo_1x1: the wish vpd_backward states for the 1x1
+ * convolutions of the BasicBlock students (VPD_WGRAD_1X1=0 / 1 overrides it).  out9 = {kernel: 0 atomics, 1 stem, 2 halo 3x3,
+ * 3 halo 1x1; pass instantiation (halo: 3, 4, 5, 10 or 13; stem: 4; atomics: 0); ring stages (atomics: its 2 LDS buffers); TR;
+ * multi; NHP (halo: padded input pixels of a chunk's halo; stem: input pixels a chunk stages; atomics: 0); ksplit = grid.y;
+ * cpb, chunks per split (64-pixel chunks; atomics: 128-pixel); grid.x}. */
+int vpd_op_wgrad_dispatch(int n, int dzHp, int dzWp, int dzC, int dzpad, int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc,
+                          int Co, const int* tapset9, int has_slab, int prefer_halo_1x1, int* out9);
+/* Grouped 64 x 64 weight gradients (conv_wgrad_halo_grouped_kernel) of `nprob` 3x3 stride-1 pad-1 convolutions in ONE launch: the
+ * form vpd_backward uses for every such convolution whose output channels are no multiple of 128.  dims: 5 ints per problem
+ * {n, H, W, Co, Ci}; dz[i], x[i]: zero-bordered NHWC [n][H+2][W+2][Co | Ci]; dw[i]: fp32 [9][Co][Ci], OVERWRITTEN; slab[i]: fp32
+ * scratch of vpd_op_wgrad_group_slab_floats(Co, Ci) floats.  Refuses, before anything is launched: nprob outside 1..18, null
+ * pointers, channels that are no multiple of 64, a plane the halo tiling does not take, problems whose halo pass counts differ.
+ * vpd_op_wgrad_group_dispatch (host-only, the launcher's own split chooser): out = {pass instantiation, tasks, grid, halo passes}
+ * followed by {ksplit, cpb, tiles} per problem, 4 + 3 nprob ints. */
+size_t vpd_op_wgrad_group_slab_floats(int Co, int Ci);
+int vpd_op_wgrad_group_dispatch(int nprob, const int* dims, int* out);
+int vpd_op_wgrad_group(int nprob, const void* const* dz, const void* const* x, float* const* dw, float* const* slab, const int* dims,
+                       void* stream);
 /* A down-sampling BasicBlock's two weight gradients in ONE launch (the form vpd_backward uses at the three stage boundaries of
  * ResNet-18/34): the 3x3 stride-2 pad-1 conv1 (dz, dw [9][Co][Kc], tapset9 = its taps as for vpd_op_wgrad) and the 1x1 stride-2 pad-0
  * branch (dz2, dw2 [Co][Kc]) read the same x; dz2 has dz's geometry.  The branch rides on conv1's staged halo as a tenth tap.
@@ -496,7 +515,9 @@ int vpd_op_tr_read_probe(const void* tile_bf16, void* out_bf16, void* stream);
  * form vpd_backward uses per ResNet stage; reference: the weight half of loss.backward(), models/util.py:52).
  * dims: 7 ints per problem {n, H, W, Co, Ci, stride, k} (H, W: output size; stride 1 or 2; k = 3: 3x3 pad 1, k = 1: 1x1 pad 0);
  * dz[i]: zero-bordered bf16 NHWC [n][H+2][W+2][Co]; x[i]: zero-bordered bf16 NHWC [n][stride*H+2][stride*W+2][Ci]; dw[i]: fp32
- * [k*k][Co][Ci]; slab[i]: vpd_op_wgrad128_slab_floats(Co, Ci) floats; dev_table: vpd_op_wgrad128_table_bytes() bytes. 
+ * [k*k][Co][Ci]; slab[i]: vpd_op_wgrad128_slab_floats(Co, Ci) floats; dev_table: vpd_op_wgrad128_table_bytes() bytes.
+ * A problem with k = 1, stride 1, Co no multiple of 128 and Ci a multiple of 128 runs with its operands swapped and its tiles stored
+ * transposed, as vpd_backward states it; dw keeps the [Co][Ci] layout.
  * The schedule is rebuilt, uploaded into `table` and the stream synchronised on EVERY call (no cache keyed by the table's address:
  * a freed and re-allocated table would be taken for uploaded): not usable under stream capture, and not a timing entry point. */
 size_t vpd_op_wgrad128_table_bytes(void);

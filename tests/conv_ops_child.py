@@ -125,6 +125,13 @@ class Geo:
         return (self.n, self.h + 2, self.w + 2, self.ci, self.ho + 2 * ypad, self.wo + 2 * ypad, self.co, ypad, self.ho, self.wo,
                 1, 0, 0, self.st, self.ci, self.co, self.fwd_taps)
 
+    def wgrad_args(self):
+        """(n, dzHp, dzWp, dzC, dzpad, xHp, xWp, xC, Hs, Ws, istr, Kc, Co), taps: of vpd_op_wgrad and vpd_op_wgrad_dispatch"""
+        if self.cs.get("stem"):      # dz dense; the input as the forward reads it
+            return (self.n, self.ho, self.wo, self.co, 0, self.h + 6, self.w + 8, 8, self.ho, self.wo, 2, 64, self.co), tapset(7, 1, 0, 1, 0, 0, 0, 1, 0)
+        return (self.n, self.ho + 2, self.wo + 2, self.co, 1, self.h + 2, self.w + 2, self.ci, self.ho, self.wo, self.st, self.ci,
+                self.co), self.fwd_taps
+
     def dgrad_launches(self):
         """stride 1: one launch; stride 2: the parity classes (ph, pw) of the input pixels (tests/test_ops_gpu.py)"""
         n, h, w, k, pad = self.n, self.h, self.w, self.k, self.pad
@@ -242,6 +249,15 @@ def run_ops(ops, G, o, want):
                                      None, stream()))
         finish(key, y, (n, ho, wo, co), 1)
     if cs.get("stem"):
+        if "wgrad" in want:                              # the atomics kernel, then conv_wgrad_stem_kernel + slab; dz dense
+            dzd = R.nhwc(o["dz"]).contiguous().to(ops.dt).cuda()
+            slab = torch.empty(L.vpd_op_wgrad_slab_bytes() // 4, dtype=torch.float32, device="cuda")
+            wa, wt = G.wgrad_args()
+            for key, use_slab in (("wgrad_atomics", False), ("wgrad_slab", True)):
+                dw = torch.zeros(7, co, 64, dtype=torch.float32, device="cuda")
+                ops.check(L.vpd_op_wgrad(ptr(dzd), ptr(xp), ptr(dw), *wa, wt, ptr(slab) if use_slab else None, stream()))
+                torch.cuda.synchronize()
+                res[key] = {"got": R.stem_wgrad_view(dw.cpu().double(), ci), "kept": True, "sha": sha(dw)}
         return res
     # data gradient: store, accumulate, masked accumulate
     launches = G.dgrad_launches()
@@ -274,14 +290,15 @@ def run_ops(ops, G, o, want):
             ops.check(L.vpd_op_conv2d_bnsums(ptr(dzp), ptr(wd), ptr(y), ptr(zd), ptr(bits), ptr(rows), a[0], a[1], a[2], a[3], a[8], a[9],
                                              a[14], a[15], a[16], acc, stream()))
         finish(key, y, (n, h, w, ci), 0, {"rows": rows.sum(dim=0).cpu(), "rows2": rows2.sum(dim=0).cpu() if two else None})
-    # weight gradients (fp32): the atomics kernel, the halo + slab kernel, the grouped persistent kernel
+    # weight gradients (fp32): the atomics kernel, the halo + slab kernel (check_wgrad_dispatch asserts both routes), the grouped
+    # persistent kernel
     if "wgrad" in want:
         k, st = G.k, G.st
         slab = torch.empty(L.vpd_op_wgrad_slab_bytes() // 4, dtype=torch.float32, device="cuda")
         for key, use_slab in (("wgrad_atomics", False), ("wgrad_slab", True)):
             dw = torch.zeros(k * k, co, ci, dtype=torch.float32, device="cuda")
-            ops.check(L.vpd_op_wgrad(ptr(dzp), ptr(xp), ptr(dw), n, ho + 2, wo + 2, co, 1, h + 2, w + 2, ci, ho, wo, st, ci, co,
-                                     G.fwd_taps, ptr(slab) if use_slab else None, stream()))
+            wa, wt = G.wgrad_args()
+            ops.check(L.vpd_op_wgrad(ptr(dzp), ptr(xp), ptr(dw), *wa, wt, ptr(slab) if use_slab else None, stream()))
             torch.cuda.synchronize()
             res[key] = {"got": dw.cpu().double().view(k, k, co, ci).permute(2, 3, 0, 1), "kept": True, "sha": sha(dw)}
         if cs["wgrad"] == "no_group":                   # (64 -> 64 channels: no 128 x 64 tile)
@@ -333,7 +350,7 @@ def references(cs, o, want, name, regime):
         M = cs["n"] * R.conv_geom(cs)[3] * R.conv_geom(cs)[4]
         # fp32 out: no final element rounding; split sums are added in fp32 (slab / atomics: a handful more roundings)
         b = R.conv_gamma(R.conv_wgrad(o["x"].abs(), o["dz"].abs(), cs), M + 64) if rnd else None
-        for key in ("wgrad_atomics", "wgrad_slab") + (() if cs["wgrad"] == "no_group" else ("wgrad_group",)):
+        for key in ("wgrad_atomics", "wgrad_slab") + (() if cs["wgrad"] in ("no_group", "stem") else ("wgrad_group",)):
             ref[key] = (wg, b)
     return ref
 
@@ -341,8 +358,8 @@ def references(cs, o, want, name, regime):
 def wanted(G, disp):
     """the operations of a case: what its kernels implement"""
     cs = G.cs
-    if cs.get("stem"):
-        return ["fwd", "fwd_plain"]                      # (the stem's data gradient is never taken; its weight gradient: test_ops_gpu.py)
+    if cs.get("stem"):                                   # (the stem's data gradient is never taken)
+        return ["fwd", "fwd_plain"] + (["wgrad"] if cs.get("wgrad") else [])
     want = ["fwd", "dgrad"]
     if G.k == 1 and G.st == 2:
         return ["fwd"]                                   # (its data gradient writes one pixel in four: no dense store to pin here)
@@ -403,6 +420,22 @@ def check_dispatch(run, table, fail):
             fail.append("epilogue mode of %s: %d" % (op, d["mode"]))
 
 
+def check_wgrad_dispatch(run, ops, G, fail):
+    """the two vpd_op_wgrad launches of a case with a weight gradient: the atomics kernel without a slab, with one the kernel and pass
+    instantiation opref.WG_ROUTES_CONV names; asked of both libraries before anything is launched"""
+    if not G.cs.get("wgrad"):
+        return {}
+    kern, inst = R.WG_ROUTES_CONV[RUNS[run][0]]
+    wa, wt = G.wgrad_args()
+    table = {}
+    for name, op in ops.items():
+        d0, d1 = R.wg_dispatch(op.L, wa, wt, 0), R.wg_dispatch(op.L, wa, wt, 1)
+        fail += R.wg_route_errors(d0, "%s wgrad_atomics" % name, kernel="atomics", inst=0)
+        fail += R.wg_route_errors(d1, "%s wgrad_slab" % name, kernel=kern, inst=inst)
+        table[name] = {"wgrad_atomics": d0, "wgrad_slab": d1}
+    return table
+
+
 def main():
     run, mode = sys.argv[1], sys.argv[2]
     torch.set_num_threads(min(16, torch.get_num_threads()))
@@ -414,7 +447,8 @@ def main():
             if table != dispatch_table(ops["fp16"], G):
                 fail.append("the two libraries dispatch differently")
             check_dispatch(one, table, fail)
-            print("RESULT " + json.dumps({"run": one, "fail": fail, "dispatch": table}))
+            wtable = check_wgrad_dispatch(one, ops, G, fail)
+            print("RESULT " + json.dumps({"run": one, "fail": fail, "dispatch": table, "wgrad_dispatch": wtable}))
         return
     cs = R.CONV_CASES[RUNS[run][0]]
     G = Geo(cs)
@@ -423,8 +457,9 @@ def main():
     if table != dispatch_table(ops["fp16"], G):
         fail.append("the two libraries dispatch differently")
     check_dispatch(run, table, fail)
+    wtable = check_wgrad_dispatch(run, ops, G, fail)
     if fail:                                             # a moved dispatch fails the run before anything is launched
-        print("RESULT " + json.dumps({"fail": fail, "dispatch": table, "record": record, "digest": digest}))
+        print("RESULT " + json.dumps({"fail": fail, "dispatch": table, "wgrad_dispatch": wtable, "record": record, "digest": digest}))
         return
     want = wanted(G, ops["bf16"].dispatch)
     seed = R.CONV_SEEDS[0]
@@ -487,7 +522,7 @@ def main():
                             fail.append("%s: %s off by %.2e / %.2e of the absolute sums" % (tag, rn, float((e1 / m1).max()), float((e2 / m2).max())))
             del got
     record["seconds"] = time.time() - t0
-    print("RESULT " + json.dumps({"fail": fail, "dispatch": table, "record": record, "digest": digest}))
+    print("RESULT " + json.dumps({"fail": fail, "dispatch": table, "wgrad_dispatch": wtable, "record": record, "digest": digest}))
 
 
 if __name__ == "__main__":

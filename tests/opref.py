@@ -346,7 +346,7 @@ CONV_CASES = {
     # stem (class 5, conv_stem_persistent_kernel): 7x7 stride 2 on the 5-channel input at the student's real size, 512 tiles of two
     # output rows, two per block; and a 32 x 32 input (eight output rows per tile)
     "stem_w128":     dict(n=16,  ci=5,   co=64,  h=128, w=128, k=7, stride=2, stem=True, blk_px=2 * 128),
-    "stem_w32":      dict(n=6,   ci=5,   co=64,  h=32, w=32, k=7, stride=2, stem=True, blk_px=128),
+    "stem_w32":      dict(n=6,   ci=5,   co=64,  h=32, w=32, k=7, stride=2, stem=True, blk_px=128, wgrad="stem"),
     "stem_w128_walk": dict(n=16, ci=5,   co=64,  h=128, w=128, k=7, stride=2, stem=True, blk_px=32 * 128),   # 16 CUs: 32 tiles per block
     # 1x1 ring GEMM (conv1x1_ws_kernel): K = 512, 200 tiles of 256 x 128
     "ring_1x1":      dict(n=50,  ci=512, co=128, h=32, w=32, k=1, blk_px=256),
@@ -916,3 +916,125 @@ def slab_sum_ref(slab):
 
 
 ZERO_RANGE_CASES = {1: (1,), 3: (1, 512 * 256 + 77, 300), 16: tuple([1, 7, 256, 257, 1000, 3, 64, 5000] * 2)}      # float4 per range
+
+
+# ---------------------------------------------------------------------------
+# 64-wide weight-gradient kernels, route by route (tests/test_wgrad_routes_gpu.py, tests/wgrad_routes_child.py,
+# tests/test_wgrad_routes_cpu.py).  Every number below is asserted through vpd_op_wgrad_dispatch / vpd_op_wgrad_group_dispatch.
+# ---------------------------------------------------------------------------
+WG_KERNELS = ("atomics", "stem", "halo3x3", "halo1x1")        # out9[0] of vpd_op_wgrad_dispatch
+WG_OUT9 = ("kernel", "inst", "stages", "TR", "multi", "NHP", "ksplit", "cpb", "grid_x")
+# grouped launch (conv_wgrad_halo_grouped_kernel): problems (n, H, W, Co, Ci) of 3x3 stride-1 pad-1 convolutions; head = (pass
+# instantiation, tasks, grid, halo passes); per problem (ksplit, cpb, tiles)
+WG_GROUPS = {
+    # six splits of 8 chunks; one split of two chunks, the second ragged (80 pixels), stored straight into dw; 4 splits x 2 tiles.
+    # 15 tasks on a grid of 16: one padded block returns early; a multi problem (4 x 4 planes) beside row problems
+    "np5_mixed":       ([(3, 32, 32, 64, 64), (5, 4, 4, 64, 64), (2, 32, 32, 128, 64)], (5, 15, 16, 5), [(6, 8, 1), (1, 2, 1), (4, 8, 2)]),
+    # the four-pass instantiation: 16-wide rows and 8 x 8 planes
+    "np4_mixed":       ([(3, 16, 16, 64, 64), (5, 8, 8, 128, 64), (7, 16, 16, 64, 128)], (4, 12, 16, 4), [(2, 6, 1), (1, 5, 2), (4, 7, 2)]),
+    # short last splits: 200 chunks in 25 splits of 8; 37 chunks in 5 splits of 8, the last holds 5
+    "np4_short_last":  ([(50, 16, 16, 64, 64), (37, 8, 8, 64, 64)], (4, 30, 32, 4), [(25, 8, 1), (5, 8, 1)]),
+    # two tasks on a grid of 8: six idle blocks
+    "np5_one":         ([(1, 32, 32, 64, 64)], (5, 2, 8, 5), [(2, 8, 1)]),
+    # four equal layer1 problems at 7 crops: 14 splits each, 56 tasks, exactly 7 per XCD
+    "np5_layer1_x4":   ([(7, 32, 32, 64, 64)] * 4, (5, 56, 56, 5), [(14, 8, 1)] * 4),
+}
+# stem (conv_wgrad_stem_kernel): (crops, H, W of the input) -> (TR, ksplit, cpb); 130 crops: 520 chunks in 174 splits of three, the
+# last holds one
+WG_STEM = {
+    "w128_n2":   ((2, 128, 128), (1, 128, 1)),
+    "w64_n3":    ((3, 64, 64), (2, 48, 1)),
+    "w32_n3":    ((3, 32, 32), (4, 12, 1)),
+    "w32_n130":  ((130, 32, 32), (4, 174, 3)),
+}
+WG_STEM_REFUSED = {"w34_n3": (3, 34, 34), "w48_n3": (3, 48, 48)}      # odd output size; 24-wide rows: neither divides a 64-pixel chunk
+
+
+# single launches (vpd_op_wgrad with a slab; without one every case takes the atomics kernel): kernel and pass instantiation.
+# tests/test_ops_gpu.py::CONV_CASES -- its 1x1 cases take the atomics kernel in both passes of that test's loop: the operator entry
+# states no wish for the halo route and VPD_WGRAD_1X1 is unset
+WG_ROUTES_OPS = {
+    "l1_3x3_s1": ("halo3x3", 4), "l2_3x3_s2": ("halo3x3", 10), "l2_1x1_s2": ("atomics", 0), "l3_3x3_s1_ragged": ("halo3x3", 5),
+    "l4_3x3_s1_tiny": ("atomics", 0),                     # 2 x 2 planes: 32 images per chunk, a halo of 256 pixels is refused
+    "l2_3x3_s1_big": ("halo3x3", 4), "l2_3x3_s2_32to16": ("halo3x3", 10), "l4_3x3_s2_8to4_ragged": ("halo3x3", 13),
+    "b1_1x1_s1_256to64": ("atomics", 0), "b3_1x1_s1_128to512_ragged": ("atomics", 0), "ds_1x1_s2_32to16": ("atomics", 0),
+    "b_1x1_s1_512to128_t256": ("atomics", 0), "b_1x1_s1_1024to256_t128": ("atomics", 0),
+}
+# the cases of CONV_CASES above that carry a weight gradient (tests/conv_ops_child.py)
+WG_ROUTES_CONV = {"c0_w32": ("halo3x3", 5), "c0_w32_walk": ("halo3x3", 5), "c6_w16": ("halo3x3", 4), "c3_w4": ("halo3x3", 5),
+                  "s2_w32": ("halo3x3", 10), "stem_w32": ("stem", 4)}
+# tests/wgrad_pair_child.py::CASES: conv1 on the halo 3x3 route, the branch (VPD_WGRAD_1X1=1) on the halo 1x1 route, same instantiation
+WG_ROUTES_PAIR = {"l2_n5": 10, "l2_n70": 10, "l3_n6": 10, "l3_n37": 10, "l4_n5": 13, "l4_n6": 13, "l4_n67": 13}
+
+
+def wg_dispatch(L, geom13, taps9, has_slab, prefer_halo_1x1=0):
+    """vpd_op_wgrad_dispatch for the 13 geometry arguments of a vpd_op_wgrad call -> dict of WG_OUT9, the kernel by name"""
+    import ctypes as C
+    out = (C.c_int * 9)()
+    if L.vpd_op_wgrad_dispatch(*geom13, taps9, int(bool(has_slab)), prefer_halo_1x1, out) != 0:
+        return {"error": L.vpd_last_error().decode()}
+    d = dict(zip(WG_OUT9, list(out)))
+    d["kernel"] = WG_KERNELS[d["kernel"]]
+    return d
+
+
+def wg_route_errors(d, what, **want):
+    """[] when the dispatch answer d holds every expected field, else one line per field that differs"""
+    return ["dispatch of %s: %s = %r, expected %r (%r)" % (what, k, d.get(k), v, d) for k, v in want.items() if d.get(k) != v]
+
+
+def wg_operands(n, ci, co, h, w, stride, regime, name, g):
+    """x [n][ci][h][w] and dz [n][co][h/stride][w/stride], float64 values the element type holds exactly.  int: {-1, 0, 1} at
+    density 1/2 (every partial sum of at most 2^24 products is an integer that fp32 holds); randn: element-rounded"""
+    sx, sz = (n, ci, h, w), (n, co, h // stride, w // stride)
+    if regime == "int":
+        return _sparse_int(sx, 0.5, g), _sparse_int(sz, 0.5, g)
+    return elem_round(torch.randn(sx, generator=g), name).double(), elem_round(torch.randn(sz, generator=g), name).double()
+
+
+def wg_bound(x, dz, cs):
+    """the per-element randn bound of a weight gradient as tests/conv_ops_child.py applies it: fp32 output, M + 64 additions"""
+    _, _, _, ho, wo = conv_geom(cs)
+    return conv_gamma(conv_wgrad(x.abs(), dz.abs(), cs), x.shape[0] * ho * wo + 64)
+
+
+def stem_wgrad_view(dw, ci):
+    """the stem kernel's dw [7][64][8 column taps x 8 channels] -> [co][ci][7][7] (the eighth tap and channels ci.. are scratch)"""
+    return dw.view(7, 64, 8, 8)[:, :, :7, :ci].permute(1, 3, 0, 2)
+
+
+def wg_chunk_mask(dz, chunk):
+    """dz with everything but the pixels of one 64-pixel chunk (NHW pixel order) zeroed"""
+    n, c, h, w = dz.shape
+    keep = torch.zeros(n * h * w, dtype=torch.bool)
+    keep[chunk * 64:(chunk + 1) * 64] = True
+    return dz * keep.view(n, 1, h, w)
+
+
+def wg_alter_last_chunk(ref, x, dz, cs, ksplit, cpb, split=0):
+    """(i) the last chunk of one split left out (an off-by-one in wg_chunk_range's end)"""
+    nch = (dz.shape[0] * dz.shape[2] * dz.shape[3] + 63) // 64
+    last = min((split + 1) * cpb, nch) - 1
+    return ref - conv_wgrad(x, wg_chunk_mask(dz, last), cs)
+
+
+def wg_alter_tap(ref, x, dz, cs, chunk=0, tap=(0, 2)):
+    """(ii) one tap left out for the pixels of one chunk"""
+    out = ref.clone()
+    out[:, :, tap[0], tap[1]] -= conv_wgrad(x, wg_chunk_mask(dz, chunk), cs)[:, :, tap[0], tap[1]]
+    return out
+
+
+def wg_alter_transposed(ref):
+    """(iv) the [Co][Ci] result of a 1x1 convolution stored as [Ci][Co]: the same memory read back in the convolution's own layout"""
+    co, ci = ref.shape[:2]
+    return ref[:, :, 0, 0].t().contiguous().view(co, ci)[:, :, None, None]
+
+
+def wg_fp32_accumulated(x, dz, cs, chunk=64):
+    """the weight gradient summed the way the kernels do: exact products, fp32 running sum over 64-pixel chunks in order"""
+    n, c, h, w = dz.shape
+    acc = torch.zeros(cs["co"], cs["ci"], cs["k"], cs["k"], dtype=torch.float32)
+    for ch in range((n * h * w + chunk - 1) // chunk):
+        acc = (acc + conv_wgrad(x, wg_chunk_mask(dz, ch), cs).float()).float()
+    return acc.double()

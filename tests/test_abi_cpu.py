@@ -149,6 +149,22 @@ def test_fused_tail_entry_points_are_declared_bound_and_exported(dtype):
 
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+def test_weight_gradient_route_entry_points_are_declared_bound_and_exported(dtype):
+    """vpd_op_wgrad_dispatch, vpd_op_wgrad_group, vpd_op_wgrad_group_slab_floats and vpd_op_wgrad_group_dispatch: test-only additions
+    under ABI 5 (their answers and refusals: tests/test_wgrad_routes_cpu.py)"""
+    from vpd_amd import _lib
+    h = _lib.lib(dtype)
+    assert h.vpd_abi_version() == _lib.ABI_VERSION == 5
+    for n, nargs in (("vpd_op_wgrad_dispatch", 17), ("vpd_op_wgrad_group", 7), ("vpd_op_wgrad_group_slab_floats", 2),
+                     ("vpd_op_wgrad_group_dispatch", 3)):
+        assert n in header_functions() and len(_lib.SIGNATURES[n][1]) == nargs and getattr(h, n).argtypes == _lib.SIGNATURES[n][1]
+    out = (C.c_int * 9)()
+    assert h.vpd_op_wgrad_dispatch(3, 18, 18, 64, 1, 18, 18, 64, 16, 16, 1, 64, 64, (C.c_int * 9)(3, 3, 0, 1, 0, 1, 0, 3, 1), 1, 0, out) == 0
+    assert list(out) == [2, 4, 3, 4, 0, 108, 12, 1, 1]      # halo 3x3, four passes, three stages, TR 4, 108 halo pixels, 12 splits of one
+    assert h.vpd_op_wgrad_group_slab_floats(64, 64) == 64 * 9 * 64 * 64 and h.vpd_op_wgrad_group_slab_floats(512, 512) == 0
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_boundary_entry_points_are_bound_and_reject_bad_arguments(dtype):
     """vpd_op_pack_input, vpd_op_pack_weights, vpd_op_unpack_grads, vpd_op_adamw_pack, vpd_op_wgrad_reduce, vpd_op_zero_ranges:
     test-only additions under ABI 5; every refusal is taken on the host, with a message, before anything is launched"""

@@ -122,7 +122,9 @@ CONV_CASES = [
     # per 64-pixel chunk), the last one with a ragged final chunk
     ("l2_3x3_s2_32to16", 2, 64, 128, 32, 32, 3, 2, 1),
     ("l4_3x3_s2_8to4_ragged", 5, 256, 512, 8, 8, 3, 2, 1),
-    # 1x1 convolutions (Bottleneck blocks, down-sampling branches): the weight gradient runs as the centre tap of the halo kernel
+    # 1x1 convolutions (Bottleneck blocks, down-sampling branches).  Their weight gradient takes the atomics kernel here, with and
+    # without a slab: vpd_op_wgrad states no wish for the halo route and VPD_WGRAD_1X1 is unset.  The centre-tap route of the halo
+    # kernel is compared on the same shapes in tests/test_wgrad_routes_gpu.py (a child with VPD_WGRAD_1X1=1)
     ("b1_1x1_s1_256to64", 3, 256, 64, 16, 16, 1, 1, 0),
     ("b3_1x1_s1_128to512_ragged", 5, 128, 512, 4, 4, 1, 1, 0),
     ("ds_1x1_s2_32to16", 2, 64, 128, 32, 32, 1, 2, 0),
@@ -188,11 +190,15 @@ def test_conv_fwd_dgrad_wgrad(case):
     # ---- weight gradient ----
     L = _lib()
     taps = tapset(k, k, 1 - pad, 1, 1 - pad, 1, 0, k, 1)
+    from tests import opref as R
     slab = torch.empty(L.vpd_op_wgrad_slab_bytes() // 4, dtype=torch.float32, device="cuda")
-    for use_slab in (False, True):        # generic (atomics) kernel, then the halo + slab kernel where eligible
+    geom = (n, ho + 2, wo + 2, co, 1, h + 2, w + 2, ci, ho, wo, stride, ci, co)
+    # the atomics kernel, then with a slab the kernel and pass instantiation opref.WG_ROUTES_OPS names for the case
+    for use_slab, (kern, inst) in ((False, ("atomics", 0)), (True, R.WG_ROUTES_OPS[name])):
+        route = R.wg_route_errors(R.wg_dispatch(L, geom, taps, use_slab), name, kernel=kern, inst=inst)
+        assert not route, route
         dw = torch.zeros(k * k, co, ci, dtype=torch.float32, device="cuda")
-        _check(L.vpd_op_wgrad(ptr(dzp), ptr(xp), ptr(dw), n, ho + 2, wo + 2, co, 1, h + 2, w + 2, ci, ho, wo, stride,
-                              ci, co, taps, ptr(slab) if use_slab else None, stream()))
+        _check(L.vpd_op_wgrad(ptr(dzp), ptr(xp), ptr(dw), *geom, taps, ptr(slab) if use_slab else None, stream()))
         torch.cuda.synchronize()
         gotdw = dw.cpu().view(k, k, co, ci).permute(2, 3, 0, 1)
         assert rel_l2(gotdw, wr.grad) < REL_TOL, use_slab
@@ -223,10 +229,13 @@ def test_stem_conv_and_wgrad():
     L = _lib()
     dzd = dz.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16).cuda()
     slab = torch.empty(L.vpd_op_wgrad_slab_bytes() // 4, dtype=torch.float32, device="cuda")
-    for use_slab in (False, True):        # generic (atomics) kernel, then the raw-row stem kernel + slab
+    from tests import opref as R
+    geom = (n, ho, wo, co, 0, h + 6, w + 8, 8, ho, wo, 2, 64, co)
+    for use_slab, want in ((False, dict(kernel="atomics", inst=0)), (True, dict(kernel="stem", inst=4, TR=4))):      # generic (atomics) kernel, then the raw-row stem kernel + slab
+        route = R.wg_route_errors(R.wg_dispatch(L, geom, taps, use_slab), "stem", **want)
+        assert not route, route
         dw = torch.zeros(7, co, 64, dtype=torch.float32, device="cuda")
-        _check(L.vpd_op_wgrad(ptr(dzd), ptr(xp), ptr(dw), n, ho, wo, co, 0, h + 6, w + 8, 8, ho, wo, 2, 64, co, taps,
-                              ptr(slab) if use_slab else None, stream()))
+        _check(L.vpd_op_wgrad(ptr(dzd), ptr(xp), ptr(dw), *geom, taps, ptr(slab) if use_slab else None, stream()))
         torch.cuda.synchronize()
         got = dw.cpu().view(7, co, 8, 8)[:, :, :7, :c].permute(1, 3, 0, 2)   # -> [co][c][r][t]
         assert rel_l2(got, wr.grad) < REL_TOL, use_slab
@@ -245,6 +254,9 @@ WG128_GROUPS = {
     # 1x1 convolutions as tasks of the same launch: Bottleneck shapes (128 x 128 and 128 x 64 tiles, ragged chunks, splits),
     # the stride-2 down-sampling branch, mixed with a 3x3 problem; (5, 8, 8, 128, 128, 1, 1): 128 x 128 tiles without the 256-channel variant
     "one_by_one_bottleneck": [(9, 16, 16, 128, 512, 1, 1), (9, 16, 16, 512, 128, 1, 1), (5, 8, 8, 256, 64, 1, 1), (5, 8, 8, 128, 128, 1, 1)],
+    # the swapped-operand form (WgradParams::transposed): 1x1 convolutions with 64 outputs and 256 / 128 inputs (ResNet-50's layer1;
+    # ragged chunks) run with dz and x exchanged and store their tiles transposed, beside an ordinary 1x1 and a 3x3 problem
+    "one_by_one_swapped_operands": [(3, 32, 32, 64, 256, 1, 1), (5, 8, 8, 64, 128, 1, 1), (5, 8, 8, 128, 128, 1, 1), (6, 16, 16, 128, 64, 1, 3)],
     "one_by_one_stride2_with_3x3": [(6, 16, 16, 128, 64, 2, 1), (5, 4, 4, 512, 256, 2, 1), (6, 16, 16, 128, 128, 1, 3), (33, 8, 8, 1024, 256, 1, 1)],
 }
 

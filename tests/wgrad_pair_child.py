@@ -57,7 +57,7 @@ def operands(ci, co, ho, n, regime, name, seed):
     return [R.elem_round(torch.randn(s, generator=g), name).double() for s in shapes]
 
 
-def run_case(L, check, name, ci, co, ho, n):
+def run_case(L, check, name, cid, ci, co, ho, n):
     dt = R.ELEM[name][0]
     fail, fig = [], {}
     taps3 = (C.c_int * 9)(3, 3, 0, 1, 0, 1, 0, 3, 1)
@@ -67,6 +67,13 @@ def run_case(L, check, name, ci, co, ho, n):
     slab2 = torch.empty(nslab, dtype=torch.float32, device="cuda")
     geom = (n, ho + 2, ho + 2, co, 1, 2 * ho + 2, 2 * ho + 2, ci, ho, ho, 2, ci, co)
     n3, n1 = 9 * co * ci, co * ci
+    # the two reference launches: conv1 on the halo 3x3 route, the branch (VPD_WGRAD_1X1=1) on the halo 1x1 route, both on the pass
+    # instantiation the case names (13 passes: the two-stage ring); nothing is launched when the launcher says otherwise
+    inst = R.WG_ROUTES_PAIR[cid]
+    fail += R.wg_route_errors(R.wg_dispatch(L, geom, taps3, 1), "%s wgrad 3x3" % cid, kernel="halo3x3", inst=inst, stages=2 if inst == 13 else 3)
+    fail += R.wg_route_errors(R.wg_dispatch(L, geom, taps1, 1), "%s wgrad 1x1" % cid, kernel="halo1x1", inst=inst, stages=2 if inst == 13 else 3)
+    if fail:
+        return {"fail": fail, "figures": fig}
     for regime in ("int", "randn"):
         x, dz, dz2 = operands(ci, co, ho, n, regime, name, 17)
         xp, dzp, dz2p = padded(x, dt), padded(dz, dt), padded(dz2, dt)
@@ -117,7 +124,7 @@ def main():
     L = lib(name)
     out = {}
     for cid, (ci, co, ho, n) in CASES.items():
-        out[cid] = run_case(L, check, name, ci, co, ho, n)
+        out[cid] = run_case(L, check, name, cid, ci, co, ho, n)
         print(cid, name, json.dumps(out[cid]["figures"]), flush=True)
     print("RESULT " + json.dumps(out), flush=True)
 

@@ -101,6 +101,10 @@ SIGNATURES = {
     "vpd_op_mse": (C.c_int, [vp, vp, C.c_longlong, vp, vp, vp, vp]),
     "vpd_op_wgrad": (C.c_int, [vp, vp, vp] + [C.c_int] * 13 + [c_int_p, vp, vp]),
     "vpd_op_wgrad_slab_bytes": (C.c_size_t, []),
+    "vpd_op_wgrad_dispatch": (C.c_int, [C.c_int] * 13 + [c_int_p, C.c_int, C.c_int, c_int_p]),
+    "vpd_op_wgrad_group_slab_floats": (C.c_size_t, [C.c_int, C.c_int]),
+    "vpd_op_wgrad_group_dispatch": (C.c_int, [C.c_int, c_int_p, c_int_p]),
+    "vpd_op_wgrad_group": (C.c_int, [C.c_int, vp, vp, vp, vp, c_int_p, vp]),
     "vpd_op_wgrad_pair": (C.c_int, [vp] * 5 + [C.c_int] * 13 + [c_int_p, vp, vp, vp]),
     "vpd_op_wgrad_pair_lds_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, c_ll_p]),
     "vpd_op_tr_read_probe": (C.c_int, [vp, vp, vp]),

@@ -892,76 +892,109 @@ static void wg_group_choose(const WgradParams* ps, int n, int* ksplit) {
     }
 }
 bool vpd_wgrad_group_eligible(const WgradParams& p) { return wg_route_any_slab(p).halo(); }
+// What vpd_launch_wgrad_group does with `n` problems: every problem's tiling and split (wg_group_choose), the task table's extent,
+// the grid and the instantiation.  0: fine; 1: a plane the halo tiling does not take; 2: the problems' pass counts differ.
+struct WgGroupPlan {
+    int npass, inst, tasks, grid;
+    int tiles[WG_GROUP_MAX], task_begin[WG_GROUP_MAX + 1];
+    WgHaloGeom g[WG_GROUP_MAX];          // ksplit and cpb set
+};
+static int wg_group_plan(const WgradParams* ps, int n, WgGroupPlan* out) {
+    int ks[WG_GROUP_MAX];
+    wg_group_choose(ps, n, ks);
+    out->tasks = 0; out->npass = 0;
+    for (int i = 0; i < n; ++i) {
+        const WgradParams& p = ps[i];
+        WgHaloGeom g;
+        if (!wg_halo_geom(p, &g)) return 1;
+        const int np = (g.NHP + 31) / 32;
+        if (out->npass == 0) out->npass = np;
+        if (np != out->npass) return 2;                           // one stage: one geometry
+        const int nchunks = (p.M + WG_CH - 1) / WG_CH;
+        g.ksplit = ks[i];
+        g.cpb = (nchunks + g.ksplit - 1) / g.ksplit;
+        out->tiles[i] = (p.Co / 64) * (p.Kc / 64);
+        out->task_begin[i] = out->tasks;
+        out->tasks += out->tiles[i] * g.ksplit;
+        out->g[i] = g;
+    }
+    out->task_begin[n] = out->tasks;
+    out->grid = ((out->tasks + 7) / 8) * 8;                       // (the kernel's XCD remap wants a multiple of 8)
+    // a stage's stride-1 convolutions: 3..5 passes (the group has no instantiation beyond 5)
+    wg_npass_dispatch(out->npass, [&](auto np) { out->inst = decltype(np)::value > 5 ? 5 : decltype(np)::value; });
+    return 0;
+}
+// host only: head4 = {pass instantiation, tasks, grid, halo passes}, per3 = {ksplit, cpb, tiles} per problem
+int vpd_wgrad_group_dispatch(const WgradParams* ps, int n, int* head4, int* per3) {
+    if (n < 1 || n > WG_GROUP_MAX) return -1;
+    WgGroupPlan gp;
+    if (const int rc = wg_group_plan(ps, n, &gp)) return rc;
+    head4[0] = gp.inst; head4[1] = gp.tasks; head4[2] = gp.grid; head4[3] = gp.npass;
+    for (int i = 0; i < n; ++i) { per3[3 * i] = gp.g[i].ksplit; per3[3 * i + 1] = gp.g[i].cpb; per3[3 * i + 2] = gp.tiles[i]; }
+    return 0;
+}
+int vpd_wgrad_group_max() { return WG_GROUP_MAX; }
 // ps[i].slab must point to vpd_wgrad_group_slab_floats() floats of its own (ignored when that is 0)
 hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stream) {
     if (n < 1 || n > WG_GROUP_MAX) return hipErrorInvalidValue;
     const int ablate = wg_ablate();
     WgGroup grp = {};
     WgReduceGroup red = {};
+    WgGroupPlan gp;
+    if (wg_group_plan(ps, n, &gp) != 0) return hipErrorInvalidValue;
     grp.nprob = n;
-    int ks[WG_GROUP_MAX];
-    wg_group_choose(ps, n, ks);
-    int tasks = 0, npass = 0;
     for (int i = 0; i < n; ++i) {
         WgradParams p = ps[i];
         p.ablate = ablate;
-        WgHaloGeom g;
-        if (!wg_halo_geom(p, &g)) return hipErrorInvalidValue;
-        const int np = (g.NHP + 31) / 32;
-        if (npass == 0) npass = np;
-        if (np != npass) return hipErrorInvalidValue;             // one stage: one geometry
-        const int nchunks = (p.M + WG_CH - 1) / WG_CH;
-        g.ksplit = ks[i];
-        g.cpb = (nchunks + g.ksplit - 1) / g.ksplit;
-        if (g.ksplit <= 1) p.slab = p.dw;                         // split 0 of a 1-split problem IS the gradient
-        else red.add(p.slab, p.dw, (long)9 * p.Co * p.Kc, g.ksplit);
-        grp.tiles[i] = (p.Co / 64) * (p.Kc / 64);
-        grp.task_begin[i] = tasks;
-        tasks += grp.tiles[i] * g.ksplit;
+        if (gp.g[i].ksplit <= 1) p.slab = p.dw;                   // split 0 of a 1-split problem IS the gradient
+        else red.add(p.slab, p.dw, (long)9 * p.Co * p.Kc, gp.g[i].ksplit);
+        grp.tiles[i] = gp.tiles[i];
+        grp.task_begin[i] = gp.task_begin[i];
         grp.p[i] = p;
-        grp.g[i] = g;
+        grp.g[i] = gp.g[i];
     }
-    grp.task_begin[n] = tasks;
-    const int grid = ((tasks + 7) / 8) * 8;                       // (the kernel's XCD remap wants a multiple of 8)
-    // a stage's stride-1 convolutions: 3..5 passes (the group has no instantiation beyond 5)
-    const size_t lds = wg_ring_lds(npass <= 3 ? 3 : npass, WG_NS, false);
-    wg_npass_dispatch(npass, [&](auto np) {
+    grp.task_begin[n] = gp.tasks;
+    const size_t lds = wg_ring_lds(gp.npass <= 3 ? 3 : gp.npass, WG_NS, false);
+    wg_npass_dispatch(gp.npass, [&](auto np) {
         constexpr int NP = decltype(np)::value > 5 ? 5 : decltype(np)::value;
-        VPD_LAUNCH(conv_wgrad_halo_grouped_kernel<NP>, dim3(grid), dim3(768), lds, stream, grp);
+        VPD_LAUNCH(conv_wgrad_halo_grouped_kernel<NP>, dim3(gp.grid), dim3(768), lds, stream, grp);
     });
     if (!(ablate & 16)) wg_launch_reduce(red, stream);
     return hipGetLastError();
 }
 
-hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
-    if (p0.Kc % 64 != 0 || p0.Co % 64 != 0 || p0.M <= 0) return hipErrorInvalidValue;
-    const WgRoute r = wg_route(p0);
-    WgradParams p = r.p;
-    p.ablate = wg_ablate();
-    if (r.kernel == WG_STEM) {
+// What vpd_launch_wgrad does with a problem: the route, the instantiation, the split and the grid (grid_x, ksplit).  The launcher
+// launches exactly this; vpd_wgrad_dispatch reports it.
+struct WgLaunchPlan {
+    WgRoute r;
+    int npass;          // halo kernels: 32-row passes of the halo
+    int inst, ns;       // halo kernels: the NPASS instantiation and its ring stages; stem: 4 and 3; atomics: 0 and its 2 LDS buffers
+    int ksplit, cpb;    // pixel splits (grid.y) and chunks per split: 64-pixel chunks, the atomics kernel's of 128 pixels
+    int grid_x;         // output tiles (atomics kernel: per tap)
+};
+static bool wg_launch_plan(const WgradParams& p0, WgLaunchPlan* out) {
+    if (p0.Kc % 64 != 0 || p0.Co % 64 != 0 || p0.M <= 0) return false;
+    WgLaunchPlan& L = *out;
+    L.r = wg_route(p0);
+    L.npass = 0;
+    const WgradParams& p = L.r.p;
+    if (L.r.kernel == WG_STEM) {
         const int nchunks = p.M / 64;
-        int ksplit = nchunks < 256 ? nchunks : 256;
-        const int cpb = (nchunks + ksplit - 1) / ksplit;
-        ksplit = (nchunks + cpb - 1) / cpb;
-        const long xelems = (long)p.N * p.xHp * p.xWp * 8 + 64;
-        VPD_LAUNCH(conv_wgrad_stem_kernel, dim3(1, ksplit), dim3(768), wg_ring_lds(4, 3, false), stream, p, r.tr_stem, cpb, xelems);
-        WgReduceGroup red = {};
-        red.add(p.slab, p.dw, (long)7 * 64 * 64, ksplit);
-        wg_launch_reduce(red, stream);
-        return hipGetLastError();
+        L.ksplit = nchunks < 256 ? nchunks : 256;
+        L.cpb = (nchunks + L.ksplit - 1) / L.ksplit;
+        L.ksplit = (nchunks + L.cpb - 1) / L.cpb;
+        L.inst = 4; L.ns = 3; L.grid_x = 1;
+        return true;
     }
-    if (r.halo()) {
-        WgHaloGeom g = r.g;
-        const int tiles = (p.Co / 64) * (p.Kc / 64);
-        g.ksplit = vpd_wgrad_split(p.M, p.Co, p.Kc, &g.cpb);
-        const int npass = (g.NHP + 31) / 32;            // 3..5 (stride 1), up to 10 / 13 (stride 2)
-        wg_npass_dispatch(npass, [&](auto np) {
-            constexpr int NP = decltype(np)::value;
-            constexpr int NS = NP > 10 ? 2 : WG_NS;     // the 13-pass halo (layer4.0: four whole input planes) leaves room for two stages
-            VPD_LAUNCH((conv_wgrad_halo_kernel<NP, NS>), dim3(tiles, g.ksplit), dim3(768), wg_ring_lds(NP, NS, false), stream, p, g);
+    if (L.r.halo()) {
+        L.grid_x = (p.Co / 64) * (p.Kc / 64);
+        L.ksplit = vpd_wgrad_split(p.M, p.Co, p.Kc, &L.cpb);
+        L.npass = (L.r.g.NHP + 31) / 32;                // 3..5 (stride 1), up to 10 / 13 (stride 2)
+        wg_npass_dispatch(L.npass, [&](auto np) {
+            L.inst = decltype(np)::value;
+            L.ns = L.inst > 10 ? 2 : WG_NS;             // the 13-pass halo (layer4.0: four whole input planes) leaves room for two stages
         });
-        if (p.defer_reduce || VPD_ABL(p, 16)) return hipGetLastError();
-        return vpd_launch_wgrad_reduce(p0, stream);
+        return true;
     }
     const int tiles = (p.Co / 64) * (p.Kc / 64) * p.taps.nr * p.taps.nc;
     const int nchunks = (p.M + 127) / 128;
@@ -971,9 +1004,49 @@ hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
     if (ksplit < 1) ksplit = 1;
     int cpb = (nchunks + ksplit - 1) / ksplit;
     if (cpb < 4) cpb = nchunks < 4 ? nchunks : 4;
-    ksplit = (nchunks + cpb - 1) / cpb;
-    p.chunks_per_block = cpb;
-    dim3 grid(tiles, ksplit);
+    L.ksplit = (nchunks + cpb - 1) / cpb;
+    L.cpb = cpb; L.inst = 0; L.ns = 2; L.grid_x = tiles;
+    return true;
+}
+// host only: out9 = {kernel (WgKernel: 0 atomics, 1 stem, 2 halo 3x3, 3 halo 1x1), pass instantiation, ring stages, TR, multi, NHP,
+// ksplit, cpb, grid.x}; TR / multi / NHP are the halo tiling's (stem: TR and the input pixels a chunk stages; atomics: 0).  false:
+// the launcher refuses the problem.
+bool vpd_wgrad_dispatch(const WgradParams& p0, int* out9) {
+    WgLaunchPlan L;
+    if (!wg_launch_plan(p0, &L)) return false;
+    const bool stem = L.r.kernel == WG_STEM, halo = L.r.halo();
+    const int v[9] = {(int)L.r.kernel, L.inst, L.ns, stem ? L.r.tr_stem : halo ? L.r.g.TR : 0, halo ? L.r.g.multi : 0,
+                      stem ? (2 * L.r.tr_stem + 5) * L.r.p.xWp : halo ? L.r.g.NHP : 0, L.ksplit, L.cpb, L.grid_x};
+    memcpy(out9, v, sizeof v);
+    return true;
+}
+
+hipError_t vpd_launch_wgrad(const WgradParams& p0, hipStream_t stream) {
+    WgLaunchPlan L;
+    if (!wg_launch_plan(p0, &L)) return hipErrorInvalidValue;
+    WgradParams p = L.r.p;
+    p.ablate = wg_ablate();
+    const dim3 grid(L.grid_x, L.ksplit);
+    if (L.r.kernel == WG_STEM) {
+        const long xelems = (long)p.N * p.xHp * p.xWp * 8 + 64;
+        VPD_LAUNCH(conv_wgrad_stem_kernel, grid, dim3(768), wg_ring_lds(L.inst, L.ns, false), stream, p, L.r.tr_stem, L.cpb, xelems);
+        WgReduceGroup red = {};
+        red.add(p.slab, p.dw, (long)7 * 64 * 64, L.ksplit);
+        wg_launch_reduce(red, stream);
+        return hipGetLastError();
+    }
+    if (L.r.halo()) {
+        WgHaloGeom g = L.r.g;
+        g.ksplit = L.ksplit; g.cpb = L.cpb;
+        wg_npass_dispatch(L.npass, [&](auto np) {
+            constexpr int NP = decltype(np)::value;
+            constexpr int NS = NP > 10 ? 2 : WG_NS;
+            VPD_LAUNCH((conv_wgrad_halo_kernel<NP, NS>), grid, dim3(768), wg_ring_lds(NP, NS, false), stream, p, g);
+        });
+        if (p.defer_reduce || VPD_ABL(p, 16)) return hipGetLastError();
+        return vpd_launch_wgrad_reduce(p0, stream);
+    }
+    p.chunks_per_block = L.cpb;
     const size_t lds = 64 * 1024;     // max(staging 2*2*16 KiB, reduction 64 KiB)
     VPD_LAUNCH(conv_wgrad_kernel, grid, dim3(256), lds, stream, p);
     return hipGetLastError();

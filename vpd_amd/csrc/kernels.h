@@ -113,6 +113,14 @@ bool vpd_wgrad_group_eligible(const WgradParams& p);
 size_t vpd_wgrad_group_slab_floats(int M, int Co, int Kc, int ntaps = 9);
 hipError_t vpd_launch_wgrad_group(const WgradParams* ps, int n, hipStream_t stream);
 bool vpd_wgrad_overwrites(const WgradParams& p);
+// host only, by the launchers' own decision code (conv_wgrad.hip).  vpd_wgrad_dispatch: what vpd_launch_wgrad does with p, out9 =
+// {kernel: 0 atomics / 1 stem / 2 halo 3x3 / 3 halo 1x1, pass instantiation, ring stages, TR, multi, NHP, ksplit, cpb, grid.x}; false
+// where it refuses p.  vpd_wgrad_group_dispatch: what vpd_launch_wgrad_group does with ps[0..n), head4 = {pass instantiation,
+// tasks, grid, halo passes}, per3 = {ksplit, cpb, tiles} per problem; 0, or -1 n outside 1..vpd_wgrad_group_max(), 1 a plane the
+// halo tiling does not take, 2 pass counts differ.
+bool vpd_wgrad_dispatch(const WgradParams& p, int* out9);
+int vpd_wgrad_group_dispatch(const WgradParams* ps, int n, int* head4, int* per3);
+int vpd_wgrad_group_max();
 // A down-sampling BasicBlock's 3x3 stride-2 conv1 (p3) and its 1x1 stride-2 branch (p1, prefer_halo_1x1 set) in ONE halo launch: the
 // branch rides as a tenth tap on conv1's staged halo (conv_wgrad_halo_pair_kernel; VPD_WGRAD_DS_RIDE=0: never).  _ok: both take the
 // halo path and share input, shapes and split.  The launch leaves both slabs unsummed when p3.defer_reduce; _reduce sums both in one
@@ -257,6 +265,16 @@ inline TapSet vpd_taps_1x1() {      // one tap at padded offset (1, 1): a 1x1 co
     TapSet t;
     t.nr = 1; t.nc = 1; t.dy0 = 1; t.dys = 1; t.dx0 = 1; t.dxs = 1; t.w0 = 0; t.wrs = 1; t.wcs = 1;
     return t;
+}
+// A 1x1 stride-1 weight-gradient problem with fewer than 128 output but a multiple of 128 input channels (layer1's 256 -> 64), restated
+// for the 128-wide grouped launch: operands swapped, result stored transposed (WgradParams::transposed), so dw keeps the
+// convolution's own [Co][Ci] layout.  Input and output planes are the same size at stride 1.  false: q is not such a problem (unchanged).
+inline bool vpd_wgrad_swap_1x1(WgradParams& q) {
+    if (!(q.taps.nr == 1 && q.taps.nc == 1 && q.istr == 1 && q.Co % 128 != 0 && q.xC % 128 == 0) || q.transposed) return false;
+    const bf16_t* dz = q.dz;
+    const int co = q.Co, ci = q.xC;
+    q.dz = q.x; q.dzC = ci; q.x = dz; q.xC = co; q.Co = ci; q.Kc = co; q.transposed = 1;
+    return true;
 }
 // a Bottleneck's closing 1x1 convolution (the tail launchers above): x padded by 1 with Kc channels, H x W output pixels
 inline ConvParams vpd_conv1x1_params(const bf16_t* x, const bf16_t* w, int n, int H, int W, int istr, int Kc, int Co) {

@@ -444,17 +444,85 @@ extern "C" int vpd_op_mse(const float* e, const float* t, long long n, float* de
     return 0;
 }
 
-extern "C" int vpd_op_wgrad(const void* dz, const void* x, float* dw, int n, int dzHp, int dzWp, int dzC, int dzpad,
-                            int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
-                            float* slab, void* stream) {
+static WgradParams op_wgrad_params(const void* dz, const void* x, float* dw, int n, int dzHp, int dzWp, int dzC, int dzpad, int xHp,
+                                   int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9, float* slab) {
     WgradParams q;
     memset(&q, 0, sizeof q);
     q.dz = (const bf16_t*)dz; q.dzHp = dzHp; q.dzWp = dzWp; q.dzC = dzC; q.dzpad = dzpad;
     q.x = (const bf16_t*)x; q.xHp = xHp; q.xWp = xWp; q.xC = xC; q.dw = dw; q.slab = slab;
     q.N = n; q.Hs = Hs; q.Ws = Ws; q.istr = istr; q.Kc = Kc; q.Co = Co; q.M = n * Hs * Ws;
     q.taps = tapset_from(tapset9);
+    return q;
+}
+extern "C" int vpd_op_wgrad(const void* dz, const void* x, float* dw, int n, int dzHp, int dzWp, int dzC, int dzpad,
+                            int xHp, int xWp, int xC, int Hs, int Ws, int istr, int Kc, int Co, const int* tapset9,
+                            float* slab, void* stream) {
+    const WgradParams q = op_wgrad_params(dz, x, dw, n, dzHp, dzWp, dzC, dzpad, xHp, xWp, xC, Hs, Ws, istr, Kc, Co, tapset9, slab);
     if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
     LCHECK(vpd_launch_wgrad(q, (hipStream_t)stream));
+    return 0;
+}
+// host-only: what vpd_launch_wgrad decides for the geometry of a vpd_op_wgrad call (has_slab: a slab is given; prefer_halo_1x1: the
+// caller's wish the plan states for the BasicBlock students' 1x1 convs).  out9: vpd_wgrad_dispatch (kernels.h)
+extern "C" int vpd_op_wgrad_dispatch(int n, int dzHp, int dzWp, int dzC, int dzpad, int xHp, int xWp, int xC, int Hs, int Ws, int istr,
+                                     int Kc, int Co, const int* tapset9, int has_slab, int prefer_halo_1x1, int* out9) {
+    if (!tapset9 || !out9) return fail("null argument");
+    if (n < 1 || Hs < 1 || Ws < 1 || (long long)n * Hs * Ws >= (1ll << 31)) return fail("bad argument");
+    static float present = 0.f;             // (the route reads the slab only as present / absent)
+    WgradParams q = op_wgrad_params(nullptr, nullptr, nullptr, n, dzHp, dzWp, dzC, dzpad, xHp, xWp, xC, Hs, Ws, istr, Kc, Co, tapset9,
+                                    has_slab ? &present : nullptr);
+    q.prefer_halo_1x1 = prefer_halo_1x1 != 0;
+    if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
+    if (!vpd_wgrad_dispatch(q, out9)) return fail("the weight-gradient launcher refuses this shape (channels not a multiple of 64)");
+    return 0;
+}
+
+// ---- the grouped 64 x 64 launch (conv_wgrad_halo_grouped_kernel) of `nprob` 3x3 stride-1 pad-1 convolutions: what
+// WgradQueue::flush (step.hip) gives vpd_launch_wgrad_group.  dims: 5 ints per problem {n, H, W, Co, Ci}; layouts as
+// vpd_op_wgrad128_group documents them; slab[i]: vpd_op_wgrad_group_slab_floats(Co, Ci) floats ----
+static const char* op_wgrad_group_params(int nprob, const void* const* dz, const void* const* x, float* const* dw, float* const* slab,
+                                         const int* dims, WgradParams* qs) {
+    if (nprob < 1 || nprob > vpd_wgrad_group_max()) return "nprob outside 1..18";
+    if (!dims) return "null argument";
+    for (int i = 0; i < nprob; ++i) {
+        const int n = dims[5 * i], H = dims[5 * i + 1], W = dims[5 * i + 2], Co = dims[5 * i + 3], Ci = dims[5 * i + 4];
+        if (n < 1 || H < 1 || W < 1 || (long long)n * H * W >= (1ll << 31)) return "bad argument";
+        if (Co < 64 || Co % 64 || Ci < 64 || Ci % 64) return "Co and Ci must be multiples of 64";
+        static float present = 0.f;
+        const int taps[9] = {3, 3, 0, 1, 0, 1, 0, 3, 1};
+        qs[i] = op_wgrad_params(dz ? dz[i] : nullptr, x ? x[i] : nullptr, dw ? dw[i] : nullptr, n, H + 2, W + 2, Co, 1, H + 2, W + 2, Ci,
+                                H, W, 1, Ci, Co, taps, slab ? slab[i] : &present);
+        if (!vpd_wgrad_group_eligible(qs[i])) return "the halo tiling does not take this plane";
+    }
+    return nullptr;
+}
+extern "C" size_t vpd_op_wgrad_group_slab_floats(int Co, int Ci) { return vpd_wgrad_group_slab_floats(0, Co, Ci, 9); }
+// host-only: out = {pass instantiation, tasks, grid, halo passes} then {ksplit, cpb, tiles} per problem (4 + 3 nprob ints)
+extern "C" int vpd_op_wgrad_group_dispatch(int nprob, const int* dims, int* out) {
+    if (!out) return fail("null argument");
+    WgradParams qs[18];
+    if (const char* e = op_wgrad_group_params(nprob, nullptr, nullptr, nullptr, nullptr, dims, qs)) return fail(e);
+    const int rc = vpd_wgrad_group_dispatch(qs, nprob, out, out + 4);
+    if (rc == 2) return fail("the problems of a group must stage the same number of halo passes");
+    if (rc != 0) return fail("the halo tiling does not take this plane");
+    return 0;
+}
+extern "C" int vpd_op_wgrad_group(int nprob, const void* const* dz, const void* const* x, float* const* dw, float* const* slab,
+                                  const int* dims, void* stream) {
+    if (!dz || !x || !dw || !slab || !dims) return fail("null argument");
+    WgradParams qs[18];
+    if (const char* e = op_wgrad_group_params(nprob, dz, x, dw, slab, dims, qs)) return fail(e);
+    int head[4], per[3 * 18];
+    const int rc = vpd_wgrad_group_dispatch(qs, nprob, head, per);
+    if (rc == 2) return fail("the problems of a group must stage the same number of halo passes");
+    if (rc != 0) return fail("the halo tiling does not take this plane");
+    for (int i = 0; i < nprob; ++i) {
+        if (!dz[i] || !x[i] || !dw[i]) return fail("null argument");
+        // (a problem of one split stores into dw; the others need their slab)
+        if (per[3 * i] > 1 && !slab[i]) return fail("null argument");
+        if ((reinterpret_cast<size_t>(dw[i]) | reinterpret_cast<size_t>(slab[i])) & 15) return fail("dw and slab must be 16-byte aligned");
+    }
+    LCHECK(vpd_launch_wgrad_group(qs, nprob, (hipStream_t)stream));
     return 0;
 }
 
@@ -504,6 +572,7 @@ extern "C" int vpd_op_wgrad128_group(int nprob, const void* const* dz, const voi
             q.taps.nr = 3; q.taps.nc = 3; q.taps.dy0 = 0; q.taps.dys = 1; q.taps.dx0 = 0; q.taps.dxs = 1;
             q.taps.w0 = 0; q.taps.wrs = 3; q.taps.wcs = 1;
         } else q.taps = vpd_taps_1x1();
+        vpd_wgrad_swap_1x1(q);      // 1x1, < 128 outputs, a multiple of 128 inputs: as the step's grouped launch states it
         if (!vpd_wgrad128_eligible(q)) return fail("shape not eligible for the 128 x 64 weight-gradient kernel");
         qs[i] = q;
     }

@@ -178,8 +178,6 @@ inline WgradParams wgrad_params(const ConvInfo& cv, int n, const bf16_t* dz, con
 // with its operands swapped, its result stored transposed (WgradParams::transposed).  The plan sizes the grouped slabs with it.
 inline WgradParams grouped_wgrad_params(const ConvInfo& cv, int n, const bf16_t* dz, const bf16_t* x) {
     WgradParams q = wgrad_params(cv, n, dz, x);
-    if (cv.k == 1 && cv.stride == 1 && cv.Co % 128 != 0 && cv.Ci % 128 == 0) {
-        q.dz = x; q.dzC = cv.Ci; q.x = dz; q.xC = cv.Co; q.Co = cv.Ci; q.Kc = cv.Co; q.transposed = 1;
-    }
+    vpd_wgrad_swap_1x1(q);
     return q;
 }
