@@ -27,6 +27,8 @@ def get_args():
     parser.add_argument('--dtype', default='bf16', choices=['bf16', 'fp16'],
                         help='(this build) element type of the HIP forward: bf16 (default) or fp16 -- the precision the reference '
                              'trains in on a GPU (fp16 autocast), same MFMA rate, 8x finer rounding')
+    parser.add_argument('--ema', action='store_true',
+                        help='(this build) load the averaged weights train_vpd_model.py --ema_decay wrote: <name>_ema.encoder.pt')
     return parser.parse_args()
 
 
@@ -38,7 +40,22 @@ def input_route(host_fp32, jitter):
     return raw_u8, (int(jitter or 0) if raw_u8 else 0)
 
 
-def main(dataset, model_dir, out_dir, model_epoch, flow_img, jitter, no_flip, host_fp32=False, dtype='bf16'):
+def checkpoint_name(model_epoch, ema=False):
+    """best_epoch | epochNNNN, with --ema the averaged twin <name>_ema"""
+    name = 'best_epoch' if model_epoch is None else 'epoch{:04d}'.format(model_epoch)
+    return name + '_ema' if ema else name
+
+
+def load_encoder(model_dir, model_name, encoder_arch, emb_dim, use_flow, device, dtype='bf16'):
+    """The student with <model_dir>/<model_name>.encoder.pt loaded (an ordinary state_dict, averaged weights or not)"""
+    encoder = RGBF_EmbeddingModel(encoder_arch, emb_dim, use_flow, device, dtype=dtype)
+    encoder.load_state_dict(torch.load(os.path.join(model_dir, '{}.encoder.pt'.format(model_name)),
+                                       map_location=device))
+    encoder.to(device)
+    return encoder
+
+
+def main(dataset, model_dir, out_dir, model_epoch, flow_img, jitter, no_flip, host_fp32=False, dtype='bf16', ema=False):
     device = 'cuda'
     model_params = load_json(os.path.join(model_dir, 'config.json'))
     emb_dim = model_params['emb_dim']
@@ -68,12 +85,9 @@ def main(dataset, model_dir, out_dir, model_epoch, flow_img, jitter, no_flip, ho
     ds = FrameDataset(tasks, img_dim, rgb_mean_std, augment_jitter=0 if raw_u8 else (jitter or 0), augment_flip=not no_flip,
                       flow_img_name=flow_img, raw_u8=raw_u8)
 
-    model_name = 'best_epoch' if model_epoch is None else 'epoch{:04d}'.format(model_epoch)
+    model_name = checkpoint_name(model_epoch, ema)
     print('Model name:', model_name)
-    encoder = RGBF_EmbeddingModel(encoder_arch, emb_dim, use_flow, device, dtype=dtype)
-    encoder.load_state_dict(torch.load(os.path.join(model_dir, '{}.encoder.pt'.format(model_name)),
-                                       map_location=device))
-    encoder.to(device)
+    encoder = load_encoder(model_dir, model_name, encoder_arch, emb_dim, use_flow, device, dtype)
 
     loader = DataLoader(ds, batch_size=apply_batch_size(jitter, no_flip), shuffle=False,
                         num_workers=max(os.cpu_count() // 2, 1), pin_memory=True)

@@ -190,6 +190,20 @@ int vpd_plan_adamw_step_scaled(vpd_plan_t* plan, float* params, const float* gra
  * scale *= growth, growth_tracker = 0.  Then found = 0. */
 int vpd_scale_state_update(vpd_scale_state* state, float growth, float backoff, int growth_interval, void* stream);
 
+/* Exponential moving average of the weights (torch.optim.swa_utils.AveragedModel / timm's ModelEmaV2), one launch over up to four
+ * ranges: dst[i][j] = fmaf(omd, src[i][j] - dst[i][j], dst[i][j]) in fp32 for j < n[i], omd = (float)(1 - d) with d computed in
+ * double: d = decay, or min(decay, (1 + t) / (10 + t)) when warmup != 0 (timm's rule; t = updates applied before this one).
+ * The ranges are DEVICE float ranges of any 4-byte alignment and any length >= 0 (the fast path wants src[i] and dst[i] to share
+ * their 16-byte phase); src[i] and dst[i] must not overlap.  The arrays src / dst / n themselves are HOST arrays, copied into the
+ * kernel's arguments: no upload, no synchronisation, capturable into a graph.
+ * state == NULL: `t` is the caller's count, t0 is ignored.  state != NULL (the block of the dynamic loss scaler whose optimizer
+ * step is in flight; call between the AdamW and vpd_scale_state_update): NOTHING is written when state->found is set, and
+ * t = state->applied_steps - t0, the caller's `t` being ignored -- t0 is the applied-step count when averaging began.
+ * Refused on the host, nothing launched: count outside 0..4 (0 returns 0 and looks at nothing else but decay, t, t0), decay outside
+ * [0, 1] or NaN, negative t or t0, null src / dst / n or a null entry, negative n[i], src[i] == dst[i]. */
+int vpd_ema_update(const float* const* src, float* const* dst, const long long* n, int count, double decay, int warmup, int t,
+                   int t0, const vpd_scale_state* state, void* stream);
+
 /* Lazy gradients for the fused train step (reference: models/util.py:50-58, where nothing looks at .grad between
  * loss.backward() and optimizer.step()).  vpd_plan_set_lazy_grads(plan, 1) arms the NEXT vpd_backward: the conv weight
  * gradients then stay in the kernels' own fp32 scratch layout and vpd_plan_adamw_step reads them there, so the layout pass

@@ -50,12 +50,22 @@ def get_args():
                         help='(this build, --dtype fp16 only) static: a fixed loss scale of 256 (default); dynamic: the reference\'s '
                              'GradScaler() -- steps with inf / NaN gradients are skipped and the scale halved, doubled after 2000 '
                              'clean steps -- decided on the device (vpd_amd.models.util.DynamicLossScaler)')
+    parser.add_argument('--ema_decay', type=float,
+                        help='(this build) keep an exponential moving average of the weights with this decay: every epoch also '
+                             'validates the averaged weights (val_ema in loss.json), best_epoch_ema.* is chosen by the moving '
+                             'average of val_ema, and every checkpoint is written a second time as <name>_ema.*')
+    parser.add_argument('--ema_warmup', action='store_true',
+                        help='(this build, with --ema_decay) decay = min(ema_decay, (1 + t) / (10 + t)) after t updates')
     parser.add_argument('--no_augment', action='store_true',
                         help='escape hatch: fp32 batches from the CPU loaders with h-flips only -- NOT the reference '
                              'recipe, whose datasets always augment (vpd_dataset/common.py:85-92)')
     args = parser.parse_args()
     if args.loss_scale == 'dynamic' and args.dtype != 'fp16':
         parser.error('--loss_scale dynamic needs --dtype fp16 (bf16 trains without a loss scale)')
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
+        parser.error('--ema_decay must be in [0, 1]')
+    if args.ema_warmup and args.ema_decay is None:
+        parser.error('--ema_warmup needs --ema_decay')
     return args
 
 
@@ -78,7 +88,8 @@ def load_dataset(dataset, dataset_kwargs, emb_dir, penn_dir, no_test_video):
 
 def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, motion, encoder_arch, save_dir,
          model_select_window, checkpoint_frequency, pretrained, emb_dir, penn_dir, no_test_video, min_pose_score,
-         synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static'):
+         synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static', ema_decay=None,
+         ema_warmup=False):
     device = 'cuda'
     # The reference builds train AND val datasets with augment=True (vpd_dataset/single_frame.py:267-272,
     # common.py:85-92): ColorJitter, mask noise, RandomResizedCrop and flips are part of the recipe, so they are the
@@ -149,7 +160,7 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
     if gpu_augment:
         from vpd_amd.augment import CropAugmenter
         augmenter = CropAugmenter(encoder.device, rgb_mean_std, img_dim, flow_img is not None)
-    trainer = ModelTrainer(encoder, motion, augmenter=augmenter, augment=True)
+    trainer = ModelTrainer(encoder, motion, augmenter=augmenter, augment=True, ema_decay=ema_decay, ema_warmup=ema_warmup)
     if world > 1:      # same initial weights on every rank (after the trainer: the motion head is initialised there)
         torch.distributed.broadcast(encoder.engine.params, 0)
         torch.distributed.broadcast(encoder.engine.bn_running, 0)
@@ -158,7 +169,9 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
     dynamic = loss_scale == 'dynamic'
     skipped_before = 0
 
+    ema = ema_decay is not None
     if rank == 0:
+        config_ema = {} if not ema else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}      # (keys only with --ema_decay)
         store_json(os.path.join(save_dir, 'config.json'), {
             'num_epochs': num_epochs, 'batch_size': batch_size, 'learning_rate': learning_rate, 'img_dim': img_dim,
             'use_flow': flow_img is not None, 'motion': motion,
@@ -168,11 +181,12 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
             'loss_scale': loss_scale if dtype == 'fp16' else None,      # fp16: static (256) | dynamic (GradScaler's rule)
             # not in the reference: which input pipeline produced the loss curves
             'augment': 'device: ColorJitter + mask noise + RandomResizedCrop + flip (reference recipe)' if gpu_augment
-                       else 'cpu: h-flip only (--no_augment)'})
+                       else 'cpu: h-flip only (--no_augment)', **config_ema})
 
     loss_file = os.path.join(save_dir, 'loss.json')
     losses = []
     best_val_loss = float('inf')
+    best_val_ema_loss = float('inf')
     for epoch in range(1, num_epochs + 1):
         train_loss = trainer.epoch(train_loader, optimizer=optimizer, scaler=scaler)
         if world > 1 and os.environ.get('VPD_DDP_AVG_BN', '0') == '1':      # per-rank BatchNorm statistics -> their mean over ranks
@@ -181,25 +195,40 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         val_loss = trainer.epoch(val_loader)
         losses.append({'epoch': epoch, 'train': train_loss, 'val': val_loss,
                        'dataset_train': [(dataset, train_loss)], 'dataset_val': [(dataset, val_loss)]})
+        if ema:      # the same validation pass with the averaged weights
+            with trainer.ema_weights():
+                losses[-1]['val_ema'] = trainer.epoch(val_loader)
+            moving_avg_val_ema_loss = get_moving_avg_loss(losses, model_select_window, 'val_ema')
         moving_avg_val_loss = get_moving_avg_loss(losses, model_select_window, 'val')
         if rank == 0:
             print('Epoch {} - train loss: {:0.4f} [avg: {:0.4f}] val loss: {:0.4f} [avg: {:0.4f}]'.format(
                 epoch, train_loss, get_moving_avg_loss(losses, model_select_window, 'train'), val_loss,
                 moving_avg_val_loss) + ('' if not dynamic else ' loss scale: {:g} skipped steps: {}'.format(
                     scaler.get_scale(), scaler.skipped_steps - skipped_before)))
+            if ema:
+                print('  averaged weights - val loss: {:0.4f} [avg: {:0.4f}]'.format(losses[-1]['val_ema'], moving_avg_val_ema_loss))
             store_json(loss_file, losses)
             if moving_avg_val_loss < best_val_loss:
                 print('New best epoch!')
                 trainer.save_model(save_dir, 'best_epoch')
+            if ema and moving_avg_val_ema_loss < best_val_ema_loss:
+                print('New best epoch of the averaged weights!')
+                trainer.save_model(save_dir, 'best_epoch', ema=True)
             if checkpoint_frequency is not None and epoch % checkpoint_frequency == 0:
                 print('Saving checkpoint: {}'.format(epoch))
                 trainer.save_model(save_dir, 'epoch{:04d}'.format(epoch))
+                if ema:
+                    trainer.save_model(save_dir, 'epoch{:04d}'.format(epoch), ema=True)
         if dynamic:
             skipped_before = scaler.skipped_steps
         best_val_loss = min(moving_avg_val_loss, best_val_loss)
+        if ema:
+            best_val_ema_loss = min(moving_avg_val_ema_loss, best_val_ema_loss)
     if rank == 0:
         print('Saving last epoch: {}'.format(epoch))
         trainer.save_model(save_dir, 'epoch{:04d}'.format(epoch))
+        if ema:
+            trainer.save_model(save_dir, 'epoch{:04d}'.format(epoch), ema=True)
         print('Done!')
     if world > 1:
         # replicas must hold identical weights (same initial broadcast, same summed gradients, same AdamW): verify

@@ -322,6 +322,17 @@ hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, h
 hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float backoff, int interval, hipStream_t s);
 hipError_t vpd_launch_scale_by_state(float* x, long n, const vpd_scale_state* st, hipStream_t stream);
 
+// exponential moving average of the weights (vpd_ema_update): float ranges of any alignment and length, passed by value
+#define EMA_MAX 4
+struct EmaRanges {
+    const float* src[EMA_MAX];
+    float* dst[EMA_MAX];
+    long n[EMA_MAX];
+    int count;
+};
+hipError_t vpd_launch_ema_update(const EmaRanges& r, double decay, int warmup, int t, int t0, const vpd_scale_state* st,
+                                 hipStream_t s);
+
 #define ZR_MAX 16
 struct ZeroRanges {                     // 16-byte aligned ranges, lengths in float4
     float* ptr[ZR_MAX];

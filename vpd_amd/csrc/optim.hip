@@ -506,6 +506,86 @@ hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float back
     return hipGetLastError();
 }
 
+// ---- exponential moving average of the weights (vpd_ema_update): dst += (1 - d) * (src - dst) over up to EMA_MAX ranges, one launch ----
+// Streaming: 4 bytes read twice and written once per element, nothing reused.  A range is split like check_finite_kernel's by the
+// alignment of `dst`: up to three floats in front, the 16-byte aligned middle -- 16 KB tiles with four 16-byte loads of each operand
+// in flight per thread, then what is left of it one float4 per thread -- and up to three floats behind.  When `src` does not share dst's 16-byte phase its middle is read float by float.
+// st != null (a DynamicLossScaler's step in flight): nothing is written when the non-finite word is set -- the AdamW before this
+// launch wrote nothing either -- and t, the number of updates so far, is the applied-step count minus its value at enable time.
+static __device__ __forceinline__ float ema1(float s, float d, float omd) {
+#pragma clang fp contract(off)
+    return fmaf(omd, s - d, d);
+}
+static __device__ __forceinline__ f32x4 ema4(const f32x4& s, const f32x4& d, float omd) {
+    return f32x4{ema1(s.x, d.x, omd), ema1(s.y, d.y, omd), ema1(s.z, d.z, omd), ema1(s.w, d.w, omd)};
+}
+// (at most 64 registers: the capped grid of 2048 blocks = 8 waves per SIMD is resident at once)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void ema_update_kernel(const EmaRanges r, double decay, int warmup, int t, int t0,
+                                                         const vpd_scale_state* st) {
+    if (st) {
+        if (st->found != 0u) return;
+        t = st->applied_steps - t0;
+        if (t < 0) t = 0;
+    }
+    double d = decay;
+    if (warmup) {      // timm's rule: min(decay, (1 + t) / (10 + t))
+        const double w = (1.0 + (double)t) / (10.0 + (double)t);
+        d = w < d ? w : d;
+    }
+    const float omd = (float)(1.0 - d);
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nth = (long)gridDim.x * 256;
+    for (int k = 0; k < r.count; ++k) {
+        const float* x = r.src[k];
+        float* y = r.dst[k];
+        const long n = r.n[k];
+        long head = (long)((16 - (reinterpret_cast<size_t>(y) & 15)) & 15) >> 2;
+        if (head > n) head = n;
+        const long n4 = (n - head) >> 2;
+        f32x4* y4 = reinterpret_cast<f32x4*>(y + head);
+        long i = tid;
+        if ((reinterpret_cast<size_t>(x + head) & 15) == 0) {
+            const f32x4* x4 = reinterpret_cast<const f32x4*>(x + head);
+            // tiles of 1024 float4 (16 KB) per block: a wave takes four consecutive 1 KB rows of each operand -- one address per
+            // operand, the rows behind it by the instruction's offset field
+            const long ntile = n4 >> 10;
+            for (long tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
+                const long e = (tl << 10) + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
+                const f32x4* xp = x4 + e;
+                f32x4* yp = y4 + e;
+                f32x4 sa = xp[0], sb = xp[64], sc = xp[128], sd = xp[192];
+                f32x4 da = yp[0], db = yp[64], dc = yp[128], dd = yp[192];
+                // every loaded value passes through one opaque point: all eight loads are issued before the first is consumed
+                // (left alone, hipcc sinks each pair of loads to its use and waits for it there: two in flight per thread)
+                asm volatile("" : "+v"(sa), "+v"(sb), "+v"(sc), "+v"(sd), "+v"(da), "+v"(db), "+v"(dc), "+v"(dd));
+                yp[0] = ema4(sa, da, omd);
+                yp[64] = ema4(sb, db, omd);
+                yp[128] = ema4(sc, dc, omd);
+                yp[192] = ema4(sd, dd, omd);
+            }
+            for (i += ntile << 10; i < n4; i += nth) y4[i] = ema4(x4[i], y4[i], omd);
+        } else {
+            const float* xs = x + head;
+            for (; i < n4; i += nth) {
+                const f32x4 s = {xs[4 * i], xs[4 * i + 1], xs[4 * i + 2], xs[4 * i + 3]};
+                y4[i] = ema4(s, y4[i], omd);
+            }
+        }
+        const long tail = head + (n4 << 2);
+        if (tid < head) y[tid] = ema1(x[tid], y[tid], omd);
+        if (tid < n - tail) y[tail + tid] = ema1(x[tail + tid], y[tail + tid], omd);
+    }
+}
+hipError_t vpd_launch_ema_update(const EmaRanges& r, double decay, int warmup, int t, int t0, const vpd_scale_state* st,
+                                 hipStream_t s) {
+    long total = 0;
+    for (int k = 0; k < r.count; ++k) total += r.n[k] > 0 ? r.n[k] : 0;
+    if (r.count <= 0 || total == 0) return hipSuccess;
+    long gsz = (total / 4 + 255) / 256;      // capped like check_finite_kernel's grid: 2048 blocks = 8 per CU
+    if (gsz > 2048) gsz = 2048;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, r, decay, warmup, t, t0, st);
+    return hipGetLastError();
+}
+
 // Zero up to ZR_MAX float ranges in ONE launch (accumulator rows of the BN statistics + the fp32 weight-gradient
 // ranges the atomics kernel adds into): hipMemsetAsync costs 5-12 us per call on this runtime.
 __global__ __launch_bounds__(256) void zero_ranges_kernel(const ZeroRanges z) {

@@ -749,6 +749,32 @@ extern "C" int vpd_scale_state_update(vpd_scale_state* state, float growth, floa
     return 0;
 }
 
+// Exponential moving average of the weights: every refusal is taken here, before anything is launched
+extern "C" int vpd_ema_update(const float* const* src, float* const* dst, const long long* n, int count, double decay,
+                              int warmup, int t, int t0, const vpd_scale_state* state, void* stream) {
+    if (count < 0 || count > EMA_MAX) return fail("vpd_ema_update: count outside 0..4");
+    if (!(decay >= 0.0 && decay <= 1.0)) return fail("vpd_ema_update: decay must be in [0, 1]");
+    if (t < 0 || t0 < 0) return fail("vpd_ema_update: t and t0 must not be negative");
+    if (reinterpret_cast<size_t>(state) & 3) return fail("vpd_ema_update: scale state must be 4-byte aligned");
+    if (count == 0) return 0;
+    if (!src || !dst || !n) return fail("vpd_ema_update: null argument");
+    EmaRanges r;
+    memset(&r, 0, sizeof r);
+    for (int i = 0; i < count; ++i) {
+        if (!src[i] || !dst[i]) return fail("vpd_ema_update: null argument");
+        if (n[i] < 0) return fail("vpd_ema_update: negative length");
+        if ((reinterpret_cast<size_t>(src[i]) | reinterpret_cast<size_t>(dst[i])) & 3)
+            return fail("vpd_ema_update: src and dst must be 4-byte aligned");
+        if (src[i] == dst[i]) return fail("vpd_ema_update: src and dst must differ");
+        r.src[i] = src[i];
+        r.dst[i] = dst[i];
+        r.n[i] = (long)n[i];
+    }
+    r.count = count;
+    LCHECK(vpd_launch_ema_update(r, decay, warmup != 0, t, t0, state, (hipStream_t)stream));
+    return 0;
+}
+
 extern "C" int vpd_plan_set_lazy_grads(vpd_plan_t* p, int on) {
     if (!p) return fail("null plan");
     p->lazy_next = on != 0;

@@ -199,6 +199,14 @@ class StudentEngine:
         self._grads2 = None            # second flat buffer an accumulating backward writes before it is added (first use)
         self.stem_dgrad_launches = 0   # input gradients asked for (conv_stem_dgrad_kernel launches)
         self.bn_frozen = False         # freeze_bn(): train-mode forwards normalise with the running statistics and leave them alone
+        # enable_ema(): exponential moving average of `params` / `bn_running`, updated by one kernel at the end of adamw_step
+        self.ema_params = None
+        self.ema_bn_running = None
+        self._ema = None               # (decay, warmup)
+        self._ema_t = 0                # updates enqueued without a scaler's block (there the device counts: applied steps - _ema_t0)
+        self._ema_t0 = 0               # adam_step when averaging began
+        self._ema_version = 0          # bumped by every update: plans packed from the EMA buffers repack
+        self._use_ema = False          # use_ema(): eval forwards read the EMA buffers
 
     # -- helpers -------------------------------------------------------------
     @property
@@ -259,7 +267,67 @@ class StudentEngine:
         return self.bn_running[rm:rm + c], self.bn_running[rv:rv + c]
 
     def weights_version(self):
-        return (self.params._version, self.bn_running._version, self._hip_version)
+        """What a plan's packed weights were made from: the live buffers' versions, and -- while use_ema() is on -- the source flag
+        and the EMA buffers' version (0 otherwise: an EMA update does not make the packed LIVE weights stale)."""
+        return (self.params._version, self.bn_running._version, self._hip_version, self._use_ema,
+                self._ema_version if self._use_ema else 0)
+
+    # -- exponential moving average of the weights ---------------------------------
+    def enable_ema(self, decay, warmup=False):
+        """Keep an exponential moving average of the parameters and of the BatchNorm running statistics (timm's ModelEmaV2 averages
+        buffers too; num_batches_tracked stays the live one): ema += (1 - d) * (live - ema) after every applied optimizer step,
+        d = decay, or min(decay, (1 + t) / (10 + t)) with warmup, t = updates so far.  `ema_params` / `ema_bn_running` start as
+        copies of the live buffers.  adamw_step() then ends with ONE more launch (vpd_ema_update) over both buffers; under a
+        DynamicLossScaler it reads the scaler's block, so a skipped step leaves the average alone and costs no synchronisation."""
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError("ema decay must be in [0, 1], not %r" % (decay,))
+        if not hasattr(self.L, "vpd_ema_update"):      # (absent only in an older A/B library)
+            raise RuntimeError("this libvpdhip has no vpd_ema_update")
+        self.ema_params = self.params.clone()
+        self.ema_bn_running = self.bn_running.clone()
+        self._ema = (decay, bool(warmup))
+        self._ema_t = 0
+        self._ema_t0 = int(self.adam_step)      # (read once; synchronises when a DynamicLossScaler is attached)
+        self._ema_version += 1
+
+    def disable_ema(self):
+        """Stop averaging (adamw_step launches what it launched before enable_ema); the buffers keep their values."""
+        self._ema = None
+        self._use_ema = False
+
+    @property
+    def ema_enabled(self):
+        return self._ema is not None
+
+    def _ema_enqueue(self, state):
+        decay, warmup = self._ema
+        src = (C.c_void_p * 2)(self.params.data_ptr(), self.bn_running.data_ptr())
+        dst = (C.c_void_p * 2)(self.ema_params.data_ptr(), self.ema_bn_running.data_ptr())
+        n = (C.c_longlong * 2)(self.param_numel, self.bn_numel)
+        self.check(self.L.vpd_ema_update(src, dst, n, 2, decay, int(warmup), 0 if state is not None else self._ema_t,
+                                         self._ema_t0, _ptr(state), self._stream()), "vpd_ema_update")
+        if state is None:
+            self._ema_t += 1
+        self._ema_version += 1
+
+    def ema_update(self):
+        """One update of the average from the live buffers as they stand: the manual call for a torch optimizer on the autograd
+        path, where the host knows whether it stepped (adamw_step() calls it by itself)."""
+        if self._ema is None:
+            raise RuntimeError("ema_update() before enable_ema()")
+        self._ema_enqueue(None)
+
+    def use_ema(self, on=True):
+        """Eval forwards compute with the averaged weights while on (every plan repacks when the source changes, and only then);
+        train-mode forwards refuse to run until it is off again.  The live buffers are not touched."""
+        if on and self._ema is None:
+            raise RuntimeError("use_ema() before enable_ema()")
+        self._use_ema = bool(on)
+
+    def _source(self):
+        """(params, bn_running) the eval forwards read"""
+        return (self.ema_params, self.ema_bn_running) if self._use_ema else (self.params, self.bn_running)
 
     def mark_weights_changed(self):
         """Call after writing `params` / `bn_running` by a path torch's version counters do not see (a collective, a
@@ -284,7 +352,8 @@ class StudentEngine:
         v = self.weights_version()
         if pl.packed_version != v:
             # the eval-mode BN fold is only needed by eval plans
-            self.check(self.L.vpd_pack_weights(pl.handle, _ptr(self.params), None if pl.train else _ptr(self.bn_running),
+            params, bn_running = self._source()
+            self.check(self.L.vpd_pack_weights(pl.handle, _ptr(params), None if pl.train else _ptr(bn_running),
                                          _ptr(pl.workspace), self._stream()), "vpd_pack_weights")
             pl.packed_version = v
 
@@ -317,7 +386,7 @@ class StudentEngine:
         pl = self.plan(h, w, n, False, motion)
         self._ensure_packed(pl)
         emb = out if out is not None else torch.empty((n, self.emb_dim), dtype=torch.float32, device=self.device)
-        self.check(self.L.vpd_forward_eval(pl.handle, _ptr(self.params), _ptr(x), n, _ptr(emb), _ptr(target),
+        self.check(self.L.vpd_forward_eval(pl.handle, _ptr(self._source()[0]), _ptr(x), n, _ptr(emb), _ptr(target),
                                      _ptr(self.loss_step) if target is not None else None,
                                      _ptr(self.loss_accum) if (target is not None and accumulate_loss) else None,
                                      _ptr(pl.workspace), self._stream()), "vpd_forward_eval")
@@ -365,6 +434,9 @@ class StudentEngine:
         else:
             self._check_input(x, self.c_in)
             n, _, h, w = x.shape
+        if self._use_ema:
+            raise RuntimeError("train-mode forward while use_ema() is on: the averaged weights are for evaluation; "
+                               "call use_ema(False) (or leave ModelTrainer.ema_weights()) first")
         pl = self.plan(h, w, n, True, motion)
         self._ensure_packed(pl)
         emb = torch.empty((n, self.emb_dim), dtype=torch.float32, device=self.device)
@@ -381,7 +453,7 @@ class StudentEngine:
         if not frozen:      # (a frozen forward read the running statistics and left them: nothing is stale, nothing was tracked)
             # BN running stats were rewritten by HIP kernels: packed eval scale/shift are stale
             self._hip_version += 1
-            pl.packed_version = (self.params._version, self.bn_running._version, self._hip_version)
+            pl.packed_version = self.weights_version()
             if n > 0:
                 self._nbt_pending += 1
         self._last = (pl, n) if target is not None else None
@@ -533,10 +605,14 @@ class StudentEngine:
                                        numel, lr, betas[0], betas[1], eps, weight_decay, self.adam_step,
                                        self._stream()), "vpd_adamw_step")
             self._hip_version += 1
+        if self._ema is not None:
+            # after the AdamW, before the scaler's update(): `found` and `applied_steps` are still those of this step
+            self._ema_enqueue(st)
 
     def capture_eval_graph(self, x, out):
         """hipGraph of the eval forward for this batch size, bound to x / out (capture needs a
         non-default stream; the graph itself is launched on the current stream)."""
+        self._no_graph_under_ema()
         self._check_input(x, self.c_in)
         n, _, h, w = x.shape
         pl = self.plan(h, w, n, False, False)
@@ -552,6 +628,7 @@ class StudentEngine:
     def capture_eval_graph_staged(self, n, img_dim, out):
         """hipGraph of the eval forward for n crops whose input is ALREADY in the plan's stem staging buffer (stage_crops /
         CropAugmenter.stage_views): the graph starts at the stem convolution."""
+        self._no_graph_under_ema()
         pl = self.plan(img_dim, img_dim, n, False, False)
         self._ensure_packed(pl)
         side = torch.cuda.Stream(device=self.device)
@@ -561,6 +638,11 @@ class StudentEngine:
         torch.cuda.current_stream(self.device).wait_stream(side)
         pl.graph_sizes.add(n)
         return pl
+
+    def _no_graph_under_ema(self):
+        if self._use_ema:
+            raise RuntimeError("eval graphs are bound to the live parameter buffer: not available while use_ema() is on "
+                               "(load ema_state_dict() into a student of its own to serve the averaged weights)")
 
     def sync_errors(self):
         """Grid-barrier time-outs counted by the train plans since their workspaces were initialised (host sync).
@@ -589,5 +671,6 @@ class StudentEngine:
         return {names[i]: dict(launches=out[3 * i], ms=out[3 * i + 1], flops=out[3 * i + 2]) for i in range(8)}
 
     def launch_eval_graph(self, pl, n):
+        self._no_graph_under_ema()
         self._ensure_packed(pl)
         self.check(self.L.vpd_graph_launch_eval(pl.handle, n, self._stream()), "vpd_graph_launch_eval")

@@ -47,6 +47,16 @@ class FCNet(nn.Module):
             self.get_parameter(k).grad = engine.view("decoder." + k, engine.grads)
         self.reset_parameters()
 
+    def ema_state_dict(self):
+        """state_dict() with the values of the engine's exponential moving average (StudentEngine.enable_ema), as copies"""
+        eng = self._engine[0]
+        if not eng.ema_enabled:
+            raise RuntimeError("ema_state_dict() before enable_ema()")
+        out = self.state_dict()
+        for k in DECODER_PARAM_NAMES:
+            out[k] = eng.view("decoder." + k, eng.ema_params).clone()
+        return out
+
     def reset_parameters(self):
         # torch nn.Linear default: kaiming_uniform(a=sqrt(5)) == U(+-1/sqrt(fan_in)) for W and b
         with torch.no_grad():

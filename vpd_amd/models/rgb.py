@@ -185,6 +185,23 @@ class RGBF_EmbeddingModel(nn.Module):
         _ = self.engine.num_batches_tracked
         return super().state_dict(*args, **kwargs)
 
+    def ema_state_dict(self):
+        """state_dict() with the values of the engine's exponential moving average (StudentEngine.enable_ema): same keys, order,
+        shapes and dtypes -- a checkpoint the reference's own module loads -- parameters and BatchNorm running statistics from
+        the averaged buffers (copies), num_batches_tracked the live one."""
+        eng = self.engine
+        if not eng.ema_enabled:
+            raise RuntimeError("ema_state_dict() before enable_ema()")
+        out = self.state_dict()
+        for k in eng.enc_names:
+            out[k] = eng.view(k, eng.ema_params).clone()
+        for bn in eng.bn_names:
+            c, rm, rv = eng.bn_layout[bn]
+            out[bn + ".running_mean"] = eng.ema_bn_running[rm:rm + c].clone()
+            out[bn + ".running_var"] = eng.ema_bn_running[rv:rv + c].clone()
+            out[bn + ".num_batches_tracked"] = out[bn + ".num_batches_tracked"].clone()
+        return out
+
     def load_state_dict(self, *args, **kwargs):
         _ = self.engine.num_batches_tracked      # fold pending counts in before the buffers are overwritten
         return super().load_state_dict(*args, **kwargs)

@@ -1,6 +1,7 @@
 """ModelTrainer: the reference's training driver (train_vpd_model.py:53-112)
 on the HIP engine.  Same methods, same epoch() return value (sum of per-batch
 sum-MSE / number of crops), same checkpoint files."""
+import contextlib
 import os
 
 import torch
@@ -62,8 +63,14 @@ class FusedAdamW(torch.optim.Optimizer):
 class ModelTrainer:
     """Class for training the encoder. Discarded after training"""
 
-    def __init__(self, encoder, motion, process_group=None, augmenter=None, augment=True):
-        """augmenter: a vpd_amd.augment.CropAugmenter -> epoch() also accepts RAW batches
+    def __init__(self, encoder, motion, process_group=None, augmenter=None, augment=True, ema_decay=None, ema_warmup=False):
+        """ema_decay: keep an exponential moving average of the weights (and of the BatchNorm running statistics) with this
+        decay; ema_warmup: timm's rule min(decay, (1 + t) / (10 + t)).  Averaging starts in get_optimizer() -- from the weights as
+        they stand then, i.e. after a checkpoint was loaded -- and every fused optimizer step ends with one more launch
+        (StudentEngine.enable_ema).  ema_weights() evaluates with the average, save_model(..., ema=True) writes it.  Under data
+        parallelism every rank averages its own (identical) parameters: no collective is added.
+
+        augmenter: a vpd_amd.augment.CropAugmenter -> epoch() also accepts RAW batches
         {'rgb_u8': u8[B,H,W,3], 'flow_u8': u8[B,H,W,2], 'mask_u8': u8[B,H,W] (optional), 'flip': int[B] (optional,
         decided by the dataset because it selects the teacher row), 'emb'} and runs the reference's per-item
         transforms (vpd_dataset/single_frame.py:168-206) on the device, straight into the stem's staging buffer."""
@@ -71,6 +78,10 @@ class ModelTrainer:
         self.augmenter, self.augment = augmenter, bool(augment)
         self.encoder = encoder.to(device)
         self.motion = bool(motion)
+        if ema_decay is not None and not 0.0 <= float(ema_decay) <= 1.0:
+            raise ValueError("ema_decay must be in [0, 1], not %r" % (ema_decay,))
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
         if motion:
             self.fcn_time = FCNet(encoder.engine, encoder.emb_dim, [128, 128], 2 * encoder.emb_dim, dropout=0)
         self._reducer = None
@@ -186,6 +197,8 @@ class ModelTrainer:
         # bf16 operands with fp32 accumulation need no GradScaler: scaler None.  A student built with dtype="fp16" gets the static
         # LossScaler (the reference: GradScaler() on 'cuda', train_vpd_model.py:104-105)
         eng = self.encoder.engine
+        if self.ema_decay is not None and not eng.ema_enabled:
+            eng.enable_ema(self.ema_decay, self.ema_warmup)      # (before a DynamicLossScaler takes the step count to the device)
         if loss_scale is None:
             scaler = LossScaler(eng) if eng.dtype == "fp16" else None
         elif eng.dtype != "fp16":
@@ -199,9 +212,23 @@ class ModelTrainer:
             scaler = LossScaler(eng, float(loss_scale))
         return FusedAdamW(params, eng, lr=learning_rate), scaler
 
-    def save_model(self, save_dir, name):
-        torch.save(self.encoder.state_dict(),
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context every eval forward (embed(), epoch() without an optimizer) computes with the averaged weights; the
+        live ones are back on exit, untouched.  Train-mode forwards refuse to run inside."""
+        eng = self.encoder.engine
+        eng.use_ema(True)
+        try:
+            yield self
+        finally:
+            eng.use_ema(False)
+
+    def save_model(self, save_dir, name, ema=False):
+        """ema: write the averaged weights instead, as <name>_ema.encoder.pt / <name>_ema.decoder.pt -- ordinary state_dicts"""
+        if ema:
+            name = '{}_ema'.format(name)
+        torch.save(self.encoder.ema_state_dict() if ema else self.encoder.state_dict(),
                    os.path.join(save_dir, '{}.encoder.pt'.format(name)))
         if hasattr(self, 'fcn_time'):
-            torch.save(self.fcn_time.state_dict(),
+            torch.save(self.fcn_time.ema_state_dict() if ema else self.fcn_time.state_dict(),
                        os.path.join(save_dir, '{}.decoder.pt'.format(name)))
