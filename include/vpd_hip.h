@@ -204,6 +204,47 @@ int vpd_scale_state_update(vpd_scale_state* state, float growth, float backoff, 
 int vpd_ema_update(const float* const* src, float* const* dst, const long long* n, int count, double decay, int warmup, int t,
                    int t0, const vpd_scale_state* state, void* stream);
 
+/* ---- gradient-norm clipping, decided on the device ----
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) between backward() and optimizer.step(), for the fused step, where the conv
+ * weight gradients never reach .grad: ONE pass over the gradients the optimizer step is about to read takes their sum of squares
+ * (every element widened to double; fixed-order reductions, no atomics: the same input gives the same bits on every launch and on
+ * every data-parallel rank), and a one-block kernel writes the caller's DEVICE block below (16-byte aligned, vpd_clip_state_bytes()
+ * bytes -- the struct and the pass's partial sums behind it; zero it once):
+ *   norm = sqrt(sum) / scale            scale: src->scale, or host_scale when src is NULL (1 without a loss scale)
+ *   coef = min(1, max_norm / (norm + 1e-6))                                  (torch's formula, clamped as torch clamps)
+ *   eff.scale = scale / coef            eff.found = (src ? src->found : 0) | (sum is inf or NaN)
+ * all in double, each stored value rounded to float once.  The step is then vpd_plan_adamw_step_scaled / vpd_adamw_step_scaled
+ * (and vpd_ema_update) called with &clip->eff: gradients x 1 / eff.scale = coef / scale.
+ * With src (a dynamic loss scaler's step in flight) eff.applied_steps is copied from it and a non-finite sum is OR-ed into src->found
+ * as the non-finite search would have done -- the search need not run: a sum of squares is non-finite exactly when an element is.
+ * Without src the block counts its own steps: eff.applied_steps is left alone; advance it with
+ * vpd_scale_state_update(&clip->eff, 1, 1, INT_MAX) after the step.  A non-finite norm without a dynamic scaler therefore SKIPS the
+ * step (parameters, moments, packed weights, EMA untouched) and counts it -- torch would write NaN into every weight. */
+typedef struct vpd_clip_state {
+    vpd_scale_state eff;         /* what this step's AdamW and EMA read */
+    float total_norm;            /* the last step's un-scaled gradient norm */
+    float norm_max;              /* running maximum of the finite norms (reset by writing 0) */
+    float coef;                  /* the last step's clip coefficient (1 when the norm was not finite) */
+    int clipped_steps;           /* steps with coef < 1 */
+    int nonfinite_steps;         /* steps whose norm was inf or NaN */
+    int reserved[3];
+} vpd_clip_state;
+size_t vpd_clip_state_bytes(void);
+
+/* The norm pass over `count` plain DEVICE float ranges x[i][0 .. n[i]) of any 4-byte alignment and any length >= 0 (x and n are
+ * HOST arrays; more than 96 ranges take more than one launch), then the one-block kernel.  max_norm = +inf measures only.
+ * Refused on the host, nothing launched: null clip, null x / n with count > 0, a null entry, negative n[i] or count, clip not
+ * 16-byte aligned, src or an entry not 4-byte aligned, max_norm not > 0 or NaN, host_scale not positive and finite when src is
+ * NULL. */
+int vpd_op_grad_norm(const float* const* x, const long long* n, int count, double max_norm, const vpd_scale_state* src,
+                     float host_scale, vpd_clip_state* clip, void* stream);
+/* The same over exactly the ranges vpd_plan_check_grads enumerates (the plan's scratch and the non-conv ranges of `grads` while
+ * vpd_plan_grads_pending(), else grads[0 .. numel)).  Floats of `grads` between tensors must be zero (they are in a buffer that was
+ * zeroed once: no pass writes them).  Also refused: null plan / grads / workspace, an unbound workspace, numel not a multiple of 4
+ * or below the plan's, grads not 16-byte aligned. */
+int vpd_plan_grad_norm(vpd_plan_t* plan, const float* grads, long long numel, double max_norm, vpd_scale_state* src,
+                       float host_scale, vpd_clip_state* clip, void* workspace, void* stream);
+
 /* Lazy gradients for the fused train step (reference: models/util.py:50-58, where nothing looks at .grad between
  * loss.backward() and optimizer.step()).  vpd_plan_set_lazy_grads(plan, 1) arms the NEXT vpd_backward: the conv weight
  * gradients then stay in the kernels' own fp32 scratch layout and vpd_plan_adamw_step reads them there, so the layout pass

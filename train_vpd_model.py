@@ -56,6 +56,9 @@ def get_args():
                              'average of val_ema, and every checkpoint is written a second time as <name>_ema.*')
     parser.add_argument('--ema_warmup', action='store_true',
                         help='(this build, with --ema_decay) decay = min(ema_decay, (1 + t) / (10 + t)) after t updates')
+    parser.add_argument('--clip_grad_norm', type=float,
+                        help='(this build) torch.nn.utils.clip_grad_norm_ with this max_norm before every optimizer step, decided '
+                             'on the device; every epoch prints grad_norm_max and clipped_steps and adds them to loss.json')
     parser.add_argument('--no_augment', action='store_true',
                         help='escape hatch: fp32 batches from the CPU loaders with h-flips only -- NOT the reference '
                              'recipe, whose datasets always augment (vpd_dataset/common.py:85-92)')
@@ -64,6 +67,8 @@ def get_args():
         parser.error('--loss_scale dynamic needs --dtype fp16 (bf16 trains without a loss scale)')
     if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
         parser.error('--ema_decay must be in [0, 1]')
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0.0:
+        parser.error('--clip_grad_norm must be > 0')
     if args.ema_warmup and args.ema_decay is None:
         parser.error('--ema_warmup needs --ema_decay')
     return args
@@ -89,7 +94,7 @@ def load_dataset(dataset, dataset_kwargs, emb_dir, penn_dir, no_test_video):
 def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, motion, encoder_arch, save_dir,
          model_select_window, checkpoint_frequency, pretrained, emb_dir, penn_dir, no_test_video, min_pose_score,
          synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static', ema_decay=None,
-         ema_warmup=False):
+         ema_warmup=False, clip_grad_norm=None):
     device = 'cuda'
     # The reference builds train AND val datasets with augment=True (vpd_dataset/single_frame.py:267-272,
     # common.py:85-92): ColorJitter, mask noise, RandomResizedCrop and flips are part of the recipe, so they are the
@@ -165,13 +170,18 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         torch.distributed.broadcast(encoder.engine.params, 0)
         torch.distributed.broadcast(encoder.engine.bn_running, 0)
         encoder.engine.mark_weights_changed()
-    optimizer, scaler = trainer.get_optimizer(learning_rate, loss_scale='dynamic' if loss_scale == 'dynamic' else None)
+    optimizer, scaler = trainer.get_optimizer(learning_rate, loss_scale='dynamic' if loss_scale == 'dynamic' else None,
+                                              max_grad_norm=clip_grad_norm)
     dynamic = loss_scale == 'dynamic'
     skipped_before = 0
+    clip = clip_grad_norm is not None
+    clipped_before = 0
 
     ema = ema_decay is not None
     if rank == 0:
         config_ema = {} if not ema else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}      # (keys only with --ema_decay)
+        if clip:
+            config_ema['clip_grad_norm'] = clip_grad_norm      # (key only with --clip_grad_norm)
         store_json(os.path.join(save_dir, 'config.json'), {
             'num_epochs': num_epochs, 'batch_size': batch_size, 'learning_rate': learning_rate, 'img_dim': img_dim,
             'use_flow': flow_img is not None, 'motion': motion,
@@ -195,6 +205,11 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         val_loss = trainer.epoch(val_loader)
         losses.append({'epoch': epoch, 'train': train_loss, 'val': val_loss,
                        'dataset_train': [(dataset, train_loss)], 'dataset_val': [(dataset, val_loss)]})
+        if clip:      # (keys only with --clip_grad_norm; norm_max starts again at 0 for the next epoch)
+            stats = optimizer.clip_stats(reset_max=True)
+            losses[-1]['grad_norm_max'] = stats['norm_max']
+            losses[-1]['clipped_steps'] = stats['clipped_steps'] - clipped_before
+            clipped_before = stats['clipped_steps']
         if ema:      # the same validation pass with the averaged weights
             with trainer.ema_weights():
                 losses[-1]['val_ema'] = trainer.epoch(val_loader)
@@ -204,7 +219,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
             print('Epoch {} - train loss: {:0.4f} [avg: {:0.4f}] val loss: {:0.4f} [avg: {:0.4f}]'.format(
                 epoch, train_loss, get_moving_avg_loss(losses, model_select_window, 'train'), val_loss,
                 moving_avg_val_loss) + ('' if not dynamic else ' loss scale: {:g} skipped steps: {}'.format(
-                    scaler.get_scale(), scaler.skipped_steps - skipped_before)))
+                    scaler.get_scale(), scaler.skipped_steps - skipped_before)) + ('' if not clip else
+                ' grad_norm_max: {:g} clipped_steps: {}'.format(losses[-1]['grad_norm_max'], losses[-1]['clipped_steps'])))
             if ema:
                 print('  averaged weights - val loss: {:0.4f} [avg: {:0.4f}]'.format(losses[-1]['val_ema'], moving_avg_val_ema_loss))
             store_json(loss_file, losses)

@@ -66,6 +66,9 @@ SIGNATURES = {
                                              C.c_double, vp, vp, vp]),
     "vpd_scale_state_update": (C.c_int, [vp, C.c_float, C.c_float, C.c_int, vp]),
     "vpd_ema_update": (C.c_int, [C.POINTER(vp), C.POINTER(vp), c_ll_p, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "vpd_clip_state_bytes": (C.c_size_t, []),
+    "vpd_op_grad_norm": (C.c_int, [C.POINTER(vp), c_ll_p, C.c_int, C.c_double, vp, C.c_float, vp, vp]),
+    "vpd_plan_grad_norm": (C.c_int, [vp, vp, C.c_longlong, C.c_double, vp, C.c_float, vp, vp, vp]),
     "vpd_plan_bucket_scratch_range": (C.c_int, [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "vpd_plan_grads_pending": (C.c_int, [vp]),
     "vpd_plan_materialize_grads": (C.c_int, [vp, vp, vp, vp]),
@@ -157,7 +160,7 @@ def lib(dtype="bf16"):
             # (an OLDER round's library, same-box A/B: the entry points added since are optional there -- engine.py asks hasattr)
             if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext",
                                                                  "vpd_plan_set_bn_frozen", "vpd_plan_set_param_grads",
-                                                                 "vpd_ema_update")):
+                                                                 "vpd_ema_update", "vpd_clip_state_bytes", "vpd_plan_grad_norm")):
                 continue
             raise VpdHipError("%s lacks symbol %s declared in include/vpd_hip.h" % (name, sym)) from e
         fn.restype = res

@@ -320,6 +320,15 @@ hipError_t vpd_launch_adamw_scaled(float* p, const float* g, float* m, float* v,
                                    double eps, double wd, const vpd_scale_state* st, hipStream_t s);
 hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, hipStream_t s);
 hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float backoff, int interval, hipStream_t s);
+// gradient-norm clipping (vpd_clip_state): one launch of the sum-of-squares pass over up to FR_MAX ranges -- `grid` blocks (from
+// vpd_grad_sqsum_grid: 0 = nothing to read, nothing launched), block b stores its double at partials[b] -- and the one-block
+// kernel that sums the first `used` slots behind the caller's block and writes norm, coefficient, statistics and clip->eff
+struct vpd_clip_state;
+#define CLIP_SLOTS 8192                 // doubles behind the struct: 2048 per launch, up to 4 launches at the full grid
+int vpd_grad_sqsum_grid(const FiniteRanges& r, int cap);
+hipError_t vpd_launch_grad_sqsum(const FiniteRanges& r, int grid, double* partials, hipStream_t s);
+hipError_t vpd_launch_clip_finalize(vpd_clip_state* clip, int used, double max_norm, vpd_scale_state* src, float host_scale,
+                                    hipStream_t s);
 hipError_t vpd_launch_scale_by_state(float* x, long n, const vpd_scale_state* st, hipStream_t stream);
 
 // exponential moving average of the weights (vpd_ema_update): float ranges of any alignment and length, passed by value

@@ -586,6 +586,117 @@ hipError_t vpd_launch_ema_update(const EmaRanges& r, double decay, int warmup, i
     return hipGetLastError();
 }
 
+// ---- gradient-norm clipping (vpd_clip_state): sum of squares over float ranges, then norm, coefficient and the effective scale ----
+// torch.nn.utils.clip_grad_norm_ decided on the device.  grad_sqsum_kernel streams the ranges of check_finite_kernel (same split:
+// up to three floats in front, the 16-byte aligned middle, up to three behind) with ema_update_kernel's loads: 32 KB tiles, a wave
+// takes four consecutive 1 KB rows in each half of the tile -- one address per half, the rows behind it by the offset field, eight
+// 16-byte loads in flight per thread, kept from sinking to their use.  Every element is widened to double and squared there, into
+// four accumulators per thread (one per float4 lane): no square overflows, and n * 2^-53 bounds the summation error.  A wave
+// reduces by shuffles, the block through LDS, both in a fixed order; thread 0 stores the block's double into its own slot.  No
+// atomics: the same input gives the same bits on every launch and on every data-parallel rank.
+static __device__ __forceinline__ void sq4(const f32x4& f, double& a0, double& a1, double& a2, double& a3) {
+    const double x = (double)f.x, y = (double)f.y, z = (double)f.z, w = (double)f.w;
+    a0 = fma(x, x, a0); a1 = fma(y, y, a1); a2 = fma(z, z, a2); a3 = fma(w, w, a3);
+}
+static __device__ __forceinline__ double wave_sum_f64(double s) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    return s;      // (lane 0 holds the wave's sum)
+}
+// (at most 64 registers, as ema_update_kernel: the capped grid of 2048 blocks = 8 waves per SIMD is resident at once)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void grad_sqsum_kernel(const FiniteRanges r, double* partials) {
+    __shared__ double wsum[4];
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nth = (long)gridDim.x * 256;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int k = 0; k < r.count; ++k) {
+        const float* x = r.ptr[k];
+        const long n = r.n[k];
+        long head = (long)((16 - (reinterpret_cast<size_t>(x) & 15)) & 15) >> 2;
+        if (head > n) head = n;
+        const f32x4* x4 = reinterpret_cast<const f32x4*>(x + head);
+        const long n4 = (n - head) >> 2;
+        // tiles of 2048 float4: the last element a tile touches is (tl << 11) + 1024 + 3 * 256 + 63 + 192 = (tl << 11) + 2047 < n4
+        const long ntile = n4 >> 11;
+        for (long tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
+            const f32x4* xa = x4 + (tl << 11) + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
+            const f32x4* xb = xa + 1024;
+            f32x4 fa = xa[0], fb = xa[64], fc = xa[128], fd = xa[192];
+            f32x4 ga = xb[0], gb = xb[64], gc = xb[128], gd = xb[192];
+            // (all eight loads are issued before the first is consumed: ema_update_kernel)
+            asm volatile("" : "+v"(fa), "+v"(fb), "+v"(fc), "+v"(fd), "+v"(ga), "+v"(gb), "+v"(gc), "+v"(gd));
+            sq4(fa, a0, a1, a2, a3); sq4(fb, a0, a1, a2, a3); sq4(fc, a0, a1, a2, a3); sq4(fd, a0, a1, a2, a3);
+            sq4(ga, a0, a1, a2, a3); sq4(gb, a0, a1, a2, a3); sq4(gc, a0, a1, a2, a3); sq4(gd, a0, a1, a2, a3);
+        }
+        for (long i = (ntile << 11) + tid; i < n4; i += nth) sq4(x4[i], a0, a1, a2, a3);
+        const long tail = head + (n4 << 2);
+        if (tid < head) { const double v = (double)x[tid]; a0 = fma(v, v, a0); }
+        if (tid < n - tail) { const double v = (double)x[tail + tid]; a1 = fma(v, v, a1); }
+    }
+    const double s = wave_sum_f64((a0 + a1) + (a2 + a3));
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+// The grid of one launch: a function of the ranges' lengths alone (the bits of the result depend on it), at most `cap` blocks
+int vpd_grad_sqsum_grid(const FiniteRanges& r, int cap) {
+    long total = 0;
+    for (int k = 0; k < r.count; ++k) total += r.n[k] > 0 ? r.n[k] : 0;
+    if (r.count <= 0 || total == 0) return 0;
+    long gsz = (total / 4 + 255) / 256;
+    if (gsz > cap) gsz = cap;
+    return gsz < 1 ? 1 : (int)gsz;
+}
+hipError_t vpd_launch_grad_sqsum(const FiniteRanges& r, int grid, double* partials, hipStream_t s) {
+    if (grid <= 0) return hipSuccess;
+    hipLaunchKernelGGL(grad_sqsum_kernel, dim3(grid), dim3(256), 0, s, r, partials);
+    return hipGetLastError();
+}
+
+// One block: the used slots summed in a fixed order (thread t takes slots t, t + 256, ...; then the wave and block order above),
+// everything in double, every stored value rounded to float once.  norm = sqrt(sum) / scale, coef = min(1, max_norm / (norm + 1e-6))
+// -- torch's formula and clamp -- and eff.scale = scale / coef, so that the AdamW that reads `eff` multiplies by coef / scale.
+// A sum of squares is non-finite exactly when an element is: eff.found then says so, to the source block as well.
+__global__ __launch_bounds__(256) void clip_finalize_kernel(vpd_clip_state* clip, int used, double max_norm, vpd_scale_state* src,
+                                                            float host_scale) {
+    __shared__ double wsum[4];
+    const double* partials = reinterpret_cast<const double*>(clip + 1);
+    double a = 0.0;
+    for (int i = threadIdx.x; i < used; i += 256) a += partials[i];
+    a = wave_sum_f64(a);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double sum = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    const bool bad = (__double_as_longlong(sum) & 0x7ff0000000000000LL) == 0x7ff0000000000000LL;      // inf or NaN
+    const double scale = src ? (double)src->scale : (double)host_scale;
+    const double norm = sqrt(sum) / scale;
+    double coef = max_norm / (norm + 1e-6);
+    coef = coef < 1.0 ? coef : 1.0;
+    if (bad) coef = 1.0;      // (the step is skipped: nothing reads it)
+    const float fnorm = (float)norm;
+    clip->total_norm = fnorm;
+    clip->coef = (float)coef;
+    clip->eff.scale = (float)(scale / coef);
+    unsigned found = bad ? 1u : 0u;
+    if (src) {
+        found |= src->found != 0u ? 1u : 0u;
+        if (bad) src->found = 1u;
+        clip->eff.applied_steps = src->applied_steps;
+    }
+    clip->eff.found = found;
+    if (bad) {
+        clip->nonfinite_steps += 1;
+    } else {
+        if (coef < 1.0) clip->clipped_steps += 1;
+        if (!nonfinite1(fnorm) && fnorm > clip->norm_max) clip->norm_max = fnorm;
+    }
+}
+hipError_t vpd_launch_clip_finalize(vpd_clip_state* clip, int used, double max_norm, vpd_scale_state* src, float host_scale,
+                                    hipStream_t s) {
+    hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, s, clip, used, max_norm, src, host_scale);
+    return hipGetLastError();
+}
+
 // Zero up to ZR_MAX float ranges in ONE launch (accumulator rows of the BN statistics + the fp32 weight-gradient
 // ranges the atomics kernel adds into): hipMemsetAsync costs 5-12 us per call on this runtime.
 __global__ __launch_bounds__(256) void zero_ranges_kernel(const ZeroRanges z) {

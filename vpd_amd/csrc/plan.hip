@@ -684,6 +684,23 @@ extern "C" int vpd_op_check_finite(const float* x, long long n, vpd_scale_state*
 // scratch while grads_in_scratch (everything behind the stem's: the stem is always unpacked into the flat buffer) and the ranges
 // of the `stem == 2` descriptors from `grads`; otherwise all of `grads`.  The conv ranges of `grads` are STALE after a lazy
 // backward and are not looked at.
+namespace {
+template <class Add>
+hipError_t for_each_step_grad_range(const vpd_plan_t* p, const float* grads, long long numel, void* workspace, Add&& add) {
+    hipError_t e = hipSuccess;
+    if (p->grads_in_scratch) {
+        const long long stem_end = (long long)p->stem.ntaps * p->stem.Co * p->stem.Kc;
+        e = add(reinterpret_cast<const float*>((char*)workspace + p->wg_off) + stem_end, p->wg_elems - stem_end);
+        for (const PackDesc& d : p->descs)
+            if (d.stem == 2 && e == hipSuccess) e = add(grads + d.src_off, d.numel);
+        if (e == hipSuccess) e = add(grads + p->nparam_padded, numel - p->nparam_padded);
+    } else {
+        e = add(grads, numel);
+    }
+    return e;
+}
+}  // namespace
+
 extern "C" int vpd_plan_check_grads(vpd_plan_t* p, const float* grads, long long numel, vpd_scale_state* state, void* workspace,
                                     void* stream) {
     if (!p || !grads || !state || !workspace) return fail("null argument");
@@ -691,17 +708,77 @@ extern "C" int vpd_plan_check_grads(vpd_plan_t* p, const float* grads, long long
     if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
     if (reinterpret_cast<size_t>(grads) & 15) return fail("grads must be 16-byte aligned");
     RangeList rl(state, (hipStream_t)stream);
-    if (p->grads_in_scratch) {
-        const long long stem_end = (long long)p->stem.ntaps * p->stem.Co * p->stem.Kc;
-        LCHECK(rl.add(reinterpret_cast<const float*>((char*)workspace + p->wg_off) + stem_end, p->wg_elems - stem_end));
-        for (const PackDesc& d : p->descs)
-            if (d.stem == 2) LCHECK(rl.add(grads + d.src_off, d.numel));
-        LCHECK(rl.add(grads + p->nparam_padded, numel - p->nparam_padded));
-    } else {
-        LCHECK(rl.add(grads, numel));
-    }
+    LCHECK(for_each_step_grad_range(p, grads, numel, workspace, [&](const float* x, long long n) { return rl.add(x, n); }));
     LCHECK(rl.flush());
     return 0;
+}
+
+// ---- gradient-norm clipping: the norm pass over the same ranges, then the one-block kernel that writes the caller's vpd_clip_state ----
+extern "C" size_t vpd_clip_state_bytes(void) { return sizeof(vpd_clip_state) + (size_t)CLIP_SLOTS * sizeof(double); }
+
+namespace {
+typedef std::vector<std::pair<const float*, long long>> NormRanges;
+int check_clip_args(double max_norm, const vpd_scale_state* src, float host_scale, const vpd_clip_state* clip) {
+    if (!clip) return fail("grad norm: null clip state");
+    if (reinterpret_cast<size_t>(clip) & 15) return fail("grad norm: clip state must be 16-byte aligned");
+    if (reinterpret_cast<size_t>(src) & 3) return fail("grad norm: scale state must be 4-byte aligned");
+    if (!(max_norm > 0.0)) return fail("grad norm: max_norm must be > 0 (+inf measures only)");
+    if (!src && (!(host_scale > 0.f) || !(host_scale < 3.0e38f))) return fail("grad norm: host_scale must be a positive finite number");
+    return 0;
+}
+// FR_MAX ranges per launch; launch l stores its blocks' sums in the slots behind launch l - 1's.  The grids depend on the ranges'
+// lengths alone, so the bits of the result do too.
+int launch_grad_norm(const NormRanges& ranges, double max_norm, vpd_scale_state* src, float host_scale, vpd_clip_state* clip,
+                     hipStream_t s) {
+    const size_t nlaunch = (ranges.size() + FR_MAX - 1) / FR_MAX;
+    if (nlaunch > CLIP_SLOTS) return fail("grad norm: too many ranges");
+    const int cap = nlaunch ? (int)std::min<size_t>(2048, CLIP_SLOTS / nlaunch) : 0;
+    double* partials = reinterpret_cast<double*>(clip + 1);
+    int used = 0;
+    for (size_t at = 0; at < ranges.size(); at += FR_MAX) {
+        FiniteRanges r;
+        memset(&r, 0, sizeof r);
+        for (size_t i = at; i < ranges.size() && i < at + FR_MAX; ++i) {
+            r.ptr[r.count] = ranges[i].first;
+            r.n[r.count++] = (long)ranges[i].second;
+        }
+        const int grid = vpd_grad_sqsum_grid(r, cap);
+        LCHECK(vpd_launch_grad_sqsum(r, grid, partials + used, s));
+        used += grid;
+    }
+    LCHECK(vpd_launch_clip_finalize(clip, used, max_norm, src, host_scale, s));
+    return 0;
+}
+}  // namespace
+
+extern "C" int vpd_op_grad_norm(const float* const* x, const long long* n, int count, double max_norm, const vpd_scale_state* src,
+                                float host_scale, vpd_clip_state* clip, void* stream) {
+    if (check_clip_args(max_norm, src, host_scale, clip)) return -1;
+    if (count < 0) return fail("grad norm: negative count");
+    if (count > 0 && (!x || !n)) return fail("grad norm: null argument");
+    NormRanges ranges;
+    for (int i = 0; i < count; ++i) {
+        if (!x[i]) return fail("grad norm: null range");
+        if (n[i] < 0) return fail("grad norm: negative length");
+        if (reinterpret_cast<size_t>(x[i]) & 3) return fail("grad norm: ranges must be 4-byte aligned");
+        if (n[i] > 0) ranges.emplace_back(x[i], n[i]);
+    }
+    return launch_grad_norm(ranges, max_norm, const_cast<vpd_scale_state*>(src), host_scale, clip, (hipStream_t)stream);
+}
+
+extern "C" int vpd_plan_grad_norm(vpd_plan_t* p, const float* grads, long long numel, double max_norm, vpd_scale_state* src,
+                                  float host_scale, vpd_clip_state* clip, void* workspace, void* stream) {
+    if (!p || !grads || !workspace) return fail("null argument");
+    if (check_clip_args(max_norm, src, host_scale, clip)) return -1;
+    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
+    if (reinterpret_cast<size_t>(grads) & 15) return fail("grads must be 16-byte aligned");
+    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
+    NormRanges ranges;
+    LCHECK(for_each_step_grad_range(p, grads, numel, workspace, [&](const float* x, long long n) {
+        if (n > 0) ranges.emplace_back(x, n);
+        return hipSuccess;
+    }));
+    return launch_grad_norm(ranges, max_norm, src, host_scale, clip, (hipStream_t)stream);
 }
 
 extern "C" int vpd_adamw_step_scaled(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,

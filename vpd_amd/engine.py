@@ -207,6 +207,9 @@ class StudentEngine:
         self._ema_t0 = 0               # adam_step when averaging began
         self._ema_version = 0          # bumped by every update: plans packed from the EMA buffers repack
         self._use_ema = False          # use_ema(): eval forwards read the EMA buffers
+        # enable_grad_clip(): the device block of the gradient-norm clipping (vpd_clip_state + partial sums, int32 words)
+        self._clip = None
+        self._clip_max_norm = None
 
     # -- helpers -------------------------------------------------------------
     @property
@@ -232,6 +235,69 @@ class StudentEngine:
         self.materialize_grads()
         self.check(self.L.vpd_op_check_finite(_ptr(self._grads), self.param_numel, _ptr(state), self._stream()),
                    "vpd_op_check_finite")
+
+    # -- gradient-norm clipping -----------------------------------------------------
+    def enable_grad_clip(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) inside adamw_step(), decided on the device: one pass takes the norm
+        of exactly the gradients the step reads (after a lazy backward: the weight-gradient scratch + the small ranges of the flat
+        buffer), a one-block kernel turns it into coef = min(1, max_norm / (norm + 1e-6)) and into the block AdamW and the EMA
+        read (include/vpd_hip.h, vpd_clip_state).  Under a DynamicLossScaler the pass replaces the non-finite search.  Without one
+        a non-finite norm SKIPS the step and counts it (torch would write NaN into every weight).  As attach_scale_state does,
+        this moves the applied-step count to the device.  float('inf') measures without clipping."""
+        max_norm = float(max_norm)
+        if not max_norm > 0.0:
+            raise ValueError("max_grad_norm must be > 0 (float('inf') measures only), not %r" % (max_norm,))
+        if not hasattr(self.L, "vpd_plan_grad_norm"):      # (absent only in an older A/B library)
+            raise RuntimeError("this libvpdhip has no vpd_plan_grad_norm")
+        if self._clip is None:
+            step = int(self.adam_step)
+            self._clip = torch.zeros(int(self.L.vpd_clip_state_bytes()) // 4, dtype=torch.int32, device=self.device)
+            self._clip[3] = step
+            if self._dyn_state is None:
+                self._dyn_state = self._clip      # (a DynamicLossScaler's block keeps the count when there is one)
+        self._clip_max_norm = max_norm
+
+    def disable_grad_clip(self):
+        """adamw_step launches what it launched before enable_grad_clip(); the step count comes back to the host when the clip
+        block held it (synchronises)."""
+        if self._clip is None:
+            return
+        if self._dyn_state is self._clip:
+            self._adam_step = int(self._clip[3].item())
+            self._dyn_state = None
+        self._clip = None
+        self._clip_max_norm = None
+
+    @property
+    def grad_clip_enabled(self):
+        return self._clip is not None
+
+    def clip_stats(self, reset_max=False):
+        """The statistics of the clip block (synchronises): the last step's norm and coefficient, the running maximum of the
+        finite norms, the steps clipped and the steps whose norm was not finite.  reset_max: norm_max starts again at 0."""
+        if self._clip is None:
+            raise RuntimeError("clip_stats() before enable_grad_clip()")
+        h = self._clip[:16].cpu()
+        f = h.view(torch.float32)
+        out = dict(total_norm=float(f[8]), norm_max=float(f[9]), coef=float(f[10]), clipped_steps=int(h[11]),
+                   nonfinite_steps=int(h[12]))
+        if reset_max:
+            self._clip[9] = 0
+        return out
+
+    def _clip_norm(self, pl, numel, src):
+        """enqueue the norm pass + the one-block kernel over what the step that follows reads (pl: its plan, or None = the flat
+        buffer); src: the DynamicLossScaler's block in flight, or None = the host's static loss scale"""
+        clip = self._clip
+        if pl is not None:
+            self.check(self.L.vpd_plan_grad_norm(pl.handle, _ptr(self._grads), numel, self._clip_max_norm, _ptr(src),
+                                                 float(self.loss_scale), _ptr(clip), _ptr(pl.workspace), self._stream()),
+                       "vpd_plan_grad_norm")
+        else:
+            x = (C.c_void_p * 1)(self._grads.data_ptr())
+            n = (C.c_longlong * 1)(numel)
+            self.check(self.L.vpd_op_grad_norm(x, n, 1, self._clip_max_norm, _ptr(src), float(self.loss_scale), _ptr(clip),
+                                               self._stream()), "vpd_op_grad_norm")
 
     @property
     def num_batches_tracked(self):
@@ -566,7 +632,8 @@ class StudentEngine:
             self.adam_m = torch.zeros_like(self.params)
             self.adam_v = torch.zeros_like(self.params)
         st = self.scale_state      # a DynamicLossScaler's step in flight: search + AdamW decided on the device, no host count
-        if st is None:
+        clip = self._clip          # enable_grad_clip(): the norm pass (instead of the search) + AdamW reading the clip block
+        if st is None and clip is None:
             self.adam_step = self.adam_step + 1
         pl = self._step_plan
         if pl is not None and numel < pl.param_numel:
@@ -577,7 +644,14 @@ class StudentEngine:
             pl = None
         if pl is not None and pl.packed_version == self.weights_version() and os.environ.get("VPD_FUSED_ADAMW", "1") != "0":
             # the train plan of the last backward: AdamW + refresh of its packed bf16 weights in one pass
-            if st is not None:
+            if clip is not None:
+                n_ = max(numel, pl.param_numel)
+                self._clip_norm(pl, n_, st)
+                self.check(self.L.vpd_plan_adamw_step_scaled(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
+                                                             _ptr(self.adam_v), n_, lr, betas[0], betas[1], eps, weight_decay,
+                                                             _ptr(clip), _ptr(pl.workspace), self._stream()),
+                           "vpd_plan_adamw_step_scaled")
+            elif st is not None:
                 n_ = max(numel, pl.param_numel)
                 self.check(self.L.vpd_plan_check_grads(pl.handle, _ptr(self._grads), n_, _ptr(st), _ptr(pl.workspace),
                                                        self._stream()), "vpd_plan_check_grads")
@@ -592,6 +666,14 @@ class StudentEngine:
                            "vpd_plan_adamw_step")
             self._hip_version += 1
             pl.packed_version = self.weights_version()
+        elif clip is not None:
+            # (a static loss scale is taken out by the kernel, through the clip block: the buffer stays as the backward left it)
+            self.materialize_grads()
+            self._clip_norm(None, numel, st)
+            self.check(self.L.vpd_adamw_step_scaled(_ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v),
+                                                    numel, lr, betas[0], betas[1], eps, weight_decay, _ptr(clip),
+                                                    self._stream()), "vpd_adamw_step_scaled")
+            self._hip_version += 1
         elif st is not None:
             self.materialize_grads()
             self.check(self.L.vpd_op_check_finite(_ptr(self._grads), numel, _ptr(st), self._stream()), "vpd_op_check_finite")
@@ -607,7 +689,10 @@ class StudentEngine:
             self._hip_version += 1
         if self._ema is not None:
             # after the AdamW, before the scaler's update(): `found` and `applied_steps` are still those of this step
-            self._ema_enqueue(st)
+            self._ema_enqueue(clip if clip is not None else st)
+        if clip is not None and st is None:
+            # no scaler's update() follows: the clip block counts its own steps (applied, or skipped on a non-finite norm)
+            self.check(self.L.vpd_scale_state_update(_ptr(clip), 1.0, 1.0, 2 ** 31 - 1, self._stream()), "vpd_scale_state_update")
 
     def capture_eval_graph(self, x, out):
         """hipGraph of the eval forward for this batch size, bound to x / out (capture needs a

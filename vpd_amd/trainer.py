@@ -36,7 +36,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     consumes_lazy_grads = True      # models.util.step(): this optimizer reads the weight-gradient kernels' own layout
 
-    def __init__(self, params, engine, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01):
+    def __init__(self, params, engine, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, max_grad_norm=None):
+        """max_grad_norm: torch.nn.utils.clip_grad_norm_(params, max_grad_norm) before every step, decided on the device over
+        exactly the gradients the step reads (StudentEngine.enable_grad_clip); None (the default): nothing is added."""
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be > 0 (float('inf') measures only), not %r" % (max_grad_norm,))
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._engine = engine
@@ -46,6 +50,13 @@ class FusedAdamW(torch.optim.Optimizer):
         ptr0 = engine.params.data_ptr()
         has_dec = any((q.data_ptr() - ptr0) // 4 >= enc_end for q in params)
         self._numel = engine.param_numel if has_dec else enc_end
+        if max_grad_norm is not None:
+            engine.enable_grad_clip(max_grad_norm)
+
+    def clip_stats(self, reset_max=False):
+        """{'total_norm', 'norm_max', 'coef', 'clipped_steps', 'nonfinite_steps'} of the clip block; synchronises, as
+        DynamicLossScaler.get_scale() does"""
+        return self._engine.clip_stats(reset_max)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -187,10 +198,13 @@ class ModelTrainer:
             epoch_emb_loss, epoch_emb_n = self._reducer.all_reduce_scalars(epoch_emb_loss, epoch_emb_n)
         return epoch_emb_loss / epoch_emb_n
 
-    def get_optimizer(self, learning_rate, loss_scale=None):
-        """loss_scale: None -- the default scaler of the student's element type (bf16: none; fp16: the static LossScaler, 256);
+    def get_optimizer(self, learning_rate, loss_scale=None, max_grad_norm=None):
+        """max_grad_norm: clip the global gradient norm before every step (FusedAdamW); None: no clipping, nothing added.
+        loss_scale: None -- the default scaler of the student's element type (bf16: none; fp16: the static LossScaler, 256);
         'dynamic' -- a DynamicLossScaler (GradScaler's defaults: skip on overflow, decided on the device); a number -- a static
         LossScaler with that scale.  A scaler is an fp16 matter: asking for one on a bf16 student raises."""
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be > 0 (float('inf') measures only), not %r" % (max_grad_norm,))
         params = list(self.encoder.parameters())
         if hasattr(self, 'fcn_time'):
             params.extend(self.fcn_time.parameters())
@@ -210,7 +224,7 @@ class ModelTrainer:
             scaler = DynamicLossScaler(eng)
         else:
             scaler = LossScaler(eng, float(loss_scale))
-        return FusedAdamW(params, eng, lr=learning_rate), scaler
+        return FusedAdamW(params, eng, lr=learning_rate, max_grad_norm=max_grad_norm), scaler
 
     @contextlib.contextmanager
     def ema_weights(self):
