@@ -74,6 +74,9 @@ struct AdamHyper { float decay, omb1, b2, omb2, step_size, inv_sqrt_bc2, eps, gs
 // ... under a dynamic loss scaler (vpd_scale_state, include/vpd_hip.h): step_size, inv_sqrt_bc2 and gscale come from the device block
 struct vpd_scale_state;
 struct AdamHyperDyn { AdamHyper h; const vpd_scale_state* st; double lr, b1, b2; };
+// What the two AdamW launchers take.  st == null: `step` (1-based) and `gscale` are the host's (adamw_kernel<AdamHyper>); else the
+// device block decides and both are ignored (<AdamHyperDyn>)
+struct AdamArgs { double lr, b1, b2, eps, wd; int step; float gscale; const vpd_scale_state* st; };
 #define FR_MAX 96
 struct FiniteRanges {                   // float ranges of any alignment and length (vpd_launch_check_finite)
     const float* ptr[FR_MAX];
@@ -305,19 +308,13 @@ hipError_t vpd_launch_pack_input(const float* x, int N, int C, int H, int W, bf1
 hipError_t vpd_launch_pack_weights(const PackDesc* d_descs, int ndesc, const int* d_blockmap, int nblocks,
                                    const float* master, bf16_t* arena, hipStream_t s);
 hipError_t vpd_launch_adamw_pack(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
-                                 float* m, float* v, bf16_t* arena, double lr, double b1, double b2, double eps, double wd,
-                                 int step, hipStream_t s, const float* wg = nullptr, float gscale = 1.f);      // wg: conv gradients still in the scratch
+                                 float* m, float* v, bf16_t* arena, const AdamArgs& a, hipStream_t s,
+                                 const float* wg = nullptr);      // wg: conv gradients still in the scratch
 hipError_t vpd_launch_unpack_grads(const PackDesc* d_descs, int ndesc, const int* d_blockmap, int nblocks,
                                    const float* wg, float* grads, hipStream_t s);
-hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
-                            double eps, double wd, int step, hipStream_t s, float gscale = 1.f);
-// dynamic loss scaling (vpd_scale_state): the two AdamW launches reading scale / applied steps / the non-finite word from the
-// device block, the inf / NaN search, the update rule; head.hip: d(loss)/d(pred) x the block's scale
-hipError_t vpd_launch_adamw_pack_scaled(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
-                                        float* m, float* v, bf16_t* arena, double lr, double b1, double b2, double eps,
-                                        double wd, const vpd_scale_state* st, hipStream_t s, const float* wg = nullptr);
-hipError_t vpd_launch_adamw_scaled(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
-                                   double eps, double wd, const vpd_scale_state* st, hipStream_t s);
+hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, const AdamArgs& a, hipStream_t s);
+// dynamic loss scaling (vpd_scale_state): the two AdamW launches above reading scale / applied steps / the non-finite word from
+// the device block (AdamArgs::st), the inf / NaN search, the update rule; head.hip: d(loss)/d(pred) x the block's scale
 hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, hipStream_t s);
 hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float backoff, int interval, hipStream_t s);
 // gradient-norm clipping (vpd_clip_state): one launch of the sum-of-squares pass over up to FR_MAX ranges -- `grid` blocks (from
@@ -325,7 +322,7 @@ hipError_t vpd_launch_scale_update(vpd_scale_state* st, float growth, float back
 // kernel that sums the first `used` slots behind the caller's block and writes norm, coefficient, statistics and clip->eff
 struct vpd_clip_state;
 #define CLIP_SLOTS 8192                 // doubles behind the struct: 2048 per launch, up to 4 launches at the full grid
-int vpd_grad_sqsum_grid(const FiniteRanges& r, int cap);
+int vpd_grad_sqsum_grid(const long* n, int count, int cap);      // (the grid of every streaming range kernel: count lengths)
 hipError_t vpd_launch_grad_sqsum(const FiniteRanges& r, int grid, double* partials, hipStream_t s);
 hipError_t vpd_launch_clip_finalize(vpd_clip_state* clip, int used, double max_norm, vpd_scale_state* src, float host_scale,
                                     hipStream_t s);

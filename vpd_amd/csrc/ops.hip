@@ -696,8 +696,8 @@ extern "C" int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* o
     hipStream_t s = (hipStream_t)stream;
     DevTables t;
     HCHECK(t.upload(descs, bmap_adam, s));
-    LCHECK(vpd_launch_adamw_pack(t.descs, t.bmap, (int)bmap_adam.size() / 2, params, grads, adam_m, adam_v, (bf16_t*)arena, lr,
-                                 beta1, beta2, eps, weight_decay, step, s, wg, gscale));
+    LCHECK(vpd_launch_adamw_pack(t.descs, t.bmap, (int)bmap_adam.size() / 2, params, grads, adam_m, adam_v, (bf16_t*)arena,
+                                 AdamArgs{lr, beta1, beta2, eps, weight_decay, step, gscale, nullptr}, s, wg));
     HCHECK(hipStreamSynchronize(s));
     return 0;
 }

@@ -256,12 +256,14 @@ static __device__ __forceinline__ void adamw4(float4& pp, const float4& gg, floa
     adamw1(pp.x, gg.x, mm.x, vv.x, h); adamw1(pp.y, gg.y, mm.y, vv.y, h);
     adamw1(pp.z, gg.z, mm.z, vv.z, h); adamw1(pp.w, gg.w, mm.w, vv.w, h);
 }
-static AdamHyper adam_hyper(double lr, double b1, double b2, double eps, double wd, int step, float gscale) {
-    const double bc1 = 1.0 - pow(b1, step);
-    const double bc2 = 1.0 - pow(b2, step);
-    return AdamHyper{(float)(1.0 - lr * wd), (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1),
-                     (float)(1.0 / sqrt(bc2)), (float)eps, gscale};
+static AdamHyper adam_hyper(const AdamArgs& a, int step, float gscale) {
+    const double bc1 = 1.0 - pow(a.b1, step);
+    const double bc2 = 1.0 - pow(a.b2, step);
+    return AdamHyper{(float)(1.0 - a.lr * a.wd), (float)(1.0 - a.b1), (float)a.b2, (float)(1.0 - a.b2), (float)(a.lr / bc1),
+                     (float)(1.0 / sqrt(bc2)), (float)a.eps, gscale};
 }
+// (step 1 / gscale 1 are place-holders: adam_live replaces step_size, inv_sqrt_bc2 and gscale from the device block)
+static AdamHyperDyn adam_hyper_dyn(const AdamArgs& a) { return AdamHyperDyn{adam_hyper(a, 1, 1.f), a.st, a.lr, a.b1, a.b2}; }
 
 // H: AdamHyper as the host computed it (every launch without a dynamic loss scaler), or AdamHyperDyn -- the same plus the
 // scaler's device block (vpd_scale_state, include/vpd_hip.h): gradient factor 1 / scale, bias corrections from the number of
@@ -295,28 +297,18 @@ __global__ __launch_bounds__(256) void adamw_kernel(float4* p, const float4* g, 
         p[i] = pp; m[i] = mm; v[i] = vv;
     }
 }
-hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
-                            double eps, double wd, int step, hipStream_t s, float gscale) {
+hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, const AdamArgs& a, hipStream_t s) {
     if (n % 4) return hipErrorInvalidValue;
     const long n4 = n / 4;
     long gsz = (n4 + 255) / 256;
     if (gsz > 4096) gsz = 4096;
-    hipLaunchKernelGGL(adamw_kernel<AdamHyper>, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, (float4*)p, (const float4*)g,
-                       (float4*)m, (float4*)v, n4, adam_hyper(lr, b1, b2, eps, wd, step, gscale));
-    return hipGetLastError();
-}
-// (step 1 / gscale 1 are place-holders: adam_live replaces step_size, inv_sqrt_bc2 and gscale from the device block)
-static AdamHyperDyn adam_hyper_dyn(double lr, double b1, double b2, double eps, double wd, const vpd_scale_state* st) {
-    return AdamHyperDyn{adam_hyper(lr, b1, b2, eps, wd, 1, 1.f), st, lr, b1, b2};
-}
-hipError_t vpd_launch_adamw_scaled(float* p, const float* g, float* m, float* v, long n, double lr, double b1, double b2,
-                                   double eps, double wd, const vpd_scale_state* st, hipStream_t s) {
-    if (n % 4) return hipErrorInvalidValue;
-    const long n4 = n / 4;
-    long gsz = (n4 + 255) / 256;
-    if (gsz > 4096) gsz = 4096;
-    hipLaunchKernelGGL(adamw_kernel<AdamHyperDyn>, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, (float4*)p,
-                       (const float4*)g, (float4*)m, (float4*)v, n4, adam_hyper_dyn(lr, b1, b2, eps, wd, st));
+    const dim3 grid(gsz < 1 ? 1 : (int)gsz);
+    if (!a.st)
+        hipLaunchKernelGGL(adamw_kernel<AdamHyper>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m, (float4*)v,
+                           n4, adam_hyper(a, a.step, a.gscale));
+    else
+        hipLaunchKernelGGL(adamw_kernel<AdamHyperDyn>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m, (float4*)v,
+                           n4, adam_hyper_dyn(a));
     return hipGetLastError();
 }
 
@@ -413,23 +405,16 @@ __global__ __launch_bounds__(256) void adamw_pack_kernel(const PackDesc* descs, 
         }
 }
 hipError_t vpd_launch_adamw_pack(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
-                                 float* m, float* v, bf16_t* arena, double lr, double b1, double b2, double eps, double wd,
-                                 int step, hipStream_t s, const float* wg, float gscale) {
+                                 float* m, float* v, bf16_t* arena, const AdamArgs& a, hipStream_t s, const float* wg) {
     if ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) |
          reinterpret_cast<size_t>(v)) & 15)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adamw_pack_kernel<AdamHyper>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v, arena,
-                       adam_hyper(lr, b1, b2, eps, wd, step, gscale), wg);
-    return hipGetLastError();
-}
-hipError_t vpd_launch_adamw_pack_scaled(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
-                                        float* m, float* v, bf16_t* arena, double lr, double b1, double b2, double eps,
-                                        double wd, const vpd_scale_state* st, hipStream_t s, const float* wg) {
-    if ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) |
-         reinterpret_cast<size_t>(v)) & 15)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(adamw_pack_kernel<AdamHyperDyn>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v,
-                       arena, adam_hyper_dyn(lr, b1, b2, eps, wd, st), wg);
+    if (!a.st)
+        hipLaunchKernelGGL(adamw_pack_kernel<AdamHyper>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v, arena,
+                           adam_hyper(a, a.step, a.gscale), wg);
+    else
+        hipLaunchKernelGGL(adamw_pack_kernel<AdamHyperDyn>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v,
+                           arena, adam_hyper_dyn(a), wg);
     return hipGetLastError();
 }
 
@@ -441,6 +426,19 @@ static __device__ __forceinline__ unsigned nonfinite1(float f) {
 static __device__ __forceinline__ unsigned nonfinite4(const float4& f) {
     return nonfinite1(f.x) | nonfinite1(f.y) | nonfinite1(f.z) | nonfinite1(f.w);
 }
+// What the three range walkers (check_finite_kernel, ema_update_kernel, grad_sqsum_kernel) share.  A float range of any alignment
+// and length, split by the 16-byte phase of `x`: `head` floats (at most three) in front, the aligned middle of `n4` float4 at
+// x + head, and the floats from `tail` on (at most three)
+struct RangeSplit { long head, n4, tail; };
+static __device__ __forceinline__ RangeSplit split_range(const float* x, long n) {
+    long head = (long)((16 - (reinterpret_cast<size_t>(x) & 15)) & 15) >> 2;
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    return RangeSplit{head, n4, head + (n4 << 2)};
+}
+// ... and a wave's four consecutive 1 KB rows of one operand: one address, the rows behind it by the instruction's offset field
+struct Rows4 { f32x4 a, b, c, d; };
+static __device__ __forceinline__ Rows4 load_rows4(const f32x4* p) { return Rows4{p[0], p[64], p[128], p[192]}; }
 // Every range of `r` (float ranges of any alignment) in one launch: a range's 16-byte aligned middle is read with 16-byte loads,
 // four in flight per thread, the up to three floats in front of it and behind it one by one.  A wave votes; a block issues ONE
 // atomic OR, and only when one of its waves found something -- a clean step (all of them but a handful) writes nothing.
@@ -453,17 +451,15 @@ __global__ __launch_bounds__(256) void check_finite_kernel(const FiniteRanges r,
     for (int k = 0; k < r.count; ++k) {
         const float* x = r.ptr[k];
         const long n = r.n[k];
-        long head = (long)((16 - (reinterpret_cast<size_t>(x) & 15)) & 15) >> 2;
-        if (head > n) head = n;
+        const RangeSplit sp = split_range(x, n);
+        const long head = sp.head, n4 = sp.n4, tail = sp.tail;
         const float4* x4 = reinterpret_cast<const float4*>(x + head);
-        const long n4 = (n - head) >> 2;
         long i = tid;
         for (; i + 3 * nth < n4; i += 4 * nth) {
             const float4 a = x4[i], b = x4[i + nth], c = x4[i + 2 * nth], d = x4[i + 3 * nth];
             bad |= nonfinite4(a) | nonfinite4(b) | nonfinite4(c) | nonfinite4(d);
         }
         for (; i < n4; i += nth) bad |= nonfinite4(x4[i]);
-        const long tail = head + (n4 << 2);
         if (tid < head) bad |= nonfinite1(x[tid]);
         if (tid < n - tail) bad |= nonfinite1(x[tail + tid]);
     }
@@ -472,12 +468,9 @@ __global__ __launch_bounds__(256) void check_finite_kernel(const FiniteRanges r,
     if (threadIdx.x == 0 && blk) atomicOr(found, 1u);
 }
 hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, hipStream_t s) {
-    long total = 0;
-    for (int k = 0; k < r.count; ++k) total += r.n[k] > 0 ? r.n[k] : 0;
-    if (r.count <= 0 || total == 0) return hipSuccess;
-    long gsz = (total / 4 + 255) / 256;      // at most 2048 blocks = 8 per CU: enough loads in flight for the fabric
-    if (gsz > 2048) gsz = 2048;
-    hipLaunchKernelGGL(check_finite_kernel, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, r, &st->found);
+    const int grid = vpd_grad_sqsum_grid(r.n, r.count, 2048);      // at most 2048 blocks = 8 per CU: enough loads in flight for the fabric
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(check_finite_kernel, dim3(grid), dim3(256), 0, s, r, &st->found);
     return hipGetLastError();
 }
 
@@ -538,9 +531,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const float* x = r.src[k];
         float* y = r.dst[k];
         const long n = r.n[k];
-        long head = (long)((16 - (reinterpret_cast<size_t>(y) & 15)) & 15) >> 2;
-        if (head > n) head = n;
-        const long n4 = (n - head) >> 2;
+        const RangeSplit sp = split_range(y, n);
+        const long head = sp.head, n4 = sp.n4, tail = sp.tail;
         f32x4* y4 = reinterpret_cast<f32x4*>(y + head);
         long i = tid;
         if ((reinterpret_cast<size_t>(x + head) & 15) == 0) {
@@ -552,15 +544,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 const long e = (tl << 10) + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
                 const f32x4* xp = x4 + e;
                 f32x4* yp = y4 + e;
-                f32x4 sa = xp[0], sb = xp[64], sc = xp[128], sd = xp[192];
-                f32x4 da = yp[0], db = yp[64], dc = yp[128], dd = yp[192];
+                Rows4 rs = load_rows4(xp), rd = load_rows4(yp);
                 // every loaded value passes through one opaque point: all eight loads are issued before the first is consumed
                 // (left alone, hipcc sinks each pair of loads to its use and waits for it there: two in flight per thread)
-                asm volatile("" : "+v"(sa), "+v"(sb), "+v"(sc), "+v"(sd), "+v"(da), "+v"(db), "+v"(dc), "+v"(dd));
-                yp[0] = ema4(sa, da, omd);
-                yp[64] = ema4(sb, db, omd);
-                yp[128] = ema4(sc, dc, omd);
-                yp[192] = ema4(sd, dd, omd);
+                asm volatile("" : "+v"(rs.a), "+v"(rs.b), "+v"(rs.c), "+v"(rs.d), "+v"(rd.a), "+v"(rd.b), "+v"(rd.c), "+v"(rd.d));
+                yp[0] = ema4(rs.a, rd.a, omd);
+                yp[64] = ema4(rs.b, rd.b, omd);
+                yp[128] = ema4(rs.c, rd.c, omd);
+                yp[192] = ema4(rs.d, rd.d, omd);
             }
             for (i += ntile << 10; i < n4; i += nth) y4[i] = ema4(x4[i], y4[i], omd);
         } else {
@@ -570,19 +561,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 y4[i] = ema4(s, y4[i], omd);
             }
         }
-        const long tail = head + (n4 << 2);
         if (tid < head) y[tid] = ema1(x[tid], y[tid], omd);
         if (tid < n - tail) y[tail + tid] = ema1(x[tail + tid], y[tail + tid], omd);
     }
 }
 hipError_t vpd_launch_ema_update(const EmaRanges& r, double decay, int warmup, int t, int t0, const vpd_scale_state* st,
                                  hipStream_t s) {
-    long total = 0;
-    for (int k = 0; k < r.count; ++k) total += r.n[k] > 0 ? r.n[k] : 0;
-    if (r.count <= 0 || total == 0) return hipSuccess;
-    long gsz = (total / 4 + 255) / 256;      // capped like check_finite_kernel's grid: 2048 blocks = 8 per CU
-    if (gsz > 2048) gsz = 2048;
-    hipLaunchKernelGGL(ema_update_kernel, dim3(gsz < 1 ? 1 : (int)gsz), dim3(256), 0, s, r, decay, warmup, t, t0, st);
+    const int grid = vpd_grad_sqsum_grid(r.n, r.count, 2048);      // capped like check_finite_kernel's grid: 2048 blocks = 8 per CU
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(grid), dim3(256), 0, s, r, decay, warmup, t, t0, st);
     return hipGetLastError();
 }
 
@@ -603,6 +590,13 @@ static __device__ __forceinline__ double wave_sum_f64(double s) {
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     return s;      // (lane 0 holds the wave's sum)
 }
+// ... and a block's: the four waves' sums through `wsum`, added as (w0 + w1) + (w2 + w3) (every thread returns the block's sum)
+static __device__ __forceinline__ double block_sum_f64(double s, double* wsum) {
+    s = wave_sum_f64(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
 // (at most 64 registers, as ema_update_kernel: the capped grid of 2048 blocks = 8 waves per SIMD is resident at once)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void grad_sqsum_kernel(const FiniteRanges r, double* partials) {
     __shared__ double wsum[4];
@@ -611,37 +605,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     for (int k = 0; k < r.count; ++k) {
         const float* x = r.ptr[k];
         const long n = r.n[k];
-        long head = (long)((16 - (reinterpret_cast<size_t>(x) & 15)) & 15) >> 2;
-        if (head > n) head = n;
+        const RangeSplit sp = split_range(x, n);
+        const long head = sp.head, n4 = sp.n4, tail = sp.tail;
         const f32x4* x4 = reinterpret_cast<const f32x4*>(x + head);
-        const long n4 = (n - head) >> 2;
         // tiles of 2048 float4: the last element a tile touches is (tl << 11) + 1024 + 3 * 256 + 63 + 192 = (tl << 11) + 2047 < n4
         const long ntile = n4 >> 11;
         for (long tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
             const f32x4* xa = x4 + (tl << 11) + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
             const f32x4* xb = xa + 1024;
-            f32x4 fa = xa[0], fb = xa[64], fc = xa[128], fd = xa[192];
-            f32x4 ga = xb[0], gb = xb[64], gc = xb[128], gd = xb[192];
+            Rows4 f = load_rows4(xa), g = load_rows4(xb);
             // (all eight loads are issued before the first is consumed: ema_update_kernel)
-            asm volatile("" : "+v"(fa), "+v"(fb), "+v"(fc), "+v"(fd), "+v"(ga), "+v"(gb), "+v"(gc), "+v"(gd));
-            sq4(fa, a0, a1, a2, a3); sq4(fb, a0, a1, a2, a3); sq4(fc, a0, a1, a2, a3); sq4(fd, a0, a1, a2, a3);
-            sq4(ga, a0, a1, a2, a3); sq4(gb, a0, a1, a2, a3); sq4(gc, a0, a1, a2, a3); sq4(gd, a0, a1, a2, a3);
+            asm volatile("" : "+v"(f.a), "+v"(f.b), "+v"(f.c), "+v"(f.d), "+v"(g.a), "+v"(g.b), "+v"(g.c), "+v"(g.d));
+            sq4(f.a, a0, a1, a2, a3); sq4(f.b, a0, a1, a2, a3); sq4(f.c, a0, a1, a2, a3); sq4(f.d, a0, a1, a2, a3);
+            sq4(g.a, a0, a1, a2, a3); sq4(g.b, a0, a1, a2, a3); sq4(g.c, a0, a1, a2, a3); sq4(g.d, a0, a1, a2, a3);
         }
         for (long i = (ntile << 11) + tid; i < n4; i += nth) sq4(x4[i], a0, a1, a2, a3);
-        const long tail = head + (n4 << 2);
         if (tid < head) { const double v = (double)x[tid]; a0 = fma(v, v, a0); }
         if (tid < n - tail) { const double v = (double)x[tail + tid]; a1 = fma(v, v, a1); }
     }
-    const double s = wave_sum_f64((a0 + a1) + (a2 + a3));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    const double s = block_sum_f64((a0 + a1) + (a2 + a3), wsum);
+    if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
-// The grid of one launch: a function of the ranges' lengths alone (the bits of the result depend on it), at most `cap` blocks
-int vpd_grad_sqsum_grid(const FiniteRanges& r, int cap) {
+// The grid of one launch of a range walker (this one, check_finite_kernel, ema_update_kernel): a function of the ranges' lengths
+// alone (the bits of a norm depend on it), at most `cap` blocks; 0 = nothing to do
+int vpd_grad_sqsum_grid(const long* n, int count, int cap) {
     long total = 0;
-    for (int k = 0; k < r.count; ++k) total += r.n[k] > 0 ? r.n[k] : 0;
-    if (r.count <= 0 || total == 0) return 0;
+    for (int k = 0; k < count; ++k) total += n[k] > 0 ? n[k] : 0;
+    if (count <= 0 || total == 0) return 0;
     long gsz = (total / 4 + 255) / 256;
     if (gsz > cap) gsz = cap;
     return gsz < 1 ? 1 : (int)gsz;
@@ -662,11 +652,8 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(vpd_clip_state* clip
     const double* partials = reinterpret_cast<const double*>(clip + 1);
     double a = 0.0;
     for (int i = threadIdx.x; i < used; i += 256) a += partials[i];
-    a = wave_sum_f64(a);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a;
-    __syncthreads();
+    const double sum = block_sum_f64(a, wsum);
     if (threadIdx.x != 0) return;
-    const double sum = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
     const bool bad = (__double_as_longlong(sum) & 0x7ff0000000000000LL) == 0x7ff0000000000000LL;      // inf or NaN
     const double scale = src ? (double)src->scale : (double)host_scale;
     const double norm = sqrt(sum) / scale;

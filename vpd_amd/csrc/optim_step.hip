@@ -1,0 +1,251 @@
+// Host side of the optimizer step (no kernel: those are optim.hip's): AdamW over a plan or over flat buffers, the loss scale and
+// the dynamic scaler's block, the non-finite search, the gradient norm of the clipping and the EMA of the weights.  Of the plan it
+// reads the pack tables, the arena and the weight-gradient scratch -- never the topology.
+#include <algorithm>
+#include <utility>
+#include <vector>
+
+#include "plan.h"
+
+namespace {
+
+// What the step entries of a plan refuse alike once their own pointers are known: a workspace that is not the bound one, a numel
+// that does not cover the plan's parameters, gradients off a 16-byte boundary (grads16 null: not looked at).  vpd_plan_grad_norm
+// takes the workspace refusal last (ws_first = false).
+int check_step_call(const vpd_plan* p, const void* workspace, long long numel, const float* grads16 = nullptr, bool ws_first = true) {
+    const char* unbound = "workspace not initialised with vpd_plan_init_workspace";
+    if (ws_first && p->bound_ws != workspace) return fail(unbound);
+    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
+    if (reinterpret_cast<size_t>(grads16) & 15) return fail("grads must be 16-byte aligned");
+    if (!ws_first && p->bound_ws != workspace) return fail(unbound);
+    return 0;
+}
+
+// One body per AdamW pair: `a` says where step and gradient factor come from (AdamArgs, kernels.h)
+int adamw_flat(float* params, const float* grads, float* adam_m, float* adam_v, long long numel, const AdamArgs& a, void* stream) {
+    if (numel % 4) return fail("numel must be a multiple of 4 (use vpd_plan_param_numel)");
+    if (!a.st && a.step < 1) return fail("step is 1-based");
+    LCHECK(vpd_launch_adamw(params, grads, adam_m, adam_v, (long)numel, a, (hipStream_t)stream));
+    return 0;
+}
+// (the stem repack runs either way: after a step the device block skipped it rewrites the values the arena already holds)
+int adamw_plan(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v, long long numel, const AdamArgs& a,
+               void* workspace, void* stream) {
+    if (check_step_call(p, workspace, numel)) return -1;
+    if (!a.st && a.step < 1) return fail("step is 1-based");
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* arena = plan_arena(p, workspace);
+    LCHECK(vpd_launch_adamw_pack(plan_descs(p, workspace), plan_bmap_adam(p, workspace), (int)p->bmap_adam.size() / 2, params, grads,
+                                 adam_m, adam_v, arena, a, s, p->grads_in_scratch ? plan_wg(p, workspace) : nullptr));
+    p->grads_in_scratch = false;      // consumed, applied or not (the scratch is rewritten by the next backward)
+    LCHECK(vpd_launch_pack_weights(plan_descs(p, workspace), (int)p->descs.size(), plan_bmap_pack(p, workspace),
+                                   p->nstem_pack_blocks, params, arena, s));
+    const long long done = p->nparam_padded;
+    if (numel > done)      // tensors the plan does not use (a motion head on a plan built without it)
+        LCHECK(vpd_launch_adamw(params + done, grads + done, adam_m + done, adam_v + done, (long)(numel - done), a, s));
+    return 0;
+}
+
+// The ranges a pass reads (empty ones are dropped), handed to `launch` in FiniteRanges batches of at most FR_MAX
+struct RangeBatcher {
+    std::vector<std::pair<const float*, long>> ranges;
+    void add(const float* x, long long n) {
+        if (n > 0) ranges.emplace_back(x, (long)n);
+    }
+    size_t nlaunch() const { return (ranges.size() + FR_MAX - 1) / FR_MAX; }
+    template <class Launch>
+    hipError_t each(Launch&& launch) const {
+        for (size_t at = 0; at < ranges.size(); at += FR_MAX) {
+            FiniteRanges r;
+            memset(&r, 0, sizeof r);
+            for (size_t i = at; i < ranges.size() && i < at + FR_MAX; ++i) {
+                r.ptr[r.count] = ranges[i].first;
+                r.n[r.count++] = ranges[i].second;
+            }
+            const hipError_t e = launch(r);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+};
+
+// Exactly what the optimizer step that follows will read: vpd_plan_adamw_step_scaled takes the conv weight gradients from the
+// scratch while grads_in_scratch (everything behind the stem's: the stem is always unpacked into the flat buffer) and the ranges
+// of the `stem == 2` descriptors from `grads`; otherwise all of `grads`.  The conv ranges of `grads` are STALE after a lazy
+// backward and are not looked at.
+RangeBatcher step_grad_ranges(const vpd_plan_t* p, const float* grads, long long numel, void* workspace) {
+    RangeBatcher b;
+    if (p->grads_in_scratch) {
+        const long long stem_end = (long long)p->stem.ntaps * p->stem.Co * p->stem.Kc;
+        b.add(plan_wg(p, workspace) + stem_end, p->wg_elems - stem_end);
+        for (const PackDesc& d : p->descs)
+            if (d.stem == 2) b.add(grads + d.src_off, d.numel);
+        b.add(grads + p->nparam_padded, numel - p->nparam_padded);
+    } else {
+        b.add(grads, numel);
+    }
+    return b;
+}
+
+// One launch over the ranges (more than FR_MAX of them: one launch per FR_MAX)
+int launch_check_finite(const RangeBatcher& b, vpd_scale_state* state, void* stream) {
+    LCHECK(b.each([&](const FiniteRanges& r) { return vpd_launch_check_finite(r, state, (hipStream_t)stream); }));
+    return 0;
+}
+
+int check_clip_args(double max_norm, const vpd_scale_state* src, float host_scale, const vpd_clip_state* clip) {
+    if (!clip) return fail("grad norm: null clip state");
+    if (reinterpret_cast<size_t>(clip) & 15) return fail("grad norm: clip state must be 16-byte aligned");
+    if (reinterpret_cast<size_t>(src) & 3) return fail("grad norm: scale state must be 4-byte aligned");
+    if (!(max_norm > 0.0)) return fail("grad norm: max_norm must be > 0 (+inf measures only)");
+    if (!src && (!(host_scale > 0.f) || !(host_scale < 3.0e38f))) return fail("grad norm: host_scale must be a positive finite number");
+    return 0;
+}
+// FR_MAX ranges per launch; launch l stores its blocks' sums in the slots behind launch l - 1's.  The grids depend on the ranges'
+// lengths alone, so the bits of the result do too.
+int launch_grad_norm(const RangeBatcher& b, double max_norm, vpd_scale_state* src, float host_scale, vpd_clip_state* clip,
+                     void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nlaunch = b.nlaunch();
+    if (nlaunch > CLIP_SLOTS) return fail("grad norm: too many ranges");
+    const int cap = nlaunch ? (int)std::min<size_t>(2048, CLIP_SLOTS / nlaunch) : 0;
+    double* partials = reinterpret_cast<double*>(clip + 1);
+    int used = 0;
+    LCHECK(b.each([&](const FiniteRanges& r) {
+        const int grid = vpd_grad_sqsum_grid(r.n, r.count, cap);
+        double* mine = partials + used;
+        used += grid;
+        return vpd_launch_grad_sqsum(r, grid, mine, s);
+    }));
+    LCHECK(vpd_launch_clip_finalize(clip, used, max_norm, src, host_scale, s));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int vpd_adamw_step(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
+                              double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                              void* stream) {
+    if (!params || !grads || !adam_m || !adam_v) return fail("null argument");
+    return adamw_flat(params, grads, adam_m, adam_v, numel, AdamArgs{lr, beta1, beta2, eps, weight_decay, step, 1.f, nullptr}, stream);
+}
+
+extern "C" int vpd_plan_adamw_step(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v,
+                                   long long numel, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, int step, void* workspace, void* stream) {
+    if (!p || !params || !grads || !adam_m || !adam_v || !workspace) return fail("null argument");
+    return adamw_plan(p, params, grads, adam_m, adam_v, numel,
+                      AdamArgs{lr, beta1, beta2, eps, weight_decay, step, 1.0f / p->loss_scale, nullptr}, workspace, stream);
+}
+
+// Loss scale of the NEXT backward passes of this plan and of vpd_plan_adamw_step (fp16 training; the reference's GradScaler,
+// models/util.py:55-57, train_vpd_model.py:105): vpd_backward multiplies d(loss)/d(pred) by `scale`, so every gradient it leaves --
+// flat buffer, weight-gradient scratch, what a reducer sums -- is scale x its value (no fp16 activation gradient underflows), and
+// vpd_plan_adamw_step multiplies the gradients it reads by 1 / scale.  1 (the default) is exact arithmetic: nothing changes.
+extern "C" int vpd_plan_set_loss_scale(vpd_plan_t* p, float scale) {
+    if (!p) return fail("null plan");
+    if (!(scale > 0.f) || !(scale < 3.0e38f)) return fail("loss scale must be a positive finite number");
+    p->loss_scale = scale;
+    return 0;
+}
+
+// ---- dynamic loss scaling: every decision is taken on the device, from the caller's vpd_scale_state block (include/vpd_hip.h) ----
+extern "C" int vpd_plan_set_scale_state(vpd_plan_t* p, const vpd_scale_state* state) {
+    if (!p) return fail("null plan");
+    if (reinterpret_cast<size_t>(state) & 3) return fail("scale state must be 4-byte aligned");
+    p->scale_state = state;
+    return 0;
+}
+
+extern "C" int vpd_op_check_finite(const float* x, long long n, vpd_scale_state* state, void* stream) {
+    if (!x || !state) return fail("null argument");
+    if (n < 0) return fail("negative length");
+    if (reinterpret_cast<size_t>(x) & 3) return fail("x must be 4-byte aligned");
+    RangeBatcher b;
+    b.add(x, n);
+    return launch_check_finite(b, state, stream);
+}
+
+extern "C" int vpd_plan_check_grads(vpd_plan_t* p, const float* grads, long long numel, vpd_scale_state* state, void* workspace,
+                                    void* stream) {
+    if (!p || !grads || !state || !workspace) return fail("null argument");
+    if (check_step_call(p, workspace, numel, grads)) return -1;
+    return launch_check_finite(step_grad_ranges(p, grads, numel, workspace), state, stream);
+}
+
+// ---- gradient-norm clipping: the norm pass over the same ranges, then the one-block kernel that writes the caller's vpd_clip_state ----
+extern "C" size_t vpd_clip_state_bytes(void) { return sizeof(vpd_clip_state) + (size_t)CLIP_SLOTS * sizeof(double); }
+
+extern "C" int vpd_op_grad_norm(const float* const* x, const long long* n, int count, double max_norm, const vpd_scale_state* src,
+                                float host_scale, vpd_clip_state* clip, void* stream) {
+    if (check_clip_args(max_norm, src, host_scale, clip)) return -1;
+    if (count < 0) return fail("grad norm: negative count");
+    if (count > 0 && (!x || !n)) return fail("grad norm: null argument");
+    RangeBatcher b;
+    for (int i = 0; i < count; ++i) {
+        if (!x[i]) return fail("grad norm: null range");
+        if (n[i] < 0) return fail("grad norm: negative length");
+        if (reinterpret_cast<size_t>(x[i]) & 3) return fail("grad norm: ranges must be 4-byte aligned");
+        b.add(x[i], n[i]);
+    }
+    return launch_grad_norm(b, max_norm, const_cast<vpd_scale_state*>(src), host_scale, clip, stream);
+}
+
+extern "C" int vpd_plan_grad_norm(vpd_plan_t* p, const float* grads, long long numel, double max_norm, vpd_scale_state* src,
+                                  float host_scale, vpd_clip_state* clip, void* workspace, void* stream) {
+    if (!p || !grads || !workspace) return fail("null argument");
+    if (check_clip_args(max_norm, src, host_scale, clip)) return -1;
+    if (check_step_call(p, workspace, numel, grads, false)) return -1;
+    return launch_grad_norm(step_grad_ranges(p, grads, numel, workspace), max_norm, src, host_scale, clip, stream);
+}
+
+extern "C" int vpd_adamw_step_scaled(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
+                                     double lr, double beta1, double beta2, double eps, double weight_decay,
+                                     const vpd_scale_state* state, void* stream) {
+    if (!params || !grads || !adam_m || !adam_v || !state) return fail("null argument");
+    return adamw_flat(params, grads, adam_m, adam_v, numel, AdamArgs{lr, beta1, beta2, eps, weight_decay, 1, 1.f, state}, stream);
+}
+
+// vpd_plan_adamw_step with the device block deciding
+extern "C" int vpd_plan_adamw_step_scaled(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v,
+                                          long long numel, double lr, double beta1, double beta2, double eps,
+                                          double weight_decay, const vpd_scale_state* state, void* workspace, void* stream) {
+    if (!p || !params || !grads || !adam_m || !adam_v || !state || !workspace) return fail("null argument");
+    return adamw_plan(p, params, grads, adam_m, adam_v, numel, AdamArgs{lr, beta1, beta2, eps, weight_decay, 1, 1.f, state},
+                      workspace, stream);
+}
+
+extern "C" int vpd_scale_state_update(vpd_scale_state* state, float growth, float backoff, int growth_interval, void* stream) {
+    if (!state) return fail("null argument");
+    if (!(growth >= 1.f) || !(growth < 3.0e38f)) return fail("growth factor must be finite and >= 1");
+    if (!(backoff > 0.f) || !(backoff <= 1.f)) return fail("backoff factor must be in (0, 1]");
+    if (growth_interval < 1) return fail("growth interval must be >= 1");
+    LCHECK(vpd_launch_scale_update(state, growth, backoff, growth_interval, (hipStream_t)stream));
+    return 0;
+}
+
+// Exponential moving average of the weights: every refusal is taken here, before anything is launched
+extern "C" int vpd_ema_update(const float* const* src, float* const* dst, const long long* n, int count, double decay,
+                              int warmup, int t, int t0, const vpd_scale_state* state, void* stream) {
+    if (count < 0 || count > EMA_MAX) return fail("vpd_ema_update: count outside 0..4");
+    if (!(decay >= 0.0 && decay <= 1.0)) return fail("vpd_ema_update: decay must be in [0, 1]");
+    if (t < 0 || t0 < 0) return fail("vpd_ema_update: t and t0 must not be negative");
+    if (reinterpret_cast<size_t>(state) & 3) return fail("vpd_ema_update: scale state must be 4-byte aligned");
+    if (count == 0) return 0;
+    if (!src || !dst || !n) return fail("vpd_ema_update: null argument");
+    EmaRanges r;
+    memset(&r, 0, sizeof r);
+    for (int i = 0; i < count; ++i) {
+        if (!src[i] || !dst[i]) return fail("vpd_ema_update: null argument");
+        if (n[i] < 0) return fail("vpd_ema_update: negative length");
+        if ((reinterpret_cast<size_t>(src[i]) | reinterpret_cast<size_t>(dst[i])) & 3)
+            return fail("vpd_ema_update: src and dst must be 4-byte aligned");
+        if (src[i] == dst[i]) return fail("vpd_ema_update: src and dst must differ");
+        r.src[i] = src[i];
+        r.dst[i] = dst[i];
+        r.n[i] = (long)n[i];
+    }
+    r.count = count;
+    LCHECK(vpd_launch_ema_update(r, decay, warmup != 0, t, t0, state, (hipStream_t)stream));
+    return 0;
+}

@@ -1,5 +1,6 @@
 // Private to plan.hip (the plan: topology, workspace layout, tables, query / setter entry points), step.hip (the passes that
-// launch on it) and ops.hip (the single-operator entry points).  Not part of the public ABI.
+// launch on it), optim_step.hip (the optimizer step's host side) and ops.hip (the single-operator entry points).  Not part of
+// the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -139,6 +140,16 @@ struct vpd_plan {
     std::vector<TimedLaunch> timed;
     std::vector<hipEvent_t> ev_pool;
 };
+
+// the tables and buffers of a plan inside its workspace `ws` (uploaded by vpd_plan_init_workspace)
+template <class T>
+inline T* plan_at(void* ws, size_t off) { return reinterpret_cast<T*>((char*)ws + off); }
+inline const PackDesc* plan_descs(const vpd_plan* p, void* ws) { return plan_at<const PackDesc>(ws, p->desc_off); }
+inline const int* plan_bmap_pack(const vpd_plan* p, void* ws) { return plan_at<const int>(ws, p->bmap_pack_off); }
+inline const int* plan_bmap_adam(const vpd_plan* p, void* ws) { return plan_at<const int>(ws, p->bmap_adam_off); }
+inline const int* plan_bmap_unpack(const vpd_plan* p, void* ws, int bucket) { return plan_at<const int>(ws, p->bmap_unpack_off[bucket]); }
+inline bf16_t* plan_arena(const vpd_plan* p, void* ws) { return plan_at<bf16_t>(ws, p->arena_off); }
+inline float* plan_wg(const vpd_plan* p, void* ws) { return plan_at<float>(ws, p->wg_off); }      // the weight-gradient scratch
 
 // min_n = 0 for the train-step entry points: a data-parallel rank whose shard of a ragged last batch is empty still
 // takes part in the step (zero loss, zero gradients, bucket events recorded) so that the collective stays matched

@@ -1,7 +1,7 @@
 // Network plan: owns the static description of the student (ResNet-18/34 BasicBlock or
-// ResNet-50/101 / wide Bottleneck encoder + optional motion MLP), the workspace layout and tables, and the query, setter,
-// workspace and optimizer entry points of include/vpd_hip.h.  The passes that launch on it: step.hip; the single-operator entry
-// points of the parity tests: ops.hip.
+// ResNet-50/101 / wide Bottleneck encoder + optional motion MLP), the workspace layout and tables, and the query, setter
+// and workspace entry points of include/vpd_hip.h.  The passes that launch on it: step.hip; the optimizer step's host side:
+// optim_step.hip; the single-operator entry points of the parity tests: ops.hip.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -589,269 +589,6 @@ extern "C" int vpd_plan_stage_views_jitter(vpd_plan_t* p, const unsigned char* r
     return 0;
 }
 
-extern "C" int vpd_adamw_step(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
-                              double lr, double beta1, double beta2, double eps, double weight_decay, int step,
-                              void* stream) {
-    if (!params || !grads || !adam_m || !adam_v) return fail("null argument");
-    if (numel % 4) return fail("numel must be a multiple of 4 (use vpd_plan_param_numel)");
-    if (step < 1) return fail("step is 1-based");
-    LCHECK(vpd_launch_adamw(params, grads, adam_m, adam_v, (long)numel, lr, beta1, beta2, eps, weight_decay, step,
-                            (hipStream_t)stream));
-    return 0;
-}
-
-extern "C" int vpd_plan_adamw_step(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v,
-                                   long long numel, double lr, double beta1, double beta2, double eps,
-                                   double weight_decay, int step, void* workspace, void* stream) {
-    if (!p || !params || !grads || !adam_m || !adam_v || !workspace) return fail("null argument");
-    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
-    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
-    if (step < 1) return fail("step is 1-based");
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    LCHECK(vpd_launch_adamw_pack(reinterpret_cast<const PackDesc*>(ws + p->desc_off),
-                                 reinterpret_cast<const int*>(ws + p->bmap_adam_off), (int)p->bmap_adam.size() / 2, params,
-                                 grads, adam_m, adam_v, reinterpret_cast<bf16_t*>(ws + p->arena_off), lr, beta1, beta2,
-                                 eps, weight_decay, step, s,
-                                 p->grads_in_scratch ? reinterpret_cast<const float*>(ws + p->wg_off) : nullptr,
-                                 1.0f / p->loss_scale));
-    p->grads_in_scratch = false;      // consumed (the scratch is rewritten by the next backward)
-    LCHECK(vpd_launch_pack_weights(reinterpret_cast<const PackDesc*>(ws + p->desc_off), (int)p->descs.size(),
-                                   reinterpret_cast<const int*>(ws + p->bmap_pack_off), p->nstem_pack_blocks, params,
-                                   reinterpret_cast<bf16_t*>(ws + p->arena_off), s));
-    if (numel > p->nparam_padded)      // tensors the plan does not use (a motion head on a plan built without it)
-        LCHECK(vpd_launch_adamw(params + p->nparam_padded, grads + p->nparam_padded, adam_m + p->nparam_padded,
-                                adam_v + p->nparam_padded, (long)(numel - p->nparam_padded), lr, beta1, beta2, eps,
-                                weight_decay, step, s, 1.0f / p->loss_scale));
-    return 0;
-}
-
-// Loss scale of the NEXT backward passes of this plan and of vpd_plan_adamw_step (fp16 training; the reference's GradScaler,
-// models/util.py:55-57, train_vpd_model.py:105): vpd_backward multiplies d(loss)/d(pred) by `scale`, so every gradient it leaves --
-// flat buffer, weight-gradient scratch, what a reducer sums -- is scale x its value (no fp16 activation gradient underflows), and
-// vpd_plan_adamw_step multiplies the gradients it reads by 1 / scale.  1 (the default) is exact arithmetic: nothing changes.
-extern "C" int vpd_plan_set_loss_scale(vpd_plan_t* p, float scale) {
-    if (!p) return fail("null plan");
-    if (!(scale > 0.f) || !(scale < 3.0e38f)) return fail("loss scale must be a positive finite number");
-    p->loss_scale = scale;
-    return 0;
-}
-
-// ---- dynamic loss scaling: every decision is taken on the device, from the caller's vpd_scale_state block (include/vpd_hip.h) ----
-extern "C" int vpd_plan_set_scale_state(vpd_plan_t* p, const vpd_scale_state* state) {
-    if (!p) return fail("null plan");
-    if (reinterpret_cast<size_t>(state) & 3) return fail("scale state must be 4-byte aligned");
-    p->scale_state = state;
-    return 0;
-}
-
-// One launch over the ranges (more than FR_MAX of them: one launch per FR_MAX)
-namespace {
-struct RangeList {
-    FiniteRanges r;
-    vpd_scale_state* st;
-    hipStream_t s;
-    RangeList(vpd_scale_state* st_, hipStream_t s_) : st(st_), s(s_) { memset(&r, 0, sizeof r); }
-    hipError_t flush() {
-        const hipError_t e = vpd_launch_check_finite(r, st, s);
-        r.count = 0;
-        return e;
-    }
-    hipError_t add(const float* x, long long n) {
-        if (n <= 0) return hipSuccess;
-        if (r.count == FR_MAX) {
-            const hipError_t e = flush();
-            if (e != hipSuccess) return e;
-        }
-        r.ptr[r.count] = x;
-        r.n[r.count++] = (long)n;
-        return hipSuccess;
-    }
-};
-}  // namespace
-
-extern "C" int vpd_op_check_finite(const float* x, long long n, vpd_scale_state* state, void* stream) {
-    if (!x || !state) return fail("null argument");
-    if (n < 0) return fail("negative length");
-    if (reinterpret_cast<size_t>(x) & 3) return fail("x must be 4-byte aligned");
-    RangeList rl(state, (hipStream_t)stream);
-    LCHECK(rl.add(x, n));
-    LCHECK(rl.flush());
-    return 0;
-}
-
-// Exactly what the optimizer step that follows will read: vpd_plan_adamw_step_scaled takes the conv weight gradients from the
-// scratch while grads_in_scratch (everything behind the stem's: the stem is always unpacked into the flat buffer) and the ranges
-// of the `stem == 2` descriptors from `grads`; otherwise all of `grads`.  The conv ranges of `grads` are STALE after a lazy
-// backward and are not looked at.
-namespace {
-template <class Add>
-hipError_t for_each_step_grad_range(const vpd_plan_t* p, const float* grads, long long numel, void* workspace, Add&& add) {
-    hipError_t e = hipSuccess;
-    if (p->grads_in_scratch) {
-        const long long stem_end = (long long)p->stem.ntaps * p->stem.Co * p->stem.Kc;
-        e = add(reinterpret_cast<const float*>((char*)workspace + p->wg_off) + stem_end, p->wg_elems - stem_end);
-        for (const PackDesc& d : p->descs)
-            if (d.stem == 2 && e == hipSuccess) e = add(grads + d.src_off, d.numel);
-        if (e == hipSuccess) e = add(grads + p->nparam_padded, numel - p->nparam_padded);
-    } else {
-        e = add(grads, numel);
-    }
-    return e;
-}
-}  // namespace
-
-extern "C" int vpd_plan_check_grads(vpd_plan_t* p, const float* grads, long long numel, vpd_scale_state* state, void* workspace,
-                                    void* stream) {
-    if (!p || !grads || !state || !workspace) return fail("null argument");
-    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
-    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
-    if (reinterpret_cast<size_t>(grads) & 15) return fail("grads must be 16-byte aligned");
-    RangeList rl(state, (hipStream_t)stream);
-    LCHECK(for_each_step_grad_range(p, grads, numel, workspace, [&](const float* x, long long n) { return rl.add(x, n); }));
-    LCHECK(rl.flush());
-    return 0;
-}
-
-// ---- gradient-norm clipping: the norm pass over the same ranges, then the one-block kernel that writes the caller's vpd_clip_state ----
-extern "C" size_t vpd_clip_state_bytes(void) { return sizeof(vpd_clip_state) + (size_t)CLIP_SLOTS * sizeof(double); }
-
-namespace {
-typedef std::vector<std::pair<const float*, long long>> NormRanges;
-int check_clip_args(double max_norm, const vpd_scale_state* src, float host_scale, const vpd_clip_state* clip) {
-    if (!clip) return fail("grad norm: null clip state");
-    if (reinterpret_cast<size_t>(clip) & 15) return fail("grad norm: clip state must be 16-byte aligned");
-    if (reinterpret_cast<size_t>(src) & 3) return fail("grad norm: scale state must be 4-byte aligned");
-    if (!(max_norm > 0.0)) return fail("grad norm: max_norm must be > 0 (+inf measures only)");
-    if (!src && (!(host_scale > 0.f) || !(host_scale < 3.0e38f))) return fail("grad norm: host_scale must be a positive finite number");
-    return 0;
-}
-// FR_MAX ranges per launch; launch l stores its blocks' sums in the slots behind launch l - 1's.  The grids depend on the ranges'
-// lengths alone, so the bits of the result do too.
-int launch_grad_norm(const NormRanges& ranges, double max_norm, vpd_scale_state* src, float host_scale, vpd_clip_state* clip,
-                     hipStream_t s) {
-    const size_t nlaunch = (ranges.size() + FR_MAX - 1) / FR_MAX;
-    if (nlaunch > CLIP_SLOTS) return fail("grad norm: too many ranges");
-    const int cap = nlaunch ? (int)std::min<size_t>(2048, CLIP_SLOTS / nlaunch) : 0;
-    double* partials = reinterpret_cast<double*>(clip + 1);
-    int used = 0;
-    for (size_t at = 0; at < ranges.size(); at += FR_MAX) {
-        FiniteRanges r;
-        memset(&r, 0, sizeof r);
-        for (size_t i = at; i < ranges.size() && i < at + FR_MAX; ++i) {
-            r.ptr[r.count] = ranges[i].first;
-            r.n[r.count++] = (long)ranges[i].second;
-        }
-        const int grid = vpd_grad_sqsum_grid(r, cap);
-        LCHECK(vpd_launch_grad_sqsum(r, grid, partials + used, s));
-        used += grid;
-    }
-    LCHECK(vpd_launch_clip_finalize(clip, used, max_norm, src, host_scale, s));
-    return 0;
-}
-}  // namespace
-
-extern "C" int vpd_op_grad_norm(const float* const* x, const long long* n, int count, double max_norm, const vpd_scale_state* src,
-                                float host_scale, vpd_clip_state* clip, void* stream) {
-    if (check_clip_args(max_norm, src, host_scale, clip)) return -1;
-    if (count < 0) return fail("grad norm: negative count");
-    if (count > 0 && (!x || !n)) return fail("grad norm: null argument");
-    NormRanges ranges;
-    for (int i = 0; i < count; ++i) {
-        if (!x[i]) return fail("grad norm: null range");
-        if (n[i] < 0) return fail("grad norm: negative length");
-        if (reinterpret_cast<size_t>(x[i]) & 3) return fail("grad norm: ranges must be 4-byte aligned");
-        if (n[i] > 0) ranges.emplace_back(x[i], n[i]);
-    }
-    return launch_grad_norm(ranges, max_norm, const_cast<vpd_scale_state*>(src), host_scale, clip, (hipStream_t)stream);
-}
-
-extern "C" int vpd_plan_grad_norm(vpd_plan_t* p, const float* grads, long long numel, double max_norm, vpd_scale_state* src,
-                                  float host_scale, vpd_clip_state* clip, void* workspace, void* stream) {
-    if (!p || !grads || !workspace) return fail("null argument");
-    if (check_clip_args(max_norm, src, host_scale, clip)) return -1;
-    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
-    if (reinterpret_cast<size_t>(grads) & 15) return fail("grads must be 16-byte aligned");
-    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
-    NormRanges ranges;
-    LCHECK(for_each_step_grad_range(p, grads, numel, workspace, [&](const float* x, long long n) {
-        if (n > 0) ranges.emplace_back(x, n);
-        return hipSuccess;
-    }));
-    return launch_grad_norm(ranges, max_norm, src, host_scale, clip, (hipStream_t)stream);
-}
-
-extern "C" int vpd_adamw_step_scaled(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
-                                     double lr, double beta1, double beta2, double eps, double weight_decay,
-                                     const vpd_scale_state* state, void* stream) {
-    if (!params || !grads || !adam_m || !adam_v || !state) return fail("null argument");
-    if (numel % 4) return fail("numel must be a multiple of 4 (use vpd_plan_param_numel)");
-    LCHECK(vpd_launch_adamw_scaled(params, grads, adam_m, adam_v, (long)numel, lr, beta1, beta2, eps, weight_decay, state,
-                                   (hipStream_t)stream));
-    return 0;
-}
-
-// vpd_plan_adamw_step with the device block deciding (the stem repack runs either way: after a skipped step it rewrites the
-// values the arena already holds)
-extern "C" int vpd_plan_adamw_step_scaled(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v,
-                                          long long numel, double lr, double beta1, double beta2, double eps,
-                                          double weight_decay, const vpd_scale_state* state, void* workspace, void* stream) {
-    if (!p || !params || !grads || !adam_m || !adam_v || !state || !workspace) return fail("null argument");
-    if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
-    if (numel % 4 || numel < p->nparam_padded) return fail("numel must be a multiple of 4 and cover the plan's parameters");
-    hipStream_t s = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    LCHECK(vpd_launch_adamw_pack_scaled(reinterpret_cast<const PackDesc*>(ws + p->desc_off),
-                                        reinterpret_cast<const int*>(ws + p->bmap_adam_off), (int)p->bmap_adam.size() / 2,
-                                        params, grads, adam_m, adam_v, reinterpret_cast<bf16_t*>(ws + p->arena_off), lr, beta1,
-                                        beta2, eps, weight_decay, state, s,
-                                        p->grads_in_scratch ? reinterpret_cast<const float*>(ws + p->wg_off) : nullptr));
-    p->grads_in_scratch = false;      // consumed, applied or not (the scratch is rewritten by the next backward)
-    LCHECK(vpd_launch_pack_weights(reinterpret_cast<const PackDesc*>(ws + p->desc_off), (int)p->descs.size(),
-                                   reinterpret_cast<const int*>(ws + p->bmap_pack_off), p->nstem_pack_blocks, params,
-                                   reinterpret_cast<bf16_t*>(ws + p->arena_off), s));
-    if (numel > p->nparam_padded)
-        LCHECK(vpd_launch_adamw_scaled(params + p->nparam_padded, grads + p->nparam_padded, adam_m + p->nparam_padded,
-                                       adam_v + p->nparam_padded, (long)(numel - p->nparam_padded), lr, beta1, beta2, eps,
-                                       weight_decay, state, s));
-    return 0;
-}
-
-extern "C" int vpd_scale_state_update(vpd_scale_state* state, float growth, float backoff, int growth_interval, void* stream) {
-    if (!state) return fail("null argument");
-    if (!(growth >= 1.f) || !(growth < 3.0e38f)) return fail("growth factor must be finite and >= 1");
-    if (!(backoff > 0.f) || !(backoff <= 1.f)) return fail("backoff factor must be in (0, 1]");
-    if (growth_interval < 1) return fail("growth interval must be >= 1");
-    LCHECK(vpd_launch_scale_update(state, growth, backoff, growth_interval, (hipStream_t)stream));
-    return 0;
-}
-
-// Exponential moving average of the weights: every refusal is taken here, before anything is launched
-extern "C" int vpd_ema_update(const float* const* src, float* const* dst, const long long* n, int count, double decay,
-                              int warmup, int t, int t0, const vpd_scale_state* state, void* stream) {
-    if (count < 0 || count > EMA_MAX) return fail("vpd_ema_update: count outside 0..4");
-    if (!(decay >= 0.0 && decay <= 1.0)) return fail("vpd_ema_update: decay must be in [0, 1]");
-    if (t < 0 || t0 < 0) return fail("vpd_ema_update: t and t0 must not be negative");
-    if (reinterpret_cast<size_t>(state) & 3) return fail("vpd_ema_update: scale state must be 4-byte aligned");
-    if (count == 0) return 0;
-    if (!src || !dst || !n) return fail("vpd_ema_update: null argument");
-    EmaRanges r;
-    memset(&r, 0, sizeof r);
-    for (int i = 0; i < count; ++i) {
-        if (!src[i] || !dst[i]) return fail("vpd_ema_update: null argument");
-        if (n[i] < 0) return fail("vpd_ema_update: negative length");
-        if ((reinterpret_cast<size_t>(src[i]) | reinterpret_cast<size_t>(dst[i])) & 3)
-            return fail("vpd_ema_update: src and dst must be 4-byte aligned");
-        if (src[i] == dst[i]) return fail("vpd_ema_update: src and dst must differ");
-        r.src[i] = src[i];
-        r.dst[i] = dst[i];
-        r.n[i] = (long)n[i];
-    }
-    r.count = count;
-    LCHECK(vpd_launch_ema_update(r, decay, warmup != 0, t, t0, state, (hipStream_t)stream));
-    return 0;
-}
-
 extern "C" int vpd_plan_set_lazy_grads(vpd_plan_t* p, int on) {
     if (!p) return fail("null plan");
     p->lazy_next = on != 0;
@@ -874,14 +611,12 @@ extern "C" int vpd_plan_materialize_grads(vpd_plan_t* p, float* grads, void* wor
     if (!p || !grads || !workspace) return fail("null argument");
     if (p->bound_ws != workspace) return fail("workspace not initialised with vpd_plan_init_workspace");
     if (!p->grads_in_scratch) return 0;
-    char* ws = (char*)workspace;
     for (int b = 0; b < 4; ++b) {
         const int nb = (int)p->bmap_unpack[b].size() / 2;
         const int skip = b == 3 ? p->nstem_unpack_blocks : 0;      // the stem was unpacked by the backward itself
         if (nb > skip)
-            LCHECK(vpd_launch_unpack_grads(reinterpret_cast<const PackDesc*>(ws + p->desc_off), (int)p->descs.size(),
-                                           reinterpret_cast<const int*>(ws + p->bmap_unpack_off[b]) + 2 * skip, nb - skip,
-                                           reinterpret_cast<const float*>(ws + p->wg_off), grads, (hipStream_t)stream));
+            LCHECK(vpd_launch_unpack_grads(plan_descs(p, workspace), (int)p->descs.size(), plan_bmap_unpack(p, workspace, b) + 2 * skip,
+                                           nb - skip, plan_wg(p, workspace), grads, (hipStream_t)stream));
     }
     p->grads_in_scratch = false;
     return 0;

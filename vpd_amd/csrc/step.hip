@@ -683,9 +683,8 @@ struct WgradQueue {
         if (c.data_only) nb = 0;      // nothing to hand over; the bucket's event is still recorded
         if (lazy) nb = b == 3 ? p->nstem_unpack_blocks : 0;      // the stem's row-tap packing is undone here either way
         if (nb > 0)
-            LCHECK(vpd_launch_unpack_grads(reinterpret_cast<const PackDesc*>(c.ws + p->desc_off), (int)p->descs.size(),
-                                           reinterpret_cast<const int*>(c.ws + p->bmap_unpack_off[b]), nb,
-                                           c.f32(p->wg_off), grads, c.s));
+            LCHECK(vpd_launch_unpack_grads(plan_descs(p, c.ws), (int)p->descs.size(), plan_bmap_unpack(p, c.ws, b), nb,
+                                           plan_wg(p, c.ws), grads, c.s));
         if (bucket_events && bucket_events[b]) LCHECK(hipEventRecord((hipEvent_t)bucket_events[b], c.s));
         return 0;
     }
@@ -920,9 +919,8 @@ extern "C" int vpd_pack_weights(vpd_plan_t* p, const float* params, const float*
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     Ctx c{p, ws, s, params, 1};
-    LCHECK(vpd_launch_pack_weights(reinterpret_cast<const PackDesc*>(ws + p->desc_off), (int)p->descs.size(),
-                                   reinterpret_cast<const int*>(ws + p->bmap_pack_off), (int)p->bmap_pack.size() / 2,
-                                   params, c.b16(p->arena_off), s));
+    LCHECK(vpd_launch_pack_weights(plan_descs(p, ws), (int)p->descs.size(), plan_bmap_pack(p, ws), (int)p->bmap_pack.size() / 2,
+                                   params, plan_arena(p, ws), s));
     if (bn_running)
         for (BnInfo* b : p->bns)
             LCHECK(vpd_launch_bn_fold(params + b->w_off, params + b->b_off, bn_running + b->rm_off,

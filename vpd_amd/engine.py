@@ -624,6 +624,23 @@ class StudentEngine:
         off = self.layout["decoder." + DECODER_PARAM_NAMES[0]][2]
         return (off + 3) & ~3
 
+    def _adamw_fused(self, pl, numel, hyper, state):
+        """vpd_plan_adamw_step through the plan of the last backward; state: the device block that decides, or None = the host step"""
+        bufs = (pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v), numel) + hyper
+        if state is not None:
+            self.check(self.L.vpd_plan_adamw_step_scaled(*bufs, _ptr(state), _ptr(pl.workspace), self._stream()),
+                       "vpd_plan_adamw_step_scaled")
+        else:
+            self.check(self.L.vpd_plan_adamw_step(*bufs, self.adam_step, _ptr(pl.workspace), self._stream()), "vpd_plan_adamw_step")
+
+    def _adamw_flat(self, numel, hyper, state):
+        """... over the leading `numel` elements of the (completed) flat buffers"""
+        bufs = (_ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v), numel) + hyper
+        if state is not None:
+            self.check(self.L.vpd_adamw_step_scaled(*bufs, _ptr(state), self._stream()), "vpd_adamw_step_scaled")
+        else:
+            self.check(self.L.vpd_adamw_step(*bufs, self.adam_step, self._stream()), "vpd_adamw_step")
+
     def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, numel=None):
         """numel: leading elements of the flat buffers to update (default: all).  An optimizer built without the motion head's
         parameters passes encoder_numel, as torch.optim.AdamW never touches tensors it was not given."""
@@ -633,63 +650,40 @@ class StudentEngine:
             self.adam_v = torch.zeros_like(self.params)
         st = self.scale_state      # a DynamicLossScaler's step in flight: search + AdamW decided on the device, no host count
         clip = self._clip          # enable_grad_clip(): the norm pass (instead of the search) + AdamW reading the clip block
-        if st is None and clip is None:
+        state = clip if clip is not None else st      # the device block AdamW and the EMA read (None: the host's step count)
+        if state is None:
             self.adam_step = self.adam_step + 1
+        # the train plan of the last backward: AdamW + refresh of its packed bf16 weights in one pass.  Not for an optimizer that
+        # was NOT given the motion head, behind a plan that trains it: the fused pass would update the head's tensors too
+        # (torch.optim.AdamW never touches tensors it was not given) -- plain flat update of the leading `numel` elements
+        # instead; the plan repacks its bf16 weights before its next forward
         pl = self._step_plan
-        if pl is not None and numel < pl.param_numel:
-            # an optimizer that was NOT given the motion head, behind a plan that trains it: the fused pass would update the
-            # head's tensors too (torch.optim.AdamW never touches tensors it was not given) -- plain flat update of the leading
-            # `numel` elements instead; the plan repacks its bf16 weights before its next forward
-            self.materialize_grads()
+        fused = (pl is not None and numel >= pl.param_numel and pl.packed_version == self.weights_version()
+                 and os.environ.get("VPD_FUSED_ADAMW", "1") != "0")
+        if not fused:
             pl = None
-        if pl is not None and pl.packed_version == self.weights_version() and os.environ.get("VPD_FUSED_ADAMW", "1") != "0":
-            # the train plan of the last backward: AdamW + refresh of its packed bf16 weights in one pass
-            if clip is not None:
-                n_ = max(numel, pl.param_numel)
-                self._clip_norm(pl, n_, st)
-                self.check(self.L.vpd_plan_adamw_step_scaled(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
-                                                             _ptr(self.adam_v), n_, lr, betas[0], betas[1], eps, weight_decay,
-                                                             _ptr(clip), _ptr(pl.workspace), self._stream()),
-                           "vpd_plan_adamw_step_scaled")
-            elif st is not None:
-                n_ = max(numel, pl.param_numel)
-                self.check(self.L.vpd_plan_check_grads(pl.handle, _ptr(self._grads), n_, _ptr(st), _ptr(pl.workspace),
-                                                       self._stream()), "vpd_plan_check_grads")
-                self.check(self.L.vpd_plan_adamw_step_scaled(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
-                                                             _ptr(self.adam_v), n_, lr, betas[0], betas[1], eps, weight_decay,
-                                                             _ptr(st), _ptr(pl.workspace), self._stream()),
-                           "vpd_plan_adamw_step_scaled")
-            else:
-                self.check(self.L.vpd_plan_adamw_step(pl.handle, _ptr(self.params), _ptr(self._grads), _ptr(self.adam_m),
-                                                      _ptr(self.adam_v), max(numel, pl.param_numel), lr, betas[0], betas[1], eps,
-                                                      weight_decay, self.adam_step, _ptr(pl.workspace), self._stream()),
-                           "vpd_plan_adamw_step")
-            self._hip_version += 1
-            pl.packed_version = self.weights_version()
-        elif clip is not None:
-            # (a static loss scale is taken out by the kernel, through the clip block: the buffer stays as the backward left it)
             self.materialize_grads()
-            self._clip_norm(None, numel, st)
-            self.check(self.L.vpd_adamw_step_scaled(_ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v),
-                                                    numel, lr, betas[0], betas[1], eps, weight_decay, _ptr(clip),
-                                                    self._stream()), "vpd_adamw_step_scaled")
-            self._hip_version += 1
+            if state is None:
+                self.unscale_grads_()      # (the flat kernel has no plan to ask for the loss scale; through a device block the
+                                           #  kernel takes it out, and the buffer stays as the backward left it)
+        if clip is not None:
+            self._clip_norm(pl, numel, st)
+        elif st is not None and fused:
+            self.check(self.L.vpd_plan_check_grads(pl.handle, _ptr(self._grads), numel, _ptr(st), _ptr(pl.workspace),
+                                                   self._stream()), "vpd_plan_check_grads")
         elif st is not None:
-            self.materialize_grads()
             self.check(self.L.vpd_op_check_finite(_ptr(self._grads), numel, _ptr(st), self._stream()), "vpd_op_check_finite")
-            self.check(self.L.vpd_adamw_step_scaled(_ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v),
-                                                    numel, lr, betas[0], betas[1], eps, weight_decay, _ptr(st),
-                                                    self._stream()), "vpd_adamw_step_scaled")
-            self._hip_version += 1
+        hyper = (lr, betas[0], betas[1], eps, weight_decay)
+        if fused:
+            self._adamw_fused(pl, numel, hyper, state)
         else:
-            self.unscale_grads_()      # (the flat kernel has no plan to ask for the loss scale)
-            self.check(self.L.vpd_adamw_step(_ptr(self.params), _ptr(self.grads), _ptr(self.adam_m), _ptr(self.adam_v),
-                                       numel, lr, betas[0], betas[1], eps, weight_decay, self.adam_step,
-                                       self._stream()), "vpd_adamw_step")
-            self._hip_version += 1
+            self._adamw_flat(numel, hyper, state)
+        self._hip_version += 1
+        if fused:
+            pl.packed_version = self.weights_version()
         if self._ema is not None:
             # after the AdamW, before the scaler's update(): `found` and `applied_steps` are still those of this step
-            self._ema_enqueue(clip if clip is not None else st)
+            self._ema_enqueue(state)
         if clip is not None and st is None:
             # no scaler's update() follows: the clip block counts its own steps (applied, or skipped on a non-finite norm)
             self.check(self.L.vpd_scale_state_update(_ptr(clip), 1.0, 1.0, 2 ** 31 - 1, self._stream()), "vpd_scale_state_update")
