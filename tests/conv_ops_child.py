@@ -58,7 +58,11 @@ RUNS = {
     "s2_w32-device":        ("s2_w32", {}, dict(kclass=4, ws1x1=1, bm=128, bn=128), dict(kclass=4, ws1x1=0, halo=0, stream1x1=0, bm=128, bn=64)),
     "s2_w8-device":         ("s2_w8", {}, dict(kclass=4, ws1x1=1, bm=128, bn=64), dict(kclass=4, ws1x1=0, halo=0, stream1x1=0, bm=64, bn=64)),
     "s2_w16_big-device":    ("s2_w16_big", {}, dict(kclass=4, ws1x1=1, bm=256, bn=128), dict(kclass=4, ws1x1=0, halo=0, stream1x1=0, bm=128, bn=128)),
-    "c3_w4-no_ws":          ("c3_w4", {"VPD_NO_WS": "1"}, dict(kclass=4, halo=1, bm=64, bn=128), None),
+    # with the ring GEMM switched off the stride-2 3x3 forward is the gather kernel's too (no other run reaches its forward
+    # epilogue): one ragged tile of 64 x 64
+    "s2_w8-ring_off":       ("s2_w8", {"VPD_CONV_S2_WS": "0"}, dict(kclass=4, ws1x1=0, halo=0, stream1x1=0, bm=64, bn=64),
+                             dict(kclass=4, ws1x1=0, halo=0, stream1x1=0, bm=64, bn=64)),
+    "c3_w4-no_ws":          ("c3_w4", {"VPD_NO_WS": "1"},dict(kclass=4, halo=1, bm=64, bn=128), None),
     "c0_w16-no_ws":         ("c0_w16", {"VPD_NO_WS": "1"}, dict(kclass=4, halo=1, bm=128, bn=64), None),
     "c1_w16-no_ws":         ("c1_w16", {"VPD_NO_WS": "1"}, dict(kclass=4, halo=1, bm=128, bn=128), None),
     # (its data gradient, 128 -> 512 channels on 51,200 pixels, is conv1x1_stream_kernel's: tests/test_ops_gpu.py has that kernel's cases)

@@ -1,17 +1,19 @@
-// Implicit-GEMM convolution on bf16 MFMA (gfx950).  One kernel serves the
-// forward convolutions (7x7 s2 stem as 7 row-taps of 64 contiguous values,
-// 3x3 s1/s2, 1x1 s2) and the data-gradient convolutions (3x3 s1 as a flipped
-// conv; stride-2 convs as one launch per output parity class).
-//
-// GEMM view: rows = output channels (Co), cols = output pixels (M), K = taps x Kc.
-// The MFMA "A" operand is the weight tile, the "B" operand the gathered pixel
-// tile, so each lane ends up with 4 consecutive channels of one pixel and the
-// NHWC store is 8 bytes per lane.
-//
-// Pipeline per 64-deep K-step: global->register prefetch of step s+1 is issued
-// before the MFMAs of step s, written to the other LDS buffer after them; one
-// barrier per step.  LDS tiles are [rows][64] bf16 (128-B rows) with the 16-B
-// chunk index XOR-ed by (row & 7): conflict-free for ds_read_b128 fragments.
+// Convolution kernels on 16x16x32 MFMA (gfx950) and their launcher.  GEMM view of every kernel here: rows = output channels
+// (Co), columns = output pixels (M), K = taps x input channels; the MFMA "A" operand is the weight tile, the "B" operand the pixel
+// tile, so a lane ends up with 4 consecutive channels of one pixel and the NHWC store is 8 bytes per lane.  LDS tiles are
+// [rows][64] elements (128-byte rows) with the 16-byte chunk index XOR-ed by (row & 7): conflict-free ds_read_b128 fragments.
+// The epilogues are conv_epilogue.h's.  What the file holds, in order:
+//   conv_igemm_kernel              gather kernel: any tap set, stride and sub-grid; the merged parity classes of a stride-2 data
+//                                  gradient (blockIdx.z), a second convolution (alt_*) or a second input (x2) in one launch
+//   conv3x3_halo_kernel            3x3 stride 1 on an LDS-resident halo, four waves (legacy: VPD_NO_WS=1, odd channel counts)
+//   conv3x3_ws_kernel              the same warp-specialised: loader waves + MFMA waves, weight ring (VPD_PWS=0; the 8-wave tile)
+//   conv3x3_c64_persistent_kernel, conv3x3_c64x2_persistent_kernel, conv_stem_persistent_kernel
+//                                  resident weights, persistent blocks: layer1 (training / inference) and the 7x7 stem
+//   launch_pws                     conv3x3_pws_kernel (conv_pws.h; its compile-time-geometry instantiations: conv_pws_geo.hip)
+//   conv1x1_ws_kernel              ring GEMM: deep 1x1, the stride-2 3x3 forward, merged stride-2 data gradients
+//   vpd_conv_kernel_class, vpd_conv_dispatch, vpd_launch_conv
+//                                  every decision of the launcher in one place, then the map to template instantiations
+//                                  (the streaming 1x1 kernels are conv_stream.hip's)
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -22,6 +24,59 @@
 #include "conv_epilogue.h"
 #include "kernels.h"
 
+// ---------------------------------------------------------------------------
+// Shared pieces of the gather kernel and the ring GEMM
+// ---------------------------------------------------------------------------
+// Second convolution of the launch (ConvParams::alt_*: a BasicBlock's 1x1 down-sampling branch beside its stride-2 3x3): the
+// blocks with blockIdx.y >= alt_y0 see it as THE convolution
+static __device__ __forceinline__ void conv_take_alt(ConvParams& p, const ConvParams& p0, int& by) {
+    if (p0.alt_w && by >= p0.alt_y0) {
+        by -= p0.alt_y0;
+        p.w = p0.alt_w; p.y = p0.alt_y; p.stats = p0.alt_stats; p.taps = p0.alt_taps;
+        p.ep_scale = p0.alt_ep_scale; p.ep_shift = p0.alt_ep_shift; p.ep_relu = p0.alt_ep_relu; p.res = nullptr;
+    }
+}
+
+// Element offset into x of the input pixel under output pixel m of the class's sub-grid (clamped to the last one), tap (0, 0)
+static __device__ __forceinline__ int conv_pixel_base(const ConvParams& p, const ConvGeo& geo, int m) {
+    const int HW = geo.Hs * geo.Ws;
+    m = m < geo.M ? m : geo.M - 1;
+    const int b = m / HW;
+    const int r = m - b * HW;
+    const int yy = r / geo.Ws;
+    const int xx = r - yy * geo.Ws;
+    return ((b * p.xHp + yy * p.istr) * p.xWp + xx * p.istr) * p.xC;
+}
+
+// K-step s = (tap s / kchunks, 64-channel chunk s % kchunks) of the nsteps1 steps of the taps; behind them, in class 0 only, the
+// chunks of the second input tensor x2 (same pixels, first tap's offset) with its own weights w2, one slice of Kc2 channels
+struct ConvKStep {
+    const bf16_t* x;      // input tensor and the element offset of the step's tap and chunk from a pixel base
+    int xoff;
+    const bf16_t* w;      // weight tensor, slice [Co][wK] number wsl, chunk cc
+    int wsl, wK, cc;
+};
+static __device__ __forceinline__ ConvKStep conv_kstep_decode(const ConvParams& p, const TapSet& taps, int s, int nsteps1, int kchunks) {
+    ConvKStep k;
+    if (s < nsteps1) {
+        const int tap = s / kchunks;
+        k.cc = s - tap * kchunks;
+        const int ir = tap / taps.nc;
+        const int ic = tap - ir * taps.nc;
+        k.x = p.x; k.w = p.w; k.wK = p.Kc;
+        k.xoff = ((taps.dy0 + ir * taps.dys) * p.xWp + (taps.dx0 + ic * taps.dxs)) * p.xC + k.cc * 64;
+        k.wsl = taps.w0 + ir * taps.wrs + ic * taps.wcs;
+    } else {
+        k.cc = s - nsteps1;
+        k.x = p.x2; k.w = p.w2; k.wK = p.Kc2;
+        k.xoff = (taps.dy0 * p.xWp + taps.dx0) * p.xC + k.cc * 64;
+        k.wsl = 0;
+    }
+    return k;
+}
+
+// Implicit-GEMM gather kernel: four waves, global -> register prefetch of step s + 1 issued before the MFMAs of step s and written
+// to the other LDS buffer after them, one barrier per step, two blocks per CU
 template <int BM, int BN, int WM, int WN, int EPM>
 __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0) {
     static_assert(WM * WN == 4, "4 waves");
@@ -42,14 +97,9 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0)
     const int wm = wave % WM;
     const int wn = wave / WM;
     const int mtile = blockIdx.x;
-    // second convolution of the launch (ConvParams::alt_*): these blocks see it as THE convolution
     ConvParams p = p0;
     int by = blockIdx.y;
-    if (p0.alt_w && by >= p0.alt_y0) {
-        by -= p0.alt_y0;
-        p.w = p0.alt_w; p.y = p0.alt_y; p.stats = p0.alt_stats; p.taps = p0.alt_taps;
-        p.ep_scale = p0.alt_ep_scale; p.ep_shift = p0.alt_ep_shift; p.ep_relu = p0.alt_ep_relu; p.res = nullptr;
-    }
+    conv_take_alt(p, p0, by);
     const int n0 = by * BN;
     const int m0 = mtile * BM;
     // parity class of a merged stride-2 data gradient (blockIdx.z); class 0 lives in the top-level fields
@@ -71,49 +121,22 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0)
 
     // per-thread gather bases (element offsets into x) for its PR pixel rows
     int pixbase[PR];
-    const int HW = geo.Hs * geo.Ws;
 #pragma unroll
-    for (int i = 0; i < PR; ++i) {
-        int m = m0 + row0 + 32 * i;
-        m = m < geo.M ? m : geo.M - 1;
-        const int b = m / HW;
-        const int r = m - b * HW;
-        const int yy = r / geo.Ws;
-        const int xx = r - yy * geo.Ws;
-        pixbase[i] = ((b * p.xHp + yy * p.istr) * p.xWp + xx * p.istr) * p.xC + piece * 8;
-    }
+    for (int i = 0; i < PR; ++i) pixbase[i] = conv_pixel_base(p, geo, m0 + row0 + 32 * i) + piece * 8;
     const int kchunks = p.Kc >> 6;
     const int nsteps1 = taps.nr * taps.nc * kchunks;
-    // class 0 only: extra K-steps from the second input tensor (same pixels, first tap's offset, its own weights)
     const int nsteps = nsteps1 + ((p.x2 && cls == 0) ? (p.Kc2 >> 6) : 0);
 
     u32x4 rp[PR], rw[WR];
     auto load_step = [&](int s) __attribute__((always_inline)) {
-        const bf16_t* xs = p.x;
-        const bf16_t* wb;
-        int toff, wstride;
-        if (s < nsteps1) {
-            const int tap = s / kchunks;
-            const int cc = s - tap * kchunks;
-            const int ir = tap / taps.nc;
-            const int ic = tap - ir * taps.nc;
-            toff = ((taps.dy0 + ir * taps.dys) * p.xWp + (taps.dx0 + ic * taps.dxs)) * p.xC + cc * 64;
-            const int wsl = taps.w0 + ir * taps.wrs + ic * taps.wcs;
-            wb = p.w + ((size_t)wsl * p.Co + n0) * p.Kc + cc * 64 + piece * 8;
-            wstride = p.Kc;
-        } else {
-            const int cc = s - nsteps1;
-            xs = p.x2;
-            toff = (taps.dy0 * p.xWp + taps.dx0) * p.xC + cc * 64;
-            wb = p.w2 + (size_t)n0 * p.Kc2 + cc * 64 + piece * 8;
-            wstride = p.Kc2;
-        }
+        const ConvKStep k = conv_kstep_decode(p, taps, s, nsteps1, kchunks);
+        const bf16_t* wb = k.w + ((size_t)k.wsl * p.Co + n0) * k.wK + k.cc * 64 + piece * 8;
 #pragma unroll
         for (int i = 0; i < PR; ++i)
-            rp[i] = *reinterpret_cast<const u32x4*>(xs + pixbase[i] + toff);
+            rp[i] = *reinterpret_cast<const u32x4*>(k.x + pixbase[i] + k.xoff);
 #pragma unroll
         for (int i = 0; i < WR; ++i)
-            rw[i] = *reinterpret_cast<const u32x4*>(wb + (size_t)(row0 + 32 * i) * wstride);
+            rw[i] = *reinterpret_cast<const u32x4*>(wb + (size_t)(row0 + 32 * i) * k.wK);
     };
     auto store_step = [&](int buf) __attribute__((always_inline)) {
         bf16_t* dP = sP + buf * BM * 64;
@@ -189,6 +212,64 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvParams p0)
 // ---------------------------------------------------------------------------
 #include "conv_pws.h"
 
+// Shared by this kernel and conv3x3_ws_kernel below: halo origin, fragment rows, the step -> tap / weight-slice decode, the weight tile
+// First padded pixel of tile mtile's halo in the input tensor (tiles of g.TR whole image rows; global output row = b * H + y)
+static __device__ __forceinline__ int halo_tile_gp0(int mtile, const HaloGeom& g, int H, int Wp) {
+    const int gr0 = mtile * g.TR;
+    int prow0;
+    if (g.multi) prow0 = (gr0 / H) * (H + 2);
+    else { const int b = gr0 / H; prow0 = b * (H + 2) + (gr0 - b * H); }
+    return prow0 * Wp;
+}
+
+// Halo row of this lane's pixel in each of its wave's MI fragments: tile pixels m0 + 16 b, m0 the lane's pixel in fragment 0 (the
+// tap's offset is added per step)
+template <int MI>
+static __device__ __forceinline__ void halo_frag_rows(const HaloGeom& g, int m0, int W, int H, int (&hbase)[MI]) {
+    const int Wp = W + 2;
+#pragma unroll
+    for (int b = 0; b < MI; ++b) {
+        const int m = m0 + b * 16;
+        const int lr = m / W;
+        const int xx = m - lr * W;
+        const int hrow = g.multi ? (lr / H) * (H + 2) + (lr % H) : lr;
+        hbase[b] = hrow * Wp + xx;
+    }
+}
+
+// Halo-row offset of tap `tap` (row-major in the 3x3 window)
+static __device__ __forceinline__ int halo_tap_offset(const TapSet& t, int tap, int Wp) {
+    const int ir = tap / 3, ic = tap - ir * 3;
+    return (t.dy0 + ir * t.dys) * Wp + (t.dx0 + ic * t.dxs);
+}
+
+// K-step `step` of the tap-streaming 3x3 kernels = (chunk step / 9, tap step % 9): returns the tap's weight slice
+static __device__ __forceinline__ int conv3x3_wslice(const TapSet& t, int step, int& cc) {
+    cc = step / 9;
+    const int tap = step - cc * 9;
+    const int ir = tap / 3, ic = tap - ir * 3;
+    return t.w0 + ir * t.wrs + ic * t.wcs;
+}
+// Chunk rotation (HaloGeom::rot, as conv3x3_pws_kernel: bit-identical results): logical chunk cc is chunk (cc + crot) % nchunks
+static __device__ __forceinline__ int conv3x3_chunk_rot(int cc, int crot, int nchunks) {
+    return cc + crot >= nchunks ? cc + crot - nchunks : cc + crot;
+}
+
+// Weight tile [BN rows][64 channels] of slice wsl, chunk cce, into dst by LDS-DMA, swizzle applied on the source address: W_PER =
+// BN / 32 instructions per wave, instruction i brings rows drow + 32 i .. + 7 (drow: 8 x the wave's number among the four that
+// issue), this lane row nrow + 32 i of them
+template <int W_PER>
+static __device__ __forceinline__ void conv_wtile_issue(const ConvParams& p, int wsl, int n0, int cce, bf16_t* dst, int drow, int nrow, int piece) {
+    const int Ci = p.Kc;
+    const bf16_t* wbp = p.w + ((size_t)wsl * p.Co + n0) * Ci + cce * 64;
+#pragma unroll
+    for (int i = 0; i < W_PER; ++i) {
+        const int n = i * 32 + nrow;
+        const bf16_t* src = wbp + (size_t)n * Ci + ((piece ^ (n & 7)) << 3);
+        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + (i * 32 + drow) * 64), 16, 0, 0);
+    }
+}
+
 template <int BM, int BN, int HROWS, bool HALO2>
 __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvParams p, const HaloGeom g) {
     constexpr int WM = 2, WN = 2;
@@ -213,23 +294,9 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvParams p, c
     const int W = p.Ws, H = p.Hs, Wp = W + 2;
     const int Ci = p.Kc;
 
-    // first padded pixel of the halo in the input tensor
-    const int gr0 = mtile * g.TR;                                 // global output row = b*H + y
-    int prow0;
-    if (g.multi) prow0 = (gr0 / H) * (H + 2);
-    else { const int b = gr0 / H; prow0 = b * (H + 2) + (gr0 - b * H); }
-    const int gp0 = prow0 * Wp;
-
-    // per-lane halo row of each pixel fragment (tap offset added per step)
+    const int gp0 = halo_tile_gp0(mtile, g, H, Wp);
     int hbase[MI];
-#pragma unroll
-    for (int b = 0; b < MI; ++b) {
-        const int m = wm * WTM + b * 16 + fr;
-        const int lr = m / W;
-        const int xx = m - lr * W;
-        const int hrow = g.multi ? (lr / H) * (H + 2) + (lr % H) : lr;
-        hbase[b] = hrow * Wp + xx;
-    }
+    halo_frag_rows(g, wm * WTM + fr, W, H, hbase);
 
     const int piece = tid & 7;
     const int srow = tid >> 3;                                    // 0..31: row within a 32-row pass
@@ -245,18 +312,9 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvParams p, c
         }
     };
     auto issue_w = [&](int step, int wb) __attribute__((always_inline)) {
-        const int cc = step / 9;
-        const int tap = step - cc * 9;
-        const int ir = tap / 3, ic = tap - ir * 3;
-        const int wsl = p.taps.w0 + ir * p.taps.wrs + ic * p.taps.wcs;
-        bf16_t* dst = sW + wb * BN * 64;
-        const bf16_t* wbp = p.w + ((size_t)wsl * p.Co + n0) * Ci + cc * 64;
-#pragma unroll
-        for (int i = 0; i < BN / 32; ++i) {
-            const int n = i * 32 + srow;
-            const bf16_t* src = wbp + (size_t)n * Ci + ((piece ^ (n & 7)) << 3);
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dst + (i * 32 + wave * 8) * 64), 16, 0, 0);
-        }
+        int cc;
+        const int wsl = conv3x3_wslice(p.taps, step, cc);
+        conv_wtile_issue<BN / 32>(p, wsl, n0, cc, sW + wb * BN * 64, wave * 8, srow, piece);
     };
 
     f32x4 acc[NI][MI];
@@ -279,8 +337,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvParams p, c
             if (HALO2 && tap == 0 && cc + 1 < nchunks && !VPD_ABL(p, 4)) issue_halo(cc + 1, (cc + 1) & 1);
             if (VPD_ABL(p, 2)) continue;
 
-            const int ir = tap / 3, ic = tap - ir * 3;
-            const int toff = (p.taps.dy0 + ir * p.taps.dys) * Wp + (p.taps.dx0 + ic * p.taps.dxs);
+            const int toff = halo_tap_offset(p.taps, tap, Wp);
             const bf16_t* cW = sW + (step & 1) * BN * 64;
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
@@ -367,34 +424,20 @@ __global__ __launch_bounds__((NMW + 4) * 64, WPS) void conv3x3_ws_kernel(const C
         const int lw = wave - NMW;
         const int piece = lane & 7;
         const int lrow = lane >> 3;
-        const int gr0 = mtile * g.TR;
-        int prow0;
-        if (g.multi) prow0 = (gr0 / H) * (H + 2);
-        else { const int b = gr0 / H; prow0 = b * (H + 2) + (gr0 - b * H); }
-        const int gp0 = prow0 * Wp;
-        // chunk rotation (HaloGeom::rot, as conv3x3_pws_kernel: bit-identical results): logical chunk cc is chunk (cc + tile) % nchunks
-        const int crot = g.rot ? mtile % nchunks : 0;
+        const int gp0 = halo_tile_gp0(mtile, g, H, Wp);
+        const int crot = g.rot ? mtile % nchunks : 0;             // chunk rotation by the tile index
         auto halo_instr = [&](int cc, int k) __attribute__((always_inline)) {      // pass k of chunk cc
             const int hp = (lw + 4 * k) * 8 + lrow;
             int gp = gp0 + hp;
             gp = gp < g.total_pix ? gp : g.total_pix - 1;
-            const int cce = cc + crot >= nchunks ? cc + crot - nchunks : cc + crot;
+            const int cce = conv3x3_chunk_rot(cc, crot, nchunks);
             const bf16_t* src = p.x + (size_t)gp * Ci + cce * 64 + ((piece ^ (hp & 7)) << 3);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sH + (cc & (HB - 1)) * HBUF + (lw + 4 * k) * 8 * 64), 16, 0, 0);
         };
         auto issue_w = [&](int step, int stage) __attribute__((always_inline)) {
-            const int cc = step / 9;
-            const int tap = step - cc * 9;
-            const int ir = tap / 3, ic = tap - ir * 3;
-            const int wsl = p.taps.w0 + ir * p.taps.wrs + ic * p.taps.wcs;
-            const int cce = cc + crot >= nchunks ? cc + crot - nchunks : cc + crot;
-            const bf16_t* wbp = p.w + ((size_t)wsl * p.Co + n0) * Ci + cce * 64;
-#pragma unroll
-            for (int i = 0; i < W_PER; ++i) {
-                const int n = (lw + 4 * i) * 8 + lrow;
-                const bf16_t* src = wbp + (size_t)n * Ci + ((piece ^ (n & 7)) << 3);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(sW + stage * WSTAGE + (lw + 4 * i) * 8 * 64), 16, 0, 0);
-            }
+            int cc;
+            const int wsl = conv3x3_wslice(p.taps, step, cc);
+            conv_wtile_issue<W_PER>(p, wsl, n0, conv3x3_chunk_rot(cc, crot, nchunks), sW + stage * WSTAGE, lw * 8, lw * 8 + lrow, piece);
         };
 #pragma unroll
         for (int k = 0; k < HPASS; ++k) halo_instr(0, k);
@@ -441,14 +484,7 @@ __global__ __launch_bounds__((NMW + 4) * 64, WPS) void conv3x3_ws_kernel(const C
     const int fr = lane & 15;
     const int fq = lane >> 4;
     int hbase[MI];
-#pragma unroll
-    for (int b = 0; b < MI; ++b) {
-        const int m = wm * WTM + b * 16 + fr;
-        const int lr = m / W;
-        const int xx = m - lr * W;
-        const int hrow = g.multi ? (lr / H) * (H + 2) + (lr % H) : lr;
-        hbase[b] = hrow * Wp + xx;
-    }
+    halo_frag_rows(g, wm * WTM + fr, W, H, hbase);
     f32x4 acc[NI][MI];
     zero_acc(acc);
 
@@ -456,8 +492,7 @@ __global__ __launch_bounds__((NMW + 4) * 64, WPS) void conv3x3_ws_kernel(const C
     auto tap_body = [&](int tap, const bf16_t* cH) __attribute__((always_inline)) {
         __builtin_amdgcn_s_barrier();                             // READY_s
         if (VPD_ABL(p, 2)) return;
-        const int ir = tap / 3, ic = tap - ir * 3;
-        const int toff = (p.taps.dy0 + ir * p.taps.dys) * Wp + (p.taps.dx0 + ic * p.taps.dxs);
+        const int toff = halo_tap_offset(p.taps, tap, Wp);
         const bf16_t* cW = sW + (s % NS) * WSTAGE;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -1220,8 +1255,7 @@ static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t
         fprintf(stderr, "%llu cycles\n", emax - lo);
     } };
 #endif
-    bool geo_launched = false;
-    geo_launched = vpd_switches().pws_geo && vpd_launch_pws_geo(BM, BN, HROWS, NS, NMW, q, g, sg, grid, block, lds, stream);
+    const bool geo_launched = vpd_switches().pws_geo && vpd_launch_pws_geo(BM, BN, HROWS, NS, NMW, q, g, sg, grid, block, lds, stream);
     if (!geo_launched) switch (conv_ep_mode(q)) {
         case 0: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 0, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
         case 1: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 1, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
@@ -1238,8 +1272,9 @@ static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t
     return hipGetLastError();
 }
 
+// NS: weight-ring depth (four stages: profiles/r02_ring_depth.txt)
 template <int BM, int BN, int HROWS, int HB, int WPS, int NS>
-static hipError_t launch_ws_ns(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
+static hipError_t launch_ws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
     dim3 grid((p.M + BM - 1) / BM, p.Co / BN);
     const size_t lds = ((size_t)HB * HROWS + NS * BN) * 64 * sizeof(bf16_t);
     static_assert(((size_t)HB * HROWS + NS * BN) * 64 * sizeof(bf16_t) <= 160 * 1024, "LDS");
@@ -1272,11 +1307,6 @@ static hipError_t launch_ws_ns(const ConvParams& p, const HaloGeom& g, hipStream
     }
     return hipGetLastError();
 }
-// NS: weight-ring depth (four stages: profiles/r02_ring_depth.txt)
-template <int BM, int BN, int HROWS, int HB, int WPS, int NS>
-static hipError_t launch_ws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
-    return launch_ws_ns<BM, BN, HROWS, HB, WPS, NS>(p, g, stream);
-}
 
 // ---------------------------------------------------------------------------
 // 1x1 stride-1 convolution (the Bottleneck students' conv1 / conv3, forward and data gradient) as a warp-specialised ring
@@ -1290,15 +1320,9 @@ static hipError_t launch_ws(const ConvParams& p, const HaloGeom& g, hipStream_t 
 // ---------------------------------------------------------------------------
 template <int BM, int BN, int NS, int EPM>
 __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p0) {
-    // second convolution of the launch (ConvParams::alt_*: a BasicBlock's 1x1 down-sampling branch beside its stride-2 3x3):
-    // the blocks with blockIdx.y >= alt_y0 see it as THE convolution
     ConvParams p = p0;
     int by = blockIdx.y;
-    if (p0.alt_w && by >= p0.alt_y0) {
-        by -= p0.alt_y0;
-        p.w = p0.alt_w; p.y = p0.alt_y; p.stats = p0.alt_stats; p.taps = p0.alt_taps;
-        p.ep_scale = p0.alt_ep_scale; p.ep_shift = p0.alt_ep_shift; p.ep_relu = p0.alt_ep_relu; p.res = nullptr;
-    }
+    conv_take_alt(p, p0, by);
     constexpr int WN = BN / 64;
     constexpr int WM = 4 / WN;
     constexpr int WTM = BM / WM;
@@ -1328,26 +1352,18 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p0) {
     const int m0 = mtile * BM;
     if (m0 >= geo.M) return;                                      // (a smaller class: whole block, before any barrier)
     const int kchunks = p.Kc >> 6;
-    const int nsteps1 = taps.nr * taps.nc * kchunks;              // K-step s = (tap s / kchunks, 64-channel chunk s % kchunks)
-    // class 0 only: extra K-steps from the second input tensor (same pixels, first tap's offset, its own weights)
+    const int nsteps1 = taps.nr * taps.nc * kchunks;
     const int nsteps = nsteps1 + ((p.x2 && cls == 0) ? (p.Kc2 >> 6) : 0);
 
     if (wave >= 4) {
         const int lw = wave - 4;
         const int piece = lane & 7;
         const int lrow = lane >> 3;
-        const int HW = geo.Hs * geo.Ws;
         int abase[A_PER], wbase[W_PER];
 #pragma unroll
         for (int i = 0; i < A_PER; ++i) {
             const int r = (lw + 4 * i) * 8 + lrow;
-            int m = m0 + r;
-            m = m < geo.M ? m : geo.M - 1;
-            const int b = m / HW;
-            const int rr = m - b * HW;
-            const int yy = rr / geo.Ws;
-            const int xx = rr - yy * geo.Ws;
-            abase[i] = ((b * p.xHp + yy * p.istr) * p.xWp + xx * p.istr) * p.xC + ((piece ^ (r & 7)) << 3);
+            abase[i] = conv_pixel_base(p, geo, m0 + r) + ((piece ^ (r & 7)) << 3);
         }
 #pragma unroll
         for (int i = 0; i < W_PER; ++i) {
@@ -1356,28 +1372,14 @@ __global__ __launch_bounds__(512) void conv1x1_ws_kernel(const ConvParams p0) {
         }
         auto issue = [&](int s) __attribute__((always_inline)) {
             bf16_t* st = ring + (s % NS) * STAGE;
-            const bf16_t* xs = p.x;
-            const bf16_t* wsrc = p.w;
-            int aoff, woff;
-            if (s < nsteps1) {
-                const int tap = s / kchunks;
-                const int cc = s - tap * kchunks;
-                const int ir = tap / taps.nc;
-                const int ic = tap - ir * taps.nc;
-                aoff = ((taps.dy0 + ir * taps.dys) * p.xWp + (taps.dx0 + ic * taps.dxs)) * p.xC + cc * 64;
-                woff = (taps.w0 + ir * taps.wrs + ic * taps.wcs) * p.Co * p.Kc + cc * 64;
-            } else {
-                const int cc = s - nsteps1;
-                xs = p.x2; wsrc = p.w2;
-                aoff = (taps.dy0 * p.xWp + taps.dx0) * p.xC + cc * 64;
-                woff = cc * 64;
-            }
+            const ConvKStep k = conv_kstep_decode(p, taps, s, nsteps1, kchunks);
+            const int woff = k.wsl * p.Co * p.Kc + k.cc * 64;
 #pragma unroll
             for (int i = 0; i < A_PER; ++i)
-                __builtin_amdgcn_global_load_lds((gptr_t)(xs + abase[i] + aoff), (lptr_t)(st + (lw + 4 * i) * 8 * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(k.x + abase[i] + k.xoff), (lptr_t)(st + (lw + 4 * i) * 8 * 64), 16, 0, 0);
 #pragma unroll
             for (int i = 0; i < W_PER; ++i)
-                __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + wbase[i] + woff), (lptr_t)(st + ASTAGE + (lw + 4 * i) * 8 * 64), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(k.w + wbase[i] + woff), (lptr_t)(st + ASTAGE + (lw + 4 * i) * 8 * 64), 16, 0, 0);
         };
 #pragma unroll
         for (int s = 0; s < AHEAD; ++s)
@@ -1465,15 +1467,20 @@ static bool conv1x1_ws_eligible(const ConvParams& p) {
     if (p.Kc < 512 && !(p.Kc >= kmin && p.M <= mmax)) return false;
     return p.taps.nr == 1 && p.taps.nc == 1 && p.istr == 1 && !p.alt_w;
 }
+// Grid of the gather kernel and the ring GEMM: pixel tiles of the largest parity class x channel tiles x classes.  With a second
+// convolution its blocks follow the first's in y (q.alt_y0)
+static dim3 conv_class_grid(ConvParams& q, int BM, int BN) {
+    int maxM = q.M;
+    for (int k = 1; k < q.ncls; ++k) maxM = q.cls[k - 1].geo.M > maxM ? q.cls[k - 1].geo.M : maxM;
+    if (q.alt_w) q.alt_y0 = q.Co / BN;
+    return dim3((maxM + BM - 1) / BM, (q.Co / BN) * (q.alt_w ? 2 : 1), q.ncls > 1 ? q.ncls : 1);
+}
 template <int BM, int BN, int NS>
 static hipError_t launch_1x1_ws(const ConvParams& p, hipStream_t stream) {
-    int maxM = p.M;
-    for (int k = 1; k < p.ncls; ++k) maxM = p.cls[k - 1].geo.M > maxM ? p.cls[k - 1].geo.M : maxM;
-    dim3 grid((maxM + BM - 1) / BM, (p.Co / BN) * (p.alt_w ? 2 : 1), p.ncls > 1 ? p.ncls : 1);
     const size_t lds = (size_t)NS * (BM + BN) * 64 * sizeof(bf16_t);
     static_assert((size_t)NS * (BM + BN) * 64 * sizeof(bf16_t) <= 160 * 1024, "LDS");
     ConvParams q = p;
-    if (q.alt_w) q.alt_y0 = p.Co / BN;      // the second convolution's blocks follow the first's
+    const dim3 grid = conv_class_grid(q, BM, BN);
     switch (conv_ep_mode(q)) {
         case 0: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 0>), grid, dim3(512), lds, stream, q); break;
         case 1: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 1>), grid, dim3(512), lds, stream, q); break;
@@ -1537,11 +1544,8 @@ static bool halo_eligible(const ConvParams& p) {
 
 template <int BM, int BN, int WM, int WN>
 static hipError_t launch_cfg(const ConvParams& p, hipStream_t stream) {
-    int maxM = p.M;
-    for (int k = 1; k < p.ncls; ++k) maxM = p.cls[k - 1].geo.M > maxM ? p.cls[k - 1].geo.M : maxM;
     ConvParams q = p;
-    if (q.alt_w) q.alt_y0 = p.Co / BN;      // the second convolution's blocks follow the first's
-    dim3 grid((maxM + BM - 1) / BM, (p.Co / BN) * (q.alt_w ? 2 : 1), p.ncls > 1 ? p.ncls : 1);
+    const dim3 grid = conv_class_grid(q, BM, BN);
     const size_t lds = (size_t)2 * (BM + BN) * 64 * sizeof(bf16_t);
     switch (conv_ep_mode(q)) {
         case 0: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 0>), grid, dim3(256), lds, stream, q); break;
@@ -1566,8 +1570,10 @@ extern "C" int vpd_conv_bm(int M, int Co) {
 
 // Kernel selection = timing class of vpd_plan_read_timing (one class per kernel function):
 //   0 conv3x3_c64_persistent_kernel<224>   1 conv3x3_ws_kernel<256,128,352>   2 conv3x3_ws_kernel<128,128,288>
-//   3 conv3x3_ws_kernel<128,64,288>        4 conv_igemm_kernel (gather; also the legacy conv3x3_halo fallback)
-//   5 conv_stem_persistent_kernel<160>
+//   3 conv3x3_ws_kernel<128,64,288>        4 conv_igemm_kernel (gather; also the legacy conv3x3_halo fallback, the ring GEMM and
+//   5 conv_stem_persistent_kernel<160>       the streaming 1x1 kernels: vpd_conv_dispatch tells them apart)
+//   6 conv3x3_ws_kernel<256,64,416>
+// (classes 1, 2, 3 and 6 run on conv3x3_pws_kernel of the same tile where vpd_conv_dispatch says pws)
 int vpd_conv_kernel_class(const ConvParams& p, HaloGeom* g) {
     const int no_ws = vpd_switches().no_ws;
     int tr_stem;
