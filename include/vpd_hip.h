@@ -245,6 +245,38 @@ int vpd_op_grad_norm(const float* const* x, const long long* n, int count, doubl
 int vpd_plan_grad_norm(vpd_plan_t* plan, const float* grads, long long numel, double max_norm, vpd_scale_state* src,
                        float host_scale, vpd_clip_state* clip, void* workspace, void* stream);
 
+/* ---- AdamW parameter groups (torch.optim.AdamW's param_groups): lr and weight decay per group, betas and eps shared ----
+ * Up to 16 groups.  The kernels find an element's group in a SEGMENT TABLE, a block of DEVICE memory owned by the caller
+ * (vpd_adam_groups_bytes(nseg) bytes, 16-byte aligned), written once by vpd_adam_groups_init: segment s is the element range
+ * [seg_begin[s], seg_begin[s + 1]) of the flat buffers and belongs to group seg_group[s]; adjacent tensors of one group form one
+ * segment, and the padding floats between tensors (zero in every buffer, and zero after any step) belong to the segment in front.
+ * Per group the step computes exactly what the ungrouped entry points compute from (lr[g], weight_decay[g]): with one group, or
+ * with equal entries, the results are the same bits.  A group with lr = 0 and weight_decay = 0 keeps its parameters bit for bit
+ * (p * 1.0f is exact and fma(-0, m / den, p) = p since den >= eps > 0); its moments are still updated, as torch's are. */
+size_t vpd_adam_groups_bytes(int nseg);
+/* Validates the HOST arrays seg_begin[nseg + 1] / seg_group[nseg] and copies them into `table` (the stream is synchronised before
+ * the call returns: the host arrays may be freed).  Refused, nothing launched or copied: a null table / seg_begin / seg_group,
+ * nseg < 1, ngroups outside 1..16, seg_begin[0] != 0, offsets not strictly ascending, seg_begin[nseg] != numel, numel not a multiple
+ * of 4, a group id outside 0..ngroups-1, a table that is not 16-byte aligned.  With a plan (NULL: none) also a boundary strictly
+ * inside one of the plan's conv weights (the fused kernel looks a conv's group up once per block) and numel !=
+ * vpd_plan_param_numel(plan). */
+int vpd_adam_groups_init(const vpd_plan_t* plan_or_null, void* table, const long long* seg_begin, const int* seg_group, int nseg,
+                         long long numel, int ngroups, void* stream);
+/* vpd_adamw_step / vpd_adamw_step_scaled with groups: lr[ngroups] and weight_decay[ngroups] are HOST arrays, copied into the
+ * kernel's arguments.  state == NULL: `step` (1-based) and `gscale` (a factor on every gradient read: 1 / loss scale, or 1) are the
+ * host's; else the device block decides as in vpd_adamw_step_scaled and both are ignored.  Refused on the host: a null buffer /
+ * table / lr / weight_decay, ngroups outside 1..16, a negative or NaN lr or weight_decay (as torch refuses them), step < 1 without
+ * a state, numel not a multiple of 4, a buffer or table that is not 16-byte aligned. */
+int vpd_adamw_step_groups(float* params, const float* grads, float* adam_m, float* adam_v, long long numel, const void* table,
+                          const double* lr, const double* weight_decay, int ngroups, double beta1, double beta2, double eps,
+                          int step, float gscale, const vpd_scale_state* state, void* stream);
+/* vpd_plan_adamw_step (state == NULL: the plan's loss scale applies) / vpd_plan_adamw_step_scaled with groups: the same launches --
+ * the fused AdamW + repack reading the scratch while gradients are pending, then the stem repack -- and the same refusals, plus those
+ * above.  numel must EQUAL vpd_plan_param_numel(plan): tensors beyond the plan's take vpd_adamw_step_groups. */
+int vpd_plan_adamw_step_groups(vpd_plan_t* plan, float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
+                               const void* table, const double* lr, const double* weight_decay, int ngroups, double beta1,
+                               double beta2, double eps, int step, const vpd_scale_state* state, void* workspace, void* stream);
+
 /* Lazy gradients for the fused train step (reference: models/util.py:50-58, where nothing looks at .grad between
  * loss.backward() and optimizer.step()).  vpd_plan_set_lazy_grads(plan, 1) arms the NEXT vpd_backward: the conv weight
  * gradients then stay in the kernels' own fp32 scratch layout and vpd_plan_adamw_step reads them there, so the layout pass
@@ -606,6 +638,14 @@ int vpd_op_unpack_grads(const float* wg, int Co, int Ci, int k, int Kc, int stem
 int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* offsets, long long numel, float* params, const float* grads,
                       float* adam_m, float* adam_v, void* arena, const float* wg, double lr, double beta1, double beta2, double eps,
                       double weight_decay, int step, float gscale, void* stream);
+/* vpd_op_adamw_pack with parameter groups (vpd_adam_groups_init's HOST arrays over the synthetic buffer, lr[ngroups] /
+ * weight_decay[ngroups]): the entry builds and uploads its own segment table and refuses a boundary inside a synthetic conv.
+ * state (or null): a device block that decides as in vpd_plan_adamw_step_scaled; step and gscale are then ignored. */
+int vpd_op_adamw_pack_groups(int nconv, const int* dims3, const long long* offsets, long long numel, float* params,
+                             const float* grads, float* adam_m, float* adam_v, void* arena, const float* wg,
+                             const long long* seg_begin, const int* seg_group, int nseg, const double* lr,
+                             const double* weight_decay, int ngroups, double beta1, double beta2, double eps, int step,
+                             float gscale, const vpd_scale_state* state, void* stream);
 /* The weight gradients' slab sums, nprob (1..18) problems in one launch: dws[i][e] = sum over s < ksplits[i] of
  * slabs[i][s * nfloats[i] + e]; nfloats[i] a multiple of 4, pointers 16-byte aligned. */
 int vpd_op_wgrad_reduce(int nprob, const float* const* slabs, float* const* dws, const long long* nfloats, const int* ksplits,

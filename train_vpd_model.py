@@ -59,6 +59,14 @@ def get_args():
     parser.add_argument('--clip_grad_norm', type=float,
                         help='(this build) torch.nn.utils.clip_grad_norm_ with this max_norm before every optimizer step, decided '
                              'on the device; every epoch prints grad_norm_max and clipped_steps and adds them to loss.json')
+    parser.add_argument('--weight_decay', type=float,
+                        help='(this build) AdamW weight decay (default 0.01, torch\'s)')
+    parser.add_argument('--no_bn_bias_decay', action='store_true',
+                        help='(this build) no weight decay on BatchNorm weights / biases and linear biases: a parameter group of '
+                             'their own with weight_decay 0 (ModelTrainer.param_groups)')
+    parser.add_argument('--backbone_lr_scale', type=float,
+                        help='(this build) the head (fc + motion head) runs at --learning_rate, everything else at this factor '
+                             'times it: the --pretrained fine-tuning recipe')
     parser.add_argument('--no_augment', action='store_true',
                         help='escape hatch: fp32 batches from the CPU loaders with h-flips only -- NOT the reference '
                              'recipe, whose datasets always augment (vpd_dataset/common.py:85-92)')
@@ -71,6 +79,10 @@ def get_args():
         parser.error('--clip_grad_norm must be > 0')
     if args.ema_warmup and args.ema_decay is None:
         parser.error('--ema_warmup needs --ema_decay')
+    if args.weight_decay is not None and not args.weight_decay >= 0.0:
+        parser.error('--weight_decay must not be negative')
+    if args.backbone_lr_scale is not None and not args.backbone_lr_scale >= 0.0:
+        parser.error('--backbone_lr_scale must not be negative')
     return args
 
 
@@ -94,7 +106,7 @@ def load_dataset(dataset, dataset_kwargs, emb_dir, penn_dir, no_test_video):
 def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, motion, encoder_arch, save_dir,
          model_select_window, checkpoint_frequency, pretrained, emb_dir, penn_dir, no_test_video, min_pose_score,
          synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static', ema_decay=None,
-         ema_warmup=False, clip_grad_norm=None):
+         ema_warmup=False, clip_grad_norm=None, weight_decay=None, no_bn_bias_decay=False, backbone_lr_scale=None):
     device = 'cuda'
     # The reference builds train AND val datasets with augment=True (vpd_dataset/single_frame.py:267-272,
     # common.py:85-92): ColorJitter, mask noise, RandomResizedCrop and flips are part of the recipe, so they are the
@@ -170,8 +182,22 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         torch.distributed.broadcast(encoder.engine.params, 0)
         torch.distributed.broadcast(encoder.engine.bn_running, 0)
         encoder.engine.mark_weights_changed()
+    # parameter groups only when one of their flags is given: without them one group, the optimizer step of always
+    grouping = {}
+    if weight_decay is not None:
+        grouping['weight_decay'] = weight_decay
+    if no_bn_bias_decay:
+        grouping['no_bn_bias_decay'] = True
+    if backbone_lr_scale is not None:
+        grouping['backbone_lr_scale'] = backbone_lr_scale
+    param_groups = None
+    if grouping:
+        param_groups = trainer.param_groups(weight_decay=0.01 if weight_decay is None else weight_decay,
+                                            decay_bn_bias=not no_bn_bias_decay,
+                                            backbone_lr_scale=1.0 if backbone_lr_scale is None else backbone_lr_scale,
+                                            lr=learning_rate)
     optimizer, scaler = trainer.get_optimizer(learning_rate, loss_scale='dynamic' if loss_scale == 'dynamic' else None,
-                                              max_grad_norm=clip_grad_norm)
+                                              max_grad_norm=clip_grad_norm, param_groups=param_groups)
     dynamic = loss_scale == 'dynamic'
     skipped_before = 0
     clip = clip_grad_norm is not None
@@ -182,6 +208,7 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         config_ema = {} if not ema else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}      # (keys only with --ema_decay)
         if clip:
             config_ema['clip_grad_norm'] = clip_grad_norm      # (key only with --clip_grad_norm)
+        config_ema.update(grouping)      # (weight_decay / no_bn_bias_decay / backbone_lr_scale: keys only with their flags)
         store_json(os.path.join(save_dir, 'config.json'), {
             'num_epochs': num_epochs, 'batch_size': batch_size, 'learning_rate': learning_rate, 'img_dim': img_dim,
             'use_flow': flow_img is not None, 'motion': motion,

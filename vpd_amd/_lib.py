@@ -15,6 +15,7 @@ ABI_VERSION = 5
 
 c_int_p = C.POINTER(C.c_int)
 c_ll_p = C.POINTER(C.c_longlong)
+c_dbl_p = C.POINTER(C.c_double)
 vp = C.c_void_p
 
 # name -> (restype, argtypes); mirrors include/vpd_hip.h one to one
@@ -69,6 +70,12 @@ SIGNATURES = {
     "vpd_clip_state_bytes": (C.c_size_t, []),
     "vpd_op_grad_norm": (C.c_int, [C.POINTER(vp), c_ll_p, C.c_int, C.c_double, vp, C.c_float, vp, vp]),
     "vpd_plan_grad_norm": (C.c_int, [vp, vp, C.c_longlong, C.c_double, vp, C.c_float, vp, vp, vp]),
+    "vpd_adam_groups_bytes": (C.c_size_t, [C.c_int]),
+    "vpd_adam_groups_init": (C.c_int, [vp, vp, c_ll_p, c_int_p, C.c_int, C.c_longlong, C.c_int, vp]),
+    "vpd_adamw_step_groups": (C.c_int, [vp, vp, vp, vp, C.c_longlong, vp, c_dbl_p, c_dbl_p, C.c_int, C.c_double, C.c_double,
+                                        C.c_double, C.c_int, C.c_float, vp, vp]),
+    "vpd_plan_adamw_step_groups": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, vp, c_dbl_p, c_dbl_p, C.c_int, C.c_double,
+                                             C.c_double, C.c_double, C.c_int, vp, vp, vp]),
     "vpd_plan_bucket_scratch_range": (C.c_int, [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "vpd_plan_grads_pending": (C.c_int, [vp]),
     "vpd_plan_materialize_grads": (C.c_int, [vp, vp, vp, vp]),
@@ -121,6 +128,8 @@ SIGNATURES = {
     "vpd_op_pack_weights": (C.c_int, [vp] + [C.c_int] * 4 + [vp, vp, vp]),
     "vpd_op_unpack_grads": (C.c_int, [vp] + [C.c_int] * 5 + [vp, vp]),
     "vpd_op_adamw_pack": (C.c_int, [C.c_int, c_int_p, c_ll_p, C.c_longlong] + [vp] * 6 + [C.c_double] * 5 + [C.c_int, C.c_float, vp]),
+    "vpd_op_adamw_pack_groups": (C.c_int, [C.c_int, c_int_p, c_ll_p, C.c_longlong] + [vp] * 6 + [c_ll_p, c_int_p, C.c_int, c_dbl_p,
+                                           c_dbl_p, C.c_int] + [C.c_double] * 3 + [C.c_int, C.c_float, vp, vp]),
     "vpd_op_wgrad_reduce": (C.c_int, [C.c_int, C.POINTER(vp), C.POINTER(vp), c_ll_p, c_int_p, vp]),
     "vpd_op_zero_ranges": (C.c_int, [C.POINTER(vp), c_ll_p, C.c_int, vp]),
 }
@@ -160,7 +169,9 @@ def lib(dtype="bf16"):
             # (an OLDER round's library, same-box A/B: the entry points added since are optional there -- engine.py asks hasattr)
             if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext",
                                                                  "vpd_plan_set_bn_frozen", "vpd_plan_set_param_grads",
-                                                                 "vpd_ema_update", "vpd_clip_state_bytes", "vpd_plan_grad_norm")):
+                                                                 "vpd_ema_update", "vpd_clip_state_bytes", "vpd_plan_grad_norm",
+                                                                 "vpd_adam_groups_bytes", "vpd_adam_groups_init",
+                                                                 "vpd_adamw_step_groups", "vpd_plan_adamw_step_groups")):
                 continue
             raise VpdHipError("%s lacks symbol %s declared in include/vpd_hip.h" % (name, sym)) from e
         fn.restype = res

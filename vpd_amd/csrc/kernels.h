@@ -77,6 +77,22 @@ struct AdamHyperDyn { AdamHyper h; const vpd_scale_state* st; double lr, b1, b2;
 // What the two AdamW launchers take.  st == null: `step` (1-based) and `gscale` are the host's (adamw_kernel<AdamHyper>); else the
 // device block decides and both are ignored (<AdamHyperDyn>)
 struct AdamArgs { double lr, b1, b2, eps, wd; int step; float gscale; const vpd_scale_state* st; };
+// Parameter groups (torch.optim.AdamW's param_groups): lr and weight decay per group, everything else shared.  The kernels find an
+// element's group in the SEGMENT TABLE, a block of device memory (vpd_adam_groups_init, include/vpd_hip.h):
+//   int nseg, ngroups, pad[2];  long long begin[nseg + 1];  int group[nseg];
+// begin[0] = 0 < ... < begin[nseg] = numel; segment s is [begin[s], begin[s + 1]) of the flat buffers and belongs to group[s].
+#define VPD_MAX_PARAM_GROUPS 16
+inline size_t vpd_adam_table_bytes(int nseg) {
+    return (16 + (size_t)(nseg + 1) * sizeof(long long) + (size_t)nseg * sizeof(int) + 15) & ~(size_t)15;
+}
+// ... AdamHyper with decay = (float)(1 - lr_g wd_g) and step_size = (float)(lr_g / bc1) per group (h.decay / h.step_size: unused; the
+// slots behind the last group hold decay 1, step_size 0: a parameter that reached one would stay as it is)
+struct AdamGroupHyper { AdamHyper h; const void* table; float decay[VPD_MAX_PARAM_GROUPS], step_size[VPD_MAX_PARAM_GROUPS]; };
+// ... under a device block: every group's step_size is formed from its double lr and the block's applied-step count
+struct AdamGroupHyperDyn { AdamGroupHyper g; const vpd_scale_state* st; double lr[VPD_MAX_PARAM_GROUPS], b1, b2; };
+// What the two grouped launchers take (AdamArgs with lr[] / wd[] of `ngroups` groups and the table)
+struct AdamGroupArgs { const void* table; const double* lr; const double* wd; int ngroups; double b1, b2, eps; int step; float gscale;
+                       const vpd_scale_state* st; };
 #define FR_MAX 96
 struct FiniteRanges {                   // float ranges of any alignment and length (vpd_launch_check_finite)
     const float* ptr[FR_MAX];
@@ -313,6 +329,11 @@ hipError_t vpd_launch_adamw_pack(const PackDesc* d_descs, const int* d_blockmap,
 hipError_t vpd_launch_unpack_grads(const PackDesc* d_descs, int ndesc, const int* d_blockmap, int nblocks,
                                    const float* wg, float* grads, hipStream_t s);
 hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, const AdamArgs& a, hipStream_t s);
+// the same two launches with parameter groups: the grouped instantiations of the same kernels (the ungrouped ones are untouched)
+hipError_t vpd_launch_adamw_pack_groups(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
+                                        float* m, float* v, bf16_t* arena, const AdamGroupArgs& a, hipStream_t s,
+                                        const float* wg = nullptr);
+hipError_t vpd_launch_adamw_groups(float* p, const float* g, float* m, float* v, long n, const AdamGroupArgs& a, hipStream_t s);
 // dynamic loss scaling (vpd_scale_state): the two AdamW launches above reading scale / applied steps / the non-finite word from
 // the device block (AdamArgs::st), the inf / NaN search, the update rule; head.hip: d(loss)/d(pred) x the block's scale
 hipError_t vpd_launch_check_finite(const FiniteRanges& r, vpd_scale_state* st, hipStream_t s);

@@ -664,17 +664,15 @@ extern "C" int vpd_op_unpack_grads(const float* wg, int Co, int Ci, int k, int K
     return 0;
 }
 
-extern "C" int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* offsets, long long numel, float* params,
-                                 const float* grads, float* adam_m, float* adam_v, void* arena, const float* wg, double lr,
-                                 double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
-                                 void* stream) {
-    if (!params || !grads || !adam_m || !adam_v || !arena || (nconv > 0 && (!dims3 || !offsets))) return fail("null argument");
+namespace {
+// the descriptors and the block map of vpd_op_adamw_pack's synthetic buffer (0, or fail())
+int op_adam_tables(int nconv, const int* dims3, const long long* offsets, long long numel, const void* arena, const float* wg,
+                   std::vector<PackDesc>& descs, std::vector<int>& bmap_adam) {
+    if (nconv > 0 && (!dims3 || !offsets)) return fail("null argument");
     if (nconv < 0 || nconv > 64) return fail("nconv outside 0..64");
     if (numel < 4 || numel % 4) return fail("numel must be a positive multiple of 4");
-    if (step < 1) return fail("step is 1-based");
     if (!aligned(arena, 16) || !aligned(wg, 16)) return fail("arena and wg must be 16-byte aligned");
-    std::vector<PackDesc> descs;
-    std::vector<int> bmap_pack, unused, bmap_adam;
+    std::vector<int> bmap_pack, unused;
     long long arena_at = 0, wg_at = 0, prev_end = 0;
     for (int i = 0; i < nconv; ++i) {
         const int Co = dims3[3 * i], Ci = dims3[3 * i + 1], k = dims3[3 * i + 2];
@@ -693,11 +691,49 @@ extern "C" int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* o
     }
     int nstem = 0;
     build_adam_map(descs, bmap_pack, -1, numel, bmap_adam, nstem);
+    return 0;
+}
+}  // namespace
+
+extern "C" int vpd_op_adamw_pack(int nconv, const int* dims3, const long long* offsets, long long numel, float* params,
+                                 const float* grads, float* adam_m, float* adam_v, void* arena, const float* wg, double lr,
+                                 double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
+                                 void* stream) {
+    if (!params || !grads || !adam_m || !adam_v || !arena) return fail("null argument");
+    if (step < 1) return fail("step is 1-based");
+    std::vector<PackDesc> descs;
+    std::vector<int> bmap_adam;
+    if (op_adam_tables(nconv, dims3, offsets, numel, arena, wg, descs, bmap_adam)) return -1;
     hipStream_t s = (hipStream_t)stream;
     DevTables t;
     HCHECK(t.upload(descs, bmap_adam, s));
     LCHECK(vpd_launch_adamw_pack(t.descs, t.bmap, (int)bmap_adam.size() / 2, params, grads, adam_m, adam_v, (bf16_t*)arena,
                                  AdamArgs{lr, beta1, beta2, eps, weight_decay, step, gscale, nullptr}, s, wg));
+    HCHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
+extern "C" int vpd_op_adamw_pack_groups(int nconv, const int* dims3, const long long* offsets, long long numel, float* params,
+                                        const float* grads, float* adam_m, float* adam_v, void* arena, const float* wg,
+                                        const long long* seg_begin, const int* seg_group, int nseg, const double* lr,
+                                        const double* weight_decay, int ngroups, double beta1, double beta2, double eps, int step,
+                                        float gscale, const vpd_scale_state* state, void* stream) {
+    if (!params || !grads || !adam_m || !adam_v || !arena) return fail("null argument");
+    std::vector<PackDesc> descs;
+    std::vector<int> bmap_adam;
+    if (op_adam_tables(nconv, dims3, offsets, numel, arena, wg, descs, bmap_adam)) return -1;
+    if (adam_group_args_check(lr, weight_decay, ngroups, step, state)) return -1;
+    if (adam_groups_check(seg_begin, seg_group, nseg, numel, ngroups)) return -1;
+    if (adam_groups_check_convs(descs, seg_begin, nseg)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    DevTables t;
+    struct Table { void* p = nullptr; ~Table() { (void)hipFree(p); } } table;
+    HCHECK(hipMalloc(&table.p, vpd_adam_table_bytes(nseg)));
+    if (adam_groups_upload(table.p, seg_begin, seg_group, nseg, ngroups, s)) return -1;
+    HCHECK(t.upload(descs, bmap_adam, s));
+    LCHECK(vpd_launch_adamw_pack_groups(t.descs, t.bmap, (int)bmap_adam.size() / 2, params, grads, adam_m, adam_v, (bf16_t*)arena,
+                                        AdamGroupArgs{table.p, lr, weight_decay, ngroups, beta1, beta2, eps, step, gscale, state}, s,
+                                        wg));
     HCHECK(hipStreamSynchronize(s));
     return 0;
 }

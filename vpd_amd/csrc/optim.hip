@@ -240,8 +240,9 @@ hipError_t vpd_launch_unpack_grads(const PackDesc* d_descs, int ndesc, const int
     return hipGetLastError();
 }
 
-// Fused AdamW over the whole flat parameter buffer (every tensor shares the
-// hyper-parameters: train_vpd_model.py:104 uses one param group, wd on all).
+// Fused AdamW over the whole flat parameter buffer.  Ungrouped (AdamHyper / AdamHyperDyn): every tensor shares the
+// hyper-parameters, as train_vpd_model.py:104's one param group with wd on all.  Grouped (AdamGroupHyper / AdamGroupHyperDyn,
+// kernels.h): lr and weight decay per parameter group, found through the segment table; the arithmetic is this one function.
 // (explicit fma placement: the flat kernel and the fused AdamW + repack kernel must round identically)
 static __device__ __forceinline__ void adamw1(float& p, float g, float& m, float& v, const AdamHyper& h) {
 #pragma clang fp contract(off)
@@ -285,16 +286,103 @@ static __device__ __forceinline__ AdamHyper adam_live(const AdamHyperDyn& d, boo
     return h;
 }
 
+// ---- parameter groups: the grouped instantiations of both kernels (the ungrouped ones take none of this: if constexpr) ----
+template <class H> struct AdamGrouped { static constexpr bool on = false; };
+template <> struct AdamGrouped<AdamGroupHyper> { static constexpr bool on = true; };
+template <> struct AdamGrouped<AdamGroupHyperDyn> { static constexpr bool on = true; };
+// What is shared (betas, eps, inv_sqrt_bc2, gscale), as the ungrouped launch forms it; bc1: the first moment's bias correction under
+// a device block, from which adam_pick forms a group's step_size exactly as adam_live(AdamHyperDyn) forms the single one
+static __device__ __forceinline__ AdamHyper adam_live(const AdamGroupHyper& g, bool& live, double& bc1) {
+    live = true;
+    bc1 = 1.0;
+    return g.h;
+}
+static __device__ __forceinline__ AdamHyper adam_live(const AdamGroupHyperDyn& d, bool& live, double& bc1) {
+    AdamHyper h = d.g.h;
+    live = d.st->found == 0;
+    bc1 = 1.0;
+    if (live) {
+        const double step = (double)(d.st->applied_steps + 1);
+        bc1 = 1.0 - pow(d.b1, step);
+        h.inv_sqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow(d.b2, step)));
+        h.gscale = 1.0f / d.st->scale;
+    }
+    return h;
+}
+// `h` with group gid's decay and step_size (gid < VPD_MAX_PARAM_GROUPS: vpd_adam_groups_init refuses any other table)
+static __device__ __forceinline__ void adam_pick(const AdamGroupHyper& g, double, int gid, AdamHyper& h) {
+    gid &= VPD_MAX_PARAM_GROUPS - 1;      // (never leaves the argument, whatever the table holds)
+    h.decay = g.decay[gid];
+    h.step_size = g.step_size[gid];
+}
+static __device__ __forceinline__ void adam_pick(const AdamGroupHyperDyn& d, double bc1, int gid, AdamHyper& h) {
+    gid &= VPD_MAX_PARAM_GROUPS - 1;
+    h.decay = d.g.decay[gid];
+    h.step_size = (float)(d.lr[gid] / bc1);
+}
+static __device__ __forceinline__ const void* adam_table(const AdamGroupHyper& g) { return g.table; }
+static __device__ __forceinline__ const void* adam_table(const AdamGroupHyperDyn& d) { return d.g.table; }
+// The segment table (layout: kernels.h) and the segment of element e by binary search: the last s with begin[s] <= e, so an e
+// behind the table's end falls into the last segment.  Plain loads of device memory a host-to-device copy wrote.
+struct SegTable { const long long* begin; const int* group; int nseg; };
+static __device__ __forceinline__ SegTable seg_table(const void* table) {
+    const int* hd = reinterpret_cast<const int*>(table);
+    const int nseg = hd[0];
+    const long long* begin = reinterpret_cast<const long long*>(hd + 4);
+    return SegTable{begin, reinterpret_cast<const int*>(begin + nseg + 1), nseg};
+}
+static __device__ __forceinline__ int seg_find(const SegTable& t, long e) {
+    int lo = 0, hi = t.nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t.begin[mid] <= e) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// ... forward from segment s (e not in front of it)
+static __device__ __forceinline__ int seg_walk(const SegTable& t, int s, long e) {
+    while (s + 1 < t.nseg && t.begin[s + 1] <= e) ++s;
+    return s;
+}
+
 template <class H>
 __global__ __launch_bounds__(256) void adamw_kernel(float4* p, const float4* g, float4* m, float4* v, long n4,
                                                     const H hh) {
-    bool live;
-    const AdamHyper h = adam_live(hh, live);
-    if (!live) return;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-        adamw4(pp, gg, mm, vv, h);
-        p[i] = pp; m[i] = mm; v[i] = vv;
+    if constexpr (AdamGrouped<H>::on) {
+        // a float4 inside one segment takes the vector path with that segment's group; one that straddles a boundary (segments may
+        // begin at any element) is done element by element
+        bool live;
+        double bc1;
+        AdamHyper h = adam_live(hh, live, bc1);
+        if (!live) return;
+        const SegTable t = seg_table(adam_table(hh));
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+            float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
+            const long e = i << 2;
+            int s = seg_find(t, e);
+            adam_pick(hh, bc1, t.group[s], h);
+            if (s + 1 >= t.nseg || t.begin[s + 1] >= e + 4) {
+                adamw4(pp, gg, mm, vv, h);
+            } else {
+                adamw1(pp.x, gg.x, mm.x, vv.x, h);
+                s = seg_walk(t, s, e + 1); adam_pick(hh, bc1, t.group[s], h);
+                adamw1(pp.y, gg.y, mm.y, vv.y, h);
+                s = seg_walk(t, s, e + 2); adam_pick(hh, bc1, t.group[s], h);
+                adamw1(pp.z, gg.z, mm.z, vv.z, h);
+                s = seg_walk(t, s, e + 3); adam_pick(hh, bc1, t.group[s], h);
+                adamw1(pp.w, gg.w, mm.w, vv.w, h);
+            }
+            p[i] = pp; m[i] = mm; v[i] = vv;
+        }
+    } else {
+        bool live;
+        const AdamHyper h = adam_live(hh, live);
+        if (!live) return;
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+            float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
+            adamw4(pp, gg, mm, vv, h);
+            p[i] = pp; m[i] = mm; v[i] = vv;
+        }
     }
 }
 hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n, const AdamArgs& a, hipStream_t s) {
@@ -309,6 +397,42 @@ hipError_t vpd_launch_adamw(float* p, const float* g, float* m, float* v, long n
     else
         hipLaunchKernelGGL(adamw_kernel<AdamHyperDyn>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m, (float4*)v,
                            n4, adam_hyper_dyn(a));
+    return hipGetLastError();
+}
+// Per group exactly what adam_hyper computes for the one (lr, wd): the same doubles, rounded to float once
+static AdamGroupHyper adam_group_hyper(const AdamGroupArgs& a, int step, float gscale) {
+    AdamGroupHyper gh;
+    gh.h = adam_hyper(AdamArgs{a.lr[0], a.b1, a.b2, a.eps, a.wd[0], step, gscale, a.st}, step, gscale);
+    gh.table = a.table;
+    const double bc1 = 1.0 - pow(a.b1, step);
+    for (int i = 0; i < VPD_MAX_PARAM_GROUPS; ++i) {
+        gh.decay[i] = i < a.ngroups ? (float)(1.0 - a.lr[i] * a.wd[i]) : 1.f;
+        gh.step_size[i] = i < a.ngroups ? (float)(a.lr[i] / bc1) : 0.f;
+    }
+    return gh;
+}
+static AdamGroupHyperDyn adam_group_hyper_dyn(const AdamGroupArgs& a) {
+    AdamGroupHyperDyn d;
+    d.g = adam_group_hyper(a, 1, 1.f);      // (place-holders, as adam_hyper_dyn's)
+    d.st = a.st; d.b1 = a.b1; d.b2 = a.b2;
+    for (int i = 0; i < VPD_MAX_PARAM_GROUPS; ++i) d.lr[i] = i < a.ngroups ? a.lr[i] : 0.0;
+    return d;
+}
+static bool adam_groups_ok(const AdamGroupArgs& a) {
+    return a.table && a.lr && a.wd && a.ngroups >= 1 && a.ngroups <= VPD_MAX_PARAM_GROUPS && (reinterpret_cast<size_t>(a.table) & 15) == 0;
+}
+hipError_t vpd_launch_adamw_groups(float* p, const float* g, float* m, float* v, long n, const AdamGroupArgs& a, hipStream_t s) {
+    if (n % 4 || !adam_groups_ok(a)) return hipErrorInvalidValue;
+    const long n4 = n / 4;
+    long gsz = (n4 + 255) / 256;
+    if (gsz > 4096) gsz = 4096;
+    const dim3 grid(gsz < 1 ? 1 : (int)gsz);
+    if (!a.st)
+        hipLaunchKernelGGL(adamw_kernel<AdamGroupHyper>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m,
+                           (float4*)v, n4, adam_group_hyper(a, a.step, a.gscale));
+    else
+        hipLaunchKernelGGL(adamw_kernel<AdamGroupHyperDyn>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m,
+                           (float4*)v, n4, adam_group_hyper_dyn(a));
     return hipGetLastError();
 }
 
@@ -333,27 +457,41 @@ static __device__ __forceinline__ float4 adamw_gather_g(const float* wgc, int Co
     }
     return float4{v[0], v[1], v[2], v[3]};
 }
-template <class H>      // AdamHyper | AdamHyperDyn (a skipped step leaves the packed weights alone too: they already hold these parameters)
+template <class H>      // AdamHyper | AdamHyperDyn | their grouped forms (a skipped step leaves the packed weights alone too: they already hold these parameters)
 __global__ __launch_bounds__(256) void adamw_pack_kernel(const PackDesc* descs, const int* blockmap, float* p,
                                                          const float* g, float* m, float* v, bf16_t* arena,
                                                          const H hh, const float* wg) {
     __shared__ unsigned short tile[32][32 * 9 + 2];      // the new weights, already rounded to bf16 (18 KB: 8 blocks per CU)
+    constexpr bool grouped = AdamGrouped<H>::on;
     bool live;
-    const AdamHyper h = adam_live(hh, live);
+    [[maybe_unused]] double bc1 = 1.0;
+    [[maybe_unused]] SegTable t{};
+    AdamHyper h;
+    if constexpr (grouped) h = adam_live(hh, live, bc1); else h = adam_live(hh, live);
     if (!live) return;
+    if constexpr (grouped) t = seg_table(adam_table(hh));
     const PackDesc d = descs[blockmap[2 * blockIdx.x]];
     const int chunk = blockmap[2 * blockIdx.x + 1];
     const int khw = d.kh * d.kw;
     if (d.stem == 2) {
+        // (grouped: a plain range spans tensors of several groups -- BatchNorm weight and bias are 64 floats each -- so the group is
+        //  resolved per element: a search for a thread's first element, a walk forward for its next ones)
         const long e0 = d.src_off + (long)chunk * ADAM_PLAIN_CHUNK;
         const long e1 = d.src_off + d.numel;
+        [[maybe_unused]] int seg = -1, gid = -1;
         for (long e = e0 + threadIdx.x; e < e0 + ADAM_PLAIN_CHUNK && e < e1; e += 256) {
+            if constexpr (grouped) {
+                seg = seg < 0 ? seg_find(t, e) : seg_walk(t, seg, e);
+                if (t.group[seg] != gid) { gid = t.group[seg]; adam_pick(hh, bc1, gid, h); }
+            }
             float pp = p[e], mm = m[e], vv = v[e];
             adamw1(pp, g[e], mm, vv, h);
             p[e] = pp; m[e] = mm; v[e] = vv;
         }
         return;
     }
+    // (grouped: a conv weight lies inside one segment -- vpd_adam_groups_init refuses any other table --: one lookup per block)
+    if constexpr (grouped) adam_pick(hh, bc1, t.group[seg_find(t, d.src_off)], h);
     const int tci = d.Ci >> 5;
     const int co0 = (chunk / tci) * 32, ci0 = (chunk % tci) * 32;
     const int run4 = (32 * khw) >> 2;
@@ -415,6 +553,20 @@ hipError_t vpd_launch_adamw_pack(const PackDesc* d_descs, const int* d_blockmap,
     else
         hipLaunchKernelGGL(adamw_pack_kernel<AdamHyperDyn>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v,
                            arena, adam_hyper_dyn(a), wg);
+    return hipGetLastError();
+}
+hipError_t vpd_launch_adamw_pack_groups(const PackDesc* d_descs, const int* d_blockmap, int nblocks, float* p, const float* g,
+                                        float* m, float* v, bf16_t* arena, const AdamGroupArgs& a, hipStream_t s, const float* wg) {
+    if ((reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(m) |
+         reinterpret_cast<size_t>(v)) & 15)
+        return hipErrorInvalidValue;
+    if (!adam_groups_ok(a)) return hipErrorInvalidValue;
+    if (!a.st)
+        hipLaunchKernelGGL(adamw_pack_kernel<AdamGroupHyper>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v,
+                           arena, adam_group_hyper(a, a.step, a.gscale), wg);
+    else
+        hipLaunchKernelGGL(adamw_pack_kernel<AdamGroupHyperDyn>, dim3(nblocks), dim3(256), 0, s, d_descs, d_blockmap, p, g, m, v,
+                           arena, adam_group_hyper_dyn(a), wg);
     return hipGetLastError();
 }
 

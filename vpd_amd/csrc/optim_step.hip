@@ -46,6 +46,30 @@ int adamw_plan(vpd_plan_t* p, float* params, const float* grads, float* adam_m, 
     return 0;
 }
 
+int adamw_plan_groups(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
+                      const AdamGroupArgs& a, void* workspace, void* stream) {
+    if (check_step_call(p, workspace, numel)) return -1;
+    if (numel != p->nparam_padded) return fail("numel must equal vpd_plan_param_numel (tensors beyond the plan's: vpd_adamw_step_groups)");
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t* arena = plan_arena(p, workspace);
+    LCHECK(vpd_launch_adamw_pack_groups(plan_descs(p, workspace), plan_bmap_adam(p, workspace), (int)p->bmap_adam.size() / 2, params,
+                                        grads, adam_m, adam_v, arena, a, s, p->grads_in_scratch ? plan_wg(p, workspace) : nullptr));
+    p->grads_in_scratch = false;
+    LCHECK(vpd_launch_pack_weights(plan_descs(p, workspace), (int)p->descs.size(), plan_bmap_pack(p, workspace),
+                                   p->nstem_pack_blocks, params, arena, s));
+    return 0;
+}
+// what both grouped step entries refuse of their buffers
+int check_group_buffers(const float* params, const float* grads, const float* adam_m, const float* adam_v, const void* table,
+                        long long numel) {
+    if (!params || !grads || !adam_m || !adam_v || !table) return fail("null argument");
+    if (numel % 4) return fail("numel must be a multiple of 4 (use vpd_plan_param_numel)");
+    if ((reinterpret_cast<size_t>(params) | reinterpret_cast<size_t>(grads) | reinterpret_cast<size_t>(adam_m) |
+         reinterpret_cast<size_t>(adam_v) | reinterpret_cast<size_t>(table)) & 15)
+        return fail("params, grads, adam_m, adam_v and the group table must be 16-byte aligned");
+    return 0;
+}
+
 // The ranges a pass reads (empty ones are dropped), handed to `launch` in FiniteRanges batches of at most FR_MAX
 struct RangeBatcher {
     std::vector<std::pair<const float*, long>> ranges;
@@ -122,6 +146,89 @@ int launch_grad_norm(const RangeBatcher& b, double max_norm, vpd_scale_state* sr
 }
 
 }  // namespace
+
+// ---- AdamW parameter groups: the segment table and the hyper-parameters of a grouped step (declared in plan.h) ----
+int adam_groups_check(const long long* seg_begin, const int* seg_group, int nseg, long long numel, int ngroups) {
+    if (!seg_begin || !seg_group) return fail("adam groups: null argument");
+    if (nseg < 1) return fail("adam groups: nseg must be >= 1");
+    if (ngroups < 1 || ngroups > VPD_MAX_PARAM_GROUPS) return fail("adam groups: ngroups outside 1..16");
+    if (seg_begin[0] != 0) return fail("adam groups: seg_begin[0] must be 0");
+    for (int i = 0; i < nseg; ++i)
+        if (seg_begin[i + 1] <= seg_begin[i]) return fail("adam groups: seg_begin must ascend strictly");
+    if (seg_begin[nseg] != numel) return fail("adam groups: seg_begin[nseg] must equal numel");
+    if (numel % 4) return fail("adam groups: numel must be a multiple of 4");
+    for (int i = 0; i < nseg; ++i)
+        if (seg_group[i] < 0 || seg_group[i] >= ngroups) return fail("adam groups: group id outside 0..ngroups-1");
+    return 0;
+}
+int adam_groups_check_convs(const std::vector<PackDesc>& descs, const long long* seg_begin, int nseg) {
+    for (const PackDesc& d : descs) {
+        if (d.stem == 2) continue;
+        const long long a = d.src_off, b = a + (long long)d.Co * d.Ci * d.kh * d.kw;
+        const long long* it = std::upper_bound(seg_begin, seg_begin + nseg + 1, a);      // the first boundary behind the conv's begin
+        if (it != seg_begin + nseg + 1 && *it < b) return fail("adam groups: a segment boundary lies inside a conv weight");
+    }
+    return 0;
+}
+int adam_groups_upload(void* table, const long long* seg_begin, const int* seg_group, int nseg, int ngroups, hipStream_t s) {
+    std::vector<char> host(vpd_adam_table_bytes(nseg), 0);
+    int* hd = reinterpret_cast<int*>(host.data());
+    hd[0] = nseg; hd[1] = ngroups;
+    long long* begin = reinterpret_cast<long long*>(hd + 4);
+    memcpy(begin, seg_begin, (size_t)(nseg + 1) * sizeof(long long));
+    memcpy(begin + nseg + 1, seg_group, (size_t)nseg * sizeof(int));
+    HCHECK(hipMemcpyAsync(table, host.data(), host.size(), hipMemcpyHostToDevice, s));
+    HCHECK(hipStreamSynchronize(s));      // (`host` goes away)
+    return 0;
+}
+int adam_group_args_check(const double* lr, const double* weight_decay, int ngroups, int step, const vpd_scale_state* state) {
+    if (!lr || !weight_decay) return fail("adam groups: null lr or weight_decay");
+    if (ngroups < 1 || ngroups > VPD_MAX_PARAM_GROUPS) return fail("adam groups: ngroups outside 1..16");
+    for (int i = 0; i < ngroups; ++i) {
+        if (!(lr[i] >= 0.0)) return fail("adam groups: lr must not be negative or NaN");
+        if (!(weight_decay[i] >= 0.0)) return fail("adam groups: weight_decay must not be negative or NaN");
+    }
+    if (!state && step < 1) return fail("step is 1-based");
+    if (reinterpret_cast<size_t>(state) & 3) return fail("scale state must be 4-byte aligned");
+    return 0;
+}
+
+extern "C" size_t vpd_adam_groups_bytes(int nseg) { return nseg < 1 ? 0 : vpd_adam_table_bytes(nseg); }
+
+extern "C" int vpd_adam_groups_init(const vpd_plan_t* p, void* table, const long long* seg_begin, const int* seg_group, int nseg,
+                                    long long numel, int ngroups, void* stream) {
+    if (!table) return fail("adam groups: null argument");
+    if (adam_groups_check(seg_begin, seg_group, nseg, numel, ngroups)) return -1;
+    if (reinterpret_cast<size_t>(table) & 15) return fail("adam groups: the table must be 16-byte aligned");
+    if (p) {
+        if (numel != p->nparam_padded) return fail("adam groups: numel must equal vpd_plan_param_numel");
+        if (adam_groups_check_convs(p->descs, seg_begin, nseg)) return -1;
+    }
+    return adam_groups_upload(table, seg_begin, seg_group, nseg, ngroups, (hipStream_t)stream);
+}
+
+extern "C" int vpd_adamw_step_groups(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
+                                     const void* table, const double* lr, const double* weight_decay, int ngroups, double beta1,
+                                     double beta2, double eps, int step, float gscale, const vpd_scale_state* state, void* stream) {
+    if (check_group_buffers(params, grads, adam_m, adam_v, table, numel)) return -1;
+    if (adam_group_args_check(lr, weight_decay, ngroups, step, state)) return -1;
+    LCHECK(vpd_launch_adamw_groups(params, grads, adam_m, adam_v, (long)numel,
+                                   AdamGroupArgs{table, lr, weight_decay, ngroups, beta1, beta2, eps, step, gscale, state},
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+extern "C" int vpd_plan_adamw_step_groups(vpd_plan_t* p, float* params, const float* grads, float* adam_m, float* adam_v,
+                                          long long numel, const void* table, const double* lr, const double* weight_decay,
+                                          int ngroups, double beta1, double beta2, double eps, int step,
+                                          const vpd_scale_state* state, void* workspace, void* stream) {
+    if (!p || !workspace) return fail("null argument");
+    if (check_group_buffers(params, grads, adam_m, adam_v, table, numel)) return -1;
+    if (adam_group_args_check(lr, weight_decay, ngroups, step, state)) return -1;
+    return adamw_plan_groups(p, params, grads, adam_m, adam_v, numel,
+                             AdamGroupArgs{table, lr, weight_decay, ngroups, beta1, beta2, eps, step, 1.0f / p->loss_scale, state},
+                             workspace, stream);
+}
 
 extern "C" int vpd_adamw_step(float* params, const float* grads, float* adam_m, float* adam_v, long long numel,
                               double lr, double beta1, double beta2, double eps, double weight_decay, int step,

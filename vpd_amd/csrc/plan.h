@@ -161,6 +161,14 @@ int push_pack_desc(std::vector<PackDesc>& descs, std::vector<int>& bmap_pack, st
 void build_adam_map(std::vector<PackDesc>& descs, const std::vector<int>& bmap_pack, int stem_id, long long nparam_padded,
                     std::vector<int>& bmap_adam, int& nstem_pack_blocks);
 
+// optim_step.hip: AdamW's parameter groups -- what vpd_adam_groups_init and vpd_op_adamw_pack_groups (ops.hip) share.  Each returns 0
+// or fail(): the host arrays of a segment table (layout: kernels.h); no boundary strictly inside a conv weight of `descs`; the
+// table built and copied to `table`, the stream synchronised; the hyper-parameters of a grouped step
+int adam_groups_check(const long long* seg_begin, const int* seg_group, int nseg, long long numel, int ngroups);
+int adam_groups_check_convs(const std::vector<PackDesc>& descs, const long long* seg_begin, int nseg);
+int adam_groups_upload(void* table, const long long* seg_begin, const int* seg_group, int nseg, int ngroups, hipStream_t s);
+int adam_group_args_check(const double* lr, const double* weight_decay, int ngroups, int step, const vpd_scale_state* state);
+
 inline TapSet conv_taps_fwd(const ConvInfo& c) {
     TapSet t;
     if (c.stem) {

@@ -210,6 +210,10 @@ class StudentEngine:
         # enable_grad_clip(): the device block of the gradient-norm clipping (vpd_clip_state + partial sums, int32 words)
         self._clip = None
         self._clip_max_norm = None
+        # adamw_step(groups=...): the device segment table of the last grouping (vpd_adam_groups_init) and what it was built from
+        self._group_table = None
+        self._group_table_key = None
+        self.group_table_builds = 0
 
     # -- helpers -------------------------------------------------------------
     @property
@@ -641,9 +645,51 @@ class StudentEngine:
         else:
             self.check(self.L.vpd_adamw_step(*bufs, self.adam_step, self._stream()), "vpd_adamw_step")
 
-    def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, numel=None):
+    def _adam_group_table(self, groups, numel, pl):
+        """the device segment table of `groups` over the leading `numel` elements: built on first use, rebuilt when the grouping
+        (which tensor is in which group: groups['key']) or numel changes -- never because an lr moved.  pl: the plan of a fused
+        step (the library then also checks that no boundary cuts a conv weight), or None"""
+        key = (groups["key"], numel)
+        if self._group_table_key != key:
+            if not hasattr(self.L, "vpd_plan_adamw_step_groups"):      # (absent only in an older A/B library)
+                raise RuntimeError("this libvpdhip has no AdamW parameter groups (vpd_plan_adamw_step_groups)")
+            begin, group = groups["seg_begin"], groups["seg_group"]
+            nseg = len(group)
+            table = torch.zeros(max(int(self.L.vpd_adam_groups_bytes(nseg)) // 4, 1), dtype=torch.int32, device=self.device)
+            self.check(self.L.vpd_adam_groups_init(None if pl is None else pl.handle, _ptr(table), (C.c_longlong * (nseg + 1))(*begin),
+                                                   (C.c_int * nseg)(*group), nseg, numel, len(groups["lr"]), self._stream()),
+                       "vpd_adam_groups_init")
+            self._group_table, self._group_table_key = table, key
+            self.group_table_builds += 1
+        return self._group_table
+
+    def _adamw_groups(self, pl, numel, groups, betas, eps, state):
+        """the grouped step: vpd_plan_adamw_step_groups through `pl`, or (pl None) vpd_adamw_step_groups over the flat buffers"""
+        n = len(groups["lr"])
+        table = self._adam_group_table(groups, numel, pl)
+        lr = (C.c_double * n)(*groups["lr"])
+        wd = (C.c_double * n)(*groups["weight_decay"])
+        step = 1 if state is not None else self.adam_step      # (ignored behind a device block)
+        bufs = (_ptr(self.params), _ptr(self._grads), _ptr(self.adam_m), _ptr(self.adam_v), numel, _ptr(table), lr, wd, n,
+                betas[0], betas[1], eps, step)
+        if pl is not None:
+            self.check(self.L.vpd_plan_adamw_step_groups(pl.handle, *bufs, _ptr(state), _ptr(pl.workspace), self._stream()),
+                       "vpd_plan_adamw_step_groups")
+        else:      # (the loss scale is out of the buffer already: unscale_grads_, or the device block takes it out)
+            self.check(self.L.vpd_adamw_step_groups(*bufs, 1.0, _ptr(state), self._stream()), "vpd_adamw_step_groups")
+
+    def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, numel=None, groups=None):
         """numel: leading elements of the flat buffers to update (default: all).  An optimizer built without the motion head's
-        parameters passes encoder_numel, as torch.optim.AdamW never touches tensors it was not given."""
+        parameters passes encoder_numel, as torch.optim.AdamW never touches tensors it was not given.
+
+        groups: None -- one (lr, weight_decay) for every element, the launches of always -- or torch.optim.AdamW's parameter
+        groups as FusedAdamW states them: {'lr': [..], 'weight_decay': [..] (one entry per group, at most 16; `lr` and
+        `weight_decay` above are then not read), 'seg_begin': [0, .., numel], 'seg_group': [..] (element ranges of the flat
+        buffers and their groups, same-group neighbours merged), 'key': hashable, changes with the grouping}.  The same two paths
+        (fused through the last backward's plan -- only when numel is exactly the plan's --, else flat), the same search / norm
+        pass / EMA around them.  A group with lr = 0 and weight_decay = 0 keeps its parameters bit for bit (p * 1.0f is exact,
+        fma(-0, m / den, p) = p as den >= eps > 0); its moments still move, as torch's do.  Clipping takes the norm of ALL
+        gradients, which is what clip_grad_norm_ over all the optimizer's parameters gives."""
         numel = self.param_numel if numel is None else int(numel)
         if self.adam_m is None:
             self.adam_m = torch.zeros_like(self.params)
@@ -660,6 +706,8 @@ class StudentEngine:
         pl = self._step_plan
         fused = (pl is not None and numel >= pl.param_numel and pl.packed_version == self.weights_version()
                  and os.environ.get("VPD_FUSED_ADAMW", "1") != "0")
+        if groups is not None and fused and numel != pl.param_numel:
+            fused = False      # (tensors beyond the plan's: the grouped fused entry has no flat tail; flat, and the plan repacks)
         if not fused:
             pl = None
             self.materialize_grads()
@@ -674,7 +722,9 @@ class StudentEngine:
         elif st is not None:
             self.check(self.L.vpd_op_check_finite(_ptr(self._grads), numel, _ptr(st), self._stream()), "vpd_op_check_finite")
         hyper = (lr, betas[0], betas[1], eps, weight_decay)
-        if fused:
+        if groups is not None:
+            self._adamw_groups(pl, numel, groups, betas, eps, state)
+        elif fused:
             self._adamw_fused(pl, numel, hyper, state)
         else:
             self._adamw_flat(numel, hyper, state)

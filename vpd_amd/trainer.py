@@ -30,9 +30,18 @@ class _Loss:
         return float(self._t.encoder.engine.loss_step.item())   # host sync, as in the reference
 
 
+MAX_PARAM_GROUPS = 16      # VPD_MAX_PARAM_GROUPS of the library
+
+
 class FusedAdamW(torch.optim.Optimizer):
-    """torch.optim.AdamW(params, lr) with torch defaults (train_vpd_model.py:104) as ONE
-    HIP kernel over the engine's flat fp32 buffers (weight decay on every tensor)."""
+    """torch.optim.AdamW(params, lr) with torch defaults (train_vpd_model.py:104) as ONE HIP kernel over the engine's flat fp32
+    buffers.  `params` is what torch takes: the tensors (one group, weight decay on every tensor), or a list of dicts --
+    parameter groups, at most 16, each with its own 'lr' and 'weight_decay'; `betas` and `eps` must be the same in all (ValueError
+    otherwise, here and at step()).  Every entry of `param_groups` is read at every step(), so torch.optim.lr_scheduler and
+    add_param_group work.  With more than one group every tensor of the engine must be in exactly one (the motion head may be
+    absent altogether): a tensor is held still with a group of lr=0, weight_decay=0 -- its parameters then keep every bit
+    (p * 1.0f is exact, fma(-0, m / den, p) = p), its moments still move, as torch's do.  Clipping (max_grad_norm) takes the norm of
+    all gradients, as clip_grad_norm_ over all the optimizer's parameters does; EMA and data parallelism need nothing new."""
 
     consumes_lazy_grads = True      # models.util.step(): this optimizer reads the weight-gradient kernels' own layout
 
@@ -44,12 +53,17 @@ class FusedAdamW(torch.optim.Optimizer):
         params = list(params)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._engine = engine
+        self._grouping = None           # (membership signature, the `groups` description without lr / weight_decay)
+        self._shared_hypers()
         # like torch.optim.AdamW, touch only the tensors that were passed in: without the motion head's parameters the
         # update stops where the encoder's tensors end in the flat buffers
         enc_end = engine.encoder_numel
         ptr0 = engine.params.data_ptr()
-        has_dec = any((q.data_ptr() - ptr0) // 4 >= enc_end for q in params)
+        has_dec = any((q.data_ptr() - ptr0) // 4 >= enc_end for g in self.param_groups for q in g["params"])
+        self._has_dec = has_dec
         self._numel = engine.param_numel if has_dec else enc_end
+        if len(self.param_groups) > 1:
+            self._groups()              # (a missing tensor or too many groups: refused here, not at the first step)
         if max_grad_norm is not None:
             engine.enable_grad_clip(max_grad_norm)
 
@@ -58,10 +72,57 @@ class FusedAdamW(torch.optim.Optimizer):
         DynamicLossScaler.get_scale() does"""
         return self._engine.clip_stats(reset_max)
 
+    def _shared_hypers(self):
+        """(betas, eps) of every group: the kernels share them"""
+        g0 = self.param_groups[0]
+        betas, eps = tuple(g0["betas"]), g0["eps"]
+        for i, g in enumerate(self.param_groups[1:], start=1):
+            if tuple(g["betas"]) != betas or g["eps"] != eps:
+                raise ValueError("FusedAdamW: betas and eps must be the same in every parameter group (group %d has betas=%r, eps=%r, "
+                                 "group 0 betas=%r, eps=%r); only lr and weight_decay are per group" % (i, g["betas"], g["eps"], betas, eps))
+        return betas, eps
+
+    def _groups(self):
+        """The engine's `groups` description of param_groups (StudentEngine.adamw_step) with this step's lr / weight_decay.  The
+        segments -- every tensor's offset from its data_ptr, sorted, same-group neighbours merged; padding floats belong to the
+        segment in front of them -- are rebuilt only when the membership changes (add_param_group), never for an lr."""
+        pgs = self.param_groups
+        if len(pgs) > MAX_PARAM_GROUPS:
+            raise ValueError("FusedAdamW: %d parameter groups, at most %d" % (len(pgs), MAX_PARAM_GROUPS))
+        sig = tuple(tuple(id(q) for q in g["params"]) for g in pgs)
+        if self._grouping is None or self._grouping[0] != sig:
+            eng = self._engine
+            ptr0 = eng.params.data_ptr()
+            group_of = {}
+            for gi, g in enumerate(pgs):
+                for q in g["params"]:
+                    group_of[(q.data_ptr() - ptr0) // 4] = gi
+            rows = [(name, row[2]) for name, row in eng.layout.items() if self._has_dec or not row[1]]      # (row: kind, is_dec, offset, ...)
+            known = {off for _, off in rows}
+            if any(off not in known for off in group_of):
+                raise ValueError("FusedAdamW: a parameter that is not one of the engine's tensors")
+            missing = [name for name, off in rows if off not in group_of]
+            if missing:
+                raise ValueError("FusedAdamW: with parameter groups every tensor must be in exactly one group; missing: %s%s.  A tensor is "
+                                 "held still with a group of lr=0, weight_decay=0"
+                                 % (", ".join(missing[:4]), " ... (%d in all)" % len(missing) if len(missing) > 4 else ""))
+            begin, group = [], []
+            for _, off in sorted(rows, key=lambda r: r[1]):
+                if not group or group[-1] != group_of[off]:
+                    begin.append(off if group else 0)
+                    group.append(group_of[off])
+            begin.append(self._numel)
+            self._grouping = (sig, dict(seg_begin=begin, seg_group=group, key=(tuple(begin), tuple(group), len(pgs))))
+        return dict(self._grouping[1], lr=[float(g["lr"]) for g in pgs], weight_decay=[float(g["weight_decay"]) for g in pgs])
+
     @torch.no_grad()
     def step(self, closure=None):
         g = self.param_groups[0]
-        self._engine.adamw_step(g["lr"], g["betas"], g["eps"], g["weight_decay"], numel=self._numel)
+        if len(self.param_groups) == 1:      # one group: the launches of always
+            self._engine.adamw_step(g["lr"], g["betas"], g["eps"], g["weight_decay"], numel=self._numel)
+            return
+        betas, eps = self._shared_hypers()
+        self._engine.adamw_step(g["lr"], betas, eps, g["weight_decay"], numel=self._numel, groups=self._groups())
 
     def zero_grad(self, set_to_none=False):
         # gradients live in the engine's flat buffer and are overwritten (not accumulated) by the next fused backward, which is
@@ -198,8 +259,36 @@ class ModelTrainer:
             epoch_emb_loss, epoch_emb_n = self._reducer.all_reduce_scalars(epoch_emb_loss, epoch_emb_n)
         return epoch_emb_loss / epoch_emb_n
 
-    def get_optimizer(self, learning_rate, loss_scale=None, max_grad_norm=None):
-        """max_grad_norm: clip the global gradient norm before every step (FusedAdamW); None: no clipping, nothing added.
+    def param_groups(self, weight_decay=0.01, decay_bn_bias=True, backbone_lr_scale=1.0, lr=None):
+        """torch-style parameter groups for get_optimizer(..., param_groups=...): the usual fine-tuning split.  The head is `fc.*`
+        plus the motion head, the backbone everything else; BatchNorm weights, BatchNorm biases and linear biases (kinds 1, 2, 4 of
+        vpd_plan_tensor_info) get weight_decay 0 unless decay_bn_bias; the backbone runs at backbone_lr_scale * lr (which then
+        must be given), the head at the optimizer's lr.  Empty groups are left out: the defaults give ONE group, i.e. the step of
+        always."""
+        eng = self.encoder.engine
+        if backbone_lr_scale != 1.0 and lr is None:
+            raise ValueError("param_groups(backbone_lr_scale=%r) needs lr" % (backbone_lr_scale,))
+        named = [(k, self.encoder.get_parameter(k)) for k in eng.enc_names]
+        if hasattr(self, 'fcn_time'):
+            from .models.module import DECODER_PARAM_NAMES
+            named += [("decoder." + k, self.fcn_time.get_parameter(k)) for k in DECODER_PARAM_NAMES]
+        buckets = {}      # (head, decays) -> tensors, in layout order
+        for name, q in named:
+            head = name.startswith("resnet.fc.") or name.startswith("decoder.")
+            decays = decay_bn_bias or eng.layout[name][0] not in (1, 2, 4)
+            buckets.setdefault((head and backbone_lr_scale != 1.0, decays), []).append(q)
+        out = []
+        for (head, decays), tensors in sorted(buckets.items(), key=lambda kv: (kv[0][0], not kv[0][1])):
+            g = dict(params=tensors, weight_decay=float(weight_decay) if decays else 0.0)
+            if lr is not None:
+                g["lr"] = float(lr) * (1.0 if head or backbone_lr_scale == 1.0 else float(backbone_lr_scale))
+            out.append(g)
+        return out
+
+    def get_optimizer(self, learning_rate, loss_scale=None, max_grad_norm=None, param_groups=None):
+        """param_groups: None -- one group over every tensor, torch's defaults -- or a torch-style list of dicts (param_groups()
+        above, or any other: FusedAdamW) whose entries without 'lr' run at learning_rate.
+        max_grad_norm: clip the global gradient norm before every step (FusedAdamW); None: no clipping, nothing added.
         loss_scale: None -- the default scaler of the student's element type (bf16: none; fp16: the static LossScaler, 256);
         'dynamic' -- a DynamicLossScaler (GradScaler's defaults: skip on overflow, decided on the device); a number -- a static
         LossScaler with that scale.  A scaler is an fp16 matter: asking for one on a bf16 student raises."""
@@ -224,6 +313,8 @@ class ModelTrainer:
             scaler = DynamicLossScaler(eng)
         else:
             scaler = LossScaler(eng, float(loss_scale))
+        if param_groups is not None:
+            params = list(param_groups)
         return FusedAdamW(params, eng, lr=learning_rate, max_grad_norm=max_grad_norm), scaler
 
     @contextlib.contextmanager
