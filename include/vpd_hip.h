@@ -293,6 +293,30 @@ int vpd_plan_bucket_scratch_range(const vpd_plan_t* plan, int bucket, long long*
 int vpd_plan_grads_pending(const vpd_plan_t* plan);
 int vpd_plan_materialize_grads(vpd_plan_t* plan, float* grads, void* workspace, void* stream);
 
+/* ---- gradient accumulation over micro-batches (K backward passes per optimizer step) ----
+ * The loss is a SUM over crops (train_vpd_model.py:87), so the gradient of a batch is the sum of its micro-batches' gradients: no
+ * 1/K factor.  The backward passes overwrite; a caller-owned ACCUMULATOR holds the window's sum so far, and the last micro-batch's
+ * live gradients take it in place, after which the non-finite search, the norm pass, every AdamW and the EMA run as always.
+ *
+ * vpd_op_grad_accumulate: dst[i][j] = add ? dst[i][j] + src[i][j] : src[i][j] for j < n[i], a plain fp32 add (correctly rounded,
+ * no contraction, no scaling) over `count` pairs of DEVICE float ranges of any 4-byte alignment and any length >= 0 (the fast path
+ * wants dst[i] and src[i] to share their 16-byte phase); a pair must not overlap.  add == 0 never reads dst.  dst / src / n are HOST
+ * arrays, copied into the kernel's arguments; more than 64 pairs take more than one launch.  Refused on the host, nothing launched:
+ * negative count (0 returns 0 and looks at nothing else), null dst / src / n, a null entry, negative n[i], an entry off a 4-byte
+ * boundary, dst[i] == src[i]. */
+int vpd_op_grad_accumulate(float* const* dst, const float* const* src, const long long* n, int count, int add, void* stream);
+/* Floats of the accumulator of `plan`: an image of the weight-gradient scratch behind the stem's gradients (the union of the
+ * vpd_plan_bucket_scratch_range ranges, in workspace order) followed by an image of the flat buffer (vpd_plan_param_numel). */
+long long vpd_plan_grad_accum_numel(const vpd_plan_t* plan);
+/* Acts over exactly the ranges vpd_plan_check_grads enumerates -- the scratch behind the stem and the non-conv ranges of `grads`
+ * while vpd_plan_grads_pending(), else grads[0 .. numel) -- each paired with its place in `accum`, so an accumulator holds ONE
+ * layout at a time and the caller keeps track of which.  mode 0: accum := live; mode 1: accum += live; both leave
+ * vpd_plan_grads_pending() == 0 (the gradients are consumed without the layout pass; the conv ranges of `grads` stay stale).
+ * mode 2: live += accum, the pending state left as it is: call it after the window's last backward, in the layout the accumulator
+ * was filled in.  Refused on the host: null plan / grads / accum / workspace, a mode outside 0..2, accum or grads not 16-byte
+ * aligned, an unbound workspace, numel not equal to vpd_plan_param_numel(plan). */
+int vpd_plan_grad_accumulate(vpd_plan_t* plan, float* grads, long long numel, float* accum, int mode, void* workspace, void* stream);
+
 /* Frozen BatchNorm for a TRAIN plan (the reference gets it from model.eval() with grad enabled: F.batch_norm(training=False) under
  * autograd): while on, vpd_forward_train normalises every BatchNorm with bn_running -- mean = running_mean, 1 / std =
  * 1 / sqrt(running_var + 1e-5) -- reads bn_running (now required) and leaves it unwritten; the convolutions still add their batch

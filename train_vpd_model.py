@@ -59,6 +59,10 @@ def get_args():
     parser.add_argument('--clip_grad_norm', type=float,
                         help='(this build) torch.nn.utils.clip_grad_norm_ with this max_norm before every optimizer step, decided '
                              'on the device; every epoch prints grad_norm_max and clipped_steps and adds them to loss.json')
+    parser.add_argument('--accum_steps', type=int,
+                        help='(this build) gradient accumulation: one optimizer step per this many batches (and at the last batch '
+                             'of an epoch), i.e. an effective batch of accum_steps x batch_size; the loss is a sum over crops, so '
+                             'the gradients are summed, not averaged')
     parser.add_argument('--weight_decay', type=float,
                         help='(this build) AdamW weight decay (default 0.01, torch\'s)')
     parser.add_argument('--no_bn_bias_decay', action='store_true',
@@ -79,6 +83,8 @@ def get_args():
         parser.error('--clip_grad_norm must be > 0')
     if args.ema_warmup and args.ema_decay is None:
         parser.error('--ema_warmup needs --ema_decay')
+    if args.accum_steps is not None and args.accum_steps < 1:
+        parser.error('--accum_steps must be >= 1')
     if args.weight_decay is not None and not args.weight_decay >= 0.0:
         parser.error('--weight_decay must not be negative')
     if args.backbone_lr_scale is not None and not args.backbone_lr_scale >= 0.0:
@@ -106,7 +112,8 @@ def load_dataset(dataset, dataset_kwargs, emb_dir, penn_dir, no_test_video):
 def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, motion, encoder_arch, save_dir,
          model_select_window, checkpoint_frequency, pretrained, emb_dir, penn_dir, no_test_video, min_pose_score,
          synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static', ema_decay=None,
-         ema_warmup=False, clip_grad_norm=None, weight_decay=None, no_bn_bias_decay=False, backbone_lr_scale=None):
+         ema_warmup=False, clip_grad_norm=None, weight_decay=None, no_bn_bias_decay=False, backbone_lr_scale=None,
+         accum_steps=None):
     device = 'cuda'
     # The reference builds train AND val datasets with augment=True (vpd_dataset/single_frame.py:267-272,
     # common.py:85-92): ColorJitter, mask noise, RandomResizedCrop and flips are part of the recipe, so they are the
@@ -177,7 +184,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
     if gpu_augment:
         from vpd_amd.augment import CropAugmenter
         augmenter = CropAugmenter(encoder.device, rgb_mean_std, img_dim, flow_img is not None)
-    trainer = ModelTrainer(encoder, motion, augmenter=augmenter, augment=True, ema_decay=ema_decay, ema_warmup=ema_warmup)
+    trainer = ModelTrainer(encoder, motion, augmenter=augmenter, augment=True, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                           accum_steps=1 if accum_steps is None else accum_steps)
     if world > 1:      # same initial weights on every rank (after the trainer: the motion head is initialised there)
         torch.distributed.broadcast(encoder.engine.params, 0)
         torch.distributed.broadcast(encoder.engine.bn_running, 0)
@@ -208,6 +216,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         config_ema = {} if not ema else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}      # (keys only with --ema_decay)
         if clip:
             config_ema['clip_grad_norm'] = clip_grad_norm      # (key only with --clip_grad_norm)
+        if accum_steps is not None:
+            config_ema['accum_steps'] = accum_steps      # (key only with --accum_steps)
         config_ema.update(grouping)      # (weight_decay / no_bn_bias_decay / backbone_lr_scale: keys only with their flags)
         store_json(os.path.join(save_dir, 'config.json'), {
             'num_epochs': num_epochs, 'batch_size': batch_size, 'learning_rate': learning_rate, 'img_dim': img_dim,

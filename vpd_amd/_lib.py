@@ -76,6 +76,9 @@ SIGNATURES = {
                                         C.c_double, C.c_int, C.c_float, vp, vp]),
     "vpd_plan_adamw_step_groups": (C.c_int, [vp, vp, vp, vp, vp, C.c_longlong, vp, c_dbl_p, c_dbl_p, C.c_int, C.c_double,
                                              C.c_double, C.c_double, C.c_int, vp, vp, vp]),
+    "vpd_op_grad_accumulate": (C.c_int, [C.POINTER(vp), C.POINTER(vp), c_ll_p, C.c_int, C.c_int, vp]),
+    "vpd_plan_grad_accum_numel": (C.c_longlong, [vp]),
+    "vpd_plan_grad_accumulate": (C.c_int, [vp, vp, C.c_longlong, vp, C.c_int, vp, vp]),
     "vpd_plan_bucket_scratch_range": (C.c_int, [vp, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "vpd_plan_grads_pending": (C.c_int, [vp]),
     "vpd_plan_materialize_grads": (C.c_int, [vp, vp, vp, vp]),
@@ -171,7 +174,8 @@ def lib(dtype="bf16"):
                                                                  "vpd_plan_set_bn_frozen", "vpd_plan_set_param_grads",
                                                                  "vpd_ema_update", "vpd_clip_state_bytes", "vpd_plan_grad_norm",
                                                                  "vpd_adam_groups_bytes", "vpd_adam_groups_init",
-                                                                 "vpd_adamw_step_groups", "vpd_plan_adamw_step_groups")):
+                                                                 "vpd_adamw_step_groups", "vpd_plan_adamw_step_groups",
+                                                                 "vpd_plan_grad_accum_numel", "vpd_plan_grad_accumulate")):
                 continue
             raise VpdHipError("%s lacks symbol %s declared in include/vpd_hip.h" % (name, sym)) from e
         fn.restype = res

@@ -360,8 +360,19 @@ struct EmaRanges {
 hipError_t vpd_launch_ema_update(const EmaRanges& r, double decay, int warmup, int t, int t0, const vpd_scale_state* st,
                                  hipStream_t s);
 
+// gradient accumulation (vpd_op_grad_accumulate, vpd_plan_grad_accumulate): dst[j] = add ? dst[j] + src[j] : src[j] over up to GA_MAX
+// pairs of float ranges of any alignment and length per launch, passed by value; the store mode never reads dst
+#define GA_MAX 64
+struct AccumRanges {
+    float* dst[GA_MAX];
+    const float* src[GA_MAX];
+    long n[GA_MAX];
+    int count;
+};
+hipError_t vpd_launch_grad_accum(const AccumRanges& r, bool add, hipStream_t s);
+
 #define ZR_MAX 16
-struct ZeroRanges {                     // 16-byte aligned ranges, lengths in float4
+struct ZeroRanges {                    // 16-byte aligned ranges, lengths in float4
     float* ptr[ZR_MAX];
     long n4[ZR_MAX];
     int count;

@@ -578,7 +578,7 @@ static __device__ __forceinline__ unsigned nonfinite1(float f) {
 static __device__ __forceinline__ unsigned nonfinite4(const float4& f) {
     return nonfinite1(f.x) | nonfinite1(f.y) | nonfinite1(f.z) | nonfinite1(f.w);
 }
-// What the three range walkers (check_finite_kernel, ema_update_kernel, grad_sqsum_kernel) share.  A float range of any alignment
+// What the four range walkers (check_finite_kernel, ema_update_kernel, grad_accum_kernel, grad_sqsum_kernel) share.  A float range of any alignment
 // and length, split by the 16-byte phase of `x`: `head` floats (at most three) in front, the aligned middle of `n4` float4 at
 // x + head, and the floats from `tail` on (at most three)
 struct RangeSplit { long head, n4, tail; };
@@ -851,5 +851,77 @@ hipError_t vpd_launch_zero_ranges(const ZeroRanges& z, hipStream_t s) {
     long gx = (mx + 255) / 256;
     if (gx > 512) gx = 512;
     hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)(gx < 1 ? 1 : gx), z.count), dim3(256), 0, s, z);
+    return hipGetLastError();
+}
+
+// ---- gradient accumulation (vpd_op_grad_accumulate): dst = src (ADD false) or dst += src (ADD true) over up to GA_MAX range pairs ----
+// ema_update_kernel's walk with a plain fp32 add in place of the fma: a pair is split by the 16-byte phase of `dst`, the aligned
+// middle goes in 16 KB tiles (a wave takes four consecutive 1 KB rows of each operand from one address, every load issued before the
+// first use), what is left of it one float4 per thread, `src` float by float when it does not share dst's phase.  The store mode
+// (the first micro-batch of a window) never reads dst: whatever the accumulator held, NaN included, is gone.
+static __device__ __forceinline__ float acc1(float d, float s) {
+#pragma clang fp contract(off)
+    return d + s;
+}
+static __device__ __forceinline__ f32x4 acc4(const f32x4& d, const f32x4& s) {
+    return f32x4{acc1(d.x, s.x), acc1(d.y, s.y), acc1(d.z, s.z), acc1(d.w, s.w)};
+}
+// (at most 64 registers, as ema_update_kernel: the capped grid of 2048 blocks = 8 waves per SIMD is resident at once)
+template <bool ADD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void grad_accum_kernel(const AccumRanges r) {
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nth = (long)gridDim.x * 256;
+    for (int k = 0; k < r.count; ++k) {
+        const float* x = r.src[k];
+        float* y = r.dst[k];
+        const long n = r.n[k];
+        const RangeSplit sp = split_range(y, n);
+        const long head = sp.head, n4 = sp.n4, tail = sp.tail;
+        f32x4* y4 = reinterpret_cast<f32x4*>(y + head);
+        long i = tid;
+        if ((reinterpret_cast<size_t>(x + head) & 15) == 0) {
+            const f32x4* x4 = reinterpret_cast<const f32x4*>(x + head);
+            // tiles of 1024 float4: the last element a tile touches is (tl << 10) + 3 * 256 + 63 + 192 = (tl << 10) + 1023 < n4
+            const long ntile = n4 >> 10;
+            for (long tl = blockIdx.x; tl < ntile; tl += gridDim.x) {
+                const long e = (tl << 10) + (threadIdx.x >> 6) * 256 + (threadIdx.x & 63);
+                const f32x4* xp = x4 + e;
+                f32x4* yp = y4 + e;
+                Rows4 rs = load_rows4(xp);
+                if constexpr (ADD) {
+                    Rows4 rd = load_rows4(yp);
+                    // (all eight loads are issued before the first is consumed: ema_update_kernel)
+                    asm volatile("" : "+v"(rs.a), "+v"(rs.b), "+v"(rs.c), "+v"(rs.d), "+v"(rd.a), "+v"(rd.b), "+v"(rd.c), "+v"(rd.d));
+                    yp[0] = acc4(rd.a, rs.a);
+                    yp[64] = acc4(rd.b, rs.b);
+                    yp[128] = acc4(rd.c, rs.c);
+                    yp[192] = acc4(rd.d, rs.d);
+                } else {
+                    asm volatile("" : "+v"(rs.a), "+v"(rs.b), "+v"(rs.c), "+v"(rs.d));
+                    yp[0] = rs.a;
+                    yp[64] = rs.b;
+                    yp[128] = rs.c;
+                    yp[192] = rs.d;
+                }
+            }
+            for (i += ntile << 10; i < n4; i += nth) {
+                if constexpr (ADD) y4[i] = acc4(y4[i], x4[i]); else y4[i] = x4[i];
+            }
+        } else {
+            const float* xs = x + head;
+            for (; i < n4; i += nth) {
+                const f32x4 s = {xs[4 * i], xs[4 * i + 1], xs[4 * i + 2], xs[4 * i + 3]};
+                if constexpr (ADD) y4[i] = acc4(y4[i], s); else y4[i] = s;
+            }
+        }
+        if (tid < head) y[tid] = ADD ? acc1(y[tid], x[tid]) : x[tid];
+        if (tid < n - tail) y[tail + tid] = ADD ? acc1(y[tail + tid], x[tail + tid]) : x[tail + tid];
+    }
+}
+hipError_t vpd_launch_grad_accum(const AccumRanges& r, bool add, hipStream_t s) {
+    if (r.count < 0 || r.count > GA_MAX) return hipErrorInvalidValue;
+    const int grid = vpd_grad_sqsum_grid(r.n, r.count, 2048);      // capped like ema_update_kernel's grid: 2048 blocks = 8 per CU
+    if (grid == 0) return hipSuccess;
+    if (add) hipLaunchKernelGGL(grad_accum_kernel<true>, dim3(grid), dim3(256), 0, s, r);
+    else hipLaunchKernelGGL(grad_accum_kernel<false>, dim3(grid), dim3(256), 0, s, r);
     return hipGetLastError();
 }

@@ -145,7 +145,76 @@ int launch_grad_norm(const RangeBatcher& b, double max_norm, vpd_scale_state* sr
     return 0;
 }
 
+// Gradient accumulation: (dst, src, n) pairs (empty ones are dropped), GA_MAX per launch
+struct AccumBatcher {
+    struct Pair { float* dst; const float* src; long n; };
+    std::vector<Pair> pairs;
+    void add(float* dst, const float* src, long long n) {
+        if (n > 0) pairs.push_back(Pair{dst, src, (long)n});
+    }
+    int launch(bool add_mode, void* stream) const {
+        for (size_t at = 0; at < pairs.size(); at += GA_MAX) {
+            AccumRanges r;
+            memset(&r, 0, sizeof r);
+            for (size_t i = at; i < pairs.size() && i < at + GA_MAX; ++i) {
+                r.dst[r.count] = pairs[i].dst;
+                r.src[r.count] = pairs[i].src;
+                r.n[r.count++] = pairs[i].n;
+            }
+            LCHECK(vpd_launch_grad_accum(r, add_mode, (hipStream_t)stream));
+        }
+        return 0;
+    }
+};
+
 }  // namespace
+
+// ---- gradient accumulation over micro-batches: the caller's accumulator and the live gradients of a plan ----
+extern "C" int vpd_op_grad_accumulate(float* const* dst, const float* const* src, const long long* n, int count, int add,
+                                      void* stream) {
+    if (count < 0) return fail("grad accumulate: negative count");
+    if (count == 0) return 0;
+    if (!dst || !src || !n) return fail("grad accumulate: null argument");
+    AccumBatcher b;
+    for (int i = 0; i < count; ++i) {
+        if (!dst[i] || !src[i]) return fail("grad accumulate: null range");
+        if (n[i] < 0) return fail("grad accumulate: negative length");
+        if ((reinterpret_cast<size_t>(dst[i]) | reinterpret_cast<size_t>(src[i])) & 3)
+            return fail("grad accumulate: ranges must be 4-byte aligned");
+        if (dst[i] == src[i]) return fail("grad accumulate: dst and src must differ");
+        b.add(dst[i], src[i], n[i]);
+    }
+    return b.launch(add != 0, stream);
+}
+
+// the scratch behind the stem's gradients (the stem is always unpacked into the flat buffer), in floats
+static long long accum_scratch_numel(const vpd_plan_t* p) {
+    const long long stem_end = (long long)p->stem.ntaps * p->stem.Co * p->stem.Kc;
+    return p->wg_elems > stem_end ? p->wg_elems - stem_end : 0;
+}
+extern "C" long long vpd_plan_grad_accum_numel(const vpd_plan_t* p) { return p ? accum_scratch_numel(p) + p->nparam_padded : 0; }
+
+extern "C" int vpd_plan_grad_accumulate(vpd_plan_t* p, float* grads, long long numel, float* accum, int mode, void* workspace,
+                                        void* stream) {
+    if (!p || !grads || !accum || !workspace) return fail("null argument");
+    if (mode < 0 || mode > 2) return fail("grad accumulate: mode outside 0..2");
+    if (reinterpret_cast<size_t>(accum) & 15) return fail("grad accumulate: accum must be 16-byte aligned");
+    if (check_step_call(p, workspace, numel, grads)) return -1;
+    if (numel != p->nparam_padded) return fail("grad accumulate: numel must equal vpd_plan_param_numel (the accumulator holds the plan's tensors)");
+    // every live range the step would read, paired with its image in the accumulator: [scratch behind the stem][flat buffer]
+    const long long nscratch = accum_scratch_numel(p);
+    const float* scratch = plan_wg(p, workspace) + (p->wg_elems - nscratch);
+    AccumBatcher b;
+    for (const auto& rg : step_grad_ranges(p, grads, numel, workspace).ranges) {
+        float* live = const_cast<float*>(rg.first);
+        const bool in_scratch = rg.first >= scratch && rg.first < scratch + nscratch;
+        float* image = in_scratch ? accum + (rg.first - scratch) : accum + nscratch + (rg.first - grads);
+        if (mode == 2) b.add(live, image, rg.second); else b.add(image, live, rg.second);
+    }
+    if (b.launch(mode != 0, stream)) return -1;
+    if (mode != 2) p->grads_in_scratch = false;      // consumed: the next backward's materialize is a no-op
+    return 0;
+}
 
 // ---- AdamW parameter groups: the segment table and the hyper-parameters of a grouped step (declared in plan.h) ----
 int adam_groups_check(const long long* seg_begin, const int* seg_group, int nseg, long long numel, int ngroups) {

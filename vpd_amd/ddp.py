@@ -8,6 +8,7 @@ crops (train_vpd_model.py:87), so gradients are SUMMED, not averaged.
 The pure functions at the top have no GPU dependency and are what the gloo /
 world_size-2 CPU tests exercise.
 """
+import ctypes as C
 import os
 
 import torch
@@ -96,11 +97,12 @@ def average_running_stats(bn_running, group=None):
     return bn_running
 
 
-def all_reduce_lazy(scratch_views, flat, small_idx, group=None, async_op=False):
+def all_reduce_lazy(scratch_views, flat, small_idx, group=None, async_op=False, extra=None):
     """Lazy gradients: SUM all-reduce of every bucket's scratch view (conv weight gradients in the kernels' own layout: a sum
     does not care) and of the other tensors of the flat buffer, gathered into one small message (BatchNorm, fc, motion head,
     stem: ~150 k of the 21.4 M elements).  Returns (works, finish): call finish() once the works are done to scatter the
-    small message back."""
+    small message back.  extra: a second flat buffer (the accumulator's image of `flat` at the end of an accumulation window)
+    whose gather is added to the small message before it travels."""
     works = []
     dt = wire_dtype()
     for v in scratch_views:
@@ -114,6 +116,13 @@ def all_reduce_lazy(scratch_views, flat, small_idx, group=None, async_op=False):
     if small is None:
         small = _WIRE_BUFFERS[key] = torch.empty(small_idx.numel(), dtype=flat.dtype, device=flat.device)
     torch.index_select(flat, 0, small_idx, out=small)
+    if extra is not None:
+        key2 = ("small+",) + key[1:]
+        small2 = _WIRE_BUFFERS.get(key2)
+        if small2 is None:
+            small2 = _WIRE_BUFFERS[key2] = torch.empty_like(small)
+        torch.index_select(extra, 0, small_idx, out=small2)
+        small.add_(small2)
     w = _WireWork(small, group, async_op, dt)
     if async_op:
         works.append(w)
@@ -152,9 +161,18 @@ class GradBucketReducer:
             raise RuntimeError("GradBucketReducer.reduce(lazy=%s) but the plan's last backward was %s" %
                                (lazy, "lazy (gradients pending in the scratch)" if pending else "eager (flat buffer complete)"))
         lazy = pending
-        cur = torch.cuda.current_stream(self.engine.device)
-        flat = self.engine._grads
+        eng = self.engine
+        cur = torch.cuda.current_stream(eng.device)
+        flat = eng._grads
         self.overlap = os.environ.get("VPD_DDP_OVERLAP", "1") != "0"
+        # the end of an accumulation window (the engine holds the earlier micro-batches' sum; their backwards started no
+        # collective): what travels is live + accumulator.  In line without overlap; else range by range on the comm stream,
+        # behind the bucket's event and in front of its collective
+        fold = eng._accum_count > 0
+        if fold and not self.overlap:
+            eng.fold_accumulated_grads()
+            fold = False
+        acc_scratch, acc_flat = eng.accum_images(plan) if fold else (None, None)
         if not self.overlap:
             # diagnostic: no overlap -- all buckets reduced in line after backward (RCCL's persistent kernels
             # hold CUs; whether overlapping them with 1-block-per-CU conv kernels pays is a measurement, not a given)
@@ -173,17 +191,31 @@ class GradBucketReducer:
                 if lazy:
                     v = plan.scratch_views[b]
                     if v.numel():
+                        if fold:
+                            self._fold(v, acc_scratch[b])
                         works.append(_WireWork(v, self.group, True, wire_dtype()))
                     if b == len(plan.buckets) - 1:      # everything else, once the whole backward is done
-                        w2, finish = all_reduce_lazy([], flat, plan.small_idx, self.group, async_op=True)
+                        w2, finish = all_reduce_lazy([], flat, plan.small_idx, self.group, async_op=True, extra=acc_flat)
                         works += w2
                 else:
+                    if fold and numel:
+                        self._fold(flat[off:off + numel], acc_flat[off:off + numel])
                     works += all_reduce_buckets(flat, [(off, numel)], self.group, async_op=True)
             for w in works:
                 w.wait()                 # comm stream waits for RCCL
             if finish is not None:
                 finish()
         cur.wait_stream(self.comm_stream)
+        if fold:
+            eng.drop_accumulated_grads()      # (consumed: the live ranges hold the window's sum over every rank)
+
+    def _fold(self, live, image):
+        """live += image on the current (comm) stream: vpd_op_grad_accumulate over one range"""
+        eng = self.engine
+        dst = (C.c_void_p * 1)(live.data_ptr())
+        src = (C.c_void_p * 1)(image.data_ptr())
+        n = (C.c_longlong * 1)(live.numel())
+        eng.check(eng.L.vpd_op_grad_accumulate(dst, src, n, 1, 1, eng._stream()), "vpd_op_grad_accumulate")
 
     def all_reduce_scalars(self, loss_sum, count):
         t = torch.tensor([loss_sum, float(count)], dtype=torch.float64, device=self.engine.device)

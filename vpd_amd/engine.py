@@ -107,10 +107,21 @@ class _Plan:
         # lazy gradients under data parallelism: bucket b's conv weight gradients as a view of the workspace (the kernels' own
         # layout), and the flat-buffer positions of everything else (BatchNorm, fc, motion head, the stem conv)
         self.scratch_views, self.small_idx = [], None
+        # gradient accumulation: where bucket b's scratch view lies in the accumulator's image of the scratch (floats; the bucket
+        # ranges tile the scratch behind the stem's gradients), and the floats of the whole accumulator
+        self.scratch_image_off, self.accum_numel = [], None
         if train:
+            ranges = []
             for b in range(len(self.buckets)):
                 check(L.vpd_plan_bucket_scratch_range(handle, b, C.byref(o), C.byref(m)), "vpd_plan_bucket_scratch_range")
                 self.scratch_views.append(self.workspace[o.value:o.value + 4 * m.value].view(torch.float32))
+                ranges.append((o.value, m.value))
+            base = min([o_ for o_, m_ in ranges if m_ > 0] or [0])
+            assert base % 16 == 0, "the scratch behind the stem must share the accumulator's 16-byte phase"
+            self.scratch_image_off = [(o_ - base) // 4 if m_ > 0 else 0 for o_, m_ in ranges]
+            if hasattr(L, "vpd_plan_grad_accum_numel"):      # (absent only in an older A/B library)
+                self.accum_numel = int(L.vpd_plan_grad_accum_numel(handle))
+                assert self.accum_numel == sum(m_ for _, m_ in ranges) + self.param_numel, "accumulator != scratch ranges + param_numel"
             small = [(off_, n_) for i, (kind_, _, off_, n_, _) in enumerate(rows) if kind_ != 0 or i == 0]
             self.small_ranges = small
             # the C side is the source of truth: together the scratch views (every conv but the stem) and the small ranges
@@ -146,6 +157,12 @@ class _Plan:
 class StudentEngine:
     """Flat fp32 parameter / gradient / optimizer-state buffers in the
     reference's state_dict order and layout, plus lazily created plans."""
+
+    # accumulate_grads() / fold_accumulated_grads(): the sum of a window's micro-batches so far.  The accumulator (allocated on
+    # first use: a K = 1 run never has one) holds an image of the weight-gradient scratch and one of the flat buffer
+    _accum = None
+    _accum_count = 0          # micro-batches held
+    _accum_layout = None      # "scratch" (lazy backwards: scratch + the small ranges of the flat buffer) | "flat"
 
     def __init__(self, arch, c_in, emb_dim, device="cuda", dtype="bf16"):
         if not torch.cuda.is_available():
@@ -324,6 +341,64 @@ class StudentEngine:
         if pl is not None and pl.handle and self.L.vpd_plan_grads_pending(pl.handle):
             self.check(self.L.vpd_plan_materialize_grads(pl.handle, _ptr(self._grads), _ptr(pl.workspace), self._stream()),
                   "vpd_plan_materialize_grads")
+
+    # -- gradient accumulation over micro-batches ---------------------------------------
+    def _accum_check(self, pl, what):
+        """the plan whose live gradients `what` is about to pair with the accumulator, and the layout they are in"""
+        if pl is None or not pl.handle:
+            raise RuntimeError("%s without a preceding backward" % what)
+        if pl.accum_numel is None:      # (absent only in an older A/B library)
+            raise RuntimeError("this libvpdhip has no gradient accumulation (vpd_plan_grad_accumulate)")
+        layout = "scratch" if self.L.vpd_plan_grads_pending(pl.handle) else "flat"
+        if self._accum_count:
+            if layout != self._accum_layout:
+                raise RuntimeError("%s: the accumulator holds %d micro-batch(es) in the %s layout, the live gradients are in the %s "
+                                   "layout (lazy and eager backwards do not mix inside a window)"
+                                   % (what, self._accum_count, self._accum_layout, layout))
+            if pl.accum_numel != self._accum.numel():
+                raise RuntimeError("%s: the accumulator holds %d floats, this plan's takes %d"
+                                   % (what, self._accum.numel(), pl.accum_numel))
+        return layout
+
+    def _accum_call(self, pl, mode):
+        self.check(self.L.vpd_plan_grad_accumulate(pl.handle, _ptr(self._grads), pl.param_numel, _ptr(self._accum), mode,
+                                                   _ptr(pl.workspace), self._stream()), "vpd_plan_grad_accumulate")
+
+    def accumulate_grads(self):
+        """A non-final micro-batch of an accumulation window: the live gradients of the last backward -- in whichever layout it
+        left them -- are stored into the accumulator (first micro-batch of the window: the store never reads it) or added onto
+        it, one streaming launch; the pending state is consumed without the layout pass.  The loss is a sum over crops, so the
+        window's sum is the big batch's gradient: no 1/K."""
+        pl = self._step_plan
+        layout = self._accum_check(pl, "accumulate_grads()")
+        if self._accum is None or (not self._accum_count and self._accum.numel() != pl.accum_numel):
+            self._accum = torch.zeros(pl.accum_numel, dtype=torch.float32, device=self.device)
+        self._accum_call(pl, 1 if self._accum_count else 0)
+        self._accum_count += 1
+        self._accum_layout = layout
+
+    def fold_accumulated_grads(self):
+        """The final micro-batch: live += accumulator, in place, in the layout the last backward left; everything that reads the
+        live gradients afterwards (search, norm pass, AdamW, a torch optimizer through `grads`) runs unchanged.  A no-op when
+        nothing is held; the accumulator is empty afterwards.  adamw_step() calls it first."""
+        if not self._accum_count:
+            return
+        pl = self._step_plan
+        self._accum_check(pl, "fold_accumulated_grads()")
+        self._accum_call(pl, 2)
+        self._accum_count = 0
+
+    def accum_images(self, pl):
+        """(per-bucket views of the accumulator's image of the scratch, its image of the flat buffer) for a reducer that folds
+        bucket by bucket on its own stream; checks layout and size as fold_accumulated_grads() does"""
+        self._accum_check(pl, "GradBucketReducer.reduce()")
+        nscratch = pl.accum_numel - pl.param_numel
+        views = [self._accum[a:a + v.numel()] for a, v in zip(pl.scratch_image_off, pl.scratch_views)]
+        return views, self._accum[nscratch:nscratch + pl.param_numel]
+
+    def drop_accumulated_grads(self):
+        """Forget what the accumulator holds (the memory stays)."""
+        self._accum_count = 0
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -691,6 +766,7 @@ class StudentEngine:
         fma(-0, m / den, p) = p as den >= eps > 0); its moments still move, as torch's do.  Clipping takes the norm of ALL
         gradients, which is what clip_grad_norm_ over all the optimizer's parameters gives."""
         numel = self.param_numel if numel is None else int(numel)
+        self.fold_accumulated_grads()      # (an accumulation window's sum first: nothing is launched when none is held)
         if self.adam_m is None:
             self.adam_m = torch.zeros_like(self.params)
             self.adam_v = torch.zeros_like(self.params)

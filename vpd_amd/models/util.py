@@ -124,9 +124,15 @@ class DynamicLossScaler(LossScaler):
                   "vpd_scale_state_update")
 
 
-def step(optimizer, scaler, loss):
+def step(optimizer, scaler, loss, accumulate=False):
     """The reference's step() (models/util.py:50-58): loss.backward(); optimizer.step() -- or, with a scaler,
     scaler.scale(loss).backward(); scaler.step(optimizer); scaler.update() -- then optimizer.zero_grad().
+
+    accumulate=True: a non-final micro-batch of a gradient-accumulation window -- scaler.scale(loss) when a scaler is given, the
+    backward, then the gradients go into the engine's accumulator (StudentEngine.accumulate_grads); optimizer.step(), scaler.step(),
+    scaler.update() and zero_grad() are NOT called, so the scale stays fixed across the window, as torch's does.  The window's last
+    call (accumulate=False) takes the sum: FusedAdamW's step folds it in by itself, any other optimizer gets it folded into the flat
+    buffer before optimizer.step() / scaler.step().  The loss is a sum over crops: no 1/K.
 
     The bf16 build computes with fp32 accumulation and needs no loss scaling: get_optimizer() returns scaler=None there; a student
     built with dtype="fp16" (the reference's own GPU precision) gets a LossScaler (static) or a DynamicLossScaler."""
@@ -137,12 +143,24 @@ def step(optimizer, scaler, loss):
     # step() accepts any: torch.optim.AdamW over encoder.parameters(), a wrapper that looks at p.grad) gets the plain
     # loss.backward(), which completes every p.grad view of the flat gradient buffer.
     lazy = _LAZY and getattr(optimizer, "consumes_lazy_grads", False) and hasattr(loss, "backward_for_step")
+    if accumulate:
+        if not hasattr(loss, "backward_for_accumulation"):
+            raise TypeError("step(accumulate=True) takes the loss object of ModelTrainer's forward (a torch loss accumulates into "
+                            ".grad by itself: call loss.backward())")
+        (loss if scaler is None else scaler.scale(loss)).backward_for_accumulation(lazy=bool(lazy))
+        return
+    # the sum of the window's earlier micro-batches, for an optimizer that reads p.grad (FusedAdamW's step folds by itself)
+    fold = None if lazy or not hasattr(loss, "_t") else loss._t.encoder.engine.fold_accumulated_grads
     if scaler is None:
         (loss.backward_for_step if lazy else loss.backward)()
+        if fold is not None:
+            fold()
         optimizer.step()
     else:
         scaled = scaler.scale(loss)
         (scaled.backward_for_step if lazy else scaled.backward)()
+        if fold is not None:
+            fold()
         scaler.step(optimizer)
         scaler.update()
     optimizer.zero_grad()

@@ -26,11 +26,37 @@ class _Loss:
         between (reference models/util.py:52-58), so the conv weight gradients may stay in the kernels' layout."""
         self._t._backward(lazy=True)
 
+    def backward_for_accumulation(self, lazy=False):
+        """A non-final micro-batch of models.util.step(..., accumulate=True): the backward (no collective under data parallelism),
+        then the live gradients go into the engine's accumulator."""
+        self._t._backward(lazy=lazy, final=False)
+        self._t.encoder.engine.accumulate_grads()
+
     def item(self):
         return float(self._t.encoder.engine.loss_step.item())   # host sync, as in the reference
 
 
 MAX_PARAM_GROUPS = 16      # VPD_MAX_PARAM_GROUPS of the library
+
+
+def accumulation_schedule(batches, accum_steps):
+    """(batch, step_now) for every batch of `batches`: step_now on every accum_steps-th batch and on the LAST one, found with a
+    one-item look-ahead (a loader need not know its length), so that no gradient crosses an epoch boundary and none is dropped.
+    accum_steps = 1: every batch steps.  A pure function of the iterable."""
+    k = int(accum_steps)
+    if k < 1:
+        raise ValueError("accum_steps must be >= 1, not %r" % (accum_steps,))
+    it = iter(batches)
+    try:
+        cur = next(it)
+    except StopIteration:
+        return
+    i = 0
+    for nxt in it:
+        i += 1
+        yield cur, i % k == 0
+        cur = nxt
+    yield cur, True
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -129,14 +155,23 @@ class FusedAdamW(torch.optim.Optimizer):
         # what zero_grad-after-every-step amounts to: no memory is touched.  The autograd path (RGBF_EmbeddingModel.forward)
         # accumulates as torch does: it is told here that the buffer counts as cleared
         self._engine._grads_cleared = True
+        self._engine._accum_count = 0      # the accumulation window is over (after a step the fold emptied it already)
         return None
 
 
 class ModelTrainer:
     """Class for training the encoder. Discarded after training"""
 
-    def __init__(self, encoder, motion, process_group=None, augmenter=None, augment=True, ema_decay=None, ema_warmup=False):
-        """ema_decay: keep an exponential moving average of the weights (and of the BatchNorm running statistics) with this
+    accum_steps = 1
+
+    def __init__(self, encoder, motion, process_group=None, augmenter=None, augment=True, ema_decay=None, ema_warmup=False,
+                 accum_steps=1):
+        """accum_steps: K >= 1 micro-batches per optimizer step (gradient accumulation).  epoch() steps on every K-th batch and on
+        the last batch of the loader; in between the gradients are summed in the engine's accumulator (no 1/K: the loss is a sum
+        over crops), BatchNorm statistics are per micro-batch, a loss scale stays fixed across the window, and under data
+        parallelism only the window's last backward all-reduces.  1 (the default) is the step of always.
+
+        ema_decay: keep an exponential moving average of the weights (and of the BatchNorm running statistics) with this
         decay; ema_warmup: timm's rule min(decay, (1 + t) / (10 + t)).  Averaging starts in get_optimizer() -- from the weights as
         they stand then, i.e. after a checkpoint was loaded -- and every fused optimizer step ends with one more launch
         (StudentEngine.enable_ema).  ema_weights() evaluates with the average, save_model(..., ema=True) writes it.  Under data
@@ -154,6 +189,9 @@ class ModelTrainer:
             raise ValueError("ema_decay must be in [0, 1], not %r" % (ema_decay,))
         self.ema_decay = None if ema_decay is None else float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
+        if int(accum_steps) != accum_steps or int(accum_steps) < 1:
+            raise ValueError("accum_steps must be an integer >= 1, not %r" % (accum_steps,))
+        self.accum_steps = int(accum_steps)
         if motion:
             self.fcn_time = FCNet(encoder.engine, encoder.emb_dim, [128, 128], 2 * encoder.emb_dim, dropout=0)
         self._reducer = None
@@ -196,9 +234,14 @@ class ModelTrainer:
             eng.forward_eval(None, gt, motion=self.motion, staged=staged)
         return _Loss(self)
 
-    def _backward(self, lazy=False):
+    def _backward(self, lazy=False, final=True):
+        """final=False: a non-final micro-batch of an accumulation window -- under data parallelism the backward records no bucket
+        events and starts no collective (the window's last backward reduces the folded sum: 1/K of the all-reduces)"""
         eng = self.encoder.engine
-        if self._reducer is not None:
+        if self._reducer is not None and not final:
+            lazy = lazy and os.environ.get("VPD_DDP_LAZY", "1") != "0"      # (one layout per window: the final backward's rule)
+            eng.backward(lazy=lazy)
+        elif self._reducer is not None:
             nb = len(eng._last[0].buckets) if eng._last is not None else 0      # (backward() raises without a forward)
             # lazy gradients stay on under data parallelism: a SUM all-reduce is layout-agnostic, so the reducer sums the
             # weight-gradient scratch ranges + the small tensors of the flat buffer (VPD_DDP_LAZY=0: flat buffer, eager unpack)
@@ -232,8 +275,12 @@ class ModelTrainer:
             self.fcn_time.eval() if optimizer is None else self.fcn_time.train()
 
         eng.loss_accum.zero_()          # the epoch accumulator of train_vpd_model.py:73,93 lives on device
+        if optimizer is not None:
+            # every train epoch ends with a step, so nothing is held here unless a window was abandoned (an exception in the
+            # middle of an epoch, accumulate=True by hand without a final step): its sum must not leak into this epoch's first window
+            eng._accum_count = 0
         epoch_emb_n = 0
-        for batch in data_loader:
+        for batch, step_now in accumulation_schedule(data_loader, self.accum_steps if optimizer is not None else 1):
             if 'rgb_u8' in batch:
                 n = batch['rgb_u8'].shape[0]
                 loss = self._forward_loss_raw(batch, train=optimizer is not None)
@@ -241,7 +288,7 @@ class ModelTrainer:
                 n = batch['img'].shape[0]
                 loss = self._forward_loss(batch['img'], batch['emb'], train=optimizer is not None)
             if optimizer is not None:
-                step(optimizer, scaler, loss)
+                step(optimizer, scaler, loss, accumulate=not step_now)
             epoch_emb_n += n
             if progress_cb is not None:
                 progress_cb(n)
@@ -315,6 +362,7 @@ class ModelTrainer:
             scaler = LossScaler(eng, float(loss_scale))
         if param_groups is not None:
             params = list(param_groups)
+        eng._accum_count = 0      # a new optimizer begins a new accumulation window (an abandoned one is forgotten)
         return FusedAdamW(params, eng, lr=learning_rate, max_grad_norm=max_grad_norm), scaler
 
     @contextlib.contextmanager
