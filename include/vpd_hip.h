@@ -456,7 +456,8 @@ int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, in
  * rows f64 [4][2][C] hold the per-channel sum / sum of squares of z as the producing convolution's epilogue left them;
  * writes mean, rstd, scale = gamma rstd, shift = beta - mean scale, updates running_mean / running_var (momentum, unbiased
  * variance) when given, and out = relu?(scale z + shift (+ residual)) into the bf16 NHWC tensor padded by 1
- * ([n][H+2][W+2][C]; residual: same layout or null), plus the ReLU bit map [n H W][C/8] when mask_bits is given. */
+ * ([n][H+2][W+2][C]; residual: same layout or null), plus the ReLU bit map [n H W][C/8] when mask_bits is given.
+ * n, H, W >= 1, C a multiple of 8 in 8..4096 (vpd_op_bn_forward2 likewise): anything else is refused before the launch. */
 int vpd_op_bn_forward(const void* z_bf16, const double* rows, const float* gamma, const float* beta, float* running_mean,
                       float* running_var, float* mean, float* rstd, float* scale, float* shift, const void* res_padded_bf16,
                       void* out_padded_bf16, unsigned char* mask_bits, int n, int H, int W, int C, int relu, float momentum,
@@ -485,6 +486,12 @@ int vpd_op_bn_forward2(const void* z_bf16, const double* rows, const float* gamm
  * running_mean / running_var (both or neither) as vpd_op_bn_forward does. */
 int vpd_op_bn_finalize(double* rows, const float* gamma, const float* beta, float* running_mean, float* running_var, float* mean,
                        float* rstd, float* scale, float* shift, int count, int C, float momentum, float eps, void* stream);
+/* The apply launch of the VPD_FUSED_BN=0 path (bn_apply_kernel; test-only addition under ABI 5, tests/test_bn_forward_ops_gpu.py):
+ * out = relu?(scale z + shift (+ residual)) into the NHWC tensor padded by 1, from coefficient vectors the caller supplies.
+ * res_kind 0: no residual; 1: res padded by 1 like out; 2: res dense like z with its own rscale / rshift (a down-sampling branch).
+ * n, H, W >= 1, C a multiple of 8 in 8..4096; refusals return non-zero with a message before anything is launched. */
+int vpd_op_bn_apply(const void* z_bf16, const float* scale, const float* shift, const void* res_bf16, const float* rscale,
+                    const float* rshift, int res_kind, void* out_padded_bf16, int n, int H, int W, int C, int relu, void* stream);
 /* BatchNorm backward, finalize + apply in one launch (bn_bwd_apply_fused_kernel): rows f64 [4][2][C] hold sum g and sum g * z
  * with g = dy * mask (what vpd_op_conv2d_bnsums leaves there); writes dz = gamma rstd (g - mean(g) - xhat mean(g xhat)) into
  * the bf16 NHWC tensor padded by 1, dgamma = sum g xhat, dbeta = sum g. */

@@ -96,6 +96,7 @@ SIGNATURES = {
     "vpd_op_set_bn_frozen": (C.c_int, [C.c_int]),
     "vpd_op_bn_forward2": (C.c_int, [vp] * 22 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
     "vpd_op_bn_finalize": (C.c_int, [vp] * 9 + [C.c_int, C.c_int, C.c_float, C.c_float, vp]),
+    "vpd_op_bn_apply": (C.c_int, [vp] * 6 + [C.c_int, vp] + [C.c_int] * 5 + [vp]),
     "vpd_op_bn_backward_apply": (C.c_int, [vp] * 10 + [C.c_int] * 4 + [vp]),
     "vpd_op_bn_backward_apply2": (C.c_int, [vp] * 18 + [C.c_int] * 4 + [vp]),
     "vpd_op_conv1x1_bn": (C.c_int, [C.c_int, vp, vp] + [C.c_int] * 6 + [vp] * 5 + [C.c_float, C.c_float] + [vp] * 12),

@@ -140,6 +140,7 @@ extern "C" int vpd_op_bn_forward(const void* z, const double* rows, const float*
                                  void* out, unsigned char* mask_bits, int n, int H, int W, int C, int relu, float momentum,
                                  float eps, void* stream) {
     if (!z || !rows || !gamma || !beta || !mean || !rstd || !scale || !shift || !out) return fail("null argument");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || C > 4096) return fail("bad shape");
     BnApplyParams a = vpd_bn_apply_params((const bf16_t*)z, res ? 1 : 0, (const bf16_t*)res, (bf16_t*)out, n, H, W, C, relu);
     a.mask_out = mask_bits;
     const BnFusedFwd f = op_fused_fwd(op_fwd_side(rows, gamma, beta, running_mean, running_var, mean, rstd, scale, shift), a.M, momentum, eps);
@@ -162,7 +163,7 @@ extern "C" int vpd_op_bn_forward2(const void* z, const double* rows, const float
     const int nrun = (running_mean != nullptr) + (running_var != nullptr) + (running_mean2 != nullptr) + (running_var2 != nullptr);
     if (nrun != 0 && nrun != 4) return fail("running statistics of both BatchNorms or of neither");
     if (g_op_bn_frozen && nrun != 4) return fail("a frozen BatchNorm needs running_mean and running_var");
-    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8) return fail("bad shape");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || C > 4096) return fail("bad shape");
     BnApplyParams a = vpd_bn_apply_params((const bf16_t*)z, 2, (const bf16_t*)z2, (bf16_t*)out, n, H, W, C, relu);
     a.mask_out = mask_bits;
     BnFusedFwd f = op_fused_fwd(op_fwd_side(rows, gamma, beta, running_mean, running_var, mean, rstd, scale, shift), a.M, momentum, eps);
@@ -182,6 +183,22 @@ extern "C" int vpd_op_bn_finalize(double* rows, const float* gamma, const float*
     if (count < 1 || C < 1) return fail("bad shape");
     LCHECK(vpd_launch_bn_finalize(rows, VPD_STAT_ROWS, C, (float)count, gamma, beta, running_mean, running_var, momentum, eps, mean,
                                   rstd, scale, shift, (hipStream_t)stream, g_op_bn_frozen != 0));
+    return 0;
+}
+
+// the VPD_FUSED_BN=0 path's apply launch (bn_apply_kernel) on coefficient vectors the caller supplies: no statistics are involved.
+// res_kind 0: out = relu?(scale z + shift); 1: + res, padded by 1 like out; 2: + rscale res + rshift, res dense like z
+extern "C" int vpd_op_bn_apply(const void* z, const float* scale, const float* shift, const void* res, const float* rscale,
+                               const float* rshift, int res_kind, void* out, int n, int H, int W, int C, int relu, void* stream) {
+    if (!z || !scale || !shift || !out) return fail("null argument");
+    if (res_kind < 0 || res_kind > 2) return fail("res_kind is 0, 1 or 2");
+    if (res_kind != 0 && !res) return fail("null argument");
+    if (res_kind == 2 && (!rscale || !rshift)) return fail("null argument");
+    if (n < 1 || H < 1 || W < 1 || C < 8 || C % 8 || C > 4096) return fail("bad shape");
+    if ((long long)n * H * W >= (1ll << 31)) return fail("bad shape");
+    BnApplyParams a = vpd_bn_apply_params((const bf16_t*)z, res_kind, (const bf16_t*)res, (bf16_t*)out, n, H, W, C, relu);
+    a.scale = scale; a.shift = shift; a.rscale = rscale; a.rshift = rshift;
+    LCHECK(vpd_launch_bn_apply(a, (hipStream_t)stream));
     return 0;
 }
 
