@@ -452,6 +452,10 @@ int vpd_op_conv2d_bnsums2(const void* x_bf16, const void* w_bf16, void* y_bf16, 
  * of the busiest block, flags & 8: a kernel takes the sums}. */
 int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub, int oph,
                            int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags, int* out12);
+/* ... and, for the same arguments, whether the launch runs conv3x3_pws_kernel with its interior loaders (tiles of whole images on the
+ * compile-time-geometry instantiations, VPD_PWS_INTERIOR): *out = 1 or 0. */
+int vpd_op_conv2d_interior(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub, int oph,
+                           int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags, int* out);
 /* BatchNorm2d in training mode as the plan runs it (one launch: finalize + apply; models/module.py:41-43 + nn.BatchNorm2d):
  * rows f64 [4][2][C] hold the per-channel sum / sum of squares of z as the producing convolution's epilogue left them;
  * writes mean, rstd, scale = gamma rstd, shift = beta - mean scale, updates running_mean / running_var (momentum, unbiased

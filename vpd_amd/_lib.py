@@ -92,6 +92,7 @@ SIGNATURES = {
     "vpd_op_conv2d_bnsums": (C.c_int, [vp] * 6 + [C.c_int] * 8 + [c_int_p, C.c_int, vp]),
     "vpd_op_conv2d_bnsums2": (C.c_int, [vp] * 8 + [C.c_int] * 8 + [c_int_p, vp]),
     "vpd_op_conv2d_dispatch": (C.c_int, [C.c_int] * 16 + [c_int_p, C.c_int, C.c_int, c_int_p]),
+    "vpd_op_conv2d_interior": (C.c_int, [C.c_int] * 16 + [c_int_p, C.c_int, C.c_int, c_int_p]),
     "vpd_op_bn_forward": (C.c_int, [vp] * 13 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),
     "vpd_op_set_bn_frozen": (C.c_int, [C.c_int]),
     "vpd_op_bn_forward2": (C.c_int, [vp] * 22 + [C.c_int] * 5 + [C.c_float, C.c_float, vp]),

@@ -1531,6 +1531,8 @@ static bool halo_geom(const ConvParams& p, int BM, int hrows_max, HaloGeom* g) {
     //  ragged tail and its hipGraph launch agree bit for bit, tests/test_fullsize_gpu.py -- and the rotation is a function of the tile index)
     g->rot = vpd_switches().pws_rot && p.Kc > 64 && conv_ep_mode(p) != 3;
     g->rnch = 1.0f / (float)(p.Kc / 64);
+    g->interior = 0;                                           // (vpd_conv_dispatch: only where the kernel has the mode)
+    g->rHp = 1.0f / (float)(H + 2);
     return g->NHP <= hrows_max;
 }
 
@@ -1664,6 +1666,11 @@ ConvDispatch vpd_conv_dispatch(const ConvParams& p, HaloGeom* g) {
         d.tiles_per_block = (sg.MT + sg.lanes - 1) / sg.lanes;
         bool flip;
         d.geo = vpd_switches().pws_geo ? vpd_pws_geo_width(bm, bn, hrows, ns, nmw, p, *g, &flip) : 0;
+        // interior loaders (conv_pws.h): the compile-time-geometry kernels on tiles of whole images -- a border pixel then has the
+        // same halo slot in every tile.  W = 4: three instructions per 6 x 6 padded image, H = 4 only.  Everything else (tiles that
+        // cut images, the generic loop, the eight-wave tiles, conv3x3_ws_kernel) keeps the border-reading loader.
+        g->interior = vpd_switches().pws_interior && d.geo && (bm / p.Ws) % p.Hs == 0 && (p.Ws != 4 || p.Hs == 4);
+        d.interior = g->interior;
     };
     switch (d.kclass) {
         case 0: {

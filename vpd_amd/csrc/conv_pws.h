@@ -53,6 +53,10 @@ struct HaloGeom {
     // forward keeps chunk order 0, 1, 2 ... for every tile, so that an embedding does not depend on the crop's position in its batch.
     int rot;             // 1: on (VPD_PWS_ROT=0 turns it off)
     float rnch;          // 1 / nchunks
+    // Interior loaders (conv3x3_pws_kernel, compile-time-geometry instantiations only; "interior mode" in pws_body): the tile holds
+    // whole images, so the halo buffers' border slots are zeroed once per launch and the loaders stream interior pixels only
+    int interior;        // 1: on (VPD_PWS_INTERIOR=0, a tile that cuts images or a kernel without the mode: 0)
+    float rHp;           // 1 / (H + 2)
 };
 
 typedef const void __attribute__((address_space(1)))* gptr_t;
@@ -232,7 +236,15 @@ struct PwsSched {
 
 // WC > 0 (round 6): the image width is a compile-time constant (WC = W; FLIP: the data gradient's mirrored taps), so a pixel
 // fragment's LDS address is a per-lane register of the launch + an IMMEDIATE per tap -- see "compile-time geometry" below
-template <int BM, int BN, int HROWS, int NS, int EPM, int NMW, bool PIPE, int WC = 0, bool FLIP = false>
+//
+// INT (interior mode; WC > 0 and tiles of whole images, HaloGeom::interior): the padded NHWC layout makes the border-reading loader
+// copy every image's zero border with its pixels -- (W + 2)(H + 2) / (W H) = 1.27x / 1.56x / 2.25x the input at W = 16 / 8 / 4 -- and
+// the loaders' DMA is bounded by wave-instructions, not bytes.  A tile of whole images puts every border pixel at the
+// same slot of the halo buffers for every tile and chunk, and nothing but the halo DMA writes them: the MFMA waves zero those
+// slots (and the slack up to HROWS) once, while the prologue's burst is in flight, and a halo is BM / 8 one-KB instructions over
+// interior row segments (W = 4: three per image over padded pixels 7 .. 30, whose borders still come from memory) instead of
+// HROWS / 8 over consecutive padded pixels.  Every interior pixel lands where it landed before, under the same swizzle key: no bit changes.
+template <int BM, int BN, int HROWS, int NS, int EPM, int NMW, bool PIPE, int WC = 0, bool FLIP = false, bool INT = false>
 static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloGeom& g, const PwsGrid& sg) {
     constexpr int WN = BN / 64;
     constexpr int WM = NMW / WN;
@@ -241,7 +253,7 @@ static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloG
     constexpr int WSTAGE = BN * 64;                  // elements
     constexpr int HBUF = HROWS * 64;
     constexpr int W_PER = BN / 32;                   // weight-tile DMA instructions per loader wave and step
-    constexpr int HINSTR = HROWS / 8;                // 1-KiB LDS-DMA instructions per halo
+    constexpr int HINSTR = !INT ? HROWS / 8 : WC == 4 ? BM / 16 * 3 : BM / 8;      // 1-KiB LDS-DMA instructions per halo
     constexpr int HPASS = (HINSTR + 3) / 4;          // ... per loader wave (the last one may be a filler when HINSTR % 4 != 0)
     constexpr int A = NS - 2;                        // weight bundles beyond the two readable steps
     constexpr int HT = 9 - A;                        // READYs of a chunk behind which the next chunk's halo slices may be issued
@@ -249,6 +261,7 @@ static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloG
     static_assert(HROWS % 8 == 0 && A >= 1 && HT >= 1 && SC::max_inflight() < 64, "ring / vmcnt geometry");
     static_assert(EPM == 0 || EPM == 1 || EPM == 2 || EPM == 3 || EPM == 6 || EPM == 7 || EPM == 8, "epilogue mode");
     static_assert(WC == 0 || NMW == 4 || NMW == 8, "compile-time geometry: four or eight MFMA waves (always the two-set fragment pipeline)");
+    static_assert(!INT || ((WC == 16 || WC == 8 || WC == 4) && HINSTR % 4 == 0), "interior mode: compile-time width, no filler instruction");
     constexpr unsigned OFF_W = 2u * HBUF * 2u;                       // bytes
     constexpr unsigned OFF_DUMP = OFF_W + NS * WSTAGE * 2u;
     constexpr unsigned OFF_RED = OFF_DUMP + 1024u;
@@ -294,9 +307,24 @@ static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloG
         // the launch: hoff[k] for the k-th halo instruction of this wave (halo pixel hp = (lw + 4k) * 8 + lrow, row hr, column xp
         // of the padded tile: hp * Ci elements + the 16-byte piece XOR-ed with key(hr, xp), HaloGeom), wrow[k] for its k-th weight
         // row.  They are computed once, in the prologue, each right in front of its first use.
+        // Interior mode: instruction j = lw + 4k copies eight consecutive pixels of ONE interior row (W = 16: half a row; W = 4: the
+        // j % 3-th eight of an image's padded pixels 7 .. 30) from halo pixel hbase[k] on -- wave-uniform, kept in SGPRs.
         unsigned hoff[HPASS];
+        int hbase[INT ? HPASS : 1];
+        auto halo_pix0 = [&](int k) __attribute__((always_inline)) {
+            const int j = lw + 4 * k;
+            if constexpr (!INT) return j * 8;
+            else if constexpr (WC == 4) { const int img = j / 3; return img * 36 + 7 + (j - img * 3) * 8; }
+            else {
+                const int r = WC == 16 ? j >> 1 : j;                 // output row of the tile
+                const int img = vpd_fdiv(r, g.rH);
+                return __builtin_amdgcn_readfirstlane((img * (H + 2) + (r - img * H) + 1) * Wp + 1 + (WC == 16 ? (j & 1) * 8 : 0));
+            }
+        };
         auto halo_off = [&](int k) __attribute__((always_inline)) {
-            const int hp = (lw + 4 * k) * 8 + lrow;
+            const int hp0 = halo_pix0(k);
+            if constexpr (INT) hbase[k] = hp0;
+            const int hp = hp0 + lrow;
             const int hr = vpd_fdiv(hp, g.rWp);
             const int key = ((hp - hr * Wp) & g.kmask) ^ ((hr & g.rowmask) << g.kshift);
             return (unsigned)(hp * Ci * 2 + ((piece ^ key) << 4));
@@ -318,11 +346,12 @@ static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloG
         auto effcc = [&](int cc, int r) __attribute__((always_inline)) { const int e = cc + r; return e >= nchunks ? e - nchunks : e; };
         auto halo_instr = [&](int gp0, int cc, int buf, int k) __attribute__((always_inline)) {      // (cc: effective chunk)
             if (HINSTR % 4 != 0 && lw + 4 * k >= HINSTR) { pws_dma16(p.w, lds0 + OFF_DUMP); return; }      // filler: keeps the counts
-            const unsigned dst = lds0 + (unsigned)buf * (HBUF * 2u) + (unsigned)(lw + 4 * k) * 1024u;
-            if (gp0 + HINSTR * 8 <= g.total_pix) {               // (wave-uniform) the whole halo lies inside the tensor
+            const int hp0 = INT ? hbase[k] : (lw + 4 * k) * 8;
+            const unsigned dst = lds0 + (unsigned)buf * (HBUF * 2u) + (unsigned)hp0 * 128u;
+            if (gp0 + (INT ? g.NHP : HINSTR * 8) <= g.total_pix) {      // (wave-uniform) the whole halo lies inside the tensor
                 pws_dma16s(reinterpret_cast<const char*>(p.x) + ((size_t)gp0 * Ci + cc * 64) * 2, hoff[k], dst);
             } else {                                             // the tensor's last tile: rows beyond it re-read its last pixel
-                const int hp = (lw + 4 * k) * 8 + lrow;
+                const int hp = hp0 + lrow;
                 const int gp = gp0 + hp < g.total_pix ? gp0 + hp : g.total_pix - 1;
                 const unsigned swz = (hoff[k] - (unsigned)(hp * Ci * 2)) >> 1;       // (piece ^ key) << 3, in elements
                 pws_dma16(p.x + (size_t)gp * Ci + cc * 64 + swz, dst);
@@ -408,6 +437,37 @@ static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloG
     const int wn = wave / WM;
     const int fr = lane & 15;
     const int fq = lane >> 4;
+    // Interior mode: zeros into every slot of BOTH halo buffers that no interior instruction writes -- x and y borders and the slack
+    // behind the last image -- once per launch, landed before this wave's first READY.  The MFMA waves write them: they have nothing
+    // to do until the prologue's burst has landed, while the loaders stall on the issue of that very burst (written by the loader
+    // waves behind their prologue, the zeros stood in front of the first READY: +0.8 .. 1.0 us on every one-tile-per-block launch,
+    // profiles/pws_interior_ab.txt).  One 16-byte piece per lane and pass (consecutive lanes, consecutive pieces: no bank
+    // conflict); the slots the DMA writes are never touched.
+    if constexpr (INT) {
+        constexpr int Wpc = WC + 2;
+        typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+        typedef u32x4_t __attribute__((address_space(3)))* lds16_t;
+        const u32x4_t zero = {0u, 0u, 0u, 0u};
+        const float rHp = g.rHp;
+        static_assert(!INT || HROWS * 8 % (NMW * 64) == 0, "interior mode: whole passes over a halo buffer");
+#pragma unroll      // (independent passes: their address arithmetic overlaps)
+        for (int it = 0; it < HROWS * 8 / (NMW * 64); ++it) {
+            const int i = tid + it * (NMW * 64);
+            const int hp = i >> 3;
+            int border;                                              // (bitwise: one predicate, no branch per term)
+            if constexpr (WC == 4) { const int q = hp % 36; border = (q < 7) | (q > 30); }
+            else {
+                const int hr = hp / Wpc, xp = hp - hr * Wpc;
+                const int ri = hr - vpd_fdiv(hr, rHp) * (H + 2);
+                border = (xp == 0) | (xp == Wpc - 1) | (ri == 0) | (ri == H + 1);
+            }
+            if (border | (hp >= g.NHP)) {
+                *(lds16_t)(size_t)(lds0 + (unsigned)i * 16u) = zero;
+                *(lds16_t)(size_t)(lds0 + HBUF * 2u + (unsigned)i * 16u) = zero;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
     // Pixel-fragment addresses.  Halo pixel r = hbase + toff (toff = tdy * Wp + tdx, the tap's shift) of K-half 0 lives at
     // hb + r * 128 + ((key ^ fq) << 4); key (HaloGeom) depends on the pixel's COLUMN and row parity only, so the lane-dependent
     // part is one of three precomputed words per fragment -- lo[ic][b] = hbase * 128 + (((column + dx_ic) & kmask) ^ rowkey ^ fq) * 16
@@ -797,10 +857,10 @@ static __device__ __forceinline__ void pws_body(const ConvParams& p, const HaloG
 #endif
 }
 
-template <int BM, int BN, int HROWS, int NS, int EPM, int NMW, bool PIPE, int WC = 0, bool FLIP = false>
+template <int BM, int BN, int HROWS, int NS, int EPM, int NMW, bool PIPE, int WC = 0, bool FLIP = false, bool INT = false>
 __global__ __launch_bounds__((NMW + 4) * 64, (NMW + 4) / 4) void conv3x3_pws_kernel(const ConvParams p, const HaloGeom g,
                                                                                    const PwsGrid sg) {
-    pws_body<BM, BN, HROWS, NS, EPM, NMW, PIPE, WC, FLIP>(p, g, sg);
+    pws_body<BM, BN, HROWS, NS, EPM, NMW, PIPE, WC, FLIP, INT>(p, g, sg);
 }
 
 // conv_pws_geo.hip: the compile-time-geometry instantiations (W = 16 / 8 on 256 x 64 tiles, W = 4 on 128 x 64 tiles; forward taps or

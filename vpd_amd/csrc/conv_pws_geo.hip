@@ -10,23 +10,23 @@
 
 namespace {
 
-template <int BM, int BN, int HROWS, int NS, int WC, int NMW = 4, bool PIPE = true>
+template <int BM, int BN, int HROWS, int NS, int WC, bool INT, int NMW = 4, bool PIPE = true>
 bool launch_geo(bool flip, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid, dim3 block, size_t lds,
                 hipStream_t stream) {
     const int mode = conv_ep_mode(q);
     if (!flip) {
         switch (mode) {
-            case 1: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 1, NMW, PIPE, WC, false>), grid, block, lds, stream, q, g, sg); return true;
-            case 3: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 3, NMW, PIPE, WC, false>), grid, block, lds, stream, q, g, sg); return true;
+            case 1: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 1, NMW, PIPE, WC, false, INT>), grid, block, lds, stream, q, g, sg); return true;
+            case 3: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 3, NMW, PIPE, WC, false, INT>), grid, block, lds, stream, q, g, sg); return true;
             default: return false;
         }
     }
     switch (mode) {
-        case 0: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 0, NMW, PIPE, WC, true>), grid, block, lds, stream, q, g, sg); return true;
-        case 2: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 2, NMW, PIPE, WC, true>), grid, block, lds, stream, q, g, sg); return true;
-        case 6: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 6, NMW, PIPE, WC, true>), grid, block, lds, stream, q, g, sg); return true;
-        case 7: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 7, NMW, PIPE, WC, true>), grid, block, lds, stream, q, g, sg); return true;
-        case 8: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 8, NMW, PIPE, WC, true>), grid, block, lds, stream, q, g, sg); return true;
+        case 0: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 0, NMW, PIPE, WC, true, INT>), grid, block, lds, stream, q, g, sg); return true;
+        case 2: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 2, NMW, PIPE, WC, true, INT>), grid, block, lds, stream, q, g, sg); return true;
+        case 6: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 6, NMW, PIPE, WC, true, INT>), grid, block, lds, stream, q, g, sg); return true;
+        case 7: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 7, NMW, PIPE, WC, true, INT>), grid, block, lds, stream, q, g, sg); return true;
+        case 8: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 8, NMW, PIPE, WC, true, INT>), grid, block, lds, stream, q, g, sg); return true;
         default: return false;
     }
 }
@@ -56,10 +56,18 @@ int vpd_pws_geo_width(int bm, int bn, int hrows, int ns, int nmw, const ConvPara
 bool vpd_launch_pws_geo(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid,
                         dim3 block, size_t lds, hipStream_t stream) {
     bool flip = false;
-    switch (vpd_pws_geo_width(bm, bn, hrows, ns, nmw, q, g, &flip)) {
-        case 16: return launch_geo<256, 64, 416, PWS_NS_C6, 16>(flip, q, g, sg, grid, block, lds, stream);
-        case 8: return launch_geo<256, 64, 416, PWS_NS_C6, 8>(flip, q, g, sg, grid, block, lds, stream);
-        case 4: return launch_geo<128, 64, 288, PWS_NS_C3, 4>(flip, q, g, sg, grid, block, lds, stream);
+    // HaloGeom::interior (vpd_conv_dispatch) picks the interior-loader twin of the same kernel: same MFMA side, same results
+    const int wc = vpd_pws_geo_width(bm, bn, hrows, ns, nmw, q, g, &flip);
+    if (g.interior) switch (wc) {
+        case 16: return launch_geo<256, 64, 416, PWS_NS_C6, 16, true>(flip, q, g, sg, grid, block, lds, stream);
+        case 8: return launch_geo<256, 64, 416, PWS_NS_C6, 8, true>(flip, q, g, sg, grid, block, lds, stream);
+        case 4: return launch_geo<128, 64, 288, PWS_NS_C3, 4, true>(flip, q, g, sg, grid, block, lds, stream);
+        default: return false;
+    }
+    switch (wc) {
+        case 16: return launch_geo<256, 64, 416, PWS_NS_C6, 16, false>(flip, q, g, sg, grid, block, lds, stream);
+        case 8: return launch_geo<256, 64, 416, PWS_NS_C6, 8, false>(flip, q, g, sg, grid, block, lds, stream);
+        case 4: return launch_geo<128, 64, 288, PWS_NS_C3, 4, false>(flip, q, g, sg, grid, block, lds, stream);
         default: return false;
     }
 }

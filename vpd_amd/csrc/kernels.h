@@ -113,6 +113,7 @@ struct ConvDispatch {
     int kclass;             // vpd_conv_kernel_class
     int pws;                // classes 1, 2, 3, 6: conv3x3_pws_kernel (persistent blocks) instead of conv3x3_ws_kernel
     int geo;                // ... its compile-time-geometry instantiation: the image width, or 0
+    int interior;           // ... with the interior loaders (HaloGeom::interior)
     int c64x2;              // class 0: the two-group inference twin conv3x3_c64x2_persistent_kernel
     int ws1x1, stream1x1;   // class 4: conv1x1_ws_kernel (ring GEMM) / conv1x1_stream_kernel
     int halo;               // class 4: the legacy conv3x3_halo_kernel

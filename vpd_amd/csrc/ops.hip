@@ -111,10 +111,8 @@ extern "C" int vpd_op_conv2d_bnsums2(const void* x, const void* w, void* y, cons
 // rows, 2 eval epilogue, 4 ReLU bit map on the old value, 8 BatchNorm sums (vpd_op_conv2d_bnsums), 16 of two BatchNorms.
 // out12 = {class, pws, geo width, c64x2, 1x1 ring GEMM, 1x1 streaming, legacy halo, tile pixels, tile channels, epilogue mode,
 // tiles per block, takes BatchNorm sums}
-extern "C" int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub,
-                                      int oph, int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags,
-                                      int* out12) {
-    if (!tapset9 || !out12) return fail("null argument");
+static int op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub, int oph, int opw,
+                              int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags, ConvDispatch* d, int* takes_sums) {
     if (n < 1 || Hs < 1 || Ws < 1 || xHp < 1 || xWp < 1 || xC < 1 || yC < Co || Kc < 64 || Kc % 64 || Co < 64 || Co % 64 || osub < 1 ||
         istr < 1 || (long long)n * Hs * Ws >= (1ll << 31) || (flags & ~31))
         return fail("bad argument");
@@ -128,10 +126,32 @@ extern "C" int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, 
     if (flags & 8) { q.bst_z = (const bf16_t*)&present; q.bst_mask = (const unsigned char*)&present; vpd_conv_set_bn_rows(q, const_cast<double*>(&present)); }
     if (flags & 16) { q.bst_z2 = (const bf16_t*)&present; q.stats2 = const_cast<double*>(&present); }
     if (q.taps.nr < 1 || q.taps.nc < 1) return fail("empty tap set");
-    const ConvDispatch d = vpd_conv_dispatch(q);
-    const int v[12] = {d.kclass, d.pws, d.geo, d.c64x2, d.ws1x1, d.stream1x1, d.halo, d.bm, d.bn, d.mode, d.tiles_per_block,
-                       (flags & 8) ? (int)vpd_conv_takes_bn_sums(q) : 0};
+    *d = vpd_conv_dispatch(q);
+    *takes_sums = (flags & 8) ? (int)vpd_conv_takes_bn_sums(q) : 0;
+    return 0;
+}
+extern "C" int vpd_op_conv2d_dispatch(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub,
+                                      int oph, int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags,
+                                      int* out12) {
+    if (!tapset9 || !out12) return fail("null argument");
+    ConvDispatch d;
+    int sums;
+    const int rc = op_conv2d_dispatch(n, xHp, xWp, xC, yHp, yWp, yC, ypad, Hs, Ws, osub, oph, opw, istr, Kc, Co, tapset9, accumulate, flags, &d, &sums);
+    if (rc) return rc;
+    const int v[12] = {d.kclass, d.pws, d.geo, d.c64x2, d.ws1x1, d.stream1x1, d.halo, d.bm, d.bn, d.mode, d.tiles_per_block, sums};
     memcpy(out12, v, sizeof v);
+    return 0;
+}
+// ... and whether that launch takes the interior loaders of conv3x3_pws_kernel (ConvDispatch::interior): *out = 1 / 0
+extern "C" int vpd_op_conv2d_interior(int n, int xHp, int xWp, int xC, int yHp, int yWp, int yC, int ypad, int Hs, int Ws, int osub,
+                                      int oph, int opw, int istr, int Kc, int Co, const int* tapset9, int accumulate, int flags,
+                                      int* out) {
+    if (!tapset9 || !out) return fail("null argument");
+    ConvDispatch d;
+    int sums;
+    const int rc = op_conv2d_dispatch(n, xHp, xWp, xC, yHp, yWp, yC, ypad, Hs, Ws, osub, oph, opw, istr, Kc, Co, tapset9, accumulate, flags, &d, &sums);
+    if (rc) return rc;
+    *out = d.interior;
     return 0;
 }
 

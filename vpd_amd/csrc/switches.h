@@ -29,6 +29,7 @@
     X(no_ws,              "VPD_NO_WS",             0)          \
     X(pws_geo,            "VPD_PWS_GEO",           1)          \
     X(pws_rot,            "VPD_PWS_ROT",           1)          \
+    X(pws_interior,       "VPD_PWS_INTERIOR",      1)          \
     X(reserve_cus,        "VPD_RESERVE_CUS",       0)          \
     X(c64x2,              "VPD_C64X2",             1)          \
     X(conv1x1_ws,         "VPD_CONV1X1_WS",        1)          \
