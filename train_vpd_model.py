@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Drop-in for reference train_vpd_model.py (same flags, files and bookkeeping; the
 student's arithmetic runs on libvpdhip).  Extra, optional flags: --synthetic N (no
-dataset files needed) and torchrun for multi-GPU data parallelism."""
+dataset files needed), torchrun for multi-GPU data parallelism, and --state_frequency N /
+--resume / --seed S to continue a run from <save_dir>/train_state.pt."""
 import argparse
 import os
 
@@ -9,6 +10,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
+from vpd_amd import checkpoint as ckpt
 from vpd_amd import paths as dataset_paths
 from vpd_amd.data import RGB_MEAN_STD, SyntheticCrops, TeacherEmbDataset, load_tennis_default
 from vpd_amd.io import store_json
@@ -71,6 +73,15 @@ def get_args():
     parser.add_argument('--backbone_lr_scale', type=float,
                         help='(this build) the head (fc + motion head) runs at --learning_rate, everything else at this factor '
                              'times it: the --pretrained fine-tuning recipe')
+    parser.add_argument('--state_frequency', type=int,
+                        help='(this build) write <save_dir>/train_state.pt -- everything --resume needs: weights, optimizer moments '
+                             'and step, loss scaler, EMA, clip statistics, random number generators, loss history, split seed -- '
+                             'after every N-th epoch and after the last one')
+    parser.add_argument('--resume', action='store_true',
+                        help='(this build) continue the run in --save_dir from its train_state.pt at the epoch after the stored one; '
+                             'every argument but --num_epochs, --checkpoint_frequency and --state_frequency must be the stored run\'s')
+    parser.add_argument('--seed', type=int,
+                        help='(this build) seed torch (CPU and device), random and numpy, and the train/val split')
     parser.add_argument('--no_augment', action='store_true',
                         help='escape hatch: fp32 batches from the CPU loaders with h-flips only -- NOT the reference '
                              'recipe, whose datasets always augment (vpd_dataset/common.py:85-92)')
@@ -89,6 +100,8 @@ def get_args():
         parser.error('--weight_decay must not be negative')
     if args.backbone_lr_scale is not None and not args.backbone_lr_scale >= 0.0:
         parser.error('--backbone_lr_scale must not be negative')
+    if args.state_frequency is not None and args.state_frequency < 1:
+        parser.error('--state_frequency must be >= 1')
     return args
 
 
@@ -113,7 +126,21 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
          model_select_window, checkpoint_frequency, pretrained, emb_dir, penn_dir, no_test_video, min_pose_score,
          synthetic=None, synthetic_emb_dim=128, gpu_augment=False, no_augment=False, dtype='bf16', loss_scale='static', ema_decay=None,
          ema_warmup=False, clip_grad_norm=None, weight_decay=None, no_bn_bias_decay=False, backbone_lr_scale=None,
-         accum_steps=None):
+         accum_steps=None, state_frequency=None, resume=False, seed=None):
+    run_args = dict(locals())      # what --resume compares with the stored run's (vpd_amd.checkpoint.check_resume_args)
+    stored = None
+    if resume:      # everything that can be refused is refused here, before any GPU work
+        state_path = ckpt.check_resume_dir(save_dir)
+        stored = ckpt.read_state(state_path)
+        ckpt.check_resume_args(stored['extra']['args'], run_args)
+        if stored['extra']['epoch'] >= num_epochs:
+            print('Nothing left to do: {} holds epoch {} of {}'.format(state_path, stored['extra']['epoch'], num_epochs))
+            return
+    if seed is not None:
+        import random
+        torch.manual_seed(seed)      # (CPU and every device)
+        random.seed(seed)
+        np.random.seed(seed % 2 ** 32)
     device = 'cuda'
     # The reference builds train AND val datasets with augment=True (vpd_dataset/single_frame.py:267-272,
     # common.py:85-92): ColorJitter, mask noise, RandomResizedCrop and flips are part of the recipe, so they are the
@@ -126,8 +153,8 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         torch.distributed.init_process_group(os.environ.get('VPD_DIST_BACKEND', 'nccl'))      # 'nccl' = RCCL
     # save_dir must not exist (train_vpd_model.py:221).  Rank 0 creates it FIRST and tells the others, so that every
     # rank leaves together instead of waiting in a collective for a rank that has raised
-    made = [None, int.from_bytes(os.urandom(4), 'little')]       # [makedirs error or None, split seed]
-    if rank == 0:
+    made = [None, int.from_bytes(os.urandom(4), 'little') if seed is None else seed]       # [makedirs error or None, split seed]
+    if rank == 0 and not resume:
         try:
             os.makedirs(save_dir)
         except OSError as e:
@@ -138,6 +165,10 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         # single_frame.py:263: a split per rank would train the shared weights on other ranks' validation frames)
         torch.distributed.broadcast_object_list(made, src=0)
         split_seed = made[1]
+    elif state_frequency is not None or seed is not None:
+        split_seed = made[1]      # a run that can be continued must be able to draw the same split again
+    if resume:
+        split_seed = stored['extra']['split_seed']
     if made[0] is not None:
         if world > 1:
             torch.distributed.destroy_process_group()
@@ -186,7 +217,7 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         augmenter = CropAugmenter(encoder.device, rgb_mean_std, img_dim, flow_img is not None)
     trainer = ModelTrainer(encoder, motion, augmenter=augmenter, augment=True, ema_decay=ema_decay, ema_warmup=ema_warmup,
                            accum_steps=1 if accum_steps is None else accum_steps)
-    if world > 1:      # same initial weights on every rank (after the trainer: the motion head is initialised there)
+    if world > 1 and not resume:      # same initial weights on every rank (after the trainer: the motion head is initialised there)
         torch.distributed.broadcast(encoder.engine.params, 0)
         torch.distributed.broadcast(encoder.engine.bn_running, 0)
         encoder.engine.mark_weights_changed()
@@ -212,12 +243,28 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
     clipped_before = 0
 
     ema = ema_decay is not None
-    if rank == 0:
+    losses = []
+    best_val_loss = float('inf')
+    best_val_ema_loss = float('inf')
+    first_epoch = 1
+    if resume:      # (the order inside load_state: weights, optimizer, scaler, EMA, clip block, random number generators)
+        extra = trainer.load_state(state_path, optimizer, scaler, state=stored)
+        losses, first_epoch = list(extra['losses']), extra['epoch'] + 1
+        best_val_loss, best_val_ema_loss = extra['best_val_loss'], extra['best_val_ema_loss']
+        skipped_before, clipped_before = extra['skipped_before'], extra['clipped_before']
+        stored = None
+        if rank == 0:
+            print('Resuming after epoch {}'.format(first_epoch - 1))
+    if rank == 0 and not resume:
         config_ema = {} if not ema else {'ema_decay': ema_decay, 'ema_warmup': ema_warmup}      # (keys only with --ema_decay)
         if clip:
             config_ema['clip_grad_norm'] = clip_grad_norm      # (key only with --clip_grad_norm)
         if accum_steps is not None:
             config_ema['accum_steps'] = accum_steps      # (key only with --accum_steps)
+        if state_frequency is not None:
+            config_ema['state_frequency'] = state_frequency      # (key only with --state_frequency)
+        if seed is not None:
+            config_ema['seed'] = seed      # (key only with --seed)
         config_ema.update(grouping)      # (weight_decay / no_bn_bias_decay / backbone_lr_scale: keys only with their flags)
         store_json(os.path.join(save_dir, 'config.json'), {
             'num_epochs': num_epochs, 'batch_size': batch_size, 'learning_rate': learning_rate, 'img_dim': img_dim,
@@ -231,10 +278,7 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
                        else 'cpu: h-flip only (--no_augment)', **config_ema})
 
     loss_file = os.path.join(save_dir, 'loss.json')
-    losses = []
-    best_val_loss = float('inf')
-    best_val_ema_loss = float('inf')
-    for epoch in range(1, num_epochs + 1):
+    for epoch in range(first_epoch, num_epochs + 1):
         train_loss = trainer.epoch(train_loader, optimizer=optimizer, scaler=scaler)
         if world > 1 and os.environ.get('VPD_DDP_AVG_BN', '0') == '1':      # per-rank BatchNorm statistics -> their mean over ranks
             from vpd_amd.ddp import average_running_stats
@@ -277,6 +321,12 @@ def main(dataset, num_epochs, batch_size, learning_rate, img_dim, flow_img, moti
         best_val_loss = min(moving_avg_val_loss, best_val_loss)
         if ema:
             best_val_ema_loss = min(moving_avg_val_ema_loss, best_val_ema_loss)
+        if state_frequency is not None and (epoch % state_frequency == 0 or epoch == num_epochs):
+            # after the epoch's bookkeeping; every rank calls (the generator states are gathered), rank 0 writes
+            trainer.save_state(os.path.join(save_dir, ckpt.STATE_FILE), optimizer, scaler, extra={
+                'epoch': epoch, 'losses': losses, 'best_val_loss': float(best_val_loss), 'best_val_ema_loss': float(best_val_ema_loss),
+                'skipped_before': int(skipped_before), 'clipped_before': int(clipped_before), 'split_seed': split_seed,
+                'args': run_args})
     if rank == 0:
         print('Saving last epoch: {}'.format(epoch))
         trainer.save_model(save_dir, 'epoch{:04d}'.format(epoch))

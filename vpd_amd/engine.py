@@ -474,6 +474,63 @@ class StudentEngine:
         """(params, bn_running) the eval forwards read"""
         return (self.ema_params, self.ema_bn_running) if self._use_ema else (self.params, self.bn_running)
 
+    # -- state for a checkpoint (ModelTrainer.save_state / load_state) -----------------------------------------------
+    def ema_state(self):
+        """The average as a checkpoint holds it: the two buffers (themselves, not copies), decay, warmup and `num_updates` -- one
+        number whichever side counts: `_ema_t` on the host, applied steps - `_ema_t0` behind a device block (synchronises)."""
+        if self._ema is None:
+            raise RuntimeError("ema_state() before enable_ema()")
+        n = self._ema_t if self._dyn_state is None else int(self.adam_step) - self._ema_t0
+        return {"params": self.ema_params, "bn_running": self.ema_bn_running, "decay": self._ema[0], "warmup": self._ema[1],
+                "num_updates": int(n)}
+
+    def load_ema_state(self, state):
+        """Restore ema_state() into an engine whose averaging is on.  Call it AFTER the optimizer's load: the count behind a device
+        block is relative to adam_step (`_ema_t0 = adam_step - num_updates`; the host's `_ema_t = num_updates` serves the other
+        mode)."""
+        if self._ema is None:
+            raise RuntimeError("load_ema_state() before enable_ema()")
+        p, b = state["params"], state["bn_running"]
+        if p.numel() != self.ema_params.numel() or b.numel() != self.ema_bn_running.numel():
+            raise ValueError("EMA: the stored buffers hold %d + %d floats, this engine's %d + %d"
+                             % (p.numel(), b.numel(), self.ema_params.numel(), self.ema_bn_running.numel()))
+        n = int(state["num_updates"])
+        if n < 0:
+            raise ValueError("EMA: num_updates %d" % n)
+        self.ema_params.copy_(p)
+        self.ema_bn_running.copy_(b)
+        self._ema = (float(state["decay"]), bool(state["warmup"]))
+        self._ema_t = n
+        self._ema_t0 = max(int(self.adam_step) - n, 0)
+        self._ema_version += 1
+
+    def clip_state(self):
+        """What of the clip block outlives a step: max_norm and the statistics clip_stats() accumulates (synchronises)"""
+        if self._clip is None:
+            raise RuntimeError("clip_state() before enable_grad_clip()")
+        st = self.clip_stats()
+        return {"max_norm": float(self._clip_max_norm), "norm_max": st["norm_max"], "clipped_steps": st["clipped_steps"],
+                "nonfinite_steps": st["nonfinite_steps"]}
+
+    def load_clip_state(self, state):
+        """Restore clip_state() into the words clip_stats() reads; the block's step word follows adam_step, so call it AFTER the
+        optimizer's load."""
+        if self._clip is None:
+            raise RuntimeError("load_clip_state() before enable_grad_clip()")
+        max_norm = float(state["max_norm"])
+        if not max_norm > 0.0:
+            raise ValueError("max_grad_norm must be > 0, not %r" % (max_norm,))
+        words = torch.zeros(4, dtype=torch.int32)
+        words.view(torch.float32)[0] = float(state["norm_max"])
+        words[1] = int(self.adam_step)
+        words[2] = int(state["clipped_steps"])
+        words[3] = int(state["nonfinite_steps"])
+        words = words.to(self.device)
+        self._clip[9:10] = words[0:1]
+        self._clip[3:4] = words[1:2]
+        self._clip[11:13] = words[2:4]
+        self._clip_max_norm = max_norm
+
     def mark_weights_changed(self):
         """Call after writing `params` / `bn_running` by a path torch's version counters do not see (a collective, a
         raw pointer): every plan repacks its bf16 weights before its next forward."""

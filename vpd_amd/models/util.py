@@ -43,6 +43,15 @@ class LossScaler:
     def update(self):
         return None
 
+    def state_dict(self):
+        """the static scaler's state: its scale"""
+        return {"scale": self._scale}
+
+    def load_state_dict(self, state):
+        if float(state["scale"]) <= 0:
+            raise ValueError("loss scale must be positive")
+        self._scale = float(state["scale"])
+
 
 class DynamicLossScaler(LossScaler):
     """torch.cuda.amp.GradScaler() as the reference runs it (train_vpd_model.py:105, its defaults): look for inf / NaN in the
@@ -122,6 +131,28 @@ class DynamicLossScaler(LossScaler):
         eng = self._engine
         eng.check(eng.L.vpd_scale_state_update(self._ptr(), self._growth, self._backoff, self._interval, eng._stream()),
                   "vpd_scale_state_update")
+
+    def state_dict(self):
+        """torch.amp.GradScaler.state_dict()'s keys (scale, growth_factor, backoff_factor, growth_interval, _growth_tracker) plus
+        skipped_steps, read from the device block (synchronises).  The applied-step count is the optimizer's `step`: not here."""
+        from ..checkpoint import scaler_state_dict
+        return scaler_state_dict(self._host(), self._growth, self._backoff, self._interval)
+
+    def load_state_dict(self, state):
+        """Scale, growth tracker and skipped steps go into the device block, the non-finite word is cleared, the three factors are
+        taken over.  A plain GradScaler dictionary loads (skipped_steps = 0).  The applied-step word is NOT written: it is the
+        optimizer's `step`, which FusedAdamW.load_state_dict() puts there through engine.adam_step -- load the optimizer first or
+        afterwards, the two do not touch each other's words."""
+        from ..checkpoint import scaler_words
+        words = scaler_words(state)
+        growth, backoff, interval = float(state["growth_factor"]), float(state["backoff_factor"]), int(state["growth_interval"])
+        if not growth >= 1.0 or not 0.0 < backoff <= 1.0 or interval < 1:
+            raise ValueError("growth_factor >= 1, 0 < backoff_factor <= 1 and growth_interval >= 1 are required")
+        words = words.to(self._state.device)
+        self._state[0:3] = words[0:3]
+        self._state[4:5] = words[4:5]
+        self._growth, self._backoff, self._interval = growth, backoff, interval
+        self._scale = float(state["scale"])
 
 
 def step(optimizer, scaler, loss, accumulate=False):

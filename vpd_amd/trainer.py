@@ -6,6 +6,7 @@ import os
 
 import torch
 
+from . import checkpoint as ckpt
 from .ddp import GradBucketReducer
 from .models.module import FCNet
 from .models.util import DynamicLossScaler, LossScaler, step
@@ -149,6 +150,60 @@ class FusedAdamW(torch.optim.Optimizer):
             return
         betas, eps = self._shared_hypers()
         self._engine.adamw_step(g["lr"], betas, eps, g["weight_decay"], numel=self._numel, groups=self._groups())
+
+    def _names(self):
+        """the layout names of the parameters, in the optimizer's own order (the indices of state_dict())"""
+        eng = self._engine
+        ptr0 = eng.params.data_ptr()
+        by_off = {row[2]: name for name, row in eng.layout.items()}
+        names = []
+        for g in self.param_groups:
+            for q in g["params"]:
+                off = (q.data_ptr() - ptr0) // 4
+                if off not in by_off:
+                    raise ValueError("FusedAdamW: a parameter that is not one of the engine's tensors")
+                names.append(by_off[off])
+        return names
+
+    def state_dict(self):
+        """torch.optim.AdamW.state_dict() of the engine's flat moments (vpd_amd.checkpoint.adamw_state_dict): `state` is empty
+        before the first step, afterwards every parameter has `step` (engine.adam_step: read from the device block when one holds
+        the count -- synchronises), `exp_avg` and `exp_avg_sq`, views of engine.adam_m / adam_v.  torch.optim.AdamW over the same
+        parameters loads it."""
+        eng = self._engine
+        step = int(eng.adam_step) if eng.adam_m is not None else 0
+        return ckpt.adamw_state_dict(eng.layout, eng.adam_m, eng.adam_v, step, self._names(), self.param_groups)
+
+    def load_state_dict(self, state_dict):
+        """The inverse, also for a dictionary of torch.optim.AdamW over the same parameters in the same order: the moments go into
+        engine.adam_m / adam_v (allocated when need be), the step into engine.adam_step -- through its setter, so the device block
+        of a DynamicLossScaler or of the clipping receives it: load the optimizer BEFORE the scaler, the EMA and the clip state --
+        and every group's lr, betas, eps and weight_decay are restored, as torch does.  Everything is checked before anything is
+        written (ValueError: group structure, steps that differ, a missing parameter, a shape, betas / eps that differ)."""
+        eng = self._engine
+        groups = state_dict["param_groups"]
+        if len(groups) != len(self.param_groups):
+            raise ValueError("FusedAdamW: the dictionary has %d parameter groups, this optimizer %d" % (len(groups), len(self.param_groups)))
+        for i, (g, ng) in enumerate(zip(self.param_groups, groups)):
+            if len(g["params"]) != len(ng["params"]):
+                raise ValueError("FusedAdamW: group %d holds %d parameters in the dictionary, %d here" % (i, len(ng["params"]), len(g["params"])))
+            if ng.get("amsgrad") or ng.get("maximize"):
+                raise ValueError("FusedAdamW: amsgrad / maximize are not implemented (group %d of the dictionary asks for one)" % i)
+        allocated = eng.adam_m is None
+        if allocated:
+            eng.adam_m = torch.zeros_like(eng.params)
+            eng.adam_v = torch.zeros_like(eng.params)
+        try:
+            step = ckpt.adamw_load_flat(state_dict, eng.layout, self._names(), eng.adam_m, eng.adam_v)
+        except Exception:
+            if allocated:
+                eng.adam_m = eng.adam_v = None
+            raise
+        eng.adam_step = step
+        for g, ng in zip(self.param_groups, groups):
+            g["lr"], g["weight_decay"] = ng["lr"], ng["weight_decay"]
+            g["betas"], g["eps"] = tuple(ng["betas"]), ng["eps"]
+        self._grouping = None
 
     def zero_grad(self, set_to_none=False):
         # gradients live in the engine's flat buffer and are overwritten (not accumulated) by the next fused backward, which is
@@ -375,6 +430,105 @@ class ModelTrainer:
             yield self
         finally:
             eng.use_ema(False)
+
+    # -- resumable training ---------------------------------------------------------------------------------------------
+    def _fingerprint(self):
+        eng = self.encoder.engine
+        return ckpt.fingerprint(eng.arch, eng.c_in, eng.emb_dim, self.motion, eng.dtype, eng.param_numel)
+
+    @staticmethod
+    def _scaler_kind(scaler):
+        return "none" if scaler is None else "dynamic" if isinstance(scaler, DynamicLossScaler) else "static"
+
+    def _rank_world(self):
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            return dist.get_rank(), dist.get_world_size()
+        return 0, 1
+
+    def save_state(self, path, optimizer, scaler, extra=None):
+        """Everything the next optimizer step depends on, in one file written atomically (vpd_amd.checkpoint.write_atomic; it loads
+        with torch.load(path, weights_only=True)): the fingerprint (arch, input channels, emb_dim, motion, dtype, param_numel,
+        format version), the encoder's and the motion head's state_dicts (num_batches_tracked included), the optimizer's and the
+        scaler's dictionaries, the EMA and the clip state when enabled, bn_frozen, accum_steps, every rank's random number
+        generators, and `extra` (the caller's bookkeeping: tensors, numbers, strings, lists, dicts).  Under data parallelism every
+        rank calls it (the generator states are gathered), rank 0 writes.  Raises in the middle of an accumulation window (a
+        partial sum is nothing to resume from), inside ema_weights(), and for an optimizer that is not this engine's FusedAdamW."""
+        eng = self.encoder.engine
+        if not isinstance(optimizer, FusedAdamW) or optimizer._engine is not eng:
+            raise TypeError("save_state() takes the FusedAdamW of this trainer's engine (get_optimizer), not %s" % type(optimizer).__name__)
+        if eng._accum_count != 0:
+            raise RuntimeError("save_state() in the middle of an accumulation window (%d micro-batch(es) held): save at a window "
+                               "boundary, after the optimizer step" % eng._accum_count)
+        if eng._use_ema:
+            raise RuntimeError("save_state() inside ema_weights(): leave the context first")
+        if scaler is not None and not isinstance(scaler, LossScaler):
+            raise TypeError("save_state() takes scaler=None or a vpd_amd.models.util.LossScaler, not %s" % type(scaler).__name__)
+        rank, world = self._rank_world()
+        state = {
+            "fingerprint": self._fingerprint(),
+            "encoder": dict(self.encoder.state_dict()),
+            "decoder": dict(self.fcn_time.state_dict()) if hasattr(self, "fcn_time") else None,
+            "optimizer": optimizer.state_dict(),
+            "scaler_kind": self._scaler_kind(scaler),
+            "scaler": None if scaler is None else scaler.state_dict(),
+            "ema": eng.ema_state() if eng.ema_enabled else None,
+            "clip": eng.clip_state() if eng.grad_clip_enabled else None,
+            "bn_frozen": bool(eng.bn_frozen), "accum_steps": int(self.accum_steps),
+            "rng": ckpt.gather_rng(rank, world), "world_size": world,
+            "extra": extra,
+        }
+        if rank == 0:
+            ckpt.write_atomic(state, path)
+
+    def load_state(self, path, optimizer, scaler, state=None):
+        """Restore what save_state() wrote into a trainer, optimizer and scaler built as the saving run built them, and return
+        `extra`.  The order matters and is fixed here: weights, then the optimizer (its step goes to the device blocks), the
+        scaler, the EMA (its count is relative to the step), the clip block, the generators.  Everything is compared before
+        anything is written: a file from another arch / input / emb_dim / motion / dtype (ValueError naming the field), the EMA
+        on one side only or with another decay / warmup, clipping on one side only or with another max_norm, another kind of
+        scaler, another number of parameter groups, another world size.  state: the file's content when the caller has read it
+        already (vpd_amd.checkpoint.read_state)."""
+        eng = self.encoder.engine
+        if not isinstance(optimizer, FusedAdamW) or optimizer._engine is not eng:
+            raise TypeError("load_state() takes the FusedAdamW of this trainer's engine (get_optimizer), not %s" % type(optimizer).__name__)
+        if state is None:
+            state = ckpt.read_state(path)
+        ckpt.check_fingerprint(state["fingerprint"], self._fingerprint())
+        ema, clip = state["ema"], state["clip"]
+        if (ema is not None) != eng.ema_enabled:
+            raise ValueError("EMA: the file %s an average, this trainer %s (ModelTrainer(ema_decay=))"
+                             % (("holds", "keeps none") if ema is not None else ("holds no", "keeps one")))
+        if ema is not None and (float(ema["decay"]), bool(ema["warmup"])) != eng._ema:
+            raise ValueError("EMA: the file's average has decay=%r, warmup=%r, this trainer decay=%r, warmup=%r"
+                             % ((float(ema["decay"]), bool(ema["warmup"])) + eng._ema))
+        if (clip is not None) != eng.grad_clip_enabled:
+            raise ValueError("gradient clipping: %s in the file, %s in this optimizer (max_grad_norm=)"
+                             % (("on", "off") if clip is not None else ("off", "on")))
+        if clip is not None and float(clip["max_norm"]) != eng._clip_max_norm:
+            raise ValueError("gradient clipping: max_norm %r in the file, %r in this optimizer" % (float(clip["max_norm"]), eng._clip_max_norm))
+        if state["scaler_kind"] != self._scaler_kind(scaler):
+            raise ValueError("loss scaler: the file was written with %s, this run has %s" % (state["scaler_kind"], self._scaler_kind(scaler)))
+        if len(state["optimizer"]["param_groups"]) != len(optimizer.param_groups):
+            raise ValueError("parameter groups: %d in the file, %d in this optimizer"
+                             % (len(state["optimizer"]["param_groups"]), len(optimizer.param_groups)))
+        rank, world = self._rank_world()
+        rng = ckpt.pick_rng(state["rng"], rank, world)
+        self.encoder.load_state_dict(state["encoder"])
+        if hasattr(self, "fcn_time"):
+            self.fcn_time.load_state_dict(state["decoder"])
+        eng.mark_weights_changed()
+        optimizer.load_state_dict(state["optimizer"])
+        if scaler is not None:
+            scaler.load_state_dict(state["scaler"])
+        if ema is not None:
+            eng.load_ema_state(ema)
+        if clip is not None:
+            eng.load_clip_state(clip)
+        eng.freeze_bn(bool(state["bn_frozen"]))
+        eng._accum_count = 0
+        ckpt.restore_rng(rng)
+        return state["extra"]
 
     def save_model(self, save_dir, name, ema=False):
         """ema: write the averaged weights instead, as <name>_ema.encoder.pt / <name>_ema.decoder.pt -- ordinary state_dicts"""
