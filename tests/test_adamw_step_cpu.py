@@ -1,56 +1,17 @@
 """StudentEngine.adamw_step, the part that needs no GPU and no native library: which entry points it calls, in which order and with
 which state block, along its two axes -- path (the fused pass over the last backward's train plan / the flat buffers) and mode
 (no device state / a DynamicLossScaler's block in flight / the clip block).  The library is a stub that records every call."""
-import ctypes as C
-
 import pytest
 import torch
 
-from vpd_amd.engine import StudentEngine
+from tests.engine_stub import BN_NUMEL, NUMEL, stub_engine
 
 HYPER = (1e-3, 0.9, 0.999, 1e-8, 0.01)      # lr, beta1, beta2, eps, weight_decay as adamw_step passes them on
-NUMEL = 64
-
-
-class _Lib:
-    """every attribute is an entry point that records (name, arguments) and returns 0"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, tuple(a.value if isinstance(a, C.c_void_p) else a for a in args)))
-            return 0
-        return entry
-
-
-class _Plan:
-    """what adamw_step touches of the train plan of the last backward"""
-
-    def __init__(self, param_numel):
-        self.handle = C.c_void_p(0x1000)
-        self.workspace = torch.zeros(16)
-        self.param_numel = param_numel
-        self.packed_version = None
-        self.motion = True
 
 
 def _engine(path, mode, ema):
-    eng = StudentEngine.__new__(StudentEngine)
-    eng.L = _Lib()
-    eng.check = lambda rc, what="": None
-    eng._stream = lambda: None
-    eng.device = torch.device("cpu")
-    eng.param_numel, eng.bn_numel = NUMEL, 8
-    eng.params, eng._grads = torch.zeros(NUMEL), torch.zeros(NUMEL)
-    eng.adam_m, eng.adam_v = torch.zeros(NUMEL), torch.zeros(NUMEL)
-    eng.bn_running = torch.zeros(8)
-    eng.loss_scale = 1.0
-    eng._adam_step, eng._dyn_state = 6, None
-    eng._hip_version = 3
-    eng._use_ema, eng._ema_version = False, 0
-    eng._ema, eng._ema_t, eng._ema_t0 = None, 0, 0
+    # the plan: current for the fused path ("fused_small": built without the motion head, fewer parameters than the buffers)
+    eng = stub_engine(None if path == "flat_no_plan" else NUMEL - 8 if path == "fused_small" else NUMEL)
     eng.scale_state = torch.zeros(8, dtype=torch.int32) if mode == "scaler" or mode == "clip+scaler" else None
     eng._clip = torch.zeros(24, dtype=torch.int32) if mode.startswith("clip") else None
     eng._clip_max_norm = 2.5 if eng._clip is not None else None
@@ -62,11 +23,7 @@ def _engine(path, mode, ema):
         eng._dyn_state[3] = 6
     if ema:
         eng._ema = (0.99, False)
-        eng.ema_params, eng.ema_bn_running = torch.zeros(NUMEL), torch.zeros(8)
-    # the plan: current for the fused path ("fused_small": built without the motion head, fewer parameters than the buffers)
-    eng._step_plan = None if path == "flat_no_plan" else _Plan(NUMEL - 8 if path == "fused_small" else NUMEL)
-    if eng._step_plan is not None:
-        eng._step_plan.packed_version = eng.weights_version()
+        eng.ema_params, eng.ema_bn_running = torch.zeros(NUMEL), torch.zeros(BN_NUMEL)
     return eng
 
 

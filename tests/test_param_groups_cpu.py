@@ -10,6 +10,7 @@ import torch
 
 from tests import opref as R
 from tests import opref_groups as G
+from tests.engine_stub import NUMEL, stub_engine
 from tests.test_abi_cpu import header_functions
 from tests.test_opref_cpu import _adamw1_f32
 
@@ -162,60 +163,15 @@ def test_grouped_step_entries_refuse_bad_arguments_on_the_host(dtype):
 # ---------------------------------------------------------------------------
 # 5: FusedAdamW on a recording library
 # ---------------------------------------------------------------------------
-class _RecLib:
-    """every attribute is an entry point that records (name, arguments) and returns 0; vpd_adam_groups_bytes answers a size"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            conv = lambda a: a.value if isinstance(a, C.c_void_p) else (list(a) if isinstance(a, C.Array) else a)
-            self.calls.append((name, tuple(conv(a) for a in args)))
-            return 64 if name == "vpd_adam_groups_bytes" else 0
-        return entry
-
-
-class _StubPlan:
-    def __init__(self, param_numel):
-        self.handle = C.c_void_p(0x1000)
-        self.workspace = torch.zeros(16)
-        self.param_numel = param_numel
-        self.packed_version = None
-
-
 # a toy layout in the engine's terms: name -> (kind, is_decoder, offset, numel, shape); 2 padding floats at the end
 LAYOUT = [("resnet.conv1.weight", 0, 0, 0, 16), ("resnet.bn1.weight", 1, 0, 16, 4), ("resnet.bn1.bias", 2, 0, 20, 4),
           ("resnet.layer1.0.conv1.weight", 0, 0, 24, 16), ("resnet.fc.weight", 3, 0, 40, 8), ("resnet.fc.bias", 4, 0, 48, 4),
           ("decoder.layers.0.weight", 3, 1, 52, 8), ("decoder.layers.0.bias", 4, 1, 60, 2)]
-NUMEL, ENC = 64, 52
+ENC = 52
 
 
 def _stub_engine(plan_numel=NUMEL):
-    from collections import OrderedDict
-
-    from vpd_amd.engine import StudentEngine
-    eng = StudentEngine.__new__(StudentEngine)
-    eng.L = _RecLib()
-    eng.check = lambda rc, what="": None
-    eng._stream = lambda: None
-    eng.device = torch.device("cpu")
-    eng.param_numel, eng.bn_numel = NUMEL, 8
-    eng.params, eng._grads = torch.zeros(NUMEL), torch.zeros(NUMEL)
-    eng.adam_m, eng.adam_v = torch.zeros(NUMEL), torch.zeros(NUMEL)
-    eng.bn_running = torch.zeros(8)
-    eng.loss_scale = 1.0
-    eng._adam_step, eng._dyn_state = 6, None
-    eng._hip_version = 3
-    eng._use_ema, eng._ema_version = False, 0
-    eng._ema, eng._ema_t, eng._ema_t0 = None, 0, 0
-    eng.scale_state, eng._clip, eng._clip_max_norm = None, None, None
-    eng._group_table, eng._group_table_key, eng.group_table_builds = None, None, 0
-    eng.layout = OrderedDict((n, (k, d, o, m, (m,))) for n, k, d, o, m in LAYOUT)
-    eng._step_plan = None if plan_numel is None else _StubPlan(plan_numel)
-    if eng._step_plan is not None:
-        eng._step_plan.packed_version = eng.weights_version()
-    return eng
+    return stub_engine(plan_numel, LAYOUT)
 
 
 def _tensors_of(eng, decoder=True):

@@ -79,8 +79,7 @@ def main():
     def hold():
         """mark the accumulator as holding one micro-batch in the lazy layout (what the warm-up's K = 2 windows left it in:
         every backward of this tool is lazy) without a backward of its own"""
-        assert eng._accum is not None and eng._accum_layout == "scratch", "run a K = 2 window first"
-        eng._accum_count = 1
+        eng.hold_accumulated_grads("scratch")      # (raises unless a K = 2 window ran first)
 
     def run_final(n):
         for _ in range(n):
@@ -117,15 +116,15 @@ def main():
     # the kinds of micro-step apart, against the K = 1 step
     eng.drop_accumulated_grads()
     run_nonfinal(2)
-    eng._accum.zero_()
+    eng.accumulator.zero_()
     kinds = {"non-final (store)": [], "non-final (add)": [], "final (fold + step)": []}
     for r in range(args.regions):
         eng.drop_accumulated_grads()
         kinds["non-final (store)"].append(timed(run_nonfinal, args.steps // 2))
-        eng._accum.zero_()
+        eng.accumulator.zero_()
         hold()
         kinds["non-final (add)"].append(timed(run_add, args.steps // 2))
-        eng._accum.zero_()
+        eng.accumulator.zero_()
         kinds["final (fold + step)"].append(timed(run_final, args.steps // 2))
         eng.drop_accumulated_grads()
     for name, v in kinds.items():
@@ -140,18 +139,18 @@ def main():
 
     def accum(n, add):
         for _ in range(n):
-            eng.check(eng.L.vpd_op_grad_accumulate(ptr(a), ptr(b), n1, 1, add, eng._stream()), "vpd_op_grad_accumulate")
+            eng.check(eng.L.vpd_op_grad_accumulate(ptr(a), ptr(b), n1, 1, add, eng.stream()), "vpd_op_grad_accumulate")
 
     def ema(n):
         for _ in range(n):
-            eng.check(eng.L.vpd_ema_update(ptr(b), ptr(a), n1, 1, 0.999, 0, 0, 0, None, eng._stream()), "vpd_ema_update")
+            eng.check(eng.L.vpd_ema_update(ptr(b), ptr(a), n1, 1, 0.999, 0, 0, 0, None, eng.stream()), "vpd_ema_update")
     for name, fn, fa, nbytes in (("grad_accum_kernel<store>", accum, (0,), 8.0), ("grad_accum_kernel<add>", accum, (1,), 12.0),
                                  ("ema_update_kernel", ema, (), 12.0)):
         us = min(timed(fn, args.kernel_reps, *fa) for _ in range(3))
         bps = nbytes * numel / (us * 1e-6)
         print("%-26s %d elements, %.1f MB moved per launch, %.2f us per launch back to back: %.2f TB/s, %.0f %% of the %.0f TB/s figure"
               % (name + ":", numel, nbytes * numel / 1e6, us, bps / 1e12, 100 * bps / (HBM_TBPS * 1e12), HBM_TBPS))
-    pl = eng._step_plan
+    pl = eng.step_plan
     nscratch = pl.accum_numel - pl.param_numel
     print("accumulator: %d floats (%.1f MB): scratch image %d + flat image %d" % (pl.accum_numel, 4.0 * pl.accum_numel / 1e6, nscratch, pl.param_numel))
     print("loss of the last step %.4f; optimizer steps applied %d" % (float(eng.loss_step.item()), eng.adam_step))

@@ -98,7 +98,7 @@ def main():
 
         if dtype == "bf16":
             # the passes alone, over the same ranges (the flat gradient buffer: the step above consumed the scratch)
-            pl = eng._step_plan
+            pl = eng.step_plan
             ptr = lambda t: C.c_void_p(t.data_ptr())
             st = torch.zeros(8, dtype=torch.int32, device=device)
             st.view(torch.float32)[0] = 1.0
@@ -108,16 +108,16 @@ def main():
             def finite(n):
                 for _ in range(n):
                     eng.check(eng.L.vpd_plan_check_grads(pl.handle, ptr(g), eng.param_numel, ptr(st), ptr(pl.workspace),
-                                                         eng._stream()), "vpd_plan_check_grads")
+                                                         eng.stream()), "vpd_plan_check_grads")
 
             def norm(n):
                 for _ in range(n):
                     eng.check(eng.L.vpd_plan_grad_norm(pl.handle, ptr(g), eng.param_numel, args.max_norm, None, 1.0, ptr(clip),
-                                                       ptr(pl.workspace), eng._stream()), "vpd_plan_grad_norm")
+                                                       ptr(pl.workspace), eng.stream()), "vpd_plan_grad_norm")
 
             def finalize(n):      # no ranges: nothing but the one-block kernel is launched
                 for _ in range(n):
-                    eng.check(eng.L.vpd_op_grad_norm(None, None, 0, args.max_norm, None, 1.0, ptr(clip), eng._stream()),
+                    eng.check(eng.L.vpd_op_grad_norm(None, None, 0, args.max_norm, None, 1.0, ptr(clip), eng.stream()),
                               "vpd_op_grad_norm")
             finite(args.kernel_reps)
             norm(args.kernel_reps)

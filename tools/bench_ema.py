@@ -100,12 +100,12 @@ def main():
 
     def finite(n):
         for _ in range(n):
-            eng.check(eng.L.vpd_op_check_finite(ptr(g), eng.param_numel, ptr(st), eng._stream()), "vpd_op_check_finite")
+            eng.check(eng.L.vpd_op_check_finite(ptr(g), eng.param_numel, ptr(st), eng.stream()), "vpd_op_check_finite")
     us_f = min(timed(finite, args.kernel_reps), timed(finite, args.kernel_reps))
     bps_f = 4.0 * eng.param_numel / (us_f * 1e-6)
     print("check_finite_kernel: %.1f MB read per launch, %.2f us per launch back to back: %.2f TB/s"
           % (4.0 * eng.param_numel / 1e6, us_f, bps_f / 1e12))
-    print("loss of the last step %.4f; average updates applied %d" % (float(eng.loss_step.item()), eng._ema_t))
+    print("loss of the last step %.4f; average updates applied %d" % (float(eng.loss_step.item()), eng.ema_state()["num_updates"]))
 
 
 if __name__ == "__main__":

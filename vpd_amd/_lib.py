@@ -139,6 +139,13 @@ SIGNATURES = {
     "vpd_op_zero_ranges": (C.c_int, [C.POINTER(vp), c_ll_p, C.c_int, vp]),
 }
 
+# what an OLDER build of the library may lack when it is A/B-ed through VPD_LIB_PATH / VPD_LIB_PATH_F16 (and every vpd_op_*
+# operator-level test entry point); the in-tree library must export every declared symbol
+OPTIONAL_SYMBOLS = ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext", "vpd_plan_set_bn_frozen",
+                    "vpd_plan_set_param_grads", "vpd_ema_update", "vpd_clip_state_bytes", "vpd_plan_grad_norm",
+                    "vpd_adam_groups_bytes", "vpd_adam_groups_init", "vpd_adamw_step_groups", "vpd_plan_adamw_step_groups",
+                    "vpd_plan_grad_accum_numel", "vpd_plan_grad_accumulate")
+
 _libs = {}
 
 
@@ -171,13 +178,8 @@ def lib(dtype="bf16"):
         try:
             fn = getattr(h, sym)
         except AttributeError as e:
-            # (an OLDER round's library, same-box A/B: the entry points added since are optional there -- engine.py asks hasattr)
-            if ab_build and (sym.startswith("vpd_op_") or sym in ("vpd_elem_dtype", "vpd_plan_set_loss_scale", "vpd_backward_ext",
-                                                                 "vpd_plan_set_bn_frozen", "vpd_plan_set_param_grads",
-                                                                 "vpd_ema_update", "vpd_clip_state_bytes", "vpd_plan_grad_norm",
-                                                                 "vpd_adam_groups_bytes", "vpd_adam_groups_init",
-                                                                 "vpd_adamw_step_groups", "vpd_plan_adamw_step_groups",
-                                                                 "vpd_plan_grad_accum_numel", "vpd_plan_grad_accumulate")):
+            # (an OLDER library, same-box A/B: the entry points added since are optional there -- OPTIONAL_SYMBOLS, require())
+            if ab_build and (sym.startswith("vpd_op_") or sym in OPTIONAL_SYMBOLS):
                 continue
             raise VpdHipError("%s lacks symbol %s declared in include/vpd_hip.h" % (name, sym)) from e
         fn.restype = res
@@ -189,6 +191,19 @@ def lib(dtype="bf16"):
         raise VpdHipError("%s was built with %s elements, %s asked for" % (path, h.vpd_elem_dtype().decode(), dtype))
     _libs[dtype] = h
     return h
+
+
+def has(L, symbol):
+    """whether this library exports `symbol` of OPTIONAL_SYMBOLS (every other symbol is there, or lib() had raised)"""
+    assert symbol in OPTIONAL_SYMBOLS, symbol
+    return hasattr(L, symbol)
+
+
+def require(L, symbol, what=None):
+    """An entry point of OPTIONAL_SYMBOLS is about to be called: RuntimeError when this (older, A/B) library lacks it.
+    what: the feature's name in the message, in front of the symbol's"""
+    if not has(L, symbol):
+        raise RuntimeError("this libvpdhip has no %s" % (symbol if what is None else "%s (%s)" % (what, symbol)))
 
 
 def check(rc, what="", dtype="bf16"):

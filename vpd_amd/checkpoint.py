@@ -10,6 +10,8 @@ import random
 import numpy as np
 import torch
 
+from . import state_words as W
+
 FORMAT_VERSION = 1
 STATE_FILE = "train_state.pt"
 
@@ -107,31 +109,31 @@ def adamw_load_flat(state_dict, layout, names, adam_m, adam_v):
     return int(step)
 
 
-# -- the dynamic loss scaler: the eight words of vpd_scale_state <-> GradScaler.state_dict() ----------------------------------
+# -- the dynamic loss scaler: vpd_scale_state (vpd_amd.state_words) <-> GradScaler.state_dict() ----------------------------------
 def scaler_state_dict(words, growth_factor, backoff_factor, growth_interval):
-    """words: int32[8] of vpd_scale_state on the host {float scale; u32 found; i32 growth_tracker, applied_steps, skipped_steps,
-    reserved[3]} -> GradScaler's five keys plus 'skipped_steps'.  The applied-step word is the optimizer's `step`: not here."""
-    words = torch.as_tensor(words, dtype=torch.int32).cpu().contiguous()
-    return {"scale": float(words[:1].view(torch.float32)[0]), "growth_factor": float(growth_factor),
-            "backoff_factor": float(backoff_factor), "growth_interval": int(growth_interval),
-            "_growth_tracker": int(words[2]), "skipped_steps": int(words[4])}
+    """words: vpd_scale_state -- the host's int32[8], or state_words.read()'s struct -- -> GradScaler's five keys plus
+    'skipped_steps'.  The applied-step word is the optimizer's `step`: not here."""
+    if not isinstance(words, W.ScaleState):
+        words = W.from_words(torch.as_tensor(words, dtype=torch.int32).cpu(), W.ScaleState)
+    return {"scale": words.scale, "growth_factor": float(growth_factor), "backoff_factor": float(backoff_factor),
+            "growth_interval": int(growth_interval), "_growth_tracker": words.growth_tracker, "skipped_steps": words.skipped_steps}
 
 
-def scaler_words(state, applied_steps=0):
-    """The inverse: int32[8] on the host with the found word clear and `applied_steps` (the optimizer's step) in its word.  A plain
-    GradScaler dictionary (no 'skipped_steps') gives skipped_steps = 0."""
+def scaler_fields(state):
+    """The inverse, by name: the fields of vpd_scale_state a scaler dictionary holds.  A plain GradScaler dictionary (no
+    'skipped_steps') gives skipped_steps = 0."""
     for k in SCALER_KEYS:
         if k not in state:
             raise ValueError("the scaler dictionary lacks %r" % (k,))
     scale = float(state["scale"])
     if not scale > 0.0:
         raise ValueError("loss scale must be positive, not %r" % (scale,))
-    words = torch.zeros(8, dtype=torch.int32)
-    words.view(torch.float32)[0] = scale
-    words[2] = int(state["_growth_tracker"])
-    words[3] = int(applied_steps)
-    words[4] = int(state.get("skipped_steps", 0))
-    return words
+    return dict(scale=scale, growth_tracker=int(state["_growth_tracker"]), skipped_steps=int(state.get("skipped_steps", 0)))
+
+
+def scaler_words(state, applied_steps=0):
+    """... as int32[8] on the host with the found word clear and `applied_steps` (the optimizer's step) in its word"""
+    return W.host_block(W.ScaleState, applied_steps=int(applied_steps), **scaler_fields(state))
 
 
 # -- random number generators --------------------------------------------------------------------------------------------

@@ -163,12 +163,12 @@ class GradBucketReducer:
         lazy = pending
         eng = self.engine
         cur = torch.cuda.current_stream(eng.device)
-        flat = eng._grads
+        flat = eng.flat_grads
         self.overlap = os.environ.get("VPD_DDP_OVERLAP", "1") != "0"
         # the end of an accumulation window (the engine holds the earlier micro-batches' sum; their backwards started no
         # collective): what travels is live + accumulator.  In line without overlap; else range by range on the comm stream,
         # behind the bucket's event and in front of its collective
-        fold = eng._accum_count > 0
+        fold = eng.held_micro_batches > 0
         if fold and not self.overlap:
             eng.fold_accumulated_grads()
             fold = False
@@ -215,7 +215,7 @@ class GradBucketReducer:
         dst = (C.c_void_p * 1)(live.data_ptr())
         src = (C.c_void_p * 1)(image.data_ptr())
         n = (C.c_longlong * 1)(live.numel())
-        eng.check(eng.L.vpd_op_grad_accumulate(dst, src, n, 1, 1, eng._stream()), "vpd_op_grad_accumulate")
+        eng.check(eng.L.vpd_op_grad_accumulate(dst, src, n, 1, 1, eng.stream()), "vpd_op_grad_accumulate")
 
     def all_reduce_scalars(self, loss_sum, count):
         t = torch.tensor([loss_sum, float(count)], dtype=torch.float64, device=self.engine.device)

@@ -10,7 +10,8 @@ from collections import OrderedDict
 
 import torch
 
-from ._lib import check, lib
+from . import state_words as W
+from ._lib import check, has, lib, require
 
 # reference: models/module.py:17-32 (ENCODER_ARCH): BasicBlock archs and the Bottleneck archs
 ENCODER_LAYERS = {"resnet18": (2, 2, 2, 2), "resnet34": (3, 4, 6, 3), "resnet50": (3, 4, 6, 3),
@@ -119,7 +120,7 @@ class _Plan:
             base = min([o_ for o_, m_ in ranges if m_ > 0] or [0])
             assert base % 16 == 0, "the scratch behind the stem must share the accumulator's 16-byte phase"
             self.scratch_image_off = [(o_ - base) // 4 if m_ > 0 else 0 for o_, m_ in ranges]
-            if hasattr(L, "vpd_plan_grad_accum_numel"):      # (absent only in an older A/B library)
+            if has(L, "vpd_plan_grad_accum_numel"):
                 self.accum_numel = int(L.vpd_plan_grad_accum_numel(handle))
                 assert self.accum_numel == sum(m_ for _, m_ in ranges) + self.param_numel, "accumulator != scratch ranges + param_numel"
             small = [(off_, n_) for i, (kind_, _, off_, n_, _) in enumerate(rows) if kind_ != 0 or i == 0]
@@ -154,6 +155,30 @@ class _Plan:
             pass
 
 
+class _StepCount:
+    """The optimizer steps applied so far (AdamW's `step`), in its one home: the host integer, or -- once a device block counts, a
+    DynamicLossScaler's or the clip block, because only the device knows whether a step was skipped -- that block's applied_steps."""
+
+    def __init__(self):
+        self.host, self.block = 0, None
+
+    def get(self):
+        """synchronises only when a block counts"""
+        return self.host if self.block is None else int(self.block[_APPLIED].item())
+
+    def set(self, value):
+        self.host = int(value)
+        if self.block is not None:
+            self.block[_APPLIED] = int(value)
+
+    def to_host(self):
+        """the count comes back from the block (synchronises)"""
+        self.host, self.block = self.get(), None
+
+
+_APPLIED = W.word(W.ScaleState, "applied_steps")      # (a clip block begins with a vpd_scale_state: the same word in both)
+
+
 class StudentEngine:
     """Flat fp32 parameter / gradient / optimizer-state buffers in the
     reference's state_dict order and layout, plus lazily created plans."""
@@ -171,11 +196,6 @@ class StudentEngine:
         # dtype: element type of activations / packed weights -- "bf16" (libvpdhip.so: training and inference) or "fp16"
         # (libvpdhip_f16.so: the reference's own GPU precision, train_vpd_model.py:79; training goes through a loss scaler)
         self.dtype = dtype
-        self.loss_scale = 1.0      # set by models.util.LossScaler around a backward pass + optimizer step (fp16 training)
-        # models.util.DynamicLossScaler: its device block (vpd_scale_state, int32[8]) -- `scale_state` while a scaled backward
-        # pass + optimizer step are in flight (the scale is then read on the device), `_dyn_state` from its construction on
-        self.scale_state = None
-        self._dyn_state = None
         self.L = lib(dtype)   # fail loudly right here if the HIP library is missing
         self.check = lambda rc, what="": check(rc, what, dtype)
         self.arch, self.c_in, self.emb_dim = arch, int(c_in), int(emb_dim)
@@ -200,9 +220,6 @@ class StudentEngine:
         # read (the property below, state_dict()) -- a one-element-per-BatchNorm add per step is a 5 us launch of its own
         self._nbt = torch.zeros(len(self.bn_names), dtype=torch.int64, device=self.device)
         self._nbt_pending = 0
-        self.adam_m = None
-        self.adam_v = None
-        self._adam_step = 0
         self.loss_step = torch.zeros(1, **z)
         self.loss_accum = torch.zeros(1, dtype=torch.float64, device=self.device)
         self._plans = {}
@@ -216,40 +233,68 @@ class StudentEngine:
         self._grads2 = None            # second flat buffer an accumulating backward writes before it is added (first use)
         self.stem_dgrad_launches = 0   # input gradients asked for (conv_stem_dgrad_kernel launches)
         self.bn_frozen = False         # freeze_bn(): train-mode forwards normalise with the running statistics and leave them alone
+        self._reset_step_state()
+
+    def _reset_step_state(self):
+        """What the optimizer step keeps from one call to the next, as a new engine has it"""
+        self.adam_m = None
+        self.adam_v = None
+        self._steps = _StepCount()     # see the `adam_step` property
+        self.loss_scale = 1.0          # set by models.util.LossScaler around a backward pass + optimizer step (fp16 training)
+        # models.util.DynamicLossScaler: its device block (vpd_scale_state) while a scaled backward pass + optimizer step are in
+        # flight (the scale is then read on the device)
+        self.scale_state = None
+        # enable_grad_clip(): the device block of the gradient-norm clipping (vpd_clip_state + partial sums, int32 words)
+        self._clip = None
+        self._clip_max_norm = None
         # enable_ema(): exponential moving average of `params` / `bn_running`, updated by one kernel at the end of adamw_step
         self.ema_params = None
         self.ema_bn_running = None
         self._ema = None               # (decay, warmup)
-        self._ema_t = 0                # updates enqueued without a scaler's block (there the device counts: applied steps - _ema_t0)
+        self._ema_t = 0                # updates enqueued without a device block (behind one the device counts: see _ema_t_host)
         self._ema_t0 = 0               # adam_step when averaging began
         self._ema_version = 0          # bumped by every update: plans packed from the EMA buffers repack
         self._use_ema = False          # use_ema(): eval forwards read the EMA buffers
-        # enable_grad_clip(): the device block of the gradient-norm clipping (vpd_clip_state + partial sums, int32 words)
-        self._clip = None
-        self._clip_max_norm = None
         # adamw_step(groups=...): the device segment table of the last grouping (vpd_adam_groups_init) and what it was built from
         self._group_table = None
         self._group_table_key = None
         self.group_table_builds = 0
+        self._accum, self._accum_count, self._accum_layout = None, 0, None      # (the class attributes above)
+
+    def _count_half(name):
+        """`_adam_step` / `_dyn_state`: the two halves of `_steps` under the names of before it, for an engine that a test builds
+        without __init__ and fills by hand"""
+        def put(self, value):
+            if "_steps" not in self.__dict__:
+                self._steps = _StepCount()
+            setattr(self._steps, name, value)
+        return property(lambda self: getattr(self._steps, name), put)
+    _adam_step, _dyn_state = _count_half("host"), _count_half("block")
 
     # -- helpers -------------------------------------------------------------
     @property
     def adam_step(self):
-        """Optimizer steps applied so far (1-based `step` of the last AdamW).  Under a DynamicLossScaler only the device knows it
-        after a skipped step: read from the scaler's block (synchronises)."""
-        if self._dyn_state is not None:
-            return int(self._dyn_state[3].item())
-        return self._adam_step
+        """Optimizer steps applied so far (1-based `step` of the last AdamW).  Behind a device block only the device knows it
+        after a skipped step: read from the block (synchronises)."""
+        return self._steps.get()
 
     @adam_step.setter
     def adam_step(self, value):
-        self._adam_step = int(value)
-        if self._dyn_state is not None:
-            self._dyn_state[3] = int(value)
+        self._steps.set(value)
 
     def attach_scale_state(self, state):
         """models.util.DynamicLossScaler: from now on the applied-step count lives in `state` (it starts at adam_step)."""
-        self._dyn_state = state
+        self._steps.block = state
+
+    def scale_state_update(self, block, growth, backoff, interval):
+        """The one-thread kernel that closes a step behind `block`: counts it as applied or skipped, moves the scale
+        (DynamicLossScaler.update(); the clip block's own count in adamw_step passes factors of 1)"""
+        self.check(self.L.vpd_scale_state_update(_ptr(block), growth, backoff, interval, self._stream()), "vpd_scale_state_update")
+
+    def unscale_grads_by_block_(self, block):
+        """The flat gradient buffer x 1 / the scale in `block`, the reciprocal taken on the device: no synchronisation"""
+        scale = W.word(W.ScaleState, "scale")
+        self._grads.mul_(1.0 / block[scale:scale + 1].view(torch.float32))
 
     def check_grads_finite_(self, state):
         """The non-finite search over the completed flat gradient buffer (a scaler in front of an optimizer that reads p.grad)."""
@@ -268,14 +313,13 @@ class StudentEngine:
         max_norm = float(max_norm)
         if not max_norm > 0.0:
             raise ValueError("max_grad_norm must be > 0 (float('inf') measures only), not %r" % (max_norm,))
-        if not hasattr(self.L, "vpd_plan_grad_norm"):      # (absent only in an older A/B library)
-            raise RuntimeError("this libvpdhip has no vpd_plan_grad_norm")
+        require(self.L, "vpd_plan_grad_norm")
         if self._clip is None:
             step = int(self.adam_step)
             self._clip = torch.zeros(int(self.L.vpd_clip_state_bytes()) // 4, dtype=torch.int32, device=self.device)
-            self._clip[3] = step
-            if self._dyn_state is None:
-                self._dyn_state = self._clip      # (a DynamicLossScaler's block keeps the count when there is one)
+            self._clip[_APPLIED] = step
+            if self._steps.block is None:
+                self._steps.block = self._clip      # (a DynamicLossScaler's block keeps the count when there is one)
         self._clip_max_norm = max_norm
 
     def disable_grad_clip(self):
@@ -283,9 +327,8 @@ class StudentEngine:
         block held it (synchronises)."""
         if self._clip is None:
             return
-        if self._dyn_state is self._clip:
-            self._adam_step = int(self._clip[3].item())
-            self._dyn_state = None
+        if self._steps.block is self._clip:
+            self._steps.to_host()
         self._clip = None
         self._clip_max_norm = None
 
@@ -293,18 +336,20 @@ class StudentEngine:
     def grad_clip_enabled(self):
         return self._clip is not None
 
+    @property
+    def clip_max_norm(self):
+        return self._clip_max_norm
+
     def clip_stats(self, reset_max=False):
         """The statistics of the clip block (synchronises): the last step's norm and coefficient, the running maximum of the
         finite norms, the steps clipped and the steps whose norm was not finite.  reset_max: norm_max starts again at 0."""
         if self._clip is None:
             raise RuntimeError("clip_stats() before enable_grad_clip()")
-        h = self._clip[:16].cpu()
-        f = h.view(torch.float32)
-        out = dict(total_norm=float(f[8]), norm_max=float(f[9]), coef=float(f[10]), clipped_steps=int(h[11]),
-                   nonfinite_steps=int(h[12]))
+        h = W.read(self._clip, W.ClipState)
         if reset_max:
-            self._clip[9] = 0
-        return out
+            self._clip[W.word(W.ClipState, "norm_max")] = 0
+        return dict(total_norm=h.total_norm, norm_max=h.norm_max, coef=h.coef, clipped_steps=h.clipped_steps,
+                    nonfinite_steps=h.nonfinite_steps)
 
     def _clip_norm(self, pl, numel, src):
         """enqueue the norm pass + the one-block kernel over what the step that follows reads (pl: its plan, or None = the flat
@@ -336,6 +381,26 @@ class StudentEngine:
         self.materialize_grads()
         return self._grads
 
+    @property
+    def flat_grads(self):
+        """The same buffer as it stands: after a lazy backward its conv weight ranges are stale (a reducer that sums the scratch
+        instead, a p.grad view that is completed before anybody reads it)"""
+        return self._grads
+
+    @property
+    def grads_cleared(self):
+        """nothing to add onto: the flat buffer is fresh, or mark_grads_cleared() said so (the autograd path's accumulate rule)"""
+        return self._grads_cleared
+
+    def mark_grads_cleared(self):
+        """an optimizer's zero_grad(): the next autograd backward overwrites the flat buffer instead of adding onto it"""
+        self._grads_cleared = True
+
+    @property
+    def step_plan(self):
+        """the train plan of the last backward (adamw_step goes through it), or None"""
+        return self._step_plan
+
     def materialize_grads(self):
         pl = self._step_plan
         if pl is not None and pl.handle and self.L.vpd_plan_grads_pending(pl.handle):
@@ -347,8 +412,7 @@ class StudentEngine:
         """the plan whose live gradients `what` is about to pair with the accumulator, and the layout they are in"""
         if pl is None or not pl.handle:
             raise RuntimeError("%s without a preceding backward" % what)
-        if pl.accum_numel is None:      # (absent only in an older A/B library)
-            raise RuntimeError("this libvpdhip has no gradient accumulation (vpd_plan_grad_accumulate)")
+        require(self.L, "vpd_plan_grad_accumulate", "gradient accumulation")
         layout = "scratch" if self.L.vpd_plan_grads_pending(pl.handle) else "flat"
         if self._accum_count:
             if layout != self._accum_layout:
@@ -400,8 +464,29 @@ class StudentEngine:
         """Forget what the accumulator holds (the memory stays)."""
         self._accum_count = 0
 
+    def hold_accumulated_grads(self, layout):
+        """The inverse, for a measurement of the fold alone: what the accumulator last held, in `layout`, counts as ONE micro-batch
+        again"""
+        if self._accum is None or self._accum_layout != layout:
+            raise RuntimeError("hold_accumulated_grads(%r): the accumulator last held %r" % (layout, self._accum_layout))
+        self._accum_count = 1
+
+    @property
+    def accumulator(self):
+        """the accumulator's buffer (None before the first accumulate_grads())"""
+        return self._accum
+
+    @property
+    def held_micro_batches(self):
+        """micro-batches of the current accumulation window that the accumulator holds"""
+        return self._accum_count
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def stream(self):
+        """the current stream of the engine's device, as the library's entry points take it"""
+        return self._stream()
 
     def view(self, name, buf=None):
         kind, dec, off, numel, shape = self.layout[name]
@@ -427,8 +512,7 @@ class StudentEngine:
         decay = float(decay)
         if not 0.0 <= decay <= 1.0:
             raise ValueError("ema decay must be in [0, 1], not %r" % (decay,))
-        if not hasattr(self.L, "vpd_ema_update"):      # (absent only in an older A/B library)
-            raise RuntimeError("this libvpdhip has no vpd_ema_update")
+        require(self.L, "vpd_ema_update")
         self.ema_params = self.params.clone()
         self.ema_bn_running = self.bn_running.clone()
         self._ema = (decay, bool(warmup))
@@ -445,14 +529,31 @@ class StudentEngine:
     def ema_enabled(self):
         return self._ema is not None
 
+    @property
+    def ema_config(self):
+        """(decay, warmup) of enable_ema(), or None"""
+        return self._ema
+
+    @property
+    def ema_in_use(self):
+        """use_ema() is on: eval forwards read the averaged weights"""
+        return self._use_ema
+
+    def _ema_t_host(self, block):
+        """Which side counts the EMA's updates behind `block` (the device block of a step, or None): `_ema_t` -- without a block
+        the host counts -- or None: the device does, as the block's applied steps - `_ema_t0`, so that a skipped step leaves the
+        count alone and costs no synchronisation"""
+        return self._ema_t if block is None else None
+
     def _ema_enqueue(self, state):
         decay, warmup = self._ema
+        t = self._ema_t_host(state)
         src = (C.c_void_p * 2)(self.params.data_ptr(), self.bn_running.data_ptr())
         dst = (C.c_void_p * 2)(self.ema_params.data_ptr(), self.ema_bn_running.data_ptr())
         n = (C.c_longlong * 2)(self.param_numel, self.bn_numel)
-        self.check(self.L.vpd_ema_update(src, dst, n, 2, decay, int(warmup), 0 if state is not None else self._ema_t,
-                                         self._ema_t0, _ptr(state), self._stream()), "vpd_ema_update")
-        if state is None:
+        self.check(self.L.vpd_ema_update(src, dst, n, 2, decay, int(warmup), 0 if t is None else t, self._ema_t0, _ptr(state),
+                                         self._stream()), "vpd_ema_update")
+        if t is not None:
             self._ema_t += 1
         self._ema_version += 1
 
@@ -480,7 +581,9 @@ class StudentEngine:
         number whichever side counts: `_ema_t` on the host, applied steps - `_ema_t0` behind a device block (synchronises)."""
         if self._ema is None:
             raise RuntimeError("ema_state() before enable_ema()")
-        n = self._ema_t if self._dyn_state is None else int(self.adam_step) - self._ema_t0
+        n = self._ema_t_host(self._steps.block)
+        if n is None:
+            n = int(self.adam_step) - self._ema_t0
         return {"params": self.ema_params, "bn_running": self.ema_bn_running, "decay": self._ema[0], "warmup": self._ema[1],
                 "num_updates": int(n)}
 
@@ -500,8 +603,7 @@ class StudentEngine:
         self.ema_params.copy_(p)
         self.ema_bn_running.copy_(b)
         self._ema = (float(state["decay"]), bool(state["warmup"]))
-        self._ema_t = n
-        self._ema_t0 = max(int(self.adam_step) - n, 0)
+        self._ema_t, self._ema_t0 = n, max(int(self.adam_step) - n, 0)      # (both sides of _ema_t_host)
         self._ema_version += 1
 
     def clip_state(self):
@@ -520,15 +622,8 @@ class StudentEngine:
         max_norm = float(state["max_norm"])
         if not max_norm > 0.0:
             raise ValueError("max_grad_norm must be > 0, not %r" % (max_norm,))
-        words = torch.zeros(4, dtype=torch.int32)
-        words.view(torch.float32)[0] = float(state["norm_max"])
-        words[1] = int(self.adam_step)
-        words[2] = int(state["clipped_steps"])
-        words[3] = int(state["nonfinite_steps"])
-        words = words.to(self.device)
-        self._clip[9:10] = words[0:1]
-        self._clip[3:4] = words[1:2]
-        self._clip[11:13] = words[2:4]
+        W.write(self._clip, W.ClipState, norm_max=float(state["norm_max"]), applied_steps=int(self.adam_step),
+                clipped_steps=int(state["clipped_steps"]), nonfinite_steps=int(state["nonfinite_steps"]))
         self._clip_max_norm = max_norm
 
     def mark_weights_changed(self):
@@ -568,8 +663,8 @@ class StudentEngine:
         """Frozen BatchNorm for the train plans (vpd_plan_set_bn_frozen): from the next train-mode forward on, every BatchNorm
         normalises with its running statistics and does not update them; the backward of a forward uses the mode that forward
         ran in.  Eval plans are not concerned (they fold the running statistics already)."""
-        if mode and not hasattr(self.L, "vpd_plan_set_bn_frozen"):      # (absent only in an older A/B library)
-            raise RuntimeError("this libvpdhip has no frozen BatchNorm (vpd_plan_set_bn_frozen)")
+        if mode:
+            require(self.L, "vpd_plan_set_bn_frozen", "frozen BatchNorm")
         self.bn_frozen = bool(mode)
 
     def _plan_flag(self, pl, attr, setter, on):
@@ -578,13 +673,18 @@ class StudentEngine:
             setattr(pl, attr, on)
 
     # -- forward / backward / step ---------------------------------------------
-    def forward_eval(self, x, target=None, motion=False, out=None, accumulate_loss=True, staged=None):
+    def _batch_shape(self, x, staged):
+        """(n, h, w) of a forward's batch: of x, or -- staged = (n, img_dim) -- of what stage_crops / stage_views left in the
+        plan's staging buffer"""
         if staged is not None:
             n, h = staged
-            w = h
-        else:
-            self._check_input(x, self.c_in)
-            n, _, h, w = x.shape
+            return n, h, h
+        self._check_input(x, self.c_in)
+        n, _, h, w = x.shape
+        return n, h, w
+
+    def forward_eval(self, x, target=None, motion=False, out=None, accumulate_loss=True, staged=None):
+        n, h, w = self._batch_shape(x, staged)
         pl = self.plan(h, w, n, False, motion)
         self._ensure_packed(pl)
         emb = out if out is not None else torch.empty((n, self.emb_dim), dtype=torch.float32, device=self.device)
@@ -594,13 +694,18 @@ class StudentEngine:
                                      _ptr(pl.workspace), self._stream()), "vpd_forward_eval")
         return emb
 
+    def _stage_target(self, rgb_u8, mean_std6, views=1, img_dim=None, train=False, motion=False):
+        """what the three stagings share: (the plan whose staging buffer takes `views` views of every frame -- at img_dim, default
+        the frames' own size --, n, h, w of the frames, mean_std6 as the C array)"""
+        n, h, w, _ = rgb_u8.shape
+        pl = self.plan(img_dim or h, img_dim or w, n * views, train, motion)
+        return pl, n, h, w, (C.c_float * 6)(*mean_std6)
+
     def stage_crops(self, rgb_u8, flow_u8, mask_u8, params_dev, noise, img_dim, mean_std6, noise_sd, scratch, train,
                     motion=False):
         """Device input pipeline (vpd_amd.augment) writing straight into the plan's stem staging buffer; follow with
         forward_train / forward_eval(x=None, staged=(n, img_dim))."""
-        n, h, w, _ = rgb_u8.shape
-        pl = self.plan(img_dim, img_dim, n, train, motion)
-        ms = (C.c_float * 6)(*mean_std6)
+        pl, n, h, w, ms = self._stage_target(rgb_u8, mean_std6, 1, img_dim, train, motion)
         self.check(self.L.vpd_plan_stage_crops(pl.handle, _ptr(rgb_u8), _ptr(flow_u8), _ptr(mask_u8), _ptr(noise),
                                          _ptr(params_dev), n, h, w, ms, float(noise_sd), _ptr(scratch),
                                          _ptr(pl.workspace), self._stream()), "vpd_plan_stage_crops")
@@ -609,9 +714,7 @@ class StudentEngine:
     def stage_views(self, rgb_u8, flow_u8, k_views, mean_std6):
         """Inference views [frame, h-flip] of decoded u8 frames straight into the EVAL plan's stem staging buffer
         (vpd_plan_stage_views: table-driven normalisation, bit-identical to stage_crops with identity parameters)."""
-        n, h, w, _ = rgb_u8.shape
-        pl = self.plan(h, w, n * k_views, False, False)
-        ms = (C.c_float * 6)(*mean_std6)
+        pl, n, h, w, ms = self._stage_target(rgb_u8, mean_std6, k_views)
         self.check(self.L.vpd_plan_stage_views(pl.handle, _ptr(rgb_u8), _ptr(flow_u8), n, k_views, h, w, ms,
                                          _ptr(pl.workspace), self._stream()), "vpd_plan_stage_views")
         return pl
@@ -620,22 +723,14 @@ class StudentEngine:
         """Jittered inference views [frame, J x jitter(frame), J x jitter(flip), flip] of decoded u8 frames straight into the
         EVAL plan's stem staging buffer (vpd_plan_stage_views_jitter; params_dev: device rows of vpd_aug_params, frame-major
         in view order)."""
-        n, h, w, _ = rgb_u8.shape
-        k = (1 + jitter) * (2 if flip else 1)
-        pl = self.plan(h, w, n * k, False, False)
-        ms = (C.c_float * 6)(*mean_std6)
+        pl, n, h, w, ms = self._stage_target(rgb_u8, mean_std6, (1 + jitter) * (2 if flip else 1))
         self.check(self.L.vpd_plan_stage_views_jitter(pl.handle, _ptr(rgb_u8), _ptr(flow_u8), _ptr(params_dev), n, jitter,
                                                       1 if flip else 0, h, w, ms, _ptr(scratch), _ptr(pl.workspace),
                                                       self._stream()), "vpd_plan_stage_views_jitter")
         return pl
 
     def forward_train(self, x, target=None, motion=False, accumulate_loss=True, staged=None):
-        if staged is not None:      # (n, img_dim): the batch is already in the staging buffer (stage_crops)
-            n, h = staged
-            w = h
-        else:
-            self._check_input(x, self.c_in)
-            n, _, h, w = x.shape
+        n, h, w = self._batch_shape(x, staged)
         if self._use_ema:
             raise RuntimeError("train-mode forward while use_ema() is on: the averaged weights are for evaluation; "
                                "call use_ema(False) (or leave ModelTrainer.ema_weights()) first")
@@ -663,6 +758,14 @@ class StudentEngine:
         self._last_fwd = (pl, n, pl.fwd_count, x is not None)
         return emb
 
+    def pending_forward_buckets(self):
+        """gradient buckets of the plan whose train forward backward() is about to consume (0: there is none, backward() raises)"""
+        return len(self._last[0].buckets) if self._last is not None else 0
+
+    def forward_ticket(self):
+        """what identifies the last train-mode forward to backward_ext(ticket=): take it right after the forward"""
+        return self._last_fwd
+
     def backward(self, events=None, lazy=False):
         """lazy: leave the conv weight gradients in the weight-gradient kernels' scratch layout for the fused optimizer step
         (with bucket events, i.e. under data parallelism, the reducer must then be told: reduce(plan, lazy=True))."""
@@ -675,7 +778,7 @@ class StudentEngine:
         ev = None
         if events is not None:
             ev = (C.c_void_p * len(events))(*[C.c_void_p(e) for e in events])
-        if self.loss_scale != 1.0 or hasattr(self.L, "vpd_plan_set_loss_scale"):      # (absent only in an older A/B library)
+        if self.loss_scale != 1.0 or has(self.L, "vpd_plan_set_loss_scale"):
             self.check(self.L.vpd_plan_set_loss_scale(pl.handle, float(self.loss_scale)), "vpd_plan_set_loss_scale")
         want = None if self.scale_state is None else self.scale_state.data_ptr()
         if getattr(pl, "scale_state_ptr", None) != want:      # (never called without a dynamic scaler)
@@ -691,7 +794,7 @@ class StudentEngine:
 
     def backward_ext(self, d_emb, want_dx=False, ticket=None, accumulate=False, discard=False):
         """loss.backward() from the caller's d(loss)/d(emb) (vpd_backward_ext) through the activations of a train-mode forward of
-        the plan WITHOUT the motion head -- `ticket`: what `_last_fwd` held right after that forward (default: the last one).
+        the plan WITHOUT the motion head -- `ticket`: forward_ticket() right after that forward (default: the last one).
         d_emb: f32 [n, emb_dim] on the engine's device, contiguous; no loss scale is passed (a scaled loss arrives scaled).
         accumulate: add onto the flat gradient buffer instead of overwriting it (backward into a second buffer + one add);
         discard: leave the flat buffer alone (no parameter asks for a gradient): the pass then computes data gradients only
@@ -722,8 +825,8 @@ class StudentEngine:
         self._last = None                  # the fused backward() of the same forward would find its activations consumed
         pl.consumed = count
         into = self._grads
-        data_only = discard and hasattr(self.L, "vpd_plan_set_param_grads")      # (absent only in an older A/B library)
-        if hasattr(self.L, "vpd_plan_set_param_grads"):
+        data_only = discard and has(self.L, "vpd_plan_set_param_grads")
+        if has(self.L, "vpd_plan_set_param_grads"):
             self._plan_flag(pl, "param_grads", "vpd_plan_set_param_grads", not data_only)
         if accumulate or (discard and not data_only):      # (data_only: `into` must be non-null but is not written)
             if self._grads2 is None:
@@ -783,8 +886,7 @@ class StudentEngine:
         step (the library then also checks that no boundary cuts a conv weight), or None"""
         key = (groups["key"], numel)
         if self._group_table_key != key:
-            if not hasattr(self.L, "vpd_plan_adamw_step_groups"):      # (absent only in an older A/B library)
-                raise RuntimeError("this libvpdhip has no AdamW parameter groups (vpd_plan_adamw_step_groups)")
+            require(self.L, "vpd_plan_adamw_step_groups", "AdamW parameter groups")
             begin, group = groups["seg_begin"], groups["seg_group"]
             nseg = len(group)
             table = torch.zeros(max(int(self.L.vpd_adam_groups_bytes(nseg)) // 4, 1), dtype=torch.int32, device=self.device)
@@ -831,7 +933,7 @@ class StudentEngine:
         clip = self._clip          # enable_grad_clip(): the norm pass (instead of the search) + AdamW reading the clip block
         state = clip if clip is not None else st      # the device block AdamW and the EMA read (None: the host's step count)
         if state is None:
-            self.adam_step = self.adam_step + 1
+            self._steps.set(self._steps.get() + 1)      # (the host counts; behind a block the device does)
         # the train plan of the last backward: AdamW + refresh of its packed bf16 weights in one pass.  Not for an optimizer that
         # was NOT given the motion head, behind a plan that trains it: the fused pass would update the head's tensors too
         # (torch.optim.AdamW never touches tensors it was not given) -- plain flat update of the leading `numel` elements
@@ -869,33 +971,26 @@ class StudentEngine:
             self._ema_enqueue(state)
         if clip is not None and st is None:
             # no scaler's update() follows: the clip block counts its own steps (applied, or skipped on a non-finite norm)
-            self.check(self.L.vpd_scale_state_update(_ptr(clip), 1.0, 1.0, 2 ** 31 - 1, self._stream()), "vpd_scale_state_update")
+            self.scale_state_update(clip, 1.0, 1.0, 2 ** 31 - 1)
 
     def capture_eval_graph(self, x, out):
         """hipGraph of the eval forward for this batch size, bound to x / out (capture needs a
         non-default stream; the graph itself is launched on the current stream)."""
+        return self._capture_eval_graph(x, None, out)
+
+    def capture_eval_graph_staged(self, n, img_dim, out):
+        """hipGraph of the eval forward for n crops whose input is ALREADY in the plan's stem staging buffer (stage_crops /
+        CropAugmenter.stage_views): the graph starts at the stem convolution."""
+        return self._capture_eval_graph(None, (n, img_dim), out)
+
+    def _capture_eval_graph(self, x, staged, out):
         self._no_graph_under_ema()
-        self._check_input(x, self.c_in)
-        n, _, h, w = x.shape
+        n, h, w = self._batch_shape(x, staged)
         pl = self.plan(h, w, n, False, False)
         self._ensure_packed(pl)
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         self.check(self.L.vpd_graph_capture_eval(pl.handle, _ptr(self.params), _ptr(x), n, _ptr(out), _ptr(pl.workspace),
-                                           C.c_void_p(side.cuda_stream)), "vpd_graph_capture_eval")
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        pl.graph_sizes.add(n)
-        return pl
-
-    def capture_eval_graph_staged(self, n, img_dim, out):
-        """hipGraph of the eval forward for n crops whose input is ALREADY in the plan's stem staging buffer (stage_crops /
-        CropAugmenter.stage_views): the graph starts at the stem convolution."""
-        self._no_graph_under_ema()
-        pl = self.plan(img_dim, img_dim, n, False, False)
-        self._ensure_packed(pl)
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        self.check(self.L.vpd_graph_capture_eval(pl.handle, _ptr(self.params), None, n, _ptr(out), _ptr(pl.workspace),
                                            C.c_void_p(side.cuda_stream)), "vpd_graph_capture_eval")
         torch.cuda.current_stream(self.device).wait_stream(side)
         pl.graph_sizes.add(n)

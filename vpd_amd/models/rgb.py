@@ -57,7 +57,7 @@ class _StudentFunction(torch.autograd.Function):
     def forward(ctx, model, x, *params):
         eng = model.engine
         emb = eng.forward_train(x, None, motion=False)
-        ctx.model, ctx.ticket, ctx.nparams = model, eng._last_fwd, len(params)
+        ctx.model, ctx.ticket, ctx.nparams = model, eng.forward_ticket(), len(params)
         return emb
 
     @staticmethod
@@ -274,10 +274,10 @@ class RGBF_EmbeddingModel(nn.Module):
                                % (dropped[0], next(k for k in names if k not in dropped)))
         if not d_emb.is_contiguous() or d_emb.dtype != torch.float32:
             d_emb = d_emb.to(torch.float32).contiguous()
-        dx = eng.backward_ext(d_emb, want_dx, ticket, accumulate=bool(names) and not dropped and not eng._grads_cleared,
+        dx = eng.backward_ext(d_emb, want_dx, ticket, accumulate=bool(names) and not dropped and not eng.grads_cleared,
                               discard=not names)
         for k in dropped:
-            self.get_parameter(k).grad = eng.view(k, eng._grads)
+            self.get_parameter(k).grad = eng.view(k, eng.flat_grads)
         return dx
 
     def embed(self, x):

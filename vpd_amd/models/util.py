@@ -1,6 +1,7 @@
 """step(): same call sequence as reference models/util.py:50-58; LossScaler / DynamicLossScaler: the GradScaler of the fp16 build."""
-import ctypes as C
 import os
+
+from .. import state_words as W
 
 _LAZY = os.environ.get("VPD_LAZY_GRADS", "1") != "0"      # A/B switch: 0 = step() runs the plain loss.backward()
 
@@ -66,44 +67,35 @@ class DynamicLossScaler(LossScaler):
     Under data parallelism the search runs after the all-reduce (inf and NaN survive a sum), so every replica decides alike."""
 
     def __init__(self, engine, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
-        import torch
         super().__init__(engine, init_scale)
         if not float(growth_factor) >= 1.0 or not 0.0 < float(backoff_factor) <= 1.0 or int(growth_interval) < 1:
             raise ValueError("growth_factor >= 1, 0 < backoff_factor <= 1 and growth_interval >= 1 are required")
         self._growth, self._backoff, self._interval = float(growth_factor), float(backoff_factor), int(growth_interval)
-        # vpd_scale_state: {float scale; u32 found; i32 growth_tracker, applied_steps, skipped_steps, reserved[3]}
-        host = torch.zeros(8, dtype=torch.int32)
-        host.view(torch.float32)[0] = float(init_scale)
-        host[3] = int(engine.adam_step)
-        self._state = host.to(engine.device)
+        self._state = W.host_block(W.ScaleState, scale=float(init_scale), applied_steps=int(engine.adam_step)).to(engine.device)
         engine.attach_scale_state(self._state)
 
     @property
     def state(self):
-        """the device block (int32[8]; element 0 holds the scale's float bits)"""
+        """the device block (vpd_scale_state as int32[8]; element 0 holds the scale's float bits)"""
         return self._state
 
-    def _ptr(self):
-        return C.c_void_p(self._state.data_ptr())
-
     def _host(self):
-        return self._state.cpu()      # synchronises
+        return W.read(self._state, W.ScaleState)      # synchronises
 
     def get_scale(self):
-        import torch
-        return float(self._host().view(torch.float32)[0])
+        return self._host().scale
 
     @property
     def growth_tracker(self):
-        return int(self._host()[2])
+        return self._host().growth_tracker
 
     @property
     def applied_steps(self):
-        return int(self._host()[3])
+        return self._host().applied_steps
 
     @property
     def skipped_steps(self):
-        return int(self._host()[4])
+        return self._host().skipped_steps
 
     def scale(self, loss):
         if not hasattr(loss, "_t"):
@@ -112,7 +104,6 @@ class DynamicLossScaler(LossScaler):
         return loss
 
     def step(self, optimizer):
-        import torch
         eng = self._engine
         if eng.scale_state is not self._state:
             raise RuntimeError("DynamicLossScaler.step() without scale(loss).backward() before it")
@@ -121,16 +112,14 @@ class DynamicLossScaler(LossScaler):
                 optimizer.step()                   # (FusedAdamW -> engine.adamw_step: non-finite search + skipping AdamW, enqueued)
             else:
                 eng.check_grads_finite_(self._state)
-                eng._grads.mul_(1.0 / self._state[:1].view(torch.float32))      # device-side reciprocal: no sync
-                if int(self._state[1].item()) == 0:                            # the one host read of this path, as torch's
+                eng.unscale_grads_by_block_(self._state)                       # device-side reciprocal: no sync
+                if int(self._state[W.word(W.ScaleState, "found")].item()) == 0:      # the one host read of this path, as torch's
                     optimizer.step()
         finally:
             eng.scale_state = None
 
     def update(self):
-        eng = self._engine
-        eng.check(eng.L.vpd_scale_state_update(self._ptr(), self._growth, self._backoff, self._interval, eng._stream()),
-                  "vpd_scale_state_update")
+        self._engine.scale_state_update(self._state, self._growth, self._backoff, self._interval)
 
     def state_dict(self):
         """torch.amp.GradScaler.state_dict()'s keys (scale, growth_factor, backoff_factor, growth_interval, _growth_tracker) plus
@@ -143,14 +132,12 @@ class DynamicLossScaler(LossScaler):
         taken over.  A plain GradScaler dictionary loads (skipped_steps = 0).  The applied-step word is NOT written: it is the
         optimizer's `step`, which FusedAdamW.load_state_dict() puts there through engine.adam_step -- load the optimizer first or
         afterwards, the two do not touch each other's words."""
-        from ..checkpoint import scaler_words
-        words = scaler_words(state)
+        from ..checkpoint import scaler_fields
+        fields = scaler_fields(state)
         growth, backoff, interval = float(state["growth_factor"]), float(state["backoff_factor"]), int(state["growth_interval"])
         if not growth >= 1.0 or not 0.0 < backoff <= 1.0 or interval < 1:
             raise ValueError("growth_factor >= 1, 0 < backoff_factor <= 1 and growth_interval >= 1 are required")
-        words = words.to(self._state.device)
-        self._state[0:3] = words[0:3]
-        self._state[4:5] = words[4:5]
+        W.write(self._state, W.ScaleState, found=0, **fields)
         self._growth, self._backoff, self._interval = growth, backoff, interval
         self._scale = float(state["scale"])
 

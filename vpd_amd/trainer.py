@@ -84,11 +84,10 @@ class FusedAdamW(torch.optim.Optimizer):
         self._shared_hypers()
         # like torch.optim.AdamW, touch only the tensors that were passed in: without the motion head's parameters the
         # update stops where the encoder's tensors end in the flat buffers
+        self._name_at = None            # flat offset -> layout name (first use: the layout never changes)
         enc_end = engine.encoder_numel
-        ptr0 = engine.params.data_ptr()
-        has_dec = any((q.data_ptr() - ptr0) // 4 >= enc_end for g in self.param_groups for q in g["params"])
-        self._has_dec = has_dec
-        self._numel = engine.param_numel if has_dec else enc_end
+        self._has_dec = any(self._offset(q) >= enc_end for g in self.param_groups for q in g["params"])
+        self._numel = engine.param_numel if self._has_dec else enc_end
         if len(self.param_groups) > 1:
             self._groups()              # (a missing tensor or too many groups: refused here, not at the first step)
         if max_grad_norm is not None:
@@ -98,6 +97,17 @@ class FusedAdamW(torch.optim.Optimizer):
         """{'total_norm', 'norm_max', 'coef', 'clipped_steps', 'nonfinite_steps'} of the clip block; synchronises, as
         DynamicLossScaler.get_scale() does"""
         return self._engine.clip_stats(reset_max)
+
+    def _offset(self, q):
+        """where a parameter begins in the engine's flat buffers"""
+        return (q.data_ptr() - self._engine.params.data_ptr()) // 4
+
+    def _locate(self, q):
+        """(_offset, layout name -- None for a tensor that is not one of the engine's) of a parameter"""
+        if self._name_at is None:
+            self._name_at = {row[2]: name for name, row in self._engine.layout.items()}      # (row: kind, is_dec, offset, ...)
+        off = self._offset(q)
+        return off, self._name_at.get(off)
 
     def _shared_hypers(self):
         """(betas, eps) of every group: the kernels share them"""
@@ -118,16 +128,12 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("FusedAdamW: %d parameter groups, at most %d" % (len(pgs), MAX_PARAM_GROUPS))
         sig = tuple(tuple(id(q) for q in g["params"]) for g in pgs)
         if self._grouping is None or self._grouping[0] != sig:
-            eng = self._engine
-            ptr0 = eng.params.data_ptr()
-            group_of = {}
-            for gi, g in enumerate(pgs):
-                for q in g["params"]:
-                    group_of[(q.data_ptr() - ptr0) // 4] = gi
-            rows = [(name, row[2]) for name, row in eng.layout.items() if self._has_dec or not row[1]]      # (row: kind, is_dec, offset, ...)
-            known = {off for _, off in rows}
-            if any(off not in known for off in group_of):
+            where = [(gi,) + self._locate(q) for gi, g in enumerate(pgs) for q in g["params"]]
+            rows = [(name, row[2]) for name, row in self._engine.layout.items() if self._has_dec or not row[1]]
+            known = {name for name, _ in rows}
+            if any(name not in known for _, _, name in where):
                 raise ValueError("FusedAdamW: a parameter that is not one of the engine's tensors")
+            group_of = {off: gi for gi, off, _ in where}
             missing = [name for name, off in rows if off not in group_of]
             if missing:
                 raise ValueError("FusedAdamW: with parameter groups every tensor must be in exactly one group; missing: %s%s.  A tensor is "
@@ -153,16 +159,9 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _names(self):
         """the layout names of the parameters, in the optimizer's own order (the indices of state_dict())"""
-        eng = self._engine
-        ptr0 = eng.params.data_ptr()
-        by_off = {row[2]: name for name, row in eng.layout.items()}
-        names = []
-        for g in self.param_groups:
-            for q in g["params"]:
-                off = (q.data_ptr() - ptr0) // 4
-                if off not in by_off:
-                    raise ValueError("FusedAdamW: a parameter that is not one of the engine's tensors")
-                names.append(by_off[off])
+        names = [self._locate(q)[1] for g in self.param_groups for q in g["params"]]
+        if None in names:
+            raise ValueError("FusedAdamW: a parameter that is not one of the engine's tensors")
         return names
 
     def state_dict(self):
@@ -209,8 +208,8 @@ class FusedAdamW(torch.optim.Optimizer):
         # gradients live in the engine's flat buffer and are overwritten (not accumulated) by the next fused backward, which is
         # what zero_grad-after-every-step amounts to: no memory is touched.  The autograd path (RGBF_EmbeddingModel.forward)
         # accumulates as torch does: it is told here that the buffer counts as cleared
-        self._engine._grads_cleared = True
-        self._engine._accum_count = 0      # the accumulation window is over (after a step the fold emptied it already)
+        self._engine.mark_grads_cleared()
+        self._engine.drop_accumulated_grads()      # the accumulation window is over (after a step the fold emptied it already)
         return None
 
 
@@ -297,7 +296,7 @@ class ModelTrainer:
             lazy = lazy and os.environ.get("VPD_DDP_LAZY", "1") != "0"      # (one layout per window: the final backward's rule)
             eng.backward(lazy=lazy)
         elif self._reducer is not None:
-            nb = len(eng._last[0].buckets) if eng._last is not None else 0      # (backward() raises without a forward)
+            nb = eng.pending_forward_buckets()      # (0 without a forward: backward() raises)
             # lazy gradients stay on under data parallelism: a SUM all-reduce is layout-agnostic, so the reducer sums the
             # weight-gradient scratch ranges + the small tensors of the flat buffer (VPD_DDP_LAZY=0: flat buffer, eager unpack)
             lazy = lazy and os.environ.get("VPD_DDP_LAZY", "1") != "0"
@@ -333,7 +332,7 @@ class ModelTrainer:
         if optimizer is not None:
             # every train epoch ends with a step, so nothing is held here unless a window was abandoned (an exception in the
             # middle of an epoch, accumulate=True by hand without a final step): its sum must not leak into this epoch's first window
-            eng._accum_count = 0
+            eng.drop_accumulated_grads()
         epoch_emb_n = 0
         for batch, step_now in accumulation_schedule(data_loader, self.accum_steps if optimizer is not None else 1):
             if 'rgb_u8' in batch:
@@ -417,7 +416,7 @@ class ModelTrainer:
             scaler = LossScaler(eng, float(loss_scale))
         if param_groups is not None:
             params = list(param_groups)
-        eng._accum_count = 0      # a new optimizer begins a new accumulation window (an abandoned one is forgotten)
+        eng.drop_accumulated_grads()      # a new optimizer begins a new accumulation window (an abandoned one is forgotten)
         return FusedAdamW(params, eng, lr=learning_rate, max_grad_norm=max_grad_norm), scaler
 
     @contextlib.contextmanager
@@ -457,10 +456,10 @@ class ModelTrainer:
         eng = self.encoder.engine
         if not isinstance(optimizer, FusedAdamW) or optimizer._engine is not eng:
             raise TypeError("save_state() takes the FusedAdamW of this trainer's engine (get_optimizer), not %s" % type(optimizer).__name__)
-        if eng._accum_count != 0:
+        if eng.held_micro_batches != 0:
             raise RuntimeError("save_state() in the middle of an accumulation window (%d micro-batch(es) held): save at a window "
-                               "boundary, after the optimizer step" % eng._accum_count)
-        if eng._use_ema:
+                               "boundary, after the optimizer step" % eng.held_micro_batches)
+        if eng.ema_in_use:
             raise RuntimeError("save_state() inside ema_weights(): leave the context first")
         if scaler is not None and not isinstance(scaler, LossScaler):
             raise TypeError("save_state() takes scaler=None or a vpd_amd.models.util.LossScaler, not %s" % type(scaler).__name__)
@@ -499,14 +498,14 @@ class ModelTrainer:
         if (ema is not None) != eng.ema_enabled:
             raise ValueError("EMA: the file %s an average, this trainer %s (ModelTrainer(ema_decay=))"
                              % (("holds", "keeps none") if ema is not None else ("holds no", "keeps one")))
-        if ema is not None and (float(ema["decay"]), bool(ema["warmup"])) != eng._ema:
+        if ema is not None and (float(ema["decay"]), bool(ema["warmup"])) != eng.ema_config:
             raise ValueError("EMA: the file's average has decay=%r, warmup=%r, this trainer decay=%r, warmup=%r"
-                             % ((float(ema["decay"]), bool(ema["warmup"])) + eng._ema))
+                             % ((float(ema["decay"]), bool(ema["warmup"])) + eng.ema_config))
         if (clip is not None) != eng.grad_clip_enabled:
             raise ValueError("gradient clipping: %s in the file, %s in this optimizer (max_grad_norm=)"
                              % (("on", "off") if clip is not None else ("off", "on")))
-        if clip is not None and float(clip["max_norm"]) != eng._clip_max_norm:
-            raise ValueError("gradient clipping: max_norm %r in the file, %r in this optimizer" % (float(clip["max_norm"]), eng._clip_max_norm))
+        if clip is not None and float(clip["max_norm"]) != eng.clip_max_norm:
+            raise ValueError("gradient clipping: max_norm %r in the file, %r in this optimizer" % (float(clip["max_norm"]), eng.clip_max_norm))
         if state["scaler_kind"] != self._scaler_kind(scaler):
             raise ValueError("loss scaler: the file was written with %s, this run has %s" % (state["scaler_kind"], self._scaler_kind(scaler)))
         if len(state["optimizer"]["param_groups"]) != len(optimizer.param_groups):
@@ -526,7 +525,7 @@ class ModelTrainer:
         if clip is not None:
             eng.load_clip_state(clip)
         eng.freeze_bn(bool(state["bn_frozen"]))
-        eng._accum_count = 0
+        eng.drop_accumulated_grads()
         ckpt.restore_rng(rng)
         return state["extra"]
 
