@@ -1,6 +1,8 @@
 // Epilogue shared by the convolution kernels (bf16 NHWC store, eval scale/shift/residual/ReLU,
 // accumulate, per-channel statistics).
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 // Shared epilogue: acc[a][b][j] = out[channel n0 + wn*WTN + a*16 + 4*fq + j][pixel m0 + wm*WTM + b*16 + fr].
@@ -18,6 +20,21 @@ static __host__ __device__ __forceinline__ int conv_ep_mode(const ConvParams& p)
     if (p.bst_z) return p.accumulate ? (p.bst_z2 ? 8 : 7) : 6;
     return p.ep_scale ? 3 : (p.accumulate ? 2 : (p.stats ? 1 : 0));
 }
+// The epilogue modes a kernel family instantiates (host side).  visit(m, f) calls f(std::integral_constant<int, m>) and returns
+// true when the family has mode m; a launcher returns hipErrorInvalidValue otherwise -- no family stands in for another's mode.
+template <int... Ms>
+struct EpModes {
+    static constexpr bool has(int m) { return ((m == Ms) || ...); }
+    template <class F>
+    static bool visit(int m, F&& f) { return ((m == Ms ? (f(std::integral_constant<int, Ms>{}), true) : false) || ...); }
+};
+using Conv3x3WsModes = EpModes<0, 1, 2, 3, 6, 7, 8>;      // conv3x3_ws_kernel, conv3x3_pws_kernel with run-time geometry
+using Conv3x3GeoFwdModes = EpModes<1, 3>;                 // conv3x3_pws_kernel, compile-time geometry: forward taps ...
+using Conv3x3GeoFlipModes = EpModes<0, 2, 6, 7, 8>;       // ... and the data gradient's mirrored ones
+using ConvC64Modes = EpModes<0, 1, 2, 3, 6, 7>;           // conv3x3_c64_persistent_kernel (its two-group twin: mode 3 only)
+using Conv1x1WsModes = EpModes<0, 1, 2, 3, 6>;            // conv1x1_ws_kernel
+using ConvGatherModes = EpModes<0, 1, 2, 3, 6, 7>;        // conv_igemm_kernel
+using Conv1x1StreamModes = EpModes<0, 1, 2, 3>;           // conv1x1_stream_kernel (mode 4: the Bottleneck tail's own launcher)
 
 // a wave's accumulator tile := 0 (in front of a tile's K loop)
 template <int NI, int MI>

@@ -895,14 +895,9 @@ static hipError_t launch_c64(const ConvParams& p, const HaloGeom& g, hipStream_t
     ConvParams q = p;
     // (the accumulate modes fetch the old values of y by dense pixel index ahead of the MFMA loop: conv_acc_prefetch)
     if (q.accumulate && (q.ypad != 0 || q.osub != 1 || q.yC != q.Co)) return hipErrorInvalidValue;
-    switch (conv_ep_mode(q)) {
-        case 0: VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, 0>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per); break;
-        case 1: VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, 1>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per); break;
-        case 2: VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, 2>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per); break;
-        case 6: VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, 6>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per); break;
-        case 7: VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, 7>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per); break;
-        default: VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, 3>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per); break;
-    }
+    if (!ConvC64Modes::visit(conv_ep_mode(q), [&](auto m) {
+            VPD_LAUNCH((conv3x3_c64_persistent_kernel<HROWS, decltype(m)::value>), dim3(grid), dim3(512), lds, stream, q, g, ntiles, per);
+        })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -1186,17 +1181,21 @@ static hipError_t launch_stem(const ConvParams& p, int TR, hipStream_t stream) {
 // ---------------------------------------------------------------------------
 // conv3x3_pws_kernel (conv_pws.h): persistent blocks, one barrier per K-step.  VPD_PWS=0 restores conv3x3_ws_kernel.
 // ---------------------------------------------------------------------------
-// ring depths per tile class (NS = A + 2: two readable steps + A weight bundles in flight); -D overrides for same-box A/B builds
-// (ring depths PWS_NS_C*: conv_pws.h)
+// (tiles and ring depths per class, NS = A + 2: two readable steps + A weight bundles in flight: conv3x3_tile, conv_pws.h)
 int pws_cu_count() {
     // VPD_PWS_BLOCKS: pretend the device has this many CUs (tests: many tiles per block on small problems)
     const int forced = vpd_switches().pws_blocks;
     return forced > 0 ? forced : vpd_cu_budget();
 }
 static bool pws_enabled(const ConvParams& p) {
-    const int mode = conv_ep_mode(p);
     // (global output rows below 2^21: the kernel's float-reciprocal divisions, vpd_fdiv)
-    return vpd_switches().pws && mode != 4 && mode != 5 && (long)p.N * p.Hs < VPD_FDIV_MAX;
+    return vpd_switches().pws && (long)p.N * p.Hs < VPD_FDIV_MAX;
+}
+// Class 1 runs on conv3x3_pws_kernel only where a block gets more than one of its tiles: with ONE tile per block conv3x3_ws_kernel,
+// whose loaders run three bundles ahead instead of two, is 3 % faster (25.5 vs 26.3 us)
+static bool pws_c1_many_tiles(const ConvParams& p) {
+    constexpr Conv3x3Tile T = conv3x3_tile(1);
+    return (p.M + T.bm - 1) / T.bm > pws_cu_count() / (p.Co / T.bn);
 }
 static PwsGrid pws_grid(const ConvParams& p, int BM, int BN) {
     PwsGrid sg;
@@ -1211,8 +1210,12 @@ static PwsGrid pws_grid(const ConvParams& p, int BM, int BN) {
     sg.rNT = 1.0f / (float)sg.NT; sg.rlanes = 1.0f / (float)lanes;
     return sg;
 }
-template <int BM, int BN, int HROWS, int NS, int NMW, bool PIPE>
+template <int KC>
 static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
+    static_assert(conv3x3_tile_class(KC), "a 3x3 tile class");
+    constexpr Conv3x3Tile T = conv3x3_tile(KC);
+    constexpr int BM = T.bm, BN = T.bn, HROWS = T.hrows, NS = T.ns, NMW = T.nmw;
+    constexpr bool PIPE = T.pipe;
     constexpr int WN = BN / 64, WM = NMW / WN;
     constexpr size_t lds = (size_t)2 * HROWS * 128 + (size_t)NS * BN * 128 + 1024 + (size_t)3 * WM * BN * 4;
     static_assert(lds <= 160 * 1024, "LDS");
@@ -1255,26 +1258,23 @@ static hipError_t launch_pws(const ConvParams& p, const HaloGeom& g, hipStream_t
         fprintf(stderr, "%llu cycles\n", emax - lo);
     } };
 #endif
-    const bool geo_launched = vpd_switches().pws_geo && vpd_launch_pws_geo(BM, BN, HROWS, NS, NMW, q, g, sg, grid, block, lds, stream);
-    if (!geo_launched) switch (conv_ep_mode(q)) {
-        case 0: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 0, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        case 1: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 1, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        case 2: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 2, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        case 3: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 3, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        case 6: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 6, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        case 7: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 7, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        case 8: VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, 8, NMW, PIPE>), grid, block, lds, stream, q, g, sg); break;
-        default: return hipErrorInvalidValue;
-    }
+    const bool geo_launched = vpd_switches().pws_geo && vpd_launch_pws_geo(KC, q, g, sg, grid, block, lds, stream);
+    if (!geo_launched && !Conv3x3WsModes::visit(conv_ep_mode(q), [&](auto m) {
+            VPD_LAUNCH((conv3x3_pws_kernel<BM, BN, HROWS, NS, decltype(m)::value, NMW, PIPE>), grid, block, lds, stream, q, g, sg);
+        })) return hipErrorInvalidValue;
 #ifdef PWS_STAMPS
     if (++nlaunch == 30) { char tag[64]; snprintf(tag, sizeof tag, "<%d,%d> NS %d mode %d", BM, BN, NS, conv_ep_mode(q)); Dump::run((int)grid.x, tag); }
 #endif
     return hipGetLastError();
 }
 
-// NS: weight-ring depth (four stages: profiles/r02_ring_depth.txt)
-template <int BM, int BN, int HROWS, int HB, int WPS, int NS>
+// conv3x3_ws_kernel on the tile of class KC: two halo buffers, two waves per SIMD, and four ring stages (the loaders three weight
+// tiles ahead): same-box A/B against 3 / 5 stages in profiles/r02_ring_depth.txt (4 is +0.5 % on the step, 5 is slower than 3)
+template <int KC>
 static hipError_t launch_ws(const ConvParams& p, const HaloGeom& g, hipStream_t stream) {
+    static_assert(conv3x3_tile_class(KC), "a 3x3 tile class");
+    constexpr Conv3x3Tile T = conv3x3_tile(KC);
+    constexpr int BM = T.bm, BN = T.bn, HROWS = T.hrows, HB = 2, WPS = 2, NS = 4;
     dim3 grid((p.M + BM - 1) / BM, p.Co / BN);
     const size_t lds = ((size_t)HB * HROWS + NS * BN) * 64 * sizeof(bf16_t);
     static_assert(((size_t)HB * HROWS + NS * BN) * 64 * sizeof(bf16_t) <= 160 * 1024, "LDS");
@@ -1282,29 +1282,14 @@ static hipError_t launch_ws(const ConvParams& p, const HaloGeom& g, hipStream_t 
     // layer2's 256 x 128 tile with EIGHT MFMA waves (64 x 64 wave tiles, two waves per SIMD) + the four loader waves
     // (the 256 x 64 tile with eight MFMA waves -- 32 x 64 wave tiles, six fragment reads per eight MFMAs -- is LDS-read-bound:
     //  class 525 -> 590 us)
-    if constexpr (BM == 256 && BN == 128 && NS == 4) {
-        if (vpd_switches().ws_mw8) {
-            switch (conv_ep_mode(q)) {
-                case 0: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 0, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                case 1: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 1, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                case 2: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 2, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                case 3: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 3, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                case 6: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 6, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                case 7: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 7, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                case 8: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, 8, NS, 8>), grid, dim3(768), lds, stream, q, g); return hipGetLastError();
-                default: break;
-            }
-        }
-    }
-    switch (conv_ep_mode(q)) {
-        case 0: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 0, NS>), grid, dim3(512), lds, stream, q, g); break;
-        case 1: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 1, NS>), grid, dim3(512), lds, stream, q, g); break;
-        case 2: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 2, NS>), grid, dim3(512), lds, stream, q, g); break;
-        case 6: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 6, NS>), grid, dim3(512), lds, stream, q, g); break;
-        case 7: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 7, NS>), grid, dim3(512), lds, stream, q, g); break;
-        case 8: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 8, NS>), grid, dim3(512), lds, stream, q, g); break;
-        default: VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, 3, NS>), grid, dim3(512), lds, stream, q, g); break;
-    }
+    constexpr bool HAS_MW8 = T.nmw == 8;
+    const bool mw8 = HAS_MW8 && vpd_switches().ws_mw8;
+    if (!Conv3x3WsModes::visit(conv_ep_mode(q), [&](auto m) {
+            constexpr int EPM = decltype(m)::value;
+            if constexpr (HAS_MW8)
+                if (mw8) { VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, 3, EPM, NS, 8>), grid, dim3(768), lds, stream, q, g); return; }
+            VPD_LAUNCH((conv3x3_ws_kernel<BM, BN, HROWS, HB, WPS, EPM, NS>), grid, dim3(512), lds, stream, q, g);
+        })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -1481,14 +1466,9 @@ static hipError_t launch_1x1_ws(const ConvParams& p, hipStream_t stream) {
     static_assert((size_t)NS * (BM + BN) * 64 * sizeof(bf16_t) <= 160 * 1024, "LDS");
     ConvParams q = p;
     const dim3 grid = conv_class_grid(q, BM, BN);
-    switch (conv_ep_mode(q)) {
-        case 0: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 0>), grid, dim3(512), lds, stream, q); break;
-        case 1: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 1>), grid, dim3(512), lds, stream, q); break;
-        case 2: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 2>), grid, dim3(512), lds, stream, q); break;
-        case 3: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 3>), grid, dim3(512), lds, stream, q); break;
-        case 6: VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, 6>), grid, dim3(512), lds, stream, q); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (!Conv1x1WsModes::visit(conv_ep_mode(q), [&](auto m) {
+            VPD_LAUNCH((conv1x1_ws_kernel<BM, BN, NS, decltype(m)::value>), grid, dim3(512), lds, stream, q);
+        })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 // tile choice: the largest tile that still gives every CU a block
@@ -1536,6 +1516,15 @@ static bool halo_geom(const ConvParams& p, int BM, int hrows_max, HaloGeom* g) {
     return g->NHP <= hrows_max;
 }
 
+// ... for the tile of a 3x3 class (conv3x3_tile), and the tiles that class cuts `p` into
+static bool halo_geom_class(const ConvParams& p, int kclass, HaloGeom* g) {
+    return halo_geom(p, conv3x3_tile(kclass).bm, conv3x3_tile(kclass).hrows, g);
+}
+static long conv3x3_tiles(const ConvParams& p, int kclass) {
+    const Conv3x3Tile T = conv3x3_tile(kclass);
+    return (long)((p.M + T.bm - 1) / T.bm) * (p.Co / T.bn);
+}
+
 // 3x3, stride 1, border-1 input, dense sub-grid: eligible for the halo kernel
 static bool halo_eligible(const ConvParams& p) {
     return p.taps.nr == 3 && p.taps.nc == 3 && p.istr == 1 && p.osub == 1 && p.oph == 0 && p.opw == 0 &&
@@ -1549,14 +1538,9 @@ static hipError_t launch_cfg(const ConvParams& p, hipStream_t stream) {
     ConvParams q = p;
     const dim3 grid = conv_class_grid(q, BM, BN);
     const size_t lds = (size_t)2 * (BM + BN) * 64 * sizeof(bf16_t);
-    switch (conv_ep_mode(q)) {
-        case 0: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 0>), grid, dim3(256), lds, stream, q); break;
-        case 1: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 1>), grid, dim3(256), lds, stream, q); break;
-        case 2: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 2>), grid, dim3(256), lds, stream, q); break;
-        case 6: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 6>), grid, dim3(256), lds, stream, q); break;
-        case 7: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 7>), grid, dim3(256), lds, stream, q); break;
-        default: VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, 3>), grid, dim3(256), lds, stream, q); break;
-    }
+    if (!ConvGatherModes::visit(conv_ep_mode(q), [&](auto m) {
+            VPD_LAUNCH((conv_igemm_kernel<BM, BN, WM, WN, decltype(m)::value>), grid, dim3(256), lds, stream, q);
+        })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -1571,32 +1555,28 @@ extern "C" int vpd_conv_bm(int M, int Co) {
 }
 
 // Kernel selection = timing class of vpd_plan_read_timing (one class per kernel function):
-//   0 conv3x3_c64_persistent_kernel<224>   1 conv3x3_ws_kernel<256,128,352>   2 conv3x3_ws_kernel<128,128,288>
-//   3 conv3x3_ws_kernel<128,64,288>        4 conv_igemm_kernel (gather; also the legacy conv3x3_halo fallback, the ring GEMM and
-//   5 conv_stem_persistent_kernel<160>       the streaming 1x1 kernels: vpd_conv_dispatch tells them apart)
-//   6 conv3x3_ws_kernel<256,64,416>
+//   0 conv3x3_c64_persistent_kernel<224>   1, 2, 3, 6 conv3x3_ws_kernel on the tile conv3x3_tile (conv_pws.h) gives the class
+//   5 conv_stem_persistent_kernel<160>     4 conv_igemm_kernel (gather; also the legacy conv3x3_halo fallback, the ring GEMM and
+//                                            the streaming 1x1 kernels: vpd_conv_dispatch tells them apart)
 // (classes 1, 2, 3 and 6 run on conv3x3_pws_kernel of the same tile where vpd_conv_dispatch says pws)
 int vpd_conv_kernel_class(const ConvParams& p, HaloGeom* g) {
     const int no_ws = vpd_switches().no_ws;
-    int tr_stem;
     if (p.alt_w || p.x2) return 4;                             // two convolutions / two inputs in one launch: gather kernel only
-    if (!no_ws && stem_eligible(p, &tr_stem)) return 5;        // conv_stem_persistent_kernel
+    if (!no_ws && stem_eligible(p, &g->TR)) return 5;          // conv_stem_persistent_kernel (its rows per tile: to the launch)
     if (halo_eligible(p) && !no_ws) {
         if (p.Co % 128 == 0) {
-            const long t256 = (long)((p.M + 255) / 256) * (p.Co / 128);
-            const long t128 = (long)((p.M + 127) / 128) * (p.Co / 128);
+            const long t256 = conv3x3_tiles(p, 1), t128 = conv3x3_tiles(p, 2);
             // 256 x 64 tiles on the pipelined persistent kernel where 256 x 128 tiles would give every block exactly one tile: twice
             // the tiles, so a block overlaps one tile's epilogue with the next one's loads (layer2 at 256 crops: 23.2 vs 25.2 us;
             // with several 256 x 128 tiles per block the eight-wave kernel below is faster: 83.7 vs 90.6 us at 1000 crops)
-            if ((p.M + 255) / 256 <= pws_cu_count() / (p.Co / 128) && pws_enabled(p) && t256 >= 200 &&
-                halo_geom(p, 256, 416, g))
-                return 6;
-            if (t256 >= 200 && halo_geom(p, 256, 352, g)) return 1;
+            if (!pws_c1_many_tiles(p) && pws_enabled(p) && t256 >= 200 && halo_geom_class(p, 6, g)) return 6;
+            if (t256 >= 200 && halo_geom_class(p, 1, g)) return 1;
             // 256 pixels x 64 channels: the FLOPs of a 128 x 128 tile for 30 % fewer staged bytes per K-step (8 KB of weights +
             // 1/9 of a 52 KB halo instead of 16 KB + 1/9 of 36 KB) where 256-pixel tiles alone would leave half the chip idle
             // (layer3 at 256 crops: 64 pixel tiles x 4 channel tiles)
-            if (vpd_switches().ws_256x64 && t128 >= 200 && (long)((p.M + 255) / 256) * (p.Co / 64) >= 200 && halo_geom(p, 256, 416, g)) return 6;
-            if (halo_geom(p, 128, 288, g)) return t128 >= 200 ? 2 : 3;    // few pixel tiles: 64-channel tiles fill the chip
+            if (vpd_switches().ws_256x64 && t128 >= 200 && conv3x3_tiles(p, 6) >= 200 && halo_geom_class(p, 6, g)) return 6;
+            const int kc128 = t128 >= 200 ? 2 : 3;                        // few pixel tiles: 64-channel tiles fill the chip
+            if (halo_geom_class(p, kc128, g)) return kc128;
         } else if (p.Kc == 64 && p.Co == 64) {
             // 64 -> 64 channels (layer1): persistent blocks with resident weights
             if (halo_geom(p, 128, 224, g)) return 0;
@@ -1608,47 +1588,34 @@ int vpd_conv_kernel_class(const ConvParams& p) { HaloGeom g; return vpd_conv_ker
 
 // Pixels per tile when `p` runs on conv3x3_pws_kernel with its XCD-affine tile order (launch_pws: lanes a multiple of 8, so that
 // pixel tile t -- and every later tile of its block -- sits on XCD t % 8), else 0.  The fused BatchNorm launches on either side of
-// such a convolution order their blocks to match (bn.hip, vpd_bn_virtual_block).
+// such a convolution order their blocks to match (bn.hip, vpd_bn_virtual_block).  Not an accessor: every call runs the whole
+// vpd_conv_dispatch.
 int vpd_conv_xcd_tile_px(const ConvParams& p) {
-    HaloGeom g;
-    if (!pws_enabled(p)) return 0;
-    int bm = 0, bn = 0;
-    switch (vpd_conv_kernel_class(p, &g)) {
-        case 1: if ((p.M + 255) / 256 > pws_cu_count() / (p.Co / 128)) { bm = 256; bn = 128; } break;
-        case 2: bm = 128; bn = 128; break;
-        case 3: bm = 128; bn = 64; break;
-        case 6: bm = 256; bn = 64; break;
-        default: break;
-    }
-    if (!bm) return 0;
-    const int MT = (p.M + bm - 1) / bm, NT = p.Co / bn;
-    int lanes = pws_cu_count() / NT;
-    if (lanes > MT) lanes = MT;
-    return lanes >= 8 ? bm : 0;
+    const ConvDispatch d = vpd_conv_dispatch(p);
+    return d.pws && pws_grid(p, d.bm, d.bn).xcd ? d.bm : 0;
 }
 
 // true when this launch's kernel can take the sums of the consuming BatchNorm's backward in its epilogue (bst_z / bst_mask)
 bool vpd_conv_takes_bn_sums(const ConvParams& p) {
     if (p.ep_scale || p.alt_w || p.yC != p.Co || p.ypad != 0) return false;
-    HaloGeom g;
-    const int kc = vpd_conv_kernel_class(p, &g);
-    if (kc == 4) {      // gather kernel: the merged parity classes of a stride-2 data gradient (plain store only)
-        if (p.bst_z2) return false;
+    // p carries bst_z (and bst_z2) as the launch will, so d.mode is 6, 7 or 8: the question is whether the family d names has it
+    // (conv1x1_stream_kernel is never that family: it is not eligible with bst_z)
+    if (!p.bst_z) return false;
+    const ConvDispatch d = vpd_conv_dispatch(p);
+    if (p.bst_z2 && !(d.mode == 8 && p.stats2)) return false;      // a second BatchNorm: the accumulating mode 8 alone, with its rows
+    if (d.kclass == 4) {      // gather kernel: the merged parity classes of a stride-2 data gradient (plain store only)
         // (the legacy conv3x3_halo_kernel -- VPD_NO_WS=1, or a 3x3 whose channel counts fit no other class -- decides its epilogue at
         //  run time and has no sums branch: with rows given it would add sum / sum of squares of d to them instead)
-        if (vpd_conv_dispatch(p).halo) return false;
+        if (d.halo || !(d.ws1x1 ? Conv1x1WsModes::has(d.mode) : ConvGatherModes::has(d.mode))) return false;
         // ... or a dense stride-1 launch of it (the Bottleneck students' 1x1 convs), plain or accumulating
         if (p.osub == 1 && p.ncls <= 1 && !p.x2) return vpd_switches().dgrad_sums_1x1 != 0;
         return vpd_switches().dgrad_sums_s2 && !p.accumulate && p.osub == 2;
     }
     if (p.x2 || p.osub != 1) return false;
     if (p.yWp != p.Ws || p.yHp != p.Hs) return false;      // (the 3x3 kernels index z / the bit map by dense pixel number)
-    if (p.bst_z2) return p.accumulate && p.stats2 && (kc == 1 || kc == 2 || kc == 3 || kc == 6);      // mode 8: conv3x3_ws_kernel only
-    if (kc == 0) {      // layer1's persistent kernel (not its two-group variant)
-        HaloGeom g2;
-        return vpd_switches().dgrad_sums_l1 && !c64x2_geom(p, &g2);
-    }
-    return kc == 1 || kc == 2 || kc == 3 || kc == 6;
+    // layer1's persistent kernel (not its two-group variant)
+    if (d.kclass == 0) return vpd_switches().dgrad_sums_l1 && !d.c64x2 && ConvC64Modes::has(d.mode);
+    return conv3x3_tile_class(d.kclass) && Conv3x3WsModes::has(d.mode);
 }
 
 // Every decision of vpd_launch_conv that depends on the problem, the device and the switches, in one place: the launcher
@@ -1658,20 +1625,22 @@ ConvDispatch vpd_conv_dispatch(const ConvParams& p, HaloGeom* g) {
     d.mode = conv_ep_mode(p);
     d.kclass = vpd_conv_kernel_class(p, g);
     d.tiles_per_block = 1;
-    const auto pws_form = [&](int bm, int bn, int hrows, int ns, int nmw, bool on) {
-        d.bm = bm; d.bn = bn;
-        d.pws = on && pws_enabled(p);
-        if (!d.pws) return;
-        const PwsGrid sg = pws_grid(p, bm, bn);
+    if (conv3x3_tile_class(d.kclass)) {
+        const Conv3x3Tile T = conv3x3_tile(d.kclass);
+        d.bm = T.bm; d.bn = T.bn;
+        d.pws = pws_enabled(p) && (d.kclass != 1 || pws_c1_many_tiles(p));
+        if (!d.pws) return d;
+        const PwsGrid sg = pws_grid(p, T.bm, T.bn);
         d.tiles_per_block = (sg.MT + sg.lanes - 1) / sg.lanes;
         bool flip;
-        d.geo = vpd_switches().pws_geo ? vpd_pws_geo_width(bm, bn, hrows, ns, nmw, p, *g, &flip) : 0;
+        d.geo = vpd_switches().pws_geo ? vpd_pws_geo_width(d.kclass, p, *g, &flip) : 0;
         // interior loaders (conv_pws.h): the compile-time-geometry kernels on tiles of whole images -- a border pixel then has the
         // same halo slot in every tile.  W = 4: three instructions per 6 x 6 padded image, H = 4 only.  Everything else (tiles that
         // cut images, the generic loop, the eight-wave tiles, conv3x3_ws_kernel) keeps the border-reading loader.
-        g->interior = vpd_switches().pws_interior && d.geo && (bm / p.Ws) % p.Hs == 0 && (p.Ws != 4 || p.Hs == 4);
+        g->interior = vpd_switches().pws_interior && d.geo && (T.bm / p.Ws) % p.Hs == 0 && (p.Ws != 4 || p.Hs == 4);
         d.interior = g->interior;
-    };
+        return d;
+    }
     switch (d.kclass) {
         case 0: {
             HaloGeom g2;
@@ -1684,12 +1653,6 @@ ConvDispatch vpd_conv_dispatch(const ConvParams& p, HaloGeom* g) {
             d.tiles_per_block = (ntiles + grid - 1) / grid;
             return d;
         }
-        // (eight MFMA waves, no fragment pipeline: two waves per SIMD cover each other's LDS round trips.  With ONE tile per
-        //  block conv3x3_ws_kernel, whose loaders run three bundles ahead instead of two, is 3 % faster: 25.5 vs 26.3 us)
-        case 1: pws_form(256, 128, 352, PWS_NS_C1, 8, (p.M + 255) / 256 > pws_cu_count() / (p.Co / 128)); return d;
-        case 2: pws_form(128, 128, 288, PWS_NS_C2, 4, true); return d;
-        case 3: pws_form(128, 64, 288, PWS_NS_C3, 4, true); return d;
-        case 6: pws_form(256, 64, 416, PWS_NS_C6, 4, true); return d;
         case 5: {
             d.bm = 128; d.bn = 64;
             const int grid = stem_grid(p);
@@ -1738,20 +1701,11 @@ hipError_t vpd_launch_conv(const ConvParams& p0, hipStream_t stream) {
     const ConvDispatch d = vpd_conv_dispatch(p, &g);
     switch (d.kclass) {
         case 0: return d.c64x2 ? launch_c64x2(p, g, stream) : launch_c64<224>(p, g, stream);
-        case 1: return d.pws ? launch_pws<256, 128, 352, PWS_NS_C1, 8, false>(p, g, stream)
-                             : launch_ws<256, 128, 352, 2, 2, 4>(p, g, stream);      // 88 + 64 KiB
-        // four ring stages (the loaders three weight tiles ahead): same-box A/B against 3 / 5 stages in
-        // profiles/r02_ring_depth.txt (4 is +0.5 % on the step, 5 is slower than 3)
-        case 2: return d.pws ? launch_pws<128, 128, 288, PWS_NS_C2, 4, true>(p, g, stream)
-                             : launch_ws<128, 128, 288, 2, 2, 4>(p, g, stream);      // 72 + 64 KiB
-        case 3: return d.pws ? launch_pws<128, 64, 288, PWS_NS_C3, 4, true>(p, g, stream)
-                             : launch_ws<128, 64, 288, 2, 2, 4>(p, g, stream);       // 72 + 32 KiB
-        // (round 4: layer2's 18 x 18 halo needs 328 rows, not 416, and the 22 KB that frees were given to a deeper weight ring,
-        //  NS 7 and 9 -- same-box 72.02 / 72.02 / 71.86 k crops/s for NS 7 / 9 / 5, profiles/r04_ab_layer2_ring_depth.txt: the K
-        //  loop is not bound by the loaders' bytes in flight; instantiations removed)
-        case 6: return d.pws ? launch_pws<256, 64, 416, PWS_NS_C6, 4, true>(p, g, stream)
-                             : launch_ws<256, 64, 416, 2, 2, 4>(p, g, stream);       // 104 + 32 KiB
-        case 5: { int tr; stem_eligible(p, &tr); return launch_stem(p, tr, stream); }
+        case 1: return d.pws ? launch_pws<1>(p, g, stream) : launch_ws<1>(p, g, stream);
+        case 2: return d.pws ? launch_pws<2>(p, g, stream) : launch_ws<2>(p, g, stream);
+        case 3: return d.pws ? launch_pws<3>(p, g, stream) : launch_ws<3>(p, g, stream);
+        case 6: return d.pws ? launch_pws<6>(p, g, stream) : launch_ws<6>(p, g, stream);
+        case 5: return launch_stem(p, g.TR, stream);
         default: break;
     }
     if (d.stream1x1) return vpd_launch_conv1x1_stream(p, stream);

@@ -36,7 +36,7 @@
 #include "conv_epilogue.h"
 
 struct HaloGeom {
-    int TR;        // output rows per tile (BM / W)
+    int TR;        // output rows per tile (BM / W); class 5: the stem kernel's rows per tile, from stem_eligible to launch_stem
     int multi;     // tile spans TR/H whole images (TR > H)
     int HR;        // padded rows in the halo
     int NHP;       // halo pixels = HR * (W + 2)
@@ -76,6 +76,30 @@ int pws_cu_count();                                            // conv_igemm.hip
 #ifndef PWS_NS_C6
 #define PWS_NS_C6 5
 #endif
+// The tile of a 3x3 timing class (1, 2, 3, 6 of vpd_conv_kernel_class), stated once: class selection, vpd_conv_dispatch and the
+// launchers of conv3x3_ws_kernel / conv3x3_pws_kernel (conv_igemm.hip, conv_pws_geo.hip) all read it here
+struct Conv3x3Tile {
+    int bm, bn;      // pixels x channels
+    int hrows;       // halo pixels (128-byte LDS rows) of a tile at most
+    int ns;          // conv3x3_pws_kernel: ring depth, ...
+    int nmw;         // ... MFMA waves (beside the four loader waves) ...
+    bool pipe;       // ... and fragment pipeline
+};
+constexpr bool conv3x3_tile_class(int kclass) { return kclass == 1 || kclass == 2 || kclass == 3 || kclass == 6; }
+constexpr Conv3x3Tile conv3x3_tile(int kclass) {
+    switch (kclass) {
+        // eight MFMA waves, no fragment pipeline: two waves per SIMD cover each other's LDS round trips (halo + conv3x3_ws_kernel's
+        // four-stage ring: 88 + 64 KiB)
+        case 1: return {256, 128, 352, PWS_NS_C1, 8, false};
+        case 2: return {128, 128, 288, PWS_NS_C2, 4, true};       // 72 + 64 KiB
+        case 3: return {128, 64, 288, PWS_NS_C3, 4, true};        // 72 + 32 KiB
+        // (round 4: layer2's 18 x 18 halo needs 328 rows, not 416, and the 22 KB that frees were given to a deeper weight ring,
+        //  NS 7 and 9 -- same-box 72.02 / 72.02 / 71.86 k crops/s for NS 7 / 9 / 5, profiles/r04_ab_layer2_ring_depth.txt: the K
+        //  loop is not bound by the loaders' bytes in flight; instantiations removed)
+        case 6: return {256, 64, 416, PWS_NS_C6, 4, true};        // 104 + 32 KiB
+        default: return {};      // not a 3x3 tile class: no tile (the launchers assert conv3x3_tile_class at compile time)
+    }
+}
 
 int vpd_conv_kernel_class(const ConvParams& p, HaloGeom* g);   // conv_igemm.hip
 
@@ -864,9 +888,9 @@ __global__ __launch_bounds__((NMW + 4) * 64, (NMW + 4) / 4) void conv3x3_pws_ker
 }
 
 // conv_pws_geo.hip: the compile-time-geometry instantiations (W = 16 / 8 on 256 x 64 tiles, W = 4 on 128 x 64 tiles; forward taps or
-// the data gradient's mirrored ones).  Returns false when (tile, W, taps, epilogue mode) has no such instantiation: the caller
+// the data gradient's mirrored ones).  Returns false when (class, W, taps, epilogue mode) has no such instantiation: the caller
 // launches the generic kernel.
-bool vpd_launch_pws_geo(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid,
-                        dim3 block, size_t lds, hipStream_t stream);
+bool vpd_launch_pws_geo(int kclass, const ConvParams& q, const HaloGeom& g, const PwsGrid& sg, dim3 grid, dim3 block, size_t lds,
+                        hipStream_t stream);
 // ... and its decision alone: the image width of the instantiation that takes the launch, or 0
-int vpd_pws_geo_width(int bm, int bn, int hrows, int ns, int nmw, const ConvParams& q, const HaloGeom& g, bool* flip_out);
+int vpd_pws_geo_width(int kclass, const ConvParams& q, const HaloGeom& g, bool* flip_out);

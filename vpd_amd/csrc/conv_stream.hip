@@ -667,13 +667,9 @@ hipError_t launch_stream(const ConvParams& p, hipStream_t stream) {
     const int NT = p.Co / BN;
     const dim3 grid(stream_lanes(sg.mtiles, NT), NT);
     constexpr size_t lds = stream_lds_bytes(KC, BM, BN, NSA);
-    switch (conv_ep_mode(p)) {
-        case 0: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 0>), grid, dim3(512), lds, stream, p, sg); break;
-        case 1: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 1>), grid, dim3(512), lds, stream, p, sg); break;
-        case 2: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 2>), grid, dim3(512), lds, stream, p, sg); break;
-        case 3: VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, 3>), grid, dim3(512), lds, stream, p, sg); break;
-        default: return hipErrorInvalidValue;
-    }
+    if (!Conv1x1StreamModes::visit(conv_ep_mode(p), [&](auto m) {
+            VPD_LAUNCH((conv1x1_stream_kernel<KC, BM, BN, NSA, decltype(m)::value>), grid, dim3(512), lds, stream, p, sg);
+        })) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

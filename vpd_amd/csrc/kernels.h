@@ -106,8 +106,8 @@ hipError_t vpd_launch_scale(float* x, long n, float s, hipStream_t stream);     
 bool vpd_conv1x1_stream_eligible(const ConvParams& p);
 hipError_t vpd_launch_conv1x1_stream(const ConvParams& p, hipStream_t stream);
 void vpd_conv1x1_stream_grid(const ConvParams& p, int* bm, int* bn, int* lanes);      // (reporting: its tile and pixel lanes)
-int vpd_conv_kernel_class(const ConvParams& p);      // 0..4, see conv_igemm.hip
-bool vpd_conv_takes_bn_sums(const ConvParams& p);
+int vpd_conv_kernel_class(const ConvParams& p);      // 0..6, see conv_igemm.hip
+bool vpd_conv_takes_bn_sums(const ConvParams& p);      // epilogue can take the consuming BatchNorm's backward sums (bst_z)
 // What vpd_launch_conv does with `p` on the current device; the launcher branches on this very struct (conv_igemm.hip)
 struct ConvDispatch {
     int kclass;             // vpd_conv_kernel_class
@@ -123,7 +123,7 @@ struct ConvDispatch {
 };
 ConvDispatch vpd_conv_dispatch(const ConvParams& p);
 // pixels per tile when `p` runs on conv3x3_pws_kernel with its XCD-affine tile order (pixel tile t on XCD t % 8), else 0
-int vpd_conv_xcd_tile_px(const ConvParams& p);         // epilogue can take the consuming BatchNorm's backward sums (bst_z)
+int vpd_conv_xcd_tile_px(const ConvParams& p);
 hipError_t vpd_launch_wgrad_reduce(const WgradParams& p, hipStream_t stream);   // slab sum of a deferred halo wgrad
 extern "C" int vpd_conv_bm(int M, int Co);
 hipError_t vpd_launch_wgrad(const WgradParams& p, hipStream_t stream);
