@@ -477,17 +477,14 @@ int vpd_bn_bwd_blocks(int M, int C, int* ppb_out) {
 }
 
 hipError_t vpd_launch_bn_bwd(const BnBwdParams& p0, float count, const float* gamma, float* dgamma, float* dbeta,
-                             hipStream_t s, bool reduce_done, bool frozen) {
+                             hipStream_t s, bool frozen) {
     BnBwdParams p = p0;
     if (p.C % 8 || p.C > 2048 || 256 % (p.C / 8)) return hipErrorInvalidValue;
     const int T = vpd_bn_bwd_blocks(p.M, p.C, &p.ppb);
-    // reduce_done: the producing data-gradient kernel already masked dy and accumulated (sum g, sum g*xhat)
     const int mask = p.act ? 1 : (p.mscale ? 2 : 0);
-    if (!reduce_done) {
-        if (mask == 1) hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(T), dim3(256), 0, s, p);
-        else if (mask == 2) hipLaunchKernelGGL(bn_bwd_reduce_kernel<2>, dim3(T), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(bn_bwd_reduce_kernel<0>, dim3(T), dim3(256), 0, s, p);
-    }
+    if (mask == 1) hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(T), dim3(256), 0, s, p);
+    else if (mask == 2) hipLaunchKernelGGL(bn_bwd_reduce_kernel<2>, dim3(T), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(bn_bwd_reduce_kernel<0>, dim3(T), dim3(256), 0, s, p);
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((p.C + 63) / 64), dim3(64), 0, s, p.partials,
                        VPD_STAT_ROWS, p.C, count,
                        gamma, p.rstd, dgamma, dbeta, p.coef, frozen ? 1 : 0);

@@ -399,7 +399,7 @@ extern "C" int vpd_op_bn_backward(void* dy, const void* z, const void* act_padde
     if (!fused) {
         if (mask_bits || dy_pooled) return fail("the three-launch path takes neither a ReLU bit map nor a pooled gradient");
         if (!coef) return fail("the three-launch path needs coef");
-        LCHECK(vpd_launch_bn_bwd(b, (float)b.M, gamma, dgamma, dbeta, (hipStream_t)stream, false, g_op_bn_frozen != 0));
+        LCHECK(vpd_launch_bn_bwd(b, (float)b.M, gamma, dgamma, dbeta, (hipStream_t)stream, g_op_bn_frozen != 0));
         return 0;
     }
     if (!sync || !err) return fail("the fused launch needs sync and err");
